@@ -18,8 +18,12 @@ step, all-gathers the state of its boundary bodies over RCCL (behind the C ABI: 
 GPU): the neighbours' boundary bodies take part in the rank's broad phase, narrow phase and solver as kinematic ghosts. Started without a
 launcher (no WORLD_SIZE in the environment) this script starts the N ranks itself, BEFORE anything touches the GPU.
 
-Prints ONE JSON line (rank 0). `roofline` describes the dominant kernel of the timed window, timed live with HIP
-events on the library's own stream (phys_profile_*) over the SAME window on one more fresh world. `traffic` and
+Prints ONE JSON line (rank 0), short enough for a driver that keeps only the tail of the output: the sub-records of
+the other workloads appear there with their headline figures only, and the prose notes are left out. `--record FILE`
+writes the whole record, every sub-record in full, to FILE as one JSON line (the input of tools/results_table.py).
+`--dump-outputs DIR` writes what the last timed step computed as .npy files, for comparing two builds output for output.
+`roofline` describes the dominant kernel of the timed window, timed live with HIP events on the library's own stream
+(phys_profile_*) over the SAME window on one more fresh world. `traffic` and
 `avg_kernel_us_rocprofv3` come from the committed rocprofv3 passes of `bench.py --profile-window` and are emitted
 only when that pass covered the same window at the same scene state (profiles/r2_<workload>_window.json says which),
 otherwise null. `cpu_baseline` is the CPU oracle (a scalar C++ restatement; the Rust reference cannot be built here)
@@ -32,6 +36,8 @@ import statistics
 import subprocess
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -149,9 +155,15 @@ def committed_profile_fields(workload_key, kernel, window, st):
     return short, r.get("avg_us"), r.get("traffic_bytes"), f"profiles/{PROFILE_ROUND}_{workload_key}_window.json (same window, same scene state)"
 
 
+STAT_FIELDS = ("n_bodies", "n_pairs", "n_manifolds", "n_contacts", "n_colors", "color_rounds", "n_ground_manifolds",
+               "cg_iterations")
+# --dump-outputs: at most this many bytes in all; larger outputs keep a sample of the bodies drawn with this seed
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240607
+
+
 def stats_dict(s):
-    return {f: int(getattr(s, f)) for f in ("n_bodies", "n_pairs", "n_manifolds", "n_contacts", "n_colors",
-                                            "color_rounds", "n_ground_manifolds", "cg_iterations")}
+    return {f: int(getattr(s, f)) for f in STAT_FIELDS}
 
 
 class Rig:
@@ -221,9 +233,10 @@ class Rig:
         return float(t.item())
 
 
-def timed_repetition(rig, preroll, warmup, steps, want_state=False):
+def timed_repetition(rig, preroll, warmup, steps, want_state=False, want_outputs=False):
     """One fresh world: preroll + warm-up (untimed), then EXACTLY `steps` timed steps. Returns (seconds = max over
-    ranks, stats after the window, state at the START of the window if asked for)."""
+    ranks, stats after the window, state at the START of the window if asked for, what the last timed step left in
+    the world if asked for: read back after the clock has stopped)."""
     import torch
     w = rig.make_world()
     rig.advance(w, preroll)
@@ -243,8 +256,40 @@ def timed_repetition(rig, preroll, warmup, steps, want_state=False):
     elapsed = rig.max_over_ranks(time.perf_counter() - t0)
     st = stats_dict(w.get_stats())
     cross = int(w.get_stats().n_cross_pairs) if rig.halo is not None else 0
+    outputs = world_outputs(w, st) if want_outputs else None
     w.close()
-    return elapsed, st, cross, state
+    return elapsed, st, cross, state, outputs
+
+
+def world_outputs(w, st):
+    """What a caller of the update receives after it: the body state (PhysicsState's transforms and velocities), the
+    constraint multipliers where the scene has constraints, and the step's counters."""
+    pos, rot = w.get_transforms()
+    lin, ang = w.get_velocities()
+    out = {"pos": pos, "rot_ijkw": rot, "lin_vel": lin, "ang_vel": ang}
+    lam = w.get_lambda()
+    if lam.size:
+        out["lambda"] = lam
+    out["scene_stats"] = np.array([st[k] for k in STAT_FIELDS], np.float64)
+    return out
+
+
+def dump_outputs(outputs, out_dir, prefix=""):
+    """Write `outputs` as <out_dir>/<prefix><name>.npy (float32 / float64). Beyond DUMP_LIMIT_BYTES in all, the per-body
+    arrays keep a fixed, seeded sample of the bodies (sample_index.npy says which, in ascending order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_body = [k for k in ("pos", "rot_ijkw", "lin_vel", "ang_vel") if k in outputs]
+    n = len(outputs["pos"])
+    total = sum(v.nbytes for v in outputs.values())
+    if total > DUMP_LIMIT_BYTES:
+        body_bytes = sum(outputs[k].nbytes for k in per_body) // max(n, 1)
+        budget = DUMP_LIMIT_BYTES - 4096 * (len(outputs) + 1)  # np.save headers
+        keep = (budget - (total - body_bytes * n)) // (body_bytes + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=max(int(keep), 1), replace=False))
+        outputs = dict(outputs, **{k: outputs[k][idx] for k in per_body}, sample_index=idx.astype(np.float64))
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), np.ascontiguousarray(a))
 
 
 def timed_period(rig, preroll, warmup):
@@ -421,14 +466,18 @@ def cpu_baseline(scene, state, window_start, sample_steps, budget_s=14.0):
                                "reference itself is single-threaded"}}
 
 
-def measure_workload(rig, args, preroll, reps, with_cpu):
-    """Timed repetitions + profile window + (optionally) CPU sample of one workload on this rank's rig."""
-    times, st, cross, state = [], None, 0, None
+def measure_workload(rig, args, preroll, reps, with_cpu, want_outputs=False):
+    """Timed repetitions + profile window + (optionally) CPU sample of one workload on this rank's rig. With
+    `want_outputs`, rec["outputs"] holds what the last timed step of the last repetition computed."""
+    times, st, cross, state, outputs = [], None, 0, None, None
     for r in range(reps):
-        e, st, cross, s = timed_repetition(rig, preroll, args.warmup, args.steps, want_state=(with_cpu and r == 0))
+        e, st, cross, s, o = timed_repetition(rig, preroll, args.warmup, args.steps, want_state=(with_cpu and r == 0),
+                                              want_outputs=(want_outputs and r == reps - 1))
         times.append(e)
         if s is not None:
             state = s
+        if o is not None:
+            outputs = o
     med = statistics.median(times)
     n_total = int(round(rig.sum_over_ranks(float(rig.scene.n))))  # strong scaling: the slabs differ by a body or two
     pairs_total = rig.sum_over_ranks(float(st["n_pairs"] + cross))
@@ -445,6 +494,8 @@ def measure_workload(rig, args, preroll, reps, with_cpu):
         "pairs_per_sec": round(pairs_total * args.steps / med, 1),
         "scene_stats": st, "n_bodies": n_total, "preroll": preroll, "cross_pairs_rank": cross,
     }
+    if outputs is not None:
+        rec["outputs"] = outputs
     if (rig.scene.flags & 1) and not (rig.scene.flags & 8) and st["n_manifolds"] > 0:  # FLAG_COLLISIONS, not broad-phase-only
         sps, slowest, med, hitch, first, last = timed_period(rig, preroll, args.warmup)
         rec["full_period"] = {"steps": 64, "steps_per_sec": round(sps, 2), "slowest_step_ms": round(slowest, 3),
@@ -465,6 +516,25 @@ def measure_workload(rig, args, preroll, reps, with_cpu):
         if with_cpu and state is not None:
             rec["cpu_baseline"] = cpu_baseline(rig.scene, state, preroll + args.warmup, args.cpu_steps)
     return rec
+
+
+# what the printed line keeps of each sub-record of "other_workloads", and the prose it leaves out (--record keeps all)
+SUMMARY_FIELDS = ("workload", "n_bodies", "value", "steps_per_sec", "ms_per_step")
+PROSE_FIELDS = ("note", "flags_note", "sample", "every_repetition")
+
+
+def _without_prose(x):
+    if not isinstance(x, dict):
+        return x
+    return {k: _without_prose(v) for k, v in x.items() if k not in PROSE_FIELDS}
+
+
+def result_line(out):
+    """The record as printed: the flagship workload's figures, the other workloads by their headline figures."""
+    line = _without_prose(out)
+    if "other_workloads" in out:
+        line["other_workloads"] = {wl: {k: rr[k] for k in SUMMARY_FIELDS if k in rr} for wl, rr in out["other_workloads"].items()}
+    return line
 
 
 def spawn_ranks(n, argv):
@@ -493,7 +563,15 @@ def main():
     ap.add_argument("--profile-window", action="store_true",
                     help="ONE world, preroll + warm-up + K steps and nothing else: the command the committed rocprofv3 "
                          "kernel-trace / PMC passes run (tools/profile_window.py cuts the last K steps out of the trace)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (body poses and velocities, "
+                         "constraint multipliers, step counters) as DIR/<name>.npy, float32 / float64, at most 64 MB in all "
+                         "(a seeded sample of the bodies beyond that); with several ranks each rank writes rank<r>_<name>.npy")
+    ap.add_argument("--record", metavar="FILE", default=None,
+                    help="also write the whole record (every sub-record in full) to FILE as one JSON line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     env_ws = os.environ.get("WORLD_SIZE")
     if env_ws is None and args.gpus > 1:
@@ -560,7 +638,9 @@ def main():
         return
 
     with_cpu = rank == 0 and not sharded and not args.no_cpu_baseline
-    rec = measure_workload(rig, args, preroll, args.reps, with_cpu)
+    rec = measure_workload(rig, args, preroll, args.reps, with_cpu, want_outputs=args.dump_outputs is not None)
+    if args.dump_outputs is not None:
+        dump_outputs(rec.pop("outputs"), args.dump_outputs, prefix=f"rank{rank}_" if world_size > 1 else "")
 
     out = None
     if rank == 0:
@@ -649,7 +729,10 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        print(json.dumps(out))
+        if args.record:
+            with open(args.record, "w") as f:
+                f.write(json.dumps(out) + "\n")
+        print(json.dumps(result_line(out)))
 
 
 if __name__ == "__main__":

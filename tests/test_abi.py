@@ -55,9 +55,9 @@ def test_config_default_matches_reference_constants():
     assert lib.phys_abi_version() == _abi.PHYS_ABI_VERSION
 
 
-def test_struct_sizes_match_the_c_compiler():
+def test_struct_sizes_match_the_c_compiler(tmp_path):
     src = '#include <stdio.h>\n#include "physics_hip.h"\nint main(){printf("%zu %zu %zu %zu", sizeof(phys_config), sizeof(phys_stats), sizeof(phys_profile), sizeof(phys_device_view));}'
-    exe = "/tmp/_phys_sizes"
+    exe = str(tmp_path / "phys_sizes")
     subprocess.run(["gcc", "-x", "c", "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", exe, "-"], input=src.encode(), check=True)
     sizes = [int(x) for x in subprocess.check_output([exe]).split()]
     assert sizes == [C.sizeof(_abi.PhysConfig), C.sizeof(_abi.PhysStats), C.sizeof(_abi.PhysProfile), C.sizeof(_abi.PhysDeviceView)]
