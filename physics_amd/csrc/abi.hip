@@ -3,6 +3,7 @@
 // is no CPU fallback anywhere in this library.
 #include <algorithm>
 #include <atomic>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <string>
@@ -95,6 +96,45 @@ void poll_snapshots(phys_world* w) {
 namespace phys {
 static std::atomic<int> g_worlds[64];
 int worlds_on_device(int device) { return g_worlds[device & 63].load(std::memory_order_relaxed); }
+bool gpu_is_exclusive(const phys_world* w) {
+    return (w->cfg.flags & PHYS_FLAG_EXCLUSIVE_GPU) && !(w->cfg.flags & PHYS_FLAG_SHARED_GPU) && worlds_on_device(w->device) == 1;
+}
+
+// the value of a switch, parsed by `parse`; std::nullopt when the variable is not set
+template <class Parse>
+static auto debug_env(const char* name, Parse parse) -> std::optional<decltype(parse(""))> {
+    if (const char* v = getenv(name)) return parse(v);
+    return std::nullopt;
+}
+static bool debug_set(const char* name) { return getenv(name) != nullptr; }
+static uint64_t parse_u64(const char* v) { return strtoull(v, nullptr, 10); }
+static bool parse_one(const char* v) { return v[0] == '1'; }
+
+const DebugSwitches& debug_switches() {
+    static const DebugSwitches d = [] {
+        DebugSwitches s;
+        s.no_cluster = debug_set("PHYS_DEBUG_NO_CLUSTER");
+        s.cluster_min = debug_env("PHYS_DEBUG_CLUSTER_MIN", parse_u64);
+        s.clusters_per_cu = debug_env("PHYS_DEBUG_CLUSTERS_PER_CU", atoi);
+        s.cluster_dynamic = debug_set("PHYS_DEBUG_CLUSTER_DYNAMIC");
+        s.cluster_cap = debug_env("PHYS_DEBUG_CLUSTER_CAP", parse_u64).value_or(0);
+        s.flow_max = debug_env("PHYS_DEBUG_FLOW_MAX", parse_u64);
+        s.flow_quad_max = debug_env("PHYS_DEBUG_FLOW_QUAD_MAX", parse_u64).value_or(0);
+        s.flow_pipeline = debug_env("PHYS_DEBUG_FLOW_PIPELINE", parse_one);
+        s.np_early_probe = debug_env("PHYS_DEBUG_NP_EARLY_PROBE", parse_one);
+        s.no_flow_preference = debug_set("PHYS_DEBUG_NO_FLOW_PREFERENCE");
+        s.flow_stall = debug_set("PHYS_DEBUG_FLOW_STALL");
+        s.flow_epoch = debug_env("PHYS_DEBUG_FLOW_EPOCH", [](const char* v) { return (uint32_t)strtoul(v, nullptr, 0); }).value_or(0u);
+        s.ctab_slots = debug_env("PHYS_DEBUG_CTAB_SLOTS", parse_u64).value_or(0);
+        s.color_kernel_lane = debug_env("PHYS_DEBUG_COLOR_KERNEL", [](const char* v) { return v[0] == 'l'; });
+        s.np_threads = debug_env("PHYS_DEBUG_NP_THREADS", atoi).value_or(0);
+        s.pair_lanes = debug_env("PHYS_DEBUG_PAIR_LANES", atoi).value_or(0);
+        s.pair_kernel_brick = debug_env("PHYS_DEBUG_PAIR_KERNEL", [](const char* v) { return v[0] != 'b' || v[1] == 'r'; });
+        s.brick_stage = debug_env("PHYS_DEBUG_BRICK_STAGE", atoi).value_or(0);
+        return s;
+    }();
+    return d;
+}
 }  // namespace phys
 
 static int32_t fail(int32_t code, const char* msg) {

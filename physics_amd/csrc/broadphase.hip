@@ -839,8 +839,8 @@ int32_t collision_alloc(phys_world* w) {
             uint64_t cap = 4096;
             while (cap < M + M / 2) cap <<= 1;
             // PHYS_DEBUG_CTAB_SLOTS=<power of two>: a smaller table (tests of the bounded walks: crowded and overfull tables)
-            static const uint64_t slots_env = getenv("PHYS_DEBUG_CTAB_SLOTS") ? strtoull(getenv("PHYS_DEBUG_CTAB_SLOTS"), nullptr, 10) : 0;
-            if (slots_env >= 64 && (slots_env & (slots_env - 1)) == 0) cap = slots_env;
+            const uint64_t slots = debug_switches().ctab_slots;
+            if (slots >= 64 && (slots & (slots - 1)) == 0) cap = slots;
             PHYS_HIP_TRY(w->ctab.resize(2 * cap));
             w->ctab_mask = (uint32_t)(cap - 1);
             w->ctab_valid = false;
@@ -863,8 +863,7 @@ int32_t collision_alloc(phys_world* w) {
             PHYS_HIP_TRY(hipMemsetAsync(w->flow_vel.p, 0, 8 * n * sizeof(float), w->stream));
             PHYS_HIP_TRY(hipMemsetAsync(w->row_acc.p, 0, 16 * M * sizeof(float), w->stream));
             // PHYS_DEBUG_FLOW_EPOCH=<n>: start the tag epoch near its wrap (test of the 16-bit epoch reset)
-            static const uint32_t epoch_env = getenv("PHYS_DEBUG_FLOW_EPOCH") ? (uint32_t)strtoul(getenv("PHYS_DEBUG_FLOW_EPOCH"), nullptr, 0) : 0u;
-            w->flow_epoch = epoch_env;
+            w->flow_epoch = debug_switches().flow_epoch;
         }
     }
     return PHYS_OK;
@@ -946,17 +945,16 @@ void launch_broadphase(phys_world* w) {
     build_sorted_grid(w);
     // small scenes are latency-bound: 4 lanes per body shorten the dependent chain; large scenes are
     // throughput-bound: one lane per body does the least total work
-    static const int pair_lanes_env = getenv("PHYS_DEBUG_PAIR_LANES") ? atoi(getenv("PHYS_DEBUG_PAIR_LANES")) : 0;  // measurements
     // (measured: one lane per body is the faster one already at 100k bodies - C3: 0.051 against 0.089 ms)
-    // PHYS_DEBUG_PAIR_KERNEL=body / brick forces one (measurements; same pair set)
-    static const char* pair_kernel_env = getenv("PHYS_DEBUG_PAIR_KERNEL");
+    // PHYS_DEBUG_PAIR_LANES=1|4 and PHYS_DEBUG_PAIR_KERNEL=body / brick force one (measurements; same pair set)
+    const DebugSwitches& dbg = debug_switches();
     // The brick kernel wins where the grid is sparsely filled - lattices, stacks of aligned boxes: many bricks of few
     // records (C4 204 -> 119 us, C5 135 -> 73) - and loses where cells are crowded (one tumbled cube sets the cell size for
     // everybody: 1M falling cubes 89 -> 102 us, C3 51 -> 82: few bricks, each a long walk for the one workgroup that has
     // it). Crowding = bodies per bucket in use, counted by k_cell_assign of an earlier update.
     const bool crowded = w->hint.valid && w->hint.n_used_buckets && (uint64_t)w->n * 10ull > (uint64_t)w->hint.n_used_buckets * 21ull;
-    const bool brick = pair_kernel_env ? pair_kernel_env[0] != 'b' || pair_kernel_env[1] == 'r' : !crowded;
-    if (brick && !pair_lanes_env) {
+    const bool brick = dbg.pair_kernel_brick.value_or(!crowded);
+    if (brick && !dbg.pair_lanes) {
         const uint32_t n_bricks = T >> 6;
         // records staged per brick: a quarter more than the largest region of an earlier update (C4: ~400 records, a pile
         // of tumbled cubes: ~1500), 1024 while nothing is known, at most what one workgroup may have of a CU's LDS
@@ -965,15 +963,15 @@ void launch_broadphase(phys_world* w) {
         cap = std::min(std::max((cap + 63u) & ~63u, 256u), kCapMax);
         const size_t dyn = (size_t)cap * 28;
         // few pairs per body (of an earlier update): the small stage, which leaves room for a seventh workgroup per CU
-        static const int stage_env = getenv("PHYS_DEBUG_BRICK_STAGE") ? atoi(getenv("PHYS_DEBUG_BRICK_STAGE")) : 0;  // measurements: 128 | 256
-        const bool small_stage = stage_env ? stage_env == 128 : (w->hint.valid && (uint64_t)w->hint.n_pairs < 3ull * w->n);
+        // (PHYS_DEBUG_BRICK_STAGE=128|256 forces one: measurements)
+        const bool small_stage = dbg.brick_stage ? dbg.brick_stage == 128 : (w->hint.valid && (uint64_t)w->hint.n_pairs < 3ull * w->n);
         const size_t fixed = (kPairThreads / 64) * (small_stage ? 128 : 256) * 8 + kRegCells * 8 + 64;
         // persistent workgroups, as many as are resident at once (the LDS decides), never more than there are bricks
         // at most seven per CU (66 registers: seven waves per SIMD). Measured, us (C4 / 1M cubes in mid-fall / C5): 3 per CU
         // 173 / 145 / 74, 4: 137 / 114 / 72, 5: 117 / 100 / 69, 6: 105 / 89 / 70, 7 (small stage): 103 / 83 / -; asked for 8
         // (not all resident: the late ones start on a drained chip) 131 / 109 / 69
-        static const size_t per_cu_max = getenv("PHYS_DEBUG_BRICK_PER_CU") ? (size_t)atoi(getenv("PHYS_DEBUG_BRICK_PER_CU")) : 7;  // measurements
-        uint32_t per_cu = (uint32_t)std::min<size_t>(per_cu_max, (160 * 1024) / (((dyn + fixed) + 1023) / 1024 * 1024));
+        constexpr size_t kBrickPerCuMax = 7;
+        uint32_t per_cu = (uint32_t)std::min<size_t>(kBrickPerCuMax, (160 * 1024) / (((dyn + fixed) + 1023) / 1024 * 1024));
         uint32_t wgs = 256u * std::max(per_cu, 1u);
         while (wgs > n_bricks) wgs >>= 1;
         static bool attr_set[64] = {};  // per device (function attributes are): more than 64 KiB of dynamic LDS needs it
@@ -992,7 +990,7 @@ void launch_broadphase(phys_world* w) {
                                w->sorted_ids.p, w->sorted_box.p, w->pairs.p, w->max_pairs, w->counters.p, cap);
         return;
     }
-    if (pair_lanes_env ? pair_lanes_env == 4 : n <= 65536u) {
+    if (dbg.pair_lanes ? dbg.pair_lanes == 4 : n <= 65536u) {
         PHYS_PROF(w, PHYS_STAGE_PAIRS);
         hipLaunchKernelGGL((k_find_pairs<4>), dim3((unsigned)(((uint64_t)n * 4 + kPairThreads - 1) / kPairThreads)), dim3(kPairThreads), 0, s,
                            w->bucket_start.p, T, axis_mask, w->sorted_ids.p, w->sorted_box.p, w->pairs.p, w->max_pairs, w->counters.p);

@@ -61,36 +61,34 @@ static uint32_t spread10(uint32_t x) {
 // the (cluster, colour) counters sit behind the 2 n mask words of body_shared, on a 16-byte boundary (the scans read uint4)
 static size_t seg_count_offset(uint64_t n) { return ((size_t)2 * n + 3) & ~(size_t)3; }
 
+// workgroups of a cluster grid of per_cu per CU, an eighth of the chip spared (at least 8)
+static uint32_t clusters_on_chip(int per_cu, int cus) { return (uint32_t)std::max(8, per_cu * (cus - cus / 8)); }
+
 int32_t cluster_assign(phys_world* w, const float* pos /* host, 3 * n_owned */) {
     w->cluster_count = 0;
     w->seg_count_dirty = false;  // (both allocations below are zeroed)
     w->seg_count_bins = 0;
     const uint64_t n = w->n, n_owned = w->n_owned;
-    static const bool off = getenv("PHYS_DEBUG_NO_CLUSTER") != nullptr;
+    const DebugSwitches& dbg = debug_switches();
     w->cluster_dynamic = false;
     w->cluster_homes_valid = false;
-    if (off || n_owned < kClusterMinBodies || !w->flow_vel.p) return PHYS_OK;
+    if (dbg.no_cluster || n_owned < kClusterMinBodies || !w->flow_vel.p) return PHYS_OK;
     int cus = 0;
     PHYS_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, w->device));
     w->cluster_cus = cus;
     // one workgroup per cluster, several per CU (their phases interleave: one waits for its rows while the others
     // solve); an eighth of the chip to spare: EVERY workgroup must be resident (the kernel's occupancy bound admits
     // kClusterPerCu* of them per CU; a workgroup that found no room would be waited for until the time-out)
-    static const char* per_cu_env = getenv("PHYS_DEBUG_CLUSTERS_PER_CU");
     const int per_cu_max = w->all_diag_inertia ? kClusterPerCuDiag : kClusterPerCuFull;
-    int per_cu = per_cu_env ? std::min(per_cu_max, std::max(1, atoi(per_cu_env))) : per_cu_max;
-    static const int spare_div = getenv("PHYS_DEBUG_CLUSTER_SPARE") ? atoi(getenv("PHYS_DEBUG_CLUSTER_SPARE")) : 8;
+    int per_cu = dbg.clusters_per_cu ? std::min(per_cu_max, std::max(1, *dbg.clusters_per_cu)) : per_cu_max;
     // PHYS_DEBUG_CLUSTER_DYNAMIC: dynamic clusters even where the static ones fit; PHYS_DEBUG_CLUSTER_CAP=<bodies>: fewer
     // homes than the LDS would hold, so that some bodies stay homeless (tests of exactly that; same bits)
-    static const bool force_dynamic = getenv("PHYS_DEBUG_CLUSTER_DYNAMIC") != nullptr;
-    static const uint64_t cap_env = getenv("PHYS_DEBUG_CLUSTER_CAP") ? strtoull(getenv("PHYS_DEBUG_CLUSTER_CAP"), nullptr, 10) : 0;
-    w->cluster_cap_limit = cap_env;
     uint32_t slots = 0;
-    bool fits = !force_dynamic;
+    bool fits = !dbg.cluster_dynamic;
     // ... and the LDS of a CU must hold all of its workgroups' bodies (64 B per slot + the segment table, in 1 KiB
     // allocation units), or the grid would not be resident: fewer, larger clusters per CU until it does
     for (; fits; --per_cu) {
-        const uint32_t max_clusters = (uint32_t)std::max(8, per_cu * (cus - (spare_div ? cus / spare_div : 0)));
+        const uint32_t max_clusters = clusters_on_chip(per_cu, cus);
         slots = (uint32_t)((n_owned + max_clusters - 1) / max_clusters);
         slots = (slots + 63u) / 64u * 64u;
         const size_t per_wg = (cluster_lds_bytes(slots) + 1023) / 1024 * 1024;
@@ -101,7 +99,7 @@ int32_t cluster_assign(phys_world* w, const float* pos /* host, 3 * n_owned */) 
         // DYNAMIC clusters: homes are dealt out every update, to the bodies that have a manifold in it, in the broad
         // phase's bucket order (launch_cluster_sort); their number and size follow the count of such bodies
         // (cluster_plan_dynamic). Needs the sorted grid of the broad phase (n > 32768: always the case here).
-        const uint32_t clusters_max = (uint32_t)std::max(8, per_cu_max * (cus - (spare_div ? cus / spare_div : 0)));
+        const uint32_t clusters_max = clusters_on_chip(per_cu_max, cus);
         const size_t homes_max = (size_t)cus * (kClusterLdsPerCu / kClusterSlotBytesDecl) + 64;
         PHYS_HIP_TRY(w->cluster_slot.resize(n));
         PHYS_HIP_TRY(w->cluster_body.resize(homes_max));
@@ -173,17 +171,16 @@ bool cluster_plan_dynamic(phys_world* w) {
     uint64_t active = w->hint.n_active;
     if (active == 0) active = std::min<uint64_t>(w->n_owned, (uint64_t)w->hint.n_manifolds);
     if (active == 0) return false;
-    static const int spare_div = getenv("PHYS_DEBUG_CLUSTER_SPARE") ? atoi(getenv("PHYS_DEBUG_CLUSTER_SPARE")) : 8;
-    static const char* per_cu_env = getenv("PHYS_DEBUG_CLUSTERS_PER_CU");
+    const DebugSwitches& dbg = debug_switches();
     const int per_cu_max = w->all_diag_inertia ? kClusterPerCuDiag : kClusterPerCuFull;
-    int per_cu = per_cu_env ? std::min(per_cu_max, std::max(1, atoi(per_cu_env))) : per_cu_max;
+    int per_cu = dbg.clusters_per_cu ? std::min(per_cu_max, std::max(1, *dbg.clusters_per_cu)) : per_cu_max;
     const int cus = w->cluster_cus;
     // homes for a quarter more bodies than the last known count; what does not get one is served as "another cluster's
     // body" (slower, never wrong), so this is a matter of speed only
     uint64_t want = active + active / 4;
-    if (w->cluster_cap_limit && want > w->cluster_cap_limit) want = w->cluster_cap_limit;
+    if (dbg.cluster_cap && want > dbg.cluster_cap) want = dbg.cluster_cap;
     for (;; --per_cu) {
-        const uint32_t clusters = (uint32_t)std::max(8, per_cu * (cus - (spare_div ? cus / spare_div : 0)));
+        const uint32_t clusters = clusters_on_chip(per_cu, cus);
         uint32_t slots = (uint32_t)((want + clusters - 1) / clusters);
         slots = std::max(64u, (slots + 63u) / 64u * 64u);
         const size_t per_wg = (cluster_lds_bytes(slots) + 1023) / 1024 * 1024;
@@ -193,11 +190,11 @@ bool cluster_plan_dynamic(phys_world* w) {
             // moment the plan has to go to two or one larger workgroups per CU the per-colour launches are faster (2.10
             // against 2.33 ms at 430k active bodies, 2.66 against 3.30 at 500k; with half the bodies homeless 3.61 against
             // 4.08) - fewer workgroups hide less of each other's colour steps. (A capacity set for tests is obeyed.)
-            if ((!ok || per_cu < per_cu_max) && !w->cluster_cap_limit && !per_cu_env) return false;
+            if ((!ok || per_cu < per_cu_max) && !dbg.cluster_cap && !dbg.clusters_per_cu) return false;
             // (PHYS_DEBUG_CLUSTERS_PER_CU asks for fewer, larger workgroups - never for homes that do not fit: with the
             // switch set, the growing 1M-cube pile once ran one 160 KiB workgroup per CU with half its bodies homeless and
             // ended in the hand-off time-out)
-            if (!ok && !w->cluster_cap_limit) return false;
+            if (!ok && !dbg.cluster_cap) return false;
             if (!ok) slots = kClusterMaxSlots / 64u * 64u;  // one workgroup per CU, as many homes as its LDS holds
             w->cluster_count = clusters;
             w->cluster_slots = slots;
@@ -418,7 +415,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                                                                   const uint32_t* __restrict__ cluster_body,
                                                                   const uint32_t* __restrict__ body_shared,
                                                                   const uint32_t* __restrict__ seg_start, uint32_t slots,
-                                                                  long long timeout_ticks, uint32_t ablate, uint32_t attempt,
+                                                                  long long timeout_ticks, uint32_t attempt,
                                                                   uint32_t last_attempt, long long arrive_ticks,
                                                                   uint32_t warm_sweep /* sweep 0 applies the starting impulses (and
                                                                   `iterations` counts it) */, const uint32_t* __restrict__ row_src,
@@ -558,10 +555,9 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                 const uint32_t info = __float_as_uint(nn.w);
                 // slot (13 bits) | publish (1) | mode (2) per side. publish: the NEXT update of this (shared, own) body is
                 // made by another workgroup, so this update must reach the granules; otherwise it stays in LDS
-                uint32_t modeA = (info >> 14) & 3u, modeB = (info >> 30) & 3u;
+                const uint32_t modeA = (info >> 14) & 3u, modeB = (info >> 30) & 3u;
                 const uint32_t slotA = info & 0x1FFFu, slotB = (info >> 16) & 0x1FFFu;
                 const bool pubA = (info >> 13) & 1u, pubB = (info >> 29) & 1u;
-                if (ablate & 8u) { if (modeA == 1u) modeA = 0u; if (modeB == 1u) modeB = 0u; }  // PHYS_DEBUG_ABLATE (timing only, wrong results)
                 geo_manifold_t gm;
                 gm.count = (int)h.z;
                 gm.has_b = h.y != PHYS_GROUND_ID;
@@ -609,7 +605,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                         IA.m[0] = fia.x; IA.m[4] = fia.y; IA.m[8] = fia.z;
                     }
                     if (tA == 0u) { const BodyVel A0 = ld_vel(vel, h.x); vA = A0.v; wA = A0.w; }
-                    needA = tA != 0u && !(ablate & 8u);
+                    needA = tA != 0u;
                 }
                 if (modeB == 0u || modeB == 1u) {
                     const float4* sb = s_body + 4 * slotB;
@@ -625,7 +621,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                         const BodyVel B0 = ld_vel(vel, h.y);
                         vB = B0.v; wB = B0.w;
                     }
-                    needB = tB != 0u && !(ablate & 8u);
+                    needB = tB != 0u;
                 }
                 if (!DIAG) {  // full tensors: gathered by body id (the rare path keeps its second round trip)
                     IA = ld_inertia_c<false>(inv_inertia, h.x * inertia_stride);
@@ -672,9 +668,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                     ctr->debug[7] = (col & 0xFFu) | ((it & 0xFFu) << 8);
                 }
                 if (!dead) {
-                    if (!(ablate & 2u))
-                        solve_manifold_geo(&gm, it == 0u || (ablate & 32u), (warm_sweep != 0u && it == 0u) ? 1 : 0, friction, xA, ima, &IA, xB, imb,
-                                           &IB, &vA, &wA, &vB, &wB);
+                    solve_manifold_geo(&gm, it == 0u, (warm_sweep != 0u && it == 0u) ? 1 : 0, friction, xA, ima, &IA, xB, imb, &IB, &vA, &wA, &vB, &wB);
                     // ---- write back
                     if (modeA == 0u || modeA == 1u) {
                         s_body[4 * slotA] = make_float4(vA.x, vA.y, vA.z, __uint_as_float(etag | (tA + 1u)));
@@ -745,7 +739,6 @@ void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float fric
                           bool diag, long long timeout_ticks) {
     const uint32_t warm_sweep = w->warm ? 1u : 0u;
     const uint32_t sweeps = w->cfg.solver_iterations + warm_sweep;
-    static const uint32_t ablate = getenv("PHYS_DEBUG_ABLATE") ? (uint32_t)atoi(getenv("PHYS_DEBUG_ABLATE")) : 0u;
     ClusterRowArrays rows;
     rows.all = (float4*)row_all; rows.cap = cap;
     const size_t lds = cluster_lds_bytes(w->cluster_slots);
@@ -780,7 +773,7 @@ void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float fric
     // run one after the other, every launch starts on an idle device, the count - 0.04 ms per update on C5 and on the
     // 1M cubes (tools/guard_cost.py) - is skipped). The guarded start is the default since round 3: a drop-in behind a render loop shares its GPU
     // with the renderer, and the unguarded launch's failure mode there is a 3 s spin.
-    const bool guarded = worlds_on_device(w->device) > 1 || !(w->cfg.flags & PHYS_FLAG_EXCLUSIVE_GPU) || (w->cfg.flags & PHYS_FLAG_SHARED_GPU) != 0u;
+    const bool guarded = !gpu_is_exclusive(w);
     const uint32_t kAttempts = guarded ? 2u : 1u;
     for (uint32_t attempt = 0; attempt < kAttempts; ++attempt) {
         const uint32_t last = attempt + 1 == kAttempts ? 1u : 0u;
@@ -788,7 +781,7 @@ void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float fric
         const long long arrive_ticks = !guarded ? -1ll : (attempt == 0 ? 50000ll : 2000000ll);
 #define PHYS_CLUSTER_ARGS g, b, lds, w->stream, w->counters.p, sweeps, w->flow_epoch, rows, friction, inertia, stride, \
                           w->vel.p, w->pos.p, w->flow_vel.p, (uint32_t)w->n, w->cluster_body.p, w->body_shared.p, w->seg_start.p,     \
-                          w->cluster_slots, timeout_ticks, ablate, attempt, last, arrive_ticks, warm_sweep, w->row_src.p,              \
+                          w->cluster_slots, timeout_ticks, attempt, last, arrive_ticks, warm_sweep, w->row_src.p,                     \
                           w->warm ? w->man_imp.p : (float*)nullptr
         if (guarded) {
             if (diag) hipLaunchKernelGGL((k_solve_cluster<true, true>), PHYS_CLUSTER_ARGS);

@@ -32,7 +32,7 @@ __device__ __forceinline__ geom_t load_geom(uint32_t i, const float* __restrict_
 }
 
 // kNpThreads: 128 for small scenes (latency-bound: more workgroups in flight, the LDS slice of the clipper
-// halves), 256 for everything else (launch_narrowphase)
+// halves), 512 for everything else (launch_narrowphase)
 template <int kNpThreads, int kNpItems>
 __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
     uint32_t n_ground /* bodies tested against the plane (0 = no ground) */, uint32_t n_owned /* pairs whose FIRST body is at
@@ -782,31 +782,27 @@ void launch_narrowphase(phys_world* w) {
     const uint32_t cache_mask = w->ctab_valid ? w->ctab_mask : 0u;
     const uint32_t stamp = (uint32_t)w->color_epoch + 1u;  // never 0xFFFFFFFF (the stamp of an empty slot) in a world's life
     // the colour-table entry of a pair is asked for ahead of the shape test where at least half of the pairs become manifolds
-    static const char* probe_env = getenv("PHYS_DEBUG_NP_EARLY_PROBE");  // 0 / 1 forces it (measurements; same bits)
-    const uint32_t early_probe = probe_env ? (uint32_t)(probe_env[0] == '1')
-                                           : (uint32_t)(!w->hint.valid || 2ull * w->hint.n_manifolds >= (uint64_t)w->hint.n_pairs);
+    const DebugSwitches& dbg = debug_switches();  // PHYS_DEBUG_NP_EARLY_PROBE=0 / 1 forces it (measurements; same bits)
+    const uint32_t early_probe = dbg.np_early_probe.value_or(!w->hint.valid || 2ull * w->hint.n_manifolds >= (uint64_t)w->hint.n_pairs);
     if (w->warm) {  // last update's records become "previous": what this update's kept manifolds start from
         std::swap(w->man_geo.p, w->man_geo_prev.p);
         std::swap(w->man_imp.p, w->man_imp_prev.p);
     }
     PHYS_PROF(w, PHYS_STAGE_NARROW);
-#define PHYS_NP_LAUNCH(T, kItems)                                                                                              \
+#define PHYS_NP_LAUNCH(T)                                                                                              \
     do {                                                                                                               \
-        uint64_t blocks = (work + T * kItems - 1) / (T * kItems);                                                      \
+        uint64_t blocks = (work + T - 1) / T;                                                                          \
         if (blocks > 256 * 16) blocks = 256 * 16;                                                                      \
-        hipLaunchKernelGGL((k_narrowphase<T, kItems>), dim3((unsigned)blocks), dim3(T), np_extra_lds, w->stream, n_ground, n_owned, w->pairs.p, \
+        hipLaunchKernelGGL((k_narrowphase<T, 1>), dim3((unsigned)blocks), dim3(T), 0, w->stream, n_ground, n_owned, w->pairs.p, \
                            w->max_pairs, w->geo.p, w->cfg.contact_margin, \
                            w->cfg.ground_height, w->max_manifolds, w->man_a.p, w->man_b.p,                             \
                            w->man_color.p, w->man_geo.p, w->man_prio.p, w->color_state.p,                              \
                            w->color_state.p + n, reinterpret_cast<ulonglong2*>(w->ctab.p), cache_mask, early_probe, stamp, \
                            w->unc_list.p, w->warm ? w->man_prev.p : nullptr, w->man_imp.p, w->counters.p);             \
     } while (0)
-    static const unsigned np_extra_lds = getenv("PHYS_DEBUG_NP_EXTRA_LDS") ? (unsigned)atoi(getenv("PHYS_DEBUG_NP_EXTRA_LDS")) : 0u;  // occupancy experiments
-    static const int np_threads_env = getenv("PHYS_DEBUG_NP_THREADS") ? atoi(getenv("PHYS_DEBUG_NP_THREADS")) : 0;  // measurements
     // 128 threads only while the whole stage is a few workgroups (C2: 10k manifolds); measured at 230k manifolds (C3):
     // 0.175 ms with 128 threads, 0.133 with 256; at 2.9M (C5): 0.86 vs 0.55 (round 2)
     const bool few = w->hint.valid ? w->hint.n_manifolds <= 32768u : n <= 200000u;
-    static const int np_items_env = getenv("PHYS_DEBUG_NP_ITEMS") ? atoi(getenv("PHYS_DEBUG_NP_ITEMS")) : 0;  // measurements
     // Workgroup shape (all variants: same manifolds, emission order is arbitrary anyway). A trip ends in one reservation
     // behind two barriers, and the waves a CU holds are what hides a trip's round trips from each other; the in-place
     // clipper's LDS slice (33 dwords per lane) admits 16 waves per CU at 118 registers. Measured, ms per update
@@ -815,13 +811,10 @@ void launch_narrowphase(phys_world* w) {
     //   256 threads, two items per lane (151 registers: 12 waves)       0.230 / 0.067 / 0.917 / 0.093
     //   512 threads, one item (2 workgroups per CU, half the atomics)   0.206 / 0.069 / 0.836 / 0.075   <- the default
     //   1024 threads, one item (a barrier over 16 waves)                0.231 / 0.084 / 0.937 / 0.080
-    // PHYS_DEBUG_NP_THREADS=128|256|512|1024 and PHYS_DEBUG_NP_ITEMS=1|2 (with 256) pick one by hand.
-    const int threads = np_threads_env ? np_threads_env : (few ? 128 : 512);
-    if (threads == 128) PHYS_NP_LAUNCH(128, 1);
-    else if (threads == 256 && np_items_env == 2) PHYS_NP_LAUNCH(256, 2);
-    else if (threads == 256) PHYS_NP_LAUNCH(256, 1);
-    else if (threads == 1024) PHYS_NP_LAUNCH(1024, 1);
-    else PHYS_NP_LAUNCH(512, 1);
+    // Only the two the library picks are built; PHYS_DEBUG_NP_THREADS=128|512 picks one by hand.
+    const int threads = dbg.np_threads ? dbg.np_threads : (few ? 128 : 512);
+    if (threads == 128) PHYS_NP_LAUNCH(128);
+    else PHYS_NP_LAUNCH(512);
 #undef PHYS_NP_LAUNCH
 }
 
@@ -863,22 +856,21 @@ void launch_coloring(phys_world* w) {
     bool snapshot_done = false;
     // cluster solver this update? (decided here because it decides the ORDER of the rows: by (cluster, colour)
     // instead of by colour). PHYS_DEBUG_CLUSTER_MIN=<manifolds> moves the threshold (measurements; same bits either way).
-    static const char* cluster_min_env = getenv("PHYS_DEBUG_CLUSTER_MIN");
+    const DebugSwitches& dbg = debug_switches();
     const bool cluster_forced = (w->cfg.flags & PHYS_FLAG_SOLVER_CLUSTER) != 0u;
-    const uint64_t cluster_min = cluster_forced ? 0 : (cluster_min_env ? strtoull(cluster_min_env, nullptr, 10) : kClusterMinManifolds);
+    const uint64_t cluster_min = cluster_forced ? 0 : dbg.cluster_min.value_or(kClusterMinManifolds);
     // worth it where contacts are dense (C5: 11 rows per body): velocities stay in LDS for many rows each. Sparse piles
     // (the 1M-cube scene: 0.4-0.5 rows per body, contacts in the bottom layers only) leave most clusters idle and a few
     // overloaded - they keep the dataflow / per-colour kernels, which spread rows evenly over the chip
     // (dynamic clusters hold only the bodies that have manifolds: nothing idles, the row count alone decides)
-    const bool dense = cluster_forced || cluster_min_env || w->cluster_dynamic || 2ull * w->hint.n_manifolds >= 3ull * w->n_owned;
+    const bool dense = cluster_forced || dbg.cluster_min.has_value() || w->cluster_dynamic || 2ull * w->hint.n_manifolds >= 3ull * w->n_owned;
     w->cluster_step = (w->cluster_count > 0 || w->cluster_dynamic) && w->hint.valid && !small && dense &&
                       w->hint.n_manifolds >= cluster_min && !(w->cfg.flags & PHYS_FLAG_SOLVER_PER_COLOR) &&
                       w->cfg.solver_iterations > 0 && w->cfg.solver_iterations < 1000 && w->hint.n_colors > 0;
     // ... unless the dataflow kernel is the faster one for this many rows and colours (kernels.hpp; only where it may take
     // the whole chip: PHYS_FLAG_EXCLUSIVE_GPU, one world on the device)
-    static const bool no_flow_pref = getenv("PHYS_DEBUG_NO_FLOW_PREFERENCE") != nullptr;  // measurements; same bits
-    w->flow_wide = (w->cfg.flags & PHYS_FLAG_EXCLUSIVE_GPU) && !(w->cfg.flags & PHYS_FLAG_SHARED_GPU) && worlds_on_device(w->device) == 1;
-    if (w->cluster_step && !cluster_forced && !cluster_min_env && !no_flow_pref && w->flow_wide && w->hint.n_manifolds <= kFlowWideMaxManifolds &&
+    w->flow_wide = gpu_is_exclusive(w);  // (PHYS_DEBUG_NO_FLOW_PREFERENCE: never; measurements, same bits)
+    if (w->cluster_step && !cluster_forced && !dbg.cluster_min.has_value() && !dbg.no_flow_preference && w->flow_wide && w->hint.n_manifolds <= kFlowWideMaxManifolds &&
         flow_quad_beats_cluster(w->hint.n_manifolds, w->hint.n_contacts, w->hint.n_colors))
         w->cluster_step = false;
     if (w->cluster_step && w->cluster_dynamic) w->cluster_step = cluster_plan_dynamic(w);  // clusters and slots (every few updates)

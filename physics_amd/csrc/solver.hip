@@ -294,14 +294,11 @@ __device__ __forceinline__ void solve_row(uint32_t d, const RowArrays& rows, flo
                                           const float* __restrict__ inv_inertia,
                                           uint32_t inertia_stride /* 0: one tensor shared by every body */,
                                           float* __restrict__ vel, int apply_only /* sweep 0 of a warm-started solve */,
-                                          int last /* the solve's last sweep: the impulses are remembered */, const WarmJob& wj,
-                                          uint32_t ablate = 0, uint32_t n_bodies = 1) {
+                                          int last /* the solve's last sweep: the impulses are remembered */, const WarmJob& wj) {
     RowRegs R;
     load_row<true, EAGER>(R, d, rows);
     solver_manifold_t& sm = R.sm;
-    // PHYS_DEBUG_ABLATE (timing diagnosis, WRONG results): bit 0 - body records gathered at consecutive indices instead
-    // of the row's bodies (what the gather's scatter costs); bit 1 - no row arithmetic; bit 2 - no velocity write-back
-    const uint32_t a = (ablate & 1u) ? d % n_bodies : R.a, b = (ablate & 1u) ? (d + 7u) % n_bodies : R.b;
+    const uint32_t a = R.a, b = R.b;
     const m33 IA = ld_inertia<DIAG>(inv_inertia, a * inertia_stride);
     BodyVel A = ld_vel(vel, a);
     const float ima = A.inv_mass;
@@ -315,12 +312,10 @@ __device__ __forceinline__ void solve_row(uint32_t d, const RowArrays& rows, flo
     if (sm.has_b) { IB = ld_inertia<DIAG>(inv_inertia, b * inertia_stride); B = ld_vel(vel, b); imb = B.inv_mass; vB = B.v; wB = B.w; }
     // rows made on the way: these kernels are throughput-bound and want the registers (k_solve_flow makes them all
     // beforehand, while it waits; same arithmetic)
-    if (!(ablate & 2u)) solve_manifold_lazy(&sm, friction, ima, &IA, imb, &IB, &vA, &wA, &vB, &wB, apply_only);
+    solve_manifold_lazy(&sm, friction, ima, &IA, imb, &IB, &vA, &wA, &vB, &wB, apply_only);
     A.v = vA; A.w = wA;
-    if (!(ablate & 4u)) {
-        st_vel(vel, a, A);
-        if (sm.has_b) { B.v = vB; B.w = wB; st_vel(vel, b, B); }
-    }
+    st_vel(vel, a, A);
+    if (sm.has_b) { B.v = vB; B.w = wB; st_vel(vel, b, B); }
     if (!apply_only) {  // (sweep 0 changes no impulse)
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -361,8 +356,7 @@ struct XcdTiles {
 template <bool DIAG>
 __global__ __launch_bounds__(256) void k_solve_color(const StepCounters* __restrict__ ctr, uint32_t col, RowArrays rows,
                                                      float friction, const float* __restrict__ inv_inertia,
-                                                     uint32_t inertia_stride, float* __restrict__ vel, uint32_t ablate,
-                                                     uint32_t n_bodies, int apply_only, int last, WarmJob wj) {
+                                                     uint32_t inertia_stride, float* __restrict__ vel, int apply_only, int last, WarmJob wj) {
     if (ctr->overflow) return;
     const uint32_t start = ctr->color_start[col], end = ctr->color_start[col + 1];
     // XCD-aware tiles: the rows of a colour are in emission (= spatial) order, so a contiguous range of them touches a
@@ -372,7 +366,7 @@ __global__ __launch_bounds__(256) void k_solve_color(const StepCounters* __restr
     // 5.6 MB of gathered records when tiles were dealt in plain blockIdx order). Speed only: any mapping is correct.
     for (XcdTiles t(end - start, blockDim.x); t.valid(); t.next()) {
         const uint32_t d = start + t.tile * blockDim.x + threadIdx.x;
-        if (d < end) solve_row<DIAG, true>(d, rows, friction, inv_inertia, inertia_stride, vel, apply_only, last, wj, ablate, n_bodies);
+        if (d < end) solve_row<DIAG, true>(d, rows, friction, inv_inertia, inertia_stride, vel, apply_only, last, wj);
     }
 }
 
@@ -1125,14 +1119,14 @@ void launch_solver(phys_world* w, float dt) {
     // from step to step.
     // (tickets are 16-bit: iterations x 64 colours must stay below 65536)
     // PHYS_DEBUG_FLOW_MAX=<manifolds>: move the dataflow / per-colour crossover (measurements only; same bits either way)
-    static const char* flow_max_env = getenv("PHYS_DEBUG_FLOW_MAX");
-    const uint64_t flow_max = flow_max_env ? strtoull(flow_max_env, nullptr, 10) : kFlowMaxManifolds;
+    const DebugSwitches& dbg = debug_switches();
+    const uint64_t flow_max = dbg.flow_max.value_or(kFlowMaxManifolds);
     const bool cluster = w->cluster_step;  // decided by launch_coloring: this update's rows are in (cluster, colour) order
     const bool flow = cluster || (w->flow_vel.p && h.valid && m_hint <= flow_max && w->cfg.solver_iterations > 0 &&
                                   w->cfg.solver_iterations < 1000);
     // fault injection for tests/test_gpu_full_size.py: one row gets a ticket nobody will ever publish, so the bounded
     // spin of the dataflow kernels must give up, flag the step (overflow bit 4) and let the launch end
-    static const bool stall = getenv("PHYS_DEBUG_FLOW_STALL") != nullptr;
+    const bool stall = dbg.flow_stall;
     const long long timeout_ticks = stall ? 2000000ll : kFlowTimeoutTicks;
     // warm starting (contact_solve.h): one sweep more, in front - it applies the impulses the rows start from
     WarmJob warm{};
@@ -1178,29 +1172,26 @@ void launch_solver(phys_world* w, float dt) {
             return;
         }
         // about one wave per SIMD or less: waiting waves must not crowd out the ones that can run
-        static const uint64_t quad_max_env = getenv("PHYS_DEBUG_FLOW_QUAD_MAX") ? strtoull(getenv("PHYS_DEBUG_FLOW_QUAD_MAX"), nullptr, 10) : 0;  // measurements
         // four lanes per manifold while the hop latency is everything - and, where the launch may take the whole chip
         // (w->flow_wide: three workgroups per CU, 672 of them), all the way up: 155k manifolds 0.250 ms against 0.446 with
         // 224 workgroups, C3's 216k 0.325 (cluster kernel 0.513), the 1M cubes' 379k 0.405 (cluster kernel 0.235)
-        const bool quad = m_hint <= (quad_max_env ? quad_max_env : (w->flow_wide ? kFlowMaxManifolds : kFlowQuadMaxManifolds));
+        const bool quad = m_hint <= (dbg.flow_quad_max ? dbg.flow_quad_max : (w->flow_wide ? kFlowMaxManifolds : kFlowQuadMaxManifolds));
         const uint32_t threads = 256u;
         const uint32_t rows_per_item = quad ? threads / 4 : threads;
         uint64_t items = (uint64_t)sweeps * ((m_hint * 5 / 4 + rows_per_item - 1) / rows_per_item) + 1;
-        static const uint64_t wgs_env = getenv("PHYS_DEBUG_FLOW_WGS") ? strtoull(getenv("PHYS_DEBUG_FLOW_WGS"), nullptr, 10) : 0;  // measurements (quad)
         int cus = 256;
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, w->device);
         // statically dealt items need every workgroup running: a third of the chip's slots by default (beside other
         // streams' kernels), seven eighths of them - the cluster kernel's share - where the GPU is this world's alone
         // (small scenes are a chain of hand-offs, not throughput: C2's 10k manifolds 0.053 ms at 224 workgroups, 0.058 at 672)
-        const uint64_t most = quad ? (wgs_env ? wgs_env : (w->flow_wide && m_hint > 32768u ? (uint64_t)(3 * (cus - cus / 8)) : 224)) : 256;
+        const uint64_t most = quad ? (w->flow_wide && m_hint > 32768u ? (uint64_t)(3 * (cus - cus / 8)) : 224) : 256;
         if (items > most) items = most;  // the remaining items are taken by the same workgroups
         PHYS_PROF(w, PHYS_STAGE_SOLVE_FLOW);
         // look one work item ahead (k_solve_flow) while a colour class keeps a good part of the launch busy; below that the
         // solve is a chain of hand-offs and an item held ahead only waits (C3: 16k rows per colour, 65k lanes: +10 %;
         // 1M cubes: 41k rows per colour: -10 %). PHYS_DEBUG_FLOW_PIPELINE=0/1 forces it (measurements; same bits).
-        static const char* pipe_env = getenv("PHYS_DEBUG_FLOW_PIPELINE");
         const uint64_t per_color = m_hint / (h.valid && h.n_colors ? h.n_colors : 1u);
-        const uint32_t pipeline = pipe_env ? (uint32_t)(pipe_env[0] == '1') : (uint32_t)(4 * per_color >= threads * items);
+        const uint32_t pipeline = (uint32_t)dbg.flow_pipeline.value_or(4 * per_color >= threads * items);
 #define PHYS_FLOW_ARGS dim3((unsigned)items), dim3(threads), 0, s, w->counters.p, sweeps, \
                        w->flow_epoch, rows, sp.friction, inertia, stride, w->vel.p, w->flow_vel.p, (uint32_t)w->n, timeout_ticks
         if (quad) { if (diag) hipLaunchKernelGGL(k_solve_flow_quad<true>, PHYS_FLOW_ARGS, warm_sweep, warm); else hipLaunchKernelGGL(k_solve_flow_quad<false>, PHYS_FLOW_ARGS, warm_sweep, warm); }
@@ -1216,13 +1207,10 @@ void launch_solver(phys_world* w, float dt) {
         while (big > 0 && h.color_count[big - 1] <= kTailMax) --big;
         if (h.n_colors - big < 2) big = h.n_colors;  // a tail of one colour is just a slower launch
     }
-    // PHYS_DEBUG_COLOR_KERNEL=lane: the one-lane-per-manifold kernel for every colour (A/B measurements, parity tests)
-    static const char* color_kernel_env = getenv("PHYS_DEBUG_COLOR_KERNEL");
-    static const uint32_t ablate = getenv("PHYS_DEBUG_ABLATE") ? (uint32_t)atoi(getenv("PHYS_DEBUG_ABLATE")) : 0u;
     // four lanes per manifold while a colour is too small to fill the chip with one lane per manifold (measured
-    // crossover ~30k rows: 15k rows 10.2 vs 11.9 us per launch, 53k rows 18.3 vs 16.7, 85k rows 21.5 vs 18.7)
+    // crossover ~30k rows: 15k rows 10.2 vs 11.9 us per launch, 53k rows 18.3 vs 16.7, 85k rows 21.5 vs 18.7).
+    // PHYS_DEBUG_COLOR_KERNEL=lane / quad: one of them for every colour (A/B measurements, parity tests)
     constexpr uint32_t kQuadColorMaxRows = 32768;
-    const int color_kernel_mode = !color_kernel_env ? 0 : (color_kernel_env[0] == 'l' ? 1 : 2);  // 0 auto, 1 lane, 2 quad
     auto grid_for_quads = [&](uint64_t count) {
         uint64_t b = (count * 5 / 4 + kQuadRowsPerGroup - 1) / kQuadRowsPerGroup + 1;
         const uint64_t hi = (cap + kQuadRowsPerGroup - 1) / kQuadRowsPerGroup;
@@ -1234,7 +1222,7 @@ void launch_solver(phys_world* w, float dt) {
         const int apply_only = warm_sweep && it == 0 ? 1 : 0, last = it + 1 == sweeps ? 1 : 0;
         for (uint32_t col = 0; col < big; ++col) {
             PHYS_PROF(w, PHYS_STAGE_SOLVE);
-            if (color_kernel_mode == 2 || (color_kernel_mode == 0 && h.color_count[col] <= kQuadColorMaxRows)) {
+            if (!dbg.color_kernel_lane.value_or(h.color_count[col] > kQuadColorMaxRows)) {  // four lanes per manifold
                 if (diag)
                     hipLaunchKernelGGL(k_solve_color_quad<true>, grid_for_quads(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
                                        sp.friction, inertia, stride, w->vel.p, (uint32_t)w->n, apply_only, last, warm);
@@ -1245,10 +1233,10 @@ void launch_solver(phys_world* w, float dt) {
             }
             if (diag)
                 hipLaunchKernelGGL(k_solve_color<true>, grid_for_count(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
-                                   sp.friction, inertia, stride, w->vel.p, ablate, (uint32_t)w->n, apply_only, last, warm);
+                                   sp.friction, inertia, stride, w->vel.p, apply_only, last, warm);
             else
                 hipLaunchKernelGGL(k_solve_color<false>, grid_for_count(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
-                                   sp.friction, inertia, stride, w->vel.p, ablate, (uint32_t)w->n, apply_only, last, warm);
+                                   sp.friction, inertia, stride, w->vel.p, apply_only, last, warm);
         }
         PHYS_PROF(w, PHYS_STAGE_SOLVE_TAIL);
         if (diag)

@@ -8,6 +8,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -177,6 +178,21 @@ struct GridShape {
 
 // worlds alive per device in this process (abi.hip): two of them step on two streams, i.e. beside each other
 int worlds_on_device(int device);
+// PHYS_FLAG_EXCLUSIVE_GPU, no PHYS_FLAG_SHARED_GPU, no other world on the device: asked afresh at each use (abi.hip)
+bool gpu_is_exclusive(const phys_world* w);
+// PHYS_DEBUG_* switches, parsed once per process by the first debug_switches() (abi.hip). Unset: false / 0 / nullopt
+struct DebugSwitches {
+    bool no_cluster = false, cluster_dynamic = false, no_flow_preference = false, flow_stall = false;
+    std::optional<uint64_t> cluster_min, flow_max;
+    std::optional<int> clusters_per_cu;
+    uint64_t cluster_cap = 0, flow_quad_max = 0, ctab_slots = 0;
+    uint32_t flow_epoch = 0;
+    int np_threads = 0, pair_lanes = 0, brick_stage = 0;
+    std::optional<bool> flow_pipeline, np_early_probe;  // the value begins with '1'
+    std::optional<bool> color_kernel_lane;              // the value begins with 'l' (four lanes otherwise)
+    std::optional<bool> pair_kernel_brick;              // brick, unless the value is 'b' followed by anything but 'r'
+};
+const DebugSwitches& debug_switches();
 
 struct Constraint {
     uint32_t kind;  // 0 fix point, 1 fix orientation
@@ -291,7 +307,6 @@ struct phys_world {
     int cluster_cus = 0;                    // CUs of the device (dynamic planning)
     uint32_t cluster_age = 0;               // cluster steps since the homes were dealt out (dynamic: remade every kClusterDynamicPeriod)
     bool cluster_homes_valid = false;
-    uint64_t cluster_cap_limit = 0;         // PHYS_DEBUG_CLUSTER_CAP: fewer homes than the LDS would hold (tests)
     phys::DevBuf<uint32_t> active_flag, active_rank;  // n + 4 each: flag / exclusive rank in the broad phase's bucket order
     bool cluster_step = false;                      // this update's rows are in (cluster, colour) order
     phys::DevBuf<uint32_t> cluster_slot;   // body -> cluster * slots + slot

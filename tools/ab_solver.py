@@ -24,13 +24,7 @@ VARIANTS = {
     "nocluster": dict(NC),
     "cluster1": {"PHYS_DEBUG_CLUSTER_MIN": "0", "PHYS_DEBUG_CLUSTERS_PER_CU": "1"},
     "cluster3": {"PHYS_DEBUG_CLUSTER_MIN": "0", "PHYS_DEBUG_CLUSTERS_PER_CU": "3"},
-    "cl_nogran": {"PHYS_DEBUG_CLUSTER_MIN": "0", "PHYS_DEBUG_ABLATE": "8"},    # timing only: shared bodies treated as local
-    "cl_nocompute": {"PHYS_DEBUG_CLUSTER_MIN": "0", "PHYS_DEBUG_ABLATE": "2"},  # timing only
-    "cl_bare": {"PHYS_DEBUG_CLUSTER_MIN": "0", "PHYS_DEBUG_ABLATE": "10"},      # timing only: neither
     "default": {},
-    "cl_norot": {"PHYS_DEBUG_ABLATE": "16"},    # same bits: rows always start on wave 0
-    "cl_remass": {"PHYS_DEBUG_ABLATE": "32"},   # same bits: row masses remade in every iteration
-    "cl_norot_remass": {"PHYS_DEBUG_ABLATE": "48"},
     "cluster2": {"PHYS_DEBUG_CLUSTERS_PER_CU": "2"},
     "dyn": {"PHYS_DEBUG_CLUSTER_DYNAMIC": "1"},                                     # clusters remade every update
     "dyn_cap": {"PHYS_DEBUG_CLUSTER_DYNAMIC": "1", "PHYS_DEBUG_CLUSTER_CAP": "60000"},  # ... with homes for 60k bodies only
@@ -39,15 +33,6 @@ VARIANTS = {
     "pairs4": {"PHYS_DEBUG_PAIR_LANES": "4"},
     "pairs1": {"PHYS_DEBUG_PAIR_LANES": "1"},
     "np128": {"PHYS_DEBUG_NP_THREADS": "128"},
-    "np256": {"PHYS_DEBUG_NP_THREADS": "256"},
-    "no_ctab": {"PHYS_DEBUG_NO_CTAB": "1"},   # timing of the rows stage without the colour-table build (colours differ)
-    "cl_allcus": {"PHYS_DEBUG_CLUSTER_SPARE": "0"},
-    "cl_spare16": {"PHYS_DEBUG_CLUSTER_SPARE": "16"},
-    # timing diagnosis of the one-lane per-colour kernel (results are WRONG by construction: hashes differ)
-    "nogather": dict(NC, PHYS_DEBUG_COLOR_KERNEL="lane", PHYS_DEBUG_FLOW_MAX="0", PHYS_DEBUG_ABLATE="1"),
-    "nocompute": dict(NC, PHYS_DEBUG_COLOR_KERNEL="lane", PHYS_DEBUG_FLOW_MAX="0", PHYS_DEBUG_ABLATE="2"),
-    "nostore": dict(NC, PHYS_DEBUG_COLOR_KERNEL="lane", PHYS_DEBUG_FLOW_MAX="0", PHYS_DEBUG_ABLATE="4"),
-    "loadonly": dict(NC, PHYS_DEBUG_COLOR_KERNEL="lane", PHYS_DEBUG_FLOW_MAX="0", PHYS_DEBUG_ABLATE="7"),
 }
 
 
