@@ -207,6 +207,42 @@ int32_t phys_get_stats(phys_world* w, phys_stats* out);
 /* manifolds per solver colour of the last update (64 entries) */
 int32_t phys_get_color_counts(phys_world* w, uint32_t* counts_out /*64*/);
 
+/* --- ray casts against the current poses (new: the reference has no queries) ---
+ * The closest hit of every ray against the CURRENT poses: the state after the last update, phys_set_bodies or write
+ * through phys_get_device_view. Read-only: the call builds a grid of its own from those poses and leaves every buffer,
+ * counter and flag of the update untouched, so updates stay bit-identical with or without ray casts in between. Works in
+ * every world, with or without PHYS_FLAG_COLLISIONS / PHYS_FLAG_BROADPHASE_ONLY; it neither reports nor clears the
+ * sticky update errors (only phys_sync does).
+ *   - dir need not be unit length: t is the Euclidean distance along dir / |dir|, and a hit counts when t <= max_t
+ *     (max_t NULL = +inf). A zero, NaN or infinite dir or origin, or a NaN or negative max_t, gives a miss.
+ *   - a miss: body = PHYS_RAY_MISS, t = +inf, normal = 0.
+ *   - targets: owned bodies only (ids < phys_stats.n_bodies; ghost slots of sharded worlds are never hit: in a sharded
+ *     world each rank answers for the bodies it owns and the caller merges the ranks' answers by least t), and of those
+ *     SPHERE (radius half_extent[0]) and BOX (the oriented box of rot and half_extent); PHYS_SHAPE_NONE bodies and bodies
+ *     with a non-finite pose are never hit. With PHYS_FLAG_GROUND_PLANE, the solid half-space y <= ground_height.
+ *   - an origin inside the closed solid of a target: t = 0, normal = -dir / |dir|. Otherwise normal is the outward unit
+ *     surface normal at the hit point (a box: the face of the slab the ray enters last).
+ *   - ignore_body[i] (NULL = none), when below n_bodies, is skipped by ray i (a ray fired from inside a body); a value
+ *     at or above n_bodies ignores nothing.
+ *   - the result is the least (t, id): an exact tie in t goes to the smaller id, and the ground loses ties to bodies. A
+ *     ray's result depends only on that ray and the world state: bit-identical across calls and ray orders.
+ *   - no bodies: every ray misses or hits the ground. n_rays == 0 is a no-op.
+ *   - PHYS_ERR_INVALID_ARG: a NULL origin, dir, body_out or t_out, or n_rays >= 2^31.
+ * Grid: e = the largest exact AABB edge of the bodies above, M = the largest |coordinate| of
+ * their bounds [lo, hi], pad p = 2^-16 (M + e), cell edge (e + 2p)(1 + 2^-10) - coarser if the padded bounds would span
+ * more than 2^20 cells along an axis - with cell corners at lo - p + k * cell. The cell edge follows the largest body:
+ * one huge body coarsens the grid, and far-flung bodies mean long walks through empty cells. Results stay correct in
+ * both cases; only speed suffers. */
+#define PHYS_RAY_MISS 0xFFFFFFFEu   /* no hit within max_t */
+#define PHYS_RAY_GROUND 0xFFFFFFFFu /* the ground plane (same id the manifolds use for it) */
+/* host arrays; synchronous (returns with the outputs written) */
+int32_t phys_raycast(phys_world* w, uint64_t n_rays, const float* origin /*3n*/, const float* dir /*3n*/,
+                     const float* max_t /*n, NULL = +inf*/, const uint32_t* ignore_body /*n, NULL = none*/,
+                     uint32_t* body_out /*n*/, float* t_out /*n*/, float* normal_out /*3n, may be NULL*/);
+/* the same on DEVICE pointers: only enqueues on the world's stream (phys_device_view.stream), no host synchronisation */
+int32_t phys_raycast_device(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
+                            const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out);
+
 /* --- per-stage device timing (HIP events on the world's stream), for bench.py's roofline --- */
 #define PHYS_STAGE_STEP_FULL 0u     /* gravity + RigidBody::step, one kernel (no collisions) */
 #define PHYS_STAGE_VELOCITY_AABB 1u /* gravity + velocity half + AABB */

@@ -162,6 +162,28 @@ class PhysicsState {  // physics.rs:25-31
         if (!m.empty()) check(phys_get_instance_matrices(w_, &m[0][0]));
         return m;
     }
+    // closest hit per ray against the entities as they are now (phys_raycast): body index, PHYS_RAY_MISS or
+    // PHYS_RAY_GROUND; t = +inf on a miss; max_t / ignore_body may be empty (none)
+    struct RayHit { uint32_t body; float t; Vector3 normal; };
+    std::vector<RayHit> raycast(const std::vector<Vector3>& origins, const std::vector<Vector3>& dirs,
+                                const std::vector<float>& max_t = {}, const std::vector<uint32_t>& ignore_body = {}) {
+        if (origins.size() != dirs.size() || (!max_t.empty() && max_t.size() != origins.size()) ||
+            (!ignore_body.empty() && ignore_body.size() != origins.size()))
+            throw Panic(PHYS_ERR_INVALID_ARG, "raycast: array lengths differ");
+        push();
+        const size_t n = origins.size();
+        std::vector<float> o(3 * n), d(3 * n), t(n), nrm(3 * n);
+        std::vector<uint32_t> body(n);
+        for (size_t i = 0; i < n; ++i) {
+            o[3 * i] = origins[i].x; o[3 * i + 1] = origins[i].y; o[3 * i + 2] = origins[i].z;
+            d[3 * i] = dirs[i].x; d[3 * i + 1] = dirs[i].y; d[3 * i + 2] = dirs[i].z;
+        }
+        if (n) check(phys_raycast(w_, n, o.data(), d.data(), max_t.empty() ? nullptr : max_t.data(),
+                                  ignore_body.empty() ? nullptr : ignore_body.data(), body.data(), t.data(), nrm.data()));
+        std::vector<RayHit> out(n);
+        for (size_t i = 0; i < n; ++i) out[i] = RayHit{body[i], t[i], Vector3(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2])};
+        return out;
+    }
     phys_world* raw() { return w_; }
 
   private:

@@ -24,6 +24,8 @@ FLAG_SOLVER_CLUSTER = 64
 FLAG_EXCLUSIVE_GPU = 128
 FLAG_NO_WARM_START = 256
 GROUND_ID = 0xFFFFFFFF
+RAY_MISS = 0xFFFFFFFE    # PHYS_RAY_MISS: no hit within max_t
+RAY_GROUND = 0xFFFFFFFF  # PHYS_RAY_GROUND: the ground plane
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -157,6 +159,9 @@ PROTOTYPES = {
     "phys_get_manifolds": (C.c_int32, [C.c_void_p, u32p, u32p, f32p, f32p, C.c_uint64, u64p]),
     "phys_get_stats": (C.c_int32, [C.c_void_p, C.POINTER(PhysStats)]),
     "phys_get_color_counts": (C.c_int32, [C.c_void_p, u32p]),
+    "phys_raycast": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, u32p, u32p, f32p, f32p]),
+    "phys_raycast_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "phys_profile_enable": (C.c_int32, [C.c_void_p, C.c_int32]),
     "phys_profile_get": (C.c_int32, [C.c_void_p, C.POINTER(PhysProfile)]),
     "phys_get_device_view": (C.c_int32, [C.c_void_p, C.POINTER(PhysDeviceView)]),

@@ -131,6 +131,7 @@ const DebugSwitches& debug_switches() {
         s.pair_lanes = debug_env("PHYS_DEBUG_PAIR_LANES", atoi).value_or(0);
         s.pair_kernel_brick = debug_env("PHYS_DEBUG_PAIR_KERNEL", [](const char* v) { return v[0] != 'b' || v[1] == 'r'; });
         s.brick_stage = debug_env("PHYS_DEBUG_BRICK_STAGE", atoi).value_or(0);
+        s.raycast_stats = debug_set("PHYS_DEBUG_RAYCAST_STATS");
         return s;
     }();
     return d;
@@ -218,17 +219,18 @@ int32_t phys_destroy(phys_world* w) {
     DevBuf<float>* fb[] = {&w->pos, &w->rot, &w->vel, &w->force, &w->torque, &w->inv_inertia_diag,
                            &w->inv_inertia, &w->half_extent, &w->aabb, &w->cg_x, &w->cg_r, &w->cg_p, &w->cg_ap,
                            &w->cg_rhs, &w->cg_c, &w->cg_scratch, &w->cg_jl, &w->geo, &w->man_geo_prev, &w->man_imp, &w->man_imp_prev, &w->man_geo, &w->row_n,
-                           &w->row_pt, &w->row_tb, &w->row_acc, &w->row_all, &w->flow_vel, &w->sorted_box, &w->slot_box};
+                           &w->row_pt, &w->row_tb, &w->row_acc, &w->row_all, &w->flow_vel, &w->sorted_box, &w->slot_box, &w->rc_records, &w->rc_in, &w->rc_out};
     for (auto* b : fb) b->free();
     DevBuf<uint32_t>* ub[] = {&w->shape, &w->global_id, &w->cg_status, &w->bucket_of, &w->bucket_count,
                               &w->bucket_start, &w->bucket_cursor, &w->sorted_ids, &w->slot_ids, &w->grid_ovf, &w->scan_block_sums, &w->pairs,
                               &w->man_a, &w->man_b, &w->man_color, &w->row_hdr, &w->halo_block_counts,
                               &w->man_prev, &w->cluster_slot, &w->cluster_body, &w->body_shared, &w->active_flag, &w->active_rank, &w->seg_count, &w->seg_start, &w->man_rank,
-                              &w->row_src, &w->cross_pairs, &w->color_block_hist, &w->cg_cols};
+                              &w->row_src, &w->cross_pairs, &w->color_block_hist, &w->cg_cols,
+                              &w->rc_header, &w->rc_count, &w->rc_start, &w->rc_tile_sum};
     for (auto* b : ub) b->free();
     w->man_prio.free(); w->color_state.free(); w->bucket_count.free(); w->step_zero.free();
     w->d_constraints.free(); w->counters.free();
-    w->ctab.free(); w->unc_list.free();
+    w->ctab.free(); w->unc_list.free(); w->rc_stats.free();
     w->prof.destroy();
     for (int k = 0; k < phys_world::kSnapRing; ++k) {
         if (w->h_snap[k]) (void)hipHostFree(w->h_snap[k]);
@@ -689,6 +691,49 @@ int32_t phys_get_device_view(phys_world* w, phys_device_view* out) {
     out->stream = (void*)w->stream;
     out->vel_stride = 8;
     return PHYS_OK;
+}
+
+static int32_t raycast_args(uint64_t n_rays, const float* origin, const float* dir, const uint32_t* body_out, const float* t_out) {
+    if (n_rays >= (1ull << 31)) return fail(PHYS_ERR_INVALID_ARG, "phys_raycast: n_rays must be below 2^31");
+    if (n_rays && (!origin || !dir || !body_out || !t_out)) return fail(PHYS_ERR_INVALID_ARG, "phys_raycast: null origin, dir, body_out or t_out");
+    return PHYS_OK;
+}
+
+int32_t phys_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
+                     const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
+    ENTER(w);
+    int32_t rc = raycast_args(n_rays, origin, dir, body_out, t_out); if (rc) return rc;
+    if (n_rays == 0) return PHYS_OK;
+    // staging: in = origin 3n | dir 3n | max_t n | ignore n, out = t n | body n | normal 3n (all 4-byte words)
+    const size_t n = (size_t)n_rays;
+    PHYS_HIP_TRY(w->rc_in.resize(8 * n));
+    PHYS_HIP_TRY(w->rc_out.resize(5 * n));
+    hipStream_t s = w->stream;
+    float* d_origin = w->rc_in.p;
+    float* d_dir = d_origin + 3 * n;
+    float* d_max_t = max_t ? d_dir + 3 * n : nullptr;
+    uint32_t* d_ignore = ignore_body ? reinterpret_cast<uint32_t*>(d_dir + 4 * n) : nullptr;
+    float* d_t = w->rc_out.p;
+    uint32_t* d_body = reinterpret_cast<uint32_t*>(d_t + n);
+    float* d_normal = normal_out ? d_t + 2 * n : nullptr;
+    PHYS_HIP_TRY(hipMemcpyAsync(d_origin, origin, 12 * n, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(d_dir, dir, 12 * n, hipMemcpyHostToDevice, s));
+    if (d_max_t) PHYS_HIP_TRY(hipMemcpyAsync(d_max_t, max_t, 4 * n, hipMemcpyHostToDevice, s));
+    if (d_ignore) PHYS_HIP_TRY(hipMemcpyAsync(d_ignore, ignore_body, 4 * n, hipMemcpyHostToDevice, s));
+    rc = launch_raycast(w, n_rays, d_origin, d_dir, d_max_t, d_ignore, d_body, d_t, d_normal); if (rc) return rc;
+    rc = d2h(w, body_out, d_body, 4 * n); if (rc) return rc;
+    rc = d2h(w, t_out, d_t, 4 * n); if (rc) return rc;
+    if (normal_out) { rc = d2h(w, normal_out, d_normal, 12 * n); if (rc) return rc; }
+    PHYS_HIP_TRY(hipStreamSynchronize(s));
+    return PHYS_OK;
+}
+
+int32_t phys_raycast_device(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
+                            const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
+    ENTER(w);
+    int32_t rc = raycast_args(n_rays, origin, dir, body_out, t_out); if (rc) return rc;
+    if (n_rays == 0) return PHYS_OK;
+    return launch_raycast(w, n_rays, origin, dir, max_t, ignore_body, body_out, t_out, normal_out);
 }
 
 int32_t phys_set_global_ids(phys_world* w, const uint32_t* global_ids) {

@@ -219,6 +219,10 @@ bool cluster_plan_dynamic(phys_world* w);  // cluster.hip: clusters / slots of t
 void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float friction, const float* inertia, uint32_t stride,
                           bool diag, long long timeout_ticks);
 
+// raycast.hip: builds the query's grid from the current poses and traces the rays (device pointers), all on w->stream
+int32_t launch_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
+                       const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out);
+
 int32_t halo_pack_bodies(phys_world* w, void* dev_out, uint64_t cap);
 int32_t halo_pack_bodies_faces(phys_world* w, void* dev_out, uint64_t cap, float x_lo, float x_hi);
 int32_t halo_unpack_ghosts(phys_world* w, const void* dev_records, uint64_t n_records, uint64_t skip_first, uint64_t skip_count);

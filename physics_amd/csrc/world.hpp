@@ -188,6 +188,7 @@ struct DebugSwitches {
     uint64_t cluster_cap = 0, flow_quad_max = 0, ctab_slots = 0;
     uint32_t flow_epoch = 0;
     int np_threads = 0, pair_lanes = 0, brick_stage = 0;
+    bool raycast_stats = false;  // PHYS_DEBUG_RAYCAST_STATS: phys_raycast counts the cells and candidates its rays visit (stderr)
     std::optional<bool> flow_pipeline, np_early_probe;  // the value begins with '1'
     std::optional<bool> color_kernel_lane;              // the value begins with 'l' (four lanes otherwise)
     std::optional<bool> pair_kernel_brick;              // brick, unless the value is 'b' followed by anything but 'r'
@@ -318,6 +319,15 @@ struct phys_world {
     phys::DevBuf<uint32_t> seg_count, seg_start;  // rows per (cluster, colour) - kept behind body_shared, seg_count itself is unused - and their exclusive scan
     phys::DevBuf<uint32_t> man_rank;       // manifold -> arrival rank inside its segment
     uint32_t flow_epoch = 0;         // solves since the buffers were cleared (upper half of every tag)
+    // ray-cast query (raycast.hip): its own grid, rebuilt from the current poses by every call; nothing an update reads
+    phys::DevBuf<uint32_t> rc_header;    // scene bounds and largest AABB edge (order-preserving keys)
+    phys::DevBuf<uint32_t> rc_count;     // insertions per bucket (left zeroed by the scatter)
+    phys::DevBuf<uint32_t> rc_start;     // table + 1: exclusive scan of rc_count
+    phys::DevBuf<uint32_t> rc_tile_sum;  // the scan's own scratch (scan_block_sums is the update's)
+    phys::DevBuf<float> rc_records;      // 8N records of 48 bytes {centre, shape} {rot} {half extent, id}, bucket order
+    phys::DevBuf<float> rc_in;           // phys_raycast (host arrays): staged origin | dir | max_t | ignore (as u32 bits)
+    phys::DevBuf<float> rc_out;          // ... and the outputs body | t | normal
+    phys::DevBuf<unsigned long long> rc_stats;  // PHYS_DEBUG_RAYCAST_STATS: cells, candidates
     // multi-GPU halo
     phys::DevBuf<uint32_t> cross_pairs;
     uint64_t max_cross_pairs = 0;

@@ -172,6 +172,12 @@ class PhysicsState:
         lam = self._world.get_lambda()
         return lam if len(lam) else None
 
+    def raycast(self, origins, dirs, max_t=None, ignore=None):
+        """Closest hit per ray against the entities as they are now (World.raycast): (body index or RAY_MISS /
+        RAY_GROUND, t, normal)."""
+        self._push()
+        return self._world.raycast(origins, dirs, max_t, ignore)
+
     def instance_matrices(self):  # what get_render_data feeds the renderer (physics.rs:61-69)
         self._push()
         return self._world.get_instance_matrices()

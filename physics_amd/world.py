@@ -158,6 +158,44 @@ class World:
         self._ck(self.lib.phys_get_aabbs(self.h, _p(out)))
         return out
 
+    def raycast(self, origins, dirs, max_t=None, ignore=None):
+        """Closest hit of every ray against the current poses (phys_raycast): origins / dirs (n, 3), max_t (n,) or None
+        (= +inf), ignore (n,) body ids or None. Returns (body u32[n], t f32[n], normal f32[n, 3]); a miss is
+        (RAY_MISS, +inf, 0), the ground RAY_GROUND."""
+        o = _f(origins).reshape(-1, 3)
+        d = _f(dirs).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError("origins and dirs differ in length")
+        mt = None if max_t is None else _f(max_t).reshape(-1)
+        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.uint32).reshape(-1)
+        for a in (mt, ig):
+            if a is not None and a.size != n:
+                raise ValueError("max_t / ignore do not match the ray count")
+        body = np.empty(n, np.uint32)
+        t = np.empty(n, np.float32)
+        normal = np.empty((n, 3), np.float32)
+        if n:
+            self._ck(self.lib.phys_raycast(self.h, n, _p(o), _p(d), _p(mt), _p(ig, u32p), _p(body, u32p), _p(t), _p(normal)))
+        return body, t, normal
+
+    def raycast_device(self, origins, dirs, body_out, t_out, normal_out=None, max_t=None, ignore=None):
+        """phys_raycast_device on contiguous torch tensors of the world's device: origins / dirs float32 (n, 3), body_out
+        int32 or uint32 (n,), t_out float32 (n,), normal_out float32 (n, 3) or None, max_t float32 (n,) or None, ignore
+        int32 / uint32 (n,) or None. Only enqueues on the world's stream (device_view().stream): order other streams'
+        work against it yourself."""
+        n = int(origins.shape[0])
+        args = []
+        for name, x, cols in (("origins", origins, 3), ("dirs", dirs, 3), ("max_t", max_t, 1), ("ignore", ignore, 1),
+                              ("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3)):
+            if x is None:
+                args.append(None)
+                continue
+            if not x.is_cuda or not x.is_contiguous() or x.numel() != n * cols or x.element_size() != 4:
+                raise ValueError(f"{name}: needs a contiguous 4-byte device tensor of {n} x {cols}")
+            args.append(C.c_void_p(x.data_ptr()))
+        self._ck(self.lib.phys_raycast_device(self.h, n, *args))
+
     def get_manifolds(self):
         n = C.c_uint64()
         self._ck(self.lib.phys_get_manifolds(self.h, None, None, None, None, 0, C.byref(n)))

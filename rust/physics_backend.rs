@@ -92,6 +92,25 @@ impl HipBackend {
         }
     }
 
+    /// Closest hit of every ray against the bodies as the last update left them (phys_raycast): per ray the entity
+    /// index, or None for a miss / Some(u32::MAX) = ffi::PHYS_RAY_GROUND for the ground, with t and the surface normal.
+    /// `max_t` and `ignore` are optional per-ray slices of the same length as `origins`.
+    pub fn raycast(&self, origins: &[[f32; 3]], dirs: &[[f32; 3]], max_t: Option<&[f32]>, ignore: Option<&[u32]>)
+                   -> Vec<(Option<u32>, f32, [f32; 3])> {
+        let n = origins.len();
+        assert_eq!(dirs.len(), n);
+        assert!(max_t.map_or(true, |m| m.len() == n) && ignore.map_or(true, |g| g.len() == n));
+        let (mut body, mut t, mut normal) = (vec![0u32; n], vec![0f32; n], vec![[0f32; 3]; n]);
+        if n > 0 {
+            unsafe {
+                check(ffi::phys_raycast(self.world, n as u64, origins.as_ptr() as *const f32, dirs.as_ptr() as *const f32,
+                                        max_t.map_or(std::ptr::null(), |m| m.as_ptr()), ignore.map_or(std::ptr::null(), |g| g.as_ptr()),
+                                        body.as_mut_ptr(), t.as_mut_ptr(), normal.as_mut_ptr() as *mut f32));
+            }
+        }
+        (0..n).map(|i| (if body[i] == ffi::PHYS_RAY_MISS { None } else { Some(body[i]) }, t[i], normal[i])).collect()
+    }
+
     /// PhysicsState::update (physics.rs:41-55). `dirty` = the caller touched entities/constraints since the
     /// last frame (lib.rs does at start-up only); when false the bodies stay resident on the GPU.
     pub fn update(&mut self, state: &mut PhysicsState, dt: &Duration, dirty: bool) {

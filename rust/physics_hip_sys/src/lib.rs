@@ -20,6 +20,8 @@ pub const PHYS_FLAG_SHARED_GPU: u32 = 0x20;
 pub const PHYS_FLAG_SOLVER_CLUSTER: u32 = 0x40;
 pub const PHYS_FLAG_EXCLUSIVE_GPU: u32 = 0x80;
 pub const PHYS_FLAG_NO_WARM_START: u32 = 0x100;
+pub const PHYS_RAY_MISS: u32 = 0xFFFF_FFFE;
+pub const PHYS_RAY_GROUND: u32 = 0xFFFF_FFFF;
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -134,6 +136,10 @@ extern "C" {
                               points_out: *mut f32, cap: u64, n_manifolds: *mut u64) -> i32;
     pub fn phys_get_stats(w: *mut phys_world, out: *mut phys_stats) -> i32;
     pub fn phys_get_color_counts(w: *mut phys_world, counts_out: *mut u32) -> i32;
+    pub fn phys_raycast(w: *mut phys_world, n_rays: u64, origin: *const f32, dir: *const f32, max_t: *const f32,
+                        ignore_body: *const u32, body_out: *mut u32, t_out: *mut f32, normal_out: *mut f32) -> i32;
+    pub fn phys_raycast_device(w: *mut phys_world, n_rays: u64, origin: *const f32, dir: *const f32, max_t: *const f32,
+                               ignore_body: *const u32, body_out: *mut u32, t_out: *mut f32, normal_out: *mut f32) -> i32;
     pub fn phys_profile_enable(w: *mut phys_world, on: i32) -> i32;
     pub fn phys_profile_get(w: *mut phys_world, out: *mut phys_profile) -> i32;
     pub fn phys_get_device_view(w: *mut phys_world, out: *mut phys_device_view) -> i32;
