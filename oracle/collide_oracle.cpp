@@ -184,6 +184,7 @@ void CollisionWorld::color_manifolds(size_t n_bodies, bool persistent) {
             --remaining;
         }
     }
+    n_new_manifolds = (uint32_t)remaining;
     std::vector<size_t> winners;
     while (remaining > 0) {
         std::fill(top.begin(), top.end(), 0ull);
@@ -310,7 +311,7 @@ void CollisionWorld::remember_impulses(const std::vector<solver_manifold_t>& row
 void CollisionWorld::collide_and_solve(std::vector<RigidBody>& bodies, float dt) {
     compute_aabbs(bodies);
     broadphase_grid();
-    if (flags & PHYS_FLAG_BROADPHASE_ONLY) { manifolds.clear(); color.clear(); n_colors = 0; n_contacts = 0; return; }
+    if (flags & PHYS_FLAG_BROADPHASE_ONLY) { manifolds.clear(); color.clear(); n_colors = 0; n_new_manifolds = 0; n_contacts = 0; return; }
     narrowphase(bodies);
     color_manifolds(bodies.size(), true);
     solve(bodies, dt);

@@ -40,6 +40,7 @@ struct CollisionWorld {
     std::vector<Manifold> manifolds;
     std::vector<uint32_t> color;
     uint32_t n_colors = 0, color_rounds = 0;
+    uint32_t n_new_manifolds = 0;  // manifolds that kept no colour in this update
     uint64_t n_contacts = 0;
 
     void configure(const phys_config& cfg);

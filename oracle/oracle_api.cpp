@@ -211,6 +211,7 @@ int32_t oracle_get_stats(oracle_world* w, phys_stats* out) {
     out->n_contacts = w->col.n_contacts;
     out->n_colors = w->col.n_colors;
     out->color_rounds = w->col.color_rounds;
+    out->n_new_manifolds = w->col.n_new_manifolds;
     out->cg_iterations = w->state.last_cg_iterations;
     out->cg_converged = w->state.last_cg_converged ? 1 : 0;
     out->steps = w->steps;

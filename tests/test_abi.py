@@ -94,12 +94,18 @@ def test_product_code_never_touches_the_oracle():
 
 
 def test_independent_gpu_checks_share_no_code_with_the_spec_or_the_oracle():
-    """tests/test_gpu_independent.py is the one place where the collision arithmetic is checked against something
-    that is NOT compiled from include/spec: it may import numpy, pytest and the product's Python host, nothing else."""
-    txt = open(os.path.join(ROOT, "tests", "test_gpu_independent.py")).read()
-    mods = set(re.findall(r"^\s*(?:from|import)\s+([A-Za-z0-9_\.]+)", txt, flags=re.M))
-    assert mods <= {"numpy", "pytest", "physics_amd"}, mods
-    assert "liboracle" not in txt and "include/spec" not in txt.split('"""')[2]
+    """tests/test_gpu_independent.py and tests/test_gpu_solver_independent.py are where the collision and solver
+    arithmetic is checked against something that is NOT compiled from include/spec: they may import numpy, pytest and
+    the product's Python host, and the second one also tests/contact_ref.py - which itself imports numpy only."""
+    imports = r"^\s*(?:from|import)\s+([A-Za-z0-9_\.]+)"
+    for name, extra in (("test_gpu_independent.py", set()), ("test_gpu_solver_independent.py", {"contact_ref"})):
+        txt = open(os.path.join(ROOT, "tests", name)).read()
+        mods = set(re.findall(imports, txt, flags=re.M))
+        assert mods <= {"numpy", "pytest", "physics_amd"} | extra, (name, mods)
+        assert "liboracle" not in txt and "include/spec" not in txt.split('"""')[2], name
+    txt = open(os.path.join(ROOT, "tests", "contact_ref.py")).read()
+    assert set(re.findall(imports, txt, flags=re.M)) == {"numpy"}
+    assert "liboracle" not in txt and "oracle" not in txt.split('"""', 2)[2]
 
 
 def test_rust_shim_declares_every_header_symbol_once():

@@ -1,0 +1,247 @@
+"""GPU: the contact solver's friction rows, warm starting, colour order and non-default parameters against the float64
+reference of tests/contact_ref.py, which shares no code with include/spec, the oracle or the kernels (tests/test_abi.py
+checks that). Every update is checked from the device's own read-back poses and velocities; the reference carries its
+own float64 impulses from update to update. Each test asserts from profile_get() which solver stage ran.
+
+Tolerances come from tests/test_contact_ref_cpu.py, which measures the same float32-against-float64 spread on the CPU
+oracle (bit-equal to the device on every solver path): at most 2.3e-6 on isolated manifolds, 3.9e-6 on coupled piles,
+5.1e-7 on the C5(16, 130, 16) tower."""
+import numpy as np
+import pytest
+
+import contact_ref as cr
+
+pytestmark = pytest.mark.gpu
+DT = 16_666_667
+DT_S = float(np.float32(np.float32(DT) / np.float32(1e9)))
+GRAVITY = np.array([0.0, -9.81, 0.0])
+TOL_ISOLATED = 1e-5  # measured at most 2.3e-6 (test_contact_ref_cpu: friction pairs, six warm-started updates)
+TOL_COUPLED = 2e-5   # measured at most 3.9e-6 (random heap; C3 over 130 updates 3.4e-6)
+TOL_TOWER = 5e-6     # measured 5.1e-7 (test_cluster_tower_against_the_oracle), x 10
+SOLVER_STAGES = {"solve", "solve_tail", "solve_flow", "solve_cluster"}
+PER_COLOR = {"solve", "solve_tail"}
+
+
+def flags_of(solver):
+    import physics_amd
+    return {"default": 0, "per_color": physics_amd.FLAG_SOLVER_PER_COLOR}[solver]
+
+
+def check_stages(stages, solver):
+    """The device picks its kernels itself; default flags on these scenes take the dataflow kernels from the first
+    update on, PHYS_FLAG_SOLVER_PER_COLOR a launch per colour (colours of more than 512 manifolds: `solve`)."""
+    if solver == "per_color":
+        assert "solve" in stages and stages <= PER_COLOR, stages
+    else:
+        assert stages == {"solve_flow"}, stages
+ALT = dict(baumgarte=0.35, slop=0.003, friction=0.9, max_bias=1.25)
+
+
+def make_world(bodies, flags=0, gravity=(0, 0, 0), **cfg):
+    import physics_amd
+    w = physics_amd.World(physics_amd.default_config(flags=physics_amd.FLAG_COLLISIONS | physics_amd.FLAG_GROUND_PLANE | flags,
+                                                     gravity_force=gravity, gravity_offset=(0, 0, 0), **cfg))
+    w.set_bodies(**bodies)
+    return w
+
+
+def checked_updates(w, ref, n_updates, inv_m, inv_I, force=None, cold=None):
+    """Per update: (reference output, device velocities, solver stages that ran[, cold reference output]). Both
+    references start from the device's poses and velocities of that update."""
+    for _ in range(n_updates):
+        pos, _ = w.get_transforms()
+        lin, ang = w.get_velocities()
+        w.profile_enable(True)
+        w.update(DT)
+        w.sync()
+        stages = set(w.profile_get()[0]) & SOLVER_STAGES
+        man = w.get_manifolds()
+        lin1, ang1 = w.get_velocities()
+        out = ref.update(man, pos, lin, ang, inv_m, inv_I, force)
+        extra = (cold.update(man, pos, lin, ang, inv_m, inv_I, force),) if cold is not None else ()
+        yield (out, lin1, ang1, stages) + extra
+
+
+# ---------------------------------------------------------------- (a) friction engaged, isolated manifolds
+@pytest.mark.parametrize("solver", ["default", "per_color"])
+@pytest.mark.parametrize("params", [{}, ALT], ids=["defaults", "baumgarte.35_slop.003_mu.9_cap1.25"])
+@pytest.mark.parametrize("iterations", [2, 8])
+@pytest.mark.parametrize("inertia", ["identity", "diag", "full"])
+def test_friction_rows_of_isolated_manifolds(inertia, iterations, params, solver):
+    """Box on box, sphere on box and box on the ground, sliding at 0 to 6 units/s: friction ends at the +-mu pn box for
+    some rows and inside it for others. One update from set_bodies, through the dataflow and the per-colour kernels."""
+    bodies = cr.friction_pairs(3, 150, inertia)
+    n = len(bodies["pos"])
+    w = make_world(bodies, flags=flags_of(solver), solver_iterations=iterations, **params)
+    ref = cr.SolverRef(n, cr.Params(DT_S, **params), iterations)
+    out, lin1, ang1, stages = next(checked_updates(w, ref, 1, *cr.body_inverses(n, bodies["mass"], bodies["inertia"])))
+    check_stages(stages, solver)
+    assert len(out["a"]) == 450
+    clamped, inside = cr.friction_row_states(out, params.get("friction", 0.5))
+    assert clamped >= 0.2 * (clamped + inside) and inside >= 0.2 * (clamped + inside), (clamped, inside)
+    # depths from -0.015 to 0.09: speculative points and points within the slop always occur; the cap binds for the
+    # non-default set (at depth > 0.0625; the default cap of 3 would need 0.26)
+    depth = np.asarray(w.get_manifolds()[3])[:, :, 3]
+    p = cr.Params(DT_S, **params)
+    act = np.arange(4)[None, :] < out["count"][:, None]
+    assert (act & (depth > 0) & (depth <= p.slop)).sum() > 20 and (act & (depth < 0)).sum() > 20
+    if params:
+        assert (act & (cr.contact_bias(depth, p) == p.max_bias)).sum() > 20
+    err, amb = cr.velocity_error(out, lin1, ang1)
+    print(f"\n{inertia} it={iterations} {params or 'defaults'} {solver} [{sorted(stages)}]: error {err:.3g} (tolerance {TOL_ISOLATED}), {amb} ambiguous")
+    assert amb <= 2
+    assert err < TOL_ISOLATED
+
+
+# ---------------------------------------------------------------- (b) warm starting
+@pytest.mark.parametrize("mode", ["default", "per_color", "no_warm_start"])
+def test_warm_started_updates_of_isolated_manifolds(mode):
+    """Six consecutive updates of 900 isolated manifolds, two iterations each. Default flags: the dataflow kernels; per
+    colour: colour 0 holds 900 > 512 manifolds and gets launches of its own; no warm start: against a cold reference.
+    Negative control: with warm starting the device does NOT match the cold reference where the carried impulses are
+    large (the warm path is live)."""
+    import physics_amd
+    flags = {"default": 0, "per_color": physics_amd.FLAG_SOLVER_PER_COLOR, "no_warm_start": physics_amd.FLAG_NO_WARM_START}[mode]
+    bodies = cr.friction_pairs(4, 300, "full")
+    n = len(bodies["pos"])
+    # two iterations: eight all but converge on an isolated manifold, from any start, and warm and cold would agree
+    w = make_world(bodies, flags=flags, solver_iterations=2)
+    warm = mode != "no_warm_start"
+    ref = cr.SolverRef(n, cr.Params(DT_S), 2, warm=warm)
+    cold = cr.SolverRef(n, cr.Params(DT_S), 2, warm=False) if warm else None
+    worst, n_amb, live, carried, off = 0.0, 0, 0, 0, 0.0
+    for u, res in enumerate(checked_updates(w, ref, 6, *cr.body_inverses(n, bodies["mass"], bodies["inertia"]), cold=cold)):
+        out, lin1, ang1, stages = res[:4]
+        err, amb = cr.velocity_error(out, lin1, ang1)
+        worst, n_amb = max(worst, err), n_amb + amb
+        check_stages(stages, "per_color" if mode == "per_color" else "default")
+        if warm and u > 0:
+            big = np.flatnonzero((np.abs(out["P0"][:, :, 2]) > 0.05).any(1) & ~out["ambiguous"])
+            carried += len(big)
+            c = res[4]
+            for m in big:
+                a, b = out["a"][m], out["b"][m]
+                bodies_m = [a] if b == cr.GROUND else [a, b]
+                d = max(np.abs(lin1[bodies_m] - c["lin"][bodies_m]).max(), np.abs(ang1[bodies_m] - c["ang"][bodies_m]).max())
+                live += d > 10 * TOL_ISOLATED
+                off = max(off, d)
+    print(f"\nwarm start {mode}: error {worst:.3g} (tolerance {TOL_ISOLATED}), {n_amb} ambiguous; "
+          f"{live} of {carried} manifolds with large carried impulses differ from the cold solve (up to {off:.3g})")
+    assert n_amb <= 0.01 * 900 * 6
+    assert worst < TOL_ISOLATED
+    if warm:
+        assert carried > 500 and live >= 0.3 * carried and off > 1000 * TOL_ISOLATED
+
+
+@pytest.mark.parametrize("case", ["turn3", "turn1", "cross"])
+def test_warm_start_follows_turning_normals(case):
+    """Sphere on a heavy spinning box: the normal turns 3 degrees per update (beyond the 2.56 degrees of 0.999: nothing
+    carried), 1 degree (carried), or 1 degree across |n.x| = 0.57735 (the normal impulse carried, friction not: the
+    tangent basis switches branch)."""
+    start, turn = {"turn3": ((0.0, 20.0), 3.0), "turn1": ((0.0, 20.0), 1.0), "cross": ((33.0, 34.8), 1.0)}[case]
+    import physics_amd
+    bodies = cr.spinning_pairs(8, 400, turn, start, DT_S)
+    n = len(bodies["pos"])
+    w = make_world(bodies, flags=physics_amd.FLAG_EXACT_ROTATION)  # (quirk Q1 would turn the box by sin(w dt / 2) only)
+    ref = cr.SolverRef(n, cr.Params(DT_S), 8)
+    worst, n_amb, with_pn, with_pt, switched = 0.0, 0, 0, 0, 0
+    for u, (out, lin1, ang1, stages) in enumerate(checked_updates(w, ref, 6, *cr.body_inverses(n, bodies["mass"], bodies["inertia"]))):
+        err, amb = cr.velocity_error(out, lin1, ang1)
+        worst, n_amb = max(worst, err), n_amb + amb
+        check_stages(stages, "default")
+        if u:
+            assert len(out["a"]) == 400
+            ok = ~out["ambiguous"]
+            with_pn += int(((out["P0"][:, 0, 2] > 0) & ok).sum())
+            with_pt += int(((out["P0"][:, 0, :2] != 0).any(1) & ok).sum())
+            nx = np.abs(np.asarray(w.get_manifolds()[2])[:, 0])
+            switched += int(((nx >= cr.BASIS_SWITCH) & (out["P0"][:, 0, 2] > 0) & ok).sum())
+    print(f"\n{case}: error {worst:.3g} (tolerance {TOL_ISOLATED}), {n_amb} ambiguous; carried pn {with_pn}, friction {with_pt}")
+    assert n_amb <= 20
+    assert worst < TOL_ISOLATED
+    if case == "turn3":
+        assert with_pn == 0 and with_pt == 0
+    elif case == "turn1":
+        assert with_pn > 1500 and with_pt > 1500
+    else:
+        assert with_pn > 1500 and switched > 300 and with_pt < with_pn - 300
+
+
+# ---------------------------------------------------------------- (c) coupled manifolds
+def test_persistent_colouring_of_a_churning_scene():
+    """130 updates of C3(12, 10, 12): colour counts, n_colors, color_rounds and n_new_manifolds of every update equal
+    the persistent colouring restated from the device's own manifolds."""
+    import physics_amd
+    from physics_amd import scenes
+    sc = scenes.c3(12, 10, 12)
+    w = physics_amd.World(sc.config())
+    sc.populate(w)
+    prev_keys = prev_colors = None
+    churn, stages_seen = 0, set()
+    for u in range(130):
+        w.profile_enable(True)
+        w.update(DT)
+        w.sync()
+        stages_seen |= set(w.profile_get()[0]) & SOLVER_STAGES
+        m = cr.unpack_manifolds(w.get_manifolds())
+        colors, n_colors, rounds, n_new = cr.color_manifolds(m["a"], m["b"], sc.n, prev_keys, prev_colors)
+        prev_keys, prev_colors = m["keys"], colors
+        st = w.get_stats()
+        assert np.array_equal(w.get_color_counts(), cr.color_counts(colors)), u
+        assert (st.n_colors, st.color_rounds, st.n_new_manifolds) == (n_colors, rounds, n_new), u
+        churn += 0 < n_new < st.n_manifolds
+    assert churn > 50 and n_colors >= 6
+    assert stages_seen and stages_seen <= SOLVER_STAGES - {"solve_cluster"}, stages_seen
+
+
+def _coupled(bodies, n_updates=6, flags=0, expect=("solve_flow",)):
+    n = len(bodies["pos"])
+    w = make_world(bodies, flags=flags, gravity=(0, -9.81, 0))
+    ref = cr.SolverRef(n, cr.Params(DT_S), 8)
+    worst, colors = 0.0, 0
+    for u, (out, lin1, ang1, stages) in enumerate(checked_updates(w, ref, n_updates, *cr.body_inverses(n, bodies.get("mass"),
+                                                                                                       bodies.get("inertia")), GRAVITY)):
+        st = w.get_stats()
+        assert np.array_equal(w.get_color_counts(), cr.color_counts(out["colors"]))
+        assert (st.n_colors, st.color_rounds, st.n_new_manifolds) == (out["n_colors"], out["color_rounds"], out["n_new_manifolds"])
+        # (update 1 may take another family: the cluster plan needs the counts of an update before)
+        assert stages == set(expect) or (u == 0 and len(stages) >= 1 and stages <= SOLVER_STAGES), (u, stages)
+        err, amb = cr.velocity_error(out, lin1, ang1)
+        assert amb <= 0.01 * len(out["a"])
+        worst, colors = max(worst, err), max(colors, out["n_colors"])
+    return worst, colors, len(out["a"])
+
+
+@pytest.mark.parametrize("scene", ["c1_settled", "heap"])
+def test_coupled_piles_in_colour_order(scene):
+    """Six warm-started updates from a fresh world, through the dataflow kernels."""
+    import physics_amd
+    from physics_amd import scenes
+    if scene == "heap":
+        bodies = cr.random_heap(5)
+    else:
+        sc = scenes.c1()
+        w0 = physics_amd.World(sc.config())
+        sc.populate(w0)
+        w0.update_n(DT, 300)
+        w0.sync()
+        pos, rot = w0.get_transforms()
+        lin, ang = w0.get_velocities()
+        w0.close()
+        bodies = dict(pos=pos, rot=rot, lin_vel=lin, ang_vel=ang, shape_type=sc.shape_type, half_extent=sc.half_extent)
+    worst, colors, m = _coupled(bodies)
+    print(f"\n{scene}: {m} manifolds, {colors} colours, error {worst:.3g} (tolerance {TOL_COUPLED})")
+    assert colors >= 3
+    assert worst < TOL_COUPLED
+
+
+def test_cluster_kernels_on_the_tower():
+    """C5(16, 130, 16) with PHYS_FLAG_SOLVER_CLUSTER: updates 2 to 6 through the cluster kernels, against the reference."""
+    import physics_amd
+    from physics_amd import scenes
+    sc = scenes.c5(16, 130, 16)
+    bodies = dict(pos=sc.pos, shape_type=sc.shape_type, half_extent=sc.half_extent)
+    worst, colors, m = _coupled(bodies, flags=physics_amd.FLAG_SOLVER_CLUSTER, expect=("solve_cluster",))
+    print(f"\nC5 tower (cluster): {m} manifolds, {colors} colours, error {worst:.3g} (tolerance {TOL_TOWER})")
+    assert m > 90_000
+    assert worst < TOL_TOWER
