@@ -369,20 +369,6 @@ void launch_cluster_sort(phys_world* w, unsigned blocks, StepCounters* snap_out)
 }
 
 // ---- the solver ----------------------------------------------------------------------------------------------
-typedef uint32_t u32x4c __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4c ld_gran(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
-    // sc0 | sc1 (what the volatile form emits): read past this XCD's L2. With sc1 alone ("agent scope") a poll could keep
-    // hitting a line its own XCD had cached before the other XCD's write-through store landed: one run in two of two
-    // worlds stepping side by side ended in the hand-off time-out (tools/ghost_cluster_stress.py), none with this form -
-    // and the scope made no difference in time.
-    return __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, (int)0x80000010);
-}
-__device__ __forceinline__ void st_gran(__amdgpu_buffer_rsrc_t r, uint32_t byte_off, v3 v, uint32_t tag) {
-    u32x4c g;
-    g.x = __float_as_uint(v.x); g.y = __float_as_uint(v.y); g.z = __float_as_uint(v.z); g.w = tag;
-    __builtin_amdgcn_raw_buffer_store_b128(g, r, byte_off, 0, 16);  // sc1: write-through
-}
-
 // Rows of a cluster step are COMPACT (k_rows_build writes them so when cluster_slots != 0): what the solver streams
 // per iteration is 9 planes of 16 bytes instead of 16 -
 //     plane 0      hdr {body a, body b, point count, tickets}
@@ -624,26 +610,18 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                     needB = tB != 0u;
                 }
                 if (!DIAG) {  // full tensors: gathered by body id (the rare path keeps its second round trip)
-                    IA = ld_inertia_c<false>(inv_inertia, h.x * inertia_stride);
-                    if (gm.has_b) IB = ld_inertia_c<false>(inv_inertia, h.y * inertia_stride);
+                    IA = ld_inertia<false>(inv_inertia, h.x * inertia_stride);
+                    if (gm.has_b) IB = ld_inertia<false>(inv_inertia, h.y * inertia_stride);
                 }
                 uint32_t sweeps = 0, late = 0;
                 while (needA || needB) {
                     if (needA) {
-                        const u32x4c g0 = ld_gran(rv, h.x * 32u), g1 = ld_gran(rv, h.x * 32u + 16u);
-                        if (g0.w == (etag | tA) && g1.w == (etag | tA)) {
-                            vA = v3_make(__uint_as_float(g0.x), __uint_as_float(g0.y), __uint_as_float(g0.z));
-                            wA = v3_make(__uint_as_float(g1.x), __uint_as_float(g1.y), __uint_as_float(g1.z));
-                            needA = false;
-                        }
+                        const u32x4 g0 = ld_granule(rv, h.x * 32u), g1 = ld_granule(rv, h.x * 32u + 16u);
+                        if (g0.w == (etag | tA) && g1.w == (etag | tA)) { vA = granule_v3(g0); wA = granule_v3(g1); needA = false; }
                     }
                     if (needB) {
-                        const u32x4c g0 = ld_gran(rv, h.y * 32u), g1 = ld_gran(rv, h.y * 32u + 16u);
-                        if (g0.w == (etag | tB) && g1.w == (etag | tB)) {
-                            vB = v3_make(__uint_as_float(g0.x), __uint_as_float(g0.y), __uint_as_float(g0.z));
-                            wB = v3_make(__uint_as_float(g1.x), __uint_as_float(g1.y), __uint_as_float(g1.z));
-                            needB = false;
-                        }
+                        const u32x4 g0 = ld_granule(rv, h.y * 32u), g1 = ld_granule(rv, h.y * 32u + 16u);
+                        if (g0.w == (etag | tB) && g1.w == (etag | tB)) { vB = granule_v3(g0); wB = granule_v3(g1); needB = false; }
                     }
                     if (needA || needB) {
                         __builtin_amdgcn_s_sleep(kPollSleep);
@@ -676,7 +654,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                     }
                     if (modeA == 1u || modeA == 2u) {
                         if (finalA) { st3(vel + 8 * (size_t)h.x, 0, vA); st3(vel + 8 * (size_t)h.x + 4, 0, wA); }  // the masses stay where they are
-                        else if (modeA == 2u || pubA) { st_gran(rv, h.x * 32u, vA, etag | (tA + 1u)); st_gran(rv, h.x * 32u + 16u, wA, etag | (tA + 1u)); }
+                        else if (modeA == 2u || pubA) { st_granule(rv, h.x * 32u, vA, etag | (tA + 1u)); st_granule(rv, h.x * 32u + 16u, wA, etag | (tA + 1u)); }
                     }
                     if (modeB == 0u || modeB == 1u) {
                         s_body[4 * slotB] = make_float4(vB.x, vB.y, vB.z, __uint_as_float(etag | (tB + 1u)));
@@ -684,7 +662,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                     }
                     if (modeB == 1u || modeB == 2u) {
                         if (finalB) { st3(vel + 8 * (size_t)h.y, 0, vB); st3(vel + 8 * (size_t)h.y + 4, 0, wB); }
-                        else if (modeB == 2u || pubB) { st_gran(rv, h.y * 32u, vB, etag | (tB + 1u)); st_gran(rv, h.y * 32u + 16u, wB, etag | (tB + 1u)); }
+                        else if (modeB == 2u || pubB) { st_granule(rv, h.y * 32u, vB, etag | (tB + 1u)); st_granule(rv, h.y * 32u + 16u, wB, etag | (tB + 1u)); }
                     }
                     if (last_it && man_imp) {  // the solve's last sweep: remembered for the next update (contact_solve.h)
                         float4* o = reinterpret_cast<float4*>(man_imp) + 3 * (size_t)row_src[d_row];
@@ -774,24 +752,19 @@ void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float fric
     // 1M cubes (tools/guard_cost.py) - is skipped). The guarded start is the default since round 3: a drop-in behind a render loop shares its GPU
     // with the renderer, and the unguarded launch's failure mode there is a 3 s spin.
     const bool guarded = !gpu_is_exclusive(w);
-    const uint32_t kAttempts = guarded ? 2u : 1u;
-    for (uint32_t attempt = 0; attempt < kAttempts; ++attempt) {
-        const uint32_t last = attempt + 1 == kAttempts ? 1u : 0u;
-        // 100 MHz ticks: 0.5 ms, then 20 ms for the workgroups to come in (alone on the device they need ~10 us); < 0: no count
-        const long long arrive_ticks = !guarded ? -1ll : (attempt == 0 ? 50000ll : 2000000ll);
-#define PHYS_CLUSTER_ARGS g, b, lds, w->stream, w->counters.p, sweeps, w->flow_epoch, rows, friction, inertia, stride, \
-                          w->vel.p, w->pos.p, w->flow_vel.p, (uint32_t)w->n, w->cluster_body.p, w->body_shared.p, w->seg_start.p,     \
-                          w->cluster_slots, timeout_ticks, attempt, last, arrive_ticks, warm_sweep, w->row_src.p,                     \
-                          w->warm ? w->man_imp.p : (float*)nullptr
-        if (guarded) {
-            if (diag) hipLaunchKernelGGL((k_solve_cluster<true, true>), PHYS_CLUSTER_ARGS);
-            else hipLaunchKernelGGL((k_solve_cluster<false, true>), PHYS_CLUSTER_ARGS);
-        } else {
-            if (diag) hipLaunchKernelGGL((k_solve_cluster<true, false>), PHYS_CLUSTER_ARGS);
-            else hipLaunchKernelGGL((k_solve_cluster<false, false>), PHYS_CLUSTER_ARGS);
+    dispatch_bool(diag, [&](auto diag_t) { dispatch_bool(guarded, [&](auto guarded_t) {
+        constexpr bool D = decltype(diag_t)::value, G = decltype(guarded_t)::value;
+        const uint32_t kAttempts = G ? 2u : 1u;
+        for (uint32_t attempt = 0; attempt < kAttempts; ++attempt) {
+            const uint32_t last = attempt + 1 == kAttempts ? 1u : 0u;
+            // 100 MHz ticks: 0.5 ms, then 20 ms for the workgroups to come in (alone on the device they need ~10 us); < 0: no count
+            const long long arrive_ticks = !G ? -1ll : (attempt == 0 ? 50000ll : 2000000ll);
+            hipLaunchKernelGGL((k_solve_cluster<D, G>), g, b, lds, w->stream, w->counters.p, sweeps, w->flow_epoch, rows, friction,
+                               inertia, stride, w->vel.p, w->pos.p, w->flow_vel.p, (uint32_t)w->n, w->cluster_body.p,
+                               w->body_shared.p, w->seg_start.p, w->cluster_slots, timeout_ticks, attempt, last, arrive_ticks,
+                               warm_sweep, w->row_src.p, w->warm ? w->man_imp.p : (float*)nullptr);
         }
-#undef PHYS_CLUSTER_ARGS
-    }
+    }); });
 }
 
 }  // namespace phys

@@ -2,6 +2,7 @@
 // of libphysics_hip.so. Every launch_* enqueues on w->stream and returns without synchronising.
 #pragma once
 #include <algorithm>
+#include <type_traits>
 #include <hip/hip_runtime.h>
 
 #include "../../include/spec/collide.h"
@@ -17,6 +18,12 @@ static_assert(PHYS_MAX_COLORS == phys::kMaxColors, "colour limit mismatch");
 #define PHYS_PROF(w, st) phys::ProfScope PHYS_PROF_CAT(_prof_scope_, __LINE__)((w)->prof, (w)->stream, (st))
 
 namespace phys {
+
+// f(std::true_type{}) or f(std::false_type{}): a launch site names each instantiation of a kernel template once
+template <class F>
+inline void dispatch_bool(bool b, F&& f) {
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
 
 // 12-byte packed attribute access as ONE dwordx3 memory instruction per lane (a wave then covers one
 // contiguous 768-B span). Written as three scalar accesses hipcc emits three dword instructions, each
@@ -53,7 +60,7 @@ __device__ __forceinline__ void st_vel(float* __restrict__ vel, uint32_t i, cons
 // rigid_body.rs:71), stored as one float4 per body = 16 B and one sector per gather instead of 36 B / two.
 // The zero off-diagonals are put back, so the arithmetic is the general path's (only signed zeros can differ).
 template <bool DIAG>
-__device__ __forceinline__ m33 ld_inertia_c(const float* __restrict__ p, uint32_t i) {
+__device__ __forceinline__ m33 ld_inertia(const float* __restrict__ p, uint32_t i) {
     m33 M;
     if (DIAG) {
         const float4 d = reinterpret_cast<const float4*>(p)[i];
@@ -65,6 +72,25 @@ __device__ __forceinline__ m33 ld_inertia_c(const float* __restrict__ p, uint32_
         for (int k = 0; k < 9; ++k) M.m[k] = p[9 * (size_t)i + k];
     }
     return M;
+}
+
+// Data-tagged 16-byte granules of the dataflow and cluster solvers: {x, y, z, tag}, written by ONE 16-byte store and
+// read by 16-byte loads only, so the tag is the ready flag of the data beside it (solver.hip, cluster.hip).
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x4 ld_granule(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
+    // sc0 | sc1 (what the volatile form emits): read past this XCD's L2. With sc1 alone ("agent scope") a poll could keep
+    // hitting a line its own XCD had cached before the other XCD's write-through store landed: one run in two of two
+    // worlds stepping side by side ended in the hand-off time-out (tools/ghost_cluster_stress.py), none with this form -
+    // and the scope made no difference in time. (Volatile also makes the compiler re-issue the load in every sweep.)
+    return __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, (int)0x80000010);
+}
+__device__ __forceinline__ void st_granule(__amdgpu_buffer_rsrc_t r, uint32_t byte_off, v3 v, uint32_t tag) {
+    u32x4 g;
+    g.x = __float_as_uint(v.x); g.y = __float_as_uint(v.y); g.z = __float_as_uint(v.z); g.w = tag;
+    __builtin_amdgcn_raw_buffer_store_b128(g, r, byte_off, 0, 16);  // sc1: write-through
+}
+__device__ __forceinline__ v3 granule_v3(u32x4 g) {
+    return v3_make(__uint_as_float(g.x), __uint_as_float(g.y), __uint_as_float(g.z));
 }
 
 // Persistent colouring: ONE hash table (a << 32 | b) -> {colour, update stamp} that lives across updates. Open addressing,

@@ -26,29 +26,6 @@
 
 namespace phys {
 
-// inverse inertia of one body. DIAG: every body's tensor is diagonal (the reference's only case: identity,
-// rigid_body.rs:71), stored as one float4 per body = 16 B and one sector per gather instead of 36 B / two.
-// The zero off-diagonals are put back, so the arithmetic is the general path's (only signed zeros can differ).
-template <bool DIAG>
-__device__ __forceinline__ m33 ld_inertia(const float* __restrict__ p, uint32_t i);
-__device__ __forceinline__ m33 ld_m33(const float* __restrict__ p, uint32_t i) {
-    m33 M;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) M.m[k] = p[9 * (size_t)i + k];
-    return M;
-}
-template <>
-__device__ __forceinline__ m33 ld_inertia<false>(const float* __restrict__ p, uint32_t i) { return ld_m33(p, i); }
-template <>
-__device__ __forceinline__ m33 ld_inertia<true>(const float* __restrict__ p, uint32_t i) {
-    const float4 d = reinterpret_cast<const float4*>(p)[i];
-    m33 M;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) M.m[k] = 0.0f;
-    M.m[0] = d.x; M.m[4] = d.y; M.m[8] = d.z;
-    return M;
-}
-
 // warm starting (contact_solve.h): where the impulses a solve ends with go, and where a row's starting impulses come from
 struct WarmJob {
     const uint32_t* man_prev;  // null: warm starting is off (rows start from zero, no sweep 0); otherwise only a flag
@@ -406,9 +383,10 @@ __global__ __launch_bounds__(kTailThreads) void k_solve_tail(const StepCounters*
 // only be made by the row holding ticket k for A (k = iteration * deg(A) + rank of the row's colour among A's
 // colours; k_rows_build). In-flight velocities live in `flow_vel` as two 16-byte granules {x, y, z, tag} whose
 // tag = (epoch << 16) | number of updates applied, i.e. THE DATA IS ITS OWN READY FLAG: a row polls its bodies'
-// granules (sc1 loads: served past the CU's L1) until both tags equal its ticket, solves, and stores them back
-// (sc1 = write-through stores) with tag + 1. One hop costs ~0.7-1.0 us (tools/hop_bench.hip) instead of a
-// launch, and rows of different colours / iterations overlap wherever the contact graph allows.
+// granules (ld_granule, kernels.hpp: sc0 sc1 loads, served past the XCD's L2) until both tags equal its ticket,
+// solves, and stores them back (sc1 = write-through stores) with tag + 1. One hop costs ~0.7-1.0 us
+// (tools/hop_bench.hip) instead of a launch, and rows of different colours / iterations overlap wherever the
+// contact graph allows.
 //   * the FIRST update of a body reads the plain `vel` record (written by the previous kernel), the LAST one
 //     writes it (read by the next kernel): flow_vel never needs initialising; stale tags of earlier steps carry
 //     another epoch;
@@ -417,21 +395,21 @@ __global__ __launch_bounds__(kTailThreads) void k_solve_tail(const StepCounters*
 //     dependency of an item was taken EARLIER by a workgroup that is running: no co-residency assumption, no
 //     deadlock by construction; and every spin is bounded (timeout -> overflow bit 4 -> PHYS_ERR_HIP at sync).
 // Granule discipline follows the guide's data-tagged hand-off: each granule is written by ONE 16-byte sc1
-// store and only ever read by 16-byte sc1 loads. Waiting waves cost issue slots and L2 bandwidth, so the launch
+// store and only ever read by 16-byte sc0 sc1 loads. Waiting waves cost issue slots and L2 bandwidth, so the launch
 // is sized to about one wave per SIMD (launch_solver) and waiters back off by their distance in hops.
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ u32x4 ld_granule(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
-    // aux: 16 = sc1, bit 31 = volatile (the compiler must re-issue the load in every sweep)
-    return __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, (int)0x80000010);
-}
-__device__ __forceinline__ void st_granule(__amdgpu_buffer_rsrc_t r, uint32_t byte_off, v3 v, uint32_t tag) {
-    u32x4 g;
-    g.x = __float_as_uint(v.x); g.y = __float_as_uint(v.y); g.z = __float_as_uint(v.z); g.w = tag;
-    __builtin_amdgcn_raw_buffer_store_b128(g, r, byte_off, 0, 16);
-}
-__device__ __forceinline__ v3 granule_v3(u32x4 g) {
-    return v3_make(__uint_as_float(g.x), __uint_as_float(g.y), __uint_as_float(g.z));
+// back-off of a waiting dataflow wave, in proportion to how many hops away the nearest waiting lane is, and its bounded
+// spin: true when the wave gives up (time-out, or another wave gave up: overflow bit 4, flagged by lane 0)
+__device__ __forceinline__ bool flow_backoff(StepCounters* ctr, bool done, uint32_t gap, uint32_t& sweeps, long long t_start,
+                                             long long timeout_ticks) {
+    if (__any(!done && gap <= 1u)) __builtin_amdgcn_s_sleep(1);
+    else if (__any(!done && gap <= 4u)) __builtin_amdgcn_s_sleep(40);
+    else __builtin_amdgcn_s_sleep(127);
+    if ((++sweeps & 63u) != 0u) return false;
+    const bool dead = (wall_clock64() - t_start > timeout_ticks) ||
+                      (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 16u);
+    if (dead && (threadIdx.x & 63u) == 0u) flag_overflow(ctr, 16u);  // wave-uniform: both inputs are
+    return dead;
 }
 
 constexpr long long kFlowTimeoutTicks = 300000000ll;  // 3 s of the 100 MHz wall clock (fault injection: 20 ms)
@@ -652,18 +630,7 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
                 }
             }
             if (__all(done)) break;
-            // back off in proportion to how many hops away the nearest waiting lane is
-            if (__any(!done && gap <= 1u)) __builtin_amdgcn_s_sleep(1);
-            else if (__any(!done && gap <= 4u)) __builtin_amdgcn_s_sleep(40);
-            else __builtin_amdgcn_s_sleep(127);
-            if ((++sweeps & 63u) == 0u) {
-                const bool dead = (wall_clock64() - t_start > timeout_ticks) ||
-                                  (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 16u);
-                if (dead) {  // wave-uniform: both inputs are
-                    if ((threadIdx.x & 63u) == 0u) flag_overflow(ctr, 16u);
-                    done = true;
-                }
-            }
+            if (flow_backoff(ctr, done, gap, sweeps, t_start, timeout_ticks)) done = true;
         }
         if (!pipeline) {
             L_next = take();
@@ -677,14 +644,14 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// The same dataflow solver with FOUR LANES PER MANIFOLD, for scenes where the hop latency is everything. At one
-// wave per SIMD the row solve is VALU-issue-bound (~65 instructions per row x 12 rows, ~2/3 of a hop). A row is
-// four dot products, a scalar update and four axpys over {vA, wA, vB, wB}: lane q of a quad owns ONE of those
-// vectors with its Jacobian column and response (made beforehand, while waiting), so a row costs each lane one
-// dot product, two cross-lane adds (DPP inside the quad: no LDS), the scalar update and one axpy - about a third
-// of the instructions. The partial sums are combined in the order of the spec ((dir.vB + aB.wB) - (dir.vA +
-// aA.wA)), so the bits are those of the one-lane kernels. The granule protocol maps one to one: lane q polls and
-// publishes exactly its own 16-byte granule (v or w of A or B), and the impulse granule of contact point q.
+// The FOUR-LANE ROW CORE of k_solve_flow_quad and k_solve_color_quad. At one wave per SIMD the one-lane row solve is
+// VALU-issue-bound (~65 instructions per row x 12 rows, ~2/3 of a hop in k_solve_flow). A row is four dot products, a
+// scalar update and four axpys over {vA, wA, vB, wB}: lane q of a quad owns ONE of those vectors with its Jacobian
+// column and response (made beforehand: quad_lane_setup), so a row costs each lane one dot product, two cross-lane
+// adds (DPP inside the quad: no LDS), the scalar update and one axpy - about a third of the instructions
+// (quad_lane_solve). The partial sums are combined in the order of the spec ((dir.vB + aB.wB) - (dir.vA + aA.wA)), so
+// the bits are those of the one-lane kernels. Both kernels run this one copy; what differs is where the rows and the
+// accumulated impulses come from and where the results go.
 template <int CTRL>
 __device__ __forceinline__ float quad_perm(float v) {
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
@@ -694,6 +661,135 @@ __device__ __forceinline__ int quad_perm_i(int v) { return __builtin_amdgcn_mov_
 constexpr int kQuadXor1 = 0xB1;  // quad_perm [1, 0, 3, 2]
 constexpr int kQuadXor2 = 0x4E;  // quad_perm [2, 3, 0, 1]
 
+// one lane's share of a manifold, in registers: its vector, its Jacobian column and (signed) response for the 12 rows;
+// replicated over the quad: the row scalars and the accumulated impulses. All zero for a lane without a row.
+// (quad_lane_setup / quad_lane_solve work on `x` and `count` in locals: read through the struct inside their loops they
+// stayed in memory until the loops were unrolled, and both kernels came out 2-6 VGPRs and up to 100 instructions longer.
+// The Jacobian columns are picked by selects, not branches: linear and angular lanes share every wave, so a branch ran
+// both sides anyway, and k_solve_flow_quad lost 1 % on C2 with it.)
+struct QuadLane {
+    v3 x, Jv[4][3], Rs[4][3];
+    float nm[4], tm0[4], tm1[4], bias[4], pn[4], pt0[4], pt1[4];
+    float keep_w;  // the other float of the lane's half of the velocity record ({v, 1/m} or {w, m}): stored back as it was
+    uint32_t body, count;
+    bool has_body;
+    __device__ __forceinline__ QuadLane() : keep_w(0.0f), body(0), count(0), has_body(false) {
+        x = v3_make(0.0f, 0.0f, 0.0f);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            nm[k] = 0.0f; tm0[k] = 0.0f; tm1[k] = 0.0f; bias[k] = 0.0f; pn[k] = 0.0f; pt0[k] = 0.0f; pt1[k] = 0.0f;
+#pragma unroll
+            for (int t = 0; t < 3; ++t) { Jv[k][t] = x; Rs[k][t] = x; }
+        }
+    }
+};
+
+// lane q (0 vA, 1 wA, 2 vB, 3 wB) of row {a, b, count} with normal `nn`, tangent masses and biases t01 / t23 (t23 read
+// by the caller only for count > 2) and the point planes pt(j) = {rA, normal mass} of point k at j = 2k, {rB, tangent
+// mass 0} at 2k + 1, read for the points below `count` only. The accumulated impulses are left to the caller.
+template <bool DIAG>
+__device__ __forceinline__ void quad_lane_setup(QuadLane& s, uint32_t q, uint32_t a, uint32_t b, uint32_t count, float4 nn,
+                                                float4 t01, float4 t23, const float4* pt, uint32_t pt_stride, const float* vel,
+                                                const float* __restrict__ inv_inertia, uint32_t inertia_stride) {
+    const bool side_a = q < 2u, angular = (q & 1u) != 0u;
+    const uint32_t body = side_a ? a : b;
+    const bool has_body = side_a || b != PHYS_GROUND_ID;
+    s.count = count; s.body = body; s.has_body = has_body;
+    v3 dir[3];
+    dir[2] = v3_make(nn.x, nn.y, nn.z);
+    tangent_basis(dir[2], &dir[0], &dir[1]);  // same inputs as solver_prep => same bits as the basis used there
+    m33 I;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) I.m[k] = 0.0f;
+    float inv_m = 0.0f;
+    v3 x = v3_make(0.0f, 0.0f, 0.0f);
+    if (has_body) {
+        // the body's half of the plain velocity record: the state itself where the caller takes it from there, the masses always
+        const float4 h0 = reinterpret_cast<const float4*>(vel)[2 * (size_t)body + (angular ? 1 : 0)];
+        x = v3_make(h0.x, h0.y, h0.z);
+        s.keep_w = h0.w;
+        if (angular) I = ld_inertia<DIAG>(inv_inertia, body * inertia_stride); else inv_m = h0.w;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k < (int)count) {
+            const float4 p0 = pt[(size_t)(2 * k) * pt_stride], p1 = pt[(size_t)(2 * k + 1) * pt_stride];
+            s.nm[k] = p0.w; s.tm0[k] = p1.w;
+            const float4 tt = k < 2 ? t01 : t23;
+            s.tm1[k] = (k & 1) ? tt.z : tt.x;
+            s.bias[k] = (k & 1) ? tt.w : tt.y;
+            const v3 r = side_a ? v3_make(p0.x, p0.y, p0.z) : v3_make(p1.x, p1.y, p1.z);
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                if (has_body) {
+                    // solver_jacobians: lA = dir * invM; aA = r x dir, mA = I aA. The A side is subtracted by the spec:
+                    // its response is stored negated (exact)
+                    const v3 jv = angular ? v3_cross_f(r, dir[t]) : dir[t];
+                    const v3 rs = angular ? inertia_mul(&I, jv) : v3_scale(dir[t], inv_m);
+                    s.Jv[k][t] = jv;
+                    s.Rs[k][t] = side_a ? v3_neg(rs) : rs;
+                }
+            }
+        }
+    }
+    s.x = x;
+}
+
+// the 12 rows of solve_manifold on the quad's four lanes; every lane of the quad takes part in the DPP exchanges.
+// apply_only: sweep 0 of a warm-started solve - the starting impulses reach the lane's vector, no row is solved
+__device__ __forceinline__ void quad_lane_solve(QuadLane& s, float friction, bool apply_only, bool side_a) {
+    const uint32_t count = s.count;
+    v3 x = s.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k < (int)count) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                // row_velocity: (dir.vB + aB.wB) - (dir.vA + aA.wA), the two sums made inside each pair
+                float lambda;
+                if (apply_only) {
+                    lambda = t == 0 ? s.pt0[k] : (t == 1 ? s.pt1[k] : s.pn[k]);
+                    x = v3_madd(x, s.Rs[k][t], lambda);
+                    continue;
+                }
+                const float part = v3_dot_f(s.Jv[k][t], x);
+                const float mine = part + quad_perm<kQuadXor1>(part);
+                const float other = quad_perm<kQuadXor2>(mine);
+                const float vrel = side_a ? other - mine : mine - other;
+                if (t < 2) {  // solve_row_dir, friction
+                    const float mass = t == 0 ? s.tm0[k] : s.tm1[k];
+                    float& acc = t == 0 ? s.pt0[k] : s.pt1[k];
+                    lambda = -mass * vrel;
+                    const float maxf = friction * s.pn[k];
+                    const float old = acc;
+                    const float np = det_maxf(-maxf, det_minf(old + lambda, maxf));
+                    lambda = np - old;
+                    acc = np;
+                } else {      // normal
+                    lambda = s.nm[k] * (s.bias[k] - vrel);
+                    const float old = s.pn[k];
+                    const float np = det_maxf(old + lambda, 0.0f);
+                    lambda = np - old;
+                    s.pn[k] = np;
+                }
+                x = v3_madd(x, s.Rs[k][t], lambda);  // row_apply
+            }
+        }
+    }
+    s.x = x;
+}
+
+// {pn, pt0, pt1} of contact point q: what lane q publishes and stores
+__device__ __forceinline__ v3 quad_point_impulses(const QuadLane& s, uint32_t q) {
+    return q == 0 ? v3_make(s.pn[0], s.pt0[0], s.pt1[0])
+         : q == 1 ? v3_make(s.pn[1], s.pt0[1], s.pt1[1])
+         : q == 2 ? v3_make(s.pn[2], s.pt0[2], s.pt1[2]) : v3_make(s.pn[3], s.pt0[3], s.pt1[3]);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The dataflow solver with FOUR LANES PER MANIFOLD (the row core above), for scenes where the hop latency is
+// everything. The granule protocol maps one to one: lane q polls and publishes exactly its own 16-byte granule (v or w
+// of A or B), and the impulse granule of contact point q.
 template <bool DIAG>
 __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restrict__ ctr, uint32_t iterations, uint32_t epoch,
                                                          RowArrays rows, float friction,
@@ -731,77 +827,26 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
         const bool last_it = it + 1 == iterations;
         const uint32_t d = chunk * rows_per_item + (threadIdx.x >> 2);
         bool done = d >= M;  // the same for the four lanes of a quad
-        // per lane: its vector, its Jacobian column and (signed) response for the 12 rows; replicated: the scalars
-        v3 x = zero, Jv[4][3], Rs[4][3];
-        float nm[4], tm0[4], tm1[4], bias[4], pn[4], pt0[4], pt1[4];
-        float keep_w = 0.0f;
-        uint32_t body = 0, count = 0, ticket = 0;
-        bool has_body = false, final_update = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            nm[k] = 0.0f; tm0[k] = 0.0f; tm1[k] = 0.0f; bias[k] = 0.0f; pn[k] = 0.0f; pt0[k] = 0.0f; pt1[k] = 0.0f;
-#pragma unroll
-            for (int t = 0; t < 3; ++t) { Jv[k][t] = zero; Rs[k][t] = zero; }
-        }
+        QuadLane s;
+        uint32_t ticket = 0;
+        bool final_update = false;
         if (!done) {
             const uint4 h = rows.hdr[d];
-            count = h.z;
-            const bool has_b = h.y != PHYS_GROUND_ID;
-            body = side_a ? h.x : h.y;
-            has_body = side_a || has_b;
             const uint32_t tk = side_a ? h.w : (h.w >> 16);
             const uint32_t rank = tk & 0xFFu, deg = (tk >> 8) & 0xFFu;
             ticket = it * deg + rank;
             final_update = last_it && rank + 1 == deg;
-            const float4 nn = rows.n[d];
-            v3 dir[3];
-            dir[2] = v3_make(nn.x, nn.y, nn.z);
-            tangent_basis(dir[2], &dir[0], &dir[1]);
-            const float4 t01 = rows.tb[d];
+            const float4 nn = rows.n[d], t01 = rows.tb[d];
             float4 t23 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (count > 2) t23 = rows.tb[cap + d];
-            m33 I;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) I.m[k] = 0.0f;
-            float inv_m = 0.0f;
-            if (has_body) {
-                // the body's half of the plain velocity record: the state itself for ticket 0, the masses always
-                const float4 h0 = reinterpret_cast<const float4*>(vel)[2 * (size_t)body + (angular ? 1 : 0)];
-                x = v3_make(h0.x, h0.y, h0.z);
-                keep_w = h0.w;
-                if (angular) I = ld_inertia<DIAG>(inv_inertia, body * inertia_stride); else inv_m = h0.w;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (k < (int)count) {
-                    const float4 p0 = rows.pt[(size_t)(2 * k) * cap + d];      // rA, normal mass
-                    const float4 p1 = rows.pt[(size_t)(2 * k + 1) * cap + d];  // rB, tangent mass 0
-                    nm[k] = p0.w; tm0[k] = p1.w;
-                    const float4 tt = k < 2 ? t01 : t23;
-                    tm1[k] = (k & 1) ? tt.z : tt.x;
-                    bias[k] = (k & 1) ? tt.w : tt.y;
-                    const v3 r = side_a ? v3_make(p0.x, p0.y, p0.z) : v3_make(p1.x, p1.y, p1.z);
-#pragma unroll
-                    for (int t = 0; t < 3; ++t) {
-                        if (has_body) {
-                            // solver_jacobians: lA = dir * invM; aA = r x dir, mA = I aA. The A side is subtracted
-                            // by the spec: its response is stored negated (exact)
-                            v3 jv, rs;
-                            if (angular) { jv = v3_cross_f(r, dir[t]); rs = inertia_mul(&I, jv); }
-                            else { jv = dir[t]; rs = v3_scale(dir[t], inv_m); }
-                            Jv[k][t] = jv;
-                            Rs[k][t] = side_a ? v3_neg(rs) : rs;
-                        }
-                    }
-                }
-            }
-            if (!has_body) x = zero;
+            if (h.z > 2) t23 = rows.tb[cap + d];
+            quad_lane_setup<DIAG>(s, q, h.x, h.y, h.z, nn, t01, t23, rows.pt + d, cap,
+                                  vel, inv_inertia, inertia_stride);
         }
         const bool apply_only = warm_sweep != 0u && it == 0u;
-        bool need = !done && has_body && ticket != 0;
-        bool need_acc = !done && it != 0 && q < count;  // lane q fetches the impulses of contact point q
+        bool need = !done && s.has_body && ticket != 0;
+        bool need_acc = !done && it != 0 && q < s.count;  // lane q fetches the impulses of contact point q
         v3 my_acc = zero;
-        if (apply_only && !done && q < count) {  // the starting impulses of point q (plain load: k_rows_build wrote them)
+        if (apply_only && !done && q < s.count) {  // the starting impulses of point q (plain load: k_rows_build wrote them)
             const float4 a0 = rows.acc[(size_t)q * cap + d];
             my_acc = v3_make(a0.x, a0.y, a0.z);
         }
@@ -810,11 +855,11 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
             uint32_t gap = 0;
             if (!done) {
                 u32x4 g, p;
-                if (need) g = ld_granule(rv, body * 32u + (angular ? 16u : 0u));
+                if (need) g = ld_granule(rv, s.body * 32u + (angular ? 16u : 0u));
                 if (need_acc) p = ld_granule(ra, (q * cap + d) * 16u);
                 if (need) {
                     const uint32_t want = etag | ticket;
-                    if (g.w == want) { x = granule_v3(g); need = false; }
+                    if (g.w == want) { s.x = granule_v3(g); need = false; }
                     else {
                         const uint32_t seen = (g.w >> 16) == epoch ? (g.w & 0xFFFFu) : 0u;
                         gap = ticket > seen ? ticket - seen : 1u;
@@ -831,95 +876,40 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
             ready &= quad_perm_i<kQuadXor2>(ready);
             if (!done && ready) {
                 if (it != 0 || apply_only) {  // everybody needs every point's accumulated impulses
-                    pn[0] = quad_perm<0x00>(my_acc.x); pt0[0] = quad_perm<0x00>(my_acc.y); pt1[0] = quad_perm<0x00>(my_acc.z);
-                    pn[1] = quad_perm<0x55>(my_acc.x); pt0[1] = quad_perm<0x55>(my_acc.y); pt1[1] = quad_perm<0x55>(my_acc.z);
-                    pn[2] = quad_perm<0xAA>(my_acc.x); pt0[2] = quad_perm<0xAA>(my_acc.y); pt1[2] = quad_perm<0xAA>(my_acc.z);
-                    pn[3] = quad_perm<0xFF>(my_acc.x); pt0[3] = quad_perm<0xFF>(my_acc.y); pt1[3] = quad_perm<0xFF>(my_acc.z);
+                    s.pn[0] = quad_perm<0x00>(my_acc.x); s.pt0[0] = quad_perm<0x00>(my_acc.y); s.pt1[0] = quad_perm<0x00>(my_acc.z);
+                    s.pn[1] = quad_perm<0x55>(my_acc.x); s.pt0[1] = quad_perm<0x55>(my_acc.y); s.pt1[1] = quad_perm<0x55>(my_acc.z);
+                    s.pn[2] = quad_perm<0xAA>(my_acc.x); s.pt0[2] = quad_perm<0xAA>(my_acc.y); s.pt1[2] = quad_perm<0xAA>(my_acc.z);
+                    s.pn[3] = quad_perm<0xFF>(my_acc.x); s.pt0[3] = quad_perm<0xFF>(my_acc.y); s.pt1[3] = quad_perm<0xFF>(my_acc.z);
                 }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (k < (int)count) {
-#pragma unroll
-                        for (int t = 0; t < 3; ++t) {
-                            // row_velocity: (dir.vB + aB.wB) - (dir.vA + aA.wA), the two sums made inside each pair
-                            float lambda;
-                            if (apply_only) {  // sweep 0 of a warm-started solve: the starting impulse reaches this lane's vector
-                                lambda = t == 0 ? pt0[k] : (t == 1 ? pt1[k] : pn[k]);
-                                x = v3_madd(x, Rs[k][t], lambda);
-                                continue;
-                            }
-                            const float part = v3_dot_f(Jv[k][t], x);
-                            const float mine = part + quad_perm<kQuadXor1>(part);
-                            const float other = quad_perm<kQuadXor2>(mine);
-                            const float vrel = side_a ? other - mine : mine - other;
-                            if (t < 2) {  // solve_row_dir, friction
-                                const float mass = t == 0 ? tm0[k] : tm1[k];
-                                float& acc = t == 0 ? pt0[k] : pt1[k];
-                                lambda = -mass * vrel;
-                                const float maxf = friction * pn[k];
-                                const float old = acc;
-                                const float np = det_maxf(-maxf, det_minf(old + lambda, maxf));
-                                lambda = np - old;
-                                acc = np;
-                            } else {      // normal
-                                lambda = nm[k] * (bias[k] - vrel);
-                                const float old = pn[k];
-                                const float np = det_maxf(old + lambda, 0.0f);
-                                lambda = np - old;
-                                pn[k] = np;
-                            }
-                            x = v3_madd(x, Rs[k][t], lambda);  // row_apply
-                        }
-                    }
-                }
-                if (has_body) {
+                quad_lane_solve(s, friction, apply_only, side_a);
+                if (s.has_body) {
                     if (final_update)
-                        reinterpret_cast<float4*>(vel)[2 * (size_t)body + (angular ? 1 : 0)] = make_float4(x.x, x.y, x.z, keep_w);
+                        reinterpret_cast<float4*>(vel)[2 * (size_t)s.body + (angular ? 1 : 0)] = make_float4(s.x.x, s.x.y, s.x.z, s.keep_w);
                     else
-                        st_granule(rv, body * 32u + (angular ? 16u : 0u), x, etag | (ticket + 1u));
+                        st_granule(rv, s.body * 32u + (angular ? 16u : 0u), s.x, etag | (ticket + 1u));
                 }
-                if (!last_it && q < count) {
-                    const v3 mine = q == 0 ? v3_make(pn[0], pt0[0], pt1[0])
-                                  : q == 1 ? v3_make(pn[1], pt0[1], pt1[1])
-                                  : q == 2 ? v3_make(pn[2], pt0[2], pt1[2]) : v3_make(pn[3], pt0[3], pt1[3]);
-                    st_granule(ra, (q * cap + d) * 16u, mine, etag | (it + 1u));
-                }
-                if (last_it && wj.man_prev) {  // lane q remembers point q's impulses (zeros beyond the count)
-                    const v3 fin = q == 0 ? v3_make(pn[0], pt0[0], pt1[0])
-                                 : q == 1 ? v3_make(pn[1], pt0[1], pt1[1])
-                                 : q == 2 ? v3_make(pn[2], pt0[2], pt1[2]) : v3_make(pn[3], pt0[3], pt1[3]);
-                    st3(wj.imp + 12 * (size_t)wj.row_src[d] + 3u * q, 0, fin);
-                }
+                if (!last_it && q < s.count) st_granule(ra, (q * cap + d) * 16u, quad_point_impulses(s, q), etag | (it + 1u));
+                if (last_it && wj.man_prev)  // lane q remembers point q's impulses (zeros beyond the count)
+                    st3(wj.imp + 12 * (size_t)wj.row_src[d] + 3u * q, 0, quad_point_impulses(s, q));
                 done = true;
             }
             if (__all(done)) break;
-            if (__any(!done && gap <= 1u)) __builtin_amdgcn_s_sleep(1);
-            else if (__any(!done && gap <= 4u)) __builtin_amdgcn_s_sleep(40);
-            else __builtin_amdgcn_s_sleep(127);
-            if ((++sweeps & 63u) == 0u) {
-                const bool dead = (wall_clock64() - t_start > timeout_ticks) ||
-                                  (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 16u);
-                if (dead) {
-                    if ((threadIdx.x & 63u) == 0u) flag_overflow(ctr, 16u);
-                    done = true;
-                }
-            }
+            if (flow_backoff(ctr, done, gap, sweeps, t_start, timeout_ticks)) done = true;
         }
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// One colour of one iteration with FOUR LANES PER MANIFOLD and the rows staged through LDS: the per-colour
-// kernel for scenes whose colour classes fill the chip (above kFlowMaxManifolds). k_solve_color runs one lane
-// per manifold: a colour of 60-70k manifolds is then ~270 workgroups = one wave per SIMD, each lane a chain of
+// One colour of one iteration with FOUR LANES PER MANIFOLD (the row core above) and the rows staged through LDS: the
+// per-colour kernel for colour classes too small to fill the chip with one lane per manifold. k_solve_color runs one
+// lane per manifold: a colour of 60-70k manifolds is then ~270 workgroups = one wave per SIMD, each lane a chain of
 // header load -> ~20 dependent dwordx4 loads -> ~1200 VALU instructions -> stores with nothing to overlap it
 // (17 us per launch for 26-33 MB, 19-24 % of the HBM rate). Here
 //   * a workgroup owns 64 consecutive rows; every 16-byte element of the 16 row planes of those rows is loaded
 //     ONCE (wave w fetches planes 4w..4w+3, 1 KiB contiguous per instruction, all issued before anything
 //     else: no load depends on the header any more) and parked in LDS (16 KiB);
-//   * lane q of a quad owns one of {vA, wA, vB, wB} exactly as in k_solve_flow_quad (same arithmetic, same
-//     DPP order of the partial sums => same bits): a third of the VALU chain per lane, four times the waves
-//     to overlap memory with arithmetic, and a gather of ONE 16-byte half record per lane.
+//   * quad_lane_setup / quad_lane_solve as in k_solve_flow_quad: a third of the VALU chain per lane, four times the
+//     waves to overlap memory with arithmetic, and a gather of ONE 16-byte half record per lane.
 // Rows of one colour share no body, so the plain loads / stores of `vel` need no ordering inside a launch.
 constexpr int kQuadRowsPerGroup = 64;
 template <bool DIAG>
@@ -934,7 +924,6 @@ __global__ __launch_bounds__(256) void k_solve_color_quad(StepCounters* ctr, uin
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t q = threadIdx.x & 3u, r = threadIdx.x >> 2;  // q: 0 vA, 1 wA, 2 vB, 3 wB
     const bool side_a = q < 2u, angular = (q & 1u) != 0u;
-    const v3 zero = v3_make(0.0f, 0.0f, 0.0f);
     // the four planes this wave stages: 4 * wave + j of the ONE row allocation (0 hdr, 1 n, 2-3 tb, 4-11 pt, 12-15 acc).
     // Plain arithmetic on purpose: written as `if (wave == 0) {pointers..} else if ..` over the five arrays, hipcc
     // (ROCm 7.2) lost one case of the pointer selection (wave 3 staged from a null pointer: memory access fault)
@@ -952,129 +941,40 @@ __global__ __launch_bounds__(256) void k_solve_color_quad(StepCounters* ctr, uin
         __syncthreads();
         const uint32_t d = base + r;
         const bool live = d < end;  // the same for the four lanes of a quad
-        v3 x = zero, Jv[4][3], Rs[4][3];
-        float nm[4], tm0[4], tm1[4], bias[4], pn[4], pt0[4], pt1[4];
-        float keep_w = 0.0f;
-        uint32_t body = 0, count = 0;
-        bool has_body = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            nm[k] = 0.0f; tm0[k] = 0.0f; tm1[k] = 0.0f; bias[k] = 0.0f; pn[k] = 0.0f; pt0[k] = 0.0f; pt1[k] = 0.0f;
-#pragma unroll
-            for (int t = 0; t < 3; ++t) { Jv[k][t] = zero; Rs[k][t] = zero; }
+        QuadLane s;
+        const float4 hraw = s_rows[0][r];
+        const uint32_t ha = __float_as_uint(hraw.x), hb = __float_as_uint(hraw.y), count = __float_as_uint(hraw.z);
+        // a row header that names no body of this world must never become an address (a faulting kernel can take the
+        // whole node down): flag the step (bit 5) and skip the row
+        const bool bad = live && (count > 4u || ha >= n_bodies || (hb != PHYS_GROUND_ID && hb >= n_bodies));
+        if (bad) {
+            flag_overflow(ctr, 32u);
+            ctr->debug[0] = d; ctr->debug[1] = ha; ctr->debug[2] = hb; ctr->debug[3] = count;
+            ctr->debug[4] = start; ctr->debug[5] = end; ctr->debug[6] = col; ctr->debug[7] = base;
         }
-        if (live) {
-            const float4 hraw = s_rows[0][r];
-            const uint32_t ha = __float_as_uint(hraw.x), hb = __float_as_uint(hraw.y);
-            count = __float_as_uint(hraw.z);
-            const bool has_b = hb != PHYS_GROUND_ID;
-            body = side_a ? ha : hb;
-            has_body = side_a || has_b;
-            // a row header that names no body of this world must never become an address (a faulting kernel can
-            // take the whole node down): flag the step (bit 5) and skip the row
-            if (count > 4u || (has_body && body >= n_bodies)) {
-                flag_overflow(ctr, 32u);
-                ctr->debug[0] = d; ctr->debug[1] = ha; ctr->debug[2] = hb; ctr->debug[3] = count;
-                ctr->debug[4] = start; ctr->debug[5] = end; ctr->debug[6] = col; ctr->debug[7] = base;
-                count = 0; has_body = false;
-            }
-            m33 I;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) I.m[k] = 0.0f;
-            float inv_m = 0.0f;
-            if (has_body) {
-                // this lane's half of the velocity record: {v, 1/m} or {w, m}
-                const float4 h0 = reinterpret_cast<const float4*>(vel)[2 * (size_t)body + (angular ? 1 : 0)];
-                x = v3_make(h0.x, h0.y, h0.z);
-                keep_w = h0.w;
-                if (angular) I = ld_inertia<DIAG>(inv_inertia, body * inertia_stride); else inv_m = h0.w;
-            }
-            const float4 nn = s_rows[1][r];
-            v3 dir[3];
-            dir[2] = v3_make(nn.x, nn.y, nn.z);
-            tangent_basis(dir[2], &dir[0], &dir[1]);
-            const float4 t01 = s_rows[2][r];
+        if (live && !bad) {
             float4 t23 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (count > 2) t23 = s_rows[3][r];
+            quad_lane_setup<DIAG>(s, q, ha, hb, count, s_rows[1][r], s_rows[2][r], t23, &s_rows[4][r], kQuadRowsPerGroup,
+                                  vel, inv_inertia, inertia_stride);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                if (k < (int)count) {
-                    const float4 p0 = s_rows[4 + 2 * k][r];      // rA, normal mass
-                    const float4 p1 = s_rows[4 + 2 * k + 1][r];  // rB, tangent mass 0
-                    const float4 ac = s_rows[12 + k][r];         // accumulated impulses of point k
-                    nm[k] = p0.w; tm0[k] = p1.w;
-                    const float4 tt = k < 2 ? t01 : t23;
-                    tm1[k] = (k & 1) ? tt.z : tt.x;
-                    bias[k] = (k & 1) ? tt.w : tt.y;
-                    pn[k] = ac.x; pt0[k] = ac.y; pt1[k] = ac.z;
-                    const v3 rr = side_a ? v3_make(p0.x, p0.y, p0.z) : v3_make(p1.x, p1.y, p1.z);
-#pragma unroll
-                    for (int t = 0; t < 3; ++t) {
-                        if (has_body) {
-                            // solver_jacobians: lA = dir * invM; aA = r x dir, mA = I aA; the A side is subtracted by
-                            // the spec, so its response is stored negated (exact)
-                            v3 jv, rs;
-                            if (angular) { jv = v3_cross_f(rr, dir[t]); rs = inertia_mul(&I, jv); }
-                            else { jv = dir[t]; rs = v3_scale(dir[t], inv_m); }
-                            Jv[k][t] = jv;
-                            Rs[k][t] = side_a ? v3_neg(rs) : rs;
-                        }
-                    }
-                }
-            }
-            if (!has_body) x = zero;
-        }
-        // every lane takes part in the DPP exchanges (dead quads carry zeros)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (k < (int)count) {
-#pragma unroll
-                for (int t = 0; t < 3; ++t) {
-                    // row_velocity: (dir.vB + aB.wB) - (dir.vA + aA.wA), the two sums made inside each pair
-                    float lambda;
-                    if (apply_only) {  // sweep 0 of a warm-started solve: the starting impulse reaches this lane's vector
-                        lambda = t == 0 ? pt0[k] : (t == 1 ? pt1[k] : pn[k]);
-                        x = v3_madd(x, Rs[k][t], lambda);
-                        continue;
-                    }
-                    const float part = v3_dot_f(Jv[k][t], x);
-                    const float mine = part + quad_perm<kQuadXor1>(part);
-                    const float other = quad_perm<kQuadXor2>(mine);
-                    const float vrel = side_a ? other - mine : mine - other;
-                    if (t < 2) {  // solve_row_dir, friction
-                        const float mass = t == 0 ? tm0[k] : tm1[k];
-                        float& acc = t == 0 ? pt0[k] : pt1[k];
-                        lambda = -mass * vrel;
-                        const float maxf = friction * pn[k];
-                        const float old = acc;
-                        const float np = det_maxf(-maxf, det_minf(old + lambda, maxf));
-                        lambda = np - old;
-                        acc = np;
-                    } else {      // normal
-                        lambda = nm[k] * (bias[k] - vrel);
-                        const float old = pn[k];
-                        const float np = det_maxf(old + lambda, 0.0f);
-                        lambda = np - old;
-                        pn[k] = np;
-                    }
-                    x = v3_madd(x, Rs[k][t], lambda);  // row_apply
+                if (k < (int)count) {  // the accumulated impulses of point k
+                    const float4 ac = s_rows[12 + k][r];
+                    s.pn[k] = ac.x; s.pt0[k] = ac.y; s.pt1[k] = ac.z;
                 }
             }
         }
+        quad_lane_solve(s, friction, apply_only != 0, side_a);  // dead quads carry zeros
         if (live) {
-            if (has_body)
-                reinterpret_cast<float4*>(vel)[2 * (size_t)body + (angular ? 1 : 0)] = make_float4(x.x, x.y, x.z, keep_w);
-            if (q < count) {
-                const float4 mine = q == 0 ? make_float4(pn[0], pt0[0], pt1[0], 0.0f)
-                                  : q == 1 ? make_float4(pn[1], pt0[1], pt1[1], 0.0f)
-                                  : q == 2 ? make_float4(pn[2], pt0[2], pt1[2], 0.0f) : make_float4(pn[3], pt0[3], pt1[3], 0.0f);
-                rows.acc[(size_t)q * cap + d] = mine;
+            if (s.has_body)
+                reinterpret_cast<float4*>(vel)[2 * (size_t)s.body + (angular ? 1 : 0)] = make_float4(s.x.x, s.x.y, s.x.z, s.keep_w);
+            if (q < s.count) {
+                const v3 mine = quad_point_impulses(s, q);
+                rows.acc[(size_t)q * cap + d] = make_float4(mine.x, mine.y, mine.z, 0.0f);
             }
-            if (last && wj.man_prev) {  // lane q remembers point q's impulses (zeros beyond the count)
-                float* o = wj.imp + 12 * (size_t)wj.row_src[d] + 3u * q;
-                st3(o, 0, q == 0 ? v3_make(pn[0], pt0[0], pt1[0]) : q == 1 ? v3_make(pn[1], pt0[1], pt1[1])
-                        : q == 2 ? v3_make(pn[2], pt0[2], pt1[2]) : v3_make(pn[3], pt0[3], pt1[3]));
-            }
+            if (last && wj.man_prev)  // lane q remembers point q's impulses (zeros beyond the count)
+                st3(wj.imp + 12 * (size_t)wj.row_src[d] + 3u * q, 0, quad_point_impulses(s, q));
         }
         __syncthreads();  // the LDS tile is restaged by the next trip
     }
@@ -1154,98 +1054,84 @@ void launch_solver(phys_world* w, float dt) {
         (void)hipMemsetAsync(w->row_acc.p, 0, 16 * cap * sizeof(float), s);
         w->flow_epoch = 1;
     }
-    { PHYS_PROF(w, PHYS_STAGE_ROWS);
-      if (diag)
-          hipLaunchKernelGGL(k_rows_build<true>, grid_for_count(m_hint), tb, 0, s, w->counters.p, rows, sp, w->row_src.p, w->man_geo.p,
-                             w->pos.p, w->vel.p, inertia, stride, w->man_color.p,
-                             w->color_state.p, flow ? (stall ? 2 : 1) : 0, table, w->cluster_slot.p, w->body_shared.p,
-                             w->cluster_step ? w->cluster_slots : 0u, w->cluster_count, warm);
-      else
-          hipLaunchKernelGGL(k_rows_build<false>, grid_for_count(m_hint), tb, 0, s, w->counters.p, rows, sp, w->row_src.p, w->man_geo.p,
+    dispatch_bool(diag, [&](auto diag_t) {  // every kernel below in the DIAG instantiation of this world
+        constexpr bool DIAG = decltype(diag_t)::value;
+        { PHYS_PROF(w, PHYS_STAGE_ROWS);
+          hipLaunchKernelGGL(k_rows_build<DIAG>, grid_for_count(m_hint), tb, 0, s, w->counters.p, rows, sp, w->row_src.p, w->man_geo.p,
                              w->pos.p, w->vel.p, inertia, stride, w->man_color.p,
                              w->color_state.p, flow ? (stall ? 2 : 1) : 0, table, w->cluster_slot.p, w->body_shared.p,
                              w->cluster_step ? w->cluster_slots : 0u, w->cluster_count, warm); }
-    if (flow) {
-        if (cluster) {
-            PHYS_PROF(w, PHYS_STAGE_SOLVE_CLUSTER);
-            launch_solve_cluster(w, rows.all, cap, sp.friction, inertia, stride, diag, timeout_ticks);
+        if (flow) {
+            if (cluster) {
+                PHYS_PROF(w, PHYS_STAGE_SOLVE_CLUSTER);
+                launch_solve_cluster(w, rows.all, cap, sp.friction, inertia, stride, diag, timeout_ticks);
+                return;
+            }
+            // about one wave per SIMD or less: waiting waves must not crowd out the ones that can run
+            // four lanes per manifold while the hop latency is everything - and, where the launch may take the whole chip
+            // (w->flow_wide: three workgroups per CU, 672 of them), all the way up: 155k manifolds 0.250 ms against 0.446 with
+            // 224 workgroups, C3's 216k 0.325 (cluster kernel 0.513), the 1M cubes' 379k 0.405 (cluster kernel 0.235)
+            const bool quad = m_hint <= (dbg.flow_quad_max ? dbg.flow_quad_max : (w->flow_wide ? kFlowMaxManifolds : kFlowQuadMaxManifolds));
+            const uint32_t threads = 256u;
+            const uint32_t rows_per_item = quad ? threads / 4 : threads;
+            uint64_t items = (uint64_t)sweeps * ((m_hint * 5 / 4 + rows_per_item - 1) / rows_per_item) + 1;
+            int cus = 256;
+            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, w->device);
+            // statically dealt items need every workgroup running: a third of the chip's slots by default (beside other
+            // streams' kernels), seven eighths of them - the cluster kernel's share - where the GPU is this world's alone
+            // (small scenes are a chain of hand-offs, not throughput: C2's 10k manifolds 0.053 ms at 224 workgroups, 0.058 at 672)
+            const uint64_t most = quad ? (w->flow_wide && m_hint > 32768u ? (uint64_t)(3 * (cus - cus / 8)) : 224) : 256;
+            if (items > most) items = most;  // the remaining items are taken by the same workgroups
+            PHYS_PROF(w, PHYS_STAGE_SOLVE_FLOW);
+            // look one work item ahead (k_solve_flow) while a colour class keeps a good part of the launch busy; below that the
+            // solve is a chain of hand-offs and an item held ahead only waits (C3: 16k rows per colour, 65k lanes: +10 %;
+            // 1M cubes: 41k rows per colour: -10 %). PHYS_DEBUG_FLOW_PIPELINE=0/1 forces it (measurements; same bits).
+            const uint64_t per_color = m_hint / (h.valid && h.n_colors ? h.n_colors : 1u);
+            const uint32_t pipeline = (uint32_t)dbg.flow_pipeline.value_or(4 * per_color >= threads * items);
+            if (quad)
+                hipLaunchKernelGGL(k_solve_flow_quad<DIAG>, dim3((unsigned)items), dim3(threads), 0, s, w->counters.p, sweeps, w->flow_epoch,
+                                   rows, sp.friction, inertia, stride, w->vel.p, w->flow_vel.p, (uint32_t)w->n, timeout_ticks, warm_sweep, warm);
+            else
+                hipLaunchKernelGGL(k_solve_flow<DIAG>, dim3((unsigned)items), dim3(threads), 0, s, w->counters.p, sweeps, w->flow_epoch,
+                                   rows, sp.friction, inertia, stride, w->vel.p, w->flow_vel.p, (uint32_t)w->n, timeout_ticks, pipeline,
+                                   warm_sweep, warm);
             return;
         }
-        // about one wave per SIMD or less: waiting waves must not crowd out the ones that can run
-        // four lanes per manifold while the hop latency is everything - and, where the launch may take the whole chip
-        // (w->flow_wide: three workgroups per CU, 672 of them), all the way up: 155k manifolds 0.250 ms against 0.446 with
-        // 224 workgroups, C3's 216k 0.325 (cluster kernel 0.513), the 1M cubes' 379k 0.405 (cluster kernel 0.235)
-        const bool quad = m_hint <= (dbg.flow_quad_max ? dbg.flow_quad_max : (w->flow_wide ? kFlowMaxManifolds : kFlowQuadMaxManifolds));
-        const uint32_t threads = 256u;
-        const uint32_t rows_per_item = quad ? threads / 4 : threads;
-        uint64_t items = (uint64_t)sweeps * ((m_hint * 5 / 4 + rows_per_item - 1) / rows_per_item) + 1;
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, w->device);
-        // statically dealt items need every workgroup running: a third of the chip's slots by default (beside other
-        // streams' kernels), seven eighths of them - the cluster kernel's share - where the GPU is this world's alone
-        // (small scenes are a chain of hand-offs, not throughput: C2's 10k manifolds 0.053 ms at 224 workgroups, 0.058 at 672)
-        const uint64_t most = quad ? (w->flow_wide && m_hint > 32768u ? (uint64_t)(3 * (cus - cus / 8)) : 224) : 256;
-        if (items > most) items = most;  // the remaining items are taken by the same workgroups
-        PHYS_PROF(w, PHYS_STAGE_SOLVE_FLOW);
-        // look one work item ahead (k_solve_flow) while a colour class keeps a good part of the launch busy; below that the
-        // solve is a chain of hand-offs and an item held ahead only waits (C3: 16k rows per colour, 65k lanes: +10 %;
-        // 1M cubes: 41k rows per colour: -10 %). PHYS_DEBUG_FLOW_PIPELINE=0/1 forces it (measurements; same bits).
-        const uint64_t per_color = m_hint / (h.valid && h.n_colors ? h.n_colors : 1u);
-        const uint32_t pipeline = (uint32_t)dbg.flow_pipeline.value_or(4 * per_color >= threads * items);
-#define PHYS_FLOW_ARGS dim3((unsigned)items), dim3(threads), 0, s, w->counters.p, sweeps, \
-                       w->flow_epoch, rows, sp.friction, inertia, stride, w->vel.p, w->flow_vel.p, (uint32_t)w->n, timeout_ticks
-        if (quad) { if (diag) hipLaunchKernelGGL(k_solve_flow_quad<true>, PHYS_FLOW_ARGS, warm_sweep, warm); else hipLaunchKernelGGL(k_solve_flow_quad<false>, PHYS_FLOW_ARGS, warm_sweep, warm); }
-        else { if (diag) hipLaunchKernelGGL(k_solve_flow<true>, PHYS_FLOW_ARGS, pipeline, warm_sweep, warm); else hipLaunchKernelGGL(k_solve_flow<false>, PHYS_FLOW_ARGS, pipeline, warm_sweep, warm); }
-#undef PHYS_FLOW_ARGS
-        return;
-    }
-    // colours [0, big) get a launch each; [big, n_colours) go through the single-workgroup tail
-    constexpr uint32_t kTailMax = 512;  // manifolds per colour the tail should take: one trip of the workgroup
-    uint32_t big = 0;
-    if (h.valid) {
-        big = h.n_colors;
-        while (big > 0 && h.color_count[big - 1] <= kTailMax) --big;
-        if (h.n_colors - big < 2) big = h.n_colors;  // a tail of one colour is just a slower launch
-    }
-    // four lanes per manifold while a colour is too small to fill the chip with one lane per manifold (measured
-    // crossover ~30k rows: 15k rows 10.2 vs 11.9 us per launch, 53k rows 18.3 vs 16.7, 85k rows 21.5 vs 18.7).
-    // PHYS_DEBUG_COLOR_KERNEL=lane / quad: one of them for every colour (A/B measurements, parity tests)
-    constexpr uint32_t kQuadColorMaxRows = 32768;
-    auto grid_for_quads = [&](uint64_t count) {
-        uint64_t b = (count * 5 / 4 + kQuadRowsPerGroup - 1) / kQuadRowsPerGroup + 1;
-        const uint64_t hi = (cap + kQuadRowsPerGroup - 1) / kQuadRowsPerGroup;
-        if (b > hi) b = hi;
-        if (b > 16384) b = 16384;
-        return dim3((unsigned)(b ? b : 1));
-    };
-    for (uint32_t it = 0; it < sweeps; ++it) {
-        const int apply_only = warm_sweep && it == 0 ? 1 : 0, last = it + 1 == sweeps ? 1 : 0;
-        for (uint32_t col = 0; col < big; ++col) {
-            PHYS_PROF(w, PHYS_STAGE_SOLVE);
-            if (!dbg.color_kernel_lane.value_or(h.color_count[col] > kQuadColorMaxRows)) {  // four lanes per manifold
-                if (diag)
-                    hipLaunchKernelGGL(k_solve_color_quad<true>, grid_for_quads(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
+        // colours [0, big) get a launch each; [big, n_colours) go through the single-workgroup tail
+        constexpr uint32_t kTailMax = 512;  // manifolds per colour the tail should take: one trip of the workgroup
+        uint32_t big = 0;
+        if (h.valid) {
+            big = h.n_colors;
+            while (big > 0 && h.color_count[big - 1] <= kTailMax) --big;
+            if (h.n_colors - big < 2) big = h.n_colors;  // a tail of one colour is just a slower launch
+        }
+        // four lanes per manifold while a colour is too small to fill the chip with one lane per manifold (measured
+        // crossover ~30k rows: 15k rows 10.2 vs 11.9 us per launch, 53k rows 18.3 vs 16.7, 85k rows 21.5 vs 18.7).
+        // PHYS_DEBUG_COLOR_KERNEL=lane / quad: one of them for every colour (A/B measurements, parity tests)
+        constexpr uint32_t kQuadColorMaxRows = 32768;
+        auto grid_for_quads = [&](uint64_t count) {
+            uint64_t b = (count * 5 / 4 + kQuadRowsPerGroup - 1) / kQuadRowsPerGroup + 1;
+            const uint64_t hi = (cap + kQuadRowsPerGroup - 1) / kQuadRowsPerGroup;
+            if (b > hi) b = hi;
+            if (b > 16384) b = 16384;
+            return dim3((unsigned)(b ? b : 1));
+        };
+        for (uint32_t it = 0; it < sweeps; ++it) {
+            const int apply_only = warm_sweep && it == 0 ? 1 : 0, last = it + 1 == sweeps ? 1 : 0;
+            for (uint32_t col = 0; col < big; ++col) {
+                PHYS_PROF(w, PHYS_STAGE_SOLVE);
+                if (!dbg.color_kernel_lane.value_or(h.color_count[col] > kQuadColorMaxRows))  // four lanes per manifold
+                    hipLaunchKernelGGL(k_solve_color_quad<DIAG>, grid_for_quads(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
                                        sp.friction, inertia, stride, w->vel.p, (uint32_t)w->n, apply_only, last, warm);
                 else
-                    hipLaunchKernelGGL(k_solve_color_quad<false>, grid_for_quads(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
-                                       sp.friction, inertia, stride, w->vel.p, (uint32_t)w->n, apply_only, last, warm);
-                continue;
+                    hipLaunchKernelGGL(k_solve_color<DIAG>, grid_for_count(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
+                                       sp.friction, inertia, stride, w->vel.p, apply_only, last, warm);
             }
-            if (diag)
-                hipLaunchKernelGGL(k_solve_color<true>, grid_for_count(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
-                                   sp.friction, inertia, stride, w->vel.p, apply_only, last, warm);
-            else
-                hipLaunchKernelGGL(k_solve_color<false>, grid_for_count(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
-                                   sp.friction, inertia, stride, w->vel.p, apply_only, last, warm);
+            PHYS_PROF(w, PHYS_STAGE_SOLVE_TAIL);
+            hipLaunchKernelGGL(k_solve_tail<DIAG>, dim3(1), dim3(kTailThreads), 0, s, w->counters.p, big, rows, sp.friction,
+                               inertia, stride, w->vel.p, apply_only, last, warm);
         }
-        PHYS_PROF(w, PHYS_STAGE_SOLVE_TAIL);
-        if (diag)
-            hipLaunchKernelGGL(k_solve_tail<true>, dim3(1), dim3(kTailThreads), 0, s, w->counters.p, big, rows, sp.friction,
-                               inertia, stride, w->vel.p, apply_only, last, warm);
-        else
-            hipLaunchKernelGGL(k_solve_tail<false>, dim3(1), dim3(kTailThreads), 0, s, w->counters.p, big, rows, sp.friction,
-                               inertia, stride, w->vel.p, apply_only, last, warm);
-    }
+    });
 }
 
 }  // namespace phys

@@ -594,6 +594,25 @@ def _probe(args, env_extra, timeout=900):
     return out.stdout
 
 
+@pytest.mark.parametrize("a,b,env", [
+    ("percolour", "default", {"PHYS_DEBUG_COLOR_KERNEL": "quad"}),  # k_solve_color_quad for every colour above the tail
+    ("percolour", "default", {"PHYS_DEBUG_COLOR_KERNEL": "lane"}),  # k_solve_color
+    ("default", "percolour", {}),                                   # k_solve_flow_quad
+    ("default", "percolour", {"PHYS_DEBUG_FLOW_QUAD_MAX": "1"}),    # k_solve_flow
+], ids=["color_quad", "color_lane", "flow_quad", "flow_lane"])
+def test_each_row_solver_kernel_equals_the_oracle(a, b, env):
+    """The profile names both per-colour kernels "solve" and both dataflow kernels "solve_flow", so a scene that picks
+    one of them says nothing about the other. Each kernel is forced here on a 33k tower whose colours exceed the tail's
+    512 rows (cluster solver off), against the other solver path and the oracle."""
+    out = _probe(["c5:16:130:16", "--pre", "4", "--steps", "8", "--a", a, "--b", b, "--oracle"],
+                 dict(env, PHYS_DEBUG_NO_CLUSTER="1"))
+    fields = dict(f.split("=", 1) for f in out.split()[1:])
+    ran = {p: set(fields[k].split("+")) for p, k in ((a, "a_ran"), (b, "b_ran"))}
+    assert out.startswith("identical") and fields["oracle"] == "identical", out
+    assert ran["default"] == {"solve_flow"}, out
+    assert "solve" in ran["percolour"] and ran["percolour"] <= {"solve", "solve_tail"}, out
+
+
 @pytest.mark.parametrize("per_cu,rows", [("3", "fewer than 256"), ("1", "257 to 512")])
 def test_cluster_rows_read_back_by_the_lane_that_stored_them(per_cu, rows):
     """Regression for round 2's d106316 (`s_waitcnt vmcnt(0)` before a lane re-reads the impulses and masses of the row
