@@ -4,8 +4,14 @@
 A "step" is one PhysicsState::update over one synthetic scene resident in HBM (SURVEY.md §8 row D).
 
 N = 1 workload: C5 = BASELINE.json configs[4], the 256k stacked-box tower: the LARGEST single-GPU configuration
-(BASELINE.json's metric is not quoted on one config). The other single-GPU configs (the 1M-cube north_star target,
-C3, C2) follow as sub-records under "other_workloads", each with its own timing, roofline and CPU sample.
+(BASELINE.json's metric is not quoted on one config). With `--full`, the other single-GPU configs (the 1M-cube
+north_star target, C3, C2, ...) follow as sub-records under "other_workloads", each with its own timing, roofline and
+CPU sample.
+
+A plain run (no `--full`) does only what the headline figure needs: it sets up, runs the timed repetitions below,
+writes `--dump-outputs` if asked, and prints the result line. `--full` adds everything else, each on worlds of its own
+after the timed repetitions: the 64-step period, the roofline and stage table of one more profiled window, the CPU
+baseline, the copy ceiling, the other workloads and, for strong scaling, the check of the pair union against one world.
 
 Timing: the window [preroll + W warm-up steps, then EXACTLY K timed steps] is repeated `--reps` times (default 5),
 every repetition on a freshly created world stepped from the same initial scene, so every repetition times the
@@ -22,8 +28,8 @@ Prints ONE JSON line (rank 0), short enough for a driver that keeps only the tai
 the other workloads appear there with their headline figures only, and the prose notes are left out. `--record FILE`
 writes the whole record, every sub-record in full, to FILE as one JSON line (the input of tools/results_table.py).
 `--dump-outputs DIR` writes what the last timed step computed as .npy files, for comparing two builds output for output.
-`roofline` describes the dominant kernel of the timed window, timed live with HIP events on the library's own stream
-(phys_profile_*) over the SAME window on one more fresh world. `traffic` and
+The fields below are those of `--full`. `roofline` describes the dominant kernel of the timed window, timed live with
+HIP events on the library's own stream (phys_profile_*) over the SAME window on one more fresh world. `traffic` and
 `avg_kernel_us_rocprofv3` come from the committed rocprofv3 passes of `bench.py --profile-window` and are emitted
 only when that pass covered the same window at the same scene state (profiles/r2_<workload>_window.json says which),
 otherwise null. `cpu_baseline` is the CPU oracle (a scalar C++ restatement; the Rust reference cannot be built here)
@@ -467,8 +473,9 @@ def cpu_baseline(scene, state, window_start, sample_steps, budget_s=14.0):
 
 
 def measure_workload(rig, args, preroll, reps, with_cpu, want_outputs=False):
-    """Timed repetitions + profile window + (optionally) CPU sample of one workload on this rank's rig. With
-    `want_outputs`, rec["outputs"] holds what the last timed step of the last repetition computed."""
+    """Timed repetitions of one workload on this rank's rig; with `--full` also the 64-step period, the profile window
+    and (optionally) the CPU sample. With `want_outputs`, rec["outputs"] holds what the last timed step of the last
+    repetition computed."""
     times, st, cross, state, outputs = [], None, 0, None, None
     for r in range(reps):
         e, st, cross, s, o = timed_repetition(rig, preroll, args.warmup, args.steps, want_state=(with_cpu and r == 0),
@@ -496,6 +503,8 @@ def measure_workload(rig, args, preroll, reps, with_cpu, want_outputs=False):
     }
     if outputs is not None:
         rec["outputs"] = outputs
+    if not args.full:
+        return rec
     if (rig.scene.flags & 1) and not (rig.scene.flags & 8) and st["n_manifolds"] > 0:  # FLAG_COLLISIONS, not broad-phase-only
         sps, slowest, med, hitch, first, last = timed_period(rig, preroll, args.warmup)
         rec["full_period"] = {"steps": 64, "steps_per_sec": round(sps, 2), "slowest_step_ms": round(slowest, 3),
@@ -554,9 +563,13 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed window (median reported)")
     ap.add_argument("--workload", default="c5", choices=["c1", "c2", "c3", "c5", "t1m", "c4", "t1m_settled", "ref_1m", "ref_cg"])
     ap.add_argument("--preroll", type=int, default=-1, help="untimed set-up steps in front of the warm-up (default per workload)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed window, measure and check everything else: the 64-step period, the roofline and "
+                         "stage table of one more profiled window, the CPU baseline, the copy ceiling, the other single-GPU "
+                         "workloads (N=1, C5) and the strong-scaling pair union; a plain run only times the window")
     ap.add_argument("--cpu-steps", type=int, default=4, help="timed oracle steps of the CPU sample (bounded by 14 s per variant)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other single-GPU workloads appended at N=1")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the other single-GPU workloads appended at N=1")
     ap.add_argument("--weak", action="store_true",
                     help="--workload c4 --gpus N: N workload-shaped slabs side by side (weak scaling) instead of the ONE 1M-body "
                          "scene cut into N equal-count slabs (strong scaling, BASELINE config 4: the default for c4)")
@@ -637,7 +650,7 @@ def main():
             dist.destroy_process_group()
         return
 
-    with_cpu = rank == 0 and not sharded and not args.no_cpu_baseline
+    with_cpu = args.full and rank == 0 and not sharded and not args.no_cpu_baseline
     rec = measure_workload(rig, args, preroll, args.reps, with_cpu, want_outputs=args.dump_outputs is not None)
     if args.dump_outputs is not None:
         dump_outputs(rec.pop("outputs"), args.dump_outputs, prefix=f"rank{rank}_" if world_size > 1 else "")
@@ -687,7 +700,7 @@ def main():
         if "full_period" in rec:
             out["full_period"] = rec["full_period"]
 
-    if rig.strong:
+    if rig.strong and args.full:
         # the union over ranks of (local pairs, cross pairs) must equal the pair count of the ONE world holding the whole
         # scene at the same step (broad-phase-only bodies fall alike on every rank: identical positions, identical AABBs)
         total_pairs = int(round(rig.sum_over_ranks(float(rec["scene_stats"]["n_pairs"] + rec.get("cross_pairs_rank", 0)))))
@@ -700,7 +713,7 @@ def main():
             w1.close()
             out["config"]["pairs_union_check"] = {"sum_over_ranks_local_plus_cross": total_pairs, "single_world": one,
                                                   "equal": total_pairs == one}
-    if rank == 0 and not sharded and not args.no_extra and args.workload == "c5":
+    if args.full and rank == 0 and not sharded and not args.no_extra and args.workload == "c5":
         # the other single-GPU configurations, measured the same way (fewer repetitions: they are sub-records)
         others = {}
         for wl in ("t1m", "c3", "c2", "c4", "t1m_settled", "ref_1m", "ref_cg"):

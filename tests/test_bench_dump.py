@@ -74,6 +74,30 @@ def test_bench_dump_is_the_same_from_run_to_run(tmp_path):
     assert not np.array_equal(np.load(a / "pos.npy"), np.load(c / "pos.npy"))
 
 
+HEADLINE_FIELDS = ("metric", "value", "unit", "higher_is_better", "dtype", "steps", "warmup", "ms_per_step", "steps_per_sec",
+                   "repetitions", "scene_stats")
+FULL_ONLY_FIELDS = ("roofline", "stages", "cpu_baseline", "full_period")
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_window_and_full_adds_the_rest():
+    """A plain run prints the headline figures and nothing that takes worlds of its own; --full adds the period, the
+    profiled window and the CPU baseline to the same headline fields."""
+    common = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--steps", "4", "--warmup", "2", "--reps", "1"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--cpu-steps", "1"])):
+        out = subprocess.run(common + extra, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines[mode] = json.loads(out.stdout.strip().splitlines()[-1])
+    for mode, line in lines.items():
+        assert all(k in line for k in HEADLINE_FIELDS), (mode, sorted(line))
+        assert line["metric"] == "rigid_body_steps_per_sec" and line["unit"] == "body-steps/s" and line["steps"] == 4
+        assert line["value"] > 0 and line["ms_per_step"] > 0
+    assert not any(k in lines["plain"] for k in FULL_ONLY_FIELDS), sorted(lines["plain"])
+    assert all(k in lines["full"] for k in FULL_ONLY_FIELDS), sorted(lines["full"])
+    assert lines["plain"]["scene_stats"] == lines["full"]["scene_stats"]  # the same K steps of the same trajectory
+
+
 def test_result_line_keeps_the_headline_of_every_workload():
     """The printed line must survive a driver that keeps only the tail of the output: the other workloads appear with
     their headline figures, the flagship record in full."""

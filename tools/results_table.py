@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The results table of DESIGN.md section 6 from a whole bench record (`bench.py --record FILE`, or a committed one):
+"""The results table of DESIGN.md section 6 from a whole bench record (`bench.py --full --record FILE`, or a committed one):
     python tools/results_table.py profiles/r3_bench.json"""
 import json
 import sys
