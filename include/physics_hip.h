@@ -198,7 +198,8 @@ int32_t phys_block_spmv(int32_t device, uint64_t nrows, uint64_t ncols, uint64_t
 int32_t phys_broadphase(phys_world* w, uint32_t* pairs_out /*2*cap*/, uint64_t cap, uint64_t* n_pairs);
 /* AABBs as computed by the device: min xyz, max xyz per body */
 int32_t phys_get_aabbs(phys_world* w, float* out /*6n*/);
-/* contact manifolds of the last update, sorted by (body_a, body_b); body_b = 0xFFFFFFFF = ground.
+/* contact manifolds of the last update, sorted by (body_a, body_b); body_b = 0xFFFFFFFF = ground,
+ * PHYS_STATIC_ID_BIT | k = static collider k.
  * rows: per manifold 2 u32 ids + u32 count; per point (4 slots): position xyz + depth. NULLs allowed. */
 int32_t phys_get_manifolds(phys_world* w, uint32_t* ids_out /*2*cap*/, uint32_t* counts_out /*cap*/,
                            float* normals_out /*3*cap*/, float* points_out /*16*cap*/, uint64_t cap,
@@ -224,7 +225,9 @@ int32_t phys_get_color_counts(phys_world* w, uint32_t* counts_out /*64*/);
  *     surface normal at the hit point (a box: the face of the slab the ray enters last).
  *   - ignore_body[i] (NULL = none), when below n_bodies, is skipped by ray i (a ray fired from inside a body); a value
  *     at or above n_bodies ignores nothing.
- *   - the result is the least (t, id): an exact tie in t goes to the smaller id, and the ground loses ties to bodies. A
+ *   - static colliders (phys_set_static_bodies) are targets too, id PHYS_STATIC_ID_BIT | k; ignore_body never names one.
+ *   - the result is the least (t, id): an exact tie in t goes to the smaller id (bodies, then statics), and the ground
+ *     loses ties to both. A
  *     ray's result depends only on that ray and the world state: bit-identical across calls and ray orders.
  *   - no bodies: every ray misses or hits the ground. n_rays == 0 is a no-op.
  *   - PHYS_ERR_INVALID_ARG: a NULL origin, dir, body_out or t_out, or n_rays >= 2^31.
@@ -243,11 +246,38 @@ int32_t phys_raycast(phys_world* w, uint64_t n_rays, const float* origin /*3n*/,
 int32_t phys_raycast_device(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                             const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out);
 
+/* --- static colliders: immovable SPHERE / BOX shapes that bodies collide with and rays hit. Not bodies. ---
+ * Level geometry (floors, walls, ramps, pillars, container sides) that never moves: no velocity, no mass, no colour of
+ * its own. A manifold against static k is one-sided like a ground manifold (body A against a partner at rest with zero
+ * inverse mass and inertia); it names the collider PHYS_STATIC_ID_BIT | k as body_b, which sorts after every body id
+ * and before PHYS_GROUND_ID, and ray casts report the same id in body_out. Statics are NOT bodies: they appear in none
+ * of n_bodies, the transforms, velocities, forces, instance matrices, AABBs, constraints, phys_device_view or halo
+ * records. A sharded world's ranks each set the statics their slab needs; nothing about them is exchanged.
+ *   - phys_set_static_bodies replaces the whole static set (n = 0 clears it) and is independent of phys_set_bodies:
+ *     neither clears the other's set. It makes the world forget its persistent colours and warm-start impulses, like
+ *     phys_set_bodies. shape_type and half_extent are required (SPHERE: radius half_extent[0]; BOX: half extents along
+ *     the collider's axes); rot NULL = identity. PHYS_ERR_INVALID_ARG: n >= 0x7FFFFFFE, a shape other than SPHERE or
+ *     BOX, a non-finite pose or half extent, a negative half extent, a NULL array that is required.
+ *   - every update (PHYS_FLAG_COLLISIONS) finds the (body, static) pairs whose fattened AABBs overlap, in the order
+ *     (body ascending, static ascending); their capacity is automatic: the first update after phys_set_static_bodies or
+ *     phys_set_bodies counts them before it stores them (one host wait) and sizes the buffer at 1.5 times that, later
+ *     updates grow it from the counts they report. An update whose pairs outgrow it after that (bodies crowding onto
+ *     many more statics than before) raises overflow bit 0 like the candidate pairs: its solve is skipped, phys_sync
+ *     reports PHYS_ERR_CAPACITY, and the following updates have room.
+ *   - phys_get_static_stats: the static count, and the (body, static) pairs and manifolds of the last update; any
+ *     output pointer may be NULL. phys_stats.n_manifolds / n_contacts include the static manifolds,
+ *     n_ground_manifolds does not.
+ * Structure and cost: DESIGN.md section 10. */
+#define PHYS_STATIC_ID_BIT 0x80000000u /* manifold body_b / ray body_out = PHYS_STATIC_ID_BIT | k for static k */
+int32_t phys_set_static_bodies(phys_world* w, uint64_t n, const float* pos /*3n*/, const float* rot_ijkw /*4n, NULL = identity*/,
+                               const uint32_t* shape_type /*n*/, const float* half_extent /*3n*/);
+int32_t phys_get_static_stats(phys_world* w, uint64_t* n_static, uint64_t* n_static_pairs, uint64_t* n_static_manifolds);
+
 /* --- per-stage device timing (HIP events on the world's stream), for bench.py's roofline --- */
 #define PHYS_STAGE_STEP_FULL 0u     /* gravity + RigidBody::step, one kernel (no collisions) */
 #define PHYS_STAGE_VELOCITY_AABB 1u /* gravity + velocity half + AABB */
 #define PHYS_STAGE_GRID 2u          /* cell assign, scan, scatter */
-#define PHYS_STAGE_PAIRS 3u         /* k_find_pairs */
+#define PHYS_STAGE_PAIRS 3u         /* k_find_pairs (+ the (body, static) pairs of worlds with static colliders) */
 #define PHYS_STAGE_NARROW 4u        /* k_narrowphase */
 #define PHYS_STAGE_COLOR 5u         /* colouring rounds */
 #define PHYS_STAGE_ROWS 6u          /* colour-major renumbering + solver_prep */

@@ -9,7 +9,8 @@
  * themselves with closed-form known answers.
  *
  * Conventions: manifold normal points from body A to body B; depth > 0 is penetration, depth < 0 a
- * speculative gap inside the contact margin. Body B may be the ground plane (PHYS_GROUND_ID).
+ * speculative gap inside the contact margin. Body B may be the ground plane (PHYS_GROUND_ID) or a static collider
+ * (PHYS_STATIC_ID_BIT | k: collide_pair with B's shape and pose read from the static set).
  */
 #ifndef PHYS_SPEC_COLLIDE_H
 #define PHYS_SPEC_COLLIDE_H
@@ -19,6 +20,12 @@
 #include "vec.h"
 
 #define PHYS_GROUND_ID 0xFFFFFFFFu
+/* body B of a one-sided manifold: the ground (PHYS_GROUND_ID) or a static collider (PHYS_STATIC_ID_BIT | k). Body and
+ * ghost ids stay below 2^31, so for a world without static colliders this is exactly b == PHYS_GROUND_ID. */
+#ifndef PHYS_STATIC_ID_BIT
+#define PHYS_STATIC_ID_BIT 0x80000000u
+#endif
+#define PHYS_IS_STATIC_PARTNER(b) (((b) & PHYS_STATIC_ID_BIT) != 0u)
 #define PHYS_SPEC_SHAPE_NONE 0u
 #define PHYS_SPEC_SHAPE_SPHERE 1u
 #define PHYS_SPEC_SHAPE_BOX 2u

@@ -26,6 +26,7 @@ FLAG_NO_WARM_START = 256
 GROUND_ID = 0xFFFFFFFF
 RAY_MISS = 0xFFFFFFFE    # PHYS_RAY_MISS: no hit within max_t
 RAY_GROUND = 0xFFFFFFFF  # PHYS_RAY_GROUND: the ground plane
+STATIC_ID_BIT = 0x80000000  # PHYS_STATIC_ID_BIT: manifold body_b / ray body = STATIC_ID_BIT | k for static collider k
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -162,6 +163,8 @@ PROTOTYPES = {
     "phys_raycast": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, u32p, u32p, f32p, f32p]),
     "phys_raycast_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "phys_set_static_bodies": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, u32p, f32p]),
+    "phys_get_static_stats": (C.c_int32, [C.c_void_p, u64p, u64p, u64p]),
     "phys_profile_enable": (C.c_int32, [C.c_void_p, C.c_int32]),
     "phys_profile_get": (C.c_int32, [C.c_void_p, C.POINTER(PhysProfile)]),
     "phys_get_device_view": (C.c_int32, [C.c_void_p, C.POINTER(PhysDeviceView)]),

@@ -3,6 +3,7 @@
 // is no CPU fallback anywhere in this library.
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
@@ -64,6 +65,7 @@ void poll_snapshots(phys_world* w) {
         const StepCounters& c = *w->h_snap[k];
         w->snap_pending[k] = false;
         w->host_sticky_overflow |= c.overflow | c.sticky_overflow;  // latched until phys_sync reports it
+        if (c.n_static_pairs > w->static_pairs_seen) w->static_pairs_seen = c.n_static_pairs;  // sizes the static pairs (static.hip)
         if (c.overflow) continue;
         w->hint.valid = true;
         w->hint.n_manifolds = c.n_manifolds;
@@ -219,14 +221,16 @@ int32_t phys_destroy(phys_world* w) {
     DevBuf<float>* fb[] = {&w->pos, &w->rot, &w->vel, &w->force, &w->torque, &w->inv_inertia_diag,
                            &w->inv_inertia, &w->half_extent, &w->aabb, &w->cg_x, &w->cg_r, &w->cg_p, &w->cg_ap,
                            &w->cg_rhs, &w->cg_c, &w->cg_scratch, &w->cg_jl, &w->geo, &w->man_geo_prev, &w->man_imp, &w->man_imp_prev, &w->man_geo, &w->row_n,
-                           &w->row_pt, &w->row_tb, &w->row_acc, &w->row_all, &w->flow_vel, &w->sorted_box, &w->slot_box, &w->rc_records, &w->rc_in, &w->rc_out};
+                           &w->row_pt, &w->row_tb, &w->row_acc, &w->row_all, &w->flow_vel, &w->sorted_box, &w->slot_box, &w->rc_records, &w->rc_in, &w->rc_out,
+                           &w->st_geo, &w->st_rc, &w->st_box};
     for (auto* b : fb) b->free();
     DevBuf<uint32_t>* ub[] = {&w->shape, &w->global_id, &w->cg_status, &w->bucket_of, &w->bucket_count,
                               &w->bucket_start, &w->bucket_cursor, &w->sorted_ids, &w->slot_ids, &w->grid_ovf, &w->scan_block_sums, &w->pairs,
                               &w->man_a, &w->man_b, &w->man_color, &w->row_hdr, &w->halo_block_counts,
                               &w->man_prev, &w->cluster_slot, &w->cluster_body, &w->body_shared, &w->active_flag, &w->active_rank, &w->seg_count, &w->seg_start, &w->man_rank,
                               &w->row_src, &w->cross_pairs, &w->color_block_hist, &w->cg_cols,
-                              &w->rc_header, &w->rc_count, &w->rc_start, &w->rc_tile_sum};
+                              &w->rc_header, &w->rc_count, &w->rc_start, &w->rc_tile_sum,
+                              &w->st_cell_start, &w->st_cell_ids, &w->st_large, &w->st_count, &w->st_block, &w->st_pairs};
     for (auto* b : ub) b->free();
     w->man_prio.free(); w->color_state.free(); w->bucket_count.free(); w->step_zero.free();
     w->d_constraints.free(); w->counters.free();
@@ -268,6 +272,7 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     w->grid_valid = false;
     w->sorted_grid_valid = false;
     w->hint = StepHint();
+    w->static_pairs_sized = false;  // static.hip: the next update measures its (body, static) pairs
     for (int k = 0; k < phys_world::kSnapRing; ++k) w->snap_pending[k] = false;  // the stream was synchronised above
     if (n == 0) return PHYS_OK;
 
@@ -426,6 +431,8 @@ static int32_t enqueue_update(phys_world* w, float dt) {
         launch_step_velocity_aabb(w, dt, gravity_pending, /*zero_step=*/!restart_extent, have_constraints);
         launch_broadphase(w);
         if (!(w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY)) {
+            const int32_t rc = launch_static_pairs(w);  // static colliders only (phys_set_static_bodies): nothing otherwise
+            if (rc != PHYS_OK) return rc;
             launch_narrowphase(w);
             launch_coloring(w);
             launch_solver(w, dt);
@@ -468,6 +475,7 @@ int32_t phys_sync(phys_world* w) {
     if (rc != PHYS_OK) return rc;
     poll_snapshots(w);  // the stream is idle: every snapshot in flight is adopted now, none can bring reported bits back later
     const uint32_t bits = w->h_counters->overflow | w->h_counters->sticky_overflow | w->host_sticky_overflow;
+    if (w->h_counters->n_static_pairs > w->static_pairs_seen) w->static_pairs_seen = w->h_counters->n_static_pairs;
     w->host_sticky_overflow = 0;
     if (w->h_counters->sticky_overflow) {
         PHYS_HIP_TRY(hipMemsetAsync(&w->counters.p->sticky_overflow, 0, sizeof(uint32_t), w->stream));
@@ -654,6 +662,44 @@ int32_t phys_get_stats(phys_world* w, phys_stats* out) {
     out->n_halo_records = c.n_halo + c.n_halo_low;  // both faces of a neighbour exchange
     out->n_cross_pairs = c.n_cross_pairs;
     out->n_ghosts = c.n_ghosts;
+    return PHYS_OK;
+}
+
+int32_t phys_set_static_bodies(phys_world* w, uint64_t n, const float* pos, const float* rot, const uint32_t* shape_type,
+                               const float* half_extent) {
+    // the arguments first: they are checked without a world or a device
+    if (n >= 0x7FFFFFFEull) return fail(PHYS_ERR_INVALID_ARG, "too many static colliders (ids are PHYS_STATIC_ID_BIT | k below 0x7FFFFFFE)");
+    if (n && (!pos || !shape_type || !half_extent)) return fail(PHYS_ERR_INVALID_ARG, "static colliders need pos, shape_type and half_extent");
+    for (uint64_t k = 0; k < n; ++k) {
+        if (shape_type[k] != PHYS_SHAPE_SPHERE && shape_type[k] != PHYS_SHAPE_BOX)
+            return fail(PHYS_ERR_INVALID_ARG, ("static collider " + std::to_string(k) + ": shape is neither SPHERE nor BOX").c_str());
+        bool finite = true, negative = false;
+        for (int a = 0; a < 3; ++a) {
+            finite = finite && std::isfinite(pos[3 * k + a]) && std::isfinite(half_extent[3 * k + a]);
+            negative = negative || half_extent[3 * k + a] < 0.0f;
+        }
+        if (rot)
+            for (int a = 0; a < 4; ++a) finite = finite && std::isfinite(rot[4 * k + a]);
+        if (!finite) return fail(PHYS_ERR_INVALID_ARG, ("static collider " + std::to_string(k) + ": non-finite pose or half extent").c_str());
+        if (negative) return fail(PHYS_ERR_INVALID_ARG, ("static collider " + std::to_string(k) + ": negative half extent").c_str());
+    }
+    ENTER(w);
+    // the colour table and the warm-start records name static ids, which are stale now (as phys_set_bodies does); also
+    // when the new set fails to upload below (the world then holds no statics)
+    w->ctab_valid = false;
+    w->color_epoch = 0;
+    w->static_pairs_seen = 0;
+    return static_set(w, n, pos, rot, shape_type, half_extent);
+}
+
+int32_t phys_get_static_stats(phys_world* w, uint64_t* n_static, uint64_t* n_static_pairs, uint64_t* n_static_manifolds) {
+    ENTER(w);
+    int32_t rc = fetch_counters(w); if (rc) return rc;
+    const StepCounters& c = *w->h_counters;
+    const bool on = w->n_static != 0;  // (the counters of an update before the set was cleared say nothing about it)
+    if (n_static) *n_static = w->n_static;
+    if (n_static_pairs) *n_static_pairs = on ? c.n_static_pairs : 0u;
+    if (n_static_manifolds) *n_static_manifolds = on ? c.n_static_manifolds : 0u;
     return PHYS_OK;
 }
 

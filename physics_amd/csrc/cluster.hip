@@ -269,7 +269,7 @@ __global__ __launch_bounds__(256) void k_cluster_keys(uint64_t max_manifolds, co
             if (c >= (uint32_t)PHYS_MAX_COLORS) continue;  // (man_rank[m] = ~0 below)
             atomicAdd(&s_hist[c], 1u);
             const uint32_t ha = cluster_home(cluster_slot, a, slots);
-            const uint32_t hb = b == PHYS_GROUND_ID ? kNoHome : cluster_home(cluster_slot, b, slots);
+            const uint32_t hb = PHYS_IS_STATIC_PARTNER(b) ? kNoHome : cluster_home(cluster_slot, b, slots);
             const uint32_t owner = cluster_row_owner(a, ha, hb, clusters);
             const uint32_t key = owner * PHYS_MAX_COLORS + c;
             uint32_t s = (key * 2654435761u) >> (32 - 11);  // 2048 slots, at most 1024 keys: the walk ends
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(256) void k_cluster_place(uint64_t max_manifolds, c
         if (r == 0xFFFFFFFFu) continue;
         const uint32_t a = man_a[m], b = man_b[m];
         const uint32_t ha = cluster_home(cluster_slot, a, slots);
-        const uint32_t hb = (ha != kNoHome || b == PHYS_GROUND_ID) ? kNoHome : cluster_home(cluster_slot, b, slots);
+        const uint32_t hb = (ha != kNoHome || PHYS_IS_STATIC_PARTNER(b)) ? kNoHome : cluster_home(cluster_slot, b, slots);
         row_src[seg_start[cluster_row_owner(a, ha, hb, clusters) * PHYS_MAX_COLORS + man_color[m]] + r] = m;
     }
 }
@@ -546,7 +546,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                 const bool pubA = (info >> 13) & 1u, pubB = (info >> 29) & 1u;
                 geo_manifold_t gm;
                 gm.count = (int)h.z;
-                gm.has_b = h.y != PHYS_GROUND_ID;
+                gm.has_b = !PHYS_IS_STATIC_PARTNER(h.y);
                 gm.n = v3_make(nn.x, nn.y, nn.z);
                 tangent_basis(gm.n, &gm.t1, &gm.t2);
                 {

@@ -245,6 +245,12 @@ bool cluster_plan_dynamic(phys_world* w);  // cluster.hip: clusters / slots of t
 void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float friction, const float* inertia, uint32_t stride,
                           bool diag, long long timeout_ticks);
 
+// static.hip: the static set (arguments checked by the caller), the per-update (body, static) pairs, and what k_narrowphase
+// takes of them (cap 0 / null pointers: no static colliders)
+int32_t static_set(phys_world* w, uint64_t n, const float* pos, const float* rot, const uint32_t* shape, const float* half_extent);
+int32_t launch_static_pairs(phys_world* w);
+void static_narrow_args(const phys_world* w, uint64_t* cap, const uint32_t** pairs, const float** geo);
+
 // raycast.hip: builds the query's grid from the current poses and traces the rays (device pointers), all on w->stream
 int32_t launch_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                        const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out);

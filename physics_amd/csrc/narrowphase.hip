@@ -2,7 +2,8 @@
 // that orders the solver, for gfx950. No reference counterpart; the arithmetic is the normative scalar
 // spec of include/spec/collide.h and the colouring rule of include/spec/contact_solve.h.
 //
-// k_narrowphase: one lane per work item (ground test of a body, or one candidate pair); manifolds are
+// k_narrowphase: one lane per work item (ground test of a body, one candidate pair, or - worlds with static colliders - one
+//   (body, static) pair of static.hip, B's shape and pose read from the static set); manifolds are
 //   compacted per workgroup (wavefront ballot + popcount prefix, wave totals through LDS, ONE global
 //   atomic per workgroup) and written as 100-byte records. Emission order is arbitrary. A manifold that
 //   existed in the previous update keeps its colour (hash-table probe); the others publish round 0 of the colouring.
@@ -33,7 +34,7 @@ __device__ __forceinline__ geom_t load_geom(uint32_t i, const float* __restrict_
 
 // kNpThreads: 128 for small scenes (latency-bound: more workgroups in flight, the LDS slice of the clipper
 // halves), 512 for everything else (launch_narrowphase)
-template <int kNpThreads, int kNpItems>
+template <int kNpThreads, int kNpItems, bool kStatics>
 __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
     uint32_t n_ground /* bodies tested against the plane (0 = no ground) */, uint32_t n_owned /* pairs whose FIRST body is at
     or beyond this index are skipped (= all body slots: the ghosts of a sharded world collide like everybody else) */,
@@ -49,7 +50,9 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
     const uint32_t* __restrict__ man_prev /* warm starting on (non-null; the index of the pair's previous manifold itself
     travels in the manifold record) */,
     float* __restrict__ man_imp /* ... and this update's impulse records, zeroed here (a solve that never runs leaves zeros) */,
-    StepCounters* __restrict__ ctr) {
+    StepCounters* __restrict__ ctr,
+    uint64_t max_static_pairs /* kStatics: (body, static) pairs of static.hip, the third kind of work item */,
+    const uint32_t* __restrict__ static_pairs, const float* __restrict__ static_geo /* 16 floats per static, the layout of geo */) {
     // per-wave totals of a trip, in two sets used alternately: a wave may start the next trip (and post its totals) while
     // another still reads this trip's to place its manifolds - there is no barrier at the end of a trip any more
     __shared__ uint32_t wtot[2][4][kNpThreads / 64];
@@ -63,10 +66,17 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
     // uses no scratch memory at all (a rule of this library - tests/test_build_rules.py)
     const uint32_t np_raw = ctr->n_pairs;
     const uint32_t n_pairs = (uint64_t)np_raw < max_pairs ? np_raw : (uint32_t)max_pairs;
-    const uint32_t total = n_ground + n_pairs;
+    uint32_t n_static = 0;
+    if (kStatics) {
+        const uint32_t ns_raw = ctr->n_static_pairs;
+        n_static = (uint64_t)ns_raw < max_static_pairs ? ns_raw : (uint32_t)max_static_pairs;
+    }
+    const uint32_t n_body_items = n_ground + n_pairs;
+    const uint32_t total = n_body_items + n_static;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t trip = 0;
     uint32_t acc_pts = 0, acc_ground = 0, acc_unc = 0;  // thread 0: statistics of this workgroup's trips, added once at the end
+    uint32_t acc_static = 0;  // kStatics, every wave: its static manifolds, added once at the end
     // A trip is a chain of dependent round trips - pair, shapes, [test], table entry, `used` masks, barrier, slot
     // reservation, barrier, stores - that the 12 waves a CU's LDS admits cannot hide from each other. A lane therefore
     // tests kNpItems work items per trip, one after the other, and everything behind the test - the ballots, the two
@@ -106,8 +116,11 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
                     if (ga.type != PHYS_SPEC_SHAPE_NONE) collide_ground(&ga, ground, margin, &m, ws);
                 }
             } else if (idx < total) {
-                const uint2 pr = reinterpret_cast<const uint2*>(pairs)[idx - n_ground];
-                a = pr.x; b = pr.y;
+                // a candidate pair of two bodies, or (kStatics, behind them) a body and static collider k: B = the static
+                const bool body_pair = !kStatics || idx < n_body_items;
+                const uint2 pr = body_pair ? reinterpret_cast<const uint2*>(pairs)[idx - n_ground]
+                                           : reinterpret_cast<const uint2*>(static_pairs)[idx - n_body_items];
+                a = pr.x; b = body_pair ? pr.y : (PHYS_STATIC_ID_BIT | pr.y);
                 if (a < n_owned) {
                     // the colour-table entry this pair would keep its colour from (a random 16-byte read): asked for NOW, so
                     // that it travels while the shapes are fetched and tested instead of being one more dependent round trip
@@ -121,7 +134,7 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
                         have_early = true;
                     }
                     const geom_t ga = load_geom(a, geo);
-                    const geom_t gb = load_geom(b, geo);
+                    const geom_t gb = body_pair ? load_geom(b, geo) : load_geom(pr.y, static_geo);
                     collide_pair(&ga, &gb, margin, &m, ws);
                 }
             }
@@ -166,12 +179,12 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
                 if (col != kUncolored) {
                     bit = 1ull << col;
                     seen_a = atomicOr(&used[a], bit);  // looked at after the barrier below
-                    if (b != PHYS_GROUND_ID) seen_b = atomicOr(&used[b], bit);
+                    if (!PHYS_IS_STATIC_PARTNER(b)) seen_b = atomicOr(&used[b], bit);
                 } else {
                     uncolored = true;
                     // round 0 of the colouring: per-body maximum priority (order-independent u64 max)
                     atomicMax(&top0[a], prio);
-                    if (b != PHYS_GROUND_ID) atomicMax(&top0[b], prio);
+                    if (!PHYS_IS_STATIC_PARTNER(b)) atomicMax(&top0[b], prio);
                 }
             }
             it.a = a; it.b = b; it.col = col; it.prev_m = prev_m; it.kept_h = kept_h;
@@ -187,6 +200,7 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
             n_has += (uint32_t)__popcll(mask[j]);
             n_unc += (uint32_t)__popcll(umask[j]);
             n_gnd += (uint32_t)__popcll(__ballot(item[j].has && item[j].b == PHYS_GROUND_ID));
+            if (kStatics) acc_static += (uint32_t)__popcll(__ballot(item[j].has && item[j].b != PHYS_GROUND_ID && PHYS_IS_STATIC_PARTNER(item[j].b)));
             pts += item[j].has ? (uint32_t)item[j].m.count : 0u;  // contact points (for the stats counter)
         }
 #pragma unroll
@@ -277,6 +291,7 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
         if (acc_ground) atomicAdd(&ctr->n_ground_manifolds, acc_ground);
         if (acc_unc) { atomicAdd(&ctr->n_uncolored, acc_unc); atomicAdd(&ctr->n_new_manifolds, acc_unc); }
     }
+    if (kStatics && (threadIdx.x & 63) == 0 && acc_static) atomicAdd(&ctr->n_static_manifolds, acc_static);
 }
 
 // ---- colouring --------------------------------------------------------------------------------------
@@ -324,7 +339,7 @@ __device__ __forceinline__ uint32_t color_round_lanes(uint32_t first, uint32_t s
         if (!next_list && man_color[m] != kUncolored) continue;
         const unsigned long long p = man_prio[m];
         const uint32_t a = man_a[m], b = man_b[m];
-        const bool gb = b == PHYS_GROUND_ID;
+        const bool gb = PHYS_IS_STATIC_PARTNER(b);  // the ground or a static collider: no colour state of its own
         bool lose = false;
         // BYPASS_L1 (single-launch finish loop): words other waves changed with atomics inside this launch
         // must come from L2, not from a line this CU cached rounds ago
@@ -775,7 +790,12 @@ void launch_narrowphase(phys_world* w) {
     // (halo.hip k_halo_unpack): they rest on the ground and on each other like everybody else
     const uint32_t n_owned = n;
     const uint32_t n_ground = (w->cfg.flags & PHYS_FLAG_GROUND_PLANE) ? n : 0u;
-    const uint64_t work = (uint64_t)n_ground + w->max_pairs;
+    // static colliders (static.hip): their pairs with the bodies are the third kind of work item
+    uint64_t st_cap = 0;
+    const uint32_t* st_pairs = nullptr;
+    const float* st_geo = nullptr;
+    static_narrow_args(w, &st_cap, &st_pairs, &st_geo);
+    const uint64_t work = (uint64_t)n_ground + w->max_pairs + st_cap;
     // colouring state of the step: used masks + three rotating priority buffers (one memset); the narrow
     // phase publishes round 0's per-body maxima as it emits manifolds
     // persistent colouring: colours of the previous update are kept (contact_solve.h)
@@ -789,16 +809,17 @@ void launch_narrowphase(phys_world* w) {
         std::swap(w->man_imp.p, w->man_imp_prev.p);
     }
     PHYS_PROF(w, PHYS_STAGE_NARROW);
-#define PHYS_NP_LAUNCH(T)                                                                                              \
+#define PHYS_NP_LAUNCH(T, S)                                                                                           \
     do {                                                                                                               \
         uint64_t blocks = (work + T - 1) / T;                                                                          \
         if (blocks > 256 * 16) blocks = 256 * 16;                                                                      \
-        hipLaunchKernelGGL((k_narrowphase<T, 1>), dim3((unsigned)blocks), dim3(T), 0, w->stream, n_ground, n_owned, w->pairs.p, \
+        hipLaunchKernelGGL((k_narrowphase<T, 1, S>), dim3((unsigned)blocks), dim3(T), 0, w->stream, n_ground, n_owned, w->pairs.p, \
                            w->max_pairs, w->geo.p, w->cfg.contact_margin, \
                            w->cfg.ground_height, w->max_manifolds, w->man_a.p, w->man_b.p,                             \
                            w->man_color.p, w->man_geo.p, w->man_prio.p, w->color_state.p,                              \
                            w->color_state.p + n, reinterpret_cast<ulonglong2*>(w->ctab.p), cache_mask, early_probe, stamp, \
-                           w->unc_list.p, w->warm ? w->man_prev.p : nullptr, w->man_imp.p, w->counters.p);             \
+                           w->unc_list.p, w->warm ? w->man_prev.p : nullptr, w->man_imp.p, w->counters.p,              \
+                           st_cap, st_pairs, st_geo);                                                                  \
     } while (0)
     // 128 threads only while the whole stage is a few workgroups (C2: 10k manifolds); measured at 230k manifolds (C3):
     // 0.175 ms with 128 threads, 0.133 with 256; at 2.9M (C5): 0.86 vs 0.55 (round 2)
@@ -813,8 +834,14 @@ void launch_narrowphase(phys_world* w) {
     //   1024 threads, one item (a barrier over 16 waves)                0.231 / 0.084 / 0.937 / 0.080
     // Only the two the library picks are built; PHYS_DEBUG_NP_THREADS=128|512 picks one by hand.
     const int threads = dbg.np_threads ? dbg.np_threads : (few ? 128 : 512);
-    if (threads == 128) PHYS_NP_LAUNCH(128);
-    else PHYS_NP_LAUNCH(512);
+    // (worlds without static colliders run the kernel they always ran: the static work items are compiled out of it)
+    if (st_pairs) {
+        if (threads == 128) PHYS_NP_LAUNCH(128, true);
+        else PHYS_NP_LAUNCH(512, true);
+    } else {
+        if (threads == 128) PHYS_NP_LAUNCH(128, false);
+        else PHYS_NP_LAUNCH(512, false);
+    }
 #undef PHYS_NP_LAUNCH
 }
 

@@ -12,6 +12,8 @@
 //   k_rc_scan_*   exclusive scan of the bucket counts (own scratch: w->scan_block_sums belongs to the update)
 //   k_rc_insert<true>   the same cells again: one 48-byte record {centre, shape} {rot} {half extent, id} per insertion, in
 //                 bucket order, so a candidate is one record read and no gather from four arrays
+// Static colliders (static.hip) are tested one by one in front of the walk, from records phys_set_static_bodies made once:
+// O(statics) per ray, nothing rebuilt per call (a world without statics runs no extra test).
 // Traversal (k_rc_trace): one ray per lane, clipped to the grid box and [0, min(max_t, ground hit)], Amanatides-Woo DDA
 // with the state in named scalars and the stepping axis chosen by selects (a runtime-indexed float[3] goes to scratch,
 // which the build rules forbid). Every candidate of a cell is tested exactly; the walk stops once the best t is at or
@@ -340,6 +342,7 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
                                                         const float* __restrict__ max_t, const uint32_t* __restrict__ ignore_body,
                                                         const RcHeader* __restrict__ hdr, uint32_t bits, const uint32_t* __restrict__ start,
                                                         const float4* __restrict__ rec, uint32_t n_bodies, int ground, float ground_y,
+                                                        const float4* __restrict__ st_rec, uint32_t n_static,
                                                         uint32_t* __restrict__ body_out, float* __restrict__ t_out, float* __restrict__ normal_out,
                                                         unsigned long long* __restrict__ stats) {
     const uint32_t r = blockIdx.x * kRcThreads + threadIdx.x;
@@ -362,6 +365,9 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
             if (tg >= 0.0f && tg <= tmax) { best.t = tg; best.id = kRayGround; }
             else { best.nx = 0.0f; best.ny = 0.0f; best.nz = 0.0f; }
         }
+        // static colliders (records of phys_set_static_bodies, id PHYS_STATIC_ID_BIT | k): every one tested, before the bodies'
+        // walk so that a static hit shortens it; bodies still win exact ties (smaller ids), the ground loses them
+        for (uint32_t k = 0; k < n_static; ++k) rc_test(st_rec, k, o.x, o.y, o.z, ux, uy, uz, tmax, 0xFFFFFFFFu, best);
         const RcGrid g = rc_grid(hdr);
         // clip to the grid box and to [0, min(max_t, best)] (bodies win ties with the ground: best.t itself stays in)
         const float iux = 1.0f / ux, iuy = 1.0f / uy, iuz = 1.0f / uz;  // +-inf on a zero component
@@ -452,7 +458,8 @@ int32_t launch_raycast(phys_world* w, uint64_t n_rays, const float* origin, cons
 #define PHYS_RC_TRACE(S)                                                                                                       \
     hipLaunchKernelGGL(k_rc_trace<S>, dim3(rc_blocks(n_rays)), dim3(kRcThreads), 0, s, (uint32_t)n_rays, origin, dir, max_t,  \
                        ignore_body, hdr, bits, (const uint32_t*)w->rc_start.p, reinterpret_cast<const float4*>(w->rc_records.p), \
-                       (uint32_t)n, ground, w->cfg.ground_height, body_out, t_out, normal_out, w->rc_stats.p)
+                       (uint32_t)n, ground, w->cfg.ground_height, reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static, \
+                       body_out, t_out, normal_out, w->rc_stats.p)
     if (stats) PHYS_RC_TRACE(true);
     else PHYS_RC_TRACE(false);
 #undef PHYS_RC_TRACE

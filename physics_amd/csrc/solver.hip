@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
             g.pt[k] = v3_make(p.x, p.y, p.z);
             g.depth[k] = p.w;
         }
-        const int has_b = b != PHYS_GROUND_ID;
+        const int has_b = !PHYS_IS_STATIC_PARTNER(b);
         // warm starting: the impulses this row starts from = what the same pair's manifold of the previous update ended
         // with, matched point by point (contact_solve.h warm_match); zero for a new pair or with warm starting off
         float w_pn[4] = {0.0f, 0.0f, 0.0f, 0.0f}, w_pt0[4] = {0.0f, 0.0f, 0.0f, 0.0f}, w_pt1[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -233,7 +233,7 @@ __device__ __forceinline__ void load_row(RowRegs& R, uint32_t d, const RowArrays
     R.a = h.x; R.b = h.y; R.ticket = h.w;
     solver_manifold_t& sm = R.sm;
     sm.count = (int)h.z;
-    sm.has_b = R.b != PHYS_GROUND_ID;
+    sm.has_b = !PHYS_IS_STATIC_PARTNER(R.b);
     const float4 nn = rows.n[d];
     sm.n = v3_make(nn.x, nn.y, nn.z);
     tangent_basis(sm.n, &sm.t1, &sm.t2);  // same inputs as solver_prep => same bits as the basis used there
@@ -475,7 +475,7 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
         g.IA = ld_inertia<DIAG>(inv_inertia, r.h.x * inertia_stride);
         const BodyVel A0 = ld_vel(vel, r.h.x);
         g.ima = A0.inv_mass; g.massA = A0.mass; g.vA = A0.v; g.wA = A0.w;
-        if (r.h.y != PHYS_GROUND_ID) {
+        if (!PHYS_IS_STATIC_PARTNER(r.h.y)) {
             g.IB = ld_inertia<DIAG>(inv_inertia, r.h.y * inertia_stride);
             const BodyVel B0 = ld_vel(vel, r.h.y);
             g.imb = B0.inv_mass; g.massB = B0.mass; g.vB = B0.v; g.wB = B0.w;
@@ -520,7 +520,7 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
         {
             solver_manifold_t& sm = R.sm;
             sm.count = done ? 0 : (int)raw.h.z;
-            sm.has_b = !done && R.b != PHYS_GROUND_ID;
+            sm.has_b = !done && !PHYS_IS_STATIC_PARTNER(R.b);
             sm.n = v3_make(raw.nn.x, raw.nn.y, raw.nn.z);
             if (done) sm.n = v3_make(0.0f, 1.0f, 0.0f);
             tangent_basis(sm.n, &sm.t1, &sm.t2);
@@ -693,7 +693,7 @@ __device__ __forceinline__ void quad_lane_setup(QuadLane& s, uint32_t q, uint32_
                                                 const float* __restrict__ inv_inertia, uint32_t inertia_stride) {
     const bool side_a = q < 2u, angular = (q & 1u) != 0u;
     const uint32_t body = side_a ? a : b;
-    const bool has_body = side_a || b != PHYS_GROUND_ID;
+    const bool has_body = side_a || !PHYS_IS_STATIC_PARTNER(b);
     s.count = count; s.body = body; s.has_body = has_body;
     v3 dir[3];
     dir[2] = v3_make(nn.x, nn.y, nn.z);
@@ -946,7 +946,7 @@ __global__ __launch_bounds__(256) void k_solve_color_quad(StepCounters* ctr, uin
         const uint32_t ha = __float_as_uint(hraw.x), hb = __float_as_uint(hraw.y), count = __float_as_uint(hraw.z);
         // a row header that names no body of this world must never become an address (a faulting kernel can take the
         // whole node down): flag the step (bit 5) and skip the row
-        const bool bad = live && (count > 4u || ha >= n_bodies || (hb != PHYS_GROUND_ID && hb >= n_bodies));
+        const bool bad = live && (count > 4u || ha >= n_bodies || (!PHYS_IS_STATIC_PARTNER(hb) && hb >= n_bodies));
         if (bad) {
             flag_overflow(ctr, 32u);
             ctr->debug[0] = d; ctr->debug[1] = ha; ctr->debug[2] = hb; ctr->debug[3] = count;

@@ -87,6 +87,8 @@ struct StepCounters {
     uint32_t n_used_buckets; // buckets of the sorted grid holding at least one body (k_cell_assign)
     uint32_t max_region;     // k_find_pairs_brick: most records in the region of one brick (sizes the LDS stage of later updates)
     uint32_t n_new_manifolds;  // manifolds that kept no colour in this update (= the colouring's work; never counted down)
+    uint32_t n_static_pairs;      // (body, static) pairs of this update, all of them (k_static_fill; only max_static_pairs are stored)
+    uint32_t n_static_manifolds;  // manifolds against a static collider (subset of n_manifolds)
     uint32_t cluster_arrived[2][8];  // k_solve_cluster, per attempt: workgroups that have begun (eight counters: same-address
                                      // atomics serialise chip-wide) ...
     uint32_t cluster_state[2];       // ... and the launch's one decision: 0 undecided, 1 go (all are resident), 2 called off
@@ -328,6 +330,22 @@ struct phys_world {
     phys::DevBuf<float> rc_in;           // phys_raycast (host arrays): staged origin | dir | max_t | ignore (as u32 bits)
     phys::DevBuf<float> rc_out;          // ... and the outputs body | t | normal
     phys::DevBuf<unsigned long long> rc_stats;  // PHYS_DEBUG_RAYCAST_STATS: cells, candidates
+    // static colliders (static.hip): immovable shapes set by phys_set_static_bodies, read-only until the next such call
+    uint64_t n_static = 0;
+    phys::DevBuf<float> st_geo;          // 16 floats per static, the layout of `geo`: {pos, shape} {rot} {half extent, -}
+    phys::DevBuf<float> st_rc;           // 12 floats per static, the ray-cast record {pos, shape} {rot} {half extent, id}
+    phys::DevBuf<float> st_box;          // 8 floats per static: {fattened AABB lo, packed first grid cell} {hi, -}
+    phys::DevBuf<uint32_t> st_cell_start, st_cell_ids;  // uniform grid over the small statics, CSR: cell -> ascending ids
+    phys::DevBuf<uint32_t> st_large;     // statics that would cover too many cells: tested by every body, ascending
+    uint32_t st_n_large = 0;
+    float st_org[3] = {0.0f, 0.0f, 0.0f}, st_inv_cell = 0.0f;
+    uint32_t st_dim[3] = {0, 0, 0};      // cells per axis (0: no small statics), each <= 1024
+    phys::DevBuf<uint32_t> st_count;     // per body slot: its static pairs (count pass), then their offsets
+    phys::DevBuf<uint32_t> st_block;     // per workgroup of the count pass: pair totals, then their exclusive scan
+    phys::DevBuf<uint32_t> st_pairs;     // 2 per pair: body, static index (not tagged), (body, static) ascending
+    uint64_t max_static_pairs = 0;       // automatic: a per-body budget, regrown from the counts of earlier updates
+    uint64_t static_pairs_seen = 0;      // the largest pair count an update has reported back (sizes the buffer)
+    bool static_pairs_sized = false;     // the next update measures its pair count first (new static or body set)
     // multi-GPU halo
     phys::DevBuf<uint32_t> cross_pairs;
     uint64_t max_cross_pairs = 0;

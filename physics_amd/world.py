@@ -65,6 +65,26 @@ class World:
         self._ck(self.lib.phys_set_bodies(self.h, n, *[_p(a) for a in arrs], _p(st, u32p), _p(he)))
         self.n = n
 
+    def set_static_bodies(self, pos, rot=None, shape_type=None, half_extent=None):
+        """Replace the static colliders (phys_set_static_bodies): pos (n, 3), rot (n, 4) [i, j, k, w] or None (identity),
+        shape_type (n,) SHAPE_SPHERE / SHAPE_BOX, half_extent (n, 3). An empty pos clears the set. Collider k is named
+        STATIC_ID_BIT | k in manifolds and ray hits."""
+        pos = _f(pos).reshape(-1, 3)
+        n = pos.shape[0]
+        rot = _f(rot)
+        st = None if shape_type is None else np.ascontiguousarray(shape_type, dtype=np.uint32).reshape(-1)
+        he = _f(half_extent)
+        for a, w in ((rot, 4), (st, 1), (he, 3)):
+            if a is not None and a.size != n * w:
+                raise ValueError("array size does not match the static collider count")
+        self._ck(self.lib.phys_set_static_bodies(self.h, n, _p(pos), _p(rot), _p(st, u32p), _p(he)))
+
+    def get_static_stats(self):
+        """(static colliders, (body, static) pairs of the last update, manifolds against statics of the last update)."""
+        out = [C.c_uint64() for _ in range(3)]
+        self._ck(self.lib.phys_get_static_stats(self.h, *[C.byref(x) for x in out]))
+        return tuple(x.value for x in out)
+
     def add_constraint_fix_point(self, body, target):
         t = _f(target)
         self._ck(self.lib.phys_add_constraint_fix_point(self.h, body, _p(t)))

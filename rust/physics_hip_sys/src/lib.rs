@@ -11,6 +11,7 @@ pub const PHYS_ERR_NO_BODIES: i32 = -8;
 pub const PHYS_SHAPE_NONE: u32 = 0;
 pub const PHYS_SHAPE_SPHERE: u32 = 1;
 pub const PHYS_SHAPE_BOX: u32 = 2;
+pub const PHYS_STATIC_ID_BIT: u32 = 0x8000_0000;
 pub const PHYS_FLAG_COLLISIONS: u32 = 0x1;
 pub const PHYS_FLAG_GROUND_PLANE: u32 = 0x2;
 pub const PHYS_FLAG_EXACT_ROTATION: u32 = 0x4;
@@ -140,6 +141,9 @@ extern "C" {
                         ignore_body: *const u32, body_out: *mut u32, t_out: *mut f32, normal_out: *mut f32) -> i32;
     pub fn phys_raycast_device(w: *mut phys_world, n_rays: u64, origin: *const f32, dir: *const f32, max_t: *const f32,
                                ignore_body: *const u32, body_out: *mut u32, t_out: *mut f32, normal_out: *mut f32) -> i32;
+    pub fn phys_set_static_bodies(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32, shape_type: *const u32,
+                                  half_extent: *const f32) -> i32;
+    pub fn phys_get_static_stats(w: *mut phys_world, n_static: *mut u64, n_static_pairs: *mut u64, n_static_manifolds: *mut u64) -> i32;
     pub fn phys_profile_enable(w: *mut phys_world, on: i32) -> i32;
     pub fn phys_profile_get(w: *mut phys_world, out: *mut phys_profile) -> i32;
     pub fn phys_get_device_view(w: *mut phys_world, out: *mut phys_device_view) -> i32;
