@@ -44,6 +44,11 @@ extern "C" {
 #define PHYS_SHAPE_NONE 0u   /* takes part in integration only */
 #define PHYS_SHAPE_SPHERE 1u /* radius = half_extent[0] */
 #define PHYS_SHAPE_BOX 2u    /* half extents along the body axes */
+/* capsule: radius = half_extent[0]; core half-length h = half_extent[1] along the body's local y axis, so the core segment
+ * runs from c - h*R[:,1] to c + h*R[:,1] (h = 0: a sphere); half_extent[2] is ignored. Added without an ABI version bump
+ * (no struct changed): a library that predates capsules refuses PHYS_SHAPE_CAPSULE in phys_set_static_bodies with
+ * PHYS_ERR_INVALID_ARG, which is how a caller can tell. Contact rules: DESIGN.md section 11. */
+#define PHYS_SHAPE_CAPSULE 3u
 
 /* phys_config.flags */
 #define PHYS_FLAG_COLLISIONS 0x1u     /* run broad-phase + narrow-phase + sequential impulses */
@@ -246,7 +251,7 @@ int32_t phys_raycast(phys_world* w, uint64_t n_rays, const float* origin /*3n*/,
 int32_t phys_raycast_device(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                             const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out);
 
-/* --- static colliders: immovable SPHERE / BOX shapes that bodies collide with and rays hit. Not bodies. ---
+/* --- static colliders: immovable SPHERE / BOX / CAPSULE shapes that bodies collide with and rays hit. Not bodies. ---
  * Level geometry (floors, walls, ramps, pillars, container sides) that never moves: no velocity, no mass, no colour of
  * its own. A manifold against static k is one-sided like a ground manifold (body A against a partner at rest with zero
  * inverse mass and inertia); it names the collider PHYS_STATIC_ID_BIT | k as body_b, which sorts after every body id
@@ -256,8 +261,9 @@ int32_t phys_raycast_device(phys_world* w, uint64_t n_rays, const float* origin,
  *   - phys_set_static_bodies replaces the whole static set (n = 0 clears it) and is independent of phys_set_bodies:
  *     neither clears the other's set. It makes the world forget its persistent colours and warm-start impulses, like
  *     phys_set_bodies. shape_type and half_extent are required (SPHERE: radius half_extent[0]; BOX: half extents along
- *     the collider's axes); rot NULL = identity. PHYS_ERR_INVALID_ARG: n >= 0x7FFFFFFE, a shape other than SPHERE or
- *     BOX, a non-finite pose or half extent, a negative half extent, a NULL array that is required.
+ *     the collider's axes; CAPSULE: radius half_extent[0], core half-length half_extent[1] along the local y axis);
+ *     rot NULL = identity. PHYS_ERR_INVALID_ARG: n >= 0x7FFFFFFE, a shape other than SPHERE, BOX or CAPSULE, a
+ *     non-finite pose or half extent, a negative half extent, a NULL array that is required.
  *   - every update (PHYS_FLAG_COLLISIONS) finds the (body, static) pairs whose fattened AABBs overlap, in the order
  *     (body ascending, static ascending); their capacity is automatic: the first update after phys_set_static_bodies or
  *     phys_set_bodies counts them before it stores them (one host wait) and sizes the buffer at 1.5 times that, later

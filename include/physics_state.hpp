@@ -74,7 +74,8 @@ struct RigidBody {  // rigid_body.rs:5-21
     Vector3 position;
     UnitQuaternion rotation;
     size_t index = 0;
-    // new: collision shape (the reference has none; PHYS_SHAPE_NONE keeps reference behaviour)
+    // new: collision shape (the reference has none; PHYS_SHAPE_NONE keeps reference behaviour). PHYS_SHAPE_SPHERE,
+    // PHYS_SHAPE_BOX or PHYS_SHAPE_CAPSULE (radius half_extent.x, core half-length half_extent.y along the local y axis)
     uint32_t shape_type = PHYS_SHAPE_NONE;
     Vector3 half_extent;
 

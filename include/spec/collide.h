@@ -29,13 +29,15 @@
 #define PHYS_SPEC_SHAPE_NONE 0u
 #define PHYS_SPEC_SHAPE_SPHERE 1u
 #define PHYS_SPEC_SHAPE_BOX 2u
+/* capsule: radius h.x, core half-length h.y along the body's local y axis (column 1 of R); h.z unused */
+#define PHYS_SPEC_SHAPE_CAPSULE 3u
 
 typedef struct { v3 lo, hi; } aabb_t;
 
 typedef struct {
     v3 c;          /* centre (world) */
     m33 R;         /* rotation matrix of the (unnormalised, quirk Q6) quaternion */
-    v3 h;          /* half extents; sphere radius in h.x */
+    v3 h;          /* half extents; sphere radius in h.x; capsule radius h.x, core half-length h.y */
     uint32_t type;
 } geom_t;
 
@@ -96,6 +98,13 @@ PHYS_HD aabb_t body_aabb(v3 c, quat q, v3 h, uint32_t type, float margin) {
         e.x = (det_absf(R.m[0]) * h.x + det_absf(R.m[1]) * h.y) + det_absf(R.m[2]) * h.z;
         e.y = (det_absf(R.m[3]) * h.x + det_absf(R.m[4]) * h.y) + det_absf(R.m[5]) * h.z;
         e.z = (det_absf(R.m[6]) * h.x + det_absf(R.m[7]) * h.y) + det_absf(R.m[8]) * h.z;
+    } else if (type == PHYS_SPEC_SHAPE_CAPSULE) {
+        /* the core segment's extent |h.y * R[:,1]| per axis, plus the radius */
+        m33 R;
+        quat_to_m33(q, &R);
+        e.x = det_absf(R.m[1]) * h.y + h.x;
+        e.y = det_absf(R.m[4]) * h.y + h.x;
+        e.z = det_absf(R.m[7]) * h.y + h.x;
     } else {
         b.lo = v3_make(3.0e38f, 3.0e38f, 3.0e38f);
         b.hi = v3_make(-3.0e38f, -3.0e38f, -3.0e38f);
@@ -410,8 +419,9 @@ PHYS_HD void collide_box_box(const geom_t* A, const geom_t* B, float margin, man
     }
 }
 
-/* body-body manifold for the ordered pair (A = lower index, B = higher index) */
-PHYS_HD void collide_pair(const geom_t* A, const geom_t* B, float margin, manifold_t* m, clip_ws_t* ws) {
+/* body-body manifold of two spheres / boxes (A = lower index, B = higher index); any other shape gives no contact.
+ * collide_pair below is the full definition; this is the part the narrow phase of a world without capsules compiles. */
+PHYS_HD void collide_pair_sphere_box(const geom_t* A, const geom_t* B, float margin, manifold_t* m, clip_ws_t* ws) {
     manifold_clear(m);
     if (A->type == PHYS_SPEC_SHAPE_SPHERE && B->type == PHYS_SPEC_SHAPE_SPHERE) {
         collide_sphere_sphere(A, B, margin, m);
@@ -426,8 +436,8 @@ PHYS_HD void collide_pair(const geom_t* A, const geom_t* B, float margin, manifo
 }
 
 /* body against the ground plane y = ground (normal +y). Manifold has A = body, B = ground, so the
- * A -> B normal is (0,-1,0). */
-PHYS_HD void collide_ground(const geom_t* A, float ground, float margin, manifold_t* m, clip_ws_t* ws) {
+ * A -> B normal is (0,-1,0). Spheres and boxes only: collide_ground below adds capsules. */
+PHYS_HD void collide_ground_sphere_box(const geom_t* A, float ground, float margin, manifold_t* m, clip_ws_t* ws) {
     manifold_clear(m);
     m->normal = v3_make(0.0f, -1.0f, 0.0f);
     if (A->type == PHYS_SPEC_SHAPE_SPHERE) {
@@ -452,6 +462,317 @@ PHYS_HD void collide_ground(const geom_t* A, float ground, float margin, manifol
         }
         if (nc == 0) return;
         manifold_reduce(cand, cdep, nc, v3_make(0.0f, 1.0f, 0.0f), m);
+    }
+}
+
+
+/* ---- capsules ------------------------------------------------------------------------------
+ * A capsule is the set of points within h.x of its core segment c +- h.y * u, u = column 1 of R. Every capsule test
+ * reduces to spheres on that segment: no polygon clipping, no clip_ws_t, at most two points. Points sit in the middle
+ * of the overlap (the sphere-sphere convention); the normal points A -> B. */
+
+/* core axis u (column 1 of R) */
+PHYS_HD v3 capsule_axis(const geom_t* A) { return v3_make(A->R.m[1], A->R.m[4], A->R.m[7]); }
+
+/* a sphere of radius r at p: what collide_sphere_sphere / collide_sphere_box_raw take */
+PHYS_HD geom_t capsule_ball(v3 p, float r) {
+    geom_t g;
+    g.c = p;
+    g.R.m[0] = 1.0f; g.R.m[1] = 0.0f; g.R.m[2] = 0.0f;
+    g.R.m[3] = 0.0f; g.R.m[4] = 1.0f; g.R.m[5] = 0.0f;
+    g.R.m[6] = 0.0f; g.R.m[7] = 0.0f; g.R.m[8] = 1.0f;
+    g.h = v3_make(r, r, r);
+    g.type = PHYS_SPEC_SHAPE_SPHERE;
+    return g;
+}
+
+/* parameter s in [-hl, hl] of the point c + s*u closest to p */
+PHYS_HD float segment_param(v3 c, v3 u, float hl, v3 p) {
+    const float uu = v3_dot(u, u);
+    float s = 0.0f;
+    if (uu > 1.0e-12f) s = v3_dot(v3_sub(p, c), u) / uu;
+    return det_maxf(-hl, det_minf(s, hl));
+}
+
+/* Closest points of the segments ca + s*ua (|s| <= ha) and cb + t*ub (|t| <= hb), clamped as in Ericson, Real-Time
+ * Collision Detection 5.1.9. Near-parallel segments (sin^2 of the angle below 1e-4) start from s = 0. */
+PHYS_HD void segment_closest(v3 ca, v3 ua, float ha, v3 cb, v3 ub, float hb, float* s_out, float* t_out) {
+    const v3 r = v3_sub(ca, cb);
+    const float a = v3_dot(ua, ua), e = v3_dot(ub, ub), b = v3_dot(ua, ub);
+    const float c = v3_dot(ua, r), f = v3_dot(ub, r);
+    const float denom = a * e - b * b;
+    float s = 0.0f, t = 0.0f;
+    if (denom > 1.0e-4f * (a * e)) s = det_maxf(-ha, det_minf((b * f - c * e) / denom, ha));
+    if (e > 1.0e-12f) t = (b * s + f) / e;
+    if (t < -hb || t > hb) {
+        t = t < -hb ? -hb : hb;
+        s = a > 1.0e-12f ? det_maxf(-ha, det_minf((b * t - c) / a, ha)) : 0.0f;
+    }
+    *s_out = s;
+    *t_out = t;
+}
+
+/* capsule A against sphere B: the sphere on A's segment closest to B's centre, then sphere-sphere. One point. */
+PHYS_HD void collide_capsule_sphere(const geom_t* A, const geom_t* B, float margin, manifold_t* m) {
+    const v3 u = capsule_axis(A);
+    const float s = segment_param(A->c, u, A->h.y, B->c);
+    const geom_t S = capsule_ball(v3_add(A->c, v3_scale(u, s)), A->h.x);
+    collide_sphere_sphere(&S, B, margin, m);
+}
+
+/* capsule A against capsule B. Near-parallel segments whose projections overlap (along A's axis, strictly) give the
+ * two ends of the overlap, with the normal of the two axes' offset - (0,1,0) for coincident axes; anything else is
+ * sphere-sphere at the segments' closest points. */
+PHYS_HD void collide_capsule_capsule(const geom_t* A, const geom_t* B, float margin, manifold_t* m) {
+    const v3 ua = capsule_axis(A), ub = capsule_axis(B);
+    const float ra = A->h.x, rb = B->h.x;
+    const float a = v3_dot(ua, ua), e = v3_dot(ub, ub), b = v3_dot(ua, ub);
+    if (a > 1.0e-12f && e > 1.0e-12f && a * e - b * b <= 1.0e-4f * (a * e)) {
+        const v3 d = v3_sub(B->c, A->c);
+        const float sb = v3_dot(d, ua) / a;                    /* B's centre along A's axis */
+        const float pb = B->h.y * (det_absf(b) / a);           /* B's half-length along A's axis */
+        const float lo = det_maxf(-A->h.y, sb - pb), hi = det_minf(A->h.y, sb + pb);
+        if (lo < hi) {
+            const v3 perp = v3_sub(d, v3_scale(ua, sb));
+            const float dist = v3_norm(perp);
+            v3 n = v3_make(0.0f, 1.0f, 0.0f);
+            if (dist > 1.0e-12f) n = v3_div(perp, dist);
+            const float r = ra + rb;
+            int nc = 0;
+            PHYS_UNROLL
+            for (int k = 0; k < 2; ++k) {
+                const float s = k == 0 ? lo : hi;
+                const v3 pa = v3_add(A->c, v3_scale(ua, s));
+                const float t = segment_param(B->c, ub, B->h.y, pa);
+                const v3 qb = v3_add(B->c, v3_scale(ub, t));
+                const float depth = r - v3_dot(v3_sub(qb, pa), n);
+                if (depth >= -margin) {
+                    const v3 p = v3_add(pa, v3_scale(n, ra - 0.5f * depth));
+                    if (nc == 0) { m->pt[0] = p; m->depth[0] = depth; }
+                    else { m->pt[1] = p; m->depth[1] = depth; }
+                    ++nc;
+                }
+            }
+            m->normal = n;
+            m->count = nc;
+            return;
+        }
+    }
+    float s, t;
+    segment_closest(A->c, ua, A->h.y, B->c, ub, B->h.y, &s, &t);
+    const geom_t SA = capsule_ball(v3_add(A->c, v3_scale(ua, s)), ra);
+    const geom_t SB = capsule_ball(v3_add(B->c, v3_scale(ub, t)), rb);
+    collide_sphere_sphere(&SA, &SB, margin, m);
+}
+
+/* the segment (pc, dl, hl) and the box edge qe + t*ue (|t| <= he), in the box frame: keeps the closer pair in (*bp, *bq) */
+PHYS_HD void capsule_edge_closest(v3 pc, v3 dl, float hl, v3 qe, v3 ue, float he, float* best, v3* bp, v3* bq) {
+    float s, t;
+    segment_closest(pc, dl, hl, qe, ue, he, &s, &t);
+    const v3 p = v3_add(pc, v3_scale(dl, s)), q = v3_add(qe, v3_scale(ue, t));
+    const v3 d = v3_sub(p, q);
+    const float d2 = v3_dot(d, d);
+    if (d2 < *best) { *best = d2; *bp = p; *bq = q; }
+}
+
+/* the nearest of the four edges of box face (axis f, side sg) to the segment (pc, dl, hl), box frame; each edge runs
+ * along one in-plane axis at +-e of the other */
+PHYS_HD void capsule_face_edges(v3 pc, v3 dl, float hl, int f, float sg, v3 e, float* best, v3* bp, v3* bq) {
+    const int ja = f == 0 ? 1 : 0, ka = f == 2 ? 1 : 2;  /* the two axes of the face */
+    const float ef = f == 0 ? e.x : (f == 1 ? e.y : e.z);
+    PHYS_UNROLL
+    for (int k = 0; k < 4; ++k) {
+        const int along = k < 2 ? ka : ja, across = k < 2 ? ja : ka;  /* along ka at +-e_ja, then along ja at +-e_ka */
+        const float side = (k & 1) ? 1.0f : -1.0f;
+        const float ec = across == 0 ? e.x : (across == 1 ? e.y : e.z);
+        const float qx = f == 0 ? sg * ef : (across == 0 ? side * ec : 0.0f);
+        const float qy = f == 1 ? sg * ef : (across == 1 ? side * ec : 0.0f);
+        const float qz = f == 2 ? sg * ef : (across == 2 ? side * ec : 0.0f);
+        const v3 ue = v3_make(along == 0 ? 1.0f : 0.0f, along == 1 ? 1.0f : 0.0f, along == 2 ? 1.0f : 0.0f);
+        const float he = along == 0 ? e.x : (along == 1 ? e.y : e.z);
+        capsule_edge_closest(pc, dl, hl, v3_make(qx, qy, qz), ue, he, best, bp, bq);
+    }
+}
+
+/* one point of capsule A against box B from the closest points p (on A's core) and q (on B's surface), box frame. Where
+ * an axis separates the core from the box (sep_f > 0) their distance is the separation; otherwise the core touches or
+ * enters the box, and nf (box -> capsule) with its separation sep_f gives normal and depth */
+PHYS_HD void capsule_box_point(const geom_t* A, const geom_t* B, v3 p, v3 q, v3 nf, float sep_f, float margin, manifold_t* m) {
+    const float r = A->h.x;
+    const v3 d = v3_sub(p, q);
+    const float dist = v3_norm(d);
+    v3 n = nf;
+    float depth = r - sep_f;
+    if (sep_f > 0.0f && dist > 1.0e-6f) { n = v3_div(d, dist); depth = r - dist; }
+    if (depth < -margin) return;
+    m->normal = v3_neg(m33_mul_v3(&B->R, n));
+    m->count = 1;
+    m->pt[0] = v3_add(B->c, m33_mul_v3(&B->R, v3_sub(p, v3_scale(n, r - 0.5f * depth))));
+    m->depth[0] = depth;
+}
+
+/* capsule A against box B, at most 2 points. SAT in the box frame over the box's 3 face axes and the 3 axes
+ * segment x box edge, the segment taken with zero radius and the radius subtracted afterwards. The faces are preferred
+ * as in collide_box_box. A face axis clips the segment to the face rectangle; each end of the clipped part within the
+ * margin is a point. An edge axis gives one point, at the closest point of the segment to that box edge. A face axis
+ * whose rectangle the segment misses (it passes beside an edge or a corner) falls back to sphere-box at the segment
+ * point nearest the box (two alternating projections). */
+PHYS_HD void collide_capsule_box(const geom_t* A, const geom_t* B, float margin, manifold_t* m) {
+    const float r = A->h.x, hl = A->h.y;
+    const v3 pc = m33_tmul_v3(&B->R, v3_sub(A->c, B->c)); /* segment centre in the box frame */
+    const v3 dl = m33_tmul_v3(&B->R, capsule_axis(A));   /* segment axis in the box frame */
+    const float ex = B->h.x, ey = B->h.y, ez = B->h.z;
+    /* face axes */
+    const float fx = det_absf(pc.x) - (ex + hl * det_absf(dl.x));
+    const float fy = det_absf(pc.y) - (ey + hl * det_absf(dl.y));
+    const float fz = det_absf(pc.z) - (ez + hl * det_absf(dl.z));
+    if (fx - r > margin || fy - r > margin || fz - r > margin) return;
+    int fAxis = 0; float fMax = fx;
+    if (fy > fMax) { fAxis = 1; fMax = fy; }
+    if (fz > fMax) { fAxis = 2; fMax = fz; }
+    /* edge axes dl x e_i (local): (0, dl.z, -dl.y), (-dl.z, 0, dl.x), (dl.y, -dl.x, 0) */
+    float eMax = -3.0e38f; int eAxis = -1;
+    PHYS_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        const v3 n = i == 0 ? v3_make(0.0f, dl.z, -dl.y) : (i == 1 ? v3_make(-dl.z, 0.0f, dl.x) : v3_make(dl.y, -dl.x, 0.0f));
+        const float len2 = v3_dot(n, n);
+        if (len2 < 1.0e-4f) continue; /* segment (nearly) parallel to this edge: covered by the face axes */
+        const float rb = (ex * det_absf(n.x) + ey * det_absf(n.y)) + ez * det_absf(n.z);
+        const float s = (det_absf(v3_dot(pc, n)) - rb) / det_sqrtf(len2);
+        if (s - r > margin) return;
+        if (s > eMax) { eMax = s; eAxis = i; }
+    }
+    /* an edge axis must beat the faces clearly; the separations of a zero-radius segment are mostly positive, so the
+     * tolerance grows with |fMax| (an edge axis that IS a face normal - a segment across a face - never wins) */
+    v3 nl; /* box -> capsule, box frame */
+    if (eAxis >= 0 && eMax > fMax + (0.05f * det_absf(fMax) + 0.01f)) {
+        v3 n = eAxis == 0 ? v3_make(0.0f, dl.z, -dl.y) : (eAxis == 1 ? v3_make(-dl.z, 0.0f, dl.x) : v3_make(dl.y, -dl.x, 0.0f));
+        n = v3_div(n, v3_norm(n));
+        if (v3_dot(n, pc) < 0.0f) n = v3_neg(n);
+        /* the box edge along axis eAxis on the side n faces */
+        const float sx = n.x > 0.0f ? ex : -ex, sy = n.y > 0.0f ? ey : -ey, sz = n.z > 0.0f ? ez : -ez;
+        const v3 qe = v3_make(eAxis == 0 ? 0.0f : sx, eAxis == 1 ? 0.0f : sy, eAxis == 2 ? 0.0f : sz);
+        const v3 ue = v3_make(eAxis == 0 ? 1.0f : 0.0f, eAxis == 1 ? 1.0f : 0.0f, eAxis == 2 ? 1.0f : 0.0f);
+        const float he = eAxis == 0 ? ex : (eAxis == 1 ? ey : ez);
+        float best = 3.0e38f;
+        v3 p = pc, q = qe;
+        capsule_edge_closest(pc, dl, hl, qe, ue, he, &best, &p, &q);
+        capsule_box_point(A, B, p, q, n, eMax, margin, m);  /* eMax > fMax: the largest separation */
+        return;
+    }
+    /* face fAxis: the part of the segment inside the face rectangle, s in [lo, hi] */
+    const float pf = fAxis == 0 ? pc.x : (fAxis == 1 ? pc.y : pc.z);
+    const float sg = pf < 0.0f ? -1.0f : 1.0f;
+    float lo = -hl, hi = hl;
+    PHYS_UNROLL
+    for (int j = 0; j < 3; ++j) {
+        if (j == fAxis) continue;
+        const float pj = j == 0 ? pc.x : (j == 1 ? pc.y : pc.z);
+        const float dj = j == 0 ? dl.x : (j == 1 ? dl.y : dl.z);
+        const float ej = j == 0 ? ex : (j == 1 ? ey : ez);
+        if (dj == 0.0f) {
+            if (det_absf(pj) > ej) { lo = 1.0f; hi = -1.0f; }
+        } else {
+            const float t0 = (-ej - pj) / dj, t1 = (ej - pj) / dj;
+            lo = det_maxf(lo, det_minf(t0, t1));
+            hi = det_minf(hi, det_maxf(t0, t1));
+        }
+    }
+    if (lo <= hi) {
+        nl = v3_make(fAxis == 0 ? sg : 0.0f, fAxis == 1 ? sg : 0.0f, fAxis == 2 ? sg : 0.0f);
+        const float ef = fAxis == 0 ? ex : (fAxis == 1 ? ey : ez);
+        const int ends = lo < hi ? 2 : 1;
+        int nc = 0;
+        PHYS_UNROLL
+        for (int k = 0; k < 2; ++k) {
+            if (k >= ends) break;
+            const float s = k == 0 ? lo : hi;
+            const v3 pa = v3_add(pc, v3_scale(dl, s));
+            const float paf = fAxis == 0 ? pa.x : (fAxis == 1 ? pa.y : pa.z);
+            const float depth = r - (sg * paf - ef);
+            if (depth >= -margin) {
+                const v3 p = v3_add(B->c, m33_mul_v3(&B->R, v3_sub(pa, v3_scale(nl, r - 0.5f * depth))));
+                if (nc == 0) { m->pt[0] = p; m->depth[0] = depth; }
+                else { m->pt[1] = p; m->depth[1] = depth; }
+                ++nc;
+            }
+        }
+        m->normal = v3_neg(m33_mul_v3(&B->R, nl));
+        m->count = nc;
+        /* a core outside the box that leans over an edge of the face comes closest beyond the clipped part: where an edge
+         * of the face is nearer than the deepest clipped end, that edge's one point is the contact */
+        const float sep = det_maxf(fMax, eMax);
+        if (sep > 0.0f) {
+            float best = 3.0e38f;
+            v3 p = pc, q = pc;
+            capsule_face_edges(pc, dl, hl, fAxis, sg, B->h, &best, &p, &q);
+            const float edge_depth = r - det_sqrtf(best);
+            const float deepest = nc == 0 ? -3.0e38f : (nc == 1 ? m->depth[0] : det_maxf(m->depth[0], m->depth[1]));
+            if (edge_depth > deepest + 1.0e-6f) {
+                manifold_clear(m);
+                capsule_box_point(A, B, p, q, nl, sep, margin, m);
+            }
+        }
+        return;
+    }
+    /* the segment misses the face rectangle */
+    float best = 3.0e38f;
+    v3 p = pc, q = pc;
+    capsule_face_edges(pc, dl, hl, fAxis, sg, B->h, &best, &p, &q);
+    capsule_box_point(A, B, p, q, v3_make(fAxis == 0 ? sg : 0.0f, fAxis == 1 ? sg : 0.0f, fAxis == 2 ? sg : 0.0f),
+                      det_maxf(fMax, eMax), margin, m);
+}
+
+/* capsule A against anything; B a capsule too, a sphere or a box */
+PHYS_HD void collide_capsule_any(const geom_t* A, const geom_t* B, float margin, manifold_t* m) {
+    if (B->type == PHYS_SPEC_SHAPE_SPHERE) collide_capsule_sphere(A, B, margin, m);
+    else if (B->type == PHYS_SPEC_SHAPE_CAPSULE) collide_capsule_capsule(A, B, margin, m);
+    else if (B->type == PHYS_SPEC_SHAPE_BOX) collide_capsule_box(A, B, margin, m);
+}
+
+/* body-body manifold for the ordered pair (A = lower index, B = higher index), every shape. Pairs with a capsule
+ * are tested with the capsule as A (swapped and the normal negated, as sphere/box does). */
+PHYS_HD void collide_pair(const geom_t* A, const geom_t* B, float margin, manifold_t* m, clip_ws_t* ws) {
+    if (A->type == PHYS_SPEC_SHAPE_CAPSULE) {
+        manifold_clear(m);
+        collide_capsule_any(A, B, margin, m);
+    } else if (B->type == PHYS_SPEC_SHAPE_CAPSULE) {
+        manifold_clear(m);
+        if (A->type != PHYS_SPEC_SHAPE_NONE) {
+            collide_capsule_any(B, A, margin, m);
+            m->normal = v3_neg(m->normal);
+        }
+    } else {
+        collide_pair_sphere_box(A, B, margin, m, ws);
+    }
+}
+
+/* capsule against the ground: one point for each end of the core segment whose sphere reaches the plane within the
+ * margin, placed as for a sphere (the middle of the overlap). Coinciding ends (h.y = 0) give one point. */
+PHYS_HD void collide_capsule_ground(const geom_t* A, float ground, float margin, manifold_t* m) {
+    const v3 ax = v3_scale(capsule_axis(A), A->h.y);
+    const v3 p0 = v3_sub(A->c, ax), p1 = v3_add(A->c, ax);
+    const float b0 = p0.y - A->h.x, b1 = p1.y - A->h.x;
+    const float d0 = ground - b0, d1 = ground - b1;
+    const int k0 = d0 >= -margin;
+    const int k1 = d1 >= -margin && !(p0.x == p1.x && p0.y == p1.y && p0.z == p1.z);
+    const v3 q0 = v3_make(p0.x, b0 + 0.5f * d0, p0.z), q1 = v3_make(p1.x, b1 + 0.5f * d1, p1.z);
+    if (k0) { m->pt[0] = q0; m->depth[0] = d0; }
+    if (k1) {
+        if (k0) { m->pt[1] = q1; m->depth[1] = d1; }
+        else { m->pt[0] = q1; m->depth[0] = d1; }
+    }
+    m->count = k0 + k1;
+}
+
+/* body against the ground plane, every shape (see collide_ground_sphere_box) */
+PHYS_HD void collide_ground(const geom_t* A, float ground, float margin, manifold_t* m, clip_ws_t* ws) {
+    if (A->type == PHYS_SPEC_SHAPE_CAPSULE) {
+        manifold_clear(m);
+        m->normal = v3_make(0.0f, -1.0f, 0.0f);
+        collide_capsule_ground(A, ground, margin, m);
+    } else {
+        collide_ground_sphere_box(A, ground, margin, m, ws);
     }
 }
 

@@ -17,6 +17,8 @@ PHYS_ERR_UNSUPPORTED = -7
 PHYS_ERR_NO_BODIES = -8
 
 SHAPE_NONE, SHAPE_SPHERE, SHAPE_BOX = 0, 1, 2
+# radius half_extent[0], core half-length half_extent[1] along the body's local y axis (include/physics_hip.h)
+SHAPE_CAPSULE = 3
 FLAG_COLLISIONS, FLAG_GROUND_PLANE, FLAG_EXACT_ROTATION, FLAG_BROADPHASE_ONLY = 1, 2, 4, 8
 FLAG_SOLVER_PER_COLOR = 16
 FLAG_SHARED_GPU = 32

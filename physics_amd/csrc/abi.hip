@@ -283,6 +283,7 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     w->singular_inertia = false;
     w->all_diag_inertia = true;
     w->uniform_inertia = true;
+    w->body_capsules = false;
     for (uint64_t i = 0; i < n; ++i) {
         if (rot) std::memcpy(&h_rot[4 * i], rot + 4 * i, 16);
         else { h_rot[4 * i] = 0.0f; h_rot[4 * i + 1] = 0.0f; h_rot[4 * i + 2] = 0.0f; h_rot[4 * i + 3] = 1.0f; }
@@ -305,6 +306,7 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
         h_diag[4 * i] = inv.m[0]; h_diag[4 * i + 1] = inv.m[4]; h_diag[4 * i + 2] = inv.m[8];
         if (h_diag[4 * i] != h_diag[0] || h_diag[4 * i + 1] != h_diag[1] || h_diag[4 * i + 2] != h_diag[2]) w->uniform_inertia = false;
         if (shape_type) h_shape[i] = shape_type[i];
+        if (h_shape[i] == PHYS_SHAPE_CAPSULE) w->body_capsules = true;
         if (half_extent) std::memcpy(&h_he[3 * i], half_extent + 3 * i, 12);
         h_gid[i] = (uint32_t)i;
     }
@@ -671,8 +673,8 @@ int32_t phys_set_static_bodies(phys_world* w, uint64_t n, const float* pos, cons
     if (n >= 0x7FFFFFFEull) return fail(PHYS_ERR_INVALID_ARG, "too many static colliders (ids are PHYS_STATIC_ID_BIT | k below 0x7FFFFFFE)");
     if (n && (!pos || !shape_type || !half_extent)) return fail(PHYS_ERR_INVALID_ARG, "static colliders need pos, shape_type and half_extent");
     for (uint64_t k = 0; k < n; ++k) {
-        if (shape_type[k] != PHYS_SHAPE_SPHERE && shape_type[k] != PHYS_SHAPE_BOX)
-            return fail(PHYS_ERR_INVALID_ARG, ("static collider " + std::to_string(k) + ": shape is neither SPHERE nor BOX").c_str());
+        if (shape_type[k] != PHYS_SHAPE_SPHERE && shape_type[k] != PHYS_SHAPE_BOX && shape_type[k] != PHYS_SHAPE_CAPSULE)
+            return fail(PHYS_ERR_INVALID_ARG, ("static collider " + std::to_string(k) + ": shape is neither SPHERE nor BOX nor CAPSULE").c_str());
         bool finite = true, negative = false;
         for (int a = 0; a < 3; ++a) {
             finite = finite && std::isfinite(pos[3 * k + a]) && std::isfinite(half_extent[3 * k + a]);

@@ -33,8 +33,10 @@ __device__ __forceinline__ geom_t load_geom(uint32_t i, const float* __restrict_
 }
 
 // kNpThreads: 128 for small scenes (latency-bound: more workgroups in flight, the LDS slice of the clipper
-// halves), 512 for everything else (launch_narrowphase)
-template <int kNpThreads, int kNpItems, bool kStatics>
+// halves), 512 for everything else (launch_narrowphase). kCapsules: the full collide_pair / collide_ground of collide.h;
+// without it only their sphere / box part is compiled (a world without capsules keeps the registers - and the resident
+// waves - the kernel had before capsules: DESIGN.md section 11)
+template <int kNpThreads, int kNpItems, bool kStatics, bool kCapsules>
 __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
     uint32_t n_ground /* bodies tested against the plane (0 = no ground) */, uint32_t n_owned /* pairs whose FIRST body is at
     or beyond this index are skipped (= all body slots: the ghosts of a sharded world collide like everybody else) */,
@@ -113,7 +115,10 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
                 const float lo_y = g2.w;
                 if (lo_y <= (ground + margin) + 1.0e-3f * (1.0f + det_absf(lo_y))) {
                     const geom_t ga = load_geom(a, geo);
-                    if (ga.type != PHYS_SPEC_SHAPE_NONE) collide_ground(&ga, ground, margin, &m, ws);
+                    if (ga.type != PHYS_SPEC_SHAPE_NONE) {
+                        if (kCapsules) collide_ground(&ga, ground, margin, &m, ws);
+                        else collide_ground_sphere_box(&ga, ground, margin, &m, ws);
+                    }
                 }
             } else if (idx < total) {
                 // a candidate pair of two bodies, or (kStatics, behind them) a body and static collider k: B = the static
@@ -135,7 +140,8 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
                     }
                     const geom_t ga = load_geom(a, geo);
                     const geom_t gb = body_pair ? load_geom(b, geo) : load_geom(pr.y, static_geo);
-                    collide_pair(&ga, &gb, margin, &m, ws);
+                    if (kCapsules) collide_pair(&ga, &gb, margin, &m, ws);
+                    else collide_pair_sphere_box(&ga, &gb, margin, &m, ws);
                 }
             }
             const bool has = m.count > 0;
@@ -809,11 +815,11 @@ void launch_narrowphase(phys_world* w) {
         std::swap(w->man_imp.p, w->man_imp_prev.p);
     }
     PHYS_PROF(w, PHYS_STAGE_NARROW);
-#define PHYS_NP_LAUNCH(T, S)                                                                                           \
+#define PHYS_NP_LAUNCH(T, S, CAP)                                                                                       \
     do {                                                                                                               \
         uint64_t blocks = (work + T - 1) / T;                                                                          \
         if (blocks > 256 * 16) blocks = 256 * 16;                                                                      \
-        hipLaunchKernelGGL((k_narrowphase<T, 1, S>), dim3((unsigned)blocks), dim3(T), 0, w->stream, n_ground, n_owned, w->pairs.p, \
+        hipLaunchKernelGGL((k_narrowphase<T, 1, S, CAP>), dim3((unsigned)blocks), dim3(T), 0, w->stream, n_ground, n_owned, w->pairs.p, \
                            w->max_pairs, w->geo.p, w->cfg.contact_margin, \
                            w->cfg.ground_height, w->max_manifolds, w->man_a.p, w->man_b.p,                             \
                            w->man_color.p, w->man_geo.p, w->man_prio.p, w->color_state.p,                              \
@@ -835,12 +841,23 @@ void launch_narrowphase(phys_world* w) {
     // Only the two the library picks are built; PHYS_DEBUG_NP_THREADS=128|512 picks one by hand.
     const int threads = dbg.np_threads ? dbg.np_threads : (few ? 128 : 512);
     // (worlds without static colliders run the kernel they always ran: the static work items are compiled out of it)
-    if (st_pairs) {
-        if (threads == 128) PHYS_NP_LAUNCH(128, true);
-        else PHYS_NP_LAUNCH(512, true);
+    // Capsules: the capsule variant wherever one can meet the narrow phase - an owned body (phys_set_bodies), a static in
+    // use, or any ghost slot: ghosts arrive on the device with the shapes of another rank, which the host never sees
+    const bool capsules = w->body_capsules || (st_pairs && w->static_capsules) || w->max_ghosts > 0;
+    if (capsules) {
+        if (st_pairs) {
+            if (threads == 128) PHYS_NP_LAUNCH(128, true, true);
+            else PHYS_NP_LAUNCH(512, true, true);
+        } else {
+            if (threads == 128) PHYS_NP_LAUNCH(128, false, true);
+            else PHYS_NP_LAUNCH(512, false, true);
+        }
+    } else if (st_pairs) {
+        if (threads == 128) PHYS_NP_LAUNCH(128, true, false);
+        else PHYS_NP_LAUNCH(512, true, false);
     } else {
-        if (threads == 128) PHYS_NP_LAUNCH(128, false);
-        else PHYS_NP_LAUNCH(512, false);
+        if (threads == 128) PHYS_NP_LAUNCH(128, false, false);
+        else PHYS_NP_LAUNCH(512, false, false);
     }
 #undef PHYS_NP_LAUNCH
 }

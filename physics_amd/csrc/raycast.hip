@@ -105,7 +105,7 @@ __device__ __forceinline__ uint32_t rc_bucket(int x, int y, int z, uint32_t bits
 __device__ __forceinline__ bool rc_aabb(const float* __restrict__ pos, const float* __restrict__ rot, const float* __restrict__ he,
                                         const uint32_t* __restrict__ shape, uint32_t i, aabb_t* out) {
     const uint32_t type = shape[i];
-    if (type != PHYS_SHAPE_SPHERE && type != PHYS_SHAPE_BOX) return false;
+    if (type != PHYS_SHAPE_SPHERE && type != PHYS_SHAPE_BOX && type != PHYS_SHAPE_CAPSULE) return false;
     const float4 q4 = reinterpret_cast<const float4*>(rot)[i];
     quat q; q.i = q4.x; q.j = q4.y; q.k = q4.z; q.w = q4.w;
     const aabb_t b = body_aabb(ld3(pos, i), q, ld3(he, i), type, 0.0f);
@@ -288,6 +288,59 @@ __device__ __forceinline__ void rc_test(const float4* __restrict__ rec, uint32_t
             const float hx = px + t * ux, hy = py + t * uy, hz = pz + t * uz;
             const float inv = 1.0f / sqrtf((hx * hx + hy * hy) + hz * hz);
             nx = hx * inv; ny = hy * inv; nz = hz * inv;
+        }
+    } else if (__float_as_uint(a.w) == PHYS_SHAPE_CAPSULE) {
+        // radius c.x, core c +- c.y * w, w = column 1 of R: the finite cylinder's side, then the two end balls; the first hit
+        // of the union is the least of their first hits (a ray that enters through a flat end of the cylinder has hit the
+        // ball there already)
+        const float4 q4 = rec[3 * (size_t)k + 1];
+        const float qi = q4.x, qj = q4.y, qk = q4.z, qw = q4.w;
+        const float wx = (qi * qj * 2.0f) - (qw * qk * 2.0f);            // R.m[1] of quat_to_m33
+        const float wy = (((qw * qw) - (qi * qi)) + (qj * qj)) - (qk * qk);  // R.m[4]
+        const float wz = (qw * qi * 2.0f) + (qj * qk * 2.0f);            // R.m[7]
+        const float r = c.x, hl = c.y, rr = r * r;
+        const float pd = (px * wx + py * wy) + pz * wz;
+        const float sp = fminf(fmaxf(pd, -hl), hl);
+        const float qx = px - sp * wx, qy = py - sp * wy, qz = pz - sp * wz;
+        if ((qx * qx + qy * qy) + qz * qz <= rr) {  // origin inside the closed capsule
+            t = 0.0f; nx = -ux; ny = -uy; nz = -uz;
+        } else {
+            t = __builtin_inff();
+            // side: the components of p and u across the axis
+            const float ud = (ux * wx + uy * wy) + uz * wz;
+            const float ax = ux - ud * wx, ay = uy - ud * wy, az = uz - ud * wz;
+            const float bx = px - pd * wx, by = py - pd * wy, bz = pz - pd * wz;
+            const float A = (ax * ax + ay * ay) + az * az;
+            const float B = (ax * bx + ay * by) + az * bz;
+            const float C = ((bx * bx + by * by) + bz * bz) - rr;
+            if (A > 1.0e-12f && B < 0.0f) {
+                const float disc = B * B - A * C;
+                if (disc >= 0.0f) {
+                    const float q = -B + sqrtf(disc);  // > 0; the near root is C / q (no cancellation)
+                    const float tc = C / q;
+                    if (tc >= 0.0f && fabsf(pd + tc * ud) <= hl) t = tc;
+                }
+            }
+            // end balls at -hl w and +hl w (the existing ray-ball test of the sphere branch)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const float s = e == 0 ? -hl : hl;
+                const float ex = px - s * wx, ey = py - s * wy, ez = pz - s * wz;
+                const float bb = (ex * ux + ey * uy) + ez * uz;
+                const float cc = ((ex * ex + ey * ey) + ez * ez) - rr;
+                if (bb < 0.0f) {
+                    const float lx = ex - bb * ux, ly = ey - bb * uy, lz = ez - bb * uz;
+                    const float disc = rr - ((lx * lx + ly * ly) + lz * lz);
+                    if (disc >= 0.0f) t = fminf(t, cc / (-bb + sqrtf(disc)));
+                }
+            }
+            if (!(t < __builtin_inff())) return;  // missed
+            // normal: from the closest point of the core to the hit
+            const float hx = px + t * ux, hy = py + t * uy, hz = pz + t * uz;
+            const float sh = fminf(fmaxf((hx * wx + hy * wy) + hz * wz, -hl), hl);
+            const float dx = hx - sh * wx, dy = hy - sh * wy, dz = hz - sh * wz;
+            const float inv = 1.0f / sqrtf((dx * dx + dy * dy) + dz * dz);
+            nx = dx * inv; ny = dy * inv; nz = dz * inv;
         }
     } else {
         const float4 q4 = rec[3 * (size_t)k + 1];

@@ -196,6 +196,7 @@ int32_t static_set(phys_world* w, uint64_t n, const float* pos, const float* rot
     // no statics until every buffer of the new set is in place: a failed allocation or copy below leaves a world without
     // statics, never a count that runs past the records (k_rc_trace, k_narrowphase)
     w->n_static = 0;
+    w->static_capsules = false;
     w->st_n_large = 0;
     w->st_dim[0] = w->st_dim[1] = w->st_dim[2] = 0;
     w->static_pairs_sized = false;
@@ -216,7 +217,9 @@ int32_t static_set(phys_world* w, uint64_t n, const float* pos, const float* rot
         std::memcpy(&rc[12 * k], g, 48);
         std::memcpy(&rc[12 * k + 3], &shape[k], 4);
         std::memcpy(&rc[12 * k + 11], &id, 4);
-        // fattened by the contact margin like the bodies' boxes: a pair is a candidate wherever body-body pairs would be
+        if (shape[k] == PHYS_SHAPE_CAPSULE) w->static_capsules = true;
+        // fattened by the contact margin like the bodies' boxes (a capsule's from its segment and radius, collide.h): a pair
+        // is a candidate wherever body-body pairs would be
         const aabb_t b = body_aabb(c, q, h, shape[k], margin);
         lo[3 * k] = b.lo.x; lo[3 * k + 1] = b.lo.y; lo[3 * k + 2] = b.lo.z;
         hi[3 * k] = b.hi.x; hi[3 * k + 1] = b.hi.y; hi[3 * k + 2] = b.hi.z;

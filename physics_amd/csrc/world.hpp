@@ -219,6 +219,7 @@ struct phys_world {
     bool singular_inertia = false;  // some body's inertia tensor has det == 0 (reference panics in step)
     bool all_diag_inertia = true;
     bool uniform_inertia = true;  // all diagonal AND identical for every body
+    bool body_capsules = false;   // some owned body is a PHYS_SHAPE_CAPSULE (phys_set_bodies): the narrow phase's capsule variant
     bool aabbs_valid = false;
     bool grid_valid = false;  // bucket grid + AABBs of the last broad phase are on the device (halo entry points)
 
@@ -332,6 +333,7 @@ struct phys_world {
     phys::DevBuf<unsigned long long> rc_stats;  // PHYS_DEBUG_RAYCAST_STATS: cells, candidates
     // static colliders (static.hip): immovable shapes set by phys_set_static_bodies, read-only until the next such call
     uint64_t n_static = 0;
+    bool static_capsules = false;        // some static is a PHYS_SHAPE_CAPSULE: the narrow phase's capsule variant
     phys::DevBuf<float> st_geo;          // 16 floats per static, the layout of `geo`: {pos, shape} {rot} {half extent, -}
     phys::DevBuf<float> st_rc;           // 12 floats per static, the ray-cast record {pos, shape} {rot} {half extent, id}
     phys::DevBuf<float> st_box;          // 8 floats per static: {fattened AABB lo, packed first grid cell} {hi, -}

@@ -7,8 +7,8 @@ benchmark scenes; reference-parity tests keep (0,0,1.5)). Jitter comes from spli
 """
 import numpy as np
 
-from ._abi import (FLAG_BROADPHASE_ONLY, FLAG_COLLISIONS, FLAG_EXCLUSIVE_GPU, FLAG_GROUND_PLANE, SHAPE_BOX, SHAPE_SPHERE,
-                   default_config)
+from ._abi import (FLAG_BROADPHASE_ONLY, FLAG_COLLISIONS, FLAG_EXCLUSIVE_GPU, FLAG_GROUND_PLANE, SHAPE_BOX, SHAPE_CAPSULE,
+                   SHAPE_SPHERE, default_config)
 
 DT_NANOS = 16_666_667  # Duration::from_nanos -> as_secs_f32 = 0.016666668 (quirk Q7)
 _GOLDEN = np.uint64(0x9E3779B97F4A7C15)
@@ -129,6 +129,34 @@ def c5(nx=16, ny=1000, nz=16):
     return Scene(f"C5_{pos.shape[0]}_tower", pos, st, he, FLAG_COLLISIONS | FLAG_GROUND_PLANE)
 
 
+def capsule_pile(nx=32, ny=20, nz=32, name=None, spacing=2.5, y0=2.0, jitter=0.05, radius=0.5, half_length=0.5):
+    """Capsules (radius 0.5, core half-length 0.5: 2 long, 1 thick) on the lattice of falling_cubes, lying down, along x in
+    even layers and along z in odd ones, dropped onto the plane: they roll and cross in the pile."""
+    pos = lattice(nx, ny, nz, spacing, y0, jitter)
+    n = pos.shape[0]
+    layer = np.arange(n) // (nx * nz)
+    s = np.float32(np.sqrt(0.5))
+    rot = np.zeros((n, 4), np.float32)
+    rot[:, 3] = s
+    rot[layer % 2 == 0, 2] = s  # 90 deg about z: the local y axis along -x
+    rot[layer % 2 == 1, 0] = s  # 90 deg about x: the local y axis along +z
+    st = np.full(n, SHAPE_CAPSULE, np.uint32)
+    he = np.tile(np.array([radius, half_length, 0.0], np.float32), (n, 1))
+    return Scene(name or f"CAPSULES_{n}_pile", pos, st, he, FLAG_COLLISIONS | FLAG_GROUND_PLANE, rot=rot)
+
+
+def capsule_inertia(mass, radius, half_length):
+    """Inertia tensor (3x3, row-major float32) of a solid capsule of uniform density about its centre, core along the
+    local y axis: a cylinder of length 2 * half_length and two hemispheres."""
+    r, h = float(radius), float(half_length)
+    v_cyl, v_sph = np.pi * r * r * 2.0 * h, 4.0 / 3.0 * np.pi * r ** 3
+    m_cyl = mass * v_cyl / (v_cyl + v_sph) if v_cyl + v_sph > 0 else 0.0
+    m_sph = mass - m_cyl
+    iy = m_cyl * r * r / 2.0 + m_sph * 2.0 * r * r / 5.0
+    ix = m_cyl * (r * r / 4.0 + h * h / 3.0) + m_sph * (2.0 * r * r / 5.0 + h * h + 3.0 * h * r / 4.0)
+    return np.diag([ix, iy, ix]).astype(np.float32)
+
+
 def target_1m():
     """north_star target scene: 1M cubes dropped onto a plane (100x100x100, spacing 2.5)."""
     return falling_cubes(100, 100, 100, "T_1M_cubes")
@@ -173,4 +201,4 @@ def reference_cg(n=4096):
 
 
 SCENES = {"c1": c1, "c2": c2, "c3": c3, "c4": c4, "c5": c5, "t1m": target_1m, "t1m_settled": target_1m,
-          "ref_1m": reference_path, "ref_cg": reference_cg}
+          "ref_1m": reference_path, "ref_cg": reference_cg, "capsules": capsule_pile}

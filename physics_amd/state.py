@@ -40,7 +40,7 @@ class RigidBody:
         self.position = np.zeros(3, np.float32)
         self.rotation = np.array([0, 0, 0, 1], np.float32)  # [i, j, k, w]
         self.index = index
-        self.shape_type = _abi.SHAPE_NONE  # new: the reference has no shapes
+        self.shape_type = _abi.SHAPE_NONE  # new: the reference has no shapes; SHAPE_SPHERE / SHAPE_BOX / SHAPE_CAPSULE
         self.half_extent = np.zeros(3, np.float32)
 
     @staticmethod

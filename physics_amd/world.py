@@ -67,7 +67,8 @@ class World:
 
     def set_static_bodies(self, pos, rot=None, shape_type=None, half_extent=None):
         """Replace the static colliders (phys_set_static_bodies): pos (n, 3), rot (n, 4) [i, j, k, w] or None (identity),
-        shape_type (n,) SHAPE_SPHERE / SHAPE_BOX, half_extent (n, 3). An empty pos clears the set. Collider k is named
+        shape_type (n,) SHAPE_SPHERE / SHAPE_BOX / SHAPE_CAPSULE, half_extent (n, 3) (capsule: radius, core half-length along
+        the local y axis, unused). An empty pos clears the set. Collider k is named
         STATIC_ID_BIT | k in manifolds and ray hits."""
         pos = _f(pos).reshape(-1, 3)
         n = pos.shape[0]

@@ -11,6 +11,8 @@ pub const PHYS_ERR_NO_BODIES: i32 = -8;
 pub const PHYS_SHAPE_NONE: u32 = 0;
 pub const PHYS_SHAPE_SPHERE: u32 = 1;
 pub const PHYS_SHAPE_BOX: u32 = 2;
+/// radius = half_extent[0], core half-length = half_extent[1] along the local y axis
+pub const PHYS_SHAPE_CAPSULE: u32 = 3;
 pub const PHYS_STATIC_ID_BIT: u32 = 0x8000_0000;
 pub const PHYS_FLAG_COLLISIONS: u32 = 0x1;
 pub const PHYS_FLAG_GROUND_PLANE: u32 = 0x2;
