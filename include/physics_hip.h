@@ -251,6 +251,58 @@ int32_t phys_raycast(phys_world* w, uint64_t n_rays, const float* origin /*3n*/,
 int32_t phys_raycast_device(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                             const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out);
 
+/* --- sphere casts and overlap queries against the current poses (new: the reference has no queries) ---
+ * Both are read-only queries with the pose rules of phys_raycast: they see the CURRENT poses, write nothing an update
+ * or phys_broadphase reads (updates stay bit-identical with or without them), and their targets are the owned bodies
+ * with a shape and a finite pose, the static colliders and, with PHYS_FLAG_GROUND_PLANE, the half-space
+ * y <= ground_height. Ghost slots and PHYS_SHAPE_NONE bodies are never reported. Ids are the ray casts' ids: the body
+ * index, PHYS_STATIC_ID_BIT | k, PHYS_RAY_GROUND. These functions were added without an ABI version change (no struct
+ * changed, PHYS_ABI_VERSION stays 2): a library that predates them lacks the symbols, which is how a caller tells.
+ *
+ * phys_spherecast: a ball of radius[i] moves from origin[i] along dir[i] / |dir[i]|; the result is the first target the
+ * closed ball touches and the distance t its centre travelled. Everything else is phys_raycast's rule: t <= max_t (NULL =
+ * +inf), ties to the least (t, id), ignore_body as for rays, a miss is PHYS_RAY_MISS with t = +inf and a zero normal, an
+ * invalid dir, origin or max_t misses, and so does a negative, NaN or infinite radius.
+ *   - a ball that already overlaps a target at t = 0 reports t = 0 and normal = -dir / |dir|.
+ *   - otherwise normal is the outward unit normal of the target at the contact: the direction from the target's closest
+ *     point to the ball's centre at t. The contact point (not an output) is centre(t) - radius * normal.
+ *   - the test is a ray cast against the target grown by the radius (its Minkowski sum with the ball): a sphere or capsule
+ *     of r + radius, the rounded box (three boxes each grown along one axis and twelve edge capsules of the radius), the
+ *     plane y = ground_height + radius. radius = 0 gives phys_raycast's answer (the same id except at exact ties or
+ *     grazing rays, t within rounding).
+ *   - the call builds phys_raycast's grid over body AABBs grown by its largest valid radius (capped at 2^100), so the
+ *     walk of the centre line meets every candidate. One huge radius coarsens the grid as one huge body does: the call
+ *     gets slower, never wrong.
+ *   - PHYS_ERR_INVALID_ARG: n >= 2^31, a NULL origin, dir, radius, body_out or t_out. n == 0 is a no-op.
+ * phys_spherecast takes host arrays and returns with the outputs written; phys_spherecast_device takes device pointers
+ * and only enqueues on the world's stream. */
+int32_t phys_spherecast(phys_world* w, uint64_t n, const float* origin /*3n*/, const float* dir /*3n*/,
+                        const float* radius /*n*/, const float* max_t /*n, NULL = +inf*/,
+                        const uint32_t* ignore_body /*n, NULL = none*/,
+                        uint32_t* body_out /*n*/, float* t_out /*n*/, float* normal_out /*3n, may be NULL*/);
+int32_t phys_spherecast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius,
+                               const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out,
+                               float* normal_out);
+/* phys_overlap: for each query shape (shape_type SPHERE, BOX or CAPSULE with the bodies' half_extent conventions, at pos
+ * with the unit quaternion rot_ijkw, NULL = identity), every target whose closed shape intersects it (touching counts).
+ *   - output (CSR): query i's ids are ids_out[offsets_out[i] .. offsets_out[i + 1]), ascending and each once: bodies,
+ *     then statics, then the ground. offsets_out (n + 1 entries) is always written; when offsets_out[n] > cap the call
+ *     returns PHYS_ERR_CAPACITY and ids_out is unspecified (resize to offsets_out[n] and call again).
+ *   - ignore_body[i] (NULL = none), when below n_bodies, is never reported for query i.
+ *   - a query with another shape type, a non-finite pose or a negative half extent gets an empty list, not an error.
+ *   - exact tests in float32: spheres and capsules by the distance of their cores, a sphere or capsule against a box by
+ *     the distance of its core to the box, box against box by separating axes (near-parallel edge pairs skipped: the face
+ *     axes cover them), the ground by the query's lowest point.
+ *   - the result depends only on the query and the world: the same across calls, query orders and batch sizes.
+ *   - candidates come from phys_raycast's grid (not grown); a query that covers more cells than there are bodies tests
+ *     every body directly. Statics are all tested, as for rays.
+ *   - PHYS_ERR_INVALID_ARG: n >= 2^31, a NULL offsets_out, a NULL shape_type, pos or half_extent with n > 0, a NULL
+ *     ids_out with cap > 0. Host arrays only; synchronous. */
+int32_t phys_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type /*n*/, const float* pos /*3n*/,
+                     const float* rot_ijkw /*4n, NULL = identity*/, const float* half_extent /*3n*/,
+                     const uint32_t* ignore_body /*n, NULL = none*/,
+                     uint64_t cap, uint64_t* offsets_out /*n + 1*/, uint32_t* ids_out /*cap*/);
+
 /* --- static colliders: immovable SPHERE / BOX / CAPSULE shapes that bodies collide with and rays hit. Not bodies. ---
  * Level geometry (floors, walls, ramps, pillars, container sides) that never moves: no velocity, no mass, no colour of
  * its own. A manifold against static k is one-sided like a ground manifold (body A against a partner at rest with zero

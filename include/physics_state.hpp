@@ -185,6 +185,54 @@ class PhysicsState {  // physics.rs:25-31
         for (size_t i = 0; i < n; ++i) out[i] = RayHit{body[i], t[i], Vector3(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2])};
         return out;
     }
+    // first hit per moving ball against the entities as they are now (phys_spherecast): as raycast, t being the
+    // distance the centre travelled
+    std::vector<RayHit> spherecast(const std::vector<Vector3>& origins, const std::vector<Vector3>& dirs,
+                                   const std::vector<float>& radius, const std::vector<float>& max_t = {},
+                                   const std::vector<uint32_t>& ignore_body = {}) {
+        if (origins.size() != dirs.size() || radius.size() != origins.size() || (!max_t.empty() && max_t.size() != origins.size()) ||
+            (!ignore_body.empty() && ignore_body.size() != origins.size()))
+            throw Panic(PHYS_ERR_INVALID_ARG, "spherecast: array lengths differ");
+        push();
+        const size_t n = origins.size();
+        std::vector<float> o(3 * n), d(3 * n), t(n), nrm(3 * n);
+        std::vector<uint32_t> body(n);
+        for (size_t i = 0; i < n; ++i) {
+            o[3 * i] = origins[i].x; o[3 * i + 1] = origins[i].y; o[3 * i + 2] = origins[i].z;
+            d[3 * i] = dirs[i].x; d[3 * i + 1] = dirs[i].y; d[3 * i + 2] = dirs[i].z;
+        }
+        if (n) check(phys_spherecast(w_, n, o.data(), d.data(), radius.data(), max_t.empty() ? nullptr : max_t.data(),
+                                     ignore_body.empty() ? nullptr : ignore_body.data(), body.data(), t.data(), nrm.data()));
+        std::vector<RayHit> out(n);
+        for (size_t i = 0; i < n; ++i) out[i] = RayHit{body[i], t[i], Vector3(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2])};
+        return out;
+    }
+    // every entity each query shape intersects as they are now (phys_overlap): per query the ascending ids; rot_ijkw
+    // (4 floats per query) may be empty (identity); retries once when the ids outgrow the first guess
+    std::vector<std::vector<uint32_t>> overlap(const std::vector<uint32_t>& shape_type, const std::vector<Vector3>& pos,
+                                               const std::vector<float>& rot_ijkw, const std::vector<Vector3>& half_extent) {
+        const size_t n = pos.size();
+        if (shape_type.size() != n || half_extent.size() != n || (!rot_ijkw.empty() && rot_ijkw.size() != 4 * n))
+            throw Panic(PHYS_ERR_INVALID_ARG, "overlap: array lengths differ");
+        push();
+        std::vector<float> p(3 * n), h(3 * n);
+        for (size_t i = 0; i < n; ++i) {
+            p[3 * i] = pos[i].x; p[3 * i + 1] = pos[i].y; p[3 * i + 2] = pos[i].z;
+            h[3 * i] = half_extent[i].x; h[3 * i + 1] = half_extent[i].y; h[3 * i + 2] = half_extent[i].z;
+        }
+        std::vector<uint64_t> off(n + 1, 0);
+        std::vector<uint32_t> ids(8 * n + 64);
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            const int32_t rc = phys_overlap(w_, n, shape_type.data(), p.data(), rot_ijkw.empty() ? nullptr : rot_ijkw.data(), h.data(),
+                                            nullptr, ids.size(), off.data(), ids.data());
+            if (rc == PHYS_ERR_CAPACITY && attempt == 0) { ids.resize(off[n]); continue; }
+            check(rc);
+            break;
+        }
+        std::vector<std::vector<uint32_t>> out(n);
+        for (size_t i = 0; i < n; ++i) out[i].assign(ids.begin() + off[i], ids.begin() + off[i + 1]);
+        return out;
+    }
     phys_world* raw() { return w_; }
 
   private:

@@ -165,6 +165,10 @@ PROTOTYPES = {
     "phys_raycast": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, u32p, u32p, f32p, f32p]),
     "phys_raycast_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "phys_spherecast": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, u32p, u32p, f32p, f32p]),
+    "phys_spherecast_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "phys_overlap": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p, f32p, u32p, C.c_uint64, u64p, u32p]),
     "phys_set_static_bodies": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, u32p, f32p]),
     "phys_get_static_stats": (C.c_int32, [C.c_void_p, u64p, u64p, u64p]),
     "phys_profile_enable": (C.c_int32, [C.c_void_p, C.c_int32]),

@@ -221,7 +221,7 @@ int32_t phys_destroy(phys_world* w) {
     DevBuf<float>* fb[] = {&w->pos, &w->rot, &w->vel, &w->force, &w->torque, &w->inv_inertia_diag,
                            &w->inv_inertia, &w->half_extent, &w->aabb, &w->cg_x, &w->cg_r, &w->cg_p, &w->cg_ap,
                            &w->cg_rhs, &w->cg_c, &w->cg_scratch, &w->cg_jl, &w->geo, &w->man_geo_prev, &w->man_imp, &w->man_imp_prev, &w->man_geo, &w->row_n,
-                           &w->row_pt, &w->row_tb, &w->row_acc, &w->row_all, &w->flow_vel, &w->sorted_box, &w->slot_box, &w->rc_records, &w->rc_in, &w->rc_out,
+                           &w->row_pt, &w->row_tb, &w->row_acc, &w->row_all, &w->flow_vel, &w->sorted_box, &w->slot_box, &w->rc_records, &w->rc_in, &w->rc_out, &w->qr_in,
                            &w->st_geo, &w->st_rc, &w->st_box};
     for (auto* b : fb) b->free();
     DevBuf<uint32_t>* ub[] = {&w->shape, &w->global_id, &w->cg_status, &w->bucket_of, &w->bucket_count,
@@ -229,12 +229,12 @@ int32_t phys_destroy(phys_world* w) {
                               &w->man_a, &w->man_b, &w->man_color, &w->row_hdr, &w->halo_block_counts,
                               &w->man_prev, &w->cluster_slot, &w->cluster_body, &w->body_shared, &w->active_flag, &w->active_rank, &w->seg_count, &w->seg_start, &w->man_rank,
                               &w->row_src, &w->cross_pairs, &w->color_block_hist, &w->cg_cols,
-                              &w->rc_header, &w->rc_count, &w->rc_start, &w->rc_tile_sum,
+                              &w->rc_header, &w->rc_count, &w->rc_start, &w->rc_tile_sum, &w->qr_count, &w->qr_ids,
                               &w->st_cell_start, &w->st_cell_ids, &w->st_large, &w->st_count, &w->st_block, &w->st_pairs};
     for (auto* b : ub) b->free();
     w->man_prio.free(); w->color_state.free(); w->bucket_count.free(); w->step_zero.free();
     w->d_constraints.free(); w->counters.free();
-    w->ctab.free(); w->unc_list.free(); w->rc_stats.free();
+    w->ctab.free(); w->unc_list.free(); w->rc_stats.free(); w->qr_off.free();
     w->prof.destroy();
     for (int k = 0; k < phys_world::kSnapRing; ++k) {
         if (w->h_snap[k]) (void)hipHostFree(w->h_snap[k]);
@@ -782,6 +782,79 @@ int32_t phys_raycast_device(phys_world* w, uint64_t n_rays, const float* origin,
     int32_t rc = raycast_args(n_rays, origin, dir, body_out, t_out); if (rc) return rc;
     if (n_rays == 0) return PHYS_OK;
     return launch_raycast(w, n_rays, origin, dir, max_t, ignore_body, body_out, t_out, normal_out);
+}
+
+static int32_t spherecast_args(uint64_t n, const float* origin, const float* dir, const float* radius, const uint32_t* body_out,
+                               const float* t_out) {
+    if (n >= (1ull << 31)) return fail(PHYS_ERR_INVALID_ARG, "phys_spherecast: n must be below 2^31");
+    if (n && (!origin || !dir || !radius || !body_out || !t_out))
+        return fail(PHYS_ERR_INVALID_ARG, "phys_spherecast: null origin, dir, radius, body_out or t_out");
+    return PHYS_OK;
+}
+
+int32_t phys_spherecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
+                        const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
+    ENTER(w);
+    int32_t rc = spherecast_args(n, origin, dir, radius, body_out, t_out); if (rc) return rc;
+    if (n == 0) return PHYS_OK;
+    // staging: in = origin 3n | dir 3n | radius n | max_t n | ignore n, out = t n | body n | normal 3n (all 4-byte words)
+    const size_t m = (size_t)n;
+    PHYS_HIP_TRY(w->qr_in.resize(9 * m));
+    PHYS_HIP_TRY(w->rc_out.resize(5 * m));
+    hipStream_t s = w->stream;
+    float* d_origin = w->qr_in.p;
+    float* d_dir = d_origin + 3 * m;
+    float* d_radius = d_dir + 3 * m;
+    float* d_max_t = max_t ? d_radius + m : nullptr;
+    uint32_t* d_ignore = ignore_body ? reinterpret_cast<uint32_t*>(d_radius + 2 * m) : nullptr;
+    float* d_t = w->rc_out.p;
+    uint32_t* d_body = reinterpret_cast<uint32_t*>(d_t + m);
+    float* d_normal = normal_out ? d_t + 2 * m : nullptr;
+    PHYS_HIP_TRY(hipMemcpyAsync(d_origin, origin, 12 * m, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(d_dir, dir, 12 * m, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(d_radius, radius, 4 * m, hipMemcpyHostToDevice, s));
+    if (d_max_t) PHYS_HIP_TRY(hipMemcpyAsync(d_max_t, max_t, 4 * m, hipMemcpyHostToDevice, s));
+    if (d_ignore) PHYS_HIP_TRY(hipMemcpyAsync(d_ignore, ignore_body, 4 * m, hipMemcpyHostToDevice, s));
+    rc = launch_spherecast(w, n, d_origin, d_dir, d_radius, d_max_t, d_ignore, d_body, d_t, d_normal); if (rc) return rc;
+    rc = d2h(w, body_out, d_body, 4 * m); if (rc) return rc;
+    rc = d2h(w, t_out, d_t, 4 * m); if (rc) return rc;
+    if (normal_out) { rc = d2h(w, normal_out, d_normal, 12 * m); if (rc) return rc; }
+    PHYS_HIP_TRY(hipStreamSynchronize(s));
+    return PHYS_OK;
+}
+
+int32_t phys_spherecast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
+                               const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
+    ENTER(w);
+    int32_t rc = spherecast_args(n, origin, dir, radius, body_out, t_out); if (rc) return rc;
+    if (n == 0) return PHYS_OK;
+    return launch_spherecast(w, n, origin, dir, radius, max_t, ignore_body, body_out, t_out, normal_out);
+}
+
+int32_t phys_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,
+                     const float* half_extent, const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out) {
+    ENTER(w);
+    if (n >= (1ull << 31)) return fail(PHYS_ERR_INVALID_ARG, "phys_overlap: n must be below 2^31");
+    if (!offsets_out) return fail(PHYS_ERR_INVALID_ARG, "phys_overlap: null offsets_out");
+    if (n && (!shape_type || !pos || !half_extent)) return fail(PHYS_ERR_INVALID_ARG, "phys_overlap: null shape_type, pos or half_extent");
+    if (cap && !ids_out) return fail(PHYS_ERR_INVALID_ARG, "phys_overlap: null ids_out with cap > 0");
+    offsets_out[0] = 0;
+    if (n == 0) return PHYS_OK;
+    // staging: type n | pos 3n | half extent 3n | ignore n | rot 4n (rot last and 16-byte aligned: read as float4)
+    const size_t m = (size_t)n;
+    PHYS_HIP_TRY(w->qr_in.resize(8 * m + 4 * m + 4));
+    hipStream_t s = w->stream;
+    uint32_t* d_type = reinterpret_cast<uint32_t*>(w->qr_in.p);
+    float* d_pos = w->qr_in.p + m;
+    float* d_he = d_pos + 3 * m;
+    uint32_t* d_ignore = ignore_body ? reinterpret_cast<uint32_t*>(d_he + 3 * m) : nullptr;
+    float* d_rot = rot_ijkw ? w->qr_in.p + ((8 * m + 3) & ~(size_t)3) : nullptr;
+    PHYS_HIP_TRY(hipMemcpyAsync(d_type, shape_type, 4 * m, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(d_pos, pos, 12 * m, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(d_he, half_extent, 12 * m, hipMemcpyHostToDevice, s));
+    if (d_ignore) PHYS_HIP_TRY(hipMemcpyAsync(d_ignore, ignore_body, 4 * m, hipMemcpyHostToDevice, s));
+    if (d_rot) PHYS_HIP_TRY(hipMemcpyAsync(d_rot, rot_ijkw, 16 * m, hipMemcpyHostToDevice, s));
+    return launch_overlap(w, n, d_type, d_pos, d_rot, d_he, d_ignore, cap, offsets_out, ids_out);
 }
 
 int32_t phys_set_global_ids(phys_world* w, const uint32_t* global_ids) {

@@ -254,6 +254,15 @@ void static_narrow_args(const phys_world* w, uint64_t* cap, const uint32_t** pai
 // raycast.hip: builds the query's grid from the current poses and traces the rays (device pointers), all on w->stream
 int32_t launch_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                        const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out);
+// ... the same walk for balls of radius[i] (the grid grown by the largest valid radius)
+int32_t launch_spherecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
+                          const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out);
+// the query grid alone (rc_header, rc_start, rc_records), every body AABB grown by the largest valid value of the device
+// array grow_radius (null: not grown); *bits = log2 of the bucket table
+int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_radius, uint32_t* bits);
+// query.hip: overlap queries on staged device arrays; writes the host offsets (n + 1) and, when they fit in cap, the ids
+int32_t launch_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot, const float* half_extent,
+                       const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out);
 
 int32_t halo_pack_bodies(phys_world* w, void* dev_out, uint64_t cap);
 int32_t halo_pack_bodies_faces(phys_world* w, void* dev_out, uint64_t cap, float x_lo, float x_hi);

@@ -1,4 +1,5 @@
-// raycast.hip — batched ray casts against the current poses (phys_raycast / phys_raycast_device).
+// raycast.hip — batched ray casts and sphere casts against the current poses (phys_raycast / phys_raycast_device,
+// phys_spherecast / phys_spherecast_device), and the query grid they and the overlap queries (query.hip) walk.
 //
 // A read-only query: it owns its acceleration structure, rebuilt on every call from the SoA poses (pos, rot, half_extent,
 // shape) inside rc_* buffers of its own, and writes nothing an update or phys_broadphase reads (no counters, no bucket_*
@@ -19,102 +20,22 @@
 // which the build rules forbid). Every candidate of a cell is tested exactly; the walk stops once the best t is at or
 // below the cell's exit t (a candidate's hit beyond the exit may still be beaten by a later cell: multi-insertion). The
 // winner is the least (t, id); the order in which the scatter's atomics placed a bucket's records changes nothing.
+// Sphere casts (k_rc_trace<, true>) run the same walk for the ball's centre over a grid whose body AABBs were grown by the
+// call's largest valid radius (k_sc_grow writes it into the header before k_rc_bounds; ray casts leave it zero, which
+// changes no arithmetic), and test each candidate with sc_test: the ray against the target grown by the ball's radius.
 #include <cstdio>
 
-#include "kernels.hpp"
+#include "rc_grid.hpp"
 
 namespace phys {
 
 namespace {
 
-constexpr int kRcThreads = 256;
 constexpr int kRcScanItems = 16;                              // per thread of the scan kernels
 constexpr uint32_t kRcScanTile = kRcThreads * kRcScanItems;   // 4096 buckets per workgroup; the table is a multiple of it
 constexpr int kRcMaxBoundsBlocks = 1024;
-constexpr uint32_t kRcMaxCellsPerAxis = 1u << 20;
-constexpr uint32_t kRayMiss = PHYS_RAY_MISS, kRayGround = PHYS_RAY_GROUND;
-
-// k_rc_bounds' result: order-preserving keys (0 = nothing seen, which no finite float maps to); the low corner as the
-// key of -x so that every slot is a max and one memset to zero resets them all
-struct RcHeader {
-    uint32_t neg_lo[3];
-    uint32_t hi[3];
-    uint32_t edge;
-    uint32_t pad;
-};
-
-__device__ __forceinline__ uint32_t f2key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
-// the grid every kernel derives from the header (same arithmetic everywhere, so insertion and walk agree on every cell)
-struct RcGrid {
-    float lox, loy, loz;  // grid origin = scene bounds - pad
-    float cell, inv, pad;
-    int nx, ny, nz;       // cells per axis
-    bool valid;           // some owned body has a shape
-};
-
-__device__ __forceinline__ int rc_dim(float span, float inv) {
-    float c = floorf(span * inv) + 1.0f;
-    c = c < 1.0f ? 1.0f : (c > (float)kRcMaxCellsPerAxis + 1.0f ? (float)kRcMaxCellsPerAxis + 1.0f : c);
-    return (int)c;
-}
-
-__device__ __forceinline__ RcGrid rc_grid(const RcHeader* __restrict__ h) {
-    RcGrid g;
-    g.valid = h->hi[0] != 0u;
-    const float lx = -key2f(h->neg_lo[0]), ly = -key2f(h->neg_lo[1]), lz = -key2f(h->neg_lo[2]);
-    const float hx = key2f(h->hi[0]), hy = key2f(h->hi[1]), hz = key2f(h->hi[2]);
-    const float e = g.valid ? key2f(h->edge) : 0.0f;
-    float m = fmaxf(fmaxf(fabsf(lx), fabsf(hx)), fmaxf(fmaxf(fabsf(ly), fabsf(hy)), fmaxf(fabsf(lz), fabsf(hz))));
-    if (!g.valid) m = 0.0f;
-    // pad: float rounding of an AABB, of a cell coordinate and of the walk's plane crossings is a few ulp of the scene's
-    // coordinates; 2^-16 of them is hundreds of ulp. The cell exceeds the padded edge, so a body touches <= 2 cells per axis
-    g.pad = 0x1p-16f * (m + e);
-    g.lox = lx - g.pad; g.loy = ly - g.pad; g.loz = lz - g.pad;
-    const float sx = (hx + g.pad) - g.lox, sy = (hy + g.pad) - g.loy, sz = (hz + g.pad) - g.loz;
-    float cell = (e + 2.0f * g.pad) * (1.0f + 0x1p-10f);
-    const float span = fmaxf(sx, fmaxf(sy, sz));
-    if (span * 0x1p-20f > cell) cell = span * 0x1p-20f;  // at most 2^20 cells per axis (far-flung scenes: coarser cells)
-    g.cell = fmaxf(cell, 1.0e-30f);
-    g.inv = 1.0f / g.cell;
-    g.nx = g.valid ? rc_dim(sx, g.inv) : 1;
-    g.ny = g.valid ? rc_dim(sy, g.inv) : 1;
-    g.nz = g.valid ? rc_dim(sz, g.inv) : 1;
-    return g;
-}
-
-__device__ __forceinline__ int rc_coord(float x, float lo, float inv, int n) {
-    float c = floorf((x - lo) * inv);
-    c = c < 0.0f ? 0.0f : (c > (float)(n - 1) ? (float)(n - 1) : c);  // NaN stays NaN -> (int) 0 on gfx950, still in range
-    const int i = (int)c;
-    return i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
-}
-
-// multiplicative hash of the cell, top `bits` bits
-__device__ __forceinline__ uint32_t rc_bucket(int x, int y, int z, uint32_t bits) {
-    const uint32_t h = ((uint32_t)x * 73856093u) ^ ((uint32_t)y * 19349663u) ^ ((uint32_t)z * 83492791u);
-    return (h * 0x9E3779B1u) >> (32u - bits);
-}
-
-__device__ __forceinline__ bool rc_aabb(const float* __restrict__ pos, const float* __restrict__ rot, const float* __restrict__ he,
-                                        const uint32_t* __restrict__ shape, uint32_t i, aabb_t* out) {
-    const uint32_t type = shape[i];
-    if (type != PHYS_SHAPE_SPHERE && type != PHYS_SHAPE_BOX && type != PHYS_SHAPE_CAPSULE) return false;
-    const float4 q4 = reinterpret_cast<const float4*>(rot)[i];
-    quat q; q.i = q4.x; q.j = q4.y; q.k = q4.z; q.w = q4.w;
-    const aabb_t b = body_aabb(ld3(pos, i), q, ld3(he, i), type, 0.0f);
-    // a non-finite pose is never inserted (and so never hit)
-    const float s = ((b.lo.x + b.lo.y) + (b.lo.z + b.hi.x)) + (b.hi.y + b.hi.z);
-    if (!isfinite(s)) return false;
-    *out = b;
-    return true;
-}
+// a sphere cast grows the grid by its largest valid radius, capped here so that grown bounds stay finite
+constexpr float kScMaxGrow = 0x1p100f;
 
 __global__ __launch_bounds__(kRcThreads) void k_rc_bounds(uint32_t n, const float* __restrict__ pos, const float* __restrict__ rot,
                                                          const float* __restrict__ he, const uint32_t* __restrict__ shape,
@@ -123,9 +44,11 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_bounds(uint32_t n, const floa
 #pragma unroll
     for (int a = 0; a < 7; ++a) k[a] = -3.0e38f;
     bool any = false;
+    const float grow = __uint_as_float(hdr->grow);  // written before this launch (k_sc_grow) or zero
     for (uint32_t i = blockIdx.x * kRcThreads + threadIdx.x; i < n; i += gridDim.x * kRcThreads) {
         aabb_t b;
         if (!rc_aabb(pos, rot, he, shape, i, &b)) continue;
+        b = rc_grown(b, grow);
         any = true;
         k[0] = fmaxf(k[0], -b.lo.x); k[1] = fmaxf(k[1], -b.lo.y); k[2] = fmaxf(k[2], -b.lo.z);
         k[3] = fmaxf(k[3], b.hi.x); k[4] = fmaxf(k[4], b.hi.y); k[5] = fmaxf(k[5], b.hi.z);
@@ -164,9 +87,8 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_insert(uint32_t n, const floa
     aabb_t b;
     if (!rc_aabb(pos, rot, he, shape, i, &b)) return;
     const RcGrid g = rc_grid(hdr);
-    const int x0 = rc_coord(b.lo.x - g.pad, g.lox, g.inv, g.nx), x1 = min(rc_coord(b.hi.x + g.pad, g.lox, g.inv, g.nx), x0 + 1);
-    const int y0 = rc_coord(b.lo.y - g.pad, g.loy, g.inv, g.ny), y1 = min(rc_coord(b.hi.y + g.pad, g.loy, g.inv, g.ny), y0 + 1);
-    const int z0 = rc_coord(b.lo.z - g.pad, g.loz, g.inv, g.nz), z1 = min(rc_coord(b.hi.z + g.pad, g.loz, g.inv, g.nz), z0 + 1);
+    const RcCells cl = rc_body_cells(g, rc_grown(b, __uint_as_float(hdr->grow)));
+    const int x0 = cl.x0, x1 = cl.x1, y0 = cl.y0, y1 = cl.y1, z0 = cl.z0, z1 = cl.z1;
     float4 r0, r1, r2;
     if (WRITE) {
         const v3 c = ld3(pos, i), h = ld3(he, i);
@@ -254,14 +176,6 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_scan_final(const uint32_t* __
     if (blockIdx.x == tiles - 1 && threadIdx.x == 0) start[(size_t)tiles * kRcScanTile] = tile_sum[tiles];
 }
 
-struct RayHit {
-    float t;
-    uint32_t id;
-    float nx, ny, nz;
-};
-
-__device__ __forceinline__ bool rc_better(float t, uint32_t id, const RayHit& b) { return t < b.t || (t == b.t && id < b.id); }
-
 // exact test of one record; accepted into `best` when t <= tmax and (t, id) beats it
 __device__ __forceinline__ void rc_test(const float4* __restrict__ rec, uint32_t k, float ox, float oy, float oz, float ux, float uy,
                                         float uz, float tmax, uint32_t ignore, RayHit& best) {
@@ -272,76 +186,12 @@ __device__ __forceinline__ void rc_test(const float4* __restrict__ rec, uint32_t
     const float px = ox - a.x, py = oy - a.y, pz = oz - a.z;  // origin relative to the centre
     float t, nx, ny, nz;
     if (__float_as_uint(a.w) == PHYS_SHAPE_SPHERE) {
-        const float r = c.x;
-        const float bb = (px * ux + py * uy) + pz * uz;
-        const float cc = ((px * px + py * py) + pz * pz) - r * r;
-        if (cc <= 0.0f) {  // origin inside the closed ball
-            t = 0.0f; nx = -ux; ny = -uy; nz = -uz;
-        } else {
-            if (bb >= 0.0f) return;  // outside and moving away
-            // distance of the line from the centre without cancellation: |p - (p.u) u|^2
-            const float lx = px - bb * ux, ly = py - bb * uy, lz = pz - bb * uz;
-            const float disc = r * r - ((lx * lx + ly * ly) + lz * lz);
-            if (disc < 0.0f) return;
-            const float q = -bb + sqrtf(disc);  // the far root (> 0); the near one is cc / q (no cancellation)
-            t = cc / q;
-            const float hx = px + t * ux, hy = py + t * uy, hz = pz + t * uz;
-            const float inv = 1.0f / sqrtf((hx * hx + hy * hy) + hz * hz);
-            nx = hx * inv; ny = hy * inv; nz = hz * inv;
-        }
+        if (!ray_ball(px, py, pz, ux, uy, uz, c.x, t, nx, ny, nz)) return;
     } else if (__float_as_uint(a.w) == PHYS_SHAPE_CAPSULE) {
-        // radius c.x, core c +- c.y * w, w = column 1 of R: the finite cylinder's side, then the two end balls; the first hit
-        // of the union is the least of their first hits (a ray that enters through a flat end of the cylinder has hit the
-        // ball there already)
-        const float4 q4 = rec[3 * (size_t)k + 1];
-        const float qi = q4.x, qj = q4.y, qk = q4.z, qw = q4.w;
-        const float wx = (qi * qj * 2.0f) - (qw * qk * 2.0f);            // R.m[1] of quat_to_m33
-        const float wy = (((qw * qw) - (qi * qi)) + (qj * qj)) - (qk * qk);  // R.m[4]
-        const float wz = (qw * qi * 2.0f) + (qj * qk * 2.0f);            // R.m[7]
-        const float r = c.x, hl = c.y, rr = r * r;
-        const float pd = (px * wx + py * wy) + pz * wz;
-        const float sp = fminf(fmaxf(pd, -hl), hl);
-        const float qx = px - sp * wx, qy = py - sp * wy, qz = pz - sp * wz;
-        if ((qx * qx + qy * qy) + qz * qz <= rr) {  // origin inside the closed capsule
-            t = 0.0f; nx = -ux; ny = -uy; nz = -uz;
-        } else {
-            t = __builtin_inff();
-            // side: the components of p and u across the axis
-            const float ud = (ux * wx + uy * wy) + uz * wz;
-            const float ax = ux - ud * wx, ay = uy - ud * wy, az = uz - ud * wz;
-            const float bx = px - pd * wx, by = py - pd * wy, bz = pz - pd * wz;
-            const float A = (ax * ax + ay * ay) + az * az;
-            const float B = (ax * bx + ay * by) + az * bz;
-            const float C = ((bx * bx + by * by) + bz * bz) - rr;
-            if (A > 1.0e-12f && B < 0.0f) {
-                const float disc = B * B - A * C;
-                if (disc >= 0.0f) {
-                    const float q = -B + sqrtf(disc);  // > 0; the near root is C / q (no cancellation)
-                    const float tc = C / q;
-                    if (tc >= 0.0f && fabsf(pd + tc * ud) <= hl) t = tc;
-                }
-            }
-            // end balls at -hl w and +hl w (the existing ray-ball test of the sphere branch)
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const float s = e == 0 ? -hl : hl;
-                const float ex = px - s * wx, ey = py - s * wy, ez = pz - s * wz;
-                const float bb = (ex * ux + ey * uy) + ez * uz;
-                const float cc = ((ex * ex + ey * ey) + ez * ez) - rr;
-                if (bb < 0.0f) {
-                    const float lx = ex - bb * ux, ly = ey - bb * uy, lz = ez - bb * uz;
-                    const float disc = rr - ((lx * lx + ly * ly) + lz * lz);
-                    if (disc >= 0.0f) t = fminf(t, cc / (-bb + sqrtf(disc)));
-                }
-            }
-            if (!(t < __builtin_inff())) return;  // missed
-            // normal: from the closest point of the core to the hit
-            const float hx = px + t * ux, hy = py + t * uy, hz = pz + t * uz;
-            const float sh = fminf(fmaxf((hx * wx + hy * wy) + hz * wz, -hl), hl);
-            const float dx = hx - sh * wx, dy = hy - sh * wy, dz = hz - sh * wz;
-            const float inv = 1.0f / sqrtf((dx * dx + dy * dy) + dz * dz);
-            nx = dx * inv; ny = dy * inv; nz = dz * inv;
-        }
+        // radius c.x, core c +- c.y * w, w = column 1 of R
+        float wx, wy, wz;
+        rc_capsule_axis(rec[3 * (size_t)k + 1], wx, wy, wz);
+        if (!ray_capsule(px, py, pz, ux, uy, uz, wx, wy, wz, c.x, c.y, t, nx, ny, nz)) return;
     } else {
         const float4 q4 = rec[3 * (size_t)k + 1];
         quat q; q.i = q4.x; q.j = q4.y; q.k = q4.z; q.w = q4.w;
@@ -353,29 +203,13 @@ __device__ __forceinline__ void rc_test(const float4* __restrict__ rec, uint32_t
         const float dx = (R.m[0] * ux + R.m[3] * uy) + R.m[6] * uz;
         const float dy = (R.m[1] * ux + R.m[4] * uy) + R.m[7] * uz;
         const float dz = (R.m[2] * ux + R.m[5] * uy) + R.m[8] * uz;
-        if (fabsf(lx) <= c.x && fabsf(ly) <= c.y && fabsf(lz) <= c.z) {  // origin inside the closed box
-            t = 0.0f; nx = -ux; ny = -uy; nz = -uz;
+        float sx, sy, sz;
+        const int res = ray_box_local(lx, ly, lz, dx, dy, dz, c.x, c.y, c.z, t, sx, sy, sz);
+        if (res == 0) return;
+        if (res == 1) {  // origin inside the closed box
+            nx = -ux; ny = -uy; nz = -uz;
         } else {
-            // slabs; an axis the ray is parallel to either always holds the ray (|l| <= h) or never (the box is missed)
-            const bool px0 = dx == 0.0f, py0 = dy == 0.0f, pz0 = dz == 0.0f;
-            if ((px0 && fabsf(lx) > c.x) || (py0 && fabsf(ly) > c.y) || (pz0 && fabsf(lz) > c.z)) return;
-            const float ix = 1.0f / dx, iy = 1.0f / dy, iz = 1.0f / dz;
-            // entering face of each slab: the one facing the ray (-sign(d) h)
-            const float ex = px0 ? -3.0e38f : (dx > 0.0f ? (-c.x - lx) : (c.x - lx)) * ix;
-            const float fx = px0 ? 3.0e38f : (dx > 0.0f ? (c.x - lx) : (-c.x - lx)) * ix;
-            const float ey = py0 ? -3.0e38f : (dy > 0.0f ? (-c.y - ly) : (c.y - ly)) * iy;
-            const float fy = py0 ? 3.0e38f : (dy > 0.0f ? (c.y - ly) : (-c.y - ly)) * iy;
-            const float ez = pz0 ? -3.0e38f : (dz > 0.0f ? (-c.z - lz) : (c.z - lz)) * iz;
-            const float fz = pz0 ? 3.0e38f : (dz > 0.0f ? (c.z - lz) : (-c.z - lz)) * iz;
-            const float tn = fmaxf(ex, fmaxf(ey, ez));
-            const float tf = fminf(fx, fminf(fy, fz));
-            if (!(tn <= tf) || tf < 0.0f || tn < 0.0f) return;
-            t = tn;
-            // local normal of the entering slab (ties: x, then y, then z), then into the world frame
-            const bool ax = ex == tn, ay = !ax && ey == tn, az = !ax && !ay;
-            const float sx = ax ? (dx > 0.0f ? -1.0f : 1.0f) : 0.0f;
-            const float sy = ay ? (dy > 0.0f ? -1.0f : 1.0f) : 0.0f;
-            const float sz = az ? (dz > 0.0f ? -1.0f : 1.0f) : 0.0f;
+            // local normal of the entering slab, into the world frame
             nx = (R.m[0] * sx + R.m[1] * sy) + R.m[2] * sz;
             ny = (R.m[3] * sx + R.m[4] * sy) + R.m[5] * sz;
             nz = (R.m[6] * sx + R.m[7] * sy) + R.m[8] * sz;
@@ -386,12 +220,97 @@ __device__ __forceinline__ void rc_test(const float4* __restrict__ rec, uint32_t
     if (t <= tmax && rc_better(t, id, best)) { best.t = t; best.id = id; best.nx = nx; best.ny = ny; best.nz = nz; }
 }
 
+// a ball of radius rad swept from o along u against one record: the ray against the record's shape grown by rad (its
+// Minkowski sum with the ball). Sphere r: the ball of r + rad. Capsule r: the capsule of r + rad. Box: the rounded box,
+// the union of three boxes each grown by rad along one axis (its flat faces) and of the twelve edge capsules of radius
+// rad (the cylinders along the edges; their end balls are the rounded corners): the least t over the fifteen. The normal
+// runs from the target's closest point to the centre at t; from inside (t = 0) it is -u.
+__device__ __forceinline__ void sc_test(const float4* __restrict__ rec, uint32_t k, float ox, float oy, float oz, float ux, float uy,
+                                        float uz, float rad, float tmax, uint32_t ignore, RayHit& best) {
+    const float4 a = rec[3 * (size_t)k];
+    const float4 c = rec[3 * (size_t)k + 2];
+    const uint32_t id = __float_as_uint(c.w);
+    if (id == ignore) return;
+    const float px = ox - a.x, py = oy - a.y, pz = oz - a.z;
+    float t, nx, ny, nz;
+    if (__float_as_uint(a.w) == PHYS_SHAPE_SPHERE) {
+        if (!ray_ball(px, py, pz, ux, uy, uz, c.x + rad, t, nx, ny, nz)) return;
+    } else if (__float_as_uint(a.w) == PHYS_SHAPE_CAPSULE) {
+        float wx, wy, wz;
+        rc_capsule_axis(rec[3 * (size_t)k + 1], wx, wy, wz);
+        if (!ray_capsule(px, py, pz, ux, uy, uz, wx, wy, wz, c.x + rad, c.y, t, nx, ny, nz)) return;
+    } else {
+        const float4 q4 = rec[3 * (size_t)k + 1];
+        quat q; q.i = q4.x; q.j = q4.y; q.k = q4.z; q.w = q4.w;
+        m33 R;
+        quat_to_m33(q, &R);
+        const float lx = (R.m[0] * px + R.m[3] * py) + R.m[6] * pz;
+        const float ly = (R.m[1] * px + R.m[4] * py) + R.m[7] * pz;
+        const float lz = (R.m[2] * px + R.m[5] * py) + R.m[8] * pz;
+        const float dx = (R.m[0] * ux + R.m[3] * uy) + R.m[6] * uz;
+        const float dy = (R.m[1] * ux + R.m[4] * uy) + R.m[7] * uz;
+        const float dz = (R.m[2] * ux + R.m[5] * uy) + R.m[8] * uz;
+        float sx, sy, sz;
+        // the rounded box lies inside the box grown by rad along every axis: a ray that misses that misses it
+        if (ray_box_local(lx, ly, lz, dx, dy, dz, c.x + rad, c.y + rad, c.z + rad, t, sx, sy, sz) == 0) return;
+        const float gx = fmaxf(fabsf(lx) - c.x, 0.0f), gy = fmaxf(fabsf(ly) - c.y, 0.0f), gz = fmaxf(fabsf(lz) - c.z, 0.0f);
+        bool inside = (gx * gx + gy * gy) + gz * gz <= rad * rad;  // the centre starts within rad of the box
+        float mx = 0.0f, my = 0.0f, mz = 0.0f;  // local normal of the best part
+        t = __builtin_inff();
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            float tb, bx, by, bz;
+            const int res = ray_box_local(lx, ly, lz, dx, dy, dz, c.x + (ax == 0 ? rad : 0.0f), c.y + (ax == 1 ? rad : 0.0f),
+                                          c.z + (ax == 2 ? rad : 0.0f), tb, bx, by, bz);
+            inside = inside || res == 1;
+            if (res == 2 && tb < t) { t = tb; mx = bx; my = by; mz = bz; }
+        }
+        // radius 0: the rounded box is the box (and a zero-radius cylinder is ill-conditioned), so no edges
+#pragma unroll
+        for (int e = 0; e < (rad > 0.0f ? 12 : 0); ++e) {
+            // edge e along axis e / 4, at the corner signs of bits 0 and 1 of e on the other two axes
+            const int ax = e >> 2;
+            const float s1 = (e & 1) ? 1.0f : -1.0f, s2 = (e & 2) ? 1.0f : -1.0f;
+            const float ex = ax == 0 ? 0.0f : s1 * c.x;
+            const float ey = ax == 1 ? 0.0f : (ax == 0 ? s1 : s2) * c.y;
+            const float ez = ax == 2 ? 0.0f : s2 * c.z;
+            const float hl = ax == 0 ? c.x : (ax == 1 ? c.y : c.z);
+            float te, ex_n, ey_n, ez_n;
+            if (ray_capsule(lx - ex, ly - ey, lz - ez, dx, dy, dz, ax == 0 ? 1.0f : 0.0f, ax == 1 ? 1.0f : 0.0f, ax == 2 ? 1.0f : 0.0f,
+                            rad, hl, te, ex_n, ey_n, ez_n) &&
+                te < t) {
+                t = te; mx = ex_n; my = ey_n; mz = ez_n;
+            }
+        }
+        if (inside) {
+            t = 0.0f; nx = -ux; ny = -uy; nz = -uz;
+        } else {
+            if (!(t < __builtin_inff())) return;
+            // the normal runs from the box's closest point to the centre at t: a face and the cylinder beside it give
+            // nearly equal t near their seam, and this does not depend on which of them rounding picked (the part's own
+            // normal stays for a centre that rounding put within rad / 2 of the box)
+            const float cx = lx + t * dx, cy = ly + t * dy, cz = lz + t * dz;
+            const float vx = cx - fminf(fmaxf(cx, -c.x), c.x), vy = cy - fminf(fmaxf(cy, -c.y), c.y), vz = cz - fminf(fmaxf(cz, -c.z), c.z);
+            if ((vx * vx + vy * vy) + vz * vz > 0.25f * (rad * rad)) { mx = vx; my = vy; mz = vz; }
+            nx = (R.m[0] * mx + R.m[1] * my) + R.m[2] * mz;
+            ny = (R.m[3] * mx + R.m[4] * my) + R.m[5] * mz;
+            nz = (R.m[6] * mx + R.m[7] * my) + R.m[8] * mz;
+            const float inv = 1.0f / sqrtf((nx * nx + ny * ny) + nz * nz);
+            nx *= inv; ny *= inv; nz *= inv;
+        }
+    }
+    if (t <= tmax && rc_better(t, id, best)) { best.t = t; best.id = id; best.nx = nx; best.ny = ny; best.nz = nz; }
+}
+
 __device__ __forceinline__ float rc_plane_t(int i, bool up, float lo, float cell, float o, float inv_u) {
     return ((lo + (float)(i + (up ? 1 : 0)) * cell) - o) * inv_u;
 }
 
-template <bool STATS>
+// SWEEP: a sphere cast (radius per ray; the grid was grown by the largest valid radius, so the walk of the centre line
+// meets every target the ball can touch); otherwise a ray cast (radius unused, the arithmetic of the ray cast unchanged)
+template <bool STATS, bool SWEEP>
 __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const float* __restrict__ origin, const float* __restrict__ dir,
+                                                        const float* __restrict__ radius,
                                                         const float* __restrict__ max_t, const uint32_t* __restrict__ ignore_body,
                                                         const RcHeader* __restrict__ hdr, uint32_t bits, const uint32_t* __restrict__ start,
                                                         const float4* __restrict__ rec, uint32_t n_bodies, int ground, float ground_y,
@@ -408,19 +327,25 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
     const uint32_t ign = ignore_body && ignore_body[r] < n_bodies ? ignore_body[r] : 0xFFFFFFFFu;
     const float len = sqrtf((d.x * d.x + d.y * d.y) + d.z * d.z);
     const float sum = ((o.x + o.y) + (o.z + d.x)) + (d.y + d.z);
-    if (len > 0.0f && len <= 3.0e38f && isfinite(sum) && tmax >= 0.0f) {
+    const float rad = SWEEP ? radius[r] : 0.0f;
+    const bool rad_ok = !SWEEP || (rad >= 0.0f && rad <= 3.4e38f);  // a negative, NaN or infinite radius misses
+    if (len > 0.0f && len <= 3.0e38f && isfinite(sum) && tmax >= 0.0f && rad_ok) {
         const float ux = d.x / len, uy = d.y / len, uz = d.z / len;
-        // the ground: the solid half-space y <= ground_y
+        // the ground: the solid half-space y <= ground_y (for a ball: its centre reaches y = ground_y + rad)
+        const float gy = SWEEP ? ground_y + rad : ground_y;
         if (ground) {
             float tg = -1.0f;
-            if (o.y <= ground_y) { tg = 0.0f; best.nx = -ux; best.ny = -uy; best.nz = -uz; }
-            else if (uy < 0.0f) { tg = (ground_y - o.y) / uy; best.nx = 0.0f; best.ny = 1.0f; best.nz = 0.0f; }
+            if (o.y <= gy) { tg = 0.0f; best.nx = -ux; best.ny = -uy; best.nz = -uz; }
+            else if (uy < 0.0f) { tg = (gy - o.y) / uy; best.nx = 0.0f; best.ny = 1.0f; best.nz = 0.0f; }
             if (tg >= 0.0f && tg <= tmax) { best.t = tg; best.id = kRayGround; }
             else { best.nx = 0.0f; best.ny = 0.0f; best.nz = 0.0f; }
         }
         // static colliders (records of phys_set_static_bodies, id PHYS_STATIC_ID_BIT | k): every one tested, before the bodies'
         // walk so that a static hit shortens it; bodies still win exact ties (smaller ids), the ground loses them
-        for (uint32_t k = 0; k < n_static; ++k) rc_test(st_rec, k, o.x, o.y, o.z, ux, uy, uz, tmax, 0xFFFFFFFFu, best);
+        for (uint32_t k = 0; k < n_static; ++k) {
+            if (SWEEP) sc_test(st_rec, k, o.x, o.y, o.z, ux, uy, uz, rad, tmax, 0xFFFFFFFFu, best);
+            else rc_test(st_rec, k, o.x, o.y, o.z, ux, uy, uz, tmax, 0xFFFFFFFFu, best);
+        }
         const RcGrid g = rc_grid(hdr);
         // clip to the grid box and to [0, min(max_t, best)] (bodies win ties with the ground: best.t itself stays in)
         const float iux = 1.0f / ux, iuy = 1.0f / uy, iuz = 1.0f / uz;  // +-inf on a zero component
@@ -450,7 +375,10 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
                 const uint32_t bk = rc_bucket(ix, iy, iz, bits);
                 const uint32_t b0 = start[bk], b1 = start[bk + 1];
                 if (STATS) { cells += 1; cands += b1 - b0; }
-                for (uint32_t k = b0; k < b1; ++k) rc_test(rec, k, o.x, o.y, o.z, ux, uy, uz, tlim, ign, best);
+                for (uint32_t k = b0; k < b1; ++k) {
+                    if (SWEEP) sc_test(rec, k, o.x, o.y, o.z, ux, uy, uz, rad, tlim, ign, best);
+                    else rc_test(rec, k, o.x, o.y, o.z, ux, uy, uz, tlim, ign, best);
+                }
                 if (best.t <= texit || texit > t1) break;
                 const bool ax = tx <= ty && tx <= tz, ay = !ax && ty <= tz, az = !ax && !ay;
                 ix += ax ? sx : 0; iy += ay ? sy : 0; iz += az ? sz : 0;
@@ -467,19 +395,37 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
     if (STATS) { atomicAdd(&stats[0], (unsigned long long)cells); atomicAdd(&stats[1], (unsigned long long)cands); }
 }
 
+// the largest valid (finite, non-negative) radius of a sphere cast into the header's grow slot, capped at kScMaxGrow:
+// non-negative floats order as their bits, so one atomicMax per workgroup
+__global__ __launch_bounds__(kRcThreads) void k_sc_grow(uint32_t n, const float* __restrict__ radius, RcHeader* __restrict__ hdr) {
+    float m = 0.0f;
+    for (uint32_t i = blockIdx.x * kRcThreads + threadIdx.x; i < n; i += gridDim.x * kRcThreads) {
+        const float r = radius[i];
+        if (r >= 0.0f && r <= 3.4e38f) m = fmaxf(m, fminf(r, kScMaxGrow));
+    }
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    __shared__ float red[kRcThreads / 64];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float v = 0.0f;
+        for (int w = 0; w < kRcThreads / 64; ++w) v = fmaxf(v, red[w]);
+        atomicMax(&hdr->grow, __float_as_uint(v));
+    }
+}
+
 }  // namespace
 
 unsigned rc_blocks(uint64_t n) { return (unsigned)((n + kRcThreads - 1) / kRcThreads); }
 
-int32_t launch_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
-                       const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
+int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_radius, uint32_t* bits_out) {
     hipStream_t s = w->stream;
     const uint64_t n = w->n_owned;
     PHYS_HIP_TRY(w->rc_header.resize(sizeof(RcHeader) / 4));
     PHYS_HIP_TRY(hipMemsetAsync(w->rc_header.p, 0, sizeof(RcHeader), s));
     const RcHeader* hdr = reinterpret_cast<const RcHeader*>(w->rc_header.p);
     uint32_t bits = 12;
-    if (n > (1ull << 29)) { set_error("phys_raycast: more than 2^29 bodies (the query's grid indexes insertions with 32 bits)"); return PHYS_ERR_UNSUPPORTED; }
+    if (n > (1ull << 29)) { set_error("query grid: more than 2^29 bodies (the query's grid indexes insertions with 32 bits)"); return PHYS_ERR_UNSUPPORTED; }
     if (n) {
         // table: a power of two >= 2N buckets (and a whole number of scan tiles); records: 8 insertions per body at most
         while ((1ull << bits) < 2 * n) ++bits;
@@ -490,6 +436,9 @@ int32_t launch_raycast(phys_world* w, uint64_t n_rays, const float* origin, cons
         PHYS_HIP_TRY(w->rc_records.resize(12 * 8 * (size_t)n));  // 8 records of three float4 per body
         PHYS_HIP_TRY(hipMemsetAsync(w->rc_count.p, 0, 4 * (size_t)table, s));
         const uint32_t nn = (uint32_t)n;
+        if (grow_radius && n_radius)
+            hipLaunchKernelGGL(k_sc_grow, dim3(std::min<unsigned>(rc_blocks(n_radius), kRcMaxBoundsBlocks)), dim3(kRcThreads), 0, s,
+                               (uint32_t)n_radius, grow_radius, reinterpret_cast<RcHeader*>(w->rc_header.p));
         const unsigned bb = std::min<unsigned>(rc_blocks(n), kRcMaxBoundsBlocks);
         hipLaunchKernelGGL(k_rc_bounds, dim3(bb), dim3(kRcThreads), 0, s, nn, w->pos.p, w->rot.p, w->half_extent.p, w->shape.p,
                            reinterpret_cast<RcHeader*>(w->rc_header.p));
@@ -502,28 +451,52 @@ int32_t launch_raycast(phys_world* w, uint64_t n_rays, const float* origin, cons
                            w->shape.p, hdr, bits, w->rc_count.p, w->rc_start.p, reinterpret_cast<float4*>(w->rc_records.p),
                            (uint32_t)(8 * n));
     }
+    *bits_out = bits;
+    return PHYS_OK;
+}
+
+// the walk shared by ray casts (radius == nullptr) and sphere casts
+static int32_t trace(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* radius, const float* max_t,
+                     const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
+    hipStream_t s = w->stream;
+    const uint64_t n = w->n_owned;
+    uint32_t bits = 12;
+    int32_t rc = launch_query_grid(w, radius, radius ? n_rays : 0, &bits); if (rc) return rc;
+    const RcHeader* hdr = reinterpret_cast<const RcHeader*>(w->rc_header.p);
     const bool stats = debug_switches().raycast_stats;
     if (stats) {
         PHYS_HIP_TRY(w->rc_stats.resize(2));
         PHYS_HIP_TRY(hipMemsetAsync(w->rc_stats.p, 0, 16, s));
     }
     const int ground = (w->cfg.flags & PHYS_FLAG_GROUND_PLANE) ? 1 : 0;
-#define PHYS_RC_TRACE(S)                                                                                                       \
-    hipLaunchKernelGGL(k_rc_trace<S>, dim3(rc_blocks(n_rays)), dim3(kRcThreads), 0, s, (uint32_t)n_rays, origin, dir, max_t,  \
-                       ignore_body, hdr, bits, (const uint32_t*)w->rc_start.p, reinterpret_cast<const float4*>(w->rc_records.p), \
-                       (uint32_t)n, ground, w->cfg.ground_height, reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static, \
-                       body_out, t_out, normal_out, w->rc_stats.p)
-    if (stats) PHYS_RC_TRACE(true);
-    else PHYS_RC_TRACE(false);
-#undef PHYS_RC_TRACE
+    dispatch_bool(stats, [&](auto st) {
+        dispatch_bool(radius != nullptr, [&](auto sw) {
+            hipLaunchKernelGGL((k_rc_trace<decltype(st)::value, decltype(sw)::value>), dim3(rc_blocks(n_rays)), dim3(kRcThreads), 0, s,
+                               (uint32_t)n_rays, origin, dir, radius, max_t, ignore_body, hdr, bits, (const uint32_t*)w->rc_start.p,
+                               reinterpret_cast<const float4*>(w->rc_records.p), (uint32_t)n, ground, w->cfg.ground_height,
+                               reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static, body_out, t_out, normal_out,
+                               w->rc_stats.p);
+        });
+    });
     PHYS_HIP_TRY(hipGetLastError());
     if (stats) {
         unsigned long long h[2] = {0, 0};
         PHYS_HIP_TRY(hipMemcpyAsync(h, w->rc_stats.p, 16, hipMemcpyDeviceToHost, s));
         PHYS_HIP_TRY(hipStreamSynchronize(s));
-        fprintf(stderr, "PHYS_RAYCAST_STATS rays=%llu cells=%llu candidates=%llu\n", (unsigned long long)n_rays, h[0], h[1]);
+        fprintf(stderr, "%s rays=%llu cells=%llu candidates=%llu\n", radius ? "PHYS_SPHERECAST_STATS" : "PHYS_RAYCAST_STATS",
+                (unsigned long long)n_rays, h[0], h[1]);
     }
     return PHYS_OK;
+}
+
+int32_t launch_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
+                       const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
+    return trace(w, n_rays, origin, dir, nullptr, max_t, ignore_body, body_out, t_out, normal_out);
+}
+
+int32_t launch_spherecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
+                          const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
+    return trace(w, n, origin, dir, radius, max_t, ignore_body, body_out, t_out, normal_out);
 }
 
 }  // namespace phys

@@ -331,6 +331,11 @@ struct phys_world {
     phys::DevBuf<float> rc_in;           // phys_raycast (host arrays): staged origin | dir | max_t | ignore (as u32 bits)
     phys::DevBuf<float> rc_out;          // ... and the outputs body | t | normal
     phys::DevBuf<unsigned long long> rc_stats;  // PHYS_DEBUG_RAYCAST_STATS: cells, candidates
+    // sphere casts and overlap queries (raycast.hip, query.hip): they walk the grid above; their own staging and output
+    phys::DevBuf<float> qr_in;           // phys_spherecast: origin | dir | radius | max_t | ignore; phys_overlap: type | pos | rot | half extent | ignore
+    phys::DevBuf<uint32_t> qr_count;     // phys_overlap: targets per query (count pass)
+    phys::DevBuf<unsigned long long> qr_off;  // ... their exclusive scan (n + 1)
+    phys::DevBuf<uint32_t> qr_ids;       // ... the ids in walk order, then each query's ids ascending
     // static colliders (static.hip): immovable shapes set by phys_set_static_bodies, read-only until the next such call
     uint64_t n_static = 0;
     bool static_capsules = false;        // some static is a PHYS_SHAPE_CAPSULE: the narrow phase's capsule variant

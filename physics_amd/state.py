@@ -178,6 +178,17 @@ class PhysicsState:
         self._push()
         return self._world.raycast(origins, dirs, max_t, ignore)
 
+    def spherecast(self, origins, dirs, radius, max_t=None, ignore=None):
+        """First target per moving ball against the entities as they are now (World.spherecast): (body index or
+        RAY_MISS / RAY_GROUND, t, normal)."""
+        self._push()
+        return self._world.spherecast(origins, dirs, radius, max_t, ignore)
+
+    def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None):
+        """Every entity each query shape intersects, as they are now (World.overlap): (offsets, ascending ids)."""
+        self._push()
+        return self._world.overlap(shape_type, pos, rot, half_extent, ignore)
+
     def instance_matrices(self):  # what get_render_data feeds the renderer (physics.rs:61-69)
         self._push()
         return self._world.get_instance_matrices()

@@ -217,6 +217,75 @@ class World:
             args.append(C.c_void_p(x.data_ptr()))
         self._ck(self.lib.phys_raycast_device(self.h, n, *args))
 
+    def spherecast(self, origins, dirs, radius, max_t=None, ignore=None):
+        """First target a moving ball touches, per ball (phys_spherecast): origins / dirs (n, 3), radius scalar or (n,),
+        max_t (n,) or None (= +inf), ignore (n,) body ids or None. Returns (body u32[n], t f32[n], normal f32[n, 3]): t is
+        the distance the centre travelled, normal the target's outward normal at the contact (-dir from an overlap at t = 0);
+        a miss is (RAY_MISS, +inf, 0)."""
+        o = _f(origins).reshape(-1, 3)
+        d = _f(dirs).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError("origins and dirs differ in length")
+        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)))
+        mt = None if max_t is None else _f(max_t).reshape(-1)
+        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.uint32).reshape(-1)
+        for a in (mt, ig):
+            if a is not None and a.size != n:
+                raise ValueError("max_t / ignore do not match the ball count")
+        body = np.empty(n, np.uint32)
+        t = np.empty(n, np.float32)
+        normal = np.empty((n, 3), np.float32)
+        if n:
+            self._ck(self.lib.phys_spherecast(self.h, n, _p(o), _p(d), _p(rad), _p(mt), _p(ig, u32p), _p(body, u32p), _p(t),
+                                              _p(normal)))
+        return body, t, normal
+
+    def spherecast_device(self, origins, dirs, radius, body_out, t_out, normal_out=None, max_t=None, ignore=None):
+        """phys_spherecast_device on contiguous torch tensors of the world's device, as raycast_device; radius float32 (n,).
+        Only enqueues on the world's stream (device_view().stream)."""
+        n = int(origins.shape[0])
+        args = []
+        for name, x, cols in (("origins", origins, 3), ("dirs", dirs, 3), ("radius", radius, 1), ("max_t", max_t, 1),
+                              ("ignore", ignore, 1), ("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3)):
+            if x is None:
+                args.append(None)
+                continue
+            if not x.is_cuda or not x.is_contiguous() or x.numel() != n * cols or x.element_size() != 4:
+                raise ValueError(f"{name}: needs a contiguous 4-byte device tensor of {n} x {cols}")
+            args.append(C.c_void_p(x.data_ptr()))
+        self._ck(self.lib.phys_spherecast_device(self.h, n, *args))
+
+    def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None, cap=None):
+        """Every target each query shape intersects (phys_overlap): shape_type scalar or (n,) SHAPE_SPHERE / BOX / CAPSULE,
+        pos (n, 3), rot (n, 4) [i, j, k, w] or None (identity), half_extent (3,) or (n, 3) with the bodies' conventions,
+        ignore (n,) body ids or None. Returns (offsets u64[n + 1], ids u32[offsets[n]]): query i's ids, ascending, are
+        ids[offsets[i]:offsets[i + 1]] (bodies, then PHYS_STATIC_ID_BIT | k, then RAY_GROUND). The first call reserves
+        `cap` ids (default 8 per query) and, if they do not fit, the call is repeated once with the reported total."""
+        p = _f(pos).reshape(-1, 3)
+        n = p.shape[0]
+        if half_extent is None:
+            raise ValueError("half_extent is required")
+        st = np.ascontiguousarray(np.broadcast_to(np.asarray(shape_type, np.uint32), (n,)))
+        he = np.ascontiguousarray(np.broadcast_to(np.asarray(half_extent, np.float32).reshape(-1, 3), (n, 3)))
+        r = None if rot is None else _f(rot).reshape(-1, 4)
+        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.uint32).reshape(-1)
+        for a, k in ((r, 4), (ig, 1)):
+            if a is not None and a.size != n * k:
+                raise ValueError("rot / ignore do not match the query count")
+        offsets = np.zeros(n + 1, np.uint64)
+        cap = 8 * n + 64 if cap is None else int(cap)
+        for attempt in range(2):
+            ids = np.empty(max(cap, 1), np.uint32)
+            rc = self.lib.phys_overlap(self.h, n, _p(st, u32p), _p(p), _p(r), _p(he), _p(ig, u32p), cap, _p(offsets, _abi.u64p),
+                                       _p(ids, u32p))
+            if rc == _abi.PHYS_ERR_CAPACITY and attempt == 0:
+                cap = int(offsets[n])
+                continue
+            self._ck(rc)
+            break
+        return offsets, ids[:int(offsets[n])]
+
     def get_manifolds(self):
         n = C.c_uint64()
         self._ck(self.lib.phys_get_manifolds(self.h, None, None, None, None, 0, C.byref(n)))

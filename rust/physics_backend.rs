@@ -111,6 +111,51 @@ impl HipBackend {
         (0..n).map(|i| (if body[i] == ffi::PHYS_RAY_MISS { None } else { Some(body[i]) }, t[i], normal[i])).collect()
     }
 
+    /// First target a ball of `radius[i]` touches moving from `origins[i]` along `dirs[i]` (phys_spherecast): as `raycast`,
+    /// t being the distance the centre travelled and the normal the target's outward normal at the contact.
+    pub fn spherecast(&self, origins: &[[f32; 3]], dirs: &[[f32; 3]], radius: &[f32], max_t: Option<&[f32]>,
+                      ignore: Option<&[u32]>) -> Vec<(Option<u32>, f32, [f32; 3])> {
+        let n = origins.len();
+        assert!(dirs.len() == n && radius.len() == n);
+        assert!(max_t.map_or(true, |m| m.len() == n) && ignore.map_or(true, |g| g.len() == n));
+        let (mut body, mut t, mut normal) = (vec![0u32; n], vec![0f32; n], vec![[0f32; 3]; n]);
+        if n > 0 {
+            unsafe {
+                check(ffi::phys_spherecast(self.world, n as u64, origins.as_ptr() as *const f32, dirs.as_ptr() as *const f32,
+                                           radius.as_ptr(), max_t.map_or(std::ptr::null(), |m| m.as_ptr()),
+                                           ignore.map_or(std::ptr::null(), |g| g.as_ptr()), body.as_mut_ptr(), t.as_mut_ptr(),
+                                           normal.as_mut_ptr() as *mut f32));
+            }
+        }
+        (0..n).map(|i| (if body[i] == ffi::PHYS_RAY_MISS { None } else { Some(body[i]) }, t[i], normal[i])).collect()
+    }
+
+    /// Every target each query shape intersects (phys_overlap): per query the ascending ids (entity index,
+    /// ffi::PHYS_STATIC_ID_BIT | k, ffi::PHYS_RAY_GROUND). `rot` is optional (identity); retries once on capacity.
+    pub fn overlap(&self, shape_type: &[u32], pos: &[[f32; 3]], rot: Option<&[[f32; 4]]>, half_extent: &[[f32; 3]],
+                   ignore: Option<&[u32]>) -> Vec<Vec<u32>> {
+        let n = pos.len();
+        assert!(shape_type.len() == n && half_extent.len() == n);
+        assert!(rot.map_or(true, |r| r.len() == n) && ignore.map_or(true, |g| g.len() == n));
+        let mut offsets = vec![0u64; n + 1];
+        let mut ids = vec![0u32; 8 * n + 64];
+        for attempt in 0..2 {
+            let rc = unsafe {
+                ffi::phys_overlap(self.world, n as u64, shape_type.as_ptr(), pos.as_ptr() as *const f32,
+                                  rot.map_or(std::ptr::null(), |r| r.as_ptr() as *const f32), half_extent.as_ptr() as *const f32,
+                                  ignore.map_or(std::ptr::null(), |g| g.as_ptr()), ids.len() as u64, offsets.as_mut_ptr(),
+                                  ids.as_mut_ptr())
+            };
+            if rc == ffi::PHYS_ERR_CAPACITY && attempt == 0 {
+                ids.resize(offsets[n] as usize, 0);
+                continue;
+            }
+            check(rc);
+            break;
+        }
+        (0..n).map(|i| ids[offsets[i] as usize..offsets[i + 1] as usize].to_vec()).collect()
+    }
+
     /// PhysicsState::update (physics.rs:41-55). `dirty` = the caller touched entities/constraints since the
     /// last frame (lib.rs does at start-up only); when false the bodies stay resident on the GPU.
     pub fn update(&mut self, state: &mut PhysicsState, dt: &Duration, dirty: bool) {

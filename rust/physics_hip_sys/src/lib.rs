@@ -7,6 +7,7 @@ use std::os::raw::{c_char, c_void};
 pub const PHYS_ABI_VERSION: u32 = 2;
 pub const PHYS_OK: i32 = 0;
 pub const PHYS_ERR_SINGULAR_INERTIA: i32 = -4;
+pub const PHYS_ERR_CAPACITY: i32 = -5;
 pub const PHYS_ERR_NO_BODIES: i32 = -8;
 pub const PHYS_SHAPE_NONE: u32 = 0;
 pub const PHYS_SHAPE_SPHERE: u32 = 1;
@@ -143,6 +144,13 @@ extern "C" {
                         ignore_body: *const u32, body_out: *mut u32, t_out: *mut f32, normal_out: *mut f32) -> i32;
     pub fn phys_raycast_device(w: *mut phys_world, n_rays: u64, origin: *const f32, dir: *const f32, max_t: *const f32,
                                ignore_body: *const u32, body_out: *mut u32, t_out: *mut f32, normal_out: *mut f32) -> i32;
+    pub fn phys_spherecast(w: *mut phys_world, n: u64, origin: *const f32, dir: *const f32, radius: *const f32, max_t: *const f32,
+                           ignore_body: *const u32, body_out: *mut u32, t_out: *mut f32, normal_out: *mut f32) -> i32;
+    pub fn phys_spherecast_device(w: *mut phys_world, n: u64, origin: *const f32, dir: *const f32, radius: *const f32,
+                                  max_t: *const f32, ignore_body: *const u32, body_out: *mut u32, t_out: *mut f32,
+                                  normal_out: *mut f32) -> i32;
+    pub fn phys_overlap(w: *mut phys_world, n: u64, shape_type: *const u32, pos: *const f32, rot_ijkw: *const f32,
+                        half_extent: *const f32, ignore_body: *const u32, cap: u64, offsets_out: *mut u64, ids_out: *mut u32) -> i32;
     pub fn phys_set_static_bodies(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32, shape_type: *const u32,
                                   half_extent: *const f32) -> i32;
     pub fn phys_get_static_stats(w: *mut phys_world, n_static: *mut u64, n_static_pairs: *mut u64, n_static_manifolds: *mut u64) -> i32;
