@@ -331,6 +331,62 @@ int32_t phys_set_static_bodies(phys_world* w, uint64_t n, const float* pos /*3n*
                                const uint32_t* shape_type /*n*/, const float* half_extent /*3n*/);
 int32_t phys_get_static_stats(phys_world* w, uint64_t* n_static, uint64_t* n_static_pairs, uint64_t* n_static_manifolds);
 
+/* --- collision filters: what may touch what (new: the reference has none) ---
+ * Every body, static collider and the ground plane carries a filter: category (u16, the layers it belongs to), mask (u16,
+ * the layers it collides with) and group (i16). Defaults: category PHYS_FILTER_DEFAULT_CATEGORY, mask
+ * PHYS_FILTER_DEFAULT_MASK, group 0; the ground's group is always 0. Two of them A and B may form a contact manifold iff
+ *     A.group == B.group && A.group != 0 ?  A.group > 0                       (same positive group: always; negative: never)
+ *                                         :  (A.category & B.mask) != 0 && (B.category & A.mask) != 0
+ * so with the defaults every pair collides, as without filters. A rejected (body, body), (body, static) or (body, ground)
+ * pair is treated exactly like a pair whose shapes do not touch: no manifold, no colour, no warm-start record. Nothing else
+ * changes: phys_broadphase, n_pairs and the (body, static) pairs still report AABB candidates, PHYS_FLAG_BROADPHASE_ONLY
+ * worlds are unaffected, and the pair capacities are the same. Added without an ABI version change (no struct changed,
+ * PHYS_ABI_VERSION stays 2): a library that predates them lacks the symbols.
+ *   - phys_set_body_filters: n must equal n_bodies (owned); phys_set_static_filters: n must equal the static count. A NULL
+ *     array gives that field its default for every item. Filters take effect at the next update (updates already
+ *     enqueued keep the filters they were enqueued with).
+ *   - phys_set_bodies resets every body filter to the defaults, phys_set_static_bodies every static filter. The ground
+ *     filter lasts for the life of the world.
+ *   - changing filters does NOT make the world forget its colours or warm-start impulses: a pair that stops or starts
+ *     colliding is the same as a pair that separates or touches.
+ *   - phys_get_body_filters: the owned bodies' filters; any output may be NULL.
+ *   - sharded worlds: a ghost carries its owner's filter in the halo record, so a contact across a cut is filtered the
+ *     same way on both sides (the record's size is unchanged; a default filter encodes as zeros).
+ *   - cost: a world runs the narrow phase's filtered variant once any filter call was made since its reset (whatever the
+ *     values), and always when it has ghost slots; DESIGN.md section 13.
+ * The _filtered queries are the queries above with one more per-query mask: a body, static or ground target is reported
+ * iff (target.category & query_mask[i]) != 0 (groups play no part). query_mask NULL = no filtering: the same kernels and
+ * bits as the call without the suffix, and query_mask[i] = 0 reports nothing. Everything else - ignore_body, ghosts never
+ * reported, the tie rules, ascending unique overlap ids, the argument errors - is the unsuffixed call's. The unsuffixed
+ * calls ignore filters. */
+#define PHYS_FILTER_DEFAULT_CATEGORY 0x0001u
+#define PHYS_FILTER_DEFAULT_MASK 0xFFFFu
+int32_t phys_set_body_filters(phys_world* w, uint64_t n, const uint16_t* category /*n, NULL = default*/,
+                              const uint16_t* mask /*n, NULL = default*/, const int16_t* group /*n, NULL = 0*/);
+int32_t phys_get_body_filters(phys_world* w, uint16_t* category_out /*n_bodies, may be NULL*/, uint16_t* mask_out /*may be NULL*/,
+                              int16_t* group_out /*may be NULL*/);
+int32_t phys_set_static_filters(phys_world* w, uint64_t n, const uint16_t* category /*n, NULL = default*/,
+                                const uint16_t* mask /*n, NULL = default*/, const int16_t* group /*n, NULL = 0*/);
+int32_t phys_set_ground_filter(phys_world* w, uint16_t category, uint16_t mask);
+int32_t phys_raycast_filtered(phys_world* w, uint64_t n_rays, const float* origin /*3n*/, const float* dir /*3n*/,
+                              const float* max_t /*n, NULL = +inf*/, const uint32_t* ignore_body /*n, NULL = none*/,
+                              const uint16_t* query_mask /*n, NULL = no filtering*/, uint32_t* body_out /*n*/, float* t_out /*n*/,
+                              float* normal_out /*3n, may be NULL*/);
+int32_t phys_raycast_device_filtered(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
+                                     const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
+                                     float* normal_out);
+int32_t phys_spherecast_filtered(phys_world* w, uint64_t n, const float* origin /*3n*/, const float* dir /*3n*/,
+                                 const float* radius /*n*/, const float* max_t /*n, NULL = +inf*/,
+                                 const uint32_t* ignore_body /*n, NULL = none*/, const uint16_t* query_mask /*n, NULL = no filtering*/,
+                                 uint32_t* body_out /*n*/, float* t_out /*n*/, float* normal_out /*3n, may be NULL*/);
+int32_t phys_spherecast_device_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius,
+                                        const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask,
+                                        uint32_t* body_out, float* t_out, float* normal_out);
+int32_t phys_overlap_filtered(phys_world* w, uint64_t n, const uint32_t* shape_type /*n*/, const float* pos /*3n*/,
+                              const float* rot_ijkw /*4n, NULL = identity*/, const float* half_extent /*3n*/,
+                              const uint32_t* ignore_body /*n, NULL = none*/, const uint16_t* query_mask /*n, NULL = no filtering*/,
+                              uint64_t cap, uint64_t* offsets_out /*n + 1*/, uint32_t* ids_out /*cap*/);
+
 /* --- per-stage device timing (HIP events on the world's stream), for bench.py's roofline --- */
 #define PHYS_STAGE_STEP_FULL 0u     /* gravity + RigidBody::step, one kernel (no collisions) */
 #define PHYS_STAGE_VELOCITY_AABB 1u /* gravity + velocity half + AABB */

@@ -29,10 +29,15 @@ GROUND_ID = 0xFFFFFFFF
 RAY_MISS = 0xFFFFFFFE    # PHYS_RAY_MISS: no hit within max_t
 RAY_GROUND = 0xFFFFFFFF  # PHYS_RAY_GROUND: the ground plane
 STATIC_ID_BIT = 0x80000000  # PHYS_STATIC_ID_BIT: manifold body_b / ray body = STATIC_ID_BIT | k for static collider k
+# collision filters (include/physics_hip.h): category u16, mask u16, group i16; these are the defaults (group 0)
+FILTER_DEFAULT_CATEGORY = 0x0001
+FILTER_DEFAULT_MASK = 0xFFFF
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
+u16p = C.POINTER(C.c_uint16)
+i16p = C.POINTER(C.c_int16)
 
 
 class PhysConfig(C.Structure):
@@ -170,6 +175,17 @@ PROTOTYPES = {
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "phys_overlap": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p, f32p, u32p, C.c_uint64, u64p, u32p]),
     "phys_set_static_bodies": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, u32p, f32p]),
+    "phys_set_body_filters": (C.c_int32, [C.c_void_p, C.c_uint64, u16p, u16p, i16p]),
+    "phys_get_body_filters": (C.c_int32, [C.c_void_p, u16p, u16p, i16p]),
+    "phys_set_static_filters": (C.c_int32, [C.c_void_p, C.c_uint64, u16p, u16p, i16p]),
+    "phys_set_ground_filter": (C.c_int32, [C.c_void_p, C.c_uint16, C.c_uint16]),
+    "phys_raycast_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, u32p, u16p, u32p, f32p, f32p]),
+    "phys_raycast_device_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "phys_spherecast_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, u32p, u16p, u32p, f32p, f32p]),
+    "phys_spherecast_device_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "phys_overlap_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p, f32p, u32p, u16p, C.c_uint64, u64p, u32p]),
     "phys_get_static_stats": (C.c_int32, [C.c_void_p, u64p, u64p, u64p]),
     "phys_profile_enable": (C.c_int32, [C.c_void_p, C.c_int32]),
     "phys_profile_get": (C.c_int32, [C.c_void_p, C.POINTER(PhysProfile)]),

@@ -230,7 +230,8 @@ int32_t phys_destroy(phys_world* w) {
                               &w->man_prev, &w->cluster_slot, &w->cluster_body, &w->body_shared, &w->active_flag, &w->active_rank, &w->seg_count, &w->seg_start, &w->man_rank,
                               &w->row_src, &w->cross_pairs, &w->color_block_hist, &w->cg_cols,
                               &w->rc_header, &w->rc_count, &w->rc_start, &w->rc_tile_sum, &w->qr_count, &w->qr_ids,
-                              &w->st_cell_start, &w->st_cell_ids, &w->st_large, &w->st_count, &w->st_block, &w->st_pairs};
+                              &w->st_cell_start, &w->st_cell_ids, &w->st_large, &w->st_count, &w->st_block, &w->st_pairs,
+                              &w->filt, &w->st_filt};
     for (auto* b : ub) b->free();
     w->man_prio.free(); w->color_state.free(); w->bucket_count.free(); w->step_zero.free();
     w->d_constraints.free(); w->counters.free();
@@ -262,6 +263,7 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     PHYS_HIP_TRY(w->inv_inertia.resize(9 * nt)); PHYS_HIP_TRY(w->inv_inertia_diag.resize(4 * nt));
     PHYS_HIP_TRY(w->half_extent.resize(3 * nt)); PHYS_HIP_TRY(w->aabb.resize(6 * nt)); PHYS_HIP_TRY(w->shape.resize(nt));
     PHYS_HIP_TRY(w->global_id.resize(nt));
+    PHYS_HIP_TRY(w->filt.resize(2 * nt));
     if ((w->cfg.flags & PHYS_FLAG_COLLISIONS) && !(w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY)) PHYS_HIP_TRY(w->geo.resize(16 * nt));
     w->n = nt;
     w->n_owned = n;
@@ -273,12 +275,14 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     w->sorted_grid_valid = false;
     w->hint = StepHint();
     w->static_pairs_sized = false;  // static.hip: the next update measures its (body, static) pairs
+    w->body_filters_set = false;    // every body slot gets the default filter below
     for (int k = 0; k < phys_world::kSnapRing; ++k) w->snap_pending[k] = false;  // the stream was synchronised above
     if (n == 0) return PHYS_OK;
 
     // host staging with RigidBody::new defaults (rigid_body.rs:64-76); ghost slots: no shape, immovable
     std::vector<float> h_pos(3 * nt, 0.0f), h_rot(4 * nt), h_vel(8 * nt), h_inv(9 * nt, 0.0f), h_diag(4 * nt, 0.0f), h_he(3 * nt, 0.0f);
-    std::vector<uint32_t> h_shape(nt, PHYS_SHAPE_NONE), h_gid(nt, 0xFFFFFFFFu);
+    std::vector<uint32_t> h_shape(nt, PHYS_SHAPE_NONE), h_gid(nt, 0xFFFFFFFFu), h_filt(2 * nt, 0u);
+    for (uint64_t i = 0; i < nt; ++i) h_filt[2 * i] = kFilterDefaultWord;
     std::memcpy(h_pos.data(), pos, 12 * n);
     w->singular_inertia = false;
     w->all_diag_inertia = true;
@@ -327,6 +331,7 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     PHYS_HIP_TRY(hipMemcpyAsync(w->half_extent.p, h_he.data(), 12 * nt, hipMemcpyHostToDevice, s));
     PHYS_HIP_TRY(hipMemcpyAsync(w->shape.p, h_shape.data(), 4 * nt, hipMemcpyHostToDevice, s));
     PHYS_HIP_TRY(hipMemcpyAsync(w->global_id.p, h_gid.data(), 4 * nt, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->filt.p, h_filt.data(), 8 * nt, hipMemcpyHostToDevice, s));
     if (!w->all_diag_inertia) w->uniform_inertia = false;
     PHYS_HIP_TRY(hipStreamSynchronize(s));  // staging vectors die here
     if (w->cfg.flags & PHYS_FLAG_COLLISIONS) {
@@ -691,7 +696,64 @@ int32_t phys_set_static_bodies(phys_world* w, uint64_t n, const float* pos, cons
     w->ctab_valid = false;
     w->color_epoch = 0;
     w->static_pairs_seen = 0;
+    w->static_filters_set = false;  // the new set starts with the default filters (static_set)
     return static_set(w, n, pos, rot, shape_type, half_extent);
+}
+
+// ---- collision filters ----
+// {category | mask << 16, (u32)group} per item; a NULL array gives that field its default
+static void pack_filters(uint64_t n, const uint16_t* category, const uint16_t* mask, const int16_t* group, std::vector<uint32_t>& out) {
+    out.resize(2 * n);
+    for (uint64_t k = 0; k < n; ++k) {
+        const uint32_t c = category ? category[k] : PHYS_FILTER_DEFAULT_CATEGORY;
+        const uint32_t m = mask ? mask[k] : PHYS_FILTER_DEFAULT_MASK;
+        out[2 * k] = c | (m << 16);
+        out[2 * k + 1] = group ? (uint32_t)(int32_t)group[k] : 0u;
+    }
+}
+
+int32_t phys_set_body_filters(phys_world* w, uint64_t n, const uint16_t* category, const uint16_t* mask, const int16_t* group) {
+    ENTER(w);
+    if (n != w->n_owned) return fail(PHYS_ERR_INVALID_ARG, "phys_set_body_filters: n must equal the body count");
+    std::vector<uint32_t> h;
+    pack_filters(n, category, mask, group, h);
+    // ordered behind the updates already enqueued: they keep the filters they were enqueued with
+    if (n) PHYS_HIP_TRY(hipMemcpyAsync(w->filt.p, h.data(), 8 * n, hipMemcpyHostToDevice, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // the staging vector dies here
+    w->body_filters_set = true;
+    return PHYS_OK;
+}
+
+int32_t phys_get_body_filters(phys_world* w, uint16_t* category_out, uint16_t* mask_out, int16_t* group_out) {
+    ENTER(w);
+    const uint64_t n = w->n_owned;
+    std::vector<uint32_t> h(2 * n);
+    if (n) PHYS_HIP_TRY(hipMemcpyAsync(h.data(), w->filt.p, 8 * n, hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    for (uint64_t k = 0; k < n; ++k) {
+        if (category_out) category_out[k] = (uint16_t)(h[2 * k] & 0xFFFFu);
+        if (mask_out) mask_out[k] = (uint16_t)(h[2 * k] >> 16);
+        if (group_out) group_out[k] = (int16_t)(uint16_t)h[2 * k + 1];
+    }
+    return PHYS_OK;
+}
+
+int32_t phys_set_static_filters(phys_world* w, uint64_t n, const uint16_t* category, const uint16_t* mask, const int16_t* group) {
+    ENTER(w);
+    if (n != w->n_static) return fail(PHYS_ERR_INVALID_ARG, "phys_set_static_filters: n must equal the static collider count");
+    std::vector<uint32_t> h;
+    pack_filters(n, category, mask, group, h);
+    if (n) PHYS_HIP_TRY(hipMemcpyAsync(w->st_filt.p, h.data(), 8 * n, hipMemcpyHostToDevice, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    w->static_filters_set = true;
+    return PHYS_OK;
+}
+
+int32_t phys_set_ground_filter(phys_world* w, uint16_t category, uint16_t mask) {
+    ENTER(w);
+    w->ground_filt = (uint32_t)category | ((uint32_t)mask << 16);  // read by the launches of the next update
+    w->ground_filter_set = true;
+    return PHYS_OK;
 }
 
 int32_t phys_get_static_stats(phys_world* w, uint64_t* n_static, uint64_t* n_static_pairs, uint64_t* n_static_manifolds) {
@@ -747,14 +809,15 @@ static int32_t raycast_args(uint64_t n_rays, const float* origin, const float* d
     return PHYS_OK;
 }
 
-int32_t phys_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
-                     const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
+// host arrays; query_mask NULL: the plain call
+static int32_t raycast_host(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
+                            const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out) {
     ENTER(w);
     int32_t rc = raycast_args(n_rays, origin, dir, body_out, t_out); if (rc) return rc;
     if (n_rays == 0) return PHYS_OK;
-    // staging: in = origin 3n | dir 3n | max_t n | ignore n, out = t n | body n | normal 3n (all 4-byte words)
+    // staging: in = origin 3n | dir 3n | max_t n | ignore n [| query mask n u16], out = t n | body n | normal 3n (4-byte words)
     const size_t n = (size_t)n_rays;
-    PHYS_HIP_TRY(w->rc_in.resize(8 * n));
+    PHYS_HIP_TRY(w->rc_in.resize(query_mask ? 8 * n + (n + 1) / 2 : 8 * n));
     PHYS_HIP_TRY(w->rc_out.resize(5 * n));
     hipStream_t s = w->stream;
     float* d_origin = w->rc_in.p;
@@ -768,12 +831,25 @@ int32_t phys_raycast(phys_world* w, uint64_t n_rays, const float* origin, const 
     PHYS_HIP_TRY(hipMemcpyAsync(d_dir, dir, 12 * n, hipMemcpyHostToDevice, s));
     if (d_max_t) PHYS_HIP_TRY(hipMemcpyAsync(d_max_t, max_t, 4 * n, hipMemcpyHostToDevice, s));
     if (d_ignore) PHYS_HIP_TRY(hipMemcpyAsync(d_ignore, ignore_body, 4 * n, hipMemcpyHostToDevice, s));
-    rc = launch_raycast(w, n_rays, d_origin, d_dir, d_max_t, d_ignore, d_body, d_t, d_normal); if (rc) return rc;
+    uint16_t* d_qmask = query_mask ? reinterpret_cast<uint16_t*>(d_origin + 8 * n) : nullptr;
+    if (d_qmask) PHYS_HIP_TRY(hipMemcpyAsync(d_qmask, query_mask, 2 * n, hipMemcpyHostToDevice, s));
+    rc = launch_raycast(w, n_rays, d_origin, d_dir, d_max_t, d_ignore, d_body, d_t, d_normal, d_qmask); if (rc) return rc;
     rc = d2h(w, body_out, d_body, 4 * n); if (rc) return rc;
     rc = d2h(w, t_out, d_t, 4 * n); if (rc) return rc;
     if (normal_out) { rc = d2h(w, normal_out, d_normal, 12 * n); if (rc) return rc; }
     PHYS_HIP_TRY(hipStreamSynchronize(s));
     return PHYS_OK;
+}
+
+int32_t phys_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
+                     const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
+    return raycast_host(w, n_rays, origin, dir, max_t, ignore_body, nullptr, body_out, t_out, normal_out);
+}
+
+int32_t phys_raycast_filtered(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
+                              const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
+                              float* normal_out) {
+    return raycast_host(w, n_rays, origin, dir, max_t, ignore_body, query_mask, body_out, t_out, normal_out);
 }
 
 int32_t phys_raycast_device(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
@@ -784,6 +860,15 @@ int32_t phys_raycast_device(phys_world* w, uint64_t n_rays, const float* origin,
     return launch_raycast(w, n_rays, origin, dir, max_t, ignore_body, body_out, t_out, normal_out);
 }
 
+int32_t phys_raycast_device_filtered(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
+                                     const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
+                                     float* normal_out) {
+    ENTER(w);
+    int32_t rc = raycast_args(n_rays, origin, dir, body_out, t_out); if (rc) return rc;
+    if (n_rays == 0) return PHYS_OK;
+    return launch_raycast(w, n_rays, origin, dir, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
+}
+
 static int32_t spherecast_args(uint64_t n, const float* origin, const float* dir, const float* radius, const uint32_t* body_out,
                                const float* t_out) {
     if (n >= (1ull << 31)) return fail(PHYS_ERR_INVALID_ARG, "phys_spherecast: n must be below 2^31");
@@ -792,14 +877,15 @@ static int32_t spherecast_args(uint64_t n, const float* origin, const float* dir
     return PHYS_OK;
 }
 
-int32_t phys_spherecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
-                        const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
+static int32_t spherecast_host(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
+                               const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
+                               float* normal_out) {
     ENTER(w);
     int32_t rc = spherecast_args(n, origin, dir, radius, body_out, t_out); if (rc) return rc;
     if (n == 0) return PHYS_OK;
-    // staging: in = origin 3n | dir 3n | radius n | max_t n | ignore n, out = t n | body n | normal 3n (all 4-byte words)
+    // staging: in = origin 3n | dir 3n | radius n | max_t n | ignore n [| query mask n u16], out = t n | body n | normal 3n
     const size_t m = (size_t)n;
-    PHYS_HIP_TRY(w->qr_in.resize(9 * m));
+    PHYS_HIP_TRY(w->qr_in.resize(query_mask ? 9 * m + (m + 1) / 2 : 9 * m));
     PHYS_HIP_TRY(w->rc_out.resize(5 * m));
     hipStream_t s = w->stream;
     float* d_origin = w->qr_in.p;
@@ -815,12 +901,25 @@ int32_t phys_spherecast(phys_world* w, uint64_t n, const float* origin, const fl
     PHYS_HIP_TRY(hipMemcpyAsync(d_radius, radius, 4 * m, hipMemcpyHostToDevice, s));
     if (d_max_t) PHYS_HIP_TRY(hipMemcpyAsync(d_max_t, max_t, 4 * m, hipMemcpyHostToDevice, s));
     if (d_ignore) PHYS_HIP_TRY(hipMemcpyAsync(d_ignore, ignore_body, 4 * m, hipMemcpyHostToDevice, s));
-    rc = launch_spherecast(w, n, d_origin, d_dir, d_radius, d_max_t, d_ignore, d_body, d_t, d_normal); if (rc) return rc;
+    uint16_t* d_qmask = query_mask ? reinterpret_cast<uint16_t*>(d_origin + 9 * m) : nullptr;
+    if (d_qmask) PHYS_HIP_TRY(hipMemcpyAsync(d_qmask, query_mask, 2 * m, hipMemcpyHostToDevice, s));
+    rc = launch_spherecast(w, n, d_origin, d_dir, d_radius, d_max_t, d_ignore, d_body, d_t, d_normal, d_qmask); if (rc) return rc;
     rc = d2h(w, body_out, d_body, 4 * m); if (rc) return rc;
     rc = d2h(w, t_out, d_t, 4 * m); if (rc) return rc;
     if (normal_out) { rc = d2h(w, normal_out, d_normal, 12 * m); if (rc) return rc; }
     PHYS_HIP_TRY(hipStreamSynchronize(s));
     return PHYS_OK;
+}
+
+int32_t phys_spherecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
+                        const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
+    return spherecast_host(w, n, origin, dir, radius, max_t, ignore_body, nullptr, body_out, t_out, normal_out);
+}
+
+int32_t phys_spherecast_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius,
+                                 const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out,
+                                 float* t_out, float* normal_out) {
+    return spherecast_host(w, n, origin, dir, radius, max_t, ignore_body, query_mask, body_out, t_out, normal_out);
 }
 
 int32_t phys_spherecast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
@@ -831,8 +930,18 @@ int32_t phys_spherecast_device(phys_world* w, uint64_t n, const float* origin, c
     return launch_spherecast(w, n, origin, dir, radius, max_t, ignore_body, body_out, t_out, normal_out);
 }
 
-int32_t phys_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,
-                     const float* half_extent, const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out) {
+int32_t phys_spherecast_device_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius,
+                                        const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask,
+                                        uint32_t* body_out, float* t_out, float* normal_out) {
+    ENTER(w);
+    int32_t rc = spherecast_args(n, origin, dir, radius, body_out, t_out); if (rc) return rc;
+    if (n == 0) return PHYS_OK;
+    return launch_spherecast(w, n, origin, dir, radius, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
+}
+
+static int32_t overlap_host(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,
+                            const float* half_extent, const uint32_t* ignore_body, const uint16_t* query_mask, uint64_t cap,
+                            uint64_t* offsets_out, uint32_t* ids_out) {
     ENTER(w);
     if (n >= (1ull << 31)) return fail(PHYS_ERR_INVALID_ARG, "phys_overlap: n must be below 2^31");
     if (!offsets_out) return fail(PHYS_ERR_INVALID_ARG, "phys_overlap: null offsets_out");
@@ -840,9 +949,9 @@ int32_t phys_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, cons
     if (cap && !ids_out) return fail(PHYS_ERR_INVALID_ARG, "phys_overlap: null ids_out with cap > 0");
     offsets_out[0] = 0;
     if (n == 0) return PHYS_OK;
-    // staging: type n | pos 3n | half extent 3n | ignore n | rot 4n (rot last and 16-byte aligned: read as float4)
+    // staging: type n | pos 3n | half extent 3n | ignore n | rot 4n (rot 16-byte aligned: read as float4) [| query mask n u16]
     const size_t m = (size_t)n;
-    PHYS_HIP_TRY(w->qr_in.resize(8 * m + 4 * m + 4));
+    PHYS_HIP_TRY(w->qr_in.resize(query_mask ? 8 * m + 4 * m + 4 + (m + 1) / 2 : 8 * m + 4 * m + 4));
     hipStream_t s = w->stream;
     uint32_t* d_type = reinterpret_cast<uint32_t*>(w->qr_in.p);
     float* d_pos = w->qr_in.p + m;
@@ -854,7 +963,20 @@ int32_t phys_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, cons
     PHYS_HIP_TRY(hipMemcpyAsync(d_he, half_extent, 12 * m, hipMemcpyHostToDevice, s));
     if (d_ignore) PHYS_HIP_TRY(hipMemcpyAsync(d_ignore, ignore_body, 4 * m, hipMemcpyHostToDevice, s));
     if (d_rot) PHYS_HIP_TRY(hipMemcpyAsync(d_rot, rot_ijkw, 16 * m, hipMemcpyHostToDevice, s));
-    return launch_overlap(w, n, d_type, d_pos, d_rot, d_he, d_ignore, cap, offsets_out, ids_out);
+    uint16_t* d_qmask = query_mask ? reinterpret_cast<uint16_t*>(w->qr_in.p + 8 * m + 4 * m + 4) : nullptr;
+    if (d_qmask) PHYS_HIP_TRY(hipMemcpyAsync(d_qmask, query_mask, 2 * m, hipMemcpyHostToDevice, s));
+    return launch_overlap(w, n, d_type, d_pos, d_rot, d_he, d_ignore, cap, offsets_out, ids_out, d_qmask);
+}
+
+int32_t phys_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,
+                     const float* half_extent, const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out) {
+    return overlap_host(w, n, shape_type, pos, rot_ijkw, half_extent, ignore_body, nullptr, cap, offsets_out, ids_out);
+}
+
+int32_t phys_overlap_filtered(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,
+                              const float* half_extent, const uint32_t* ignore_body, const uint16_t* query_mask, uint64_t cap,
+                              uint64_t* offsets_out, uint32_t* ids_out) {
+    return overlap_host(w, n, shape_type, pos, rot_ijkw, half_extent, ignore_body, query_mask, cap, offsets_out, ids_out);
 }
 
 int32_t phys_set_global_ids(phys_world* w, const uint32_t* global_ids) {

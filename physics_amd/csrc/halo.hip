@@ -177,7 +177,8 @@ __global__ __launch_bounds__(256) void k_halo_pairs(uint32_t n_remote, uint32_t 
 // Ghost bodies (SURVEY rows E + N4): the full state of boundary bodies crosses the cut planes, and a rank sees its
 // neighbours' boundary bodies as kinematic bodies in slots [n_owned, n_owned + max_ghosts) of its own arrays, so the
 // ordinary pipeline collides and solves against them. 96-byte record = six float4:
-//   {pos.xyz, rot.i} {rot.jkw, lin.x} {lin.yz, ang.xy} {ang.z, half.xyz} {shape, global id, 0, 0} {0, 0, 0, 0}
+//   {pos.xyz, rot.i} {rot.jkw, lin.x} {lin.yz, ang.xy} {ang.z, half.xyz} {shape, global id, inverse mass, full-inertia flag
+//   (bit 0) | filter group << 16} {inverse inertia diagonal, (filter category | mask << 16) ^ 0xFFFF0001}
 // Both compactions (boundary bodies -> records, gathered records -> ghost slots) are ORDERED: a count per workgroup,
 // then every workgroup sums the counts in front of it and places its items at ballot-prefix offsets. No atomics, so
 // the record order and the ghost slot of every remote body are functions of the data alone and a sharded run repeats
@@ -241,7 +242,8 @@ __global__ __launch_bounds__(256) void k_halo_pack_bodies(uint32_t n_owned, cons
                                                           const float* __restrict__ half_extent,
                                                           const uint32_t* __restrict__ shape,
                                                           const uint32_t* __restrict__ global_id,
-                                                          const float* __restrict__ inv_inertia /* 9 per body */, float x_lo, float x_hi,
+                                                          const float* __restrict__ inv_inertia /* 9 per body */,
+                                                          const uint2* __restrict__ filt, float x_lo, float x_hi,
                                                           float reach, const uint32_t* __restrict__ block_counts,
                                                           BodyRecord* __restrict__ out, uint32_t cap, StepCounters* ctr) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -262,17 +264,21 @@ __global__ __launch_bounds__(256) void k_halo_pack_bodies(uint32_t n_owned, cons
     // inertia fits the record; a full tensor is flagged and that body crosses as a kinematic one, as in round 2.
     const float* I = inv_inertia + 9 * (size_t)i;
     const bool full = I[1] != 0.0f || I[2] != 0.0f || I[3] != 0.0f || I[5] != 0.0f || I[6] != 0.0f || I[7] != 0.0f;
-    r.q[4] = make_float4(__uint_as_float(shape[i]), __uint_as_float(global_id[i]), bv.inv_mass, __uint_as_float(full ? 1u : 0u));
-    r.q[5] = make_float4(I[0], I[4], I[8], 0.0f);
+    // the collision filter in the record's spare room, so that the default filter encodes as zeros:
+    // the group in bits 16-31 of q[4].w beside the full-inertia flag (bit 0), category | mask << 16 xor the default in q[5].w
+    const uint2 f = filt[i];
+    r.q[4] = make_float4(__uint_as_float(shape[i]), __uint_as_float(global_id[i]), bv.inv_mass,
+                         __uint_as_float((full ? 1u : 0u) | (f.y << 16)));
+    r.q[5] = make_float4(I[0], I[4], I[8], __uint_as_float(f.x ^ kFilterDefaultWord));
 #pragma unroll
     for (int k = 0; k < 6; ++k) out[slot].q[k] = r.q[k];
 }
 
 // every ghost slot back to "nobody" before the records of this step are placed (shape NONE takes part in nothing)
 __global__ __launch_bounds__(256) void k_ghost_clear(uint32_t n_owned, uint32_t n_total, uint32_t* __restrict__ shape,
-                                                     uint32_t* __restrict__ global_id, StepCounters* ctr) {
+                                                     uint32_t* __restrict__ global_id, uint2* __restrict__ filt, StepCounters* ctr) {
     const uint32_t i = n_owned + blockIdx.x * 256u + threadIdx.x;
-    if (i < n_total) { shape[i] = PHYS_SPEC_SHAPE_NONE; global_id[i] = 0xFFFFFFFFu; }
+    if (i < n_total) { shape[i] = PHYS_SPEC_SHAPE_NONE; global_id[i] = 0xFFFFFFFFu; filt[i] = make_uint2(kFilterDefaultWord, 0u); }
     if (blockIdx.x == 0 && threadIdx.x == 0) ctr->n_ghosts = 0;
 }
 
@@ -283,7 +289,7 @@ __global__ __launch_bounds__(256) void k_halo_unpack(uint32_t n_records, uint32_
                                                      float* __restrict__ vel, float* __restrict__ half_extent,
                                                      uint32_t* __restrict__ shape, uint32_t* __restrict__ global_id,
                                                      float* __restrict__ inv_inertia, float* __restrict__ inv_inertia_diag,
-                                                     StepCounters* ctr) {
+                                                     uint2* __restrict__ filt, StepCounters* ctr) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     const bool take = ghost_record(k, n_records, skip_first, skip_count, rec, x_lo, x_hi, reach);
     const uint32_t slot = ordered_slot(take, block_counts, &ctr->n_ghosts);
@@ -301,7 +307,7 @@ __global__ __launch_bounds__(256) void k_halo_unpack(uint32_t n_records, uint32_
     // contact it is - on both sides of the plane alike, each side keeping its own body's half of the outcome. Its state
     // here is forgotten when the next exchange brings the owner's. A body with a full inertia tensor (flagged by the
     // sender: the record holds a diagonal) stays kinematic: inverse mass and inertia 0, F / m = 0.
-    const bool kinematic = __float_as_uint(q[4].w) != 0u || !(q[4].z > 0.0f);
+    const bool kinematic = (__float_as_uint(q[4].w) & 1u) != 0u || !(q[4].z > 0.0f);
     BodyVel bv;
     bv.v = v3_make(q[1].w, q[2].x, q[2].y); bv.inv_mass = kinematic ? 0.0f : q[4].z;
     bv.w = v3_make(q[2].z, q[2].w, q[3].x); bv.mass = kinematic ? __uint_as_float(0x7F800000u) : 1.0f / q[4].z;
@@ -313,6 +319,8 @@ __global__ __launch_bounds__(256) void k_halo_unpack(uint32_t n_records, uint32_
     st3(half_extent, i, v3_make(q[3].y, q[3].z, q[3].w));
     shape[i] = __float_as_uint(q[4].x);
     global_id[i] = __float_as_uint(q[4].y);
+    // the sender's filter: a contact across the cut is filtered the same way on both sides
+    filt[i] = make_uint2(__float_as_uint(q[5].w) ^ kFilterDefaultWord, (uint32_t)(int32_t)(int16_t)(__float_as_uint(q[4].w) >> 16));
 }
 
 static int32_t halo_counts_room(phys_world* w, uint64_t items) {
@@ -342,7 +350,8 @@ int32_t halo_pack_bodies_faces(phys_world* w, void* dev_out, uint64_t cap, float
         hipLaunchKernelGGL(k_halo_count<0>, g, b, 0, w->stream, n, n, w->pos.p, w->shape.p, (const BodyRecord*)nullptr, 0u, 0u,
                            x_lo, x_hi, w->slab_reach, w->halo_block_counts.p);
         hipLaunchKernelGGL(k_halo_pack_bodies, g, b, 0, w->stream, n, w->pos.p, w->rot.p, w->vel.p, w->half_extent.p, w->shape.p,
-                           w->global_id.p, w->inv_inertia.p, x_lo, x_hi, w->slab_reach, w->halo_block_counts.p, (BodyRecord*)dev_out,
+                           w->global_id.p, w->inv_inertia.p, reinterpret_cast<const uint2*>(w->filt.p), x_lo, x_hi, w->slab_reach,
+                           w->halo_block_counts.p, (BodyRecord*)dev_out,
                            (uint32_t)cap, w->counters.p);
     }
     PHYS_HIP_TRY(hipGetLastError());
@@ -359,7 +368,7 @@ int32_t halo_unpack_ghosts(phys_world* w, const void* dev_records, uint64_t n_re
     PHYS_PROF(w, PHYS_STAGE_MISC);
     const uint32_t G = (uint32_t)w->max_ghosts, n_owned = (uint32_t)w->n_owned;
     hipLaunchKernelGGL(k_ghost_clear, dim3((G + 255) / 256), dim3(256), 0, w->stream, n_owned, (uint32_t)w->n, w->shape.p,
-                       w->global_id.p, w->counters.p);
+                       w->global_id.p, reinterpret_cast<uint2*>(w->filt.p), w->counters.p);
     if (n_records) {
         const dim3 g((unsigned)((n_records + 255) / 256)), b(256);
         hipLaunchKernelGGL(k_halo_count<1>, g, b, 0, w->stream, (uint32_t)n_records, n_owned, (const float*)nullptr,
@@ -368,7 +377,7 @@ int32_t halo_unpack_ghosts(phys_world* w, const void* dev_records, uint64_t n_re
         hipLaunchKernelGGL(k_halo_unpack, g, b, 0, w->stream, (uint32_t)n_records, (uint32_t)skip_first, (uint32_t)skip_count,
                            (const BodyRecord*)dev_records, w->slab_lo, w->slab_hi, w->slab_reach, w->halo_block_counts.p, n_owned, G,
                            w->pos.p, w->rot.p, w->vel.p, w->half_extent.p, w->shape.p, w->global_id.p, w->inv_inertia.p,
-                           w->inv_inertia_diag.p, w->counters.p);
+                           w->inv_inertia_diag.p, reinterpret_cast<uint2*>(w->filt.p), w->counters.p);
     }
     PHYS_HIP_TRY(hipGetLastError());
     w->aabbs_valid = false;

@@ -140,6 +140,34 @@ __device__ __forceinline__ void color_table_insert(const ColorTableJob& job, uin
     }
 }
 
+// ---- collision filters -------------------------------------------------------------------------
+// A filter is {category | mask << 16, (uint32_t)(int32_t)group}: one 8-byte load per body or static. The defaults
+// (category 0x0001, mask 0xFFFF, group 0) let everything collide. Two filters collide unless the rule says otherwise:
+// the same nonzero group decides by its sign, anything else needs each category in the other's mask.
+constexpr uint32_t kFilterDefaultWord = 0xFFFF0001u;  // category 0x0001 | mask 0xFFFF << 16
+__host__ __device__ __forceinline__ bool filter_pass(uint2 fa, uint2 fb) {
+    if (fa.y == fb.y && fa.y != 0u) return (int32_t)fa.y > 0;
+    return (fa.x & (fb.x >> 16)) != 0u && (fb.x & (fa.x >> 16)) != 0u;
+}
+// the narrow phase's filters (k_narrowphase<..., kFilters = true>)
+struct NpFilters {
+    const uint2* body;  // per body slot
+    const uint2* st;    // per static collider (null without statics)
+    uint2 ground;       // {category | mask << 16, 0}
+};
+// a query's filters (the _filtered query calls): a target is seen iff its category meets the query's mask
+struct QueryFilters {
+    const uint16_t* query_mask;  // one per query
+    const uint2* body;           // per owned body
+    const uint2* st;             // per static collider
+    uint32_t ground;             // the ground's category
+};
+// the one filter argument of a filtered kernel instance. The filter arguments travel as a parameter pack that is empty in
+// the unfiltered instance, so that instance keeps the kernel arguments - and with them the offsets of the hidden
+// arguments it reads - and compiles to the instructions it had before filters.
+template <typename T>
+__device__ __forceinline__ T filter_arg(T f) { return f; }
+
 // ---- uniform grid of the broad phase: cell -> bucket -----------------------------------------------------------------
 // The table has 2^bits buckets, bits = bx + by + bz split over the axes in proportion to the scene's extent (a tower 16
 // cells wide and 980 high gets x 4, y 10, z 5 instead of 7 + 7 + 7: with equal bits its 128-cell axis wrapped 7.6 times
@@ -253,16 +281,19 @@ void static_narrow_args(const phys_world* w, uint64_t* cap, const uint32_t** pai
 
 // raycast.hip: builds the query's grid from the current poses and traces the rays (device pointers), all on w->stream
 int32_t launch_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
-                       const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out);
+                       const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out,
+                       const uint16_t* query_mask = nullptr /* device, n_rays; null: no filtering */);
 // ... the same walk for balls of radius[i] (the grid grown by the largest valid radius)
 int32_t launch_spherecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
-                          const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out);
+                          const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out,
+                          const uint16_t* query_mask = nullptr);
 // the query grid alone (rc_header, rc_start, rc_records), every body AABB grown by the largest valid value of the device
 // array grow_radius (null: not grown); *bits = log2 of the bucket table
 int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_radius, uint32_t* bits);
 // query.hip: overlap queries on staged device arrays; writes the host offsets (n + 1) and, when they fit in cap, the ids
 int32_t launch_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot, const float* half_extent,
-                       const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out);
+                       const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out,
+                       const uint16_t* query_mask = nullptr /* device, n; null: no filtering */);
 
 int32_t halo_pack_bodies(phys_world* w, void* dev_out, uint64_t cap);
 int32_t halo_pack_bodies_faces(phys_world* w, void* dev_out, uint64_t cap, float x_lo, float x_hi);

@@ -35,8 +35,10 @@ __device__ __forceinline__ geom_t load_geom(uint32_t i, const float* __restrict_
 // kNpThreads: 128 for small scenes (latency-bound: more workgroups in flight, the LDS slice of the clipper
 // halves), 512 for everything else (launch_narrowphase). kCapsules: the full collide_pair / collide_ground of collide.h;
 // without it only their sphere / box part is compiled (a world without capsules keeps the registers - and the resident
-// waves - the kernel had before capsules: DESIGN.md section 11)
-template <int kNpThreads, int kNpItems, bool kStatics, bool kCapsules>
+// waves - the kernel had before capsules: DESIGN.md section 11). kFilters: every work item is first tested against the
+// collision filters of its two sides (one NpFilters argument, the pack `filt`); an item they reject
+// is an item whose shapes do not touch. Without it the pack is empty and the kernel is the one it was before filters.
+template <int kNpThreads, int kNpItems, bool kStatics, bool kCapsules, bool kFilters, typename... Filt>
 __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
     uint32_t n_ground /* bodies tested against the plane (0 = no ground) */, uint32_t n_owned /* pairs whose FIRST body is at
     or beyond this index are skipped (= all body slots: the ghosts of a sharded world collide like everybody else) */,
@@ -54,7 +56,11 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
     float* __restrict__ man_imp /* ... and this update's impulse records, zeroed here (a solve that never runs leaves zeros) */,
     StepCounters* __restrict__ ctr,
     uint64_t max_static_pairs /* kStatics: (body, static) pairs of static.hip, the third kind of work item */,
-    const uint32_t* __restrict__ static_pairs, const float* __restrict__ static_geo /* 16 floats per static, the layout of geo */) {
+    const uint32_t* __restrict__ static_pairs, const float* __restrict__ static_geo /* 16 floats per static, the layout of geo */,
+    Filt... filt /* kFilters: one NpFilters */) {
+    static_assert(sizeof...(Filt) == (kFilters ? 1u : 0u), "one NpFilters argument exactly in the filtered instance");
+    NpFilters flt{};
+    if constexpr (kFilters) flt = filter_arg(filt...);
     // per-wave totals of a trip, in two sets used alternately: a wave may start the next trip (and post its totals) while
     // another still reads this trip's to place its manifolds - there is no barrier at the end of a trip any more
     __shared__ uint32_t wtot[2][4][kNpThreads / 64];
@@ -108,6 +114,9 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
             bool have_early = false;
             if (idx < n_ground) {
                 a = (uint32_t)idx;
+                if (kFilters && !filter_pass(flt.body[a], flt.ground)) {
+                    // filtered out: no manifold, like a body clear of the plane
+                } else {
                 // the fattened AABB of this step (k_step_velocity_aabb; lo.y = lowest corner - margin) rules most bodies out
                 // without their orientation being read or a corner being made: a million-cube drop has 1 % of its bodies on
                 // the plane. Conservative: a body is kept unless its AABB clears ground + margin by more than rounding.
@@ -120,13 +129,15 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
                         else collide_ground_sphere_box(&ga, ground, margin, &m, ws);
                     }
                 }
+                }
             } else if (idx < total) {
                 // a candidate pair of two bodies, or (kStatics, behind them) a body and static collider k: B = the static
                 const bool body_pair = !kStatics || idx < n_body_items;
                 const uint2 pr = body_pair ? reinterpret_cast<const uint2*>(pairs)[idx - n_ground]
                                            : reinterpret_cast<const uint2*>(static_pairs)[idx - n_body_items];
                 a = pr.x; b = body_pair ? pr.y : (PHYS_STATIC_ID_BIT | pr.y);
-                if (a < n_owned) {
+                // kFilters: the two filters before anything else of the pair is read (a rejected pair costs two 8-byte loads)
+                if (a < n_owned && (!kFilters || filter_pass(flt.body[a], body_pair ? flt.body[pr.y] : flt.st[pr.y]))) {
                     // the colour-table entry this pair would keep its colour from (a random 16-byte read): asked for NOW, so
                     // that it travels while the shapes are fetched and tested instead of being one more dependent round trip
                     // behind the emission below (nearly every candidate pair of a resting pile becomes a manifold)
@@ -815,17 +826,17 @@ void launch_narrowphase(phys_world* w) {
         std::swap(w->man_imp.p, w->man_imp_prev.p);
     }
     PHYS_PROF(w, PHYS_STAGE_NARROW);
-#define PHYS_NP_LAUNCH(T, S, CAP)                                                                                       \
+#define PHYS_NP_LAUNCH(T, S, CAP, FLT, ...)                                                                             \
     do {                                                                                                               \
         uint64_t blocks = (work + T - 1) / T;                                                                          \
         if (blocks > 256 * 16) blocks = 256 * 16;                                                                      \
-        hipLaunchKernelGGL((k_narrowphase<T, 1, S, CAP>), dim3((unsigned)blocks), dim3(T), 0, w->stream, n_ground, n_owned, w->pairs.p, \
+        hipLaunchKernelGGL((k_narrowphase<T, 1, S, CAP, FLT>), dim3((unsigned)blocks), dim3(T), 0, w->stream, n_ground, n_owned, w->pairs.p, \
                            w->max_pairs, w->geo.p, w->cfg.contact_margin, \
                            w->cfg.ground_height, w->max_manifolds, w->man_a.p, w->man_b.p,                             \
                            w->man_color.p, w->man_geo.p, w->man_prio.p, w->color_state.p,                              \
                            w->color_state.p + n, reinterpret_cast<ulonglong2*>(w->ctab.p), cache_mask, early_probe, stamp, \
                            w->unc_list.p, w->warm ? w->man_prev.p : nullptr, w->man_imp.p, w->counters.p,              \
-                           st_cap, st_pairs, st_geo);                                                                  \
+                           st_cap, st_pairs, st_geo, ##__VA_ARGS__);                                                   \
     } while (0)
     // 128 threads only while the whole stage is a few workgroups (C2: 10k manifolds); measured at 230k manifolds (C3):
     // 0.175 ms with 128 threads, 0.133 with 256; at 2.9M (C5): 0.86 vs 0.55 (round 2)
@@ -844,21 +855,32 @@ void launch_narrowphase(phys_world* w) {
     // Capsules: the capsule variant wherever one can meet the narrow phase - an owned body (phys_set_bodies), a static in
     // use, or any ghost slot: ghosts arrive on the device with the shapes of another rank, which the host never sees
     const bool capsules = w->body_capsules || (st_pairs && w->static_capsules) || w->max_ghosts > 0;
-    if (capsules) {
-        if (st_pairs) {
-            if (threads == 128) PHYS_NP_LAUNCH(128, true, true);
-            else PHYS_NP_LAUNCH(512, true, true);
+    // Filters: the filtered variant once any filter was set since its reset (whatever the values), and
+    // in every world with ghost slots: their filters arrive with the halo records, which the host never sees
+    const bool filters = w->body_filters_set || (st_pairs && w->static_filters_set) || (n_ground && w->ground_filter_set) ||
+                         w->max_ghosts > 0;
+    NpFilters flt{};
+    flt.body = reinterpret_cast<const uint2*>(w->filt.p);
+    flt.st = st_pairs ? reinterpret_cast<const uint2*>(w->st_filt.p) : nullptr;
+    flt.ground = make_uint2(w->ground_filt, 0u);
+    // (the filtered instance takes `flt` as one more argument; the unfiltered one is launched exactly as before filters)
+#define PHYS_NP_PICK(S, CAP)                                                                                           \
+    do {                                                                                                               \
+        if constexpr (kF) { if (threads == 128) PHYS_NP_LAUNCH(128, S, CAP, true, flt); else PHYS_NP_LAUNCH(512, S, CAP, true, flt); } \
+        else { if (threads == 128) PHYS_NP_LAUNCH(128, S, CAP, false); else PHYS_NP_LAUNCH(512, S, CAP, false); }           \
+    } while (0)
+    dispatch_bool(filters, [&](auto fl) {
+        constexpr bool kF = decltype(fl)::value;
+        if (capsules) {
+            if (st_pairs) PHYS_NP_PICK(true, true);
+            else PHYS_NP_PICK(false, true);
+        } else if (st_pairs) {
+            PHYS_NP_PICK(true, false);
         } else {
-            if (threads == 128) PHYS_NP_LAUNCH(128, false, true);
-            else PHYS_NP_LAUNCH(512, false, true);
+            PHYS_NP_PICK(false, false);
         }
-    } else if (st_pairs) {
-        if (threads == 128) PHYS_NP_LAUNCH(128, true, false);
-        else PHYS_NP_LAUNCH(512, true, false);
-    } else {
-        if (threads == 128) PHYS_NP_LAUNCH(128, false, false);
-        else PHYS_NP_LAUNCH(512, false, false);
-    }
+    });
+#undef PHYS_NP_PICK
 #undef PHYS_NP_LAUNCH
 }
 

@@ -182,7 +182,9 @@ __device__ __forceinline__ bool aabb_touch(const aabb_t& a, const aabb_t& b) {
 }
 
 // FILL = false: count[q] = the number of targets query q intersects. FILL = true: their ids into ids[offsets[q] ...]
-template <bool FILL>
+// FILT: phys_overlap_filtered (one QueryFilters argument, the pack `filt`): a target whose category misses the query's mask
+// is skipped before its exact test; without it the pack is empty and the kernel is the one it was before filters
+template <bool FILL, bool FILT, typename... Filt>
 __global__ __launch_bounds__(kOvThreads) void k_ov_query(uint32_t nq, const uint32_t* __restrict__ qtype, const float* __restrict__ qpos,
                                                         const float* __restrict__ qrot, const float* __restrict__ qhe,
                                                         const uint32_t* __restrict__ ignore_body, const RcHeader* __restrict__ hdr,
@@ -191,9 +193,13 @@ __global__ __launch_bounds__(kOvThreads) void k_ov_query(uint32_t nq, const uint
                                                         const float* __restrict__ he, const uint32_t* __restrict__ shape, int ground,
                                                         float ground_y, const float4* __restrict__ st_rec, uint32_t n_static,
                                                         uint32_t* __restrict__ count, const unsigned long long* __restrict__ offsets,
-                                                        uint32_t* __restrict__ ids) {
+                                                        uint32_t* __restrict__ ids, Filt... filt) {
+    static_assert(sizeof...(Filt) == (FILT ? 1u : 0u), "one QueryFilters argument exactly in the filtered instance");
     const uint32_t q = blockIdx.x * kOvThreads + threadIdx.x;
     if (q >= nq) return;
+    QueryFilters qf{};
+    if constexpr (FILT) qf = filter_arg(filt...);
+    const uint32_t qm = FILT ? (uint32_t)qf.query_mask[q] : 0xFFFFu;
     uint32_t cnt = 0;
     const unsigned long long base = FILL ? offsets[q] : 0ull;
     const uint32_t room = FILL ? (uint32_t)(offsets[q + 1] - base) : 0u;
@@ -224,7 +230,7 @@ __global__ __launch_bounds__(kOvThreads) void k_ov_query(uint32_t nq, const uint
                 // more cells than bodies: every owned body directly, in ascending order
                 for (uint32_t i = 0; i < n_bodies; ++i) {
                     aabb_t b;
-                    if (i == ign || !rc_aabb(pos, rot, he, shape, i, &b) || !aabb_touch(b, qp)) continue;
+                    if (i == ign || (FILT && (qf.body[i].x & qm) == 0u) || !rc_aabb(pos, rot, he, shape, i, &b) || !aabb_touch(b, qp)) continue;
                     if (qr_overlap(Q, qs_make(shape[i], ld3(pos, i), reinterpret_cast<const float4*>(rot)[i], ld3(he, i)))) emit(i);
                 }
             } else {
@@ -238,7 +244,9 @@ __global__ __launch_bounds__(kOvThreads) void k_ov_query(uint32_t nq, const uint
                                 const uint32_t id = __float_as_uint(r2.w);
                                 const v3 bc = v3_make(r0.x, r0.y, r0.z), bh = v3_make(r2.x, r2.y, r2.z);
                                 aabb_t b;
-                                if (id == ign || !rc_aabb_of(bc, r1, bh, __float_as_uint(r0.w), &b) || !aabb_touch(b, qp)) continue;
+                                if (id == ign || (FILT && (qf.body[id].x & qm) == 0u) || !rc_aabb_of(bc, r1, bh, __float_as_uint(r0.w), &b) ||
+                                    !aabb_touch(b, qp))
+                                    continue;
                                 // only in the first cell the body shares with the query: the record may be another cell's
                                 const RcCells bcl = rc_body_cells(g, b);
                                 if (x > bcl.x1 || y > bcl.y1 || z > bcl.z1 || max(bcl.x0, x0) != x || max(bcl.y0, y0) != y ||
@@ -255,6 +263,7 @@ __global__ __launch_bounds__(kOvThreads) void k_ov_query(uint32_t nq, const uint
         }
         // static colliders, ascending (ids PHYS_STATIC_ID_BIT | k above every body id)
         for (uint32_t k = 0; k < n_static; ++k) {
+            if (FILT && (qf.st[k].x & qm) == 0u) continue;
             const float4 r0 = st_rec[3 * (size_t)k], r1 = st_rec[3 * (size_t)k + 1], r2 = st_rec[3 * (size_t)k + 2];
             const v3 bc = v3_make(r0.x, r0.y, r0.z), bh = v3_make(r2.x, r2.y, r2.z);
             aabb_t b;
@@ -262,7 +271,7 @@ __global__ __launch_bounds__(kOvThreads) void k_ov_query(uint32_t nq, const uint
             if (qr_overlap(Q, qs_make(__float_as_uint(r0.w), bc, r1, bh))) emit(__float_as_uint(r2.w));
         }
         // the ground half-space y <= ground_y: the query's lowest point is its AABB's low y
-        if (ground && qa.lo.y <= ground_y) emit(kRayGround);
+        if (ground && (!FILT || (qf.ground & qm) != 0u) && qa.lo.y <= ground_y) emit(kRayGround);
     }
     if (!FILL) count[q] = cnt;
 }
@@ -321,7 +330,7 @@ __global__ __launch_bounds__(kOvSortThreads) void k_ov_order(uint32_t nq, const 
 }  // namespace
 
 int32_t launch_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot, const float* half_extent,
-                       const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out) {
+                       const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out, const uint16_t* query_mask) {
     hipStream_t s = w->stream;
     uint32_t bits = 12;
     int32_t rc = launch_query_grid(w, nullptr, 0, &bits); if (rc) return rc;
@@ -333,9 +342,18 @@ int32_t launch_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, co
     const uint32_t nb = (uint32_t)w->n_owned;
     const float4* st = reinterpret_cast<const float4*>(w->st_rc.p);
     const float4* rec = reinterpret_cast<const float4*>(w->rc_records.p);
-    hipLaunchKernelGGL(k_ov_query<false>, dim3(blocks), dim3(kOvThreads), 0, s, (uint32_t)n, shape_type, pos, rot, half_extent, ignore_body,
-                       hdr, bits, (const uint32_t*)w->rc_start.p, rec, nb, w->pos.p, w->rot.p, w->half_extent.p, w->shape.p, ground,
-                       w->cfg.ground_height, st, (uint32_t)w->n_static, w->qr_count.p, (const unsigned long long*)nullptr, (uint32_t*)nullptr);
+    QueryFilters qf{};
+    qf.query_mask = query_mask;
+    qf.body = reinterpret_cast<const uint2*>(w->filt.p);
+    qf.st = reinterpret_cast<const uint2*>(w->st_filt.p);
+    qf.ground = w->ground_filt & 0xFFFFu;
+    // (the filtered instances take `qf` as one more argument; the unfiltered ones are launched exactly as before filters)
+#define PHYS_OV_LAUNCH(FILL, FILT, count, offsets, ids, ...)                                                                 \
+    hipLaunchKernelGGL((k_ov_query<FILL, FILT>), dim3(blocks), dim3(kOvThreads), 0, s, (uint32_t)n, shape_type, pos, rot, half_extent, \
+                       ignore_body, hdr, bits, (const uint32_t*)w->rc_start.p, rec, nb, w->pos.p, w->rot.p, w->half_extent.p,      \
+                       w->shape.p, ground, w->cfg.ground_height, st, (uint32_t)w->n_static, count, offsets, ids, ##__VA_ARGS__)
+    if (query_mask) PHYS_OV_LAUNCH(false, true, w->qr_count.p, (const unsigned long long*)nullptr, (uint32_t*)nullptr, qf);
+    else PHYS_OV_LAUNCH(false, false, w->qr_count.p, (const unsigned long long*)nullptr, (uint32_t*)nullptr);
     PHYS_HIP_TRY(hipGetLastError());
     // exclusive scan on the host: the offsets are an output of the call anyway
     std::vector<uint32_t> cnt((size_t)n);
@@ -353,10 +371,9 @@ int32_t launch_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, co
     uint32_t* tmp = w->qr_ids.p;
     uint32_t* out = w->qr_ids.p + run;
     PHYS_HIP_TRY(hipMemcpyAsync(w->qr_off.p, offsets_out, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_ov_query<true>, dim3(blocks), dim3(kOvThreads), 0, s, (uint32_t)n, shape_type, pos, rot, half_extent, ignore_body,
-                       hdr, bits, (const uint32_t*)w->rc_start.p, rec, nb, w->pos.p, w->rot.p, w->half_extent.p, w->shape.p, ground,
-                       w->cfg.ground_height, st, (uint32_t)w->n_static, (uint32_t*)nullptr,
-                       (const unsigned long long*)w->qr_off.p, tmp);
+    if (query_mask) PHYS_OV_LAUNCH(true, true, (uint32_t*)nullptr, (const unsigned long long*)w->qr_off.p, tmp, qf);
+    else PHYS_OV_LAUNCH(true, false, (uint32_t*)nullptr, (const unsigned long long*)w->qr_off.p, tmp);
+#undef PHYS_OV_LAUNCH
     hipLaunchKernelGGL(k_ov_order, dim3((unsigned)std::min<uint64_t>(n, kOvMaxSortBlocks)), dim3(kOvSortThreads), 0, s, (uint32_t)n,
                        (const unsigned long long*)w->qr_off.p, (const uint32_t*)tmp, out);
     PHYS_HIP_TRY(hipGetLastError());

@@ -307,8 +307,10 @@ __device__ __forceinline__ float rc_plane_t(int i, bool up, float lo, float cell
 }
 
 // SWEEP: a sphere cast (radius per ray; the grid was grown by the largest valid radius, so the walk of the centre line
-// meets every target the ball can touch); otherwise a ray cast (radius unused, the arithmetic of the ray cast unchanged)
-template <bool STATS, bool SWEEP>
+// meets every target the ball can touch); otherwise a ray cast (radius unused, the arithmetic of the ray cast unchanged).
+// FILT: the _filtered calls (one QueryFilters argument, the pack `filt`): a target whose category misses the query's mask
+// is skipped before its exact test; without it the pack is empty and the kernel is the one it was before filters
+template <bool STATS, bool SWEEP, bool FILT, typename... Filt>
 __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const float* __restrict__ origin, const float* __restrict__ dir,
                                                         const float* __restrict__ radius,
                                                         const float* __restrict__ max_t, const uint32_t* __restrict__ ignore_body,
@@ -316,9 +318,13 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
                                                         const float4* __restrict__ rec, uint32_t n_bodies, int ground, float ground_y,
                                                         const float4* __restrict__ st_rec, uint32_t n_static,
                                                         uint32_t* __restrict__ body_out, float* __restrict__ t_out, float* __restrict__ normal_out,
-                                                        unsigned long long* __restrict__ stats) {
+                                                        unsigned long long* __restrict__ stats, Filt... filt) {
+    static_assert(sizeof...(Filt) == (FILT ? 1u : 0u), "one QueryFilters argument exactly in the filtered instance");
     const uint32_t r = blockIdx.x * kRcThreads + threadIdx.x;
     if (r >= n_rays) return;
+    QueryFilters qf{};
+    if constexpr (FILT) qf = filter_arg(filt...);
+    const uint32_t qm = FILT ? (uint32_t)qf.query_mask[r] : 0xFFFFu;
     RayHit best;
     best.t = __builtin_inff(); best.id = kRayMiss; best.nx = 0.0f; best.ny = 0.0f; best.nz = 0.0f;
     uint32_t cells = 0, cands = 0;
@@ -333,7 +339,7 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
         const float ux = d.x / len, uy = d.y / len, uz = d.z / len;
         // the ground: the solid half-space y <= ground_y (for a ball: its centre reaches y = ground_y + rad)
         const float gy = SWEEP ? ground_y + rad : ground_y;
-        if (ground) {
+        if (ground && (!FILT || (qf.ground & qm) != 0u)) {
             float tg = -1.0f;
             if (o.y <= gy) { tg = 0.0f; best.nx = -ux; best.ny = -uy; best.nz = -uz; }
             else if (uy < 0.0f) { tg = (gy - o.y) / uy; best.nx = 0.0f; best.ny = 1.0f; best.nz = 0.0f; }
@@ -343,6 +349,7 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
         // static colliders (records of phys_set_static_bodies, id PHYS_STATIC_ID_BIT | k): every one tested, before the bodies'
         // walk so that a static hit shortens it; bodies still win exact ties (smaller ids), the ground loses them
         for (uint32_t k = 0; k < n_static; ++k) {
+            if (FILT && (qf.st[k].x & qm) == 0u) continue;
             if (SWEEP) sc_test(st_rec, k, o.x, o.y, o.z, ux, uy, uz, rad, tmax, 0xFFFFFFFFu, best);
             else rc_test(st_rec, k, o.x, o.y, o.z, ux, uy, uz, tmax, 0xFFFFFFFFu, best);
         }
@@ -376,6 +383,7 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
                 const uint32_t b0 = start[bk], b1 = start[bk + 1];
                 if (STATS) { cells += 1; cands += b1 - b0; }
                 for (uint32_t k = b0; k < b1; ++k) {
+                    if (FILT && (qf.body[__float_as_uint(rec[3 * (size_t)k + 2].w)].x & qm) == 0u) continue;
                     if (SWEEP) sc_test(rec, k, o.x, o.y, o.z, ux, uy, uz, rad, tlim, ign, best);
                     else rc_test(rec, k, o.x, o.y, o.z, ux, uy, uz, tlim, ign, best);
                 }
@@ -457,7 +465,7 @@ int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_ra
 
 // the walk shared by ray casts (radius == nullptr) and sphere casts
 static int32_t trace(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* radius, const float* max_t,
-                     const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
+                     const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out, const uint16_t* query_mask) {
     hipStream_t s = w->stream;
     const uint64_t n = w->n_owned;
     uint32_t bits = 12;
@@ -469,13 +477,23 @@ static int32_t trace(phys_world* w, uint64_t n_rays, const float* origin, const 
         PHYS_HIP_TRY(hipMemsetAsync(w->rc_stats.p, 0, 16, s));
     }
     const int ground = (w->cfg.flags & PHYS_FLAG_GROUND_PLANE) ? 1 : 0;
+    QueryFilters qf{};
+    qf.query_mask = query_mask;
+    qf.body = reinterpret_cast<const uint2*>(w->filt.p);
+    qf.st = reinterpret_cast<const uint2*>(w->st_filt.p);
+    qf.ground = w->ground_filt & 0xFFFFu;
     dispatch_bool(stats, [&](auto st) {
         dispatch_bool(radius != nullptr, [&](auto sw) {
-            hipLaunchKernelGGL((k_rc_trace<decltype(st)::value, decltype(sw)::value>), dim3(rc_blocks(n_rays)), dim3(kRcThreads), 0, s,
-                               (uint32_t)n_rays, origin, dir, radius, max_t, ignore_body, hdr, bits, (const uint32_t*)w->rc_start.p,
-                               reinterpret_cast<const float4*>(w->rc_records.p), (uint32_t)n, ground, w->cfg.ground_height,
-                               reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static, body_out, t_out, normal_out,
-                               w->rc_stats.p);
+            constexpr bool kSt = decltype(st)::value, kSw = decltype(sw)::value;
+#define PHYS_RC_LAUNCH(FILT, ...)                                                                                            \
+    hipLaunchKernelGGL((k_rc_trace<kSt, kSw, FILT>), dim3(rc_blocks(n_rays)), dim3(kRcThreads), 0, s, (uint32_t)n_rays, origin, dir,  \
+                       radius, max_t, ignore_body, hdr, bits, (const uint32_t*)w->rc_start.p,                                      \
+                       reinterpret_cast<const float4*>(w->rc_records.p), (uint32_t)n, ground, w->cfg.ground_height,               \
+                       reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static, body_out, t_out, normal_out,           \
+                       w->rc_stats.p, ##__VA_ARGS__)
+            if (query_mask) PHYS_RC_LAUNCH(true, qf);
+            else PHYS_RC_LAUNCH(false);
+#undef PHYS_RC_LAUNCH
         });
     });
     PHYS_HIP_TRY(hipGetLastError());
@@ -490,13 +508,13 @@ static int32_t trace(phys_world* w, uint64_t n_rays, const float* origin, const 
 }
 
 int32_t launch_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
-                       const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    return trace(w, n_rays, origin, dir, nullptr, max_t, ignore_body, body_out, t_out, normal_out);
+                       const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out, const uint16_t* query_mask) {
+    return trace(w, n_rays, origin, dir, nullptr, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
 }
 
 int32_t launch_spherecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
-                          const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    return trace(w, n, origin, dir, radius, max_t, ignore_body, body_out, t_out, normal_out);
+                          const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out, const uint16_t* query_mask) {
+    return trace(w, n, origin, dir, radius, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
 }
 
 }  // namespace phys

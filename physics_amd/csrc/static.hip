@@ -306,6 +306,11 @@ int32_t static_set(phys_world* w, uint64_t n, const float* pos, const float* rot
     PHYS_HIP_TRY(w->st_cell_start.resize(cell_start.size()));
     PHYS_HIP_TRY(w->st_cell_ids.resize(cell_ids.size()));
     PHYS_HIP_TRY(w->st_large.resize(large.size()));
+    // every static starts with the default collision filter (phys_set_static_filters changes them)
+    std::vector<uint32_t> filt(2 * n);
+    for (uint64_t k = 0; k < n; ++k) { filt[2 * k] = kFilterDefaultWord; filt[2 * k + 1] = 0u; }
+    PHYS_HIP_TRY(w->st_filt.resize(2 * n));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->st_filt.p, filt.data(), 4 * filt.size(), hipMemcpyHostToDevice, s));
     PHYS_HIP_TRY(hipMemcpyAsync(w->st_geo.p, geo.data(), 4 * geo.size(), hipMemcpyHostToDevice, s));
     PHYS_HIP_TRY(hipMemcpyAsync(w->st_rc.p, rc.data(), 4 * rc.size(), hipMemcpyHostToDevice, s));
     PHYS_HIP_TRY(hipMemcpyAsync(w->st_box.p, box.data(), 4 * box.size(), hipMemcpyHostToDevice, s));

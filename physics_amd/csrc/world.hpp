@@ -231,6 +231,13 @@ struct phys_world {
     // the fattened AABB}; written once per update by k_step_velocity_aabb (which has it all in registers), gathered twice
     // per candidate pair - instead of four 4-to-16-byte gathers per body out of four arrays (C5: 3M pairs per update)
     phys::DevBuf<float> geo;  // 16 floats per body (48 bytes used)
+    // collision filters: one {category | mask << 16, (u32)group} per body slot, owned and ghost (2n
+    // words; the defaults after phys_set_bodies, ghost slots reset by k_ghost_clear and written by k_halo_unpack)
+    phys::DevBuf<uint32_t> filt;
+    bool body_filters_set = false;    // phys_set_body_filters since the last phys_set_bodies: the narrow phase's filtered variant
+    bool static_filters_set = false;  // phys_set_static_filters since the last phys_set_static_bodies
+    bool ground_filter_set = false;   // phys_set_ground_filter ever (the ground filter lasts for the life of the world)
+    uint32_t ground_filt = 0xFFFF0001u;  // the ground's category | mask << 16 (its group is 0)
 
     // constraints (A3-A7)
     std::vector<phys::Constraint> constraints;
@@ -341,6 +348,7 @@ struct phys_world {
     bool static_capsules = false;        // some static is a PHYS_SHAPE_CAPSULE: the narrow phase's capsule variant
     phys::DevBuf<float> st_geo;          // 16 floats per static, the layout of `geo`: {pos, shape} {rot} {half extent, -}
     phys::DevBuf<float> st_rc;           // 12 floats per static, the ray-cast record {pos, shape} {rot} {half extent, id}
+    phys::DevBuf<uint32_t> st_filt;      // 2 words per static: its filter, the layout of `filt` (defaults after phys_set_static_bodies)
     phys::DevBuf<float> st_box;          // 8 floats per static: {fattened AABB lo, packed first grid cell} {hi, -}
     phys::DevBuf<uint32_t> st_cell_start, st_cell_ids;  // uniform grid over the small statics, CSR: cell -> ascending ids
     phys::DevBuf<uint32_t> st_large;     // statics that would cover too many cells: tested by every body, ascending

@@ -172,22 +172,22 @@ class PhysicsState:
         lam = self._world.get_lambda()
         return lam if len(lam) else None
 
-    def raycast(self, origins, dirs, max_t=None, ignore=None):
+    def raycast(self, origins, dirs, max_t=None, ignore=None, mask=None):
         """Closest hit per ray against the entities as they are now (World.raycast): (body index or RAY_MISS /
         RAY_GROUND, t, normal)."""
         self._push()
-        return self._world.raycast(origins, dirs, max_t, ignore)
+        return self._world.raycast(origins, dirs, max_t, ignore, mask=mask)
 
-    def spherecast(self, origins, dirs, radius, max_t=None, ignore=None):
+    def spherecast(self, origins, dirs, radius, max_t=None, ignore=None, mask=None):
         """First target per moving ball against the entities as they are now (World.spherecast): (body index or
         RAY_MISS / RAY_GROUND, t, normal)."""
         self._push()
-        return self._world.spherecast(origins, dirs, radius, max_t, ignore)
+        return self._world.spherecast(origins, dirs, radius, max_t, ignore, mask=mask)
 
-    def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None):
+    def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None, mask=None):
         """Every entity each query shape intersects, as they are now (World.overlap): (offsets, ascending ids)."""
         self._push()
-        return self._world.overlap(shape_type, pos, rot, half_extent, ignore)
+        return self._world.overlap(shape_type, pos, rot, half_extent, ignore, mask=mask)
 
     def instance_matrices(self):  # what get_render_data feeds the renderer (physics.rs:61-69)
         self._push()

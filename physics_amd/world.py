@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import STAGE_NAMES, PhysDeviceView, PhysProfile, PhysStats, f32p, u32p
+from ._abi import STAGE_NAMES, PhysDeviceView, PhysProfile, PhysStats, f32p, i16p, u16p, u32p
 
 
 class PhysError(RuntimeError):
@@ -22,12 +22,54 @@ def _p(a, t=f32p):
     return None if a is None else a.ctypes.data_as(t)
 
 
+def _filter_field(a, n, name, lo, hi, dtype):
+    """A per-item filter field as a contiguous array of n `dtype` values, or None; out-of-range or non-integer values and a
+    wrong length raise before the library is called."""
+    if a is None:
+        return None
+    v = np.asarray(a)
+    if v.dtype.kind not in "iub":
+        raise ValueError(f"{name}: needs integers")
+    v = np.broadcast_to(v, (n,)) if v.ndim == 0 else v
+    if v.ndim != 1 or v.shape[0] != n:
+        raise ValueError(f"{name}: needs {n} values, got shape {np.shape(a)}")
+    if v.size and (v.min() < lo or v.max() > hi):
+        raise ValueError(f"{name}: values must lie in [{lo}, {hi}]")
+    return np.ascontiguousarray(v, dtype=dtype)
+
+
+def _query_mask(mask, n):
+    """The per-query mask of a _filtered query: a scalar or (n,) integers in [0, 0xFFFF]."""
+    return _filter_field(mask, n, "mask", 0, 0xFFFF, np.uint16)
+
+
+def _device_args(n, items):
+    """c_void_p of contiguous 4-byte device tensors of n x cols elements (None passes through)."""
+    args = []
+    for name, x, cols in items:
+        if x is None:
+            args.append(None)
+            continue
+        if not x.is_cuda or not x.is_contiguous() or x.numel() != n * cols or x.element_size() != 4:
+            raise ValueError(f"{name}: needs a contiguous 4-byte device tensor of {n} x {cols}")
+        args.append(C.c_void_p(x.data_ptr()))
+    return args
+
+
+def _device_mask(mask, n):
+    """c_void_p of a contiguous 2-byte device tensor of n query masks."""
+    if not mask.is_cuda or not mask.is_contiguous() or mask.numel() != n or mask.element_size() != 2 or mask.is_floating_point():
+        raise ValueError(f"mask: needs a contiguous int16 / uint16 device tensor of {n}")
+    return C.c_void_p(mask.data_ptr())
+
+
 class World:
     def __init__(self, cfg=None):
         self.lib = _abi.load_library()
         self.cfg = cfg if cfg is not None else _abi.default_config()
         self.h = C.c_void_p()
         self.n = 0
+        self.n_static = 0
         self._ck(self.lib.phys_create(C.byref(self.cfg), C.byref(self.h)))
 
     def _ck(self, rc):
@@ -79,6 +121,42 @@ class World:
             if a is not None and a.size != n * w:
                 raise ValueError("array size does not match the static collider count")
         self._ck(self.lib.phys_set_static_bodies(self.h, n, _p(pos), _p(rot), _p(st, u32p), _p(he)))
+        self.n_static = n
+
+    # ---- collision filters (include/physics_hip.h): category u16, mask u16, group i16 per body / static
+    def set_body_filters(self, category=None, mask=None, group=None):
+        """Filters of the owned bodies (phys_set_body_filters): each of category / mask / group a scalar or (n_bodies,)
+        integers, or None for the default (category FILTER_DEFAULT_CATEGORY, mask FILTER_DEFAULT_MASK, group 0). Two bodies
+        collide iff they share a nonzero group that is positive, or (without one) each one's category meets the other's
+        mask. Takes effect at the next update; set_bodies resets the filters."""
+        n = self.n
+        c = _filter_field(category, n, "category", 0, 0xFFFF, np.uint16)
+        m = _filter_field(mask, n, "mask", 0, 0xFFFF, np.uint16)
+        g = _filter_field(group, n, "group", -0x8000, 0x7FFF, np.int16)
+        self._ck(self.lib.phys_set_body_filters(self.h, n, _p(c, u16p), _p(m, u16p), _p(g, i16p)))
+
+    def get_body_filters(self):
+        """(category u16[n], mask u16[n], group i16[n]) of the owned bodies."""
+        c = np.empty(self.n, np.uint16)
+        m = np.empty(self.n, np.uint16)
+        g = np.empty(self.n, np.int16)
+        self._ck(self.lib.phys_get_body_filters(self.h, _p(c, u16p), _p(m, u16p), _p(g, i16p)))
+        return c, m, g
+
+    def set_static_filters(self, category=None, mask=None, group=None):
+        """Filters of the static colliders (phys_set_static_filters), as set_body_filters; set_static_bodies resets them."""
+        n = self.n_static
+        c = _filter_field(category, n, "category", 0, 0xFFFF, np.uint16)
+        m = _filter_field(mask, n, "mask", 0, 0xFFFF, np.uint16)
+        g = _filter_field(group, n, "group", -0x8000, 0x7FFF, np.int16)
+        self._ck(self.lib.phys_set_static_filters(self.h, n, _p(c, u16p), _p(m, u16p), _p(g, i16p)))
+
+    def set_ground_filter(self, category, mask):
+        """The ground plane's category and mask (its group is 0); lasts for the life of the world."""
+        for name, v in (("category", category), ("mask", mask)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xFFFF:
+                raise ValueError(f"{name}: needs an integer in [0, 65535]")
+        self._ck(self.lib.phys_set_ground_filter(self.h, int(category), int(mask)))
 
     def get_static_stats(self):
         """(static colliders, (body, static) pairs of the last update, manifolds against statics of the last update)."""
@@ -179,10 +257,11 @@ class World:
         self._ck(self.lib.phys_get_aabbs(self.h, _p(out)))
         return out
 
-    def raycast(self, origins, dirs, max_t=None, ignore=None):
+    def raycast(self, origins, dirs, max_t=None, ignore=None, mask=None):
         """Closest hit of every ray against the current poses (phys_raycast): origins / dirs (n, 3), max_t (n,) or None
         (= +inf), ignore (n,) body ids or None. Returns (body u32[n], t f32[n], normal f32[n, 3]); a miss is
-        (RAY_MISS, +inf, 0), the ground RAY_GROUND."""
+        (RAY_MISS, +inf, 0), the ground RAY_GROUND. mask (scalar or (n,) u16): only targets whose filter category meets
+        it are seen (phys_raycast_filtered); None: every target."""
         o = _f(origins).reshape(-1, 3)
         d = _f(dirs).reshape(-1, 3)
         n = o.shape[0]
@@ -193,35 +272,35 @@ class World:
         for a in (mt, ig):
             if a is not None and a.size != n:
                 raise ValueError("max_t / ignore do not match the ray count")
+        qm = _query_mask(mask, n)
         body = np.empty(n, np.uint32)
         t = np.empty(n, np.float32)
         normal = np.empty((n, 3), np.float32)
-        if n:
+        if n and qm is None:
             self._ck(self.lib.phys_raycast(self.h, n, _p(o), _p(d), _p(mt), _p(ig, u32p), _p(body, u32p), _p(t), _p(normal)))
+        elif n:
+            self._ck(self.lib.phys_raycast_filtered(self.h, n, _p(o), _p(d), _p(mt), _p(ig, u32p), _p(qm, u16p), _p(body, u32p),
+                                                    _p(t), _p(normal)))
         return body, t, normal
 
-    def raycast_device(self, origins, dirs, body_out, t_out, normal_out=None, max_t=None, ignore=None):
+    def raycast_device(self, origins, dirs, body_out, t_out, normal_out=None, max_t=None, ignore=None, mask=None):
         """phys_raycast_device on contiguous torch tensors of the world's device: origins / dirs float32 (n, 3), body_out
         int32 or uint32 (n,), t_out float32 (n,), normal_out float32 (n, 3) or None, max_t float32 (n,) or None, ignore
-        int32 / uint32 (n,) or None. Only enqueues on the world's stream (device_view().stream): order other streams'
-        work against it yourself."""
+        int32 / uint32 (n,) or None, mask int16 / uint16 (n,) or None (phys_raycast_device_filtered). Only enqueues on
+        the world's stream (device_view().stream): order other streams' work against it yourself."""
         n = int(origins.shape[0])
-        args = []
-        for name, x, cols in (("origins", origins, 3), ("dirs", dirs, 3), ("max_t", max_t, 1), ("ignore", ignore, 1),
-                              ("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3)):
-            if x is None:
-                args.append(None)
-                continue
-            if not x.is_cuda or not x.is_contiguous() or x.numel() != n * cols or x.element_size() != 4:
-                raise ValueError(f"{name}: needs a contiguous 4-byte device tensor of {n} x {cols}")
-            args.append(C.c_void_p(x.data_ptr()))
-        self._ck(self.lib.phys_raycast_device(self.h, n, *args))
+        args = _device_args(n, (("origins", origins, 3), ("dirs", dirs, 3), ("max_t", max_t, 1), ("ignore", ignore, 1)))
+        out = _device_args(n, (("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3)))
+        if mask is None:
+            self._ck(self.lib.phys_raycast_device(self.h, n, *args, *out))
+        else:
+            self._ck(self.lib.phys_raycast_device_filtered(self.h, n, *args, _device_mask(mask, n), *out))
 
-    def spherecast(self, origins, dirs, radius, max_t=None, ignore=None):
+    def spherecast(self, origins, dirs, radius, max_t=None, ignore=None, mask=None):
         """First target a moving ball touches, per ball (phys_spherecast): origins / dirs (n, 3), radius scalar or (n,),
         max_t (n,) or None (= +inf), ignore (n,) body ids or None. Returns (body u32[n], t f32[n], normal f32[n, 3]): t is
         the distance the centre travelled, normal the target's outward normal at the contact (-dir from an overlap at t = 0);
-        a miss is (RAY_MISS, +inf, 0)."""
+        a miss is (RAY_MISS, +inf, 0). mask: as for raycast (phys_spherecast_filtered)."""
         o = _f(origins).reshape(-1, 3)
         d = _f(dirs).reshape(-1, 3)
         n = o.shape[0]
@@ -233,35 +312,37 @@ class World:
         for a in (mt, ig):
             if a is not None and a.size != n:
                 raise ValueError("max_t / ignore do not match the ball count")
+        qm = _query_mask(mask, n)
         body = np.empty(n, np.uint32)
         t = np.empty(n, np.float32)
         normal = np.empty((n, 3), np.float32)
-        if n:
+        if n and qm is None:
             self._ck(self.lib.phys_spherecast(self.h, n, _p(o), _p(d), _p(rad), _p(mt), _p(ig, u32p), _p(body, u32p), _p(t),
                                               _p(normal)))
+        elif n:
+            self._ck(self.lib.phys_spherecast_filtered(self.h, n, _p(o), _p(d), _p(rad), _p(mt), _p(ig, u32p), _p(qm, u16p),
+                                                       _p(body, u32p), _p(t), _p(normal)))
         return body, t, normal
 
-    def spherecast_device(self, origins, dirs, radius, body_out, t_out, normal_out=None, max_t=None, ignore=None):
+    def spherecast_device(self, origins, dirs, radius, body_out, t_out, normal_out=None, max_t=None, ignore=None, mask=None):
         """phys_spherecast_device on contiguous torch tensors of the world's device, as raycast_device; radius float32 (n,).
         Only enqueues on the world's stream (device_view().stream)."""
         n = int(origins.shape[0])
-        args = []
-        for name, x, cols in (("origins", origins, 3), ("dirs", dirs, 3), ("radius", radius, 1), ("max_t", max_t, 1),
-                              ("ignore", ignore, 1), ("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3)):
-            if x is None:
-                args.append(None)
-                continue
-            if not x.is_cuda or not x.is_contiguous() or x.numel() != n * cols or x.element_size() != 4:
-                raise ValueError(f"{name}: needs a contiguous 4-byte device tensor of {n} x {cols}")
-            args.append(C.c_void_p(x.data_ptr()))
-        self._ck(self.lib.phys_spherecast_device(self.h, n, *args))
+        args = _device_args(n, (("origins", origins, 3), ("dirs", dirs, 3), ("radius", radius, 1), ("max_t", max_t, 1),
+                                ("ignore", ignore, 1)))
+        out = _device_args(n, (("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3)))
+        if mask is None:
+            self._ck(self.lib.phys_spherecast_device(self.h, n, *args, *out))
+        else:
+            self._ck(self.lib.phys_spherecast_device_filtered(self.h, n, *args, _device_mask(mask, n), *out))
 
-    def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None, cap=None):
+    def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None, cap=None, mask=None):
         """Every target each query shape intersects (phys_overlap): shape_type scalar or (n,) SHAPE_SPHERE / BOX / CAPSULE,
         pos (n, 3), rot (n, 4) [i, j, k, w] or None (identity), half_extent (3,) or (n, 3) with the bodies' conventions,
         ignore (n,) body ids or None. Returns (offsets u64[n + 1], ids u32[offsets[n]]): query i's ids, ascending, are
         ids[offsets[i]:offsets[i + 1]] (bodies, then PHYS_STATIC_ID_BIT | k, then RAY_GROUND). The first call reserves
-        `cap` ids (default 8 per query) and, if they do not fit, the call is repeated once with the reported total."""
+        `cap` ids (default 8 per query) and, if they do not fit, the call is repeated once with the reported total. mask: as
+        for raycast (phys_overlap_filtered)."""
         p = _f(pos).reshape(-1, 3)
         n = p.shape[0]
         if half_extent is None:
@@ -273,12 +354,17 @@ class World:
         for a, k in ((r, 4), (ig, 1)):
             if a is not None and a.size != n * k:
                 raise ValueError("rot / ignore do not match the query count")
+        qm = _query_mask(mask, n)
         offsets = np.zeros(n + 1, np.uint64)
         cap = 8 * n + 64 if cap is None else int(cap)
         for attempt in range(2):
             ids = np.empty(max(cap, 1), np.uint32)
-            rc = self.lib.phys_overlap(self.h, n, _p(st, u32p), _p(p), _p(r), _p(he), _p(ig, u32p), cap, _p(offsets, _abi.u64p),
-                                       _p(ids, u32p))
+            if qm is None:
+                rc = self.lib.phys_overlap(self.h, n, _p(st, u32p), _p(p), _p(r), _p(he), _p(ig, u32p), cap, _p(offsets, _abi.u64p),
+                                           _p(ids, u32p))
+            else:
+                rc = self.lib.phys_overlap_filtered(self.h, n, _p(st, u32p), _p(p), _p(r), _p(he), _p(ig, u32p), _p(qm, u16p), cap,
+                                                    _p(offsets, _abi.u64p), _p(ids, u32p))
             if rc == _abi.PHYS_ERR_CAPACITY and attempt == 0:
                 cap = int(offsets[n])
                 continue

@@ -15,6 +15,9 @@ pub const PHYS_SHAPE_BOX: u32 = 2;
 /// radius = half_extent[0], core half-length = half_extent[1] along the local y axis
 pub const PHYS_SHAPE_CAPSULE: u32 = 3;
 pub const PHYS_STATIC_ID_BIT: u32 = 0x8000_0000;
+// collision filters: category and mask are u16 layer bits, group an i16 (phys_set_body_filters)
+pub const PHYS_FILTER_DEFAULT_CATEGORY: u16 = 0x0001;
+pub const PHYS_FILTER_DEFAULT_MASK: u16 = 0xFFFF;
 pub const PHYS_FLAG_COLLISIONS: u32 = 0x1;
 pub const PHYS_FLAG_GROUND_PLANE: u32 = 0x2;
 pub const PHYS_FLAG_EXACT_ROTATION: u32 = 0x4;
@@ -153,6 +156,25 @@ extern "C" {
                         half_extent: *const f32, ignore_body: *const u32, cap: u64, offsets_out: *mut u64, ids_out: *mut u32) -> i32;
     pub fn phys_set_static_bodies(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32, shape_type: *const u32,
                                   half_extent: *const f32) -> i32;
+    pub fn phys_set_body_filters(w: *mut phys_world, n: u64, category: *const u16, mask: *const u16, group: *const i16) -> i32;
+    pub fn phys_get_body_filters(w: *mut phys_world, category_out: *mut u16, mask_out: *mut u16, group_out: *mut i16) -> i32;
+    pub fn phys_set_static_filters(w: *mut phys_world, n: u64, category: *const u16, mask: *const u16, group: *const i16) -> i32;
+    pub fn phys_set_ground_filter(w: *mut phys_world, category: u16, mask: u16) -> i32;
+    pub fn phys_raycast_filtered(w: *mut phys_world, n_rays: u64, origin: *const f32, dir: *const f32, max_t: *const f32,
+                                 ignore_body: *const u32, query_mask: *const u16, body_out: *mut u32, t_out: *mut f32,
+                                 normal_out: *mut f32) -> i32;
+    pub fn phys_raycast_device_filtered(w: *mut phys_world, n_rays: u64, origin: *const f32, dir: *const f32, max_t: *const f32,
+                                        ignore_body: *const u32, query_mask: *const u16, body_out: *mut u32, t_out: *mut f32,
+                                        normal_out: *mut f32) -> i32;
+    pub fn phys_spherecast_filtered(w: *mut phys_world, n: u64, origin: *const f32, dir: *const f32, radius: *const f32,
+                                    max_t: *const f32, ignore_body: *const u32, query_mask: *const u16, body_out: *mut u32,
+                                    t_out: *mut f32, normal_out: *mut f32) -> i32;
+    pub fn phys_spherecast_device_filtered(w: *mut phys_world, n: u64, origin: *const f32, dir: *const f32, radius: *const f32,
+                                           max_t: *const f32, ignore_body: *const u32, query_mask: *const u16, body_out: *mut u32,
+                                           t_out: *mut f32, normal_out: *mut f32) -> i32;
+    pub fn phys_overlap_filtered(w: *mut phys_world, n: u64, shape_type: *const u32, pos: *const f32, rot_ijkw: *const f32,
+                                 half_extent: *const f32, ignore_body: *const u32, query_mask: *const u16, cap: u64,
+                                 offsets_out: *mut u64, ids_out: *mut u32) -> i32;
     pub fn phys_get_static_stats(w: *mut phys_world, n_static: *mut u64, n_static_pairs: *mut u64, n_static_manifolds: *mut u64) -> i32;
     pub fn phys_profile_enable(w: *mut phys_world, on: i32) -> i32;
     pub fn phys_profile_get(w: *mut phys_world, out: *mut phys_profile) -> i32;
