@@ -387,6 +387,38 @@ int32_t phys_overlap_filtered(phys_world* w, uint64_t n, const uint32_t* shape_t
                               const uint32_t* ignore_body /*n, NULL = none*/, const uint16_t* query_mask /*n, NULL = no filtering*/,
                               uint64_t cap, uint64_t* offsets_out /*n + 1*/, uint32_t* ids_out /*cap*/);
 
+/* --- materials: how two things behave once they touch (new: the reference has none) ---
+ * Every body, static collider and the ground plane carries a material {friction >= 0, restitution in [0, 1]}. Defaults:
+ * friction = phys_config.friction, restitution = 0 - a world that never calls these functions behaves, and costs, as before.
+ * A manifold's friction is the geometric mean of its two sides' ((float)sqrt((double)fa * fb): combining a value with itself
+ * gives it back exactly), its restitution the larger of the two. A contact point whose approach speed along the normal
+ * exceeds the restitution threshold (default 1.0 length unit / s) and that touches within the update leaves with at least
+ * restitution times that speed; slower contacts - a pile at rest - are solved as without restitution. The rules are
+ * normative in include/spec/contact_solve.h (material_friction, material_restitution, contact_bias_restitution);
+ * DESIGN.md section 14.
+ *   - phys_set_body_materials: n must equal n_bodies (owned); phys_set_static_materials: n must equal the static count. A
+ *     NULL array gives that field its default for every item. Calls take effect at the next update (updates already
+ *     enqueued keep the materials they were enqueued with).
+ *   - phys_set_bodies resets every body material to the defaults, phys_set_static_bodies every static material. The
+ *     ground's material and the threshold last for the life of the world.
+ *   - changing materials does NOT make the world forget its colours or warm-start impulses.
+ *   - phys_get_body_materials: the owned bodies' materials; either output may be NULL.
+ *   - PHYS_ERR_INVALID_ARG: a wrong n, a negative or non-finite friction, a restitution outside [0, 1], a negative or
+ *     non-finite threshold.
+ *   - sharded worlds: materials do not cross slab cuts. A world created with max_ghosts > 0 answers every call below
+ *     with PHYS_ERR_UNSUPPORTED.
+ *   - cost: a world runs the solver's material kernels once a material call was made since the reset of what it set;
+ *     with every material at its default they produce the same bits as the plain kernels.
+ * These functions were added without an ABI version change (no struct changed): a caller tells an older library by the
+ * missing symbols. */
+int32_t phys_set_body_materials(phys_world* w, uint64_t n, const float* friction /*n, NULL = default*/,
+                                const float* restitution /*n, NULL = 0*/);
+int32_t phys_get_body_materials(phys_world* w, float* friction_out /*n_bodies, may be NULL*/, float* restitution_out /*may be NULL*/);
+int32_t phys_set_static_materials(phys_world* w, uint64_t n, const float* friction /*n, NULL = default*/,
+                                  const float* restitution /*n, NULL = 0*/);
+int32_t phys_set_ground_material(phys_world* w, float friction, float restitution);
+int32_t phys_set_restitution_threshold(phys_world* w, float v /* >= 0, finite */);
+
 /* --- per-stage device timing (HIP events on the world's stream), for bench.py's roofline --- */
 #define PHYS_STAGE_STEP_FULL 0u     /* gravity + RigidBody::step, one kernel (no collisions) */
 #define PHYS_STAGE_VELOCITY_AABB 1u /* gravity + velocity half + AABB */

@@ -78,6 +78,9 @@ struct RigidBody {  // rigid_body.rs:5-21
     // PHYS_SHAPE_BOX or PHYS_SHAPE_CAPSULE (radius half_extent.x, core half-length half_extent.y along the local y axis)
     uint32_t shape_type = PHYS_SHAPE_NONE;
     Vector3 half_extent;
+    // new: contact material (phys_set_body_materials). friction < 0: the world's phys_config.friction; restitution in [0, 1]
+    float friction = -1.0f;
+    float restitution = 0.0f;
 
     static RigidBody new_(size_t index) { RigidBody b; b.index = index; return b; }  // rigid_body.rs:64-76
     void apply_force_centre_of_gravity(const Vector3& f) { force = add(force, f); }       // :43-45
@@ -125,6 +128,7 @@ class PhysicsState {  // physics.rs:25-31
         phys_config c;
         if (cfg) c = *cfg; else phys_config_default(&c);
         check(phys_create(&c, &w_));
+        default_friction_ = c.friction;
     }
     ~PhysicsState() { if (w_) phys_destroy(w_); }
     PhysicsState(const PhysicsState&) = delete;
@@ -233,6 +237,10 @@ class PhysicsState {  // physics.rs:25-31
         for (size_t i = 0; i < n; ++i) out[i].assign(ids.begin() + off[i], ids.begin() + off[i + 1]);
         return out;
     }
+    // the ground plane's material and the approach speed below which nothing bounces (phys_set_ground_material,
+    // phys_set_restitution_threshold): both last for the life of the state
+    void set_ground_material(float friction, float restitution) { check(phys_set_ground_material(w_, friction, restitution)); }
+    void set_restitution_threshold(float v) { check(phys_set_restitution_threshold(w_, v)); }
     phys_world* raw() { return w_; }
 
   private:
@@ -240,6 +248,8 @@ class PhysicsState {  // physics.rs:25-31
     std::vector<Entity> snapshot_;
     std::vector<constraints::Constraints> con_snapshot_;
     bool uploaded_ = false;
+    bool materials_uploaded_ = false;  // phys_set_body_materials was called since the last phys_set_bodies
+    float default_friction_ = 0.0f;
 
     static void check(int32_t rc) {
         if (rc != PHYS_OK) throw Panic(rc, phys_last_error());
@@ -256,6 +266,13 @@ class PhysicsState {  // physics.rs:25-31
         const size_t n = entities.size();
         bool bodies_changed = !uploaded_ || snapshot_.size() != n;
         bool forces_changed = false;
+        bool materials_changed = false, materials_default = true;
+        for (size_t i = 0; i < n; ++i) {
+            const rigid_body::RigidBody& a = entities[i].body;
+            if (a.friction >= 0.0f || a.restitution != 0.0f) materials_default = false;
+            if (i < snapshot_.size() && (a.friction != snapshot_[i].body.friction || a.restitution != snapshot_[i].body.restitution))
+                materials_changed = true;
+        }
         for (size_t i = 0; i < n && !bodies_changed; ++i) {
             rigid_body::RigidBody a = entities[i].body, b = snapshot_[i].body;
             if (!(a.force == b.force) || !(a.torque == b.torque)) forces_changed = true;
@@ -280,6 +297,19 @@ class PhysicsState {  // physics.rs:25-31
             forces_changed = true;
             con_snapshot_.clear();
             uploaded_ = true;
+            materials_uploaded_ = false;  // phys_set_bodies reset them
+        }
+        // materials: never sent while every body has the defaults (the world then runs its plain solver kernels)
+        // (sent when some body is off the defaults, or to take an earlier upload back; then whenever something changed)
+        if (n && (!materials_default || materials_uploaded_) && (bodies_changed || materials_changed || !materials_uploaded_)) {
+            std::vector<float> fr(n), re(n);
+            for (size_t i = 0; i < n; ++i) {
+                const rigid_body::RigidBody& b = entities[i].body;
+                fr[i] = b.friction >= 0.0f ? b.friction : default_friction_;
+                re[i] = b.restitution;
+            }
+            check(phys_set_body_materials(w_, n, fr.data(), re.data()));
+            materials_uploaded_ = true;
         }
         if (forces_changed && n) {
             std::vector<float> f(3 * n), t(3 * n);

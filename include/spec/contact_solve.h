@@ -142,6 +142,33 @@ PHYS_HD float contact_bias(float depth, const solve_params_t* sp) {
     return bias;
 }
 
+/* ---- materials: friction and restitution per body, static collider and ground plane.
+ * A manifold's friction is the geometric mean of its two sides' (as in Box2D), made so that combining a value with
+ * itself gives it back bit for bit: the product of two floats is exact in double, and the correctly rounded root of an
+ * exact square is exact. A world whose materials all carry the configured friction therefore solves with exactly that
+ * number. The root is taken once per manifold where the rows are built, never in the solve. */
+PHYS_HD float material_friction(float fa, float fb) { return (float)det_sqrtd((double)fa * (double)fb); }
+/* ... its restitution the larger of the two */
+PHYS_HD float material_restitution(float ea, float eb) { return det_maxf(ea, eb); }
+
+/* approach velocity of a contact point along the normal, body B minus body A, from the velocities the solve starts
+ * with: n . ((vB + wB x rB) - (vA + wA x rA)). The caller passes zeros for a body B that does not move (ground, statics). */
+PHYS_HD float contact_normal_velocity(v3 n, v3 vA, v3 wA, v3 rA, v3 vB, v3 wB, v3 rB) {
+    const v3 pa = v3_add(vA, v3_cross(wA, rA));
+    const v3 pb = v3_add(vB, v3_cross(wB, rB));
+    return v3_dot(n, v3_sub(pb, pa));
+}
+
+/* velocity the normal row of a point asks for, with restitution e. The point bounces iff e > 0, it approaches faster
+ * than `threshold`, and it touches within this update (a speculative point must close its gap: depth - vn dt >= 0, which
+ * always holds for depth >= 0). A bouncing point asks for the larger of push-out and rebound; every other point for
+ * contact_bias(depth), so e == 0 gives that function's bits. */
+PHYS_HD float contact_bias_restitution(float depth, float vn, float e, float threshold, const solve_params_t* sp) {
+    const float bias = contact_bias(depth, sp);
+    if (e > 0.0f && vn < -threshold && depth - vn * sp->dt >= 0.0f) return det_maxf(bias, -e * vn);
+    return bias;
+}
+
 /* build the solver rows of one manifold. xB / invMB / IB are ignored when has_b == 0. */
 PHYS_HD void solver_prep(const manifold_t* m, int has_b, v3 xA, v3 xB, float invMA, const m33* IA, float invMB,
                          const m33* IB, const solve_params_t* sp, solver_manifold_t* out) {

@@ -186,6 +186,11 @@ PROTOTYPES = {
     "phys_spherecast_device_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "phys_overlap_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p, f32p, u32p, u16p, C.c_uint64, u64p, u32p]),
+    "phys_set_body_materials": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p]),
+    "phys_get_body_materials": (C.c_int32, [C.c_void_p, f32p, f32p]),
+    "phys_set_static_materials": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p]),
+    "phys_set_ground_material": (C.c_int32, [C.c_void_p, C.c_float, C.c_float]),
+    "phys_set_restitution_threshold": (C.c_int32, [C.c_void_p, C.c_float]),
     "phys_get_static_stats": (C.c_int32, [C.c_void_p, u64p, u64p, u64p]),
     "phys_profile_enable": (C.c_int32, [C.c_void_p, C.c_int32]),
     "phys_profile_get": (C.c_int32, [C.c_void_p, C.POINTER(PhysProfile)]),

@@ -222,7 +222,7 @@ int32_t phys_destroy(phys_world* w) {
                            &w->inv_inertia, &w->half_extent, &w->aabb, &w->cg_x, &w->cg_r, &w->cg_p, &w->cg_ap,
                            &w->cg_rhs, &w->cg_c, &w->cg_scratch, &w->cg_jl, &w->geo, &w->man_geo_prev, &w->man_imp, &w->man_imp_prev, &w->man_geo, &w->row_n,
                            &w->row_pt, &w->row_tb, &w->row_acc, &w->row_all, &w->flow_vel, &w->sorted_box, &w->slot_box, &w->rc_records, &w->rc_in, &w->rc_out, &w->qr_in,
-                           &w->st_geo, &w->st_rc, &w->st_box};
+                           &w->st_geo, &w->st_rc, &w->st_box, &w->mat, &w->st_mat};
     for (auto* b : fb) b->free();
     DevBuf<uint32_t>* ub[] = {&w->shape, &w->global_id, &w->cg_status, &w->bucket_of, &w->bucket_count,
                               &w->bucket_start, &w->bucket_cursor, &w->sorted_ids, &w->slot_ids, &w->grid_ovf, &w->scan_block_sums, &w->pairs,
@@ -264,6 +264,7 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     PHYS_HIP_TRY(w->half_extent.resize(3 * nt)); PHYS_HIP_TRY(w->aabb.resize(6 * nt)); PHYS_HIP_TRY(w->shape.resize(nt));
     PHYS_HIP_TRY(w->global_id.resize(nt));
     PHYS_HIP_TRY(w->filt.resize(2 * nt));
+    PHYS_HIP_TRY(w->mat.resize(2 * nt));
     if ((w->cfg.flags & PHYS_FLAG_COLLISIONS) && !(w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY)) PHYS_HIP_TRY(w->geo.resize(16 * nt));
     w->n = nt;
     w->n_owned = n;
@@ -276,6 +277,7 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     w->hint = StepHint();
     w->static_pairs_sized = false;  // static.hip: the next update measures its (body, static) pairs
     w->body_filters_set = false;    // every body slot gets the default filter below
+    w->body_materials_set = false;  // ... and the default material
     for (int k = 0; k < phys_world::kSnapRing; ++k) w->snap_pending[k] = false;  // the stream was synchronised above
     if (n == 0) return PHYS_OK;
 
@@ -283,6 +285,8 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     std::vector<float> h_pos(3 * nt, 0.0f), h_rot(4 * nt), h_vel(8 * nt), h_inv(9 * nt, 0.0f), h_diag(4 * nt, 0.0f), h_he(3 * nt, 0.0f);
     std::vector<uint32_t> h_shape(nt, PHYS_SHAPE_NONE), h_gid(nt, 0xFFFFFFFFu), h_filt(2 * nt, 0u);
     for (uint64_t i = 0; i < nt; ++i) h_filt[2 * i] = kFilterDefaultWord;
+    std::vector<float> h_mat(2 * nt, 0.0f);
+    for (uint64_t i = 0; i < nt; ++i) h_mat[2 * i] = w->cfg.friction;
     std::memcpy(h_pos.data(), pos, 12 * n);
     w->singular_inertia = false;
     w->all_diag_inertia = true;
@@ -332,6 +336,7 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     PHYS_HIP_TRY(hipMemcpyAsync(w->shape.p, h_shape.data(), 4 * nt, hipMemcpyHostToDevice, s));
     PHYS_HIP_TRY(hipMemcpyAsync(w->global_id.p, h_gid.data(), 4 * nt, hipMemcpyHostToDevice, s));
     PHYS_HIP_TRY(hipMemcpyAsync(w->filt.p, h_filt.data(), 8 * nt, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->mat.p, h_mat.data(), 8 * nt, hipMemcpyHostToDevice, s));
     if (!w->all_diag_inertia) w->uniform_inertia = false;
     PHYS_HIP_TRY(hipStreamSynchronize(s));  // staging vectors die here
     if (w->cfg.flags & PHYS_FLAG_COLLISIONS) {
@@ -697,6 +702,7 @@ int32_t phys_set_static_bodies(phys_world* w, uint64_t n, const float* pos, cons
     w->color_epoch = 0;
     w->static_pairs_seen = 0;
     w->static_filters_set = false;  // the new set starts with the default filters (static_set)
+    w->static_materials_set = false;  // ... and the default materials
     return static_set(w, n, pos, rot, shape_type, half_extent);
 }
 
@@ -753,6 +759,79 @@ int32_t phys_set_ground_filter(phys_world* w, uint16_t category, uint16_t mask) 
     ENTER(w);
     w->ground_filt = (uint32_t)category | ((uint32_t)mask << 16);  // read by the launches of the next update
     w->ground_filter_set = true;
+    return PHYS_OK;
+}
+
+// ---- materials ----
+// {friction, restitution} per item; a NULL array gives that field its default. false: a value out of range
+static bool pack_materials(uint64_t n, const float* friction, const float* restitution, float default_friction, std::vector<float>& out) {
+    out.resize(2 * n);
+    for (uint64_t k = 0; k < n; ++k) {
+        const float f = friction ? friction[k] : default_friction, e = restitution ? restitution[k] : 0.0f;
+        if (!std::isfinite(f) || f < 0.0f || !(e >= 0.0f && e <= 1.0f)) return false;
+        out[2 * k] = f; out[2 * k + 1] = e;
+    }
+    return true;
+}
+static const char* const kMaterialRange = "a friction must be finite and >= 0, a restitution in [0, 1]";
+// materials do not cross slab cuts (the halo record has no room for them): a sharded world refuses the calls
+#define PHYS_NO_MATERIALS_WHEN_SHARDED(w) \
+    do { if ((w)->cfg.max_ghosts > 0) return fail(PHYS_ERR_UNSUPPORTED, "materials are not supported in a world with max_ghosts > 0"); } while (0)
+
+int32_t phys_set_body_materials(phys_world* w, uint64_t n, const float* friction, const float* restitution) {
+    ENTER(w);
+    PHYS_NO_MATERIALS_WHEN_SHARDED(w);
+    if (n != w->n_owned) return fail(PHYS_ERR_INVALID_ARG, "phys_set_body_materials: n must equal the body count");
+    std::vector<float> h;
+    if (!pack_materials(n, friction, restitution, w->cfg.friction, h)) return fail(PHYS_ERR_INVALID_ARG, kMaterialRange);
+    // ordered behind the updates already enqueued: they keep the materials they were enqueued with
+    if (n) PHYS_HIP_TRY(hipMemcpyAsync(w->mat.p, h.data(), 8 * n, hipMemcpyHostToDevice, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // the staging vector dies here
+    w->body_materials_set = true;
+    return PHYS_OK;
+}
+
+int32_t phys_get_body_materials(phys_world* w, float* friction_out, float* restitution_out) {
+    ENTER(w);
+    PHYS_NO_MATERIALS_WHEN_SHARDED(w);
+    const uint64_t n = w->n_owned;
+    std::vector<float> h(2 * n);
+    if (n) PHYS_HIP_TRY(hipMemcpyAsync(h.data(), w->mat.p, 8 * n, hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    for (uint64_t k = 0; k < n; ++k) {
+        if (friction_out) friction_out[k] = h[2 * k];
+        if (restitution_out) restitution_out[k] = h[2 * k + 1];
+    }
+    return PHYS_OK;
+}
+
+int32_t phys_set_static_materials(phys_world* w, uint64_t n, const float* friction, const float* restitution) {
+    ENTER(w);
+    PHYS_NO_MATERIALS_WHEN_SHARDED(w);
+    if (n != w->n_static) return fail(PHYS_ERR_INVALID_ARG, "phys_set_static_materials: n must equal the static collider count");
+    std::vector<float> h;
+    if (!pack_materials(n, friction, restitution, w->cfg.friction, h)) return fail(PHYS_ERR_INVALID_ARG, kMaterialRange);
+    if (n) PHYS_HIP_TRY(hipMemcpyAsync(w->st_mat.p, h.data(), 8 * n, hipMemcpyHostToDevice, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    w->static_materials_set = true;
+    return PHYS_OK;
+}
+
+int32_t phys_set_ground_material(phys_world* w, float friction, float restitution) {
+    ENTER(w);
+    PHYS_NO_MATERIALS_WHEN_SHARDED(w);
+    std::vector<float> h;
+    if (!pack_materials(1, &friction, &restitution, 0.0f, h)) return fail(PHYS_ERR_INVALID_ARG, kMaterialRange);
+    w->ground_mat[0] = friction; w->ground_mat[1] = restitution;  // read by the launches of the next update
+    w->ground_mat_set = true;
+    return PHYS_OK;
+}
+
+int32_t phys_set_restitution_threshold(phys_world* w, float v) {
+    ENTER(w);
+    PHYS_NO_MATERIALS_WHEN_SHARDED(w);
+    if (!std::isfinite(v) || v < 0.0f) return fail(PHYS_ERR_INVALID_ARG, "phys_set_restitution_threshold: v must be finite and >= 0");
+    w->restitution_threshold = v;  // read by the launches of the next update
     return PHYS_OK;
 }
 

@@ -379,6 +379,10 @@ void launch_cluster_sort(phys_world* w, unsigned blocks, StepCounters* snap_out)
 //     planes 12-13 rows whose body B belongs to ANOTHER cluster: {position of B, 1/m} {inverse inertia diagonal of B}
 //                  (what never changes during a solve; gathering it by body id after the row has arrived was a second
 //                  dependent round trip to memory in the chain of every colour step: 2.08 -> ~1.2 ms on C5)
+// Material worlds (k_rows_build's MAT instance) pack planes 0 differently - no plane more, no load more:
+//     plane 0      hdr {body a, body b, the manifold's friction mu (float bits), tickets | point count}
+//                  the count sits in ticket bits that are never set: bits 6-7 (its low two bits; a rank is below 64) and
+//                  bit 15 (its bit 2; a degree is at most 64)
 // and everything else solver_prep would have stored (the lever arms) is remade from the contact point and the two body
 // POSITIONS, which live in LDS beside the velocities (solve_manifold_geo: same operations, same bits;
 // tests/test_collide_kat.py holds the three drivers against each other). So k_rows_build reads nothing of the bodies
@@ -393,7 +397,7 @@ constexpr int kClusterThreads = 256;
 #define PHYS_POLL_SLEEP 8
 #endif
 constexpr int kPollSleep = PHYS_POLL_SLEEP;
-template <bool DIAG, bool GUARDED>
+template <bool DIAG, bool GUARDED, bool MAT>
 __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kClusterPerCuFull) void k_solve_cluster(StepCounters* ctr, uint32_t iterations, uint32_t epoch,
                                                                   ClusterRowArrays rows, float friction,
                                                                   const float* __restrict__ inv_inertia, uint32_t inertia_stride,
@@ -537,7 +541,10 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
             // the lane's row is never of an earlier colour of this iteration (it would have been solved then)
             while (have && lit == it && d < seg_hi) {
                 const uint32_t d_row = d;
-                const uint4 h = make_uint4(__float_as_uint(hraw.x), __float_as_uint(hraw.y), __float_as_uint(hraw.z), __float_as_uint(hraw.w));
+                // MAT: hdr.z is the row's friction, the point count rides in spare ticket bits (layout above)
+                const uint32_t hw = __float_as_uint(hraw.w);
+                const uint4 h = MAT ? make_uint4(__float_as_uint(hraw.x), __float_as_uint(hraw.y), ((hw >> 6) & 3u) | ((hw >> 13) & 4u), hw & 0xFFFF7F3Fu)
+                                    : make_uint4(__float_as_uint(hraw.x), __float_as_uint(hraw.y), __float_as_uint(hraw.z), hw);
                 const uint32_t info = __float_as_uint(nn.w);
                 // slot (13 bits) | publish (1) | mode (2) per side. publish: the NEXT update of this (shared, own) body is
                 // made by another workgroup, so this update must reach the granules; otherwise it stays in LDS
@@ -646,7 +653,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                     ctr->debug[7] = (col & 0xFFu) | ((it & 0xFFu) << 8);
                 }
                 if (!dead) {
-                    solve_manifold_geo(&gm, it == 0u, (warm_sweep != 0u && it == 0u) ? 1 : 0, friction, xA, ima, &IA, xB, imb, &IB, &vA, &wA, &vB, &wB);
+                    solve_manifold_geo(&gm, it == 0u, (warm_sweep != 0u && it == 0u) ? 1 : 0, MAT ? hraw.z : friction, xA, ima, &IA, xB, imb, &IB, &vA, &wA, &vB, &wB);
                     // ---- write back
                     if (modeA == 0u || modeA == 1u) {
                         s_body[4 * slotA] = make_float4(vA.x, vA.y, vA.z, __uint_as_float(etag | (tA + 1u)));
@@ -714,7 +721,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
 }
 
 void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float friction, const float* inertia, uint32_t stride,
-                          bool diag, long long timeout_ticks) {
+                          bool diag, long long timeout_ticks, bool materials) {
     const uint32_t warm_sweep = w->warm ? 1u : 0u;
     const uint32_t sweeps = w->cfg.solver_iterations + warm_sweep;
     ClusterRowArrays rows;
@@ -734,10 +741,12 @@ void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float fric
         // lock (two host threads), the current device being the world's (ENTER of the ABI call) - ADVICE r2
         static bool attr_set[64] = {};
         if (!attr_set[w->device & 63]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_cluster<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_cluster<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_cluster<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_cluster<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            hipError_t e = hipSuccess;
+            auto allow = [&](const void* f) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); };
+            allow(reinterpret_cast<const void*>(&k_solve_cluster<true, true, false>)); allow(reinterpret_cast<const void*>(&k_solve_cluster<true, false, false>));
+            allow(reinterpret_cast<const void*>(&k_solve_cluster<false, true, false>)); allow(reinterpret_cast<const void*>(&k_solve_cluster<false, false, false>));
+            allow(reinterpret_cast<const void*>(&k_solve_cluster<true, true, true>)); allow(reinterpret_cast<const void*>(&k_solve_cluster<true, false, true>));
+            allow(reinterpret_cast<const void*>(&k_solve_cluster<false, true, true>)); allow(reinterpret_cast<const void*>(&k_solve_cluster<false, false, true>));
             if (e != hipSuccess) { (void)hipGetLastError(); set_error(std::string("hipFuncSetAttribute(k_solve_cluster): ") + hipGetErrorString(e)); }
             else attr_set[w->device & 63] = true;
         }
@@ -752,19 +761,19 @@ void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float fric
     // 1M cubes (tools/guard_cost.py) - is skipped). The guarded start is the default since round 3: a drop-in behind a render loop shares its GPU
     // with the renderer, and the unguarded launch's failure mode there is a 3 s spin.
     const bool guarded = !gpu_is_exclusive(w);
-    dispatch_bool(diag, [&](auto diag_t) { dispatch_bool(guarded, [&](auto guarded_t) {
-        constexpr bool D = decltype(diag_t)::value, G = decltype(guarded_t)::value;
+    dispatch_bool(diag, [&](auto diag_t) { dispatch_bool(guarded, [&](auto guarded_t) { dispatch_bool(materials, [&](auto mat_t) {
+        constexpr bool D = decltype(diag_t)::value, G = decltype(guarded_t)::value, MT = decltype(mat_t)::value;
         const uint32_t kAttempts = G ? 2u : 1u;
         for (uint32_t attempt = 0; attempt < kAttempts; ++attempt) {
             const uint32_t last = attempt + 1 == kAttempts ? 1u : 0u;
             // 100 MHz ticks: 0.5 ms, then 20 ms for the workgroups to come in (alone on the device they need ~10 us); < 0: no count
             const long long arrive_ticks = !G ? -1ll : (attempt == 0 ? 50000ll : 2000000ll);
-            hipLaunchKernelGGL((k_solve_cluster<D, G>), g, b, lds, w->stream, w->counters.p, sweeps, w->flow_epoch, rows, friction,
+            hipLaunchKernelGGL((k_solve_cluster<D, G, MT>), g, b, lds, w->stream, w->counters.p, sweeps, w->flow_epoch, rows, friction,
                                inertia, stride, w->vel.p, w->pos.p, w->flow_vel.p, (uint32_t)w->n, w->cluster_body.p,
                                w->body_shared.p, w->seg_start.p, w->cluster_slots, timeout_ticks, attempt, last, arrive_ticks,
                                warm_sweep, w->row_src.p, w->warm ? w->man_imp.p : (float*)nullptr);
         }
-    }); });
+    }); }); });
 }
 
 }  // namespace phys

@@ -168,6 +168,21 @@ struct QueryFilters {
 template <typename T>
 __device__ __forceinline__ T filter_arg(T f) { return f; }
 
+// ---- materials ---------------------------------------------------------------------------------
+// One {friction, restitution} per body slot and per static collider: one 8-byte load per side of a manifold, made by
+// k_rows_build alone. The ground's material and the restitution threshold are kernel arguments.
+struct RowMaterials {
+    const float2* body;  // per body slot
+    const float2* st;    // per static collider (null without statics)
+    float2 ground;
+    float threshold;     // approach speed below which nothing bounces
+};
+// the one material argument of k_rows_build's material instance (a parameter pack that is empty in the plain one: see filter_arg)
+template <typename T>
+__device__ __forceinline__ T material_arg(T m) { return m; }
+// a material call was made since the reset of what it set: the solver runs its material instances
+inline bool materials_active(const phys_world* w) { return w->body_materials_set || w->static_materials_set || w->ground_mat_set; }
+
 // ---- uniform grid of the broad phase: cell -> bucket -----------------------------------------------------------------
 // The table has 2^bits buckets, bits = bx + by + bz split over the axes in proportion to the scene's extent (a tower 16
 // cells wide and 980 high gets x 4, y 10, z 5 instead of 7 + 7 + 7: with equal bits its 128-cell axis wrapped 7.6 times
@@ -271,7 +286,7 @@ void launch_exclusive_scan(phys_world* w, uint32_t* in, uint32_t count, uint32_t
 bool scan_is_one_launch(uint32_t count);  // ... in which case zero_in leaves the counters zeroed behind the scan
 bool cluster_plan_dynamic(phys_world* w);  // cluster.hip: clusters / slots of this update from the hint (dynamic clusters)
 void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float friction, const float* inertia, uint32_t stride,
-                          bool diag, long long timeout_ticks);
+                          bool diag, long long timeout_ticks, bool materials /* the rows carry their own friction */);
 
 // static.hip: the static set (arguments checked by the caller), the per-update (body, static) pairs, and what k_narrowphase
 // takes of them (cap 0 / null pointers: no static colliders)

@@ -11,7 +11,7 @@
 // dword loads - the row solve is a long dependent chain at one wave per SIMD, and the number of memory
 // instructions in front of it is what its latency is made of:
 //     row_hdr uint4  [d]              {body a, body b, point count, update tickets (k_solve_flow)}
-//     row_n   float4 [d]              {normal xyz, 0}
+//     row_n   float4 [d]              {normal xyz, 0}; material worlds: {normal xyz, the manifold's friction mu} (k_rows_build)
 //     row_pt  float4 [(2k)*cap + d]   {rA xyz, normal mass}          point k = 0..3
 //                    [(2k+1)*cap + d] {rB xyz, tangent mass 0}
 //     row_tb  float4 [d]              {tangent mass 1, bias} of points 0 and 1;  [cap + d]: points 2 and 3
@@ -51,7 +51,13 @@ struct RowArrays {
     uint64_t cap;
 };
 
-template <bool DIAG>
+// MAT: the material instance. It combines the two sides' materials into the manifold's friction `mu`,
+// which rides in the row (prepared rows: row_n.w, which is the cluster info and 0 outside cluster steps; compact rows: the
+// whole of hdr.z, the point count moving into spare ticket bits - see cluster.hip), and gives a point that bounces the
+// restitution bias of contact_solve.h. Only a row whose restitution is not zero reads more of its bodies than before.
+// The material arguments travel as a parameter pack that is empty in the plain instance, which keeps its kernel
+// arguments and its instructions (the technique of section 13).
+template <bool DIAG, bool MAT, typename... Mat>
 __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ ctr, RowArrays rows, solve_params_t sp,
                                                     const uint32_t* __restrict__ row_src,
                                                     const float* __restrict__ man_geo /* 128-byte records */,
@@ -64,7 +70,10 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
                                                     ColorTableJob table, const uint32_t* __restrict__ cluster_slot,
                                                     const uint32_t* __restrict__ body_shared,
                                                     uint32_t cluster_slots /* 0: not a cluster-solver step */, uint32_t cluster_count,
-                                                    WarmJob warm) {
+                                                    WarmJob warm, Mat... mat /* MAT: one RowMaterials */) {
+    static_assert(sizeof...(Mat) == (MAT ? 1u : 0u), "one RowMaterials argument exactly in the material instance");
+    RowMaterials mt{};
+    if constexpr (MAT) mt = material_arg(mat...);
     if (ctr->overflow) return;  // never solve a truncated set; phys_sync / phys_get_stats report it
     const uint32_t M = ctr->n_manifolds;
     const uint64_t cap = rows.cap;
@@ -107,6 +116,10 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
         if (table.tab && (table.all || __float_as_uint(r0.w) == 0u)) color_table_insert(table, a, b, m, ctr);
         // a kept colour came with the record; a new manifold's was made by the colouring rounds since
         const uint32_t color_m = __float_as_uint(r0.w) != 0u ? __float_as_uint(r0.w) - 1u : man_color[m];
+        // Ticket word: rank A (bits 0-5) | degree A (8-14) | rank B (16-21) | degree B (24-30). A rank is below PHYS_MAX_COLORS and
+        // a degree at most PHYS_MAX_COLORS, so bits 6, 7 and 15 are never set: they are RESERVED for the point count of the
+        // compact rows of material worlds (below; cluster.hip). A change of this format must keep them clear.
+        static_assert(PHYS_MAX_COLORS <= 64, "ticket bits 6, 7 and 15 hold the point count of material compact rows");
         uint32_t ticket = 0;
         if (flow) {
             // the colours in use at a body are exactly the colours of its manifolds (all distinct), so the rank of
@@ -120,7 +133,44 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
             }
             if (flow == 2 && d == 0) ticket += 1;  // fault injection (PHYS_DEBUG_FLOW_STALL): row 0 waits for a turn that never comes
         }
-        rows.hdr[d] = make_uint4(a, b, (uint32_t)g.count, ticket);
+        // materials: the manifold's friction and restitution; a row that bounces needs the velocities the solve starts from
+        float mu = 0.0f, rest = 0.0f;
+        v3 m_xA = v3_make(0.0f, 0.0f, 0.0f), m_vA = m_xA, m_wA = m_xA, m_xB = m_xA, m_vB = m_xA, m_wB = m_xA;
+        if constexpr (MAT) {
+            const float2 ma = mt.body[a];
+            // (three assignments, not one conditional expression: that selects between ADDRESSES, and the argument struct
+            // went to scratch memory for it)
+            float2 mb = mt.ground;
+            if (has_b) mb = mt.body[b];
+            else if (b != PHYS_GROUND_ID) mb = mt.st[b & ~PHYS_STATIC_ID_BIT];
+            mu = material_friction(ma.x, mb.x);
+            rest = material_restitution(ma.y, mb.y);
+            if (rest > 0.0f) {
+                const BodyVel A = ld_vel(vel, a);
+                m_xA = ld3(pos, a); m_vA = A.v; m_wA = A.w;
+                if (has_b) { const BodyVel B = ld_vel(vel, b); m_xB = ld3(pos, b); m_vB = B.v; m_wB = B.w; }
+            }
+        }
+        // bias of point k (contact_solve.h); rB = 0 for a body B that does not move, as solver_prep has it
+        auto point_bias = [&](v3 pt, float depth) -> float {
+            if constexpr (MAT) {
+                if (rest > 0.0f) {
+                    const v3 rA = v3_sub(pt, m_xA);
+                    const v3 rB = has_b ? v3_sub(pt, m_xB) : v3_make(0.0f, 0.0f, 0.0f);
+                    const float vn = contact_normal_velocity(g.normal, m_vA, m_wA, rA, m_vB, m_wB, rB);
+                    return contact_bias_restitution(depth, vn, rest, mt.threshold, &sp);
+                }
+            }
+            return contact_bias(depth, &sp);
+        };
+        if constexpr (MAT) {
+            if (cluster_slots)  // compact rows: mu takes hdr.z; the count goes to ticket bits that are never set (rank < 64, degree <= 64)
+                rows.hdr[d] = make_uint4(a, b, __float_as_uint(mu), ticket | (((uint32_t)g.count & 3u) << 6) | (((uint32_t)g.count >> 2) << 15));
+            else
+                rows.hdr[d] = make_uint4(a, b, (uint32_t)g.count, ticket);
+        } else {
+            rows.hdr[d] = make_uint4(a, b, (uint32_t)g.count, ticket);
+        }
         uint32_t info = 0;
         if (cluster_slots) {
             // cluster solver (cluster.hip): where each side's velocity lives. Per side: slot (13 bits) | publish (1) |
@@ -149,14 +199,15 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
             const uint32_t ib = has_b ? side(b, hb) : (3u << 14);
             info |= ib << 16;
         }
-        rows.n[d] = make_float4(g.normal.x, g.normal.y, g.normal.z, __uint_as_float(info));
+        if constexpr (MAT) rows.n[d] = make_float4(g.normal.x, g.normal.y, g.normal.z, cluster_slots ? __uint_as_float(info) : mu);
+        else rows.n[d] = make_float4(g.normal.x, g.normal.y, g.normal.z, __uint_as_float(info));
         if (cluster_slots) {
             // compact rows of the cluster solver (cluster.hip): the contact points themselves and the bias; lever arms and
             // row masses are remade there from the body positions it keeps in LDS. Nothing of the bodies is read here.
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (k < g.count)
-                    rows.all[(size_t)(2 + k) * cap + d] = make_float4(g.pt[k].x, g.pt[k].y, g.pt[k].z, contact_bias(g.depth[k], &sp));
+                    rows.all[(size_t)(2 + k) * cap + d] = make_float4(g.pt[k].x, g.pt[k].y, g.pt[k].z, MAT ? point_bias(g.pt[k], g.depth[k]) : contact_bias(g.depth[k], &sp));
             if (warm.man_prev) {  // the starting impulses, packed like the solver packs them (planes 6-8; read in sweep 0)
                 rows.all[(size_t)6 * cap + d] = make_float4(w_pn[0], w_pt0[0], w_pt1[0], w_pn[1]);
                 rows.all[(size_t)7 * cap + d] = make_float4(w_pt0[1], w_pt1[1], w_pn[2], w_pt0[2]);
@@ -188,6 +239,11 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
         if (has_b) { IB = ld_inertia<DIAG>(inv_inertia, b * inertia_stride); imb = vel[8 * (size_t)b + 3]; xB = ld3(pos, b); }
         solver_manifold_t sm;
         solver_prep(&g, has_b, ld3(pos, a), xB, vel[8 * (size_t)a + 3], &IA, imb, &IB, &sp, &sm);
+        if constexpr (MAT) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < sm.count) sm.row[k].bias = point_bias(g.pt[k], g.depth[k]);
+        }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (k < sm.count) {
@@ -216,8 +272,9 @@ struct RowRegs {
 // EAGER: every plane of the row is fetched at once, whatever the point count turns out to be (planes beyond it hold
 // stale but readable data that is then ignored): no load waits for the header. For the per-colour kernel of large
 // scenes, where a launch is one wave per SIMD and a second dependent round trip to memory is ~1.5 us of every launch.
+// Returns row_n.w: the manifold's friction where the material instance of k_rows_build wrote the row (0 in plain rows).
 template <bool ACC, bool EAGER = false>
-__device__ __forceinline__ void load_row(RowRegs& R, uint32_t d, const RowArrays& rows) {
+__device__ __forceinline__ float load_row(RowRegs& R, uint32_t d, const RowArrays& rows) {
     const uint64_t cap = rows.cap;
     float4 e_p0[4], e_p1[4], e_acc[4], e_t23;
     if (EAGER) {
@@ -263,17 +320,19 @@ __device__ __forceinline__ void load_row(RowRegs& R, uint32_t d, const RowArrays
             c.pn = 0.0f; c.pt[0] = 0.0f; c.pt[1] = 0.0f;
         }
     }
+    return nn.w;
 }
 
 // gather the two bodies, solve_manifold, write velocities and accumulated impulses back
-template <bool DIAG, bool EAGER = false>
+// MAT: the friction is the row's own, not the kernel argument
+template <bool DIAG, bool EAGER = false, bool MAT = false>
 __device__ __forceinline__ void solve_row(uint32_t d, const RowArrays& rows, float friction,
                                           const float* __restrict__ inv_inertia,
                                           uint32_t inertia_stride /* 0: one tensor shared by every body */,
                                           float* __restrict__ vel, int apply_only /* sweep 0 of a warm-started solve */,
                                           int last /* the solve's last sweep: the impulses are remembered */, const WarmJob& wj) {
     RowRegs R;
-    load_row<true, EAGER>(R, d, rows);
+    const float row_mu = load_row<true, EAGER>(R, d, rows);
     solver_manifold_t& sm = R.sm;
     const uint32_t a = R.a, b = R.b;
     const m33 IA = ld_inertia<DIAG>(inv_inertia, a * inertia_stride);
@@ -289,7 +348,7 @@ __device__ __forceinline__ void solve_row(uint32_t d, const RowArrays& rows, flo
     if (sm.has_b) { IB = ld_inertia<DIAG>(inv_inertia, b * inertia_stride); B = ld_vel(vel, b); imb = B.inv_mass; vB = B.v; wB = B.w; }
     // rows made on the way: these kernels are throughput-bound and want the registers (k_solve_flow makes them all
     // beforehand, while it waits; same arithmetic)
-    solve_manifold_lazy(&sm, friction, ima, &IA, imb, &IB, &vA, &wA, &vB, &wB, apply_only);
+    solve_manifold_lazy(&sm, MAT ? row_mu : friction, ima, &IA, imb, &IB, &vA, &wA, &vB, &wB, apply_only);
     A.v = vA; A.w = wA;
     st_vel(vel, a, A);
     if (sm.has_b) { B.v = vB; B.w = wB; st_vel(vel, b, B); }
@@ -330,7 +389,7 @@ struct XcdTiles {
 };
 
 // one colour of one iteration; the row range comes from the device-side colour table
-template <bool DIAG>
+template <bool DIAG, bool MAT>
 __global__ __launch_bounds__(256) void k_solve_color(const StepCounters* __restrict__ ctr, uint32_t col, RowArrays rows,
                                                      float friction, const float* __restrict__ inv_inertia,
                                                      uint32_t inertia_stride, float* __restrict__ vel, int apply_only, int last, WarmJob wj) {
@@ -343,7 +402,7 @@ __global__ __launch_bounds__(256) void k_solve_color(const StepCounters* __restr
     // 5.6 MB of gathered records when tiles were dealt in plain blockIdx order). Speed only: any mapping is correct.
     for (XcdTiles t(end - start, blockDim.x); t.valid(); t.next()) {
         const uint32_t d = start + t.tile * blockDim.x + threadIdx.x;
-        if (d < end) solve_row<DIAG, true>(d, rows, friction, inv_inertia, inertia_stride, vel, apply_only, last, wj);
+        if (d < end) solve_row<DIAG, true, MAT>(d, rows, friction, inv_inertia, inertia_stride, vel, apply_only, last, wj);
     }
 }
 
@@ -353,7 +412,7 @@ __global__ __launch_bounds__(256) void k_solve_color(const StepCounters* __restr
 // colour, without paying a ~8 us launch for a few hundred manifolds. `first` is a host HINT (the small
 // colours of the previous step); any value gives the same result, only the speed changes.
 constexpr int kTailThreads = 512;  // 2 waves per SIMD: the row solve needs >128 VGPRs, 1024 threads would spill
-template <bool DIAG>
+template <bool DIAG, bool MAT>
 __global__ __launch_bounds__(kTailThreads) void k_solve_tail(const StepCounters* __restrict__ ctr, uint32_t first, RowArrays rows,
                                                             float friction, const float* __restrict__ inv_inertia,
                                                             uint32_t inertia_stride, float* __restrict__ vel, int apply_only,
@@ -369,7 +428,7 @@ __global__ __launch_bounds__(kTailThreads) void k_solve_tail(const StepCounters*
     for (uint32_t col = first; col < last; ++col) {
         const uint32_t start = s_start[col], end = s_start[col + 1];
         for (uint32_t d = start + threadIdx.x; d < end; d += kTailThreads)
-            solve_row<DIAG>(d, rows, friction, inv_inertia, inertia_stride, vel, apply_only, last_sweep, wj);
+            solve_row<DIAG, false, MAT>(d, rows, friction, inv_inertia, inertia_stride, vel, apply_only, last_sweep, wj);
         __threadfence_block();
         __syncthreads();
     }
@@ -431,7 +490,7 @@ constexpr uint64_t kFlowQuadMaxManifolds = 200000;
 struct FlowRowRaw { uint4 h; float4 nn, t01, t23, p[8]; };
 struct FlowBodies { m33 IA, IB; float ima, imb, massA, massB; v3 vA, wA, vB, wB; };
 
-template <bool DIAG>
+template <bool DIAG, bool MAT>
 __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ ctr, uint32_t iterations, uint32_t epoch,
                                                     RowArrays rows, float friction,
                                                     const float* __restrict__ inv_inertia, uint32_t inertia_stride,
@@ -607,7 +666,8 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
                     }
                 }
                 if (!needA && !needB && !needAcc) {
-                    solve_manifold(&R.sm, &J, friction, &vA, &wA, &vB, &wB, apply_only ? 1 : 0);
+                    if constexpr (MAT) solve_manifold(&R.sm, &J, raw.nn.w, &vA, &wA, &vB, &wB, apply_only ? 1 : 0);  // the row's own friction
+                    else solve_manifold(&R.sm, &J, friction, &vA, &wA, &vB, &wB, apply_only ? 1 : 0);
                     // publish: bodies first (they are what other rows wait for)
                     if (finalA) { BodyVel o; o.v = vA; o.inv_mass = ima; o.w = wA; o.mass = massA; st_vel(vel, R.a, o); }
                     else { st_granule(rv, R.a * 32u, vA, etag | (tA + 1u)); st_granule(rv, R.a * 32u + 16u, wA, etag | (tA + 1u)); }
@@ -790,7 +850,7 @@ __device__ __forceinline__ v3 quad_point_impulses(const QuadLane& s, uint32_t q)
 // The dataflow solver with FOUR LANES PER MANIFOLD (the row core above), for scenes where the hop latency is
 // everything. The granule protocol maps one to one: lane q polls and publishes exactly its own 16-byte granule (v or w
 // of A or B), and the impulse granule of contact point q.
-template <bool DIAG>
+template <bool DIAG, bool MAT>
 __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restrict__ ctr, uint32_t iterations, uint32_t epoch,
                                                          RowArrays rows, float friction,
                                                          const float* __restrict__ inv_inertia, uint32_t inertia_stride,
@@ -830,6 +890,7 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
         QuadLane s;
         uint32_t ticket = 0;
         bool final_update = false;
+        float mu = friction;  // MAT: the row's own
         if (!done) {
             const uint4 h = rows.hdr[d];
             const uint32_t tk = side_a ? h.w : (h.w >> 16);
@@ -839,6 +900,7 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
             const float4 nn = rows.n[d], t01 = rows.tb[d];
             float4 t23 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (h.z > 2) t23 = rows.tb[cap + d];
+            if constexpr (MAT) mu = nn.w;
             quad_lane_setup<DIAG>(s, q, h.x, h.y, h.z, nn, t01, t23, rows.pt + d, cap,
                                   vel, inv_inertia, inertia_stride);
         }
@@ -881,7 +943,7 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
                     s.pn[2] = quad_perm<0xAA>(my_acc.x); s.pt0[2] = quad_perm<0xAA>(my_acc.y); s.pt1[2] = quad_perm<0xAA>(my_acc.z);
                     s.pn[3] = quad_perm<0xFF>(my_acc.x); s.pt0[3] = quad_perm<0xFF>(my_acc.y); s.pt1[3] = quad_perm<0xFF>(my_acc.z);
                 }
-                quad_lane_solve(s, friction, apply_only, side_a);
+                quad_lane_solve(s, mu, apply_only, side_a);
                 if (s.has_body) {
                     if (final_update)
                         reinterpret_cast<float4*>(vel)[2 * (size_t)s.body + (angular ? 1 : 0)] = make_float4(s.x.x, s.x.y, s.x.z, s.keep_w);
@@ -912,7 +974,7 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
 //     waves to overlap memory with arithmetic, and a gather of ONE 16-byte half record per lane.
 // Rows of one colour share no body, so the plain loads / stores of `vel` need no ordering inside a launch.
 constexpr int kQuadRowsPerGroup = 64;
-template <bool DIAG>
+template <bool DIAG, bool MAT>
 __global__ __launch_bounds__(256) void k_solve_color_quad(StepCounters* ctr, uint32_t col, RowArrays rows,
                                                           float friction, const float* __restrict__ inv_inertia,
                                                           uint32_t inertia_stride, float* __restrict__ vel, uint32_t n_bodies,
@@ -965,7 +1027,8 @@ __global__ __launch_bounds__(256) void k_solve_color_quad(StepCounters* ctr, uin
                 }
             }
         }
-        quad_lane_solve(s, friction, apply_only != 0, side_a);  // dead quads carry zeros
+        // dead quads carry zeros (and, MAT, a clean friction: their slot of the tile holds another colour's row or stale memory)
+        quad_lane_solve(s, MAT ? (live ? s_rows[1][r].w : 0.0f) : friction, apply_only != 0, side_a);
         if (live) {
             if (s.has_body)
                 reinterpret_cast<float4*>(vel)[2 * (size_t)s.body + (angular ? 1 : 0)] = make_float4(s.x.x, s.x.y, s.x.z, s.keep_w);
@@ -1054,17 +1117,29 @@ void launch_solver(phys_world* w, float dt) {
         (void)hipMemsetAsync(w->row_acc.p, 0, 16 * cap * sizeof(float), s);
         w->flow_epoch = 1;
     }
-    dispatch_bool(diag, [&](auto diag_t) {  // every kernel below in the DIAG instantiation of this world
-        constexpr bool DIAG = decltype(diag_t)::value;
+    // materials: once a material call was made, the material instances of every kernel below - same
+    // path choice, same launch sizes; they take the friction from the row. With every material at its default they give the
+    // plain instances' bits.
+    const bool materials = materials_active(w);
+    RowMaterials mats{};
+    mats.body = reinterpret_cast<const float2*>(w->mat.p);
+    mats.st = reinterpret_cast<const float2*>(w->st_mat.p);
+    mats.ground = make_float2(w->ground_mat_set ? w->ground_mat[0] : w->cfg.friction, w->ground_mat_set ? w->ground_mat[1] : 0.0f);
+    mats.threshold = w->restitution_threshold;
+    dispatch_bool(diag, [&](auto diag_t) { dispatch_bool(materials, [&](auto mat_t) {  // every kernel below in this world's instantiation
+        constexpr bool DIAG = decltype(diag_t)::value, MAT = decltype(mat_t)::value;
         { PHYS_PROF(w, PHYS_STAGE_ROWS);
-          hipLaunchKernelGGL(k_rows_build<DIAG>, grid_for_count(m_hint), tb, 0, s, w->counters.p, rows, sp, w->row_src.p, w->man_geo.p,
-                             w->pos.p, w->vel.p, inertia, stride, w->man_color.p,
-                             w->color_state.p, flow ? (stall ? 2 : 1) : 0, table, w->cluster_slot.p, w->body_shared.p,
-                             w->cluster_step ? w->cluster_slots : 0u, w->cluster_count, warm); }
+          auto rows_build = [&](auto... mat) {
+              hipLaunchKernelGGL((k_rows_build<DIAG, MAT, decltype(mat)...>), grid_for_count(m_hint), tb, 0, s, w->counters.p, rows, sp, w->row_src.p, w->man_geo.p,
+                                 w->pos.p, w->vel.p, inertia, stride, w->man_color.p,
+                                 w->color_state.p, flow ? (stall ? 2 : 1) : 0, table, w->cluster_slot.p, w->body_shared.p,
+                                 w->cluster_step ? w->cluster_slots : 0u, w->cluster_count, warm, mat...);
+          };
+          if constexpr (MAT) rows_build(mats); else rows_build(); }
         if (flow) {
             if (cluster) {
                 PHYS_PROF(w, PHYS_STAGE_SOLVE_CLUSTER);
-                launch_solve_cluster(w, rows.all, cap, sp.friction, inertia, stride, diag, timeout_ticks);
+                launch_solve_cluster(w, rows.all, cap, sp.friction, inertia, stride, diag, timeout_ticks, MAT);
                 return;
             }
             // about one wave per SIMD or less: waiting waves must not crowd out the ones that can run
@@ -1089,10 +1164,10 @@ void launch_solver(phys_world* w, float dt) {
             const uint64_t per_color = m_hint / (h.valid && h.n_colors ? h.n_colors : 1u);
             const uint32_t pipeline = (uint32_t)dbg.flow_pipeline.value_or(4 * per_color >= threads * items);
             if (quad)
-                hipLaunchKernelGGL(k_solve_flow_quad<DIAG>, dim3((unsigned)items), dim3(threads), 0, s, w->counters.p, sweeps, w->flow_epoch,
+                hipLaunchKernelGGL((k_solve_flow_quad<DIAG, MAT>), dim3((unsigned)items), dim3(threads), 0, s, w->counters.p, sweeps, w->flow_epoch,
                                    rows, sp.friction, inertia, stride, w->vel.p, w->flow_vel.p, (uint32_t)w->n, timeout_ticks, warm_sweep, warm);
             else
-                hipLaunchKernelGGL(k_solve_flow<DIAG>, dim3((unsigned)items), dim3(threads), 0, s, w->counters.p, sweeps, w->flow_epoch,
+                hipLaunchKernelGGL((k_solve_flow<DIAG, MAT>), dim3((unsigned)items), dim3(threads), 0, s, w->counters.p, sweeps, w->flow_epoch,
                                    rows, sp.friction, inertia, stride, w->vel.p, w->flow_vel.p, (uint32_t)w->n, timeout_ticks, pipeline,
                                    warm_sweep, warm);
             return;
@@ -1121,17 +1196,17 @@ void launch_solver(phys_world* w, float dt) {
             for (uint32_t col = 0; col < big; ++col) {
                 PHYS_PROF(w, PHYS_STAGE_SOLVE);
                 if (!dbg.color_kernel_lane.value_or(h.color_count[col] > kQuadColorMaxRows))  // four lanes per manifold
-                    hipLaunchKernelGGL(k_solve_color_quad<DIAG>, grid_for_quads(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
+                    hipLaunchKernelGGL((k_solve_color_quad<DIAG, MAT>), grid_for_quads(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
                                        sp.friction, inertia, stride, w->vel.p, (uint32_t)w->n, apply_only, last, warm);
                 else
-                    hipLaunchKernelGGL(k_solve_color<DIAG>, grid_for_count(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
+                    hipLaunchKernelGGL((k_solve_color<DIAG, MAT>), grid_for_count(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
                                        sp.friction, inertia, stride, w->vel.p, apply_only, last, warm);
             }
             PHYS_PROF(w, PHYS_STAGE_SOLVE_TAIL);
-            hipLaunchKernelGGL(k_solve_tail<DIAG>, dim3(1), dim3(kTailThreads), 0, s, w->counters.p, big, rows, sp.friction,
+            hipLaunchKernelGGL((k_solve_tail<DIAG, MAT>), dim3(1), dim3(kTailThreads), 0, s, w->counters.p, big, rows, sp.friction,
                                inertia, stride, w->vel.p, apply_only, last, warm);
         }
-    });
+    }); });
 }
 
 }  // namespace phys

@@ -311,6 +311,11 @@ int32_t static_set(phys_world* w, uint64_t n, const float* pos, const float* rot
     for (uint64_t k = 0; k < n; ++k) { filt[2 * k] = kFilterDefaultWord; filt[2 * k + 1] = 0u; }
     PHYS_HIP_TRY(w->st_filt.resize(2 * n));
     PHYS_HIP_TRY(hipMemcpyAsync(w->st_filt.p, filt.data(), 4 * filt.size(), hipMemcpyHostToDevice, s));
+    // ... and the default material {cfg.friction, 0} (phys_set_static_materials)
+    std::vector<float> mat(2 * n, 0.0f);
+    for (uint64_t k = 0; k < n; ++k) mat[2 * k] = w->cfg.friction;
+    PHYS_HIP_TRY(w->st_mat.resize(2 * n));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->st_mat.p, mat.data(), 4 * mat.size(), hipMemcpyHostToDevice, s));
     PHYS_HIP_TRY(hipMemcpyAsync(w->st_geo.p, geo.data(), 4 * geo.size(), hipMemcpyHostToDevice, s));
     PHYS_HIP_TRY(hipMemcpyAsync(w->st_rc.p, rc.data(), 4 * rc.size(), hipMemcpyHostToDevice, s));
     PHYS_HIP_TRY(hipMemcpyAsync(w->st_box.p, box.data(), 4 * box.size(), hipMemcpyHostToDevice, s));

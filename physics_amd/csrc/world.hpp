@@ -238,6 +238,14 @@ struct phys_world {
     bool static_filters_set = false;  // phys_set_static_filters since the last phys_set_static_bodies
     bool ground_filter_set = false;   // phys_set_ground_filter ever (the ground filter lasts for the life of the world)
     uint32_t ground_filt = 0xFFFF0001u;  // the ground's category | mask << 16 (its group is 0)
+    // materials: one {friction, restitution} per body slot (2n floats; {cfg.friction, 0} after
+    // phys_set_bodies) and per static (after phys_set_static_bodies); read by k_rows_build's material instance only
+    phys::DevBuf<float> mat, st_mat;
+    bool body_materials_set = false;    // phys_set_body_materials since the last phys_set_bodies
+    bool static_materials_set = false;  // phys_set_static_materials since the last phys_set_static_bodies
+    bool ground_mat_set = false;        // phys_set_ground_material ever (it lasts for the life of the world)
+    float ground_mat[2] = {0.0f, 0.0f}; // {friction, restitution}, valid when ground_mat_set (cfg.friction, 0 otherwise)
+    float restitution_threshold = 1.0f; // phys_set_restitution_threshold
 
     // constraints (A3-A7)
     std::vector<phys::Constraint> constraints;

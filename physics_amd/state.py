@@ -42,6 +42,8 @@ class RigidBody:
         self.index = index
         self.shape_type = _abi.SHAPE_NONE  # new: the reference has no shapes; SHAPE_SPHERE / SHAPE_BOX / SHAPE_CAPSULE
         self.half_extent = np.zeros(3, np.float32)
+        self.friction = None  # new: contact material (World.set_body_materials); None: the config's friction
+        self.restitution = 0.0
 
     @staticmethod
     def new(index):
@@ -100,6 +102,7 @@ class PhysicsState:
         self._world = World(cfg)
         self._snap = None
         self._con_snap = None
+        self._mat_snap = None  # the materials last sent (None: the world holds the defaults)
 
     # ---- host <-> device
     def _push(self):
@@ -120,6 +123,14 @@ class PhysicsState:
                 shape_type=np.array([x.shape_type for x in b], np.uint32) if n else None,
                 half_extent=np.stack([x.half_extent for x in b]) if n else None)
             self._con_snap = None
+            self._mat_snap = None  # set_bodies reset them
+        # materials: never sent while every body has the defaults (the world then runs its plain solver kernels)
+        mats = [(e.body.friction, float(e.body.restitution)) for e in self.entities]
+        if n and mats != self._mat_snap and (self._mat_snap is not None or any(m != (None, 0.0) for m in mats)):
+            self._world.set_body_materials(
+                friction=np.array([self._world.cfg.friction if f is None else f for f, _ in mats], np.float32),
+                restitution=np.array([r for _, r in mats], np.float32))
+            self._mat_snap = mats
         if n and (bodies_changed or not np.array_equal(self._snap[1], forces)):
             self._world.set_forces(forces[:, :3].copy(), forces[:, 3:].copy())
         cons = [(type(c) is FixedOrientationConstraint, c.rigid_body, tuple(c.position.tolist()))
@@ -188,6 +199,14 @@ class PhysicsState:
         """Every entity each query shape intersects, as they are now (World.overlap): (offsets, ascending ids)."""
         self._push()
         return self._world.overlap(shape_type, pos, rot, half_extent, ignore, mask=mask)
+
+    def set_ground_material(self, friction, restitution=0.0):
+        """The ground plane's material (World.set_ground_material); lasts for the life of the state."""
+        self._world.set_ground_material(friction, restitution)
+
+    def set_restitution_threshold(self, v):
+        """Approach speed below which no contact bounces (World.set_restitution_threshold)."""
+        self._world.set_restitution_threshold(v)
 
     def instance_matrices(self):  # what get_render_data feeds the renderer (physics.rs:61-69)
         self._push()

@@ -38,6 +38,23 @@ def _filter_field(a, n, name, lo, hi, dtype):
     return np.ascontiguousarray(v, dtype=dtype)
 
 
+def _material_field(a, n, name, hi):
+    """A per-item material field as a contiguous array of n floats, or None; a wrong length, a non-finite or negative
+    value, or one above `hi` raises before the library is called."""
+    if a is None:
+        return None
+    v = np.asarray(a)
+    if v.dtype.kind not in "fiu":
+        raise ValueError(f"{name}: needs numbers")
+    v = np.broadcast_to(v, (n,)) if v.ndim == 0 else v
+    if v.ndim != 1 or v.shape[0] != n:
+        raise ValueError(f"{name}: needs {n} values, got shape {np.shape(a)}")
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    if v.size and not (np.all(np.isfinite(v)) and v.min() >= 0.0 and v.max() <= hi):
+        raise ValueError(f"{name}: values must be finite and lie in [0, {hi}]")
+    return v
+
+
 def _query_mask(mask, n):
     """The per-query mask of a _filtered query: a scalar or (n,) integers in [0, 0xFFFF]."""
     return _filter_field(mask, n, "mask", 0, 0xFFFF, np.uint16)
@@ -157,6 +174,45 @@ class World:
             if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= 0xFFFF:
                 raise ValueError(f"{name}: needs an integer in [0, 65535]")
         self._ck(self.lib.phys_set_ground_filter(self.h, int(category), int(mask)))
+
+    # ---- materials (include/physics_hip.h): friction >= 0 and restitution in [0, 1] per body / static / ground
+    def set_body_materials(self, friction=None, restitution=None):
+        """Materials of the owned bodies (phys_set_body_materials): each of friction / restitution a scalar or (n_bodies,)
+        floats, or None for the default (the config's friction; restitution 0). A manifold's friction is the geometric
+        mean of its two sides', its restitution the larger one. Takes effect at the next update; set_bodies resets them."""
+        n = self.n
+        f = _material_field(friction, n, "friction", np.inf)
+        e = _material_field(restitution, n, "restitution", 1.0)
+        self._ck(self.lib.phys_set_body_materials(self.h, n, _p(f), _p(e)))
+
+    def get_body_materials(self):
+        """(friction f32[n], restitution f32[n]) of the owned bodies."""
+        f = np.empty(self.n, np.float32)
+        e = np.empty(self.n, np.float32)
+        self._ck(self.lib.phys_get_body_materials(self.h, _p(f), _p(e)))
+        return f, e
+
+    def set_static_materials(self, friction=None, restitution=None):
+        """Materials of the static colliders (phys_set_static_materials), as set_body_materials; set_static_bodies resets them."""
+        n = self.n_static
+        f = _material_field(friction, n, "friction", np.inf)
+        e = _material_field(restitution, n, "restitution", 1.0)
+        self._ck(self.lib.phys_set_static_materials(self.h, n, _p(f), _p(e)))
+
+    def set_ground_material(self, friction, restitution=0.0):
+        """The ground plane's material; lasts for the life of the world."""
+        f = _material_field(friction, 1, "friction", np.inf)
+        e = _material_field(restitution, 1, "restitution", 1.0)
+        if f is None or e is None:
+            raise ValueError("the ground's friction and restitution are numbers")
+        self._ck(self.lib.phys_set_ground_material(self.h, float(f[0]), float(e[0])))
+
+    def set_restitution_threshold(self, v):
+        """Approach speed along the normal below which no contact bounces (default 1.0); lasts for the life of the world."""
+        t = _material_field(v, 1, "threshold", np.inf)
+        if t is None:
+            raise ValueError("the threshold is a number")
+        self._ck(self.lib.phys_set_restitution_threshold(self.h, float(t[0])))
 
     def get_static_stats(self):
         """(static colliders, (body, static) pairs of the last update, manifolds against statics of the last update)."""

@@ -160,6 +160,11 @@ extern "C" {
     pub fn phys_get_body_filters(w: *mut phys_world, category_out: *mut u16, mask_out: *mut u16, group_out: *mut i16) -> i32;
     pub fn phys_set_static_filters(w: *mut phys_world, n: u64, category: *const u16, mask: *const u16, group: *const i16) -> i32;
     pub fn phys_set_ground_filter(w: *mut phys_world, category: u16, mask: u16) -> i32;
+    pub fn phys_set_body_materials(w: *mut phys_world, n: u64, friction: *const f32, restitution: *const f32) -> i32;
+    pub fn phys_get_body_materials(w: *mut phys_world, friction_out: *mut f32, restitution_out: *mut f32) -> i32;
+    pub fn phys_set_static_materials(w: *mut phys_world, n: u64, friction: *const f32, restitution: *const f32) -> i32;
+    pub fn phys_set_ground_material(w: *mut phys_world, friction: f32, restitution: f32) -> i32;
+    pub fn phys_set_restitution_threshold(w: *mut phys_world, v: f32) -> i32;
     pub fn phys_raycast_filtered(w: *mut phys_world, n_rays: u64, origin: *const f32, dir: *const f32, max_t: *const f32,
                                  ignore_body: *const u32, query_mask: *const u16, body_out: *mut u32, t_out: *mut f32,
                                  normal_out: *mut f32) -> i32;
