@@ -419,6 +419,64 @@ int32_t phys_set_static_materials(phys_world* w, uint64_t n, const float* fricti
 int32_t phys_set_ground_material(phys_world* w, float friction, float restitution);
 int32_t phys_set_restitution_threshold(phys_world* w, float v /* >= 0, finite */);
 
+/* --- contact events: what began and what stopped touching, and how hard (new: the reference has none) ---
+ * A pair is what a manifold names: (body_a, body_b) with phys_get_manifolds' ids - body indices (ghost slots included),
+ * PHYS_STATIC_ID_BIT | k, 0xFFFFFFFF for the ground. Events are raised per update E with PHYS_FLAG_COLLISIONS (an update
+ * with dt = 0 has no collision stage: it raises nothing and is not an "update" below):
+ *   BEGIN  a manifold of update E whose pair had no manifold in update E - 1: exactly the manifolds counted in
+ *          phys_stats.n_new_manifolds (the persistent colouring's "new"; there is no second notion of persistence).
+ *   END    a manifold of update E - 1 whose pair has none in update E, whatever the cause: the pair separated, was
+ *          filtered out, or dropped out of the candidate pairs.
+ * A pair that persists raises nothing. The first update after phys_set_bodies or phys_set_static_bodies raises BEGIN for
+ * every manifold and no END: both calls make the world forget its colours and with them its contact history, and both
+ * discard the events not yet drained (their ids would name other things). Enabling events resets nothing: the next update
+ * reports against the update before it (its END events are missed only if phys_broadphase, which clears the step counters,
+ * was called in between).
+ * An update flagged with an overflow bit skips its contact solve and keeps its new manifolds out of the colour table. It
+ * raises BEGIN (impulse 0) / END from the manifolds it stored; the next clean update then sees those pairs as new again
+ * (one more BEGIN, and an END for the stored manifold it replaces), and the update after that reports correctly again.
+ * Nothing is written out of bounds in any of them.
+ *
+ * phys_contact_events_enable: `capacity` = events the device keeps between two drains. 0 turns events off, frees the
+ *   buffers and drops pending events; a call with a new capacity drops pending events; the same capacity is a no-op.
+ *   Events accumulate on the device across updates, also inside a phys_update_n batch, at no host round trip; when the
+ *   buffer is full further events are counted but not stored (no sticky error, no skipped solve). A world that never
+ *   calls this launches the kernels it always launched. PHYS_ERR_UNSUPPORTED: a world without PHYS_FLAG_COLLISIONS, with
+ *   PHYS_FLAG_BROADPHASE_ONLY, or without warm starting - PHYS_FLAG_NO_WARM_START, or a manifold capacity
+ *   (phys_config.max_manifolds, 0 = 17 per body) of 2^26 or more: the previous update's records and the impulse records
+ *   exist only in warm worlds. (A phys_set_bodies that raises the automatic capacity that far turns events off; the
+ *   getter then says PHYS_ERR_UNSUPPORTED.) PHYS_ERR_INVALID_ARG: capacity >= 2^31.
+ * phys_get_contact_events: synchronises the world's stream, copies the stored events sorted by (step, kind, body_a,
+ *   body_b) - device order is arbitrary, like manifolds - writes *n (events returned) and *n_dropped (events raised since
+ *   the last drain that did not fit the device buffer; may be NULL), then empties the buffer. More stored than `cap`:
+ *   PHYS_ERR_CAPACITY with *n = the stored count, and the buffer is kept (resize and call again, as for phys_overlap).
+ *   out == NULL with cap == 0 only counts: PHYS_OK, *n and *n_dropped written, the buffer kept. While n_dropped == 0 the
+ *   list is complete and a function of the world's history alone: bit-identical across runs. With drops the counts are
+ *   exact; which events were stored is unspecified. Events off: PHYS_ERR_UNSUPPORTED. It neither reports nor clears the
+ *   sticky update errors (only phys_sync does).
+ * phys_get_contact_impulses: the solver's final impulses of the LAST update, {pn, pt0, pt1} for each of the 4 point slots
+ *   of every manifold (zeros beyond its count), in phys_get_manifolds' order so that the two calls line up row for row.
+ *   Works in every warm world with collisions, events on or off; PHYS_ERR_UNSUPPORTED otherwise. out == NULL queries the
+ *   count. An update whose solve was skipped reports zeros.
+ * Added without an ABI version change (no struct changed): a library that predates them lacks the symbols. DESIGN.md
+ * section 15. */
+#define PHYS_CONTACT_BEGIN 1u
+#define PHYS_CONTACT_END   2u
+typedef struct phys_contact_event {   /* 48 bytes */
+    uint32_t body_a, body_b;  /* as phys_get_manifolds */
+    uint32_t kind;            /* PHYS_CONTACT_BEGIN / PHYS_CONTACT_END */
+    uint32_t step;            /* low 32 bits of phys_stats.steps after the update that raised it (1 = first update) */
+    float point[3];           /* BEGIN: the manifold's deepest point (largest depth, lowest index on a tie); END: 0 */
+    float impulse;            /* BEGIN: sum of the manifold's normal impulses pn at the end of that update's solve,
+                                 ((p0 + p1) + p2) + p3; 0 if the solve was skipped; END: 0 */
+    float normal[3];          /* BEGIN: the manifold's normal as phys_get_manifolds reports it; END: 0 */
+    uint32_t reserved;        /* 0 */
+} phys_contact_event;
+
+int32_t phys_contact_events_enable(phys_world* w, uint64_t capacity);
+int32_t phys_get_contact_events(phys_world* w, phys_contact_event* out, uint64_t cap, uint64_t* n, uint64_t* n_dropped);
+int32_t phys_get_contact_impulses(phys_world* w, float* out /*12*cap*/, uint64_t cap, uint64_t* n_manifolds);
+
 /* --- per-stage device timing (HIP events on the world's stream), for bench.py's roofline --- */
 #define PHYS_STAGE_STEP_FULL 0u     /* gravity + RigidBody::step, one kernel (no collisions) */
 #define PHYS_STAGE_VELOCITY_AABB 1u /* gravity + velocity half + AABB */

@@ -241,6 +241,28 @@ class PhysicsState {  // physics.rs:25-31
     // phys_set_restitution_threshold): both last for the life of the state
     void set_ground_material(float friction, float restitution) { check(phys_set_ground_material(w_, friction, restitution)); }
     void set_restitution_threshold(float v) { check(phys_set_restitution_threshold(w_, v)); }
+    // contact events (phys_contact_events_enable): keep up to `capacity` events on the device between two drains; 0 = off
+    using ContactEvent = phys_contact_event;
+    void enable_contact_events(uint64_t capacity) { check(phys_contact_events_enable(w_, capacity)); }
+    // every event raised since the last drain, sorted by (step, kind, body_a, body_b); *n_dropped (may be null): events that
+    // did not fit the device buffer. Empties the buffer (phys_get_contact_events)
+    std::vector<ContactEvent> drain_contact_events(uint64_t* n_dropped = nullptr) {
+        uint64_t n = 0, dropped = 0;
+        check(phys_get_contact_events(w_, nullptr, 0, &n, &dropped));  // count only
+        std::vector<ContactEvent> ev(n);
+        if (n) check(phys_get_contact_events(w_, ev.data(), ev.size(), &n, &dropped));
+        ev.resize(n);
+        if (n_dropped) *n_dropped = dropped;
+        return ev;
+    }
+    // {pn, pt0, pt1} the last update's solve ended with, per point slot (4) of every manifold, in phys_get_manifolds' order
+    std::vector<std::array<float, 12>> contact_impulses() {
+        uint64_t n = 0;
+        check(phys_get_contact_impulses(w_, nullptr, 0, &n));
+        std::vector<std::array<float, 12>> imp(n);
+        if (n) check(phys_get_contact_impulses(w_, &imp[0][0], n, &n));
+        return imp;
+    }
     phys_world* raw() { return w_; }
 
   private:

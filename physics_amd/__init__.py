@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference's `PhysicsState` surface over the C ABI of libphysics_hip.so
 (include/physics_hip.h). The compute path is hand-written HIP; there is no CPU fallback."""
-from ._abi import (FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, FLAG_BROADPHASE_ONLY, FLAG_COLLISIONS, FLAG_EXACT_ROTATION,
+from ._abi import (CONTACT_BEGIN, CONTACT_END, FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, FLAG_BROADPHASE_ONLY, FLAG_COLLISIONS, FLAG_EXACT_ROTATION,
                    FLAG_GROUND_PLANE, FLAG_EXCLUSIVE_GPU, FLAG_NO_WARM_START, FLAG_SHARED_GPU, FLAG_SOLVER_CLUSTER, FLAG_SOLVER_PER_COLOR, GROUND_ID,
                    RAY_GROUND, RAY_MISS, SHAPE_BOX, SHAPE_CAPSULE, STATIC_ID_BIT, SHAPE_NONE, SHAPE_SPHERE, PhysicsHipMissing,
                    default_config)
@@ -12,4 +12,5 @@ from .world import Comm, PhysError, World, block_spmv
 
 __all__ = ["World", "Comm", "block_spmv", "PhysError", "PhysicsHipMissing", "default_config", "FLAG_COLLISIONS", "FLAG_GROUND_PLANE",
            "FLAG_EXACT_ROTATION", "FLAG_BROADPHASE_ONLY", "FLAG_SOLVER_PER_COLOR", "FLAG_SHARED_GPU", "FLAG_SOLVER_CLUSTER", "FLAG_EXCLUSIVE_GPU", "FLAG_NO_WARM_START", "SHAPE_NONE", "SHAPE_SPHERE", "SHAPE_BOX", "SHAPE_CAPSULE", "GROUND_ID",
-           "RAY_MISS", "RAY_GROUND", "STATIC_ID_BIT", "FILTER_DEFAULT_CATEGORY", "FILTER_DEFAULT_MASK", "capsule_inertia"]
+           "RAY_MISS", "RAY_GROUND", "STATIC_ID_BIT", "FILTER_DEFAULT_CATEGORY", "FILTER_DEFAULT_MASK", "capsule_inertia", "CONTACT_BEGIN",
+           "CONTACT_END"]

@@ -32,6 +32,8 @@ STATIC_ID_BIT = 0x80000000  # PHYS_STATIC_ID_BIT: manifold body_b / ray body = S
 # collision filters (include/physics_hip.h): category u16, mask u16, group i16; these are the defaults (group 0)
 FILTER_DEFAULT_CATEGORY = 0x0001
 FILTER_DEFAULT_MASK = 0xFFFF
+# contact events (include/physics_hip.h): phys_contact_event.kind
+CONTACT_BEGIN, CONTACT_END = 1, 2
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -104,6 +106,20 @@ class PhysDeviceView(C.Structure):
         ("aabb", C.c_void_p),
         ("stream", C.c_void_p),
         ("vel_stride", C.c_uint64),
+    ]
+
+
+class PhysContactEvent(C.Structure):
+    """struct phys_contact_event (include/physics_hip.h), 48 bytes."""
+    _fields_ = [
+        ("body_a", C.c_uint32),
+        ("body_b", C.c_uint32),
+        ("kind", C.c_uint32),
+        ("step", C.c_uint32),
+        ("point", C.c_float * 3),
+        ("impulse", C.c_float),
+        ("normal", C.c_float * 3),
+        ("reserved", C.c_uint32),
     ]
 
 
@@ -192,6 +208,9 @@ PROTOTYPES = {
     "phys_set_ground_material": (C.c_int32, [C.c_void_p, C.c_float, C.c_float]),
     "phys_set_restitution_threshold": (C.c_int32, [C.c_void_p, C.c_float]),
     "phys_get_static_stats": (C.c_int32, [C.c_void_p, u64p, u64p, u64p]),
+    "phys_contact_events_enable": (C.c_int32, [C.c_void_p, C.c_uint64]),
+    "phys_get_contact_events": (C.c_int32, [C.c_void_p, C.POINTER(PhysContactEvent), C.c_uint64, u64p, u64p]),
+    "phys_get_contact_impulses": (C.c_int32, [C.c_void_p, f32p, C.c_uint64, u64p]),
     "phys_profile_enable": (C.c_int32, [C.c_void_p, C.c_int32]),
     "phys_profile_get": (C.c_int32, [C.c_void_p, C.POINTER(PhysProfile)]),
     "phys_get_device_view": (C.c_int32, [C.c_void_p, C.POINTER(PhysDeviceView)]),

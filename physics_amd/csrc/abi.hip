@@ -235,6 +235,7 @@ int32_t phys_destroy(phys_world* w) {
     for (auto* b : ub) b->free();
     w->man_prio.free(); w->color_state.free(); w->bucket_count.free(); w->step_zero.free();
     w->d_constraints.free(); w->counters.free();
+    w->ev_buf.free(); w->ev_matched.free(); w->ev_state.free();
     w->ctab.free(); w->unc_list.free(); w->rc_stats.free(); w->qr_off.free();
     w->prof.destroy();
     for (int k = 0; k < phys_world::kSnapRing; ++k) {
@@ -279,6 +280,7 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     w->body_filters_set = false;    // every body slot gets the default filter below
     w->body_materials_set = false;  // ... and the default material
     for (int k = 0; k < phys_world::kSnapRing; ++k) w->snap_pending[k] = false;  // the stream was synchronised above
+    { const int32_t rc = events_reset(w); if (rc != PHYS_OK) return rc; }  // contact events: history and pending events are gone
     if (n == 0) return PHYS_OK;
 
     // host staging with RigidBody::new defaults (rigid_body.rs:64-76); ghost slots: no shape, immovable
@@ -345,6 +347,11 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
         if (rc != PHYS_OK) return rc;
         if (!(w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY)) {
             rc = cluster_assign(w, pos);  // spatial clusters of the cluster solver (large scenes only)
+            if (rc != PHYS_OK) return rc;
+            // contact events follow the manifold capacity; a body set too large for warm starting turns them off
+            // (phys_get_contact_events then answers PHYS_ERR_UNSUPPORTED)
+            if (w->ev_capacity && !w->warm) w->ev_capacity = 0;
+            rc = events_alloc(w);
             if (rc != PHYS_OK) return rc;
         }
     }
@@ -448,6 +455,7 @@ static int32_t enqueue_update(phys_world* w, float dt) {
             launch_narrowphase(w);
             launch_coloring(w);
             launch_solver(w, dt);
+            if (w->ev_capacity) launch_events(w, (uint32_t)(w->steps + 1));  // contact events: nothing in a world without them
         } else {
             snapshot_counters_async(w);  // launch-size hints of later updates (the colouring stage takes it otherwise)
         }
@@ -703,6 +711,7 @@ int32_t phys_set_static_bodies(phys_world* w, uint64_t n, const float* pos, cons
     w->static_pairs_seen = 0;
     w->static_filters_set = false;  // the new set starts with the default filters (static_set)
     w->static_materials_set = false;  // ... and the default materials
+    { const int32_t rc = events_reset(w); if (rc != PHYS_OK) return rc; }  // contact events name static ids too
     return static_set(w, n, pos, rot, shape_type, half_extent);
 }
 

@@ -1,0 +1,286 @@
+// events.hip — contact events: which pairs began and stopped touching in an update, read off
+// what the collision stage leaves on the device anyway. Two streaming kernels behind the solve of every update of a
+// world with events on; a world that never enables them launches nothing of this file.
+//
+//   k_events_begin  over this update's manifolds: a manifold whose pair had one in the previous update (the narrow phase
+//                   wrote that manifold's index into the record, from the persistent colour table) stamps
+//                   ev_matched[index]; one whose pair had none raises BEGIN with its deepest point, its normal and the
+//                   normal impulses its solve ended with.
+//   k_events_end    over the previous update's manifolds: one that nobody stamped raises END.
+//
+// Events are appended to one buffer that lives across updates (also inside a phys_update_n batch). The cursor is
+// reserved once per workgroup and trip - wave ballot + popcount, per-wave totals in LDS, ONE global atomic - because
+// same-address atomics serialise chip-wide (~88 per microsecond). Slots at or beyond the capacity are not written; the
+// cursor keeps counting, and the drain reports the difference as dropped.
+#include "kernels.hpp"
+
+namespace phys {
+
+constexpr int kEventThreads = 256;
+constexpr int kEventWaves = kEventThreads / 64;
+
+// device words of the event state: {cursor (64 bits), manifold count of the even updates, ... of the odd updates}
+struct EventState {
+    unsigned long long cursor;  // events raised since the last drain (stored ones: the first `capacity` of them)
+    uint32_t count[2];          // stored manifolds of the last two updates with events, by the update's parity
+};
+
+// LDS of one reservation; the per-wave totals alternate between two sets, so that a wave which runs ahead into the
+// next trip does not overwrite totals a slower wave still adds up
+struct EventAppend {
+    uint32_t wave_total[2][kEventWaves];
+    unsigned long long base;
+};
+
+// the slot of this lane's event (meaningful where emit is true); every thread of the workgroup calls it, once per trip
+__device__ __forceinline__ unsigned long long event_reserve(bool emit, uint32_t trip, EventAppend& sh, EventState* st) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, set = trip & 1u;
+    const unsigned long long mask = __ballot(emit);
+    if (lane == 0) sh.wave_total[set][wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int k = 0; k < kEventWaves; ++k) t += sh.wave_total[set][k];
+        sh.base = t ? atomicAdd(&st->cursor, (unsigned long long)t) : 0ull;
+    }
+    __syncthreads();
+    uint32_t off = 0;
+    for (uint32_t k = 0; k < wave; ++k) off += sh.wave_total[set][k];
+    return sh.base + off + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+}
+
+__device__ __forceinline__ void event_store(uint32_t* __restrict__ ev_buf, unsigned long long slot, uint4 w0, uint4 w1, uint4 w2) {
+    uint4* o = reinterpret_cast<uint4*>(ev_buf) + 3 * slot;  // 48 bytes = phys_contact_event
+    o[0] = w0; o[1] = w1; o[2] = w2;
+}
+
+__global__ __launch_bounds__(kEventThreads) void k_events_begin(const StepCounters* __restrict__ ctr, uint64_t max_manifolds,
+                                                                const float* __restrict__ man_geo /* 128-byte records */,
+                                                                const float* __restrict__ man_imp /* 12 floats per manifold */,
+                                                                uint32_t* __restrict__ ev_matched, uint32_t stamp, uint32_t step,
+                                                                uint32_t parity, EventState* __restrict__ st,
+                                                                uint32_t* __restrict__ ev_buf, uint64_t capacity) {
+    __shared__ EventAppend sh;
+    const uint32_t n = ctr->n_manifolds;  // final: the narrow phase ended launches ago
+    const uint32_t M = (uint64_t)n < max_manifolds ? n : (uint32_t)max_manifolds;
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->count[parity] = M;  // what the next update's k_events_end runs over
+    const uint32_t stride = gridDim.x * kEventThreads;
+    const uint32_t trips = (M + stride - 1) / stride;  // the same for every thread: the reservation has barriers
+    for (uint32_t trip = 0; trip < trips; ++trip) {
+        const uint32_t m = trip * stride + blockIdx.x * kEventThreads + threadIdx.x;
+        bool emit = false;
+        uint4 w0 = make_uint4(0, 0, 0, 0), w1 = w0, w2 = w0;
+        if (m < M) {
+            const float4* rec = reinterpret_cast<const float4*>(man_geo) + 8 * (size_t)m;
+            const float4 r0 = rec[0], r1 = rec[1];
+            const uint32_t prev_m = __float_as_uint(r1.w);
+            if (prev_m != 0xFFFFFFFFu) {
+                // pairs are unique: no two lanes write one word
+                if ((uint64_t)prev_m < max_manifolds) ev_matched[prev_m] = stamp;
+            } else {
+                emit = true;
+                const uint32_t count = __float_as_uint(r0.z);
+                const float4 p0 = rec[2], p1 = rec[3], p2 = rec[4], p3 = rec[5];
+                const float4* imp = reinterpret_cast<const float4*>(man_imp) + 3 * (size_t)m;
+                const float4 i0 = imp[0], i1 = imp[1], i2 = imp[2];  // {pn, pt0, pt1} x 4, packed
+                // the deepest point: largest depth, lowest index on a tie
+                float4 best = p0;
+                if (count > 1u && p1.w > best.w) best = p1;
+                if (count > 2u && p2.w > best.w) best = p2;
+                if (count > 3u && p3.w > best.w) best = p3;
+                const float n0 = count > 0u ? i0.x : 0.0f, n1 = count > 1u ? i0.w : 0.0f;
+                const float n2 = count > 2u ? i1.z : 0.0f, n3 = count > 3u ? i2.y : 0.0f;
+                const float impulse = ((n0 + n1) + n2) + n3;
+                w0 = make_uint4(__float_as_uint(r0.x), __float_as_uint(r0.y), PHYS_CONTACT_BEGIN, step);
+                w1 = make_uint4(__float_as_uint(best.x), __float_as_uint(best.y), __float_as_uint(best.z), __float_as_uint(impulse));
+                w2 = make_uint4(__float_as_uint(r1.x), __float_as_uint(r1.y), __float_as_uint(r1.z), 0u);
+            }
+        }
+        const unsigned long long slot = event_reserve(emit, trip, sh, st);
+        if (emit && slot < capacity) event_store(ev_buf, slot, w0, w1, w2);
+    }
+}
+
+__global__ __launch_bounds__(kEventThreads) void k_events_end(uint64_t max_manifolds, const float* __restrict__ man_geo_prev,
+                                                              const uint32_t* __restrict__ ev_matched, uint32_t stamp, uint32_t step,
+                                                              uint32_t parity_prev, EventState* __restrict__ st,
+                                                              uint32_t* __restrict__ ev_buf, uint64_t capacity) {
+    __shared__ EventAppend sh;
+    const uint32_t n = st->count[parity_prev];  // left by the previous update's k_events_begin; 0 after a reset
+    const uint32_t M = (uint64_t)n < max_manifolds ? n : (uint32_t)max_manifolds;
+    const uint32_t stride = gridDim.x * kEventThreads;
+    const uint32_t trips = (M + stride - 1) / stride;
+    for (uint32_t trip = 0; trip < trips; ++trip) {
+        const uint32_t k = trip * stride + blockIdx.x * kEventThreads + threadIdx.x;
+        bool emit = false;
+        uint4 w0 = make_uint4(0, 0, 0, 0);
+        if (k < M && ev_matched[k] != stamp) {
+            emit = true;
+            const uint2 ab = *reinterpret_cast<const uint2*>(man_geo_prev + 32 * (size_t)k);
+            w0 = make_uint4(ab.x, ab.y, PHYS_CONTACT_END, step);
+        }
+        const unsigned long long slot = event_reserve(emit, trip, sh, st);
+        if (emit && slot < capacity) event_store(ev_buf, slot, w0, make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0));
+    }
+}
+
+static_assert(sizeof(EventState) == 16, "cursor | two counts");
+
+// (re)allocates what events need for the world's current manifold capacity; the buffers of a world with events off are freed
+int32_t events_alloc(phys_world* w) {
+    if (w->ev_capacity == 0) {
+        w->ev_buf.free(); w->ev_matched.free(); w->ev_state.free();
+        return PHYS_OK;
+    }
+    PHYS_HIP_TRY(w->ev_buf.resize(12 * (size_t)w->ev_capacity));
+    PHYS_HIP_TRY(w->ev_state.resize(4));
+    if (w->max_manifolds && w->ev_matched.n < w->max_manifolds) {
+        PHYS_HIP_TRY(w->ev_matched.resize(w->max_manifolds));
+        // no stamp is ever 0 (launch_events), and stamps only grow: zeroed words match no update
+        PHYS_HIP_TRY(hipMemsetAsync(w->ev_matched.p, 0, 4 * w->ev_matched.n, w->stream));
+    }
+    return PHYS_OK;
+}
+
+// forget the contact history and the events not yet drained (phys_set_bodies, phys_set_static_bodies: the ids name other things)
+int32_t events_reset(phys_world* w) {
+    if (w->ev_capacity == 0 || !w->ev_state.p) return PHYS_OK;
+    PHYS_HIP_TRY(hipMemsetAsync(w->ev_state.p, 0, sizeof(EventState), w->stream));
+    return PHYS_OK;
+}
+
+// `step`: phys_stats.steps after this update (low 32 bits)
+void launch_events(phys_world* w, uint32_t step) {
+    if (w->ev_capacity == 0 || !w->ev_matched.p || w->n == 0) return;
+    // The stamp that says "matched in THIS update": a 32-bit count of the updates with events of this world, never 0 (the
+    // value of a fresh ev_matched). At its wrap - 2^32 updates, months of stepping - the words are zeroed and the count
+    // starts again at 1, so a stamp written 2^32 updates ago can never pass for this update's.
+    if (++w->ev_stamp == 0u) {
+        PHYS_PROF(w, PHYS_STAGE_MISC);
+        (void)hipMemsetAsync(w->ev_matched.p, 0, 4 * w->ev_matched.n, w->stream);
+        w->ev_stamp = 1u;
+    }
+    const uint32_t parity = w->ev_parity;
+    w->ev_parity ^= 1u;
+    // any grid is correct (the kernels stride); sized from an earlier update's count where one is known
+    const uint64_t m_guess = w->hint.valid ? (uint64_t)w->hint.n_manifolds * 5 / 4 + kEventThreads : w->max_manifolds;
+    uint64_t blocks = (std::min<uint64_t>(m_guess, w->max_manifolds) + kEventThreads - 1) / kEventThreads;
+    blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, 2048));
+    EventState* st = reinterpret_cast<EventState*>(w->ev_state.p);
+    { PHYS_PROF(w, PHYS_STAGE_MISC);
+      hipLaunchKernelGGL(k_events_begin, dim3((unsigned)blocks), dim3(kEventThreads), 0, w->stream, w->counters.p, w->max_manifolds,
+                         w->man_geo.p, w->man_imp.p, w->ev_matched.p, w->ev_stamp, step, parity, st, w->ev_buf.p, w->ev_capacity); }
+    { PHYS_PROF(w, PHYS_STAGE_MISC);
+      hipLaunchKernelGGL(k_events_end, dim3((unsigned)blocks), dim3(kEventThreads), 0, w->stream, w->max_manifolds, w->man_geo_prev.p,
+                         w->ev_matched.p, w->ev_stamp, step, parity ^ 1u, st, w->ev_buf.p, w->ev_capacity); }
+}
+
+}  // namespace phys
+
+using namespace phys;
+
+static int32_t ev_fail(int32_t code, const char* msg) {
+    set_error(msg);
+    return code;
+}
+
+extern "C" {
+
+int32_t phys_contact_events_enable(phys_world* w, uint64_t capacity) {
+    if (!w) return ev_fail(PHYS_ERR_INVALID_ARG, "null world");
+    PHYS_HIP_TRY(hipSetDevice(w->device));
+    if (capacity >= (1ull << 31)) return ev_fail(PHYS_ERR_INVALID_ARG, "phys_contact_events_enable: capacity must be below 2^31");
+    if (!(w->cfg.flags & PHYS_FLAG_COLLISIONS) || (w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY))
+        return ev_fail(PHYS_ERR_UNSUPPORTED, "contact events need PHYS_FLAG_COLLISIONS without PHYS_FLAG_BROADPHASE_ONLY");
+    // the previous update's records and the impulse records exist only in worlds with warm starting (w->warm once bodies are set)
+    const uint64_t cap_cfg = w->cfg.max_manifolds;
+    if ((w->cfg.flags & PHYS_FLAG_NO_WARM_START) || (w->n ? !w->warm : cap_cfg >= (1ull << 26)))
+        return ev_fail(PHYS_ERR_UNSUPPORTED, "contact events need warm starting: no PHYS_FLAG_NO_WARM_START, manifold capacity below 2^26");
+    if (capacity == w->ev_capacity) return PHYS_OK;
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    const bool was_on = w->ev_capacity != 0;
+    w->ev_capacity = capacity;
+    if (capacity == 0) return events_alloc(w);  // off: buffers freed, pending events gone
+    w->ev_buf.free();  // a new capacity: a buffer of exactly that size
+    int32_t rc = events_alloc(w); if (rc) return rc;
+    EventState h{};
+    if (was_on) {
+        PHYS_HIP_TRY(hipMemcpyAsync(&h, w->ev_state.p, sizeof(h), hipMemcpyDeviceToHost, w->stream));
+        PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+        h.cursor = 0;  // a new capacity drops the pending events, nothing else
+    } else if (w->ctab_valid && w->n) {
+        // Enabling resets nothing: the next update reports against the last one, whose records are on the device and whose
+        // manifold count is in the step counters (a phys_broadphase call since then has zeroed it: no END events then).
+        uint32_t n = 0;
+        PHYS_HIP_TRY(hipMemcpyAsync(&n, &w->counters.p->n_manifolds, 4, hipMemcpyDeviceToHost, w->stream));
+        PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+        h.count[w->ev_parity ^ 1u] = (uint64_t)n < w->max_manifolds ? n : (uint32_t)w->max_manifolds;
+    }
+    PHYS_HIP_TRY(hipMemcpyAsync(w->ev_state.p, &h, sizeof(h), hipMemcpyHostToDevice, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // `h` dies here
+    return PHYS_OK;
+}
+
+int32_t phys_get_contact_events(phys_world* w, phys_contact_event* out, uint64_t cap, uint64_t* n, uint64_t* n_dropped) {
+    if (!w) return ev_fail(PHYS_ERR_INVALID_ARG, "null world");
+    PHYS_HIP_TRY(hipSetDevice(w->device));
+    if (!n) return ev_fail(PHYS_ERR_INVALID_ARG, "phys_get_contact_events: null n");
+    if (cap && !out) return ev_fail(PHYS_ERR_INVALID_ARG, "phys_get_contact_events: null out with cap > 0");
+    if (w->ev_capacity == 0) return ev_fail(PHYS_ERR_UNSUPPORTED, "contact events are off (phys_contact_events_enable)");
+    EventState h{};
+    PHYS_HIP_TRY(hipMemcpyAsync(&h, w->ev_state.p, sizeof(h), hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    const uint64_t stored = h.cursor < w->ev_capacity ? h.cursor : w->ev_capacity;
+    *n = stored;
+    if (n_dropped) *n_dropped = h.cursor - stored;
+    if (!out && cap == 0) return PHYS_OK;  // count query: the buffer stays
+    if (stored > cap) return ev_fail(PHYS_ERR_CAPACITY, "phys_get_contact_events: more events stored than cap (*n says how many); nothing was drained");
+    if (stored) {
+        PHYS_HIP_TRY(hipMemcpyAsync(out, w->ev_buf.p, stored * sizeof(phys_contact_event), hipMemcpyDeviceToHost, w->stream));
+        PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+        // device order is arbitrary; a read-out convenience as in phys_get_manifolds
+        std::sort(out, out + stored, [](const phys_contact_event& x, const phys_contact_event& y) {
+            if (x.step != y.step) return x.step < y.step;
+            if (x.kind != y.kind) return x.kind < y.kind;
+            if (x.body_a != y.body_a) return x.body_a < y.body_a;
+            return x.body_b < y.body_b;
+        });
+    }
+    // the cursor word only; ordered on the world's stream in front of the next update's kernels
+    if (h.cursor) PHYS_HIP_TRY(hipMemsetAsync(w->ev_state.p, 0, sizeof(h.cursor), w->stream));
+    return PHYS_OK;
+}
+
+int32_t phys_get_contact_impulses(phys_world* w, float* out, uint64_t cap, uint64_t* n_manifolds) {
+    if (!w) return ev_fail(PHYS_ERR_INVALID_ARG, "null world");
+    PHYS_HIP_TRY(hipSetDevice(w->device));
+    if (!n_manifolds) return ev_fail(PHYS_ERR_INVALID_ARG, "phys_get_contact_impulses: null n_manifolds");
+    if (!w->warm || !(w->cfg.flags & PHYS_FLAG_COLLISIONS) || (w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY))
+        return ev_fail(PHYS_ERR_UNSUPPORTED, "contact impulses are kept only in worlds with collisions and warm starting");
+    uint32_t counted = 0;
+    PHYS_HIP_TRY(hipMemcpyAsync(&counted, &w->counters.p->n_manifolds, 4, hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    const uint64_t m = (uint64_t)counted < w->max_manifolds ? counted : w->max_manifolds;
+    *n_manifolds = m;
+    if (!out || m == 0) return PHYS_OK;
+    // {a, b, count, -} of every record (16 bytes out of each 128-byte line) and the 48-byte impulse records, storage order
+    std::vector<uint32_t> head(4 * m);
+    std::vector<float> imp(12 * m);
+    PHYS_HIP_TRY(hipMemcpy2DAsync(head.data(), 16, w->man_geo.p, 128, 16, m, hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipMemcpyAsync(imp.data(), w->man_imp.p, 48 * m, hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    std::vector<uint64_t> order(m);
+    for (uint64_t k = 0; k < m; ++k) order[k] = k;
+    // phys_get_manifolds' order: pairs are unique, so (a, b) fixes it
+    std::sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) {
+        return head[4 * x] < head[4 * y] || (head[4 * x] == head[4 * y] && head[4 * x + 1] < head[4 * y + 1]);
+    });
+    for (uint64_t k = 0; k < m && k < cap; ++k) {
+        const uint64_t s = order[k];
+        const uint32_t count = head[4 * s + 2];
+        for (uint32_t q = 0; q < 12; ++q) out[12 * k + q] = q / 3 < count ? imp[12 * s + q] : 0.0f;
+    }
+    return PHYS_OK;
+}
+
+}  // extern "C"

@@ -246,6 +246,10 @@ StepCounters* snapshot_acquire(phys_world* w);  // abi.hip: pinned slot a kernel
 void snapshot_commit(phys_world* w);             // ... then mark it in flight
 void poll_snapshots(phys_world* w);           // abi.hip
 void launch_solver(phys_world* w, float dt);
+// contact events (events.hip): two kernels behind the solve, only in a world with events on
+void launch_events(phys_world* w, uint32_t step);
+int32_t events_alloc(phys_world* w);  // buffers for the current event and manifold capacities (frees them when events are off)
+int32_t events_reset(phys_world* w);  // forget the contact history and the pending events (a new body or static set)
 
 // constraints.hip
 int32_t constraints_alloc(phys_world* w);

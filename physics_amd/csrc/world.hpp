@@ -369,6 +369,13 @@ struct phys_world {
     uint64_t max_static_pairs = 0;       // automatic: a per-body budget, regrown from the counts of earlier updates
     uint64_t static_pairs_seen = 0;      // the largest pair count an update has reported back (sizes the buffer)
     bool static_pairs_sized = false;     // the next update measures its pair count first (new static or body set)
+    // contact events (events.hip): off unless phys_contact_events_enable gave a capacity
+    uint64_t ev_capacity = 0;            // events the device keeps between two drains (0: off, nothing below is allocated)
+    phys::DevBuf<uint32_t> ev_buf;       // 12 words = one phys_contact_event per slot
+    phys::DevBuf<uint32_t> ev_matched;   // per manifold slot of the previous update: the stamp of the update that found its pair again
+    phys::DevBuf<uint32_t> ev_state;     // 4 words: the 64-bit event cursor and the manifold counts of the last two updates (events.hip EventState)
+    uint32_t ev_stamp = 0;               // updates with events so far (never 0 once one ran; wrap: launch_events)
+    uint32_t ev_parity = 0;              // which of the two count words the next update writes
     // multi-GPU halo
     phys::DevBuf<uint32_t> cross_pairs;
     uint64_t max_cross_pairs = 0;

@@ -5,7 +5,11 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import STAGE_NAMES, PhysDeviceView, PhysProfile, PhysStats, f32p, i16p, u16p, u32p
+from ._abi import STAGE_NAMES, PhysContactEvent, PhysDeviceView, PhysProfile, PhysStats, f32p, i16p, u16p, u32p
+
+# one phys_contact_event as a numpy record (the layout of _abi.PhysContactEvent, 48 bytes)
+CONTACT_EVENT_DTYPE = np.dtype([("body_a", "<u4"), ("body_b", "<u4"), ("kind", "<u4"), ("step", "<u4"), ("point", "<f4", (3,)),
+                                ("impulse", "<f4"), ("normal", "<f4", (3,)), ("reserved", "<u4")])
 
 
 class PhysError(RuntimeError):
@@ -440,6 +444,36 @@ class World:
             self._ck(self.lib.phys_get_manifolds(self.h, _p(ids, u32p), _p(counts, u32p), _p(normals), _p(points), m,
                                                  C.byref(n)))
         return ids, counts, normals, points
+
+    # ---- contact events (include/physics_hip.h): what began / stopped touching per update, and the solver's impulses
+    def enable_contact_events(self, capacity):
+        """Keep up to `capacity` contact events on the device between two drains (phys_contact_events_enable); 0 turns
+        events off. A new capacity drops the events not yet drained."""
+        self._ck(self.lib.phys_contact_events_enable(self.h, int(capacity)))
+
+    def get_contact_events(self):
+        """(events, n_dropped): every event stored since the last drain as a structured array (CONTACT_EVENT_DTYPE: body_a,
+        body_b, kind CONTACT_BEGIN / CONTACT_END, step, point, impulse, normal), sorted by (step, kind, body_a, body_b),
+        and the number of events that did not fit the device buffer. Empties the buffer."""
+        n, dropped = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.phys_get_contact_events(self.h, None, 0, C.byref(n), C.byref(dropped)))  # count only
+        while True:
+            out = np.zeros(n.value, CONTACT_EVENT_DTYPE)
+            rc = self.lib.phys_get_contact_events(self.h, out.ctypes.data_as(C.POINTER(PhysContactEvent)), out.shape[0],
+                                                  C.byref(n), C.byref(dropped))
+            if rc != _abi.PHYS_ERR_CAPACITY:  # (more than counted: another thread stepped the world in between; resize)
+                self._ck(rc)
+                return out[:n.value], dropped.value
+
+    def get_contact_impulses(self):
+        """(M, 4, 3) float32: {pn, pt0, pt1} the last update's solve ended with, per point slot of every manifold (zeros beyond
+        its count), row for row in get_manifolds' order."""
+        n = C.c_uint64()
+        self._ck(self.lib.phys_get_contact_impulses(self.h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 4, 3), np.float32)
+        if n.value:
+            self._ck(self.lib.phys_get_contact_impulses(self.h, _p(out), n.value, C.byref(n)))
+        return out
 
     def get_color_counts(self):
         out = np.zeros(64, np.uint32)

@@ -29,6 +29,9 @@ pub const PHYS_FLAG_EXCLUSIVE_GPU: u32 = 0x80;
 pub const PHYS_FLAG_NO_WARM_START: u32 = 0x100;
 pub const PHYS_RAY_MISS: u32 = 0xFFFF_FFFE;
 pub const PHYS_RAY_GROUND: u32 = 0xFFFF_FFFF;
+// contact events: phys_contact_event.kind
+pub const PHYS_CONTACT_BEGIN: u32 = 1;
+pub const PHYS_CONTACT_END: u32 = 2;
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -72,6 +75,21 @@ pub struct phys_stats {
     pub n_cross_pairs: u64,
     pub n_ghosts: u32,
     pub n_new_manifolds: u32,
+}
+
+/// One contact event (48 bytes): a pair that began (BEGIN: deepest point, normal, summed normal impulse) or stopped
+/// (END: zeros) touching in update `step`
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct phys_contact_event {
+    pub body_a: u32,
+    pub body_b: u32,
+    pub kind: u32,
+    pub step: u32,
+    pub point: [f32; 3],
+    pub impulse: f32,
+    pub normal: [f32; 3],
+    pub reserved: u32,
 }
 
 #[repr(C)]
@@ -181,6 +199,9 @@ extern "C" {
                                  half_extent: *const f32, ignore_body: *const u32, query_mask: *const u16, cap: u64,
                                  offsets_out: *mut u64, ids_out: *mut u32) -> i32;
     pub fn phys_get_static_stats(w: *mut phys_world, n_static: *mut u64, n_static_pairs: *mut u64, n_static_manifolds: *mut u64) -> i32;
+    pub fn phys_contact_events_enable(w: *mut phys_world, capacity: u64) -> i32;
+    pub fn phys_get_contact_events(w: *mut phys_world, out: *mut phys_contact_event, cap: u64, n: *mut u64, n_dropped: *mut u64) -> i32;
+    pub fn phys_get_contact_impulses(w: *mut phys_world, out: *mut f32, cap: u64, n_manifolds: *mut u64) -> i32;
     pub fn phys_profile_enable(w: *mut phys_world, on: i32) -> i32;
     pub fn phys_profile_get(w: *mut phys_world, out: *mut phys_profile) -> i32;
     pub fn phys_get_device_view(w: *mut phys_world, out: *mut phys_device_view) -> i32;
