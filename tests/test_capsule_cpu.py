@@ -1,6 +1,10 @@
 """CPU: the capsule shape on every surface (C header, Python, Rust shim, C++ host mirror), static capsules accepted and
 invalid ones refused before any device is touched, and the spec's capsule contacts (through the oracle) against the
-float64 reference of capsule_ref on random pairs."""
+float64 reference of capsule_ref on random pairs.
+
+What this file leaves out - pairs without a contact, cores inside the box, near-parallel capsules, the swapped index
+order, static partners, the second point on a face - is covered by tests/shape_pair_ref.py: tests/test_shape_pairs_cpu.py
+runs its checks through the oracle, tests/test_gpu_shape_pairs.py on the GPU's own manifolds."""
 import os
 import re
 
