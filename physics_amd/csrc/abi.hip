@@ -140,11 +140,6 @@ const DebugSwitches& debug_switches() {
 }
 }  // namespace phys
 
-static int32_t fail(int32_t code, const char* msg) {
-    set_error(msg);
-    return code;
-}
-
 // std::time::Duration::as_secs_f32 (used at rigid_body.rs:25)
 static float duration_as_secs_f32(uint64_t nanos_total) {
     const uint64_t secs = nanos_total / 1000000000ull;
@@ -152,11 +147,71 @@ static float duration_as_secs_f32(uint64_t nanos_total) {
     return (float)secs + (float)nanos / 1.0e9f;
 }
 
-#define ENTER(w)                                                                    \
-    do {                                                                            \
-        if (!(w)) return fail(PHYS_ERR_INVALID_ARG, "null world");                  \
-        PHYS_HIP_TRY(hipSetDevice((w)->device));                                    \
-    } while (0)
+// The one teardown of a world, also of a half-made one (phys_create's failure paths): nothing is released while work on
+// the stream can still touch it; the device buffers go with the members, after this body.
+phys_world::~phys_world() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    prof.destroy();
+    for (int k = 0; k < kSnapRing; ++k) {
+        if (h_snap[k]) (void)hipHostFree(h_snap[k]);
+        if (snap_event[k]) (void)hipEventDestroy(snap_event[k]);
+    }
+    if (h_counters) (void)hipHostFree(h_counters);
+    if (stream) (void)hipStreamDestroy(stream);
+}
+
+// a {word, word} pair per item (filters, materials), up: ordered behind the updates already enqueued, which keep what they were
+// enqueued with ...
+template <typename T>
+static int32_t upload_pairs(phys_world* w, DevBuf<T>& dst, const std::vector<T>& h, bool& set_flag) {
+    if (!h.empty()) PHYS_HIP_TRY(hipMemcpyAsync(dst.p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // the staging vector dies with the caller
+    set_flag = true;
+    return PHYS_OK;
+}
+// ... and the owned bodies' pairs back down
+template <typename T>
+static int32_t download_body_pairs(phys_world* w, const DevBuf<T>& src, std::vector<T>& h) {
+    h.resize(2 * w->n_owned);
+    if (!h.empty()) PHYS_HIP_TRY(hipMemcpyAsync(h.data(), src.p, sizeof(T) * h.size(), hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    return PHYS_OK;
+}
+
+// The device layout of a call's host arrays: a bump allocator over ONE device buffer. The call declares its arrays in order
+// (add), reserve() sizes the buffer from those declarations, copy() moves every array that is there, one hipMemcpyAsync each.
+struct Staging {
+    struct Array { void* host; size_t bytes, offset; };
+    template <typename T>
+    struct Slot { size_t offset; bool there; };  // what add() gives and at() takes: where an array of T lies, if it is there
+    phys_world* w;
+    DevBuf<uint8_t>& buf;
+    Array arrays[6] = {};
+    int count = 0;
+    size_t total = 0;
+    // `n` elements at the next multiple of `align` bytes; a null array takes no room
+    template <typename T>
+    Slot<T> add(const T* host, size_t n, size_t align = alignof(T)) {
+        if (!host) return {0, false};
+        const size_t offset = (total + align - 1) / align * align;
+        arrays[count++] = {const_cast<T*>(host), n * sizeof(T), offset};
+        total = offset + n * sizeof(T);
+        return {offset, true};
+    }
+    int32_t reserve() { PHYS_HIP_TRY(buf.resize(total)); return PHYS_OK; }
+    // the device array of a slot, null for a null host array (valid after reserve())
+    template <typename T>
+    T* at(Slot<T> s) const { return s.there ? reinterpret_cast<T*>(buf.p + s.offset) : nullptr; }
+    int32_t copy(hipMemcpyKind kind) {
+        for (int k = 0; k < count; ++k) {
+            const Array& a = arrays[k];
+            if (kind == hipMemcpyHostToDevice) PHYS_HIP_TRY(hipMemcpyAsync(buf.p + a.offset, a.host, a.bytes, kind, w->stream));
+            else PHYS_HIP_TRY(hipMemcpyAsync(a.host, buf.p + a.offset, a.bytes, kind, w->stream));
+        }
+        return PHYS_OK;
+    }
+};
 
 extern "C" {
 
@@ -202,7 +257,7 @@ int32_t phys_create(const phys_config* cfg, phys_world** out) {
     w->cfg = *cfg;
     w->device = cfg->device;
     hipError_t e = hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete w; return fail(PHYS_ERR_HIP, "hipStreamCreate failed"); }
+    if (e != hipSuccess) { delete w; return fail(PHYS_ERR_HIP, "hipStreamCreate failed"); }  // ~phys_world: whatever exists by then
     e = w->counters.resize(1);
     if (e == hipSuccess) e = hipHostMalloc((void**)&w->h_counters, sizeof(StepCounters), hipHostMallocDefault);
     if (e == hipSuccess) e = hipMemsetAsync(w->counters.p, 0, sizeof(StepCounters), w->stream);
@@ -216,34 +271,6 @@ int32_t phys_create(const phys_config* cfg, phys_world** out) {
 int32_t phys_destroy(phys_world* w) {
     if (!w) return PHYS_OK;
     phys::g_worlds[w->device & 63].fetch_sub(1);
-    (void)hipSetDevice(w->device);
-    if (w->stream) (void)hipStreamSynchronize(w->stream);
-    DevBuf<float>* fb[] = {&w->pos, &w->rot, &w->vel, &w->force, &w->torque, &w->inv_inertia_diag,
-                           &w->inv_inertia, &w->half_extent, &w->aabb, &w->cg_x, &w->cg_r, &w->cg_p, &w->cg_ap,
-                           &w->cg_rhs, &w->cg_c, &w->cg_scratch, &w->cg_jl, &w->geo, &w->man_geo_prev, &w->man_imp, &w->man_imp_prev, &w->man_geo, &w->row_n,
-                           &w->row_pt, &w->row_tb, &w->row_acc, &w->row_all, &w->flow_vel, &w->sorted_box, &w->slot_box, &w->rc_records, &w->rc_in, &w->rc_out, &w->qr_in,
-                           &w->st_geo, &w->st_rc, &w->st_box, &w->mat, &w->st_mat};
-    for (auto* b : fb) b->free();
-    DevBuf<uint32_t>* ub[] = {&w->shape, &w->global_id, &w->cg_status, &w->bucket_of, &w->bucket_count,
-                              &w->bucket_start, &w->bucket_cursor, &w->sorted_ids, &w->slot_ids, &w->grid_ovf, &w->scan_block_sums, &w->pairs,
-                              &w->man_a, &w->man_b, &w->man_color, &w->row_hdr, &w->halo_block_counts,
-                              &w->man_prev, &w->cluster_slot, &w->cluster_body, &w->body_shared, &w->active_flag, &w->active_rank, &w->seg_count, &w->seg_start, &w->man_rank,
-                              &w->row_src, &w->cross_pairs, &w->color_block_hist, &w->cg_cols,
-                              &w->rc_header, &w->rc_count, &w->rc_start, &w->rc_tile_sum, &w->qr_count, &w->qr_ids,
-                              &w->st_cell_start, &w->st_cell_ids, &w->st_large, &w->st_count, &w->st_block, &w->st_pairs,
-                              &w->filt, &w->st_filt};
-    for (auto* b : ub) b->free();
-    w->man_prio.free(); w->color_state.free(); w->bucket_count.free(); w->step_zero.free();
-    w->d_constraints.free(); w->counters.free();
-    w->ev_buf.free(); w->ev_matched.free(); w->ev_state.free();
-    w->ctab.free(); w->unc_list.free(); w->rc_stats.free(); w->qr_off.free();
-    w->prof.destroy();
-    for (int k = 0; k < phys_world::kSnapRing; ++k) {
-        if (w->h_snap[k]) (void)hipHostFree(w->h_snap[k]);
-        if (w->snap_event[k]) (void)hipEventDestroy(w->snap_event[k]);
-    }
-    if (w->h_counters) (void)hipHostFree(w->h_counters);
-    if (w->stream) (void)hipStreamDestroy(w->stream);
     delete w;
     return PHYS_OK;
 }
@@ -501,7 +528,7 @@ int32_t phys_sync(phys_world* w) {
         PHYS_HIP_TRY(hipMemsetAsync(&w->counters.p->sticky_overflow, 0, sizeof(uint32_t), w->stream));
         PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     }
-    if (bits & 32u) {
+    if (bits & kOvfCorruptRow) {
         const uint32_t* g = w->h_counters->debug;
         return fail(PHYS_ERR_HIP, ("internal error: a solver row names no body of this world and was refused (row " +
                                    std::to_string(g[0]) + ": a " + std::to_string(g[1]) + ", b " + std::to_string(g[2]) + ", points " +
@@ -512,7 +539,7 @@ int32_t phys_sync(phys_world* w) {
         PHYS_HIP_TRY(hipMemsetAsync(w->counters.p->debug, 0, sizeof(w->counters.p->debug), w->stream));
         PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     }
-    if ((bits & 16u) && w->h_counters->debug[0] == 0xC1u) {
+    if ((bits & kOvfHandoff) && w->h_counters->debug[0] == 0xC1u) {
         const uint32_t* g = w->h_counters->debug;  // what the first lane of k_solve_cluster to give up was waiting for
         return fail(PHYS_ERR_HIP, ("contact solver hand-off timed out (k_solve_cluster) in a step since the last phys_sync; velocities "
                                    "are invalid from that step on. First lane to give up: cluster " + std::to_string(g[1] & 0xFFFFu) + " of " + std::to_string(g[1] >> 16) + ", row " +
@@ -523,15 +550,15 @@ int32_t phys_sync(phys_world* w) {
                                    std::to_string((g[7] >> 8) & 0xFFu) + ", colour " + std::to_string(g[7] & 0xFFu) +
                                    ". If other work shares this GPU with phys_update, create the world WITHOUT PHYS_FLAG_EXCLUSIVE_GPU").c_str());
     }
-    if (bits & 16u)
+    if (bits & kOvfHandoff)
         return fail(PHYS_ERR_HIP, "contact solver hand-off timed out (k_solve_flow) in a step since the last phys_sync; "
                                   "velocities are invalid from that step on");
-    if (bits & 4u)
+    if (bits & kOvfColors)
         return fail(PHYS_ERR_CAPACITY, "a body has more than 64 contact manifolds (PHYS_MAX_COLORS): the contact solve of "
                                        "that step was skipped. This limit is not configurable");
-    if (bits & 8u)
+    if (bits & kOvfHalo)
         return fail(PHYS_ERR_CAPACITY, "halo record / cross-pair capacity exceeded in a step since the last phys_sync");
-    if (bits & 64u)
+    if (bits & kOvfColorTable)
         return fail(PHYS_ERR_CAPACITY, "the persistent colour table is full (a look-up or an insert gave up after thousands of "
                                        "slots): the contact solve of that step was skipped. Raise phys_config.max_manifolds");
     if (bits)
@@ -573,13 +600,11 @@ int32_t phys_get_instance_matrices(phys_world* w, float* out) {
     ENTER(w);
     if (!out) return fail(PHYS_ERR_INVALID_ARG, "null output");
     if (w->n == 0) return PHYS_OK;
-    float* d = nullptr;
-    PHYS_HIP_TRY(hipMalloc((void**)&d, 64 * w->n));
-    launch_instance_matrices(w, d);
-    hipError_t e = hipMemcpyAsync(out, d, 64 * w->n_owned, hipMemcpyDeviceToHost, w->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(w->stream);
-    (void)hipFree(d);
-    PHYS_HIP_TRY(e);
+    DevBuf<float> d;  // scratch of this call
+    PHYS_HIP_TRY(d.resize(16 * w->n));
+    launch_instance_matrices(w, d.p);
+    PHYS_HIP_TRY(hipMemcpyAsync(out, d.p, 64 * w->n_owned, hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     return PHYS_OK;
 }
 
@@ -727,40 +752,34 @@ static void pack_filters(uint64_t n, const uint16_t* category, const uint16_t* m
     }
 }
 
-int32_t phys_set_body_filters(phys_world* w, uint64_t n, const uint16_t* category, const uint16_t* mask, const int16_t* group) {
-    ENTER(w);
-    if (n != w->n_owned) return fail(PHYS_ERR_INVALID_ARG, "phys_set_body_filters: n must equal the body count");
+static int32_t set_filters(phys_world* w, DevBuf<uint32_t>& dst, uint64_t expected, bool& set_flag, const char* wrong_count,
+                           uint64_t n, const uint16_t* category, const uint16_t* mask, const int16_t* group) {
+    if (n != expected) return fail(PHYS_ERR_INVALID_ARG, wrong_count);
     std::vector<uint32_t> h;
     pack_filters(n, category, mask, group, h);
-    // ordered behind the updates already enqueued: they keep the filters they were enqueued with
-    if (n) PHYS_HIP_TRY(hipMemcpyAsync(w->filt.p, h.data(), 8 * n, hipMemcpyHostToDevice, w->stream));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // the staging vector dies here
-    w->body_filters_set = true;
-    return PHYS_OK;
+    return upload_pairs(w, dst, h, set_flag);
 }
 
-int32_t phys_get_body_filters(phys_world* w, uint16_t* category_out, uint16_t* mask_out, int16_t* group_out) {
+int32_t phys_set_body_filters(phys_world* w, uint64_t n, const uint16_t* category, const uint16_t* mask, const int16_t* group) {
     ENTER(w);
-    const uint64_t n = w->n_owned;
-    std::vector<uint32_t> h(2 * n);
-    if (n) PHYS_HIP_TRY(hipMemcpyAsync(h.data(), w->filt.p, 8 * n, hipMemcpyDeviceToHost, w->stream));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    for (uint64_t k = 0; k < n; ++k) {
-        if (category_out) category_out[k] = (uint16_t)(h[2 * k] & 0xFFFFu);
-        if (mask_out) mask_out[k] = (uint16_t)(h[2 * k] >> 16);
-        if (group_out) group_out[k] = (int16_t)(uint16_t)h[2 * k + 1];
-    }
-    return PHYS_OK;
+    return set_filters(w, w->filt, w->n_owned, w->body_filters_set, "phys_set_body_filters: n must equal the body count", n, category, mask, group);
 }
 
 int32_t phys_set_static_filters(phys_world* w, uint64_t n, const uint16_t* category, const uint16_t* mask, const int16_t* group) {
     ENTER(w);
-    if (n != w->n_static) return fail(PHYS_ERR_INVALID_ARG, "phys_set_static_filters: n must equal the static collider count");
+    return set_filters(w, w->st_filt, w->n_static, w->static_filters_set, "phys_set_static_filters: n must equal the static collider count", n,
+                       category, mask, group);
+}
+
+int32_t phys_get_body_filters(phys_world* w, uint16_t* category_out, uint16_t* mask_out, int16_t* group_out) {
+    ENTER(w);
     std::vector<uint32_t> h;
-    pack_filters(n, category, mask, group, h);
-    if (n) PHYS_HIP_TRY(hipMemcpyAsync(w->st_filt.p, h.data(), 8 * n, hipMemcpyHostToDevice, w->stream));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    w->static_filters_set = true;
+    const int32_t rc = download_body_pairs(w, w->filt, h); if (rc) return rc;
+    for (uint64_t k = 0; k < w->n_owned; ++k) {
+        if (category_out) category_out[k] = (uint16_t)(h[2 * k] & 0xFFFFu);
+        if (mask_out) mask_out[k] = (uint16_t)(h[2 * k] >> 16);
+        if (group_out) group_out[k] = (int16_t)(uint16_t)h[2 * k + 1];
+    }
     return PHYS_OK;
 }
 
@@ -787,42 +806,35 @@ static const char* const kMaterialRange = "a friction must be finite and >= 0, a
 #define PHYS_NO_MATERIALS_WHEN_SHARDED(w) \
     do { if ((w)->cfg.max_ghosts > 0) return fail(PHYS_ERR_UNSUPPORTED, "materials are not supported in a world with max_ghosts > 0"); } while (0)
 
-int32_t phys_set_body_materials(phys_world* w, uint64_t n, const float* friction, const float* restitution) {
-    ENTER(w);
+static int32_t set_materials(phys_world* w, DevBuf<float>& dst, uint64_t expected, bool& set_flag, const char* wrong_count, uint64_t n,
+                             const float* friction, const float* restitution) {
     PHYS_NO_MATERIALS_WHEN_SHARDED(w);
-    if (n != w->n_owned) return fail(PHYS_ERR_INVALID_ARG, "phys_set_body_materials: n must equal the body count");
+    if (n != expected) return fail(PHYS_ERR_INVALID_ARG, wrong_count);
     std::vector<float> h;
     if (!pack_materials(n, friction, restitution, w->cfg.friction, h)) return fail(PHYS_ERR_INVALID_ARG, kMaterialRange);
-    // ordered behind the updates already enqueued: they keep the materials they were enqueued with
-    if (n) PHYS_HIP_TRY(hipMemcpyAsync(w->mat.p, h.data(), 8 * n, hipMemcpyHostToDevice, w->stream));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // the staging vector dies here
-    w->body_materials_set = true;
-    return PHYS_OK;
+    return upload_pairs(w, dst, h, set_flag);
+}
+
+int32_t phys_set_body_materials(phys_world* w, uint64_t n, const float* friction, const float* restitution) {
+    ENTER(w);
+    return set_materials(w, w->mat, w->n_owned, w->body_materials_set, "phys_set_body_materials: n must equal the body count", n, friction, restitution);
+}
+
+int32_t phys_set_static_materials(phys_world* w, uint64_t n, const float* friction, const float* restitution) {
+    ENTER(w);
+    return set_materials(w, w->st_mat, w->n_static, w->static_materials_set, "phys_set_static_materials: n must equal the static collider count", n,
+                         friction, restitution);
 }
 
 int32_t phys_get_body_materials(phys_world* w, float* friction_out, float* restitution_out) {
     ENTER(w);
     PHYS_NO_MATERIALS_WHEN_SHARDED(w);
-    const uint64_t n = w->n_owned;
-    std::vector<float> h(2 * n);
-    if (n) PHYS_HIP_TRY(hipMemcpyAsync(h.data(), w->mat.p, 8 * n, hipMemcpyDeviceToHost, w->stream));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    for (uint64_t k = 0; k < n; ++k) {
+    std::vector<float> h;
+    const int32_t rc = download_body_pairs(w, w->mat, h); if (rc) return rc;
+    for (uint64_t k = 0; k < w->n_owned; ++k) {
         if (friction_out) friction_out[k] = h[2 * k];
         if (restitution_out) restitution_out[k] = h[2 * k + 1];
     }
-    return PHYS_OK;
-}
-
-int32_t phys_set_static_materials(phys_world* w, uint64_t n, const float* friction, const float* restitution) {
-    ENTER(w);
-    PHYS_NO_MATERIALS_WHEN_SHARDED(w);
-    if (n != w->n_static) return fail(PHYS_ERR_INVALID_ARG, "phys_set_static_materials: n must equal the static collider count");
-    std::vector<float> h;
-    if (!pack_materials(n, friction, restitution, w->cfg.friction, h)) return fail(PHYS_ERR_INVALID_ARG, kMaterialRange);
-    if (n) PHYS_HIP_TRY(hipMemcpyAsync(w->st_mat.p, h.data(), 8 * n, hipMemcpyHostToDevice, w->stream));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    w->static_materials_set = true;
     return PHYS_OK;
 }
 
@@ -891,140 +903,93 @@ int32_t phys_get_device_view(phys_world* w, phys_device_view* out) {
     return PHYS_OK;
 }
 
-static int32_t raycast_args(uint64_t n_rays, const float* origin, const float* dir, const uint32_t* body_out, const float* t_out) {
-    if (n_rays >= (1ull << 31)) return fail(PHYS_ERR_INVALID_ARG, "phys_raycast: n_rays must be below 2^31");
-    if (n_rays && (!origin || !dir || !body_out || !t_out)) return fail(PHYS_ERR_INVALID_ARG, "phys_raycast: null origin, dir, body_out or t_out");
+// ---- queries: ray casts, sphere casts, overlaps ----
+// what every cast entry point checks; `sphere`: the phys_spherecast family (radius required), phys_raycast's otherwise
+static int32_t cast_args(bool sphere, uint64_t n, const float* origin, const float* dir, const float* radius, const uint32_t* body_out,
+                         const float* t_out) {
+    if (n >= (1ull << 31))
+        return fail(PHYS_ERR_INVALID_ARG, sphere ? "phys_spherecast: n must be below 2^31" : "phys_raycast: n_rays must be below 2^31");
+    if (n && (!origin || !dir || (sphere && !radius) || !body_out || !t_out))
+        return fail(PHYS_ERR_INVALID_ARG, sphere ? "phys_spherecast: null origin, dir, radius, body_out or t_out"
+                                                 : "phys_raycast: null origin, dir, body_out or t_out");
     return PHYS_OK;
 }
 
-// host arrays; query_mask NULL: the plain call
-static int32_t raycast_host(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
-                            const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out) {
+// casts on device arrays: checked, then enqueued. radius null: rays (raycast.hip launch_trace); query_mask null: the plain call
+static int32_t cast_device(phys_world* w, bool sphere, uint64_t n, const float* origin, const float* dir, const float* radius,
+                           const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
+                           float* normal_out) {
     ENTER(w);
-    int32_t rc = raycast_args(n_rays, origin, dir, body_out, t_out); if (rc) return rc;
-    if (n_rays == 0) return PHYS_OK;
-    // staging: in = origin 3n | dir 3n | max_t n | ignore n [| query mask n u16], out = t n | body n | normal 3n (4-byte words)
-    const size_t n = (size_t)n_rays;
-    PHYS_HIP_TRY(w->rc_in.resize(query_mask ? 8 * n + (n + 1) / 2 : 8 * n));
-    PHYS_HIP_TRY(w->rc_out.resize(5 * n));
-    hipStream_t s = w->stream;
-    float* d_origin = w->rc_in.p;
-    float* d_dir = d_origin + 3 * n;
-    float* d_max_t = max_t ? d_dir + 3 * n : nullptr;
-    uint32_t* d_ignore = ignore_body ? reinterpret_cast<uint32_t*>(d_dir + 4 * n) : nullptr;
-    float* d_t = w->rc_out.p;
-    uint32_t* d_body = reinterpret_cast<uint32_t*>(d_t + n);
-    float* d_normal = normal_out ? d_t + 2 * n : nullptr;
-    PHYS_HIP_TRY(hipMemcpyAsync(d_origin, origin, 12 * n, hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(d_dir, dir, 12 * n, hipMemcpyHostToDevice, s));
-    if (d_max_t) PHYS_HIP_TRY(hipMemcpyAsync(d_max_t, max_t, 4 * n, hipMemcpyHostToDevice, s));
-    if (d_ignore) PHYS_HIP_TRY(hipMemcpyAsync(d_ignore, ignore_body, 4 * n, hipMemcpyHostToDevice, s));
-    uint16_t* d_qmask = query_mask ? reinterpret_cast<uint16_t*>(d_origin + 8 * n) : nullptr;
-    if (d_qmask) PHYS_HIP_TRY(hipMemcpyAsync(d_qmask, query_mask, 2 * n, hipMemcpyHostToDevice, s));
-    rc = launch_raycast(w, n_rays, d_origin, d_dir, d_max_t, d_ignore, d_body, d_t, d_normal, d_qmask); if (rc) return rc;
-    rc = d2h(w, body_out, d_body, 4 * n); if (rc) return rc;
-    rc = d2h(w, t_out, d_t, 4 * n); if (rc) return rc;
-    if (normal_out) { rc = d2h(w, normal_out, d_normal, 12 * n); if (rc) return rc; }
-    PHYS_HIP_TRY(hipStreamSynchronize(s));
+    const int32_t rc = cast_args(sphere, n, origin, dir, radius, body_out, t_out); if (rc) return rc;
+    if (n == 0) return PHYS_OK;
+    return launch_trace(w, n, origin, dir, radius, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
+}
+
+// casts on host arrays: staged, traced, read back; synchronises
+static int32_t cast_host(phys_world* w, bool sphere, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
+                         const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out) {
+    ENTER(w);
+    int32_t rc = cast_args(sphere, n, origin, dir, radius, body_out, t_out); if (rc) return rc;
+    if (n == 0) return PHYS_OK;
+    Staging in{w, w->stage}, out{w, w->rc_out};
+    const auto s_origin = in.add(origin, 3 * n), s_dir = in.add(dir, 3 * n), s_radius = in.add(radius, n), s_max_t = in.add(max_t, n);
+    const auto s_ignore = in.add(ignore_body, n);
+    const auto s_mask = in.add(query_mask, n);
+    const auto s_body = out.add(body_out, n);
+    const auto s_t = out.add(t_out, n), s_normal = out.add(normal_out, 3 * n);
+    rc = in.reserve(); if (rc) return rc;
+    rc = out.reserve(); if (rc) return rc;
+    rc = in.copy(hipMemcpyHostToDevice); if (rc) return rc;
+    rc = launch_trace(w, n, in.at(s_origin), in.at(s_dir), in.at(s_radius), in.at(s_max_t), in.at(s_ignore), out.at(s_body), out.at(s_t),
+                      out.at(s_normal), in.at(s_mask));
+    if (rc) return rc;
+    rc = out.copy(hipMemcpyDeviceToHost); if (rc) return rc;
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     return PHYS_OK;
 }
 
 int32_t phys_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                      const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    return raycast_host(w, n_rays, origin, dir, max_t, ignore_body, nullptr, body_out, t_out, normal_out);
+    return cast_host(w, false, n_rays, origin, dir, nullptr, max_t, ignore_body, nullptr, body_out, t_out, normal_out);
 }
 
 int32_t phys_raycast_filtered(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                               const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
                               float* normal_out) {
-    return raycast_host(w, n_rays, origin, dir, max_t, ignore_body, query_mask, body_out, t_out, normal_out);
+    return cast_host(w, false, n_rays, origin, dir, nullptr, max_t, ignore_body, query_mask, body_out, t_out, normal_out);
 }
 
 int32_t phys_raycast_device(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                             const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    ENTER(w);
-    int32_t rc = raycast_args(n_rays, origin, dir, body_out, t_out); if (rc) return rc;
-    if (n_rays == 0) return PHYS_OK;
-    return launch_raycast(w, n_rays, origin, dir, max_t, ignore_body, body_out, t_out, normal_out);
+    return cast_device(w, false, n_rays, origin, dir, nullptr, max_t, ignore_body, nullptr, body_out, t_out, normal_out);
 }
 
 int32_t phys_raycast_device_filtered(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                                      const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
                                      float* normal_out) {
-    ENTER(w);
-    int32_t rc = raycast_args(n_rays, origin, dir, body_out, t_out); if (rc) return rc;
-    if (n_rays == 0) return PHYS_OK;
-    return launch_raycast(w, n_rays, origin, dir, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
-}
-
-static int32_t spherecast_args(uint64_t n, const float* origin, const float* dir, const float* radius, const uint32_t* body_out,
-                               const float* t_out) {
-    if (n >= (1ull << 31)) return fail(PHYS_ERR_INVALID_ARG, "phys_spherecast: n must be below 2^31");
-    if (n && (!origin || !dir || !radius || !body_out || !t_out))
-        return fail(PHYS_ERR_INVALID_ARG, "phys_spherecast: null origin, dir, radius, body_out or t_out");
-    return PHYS_OK;
-}
-
-static int32_t spherecast_host(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
-                               const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
-                               float* normal_out) {
-    ENTER(w);
-    int32_t rc = spherecast_args(n, origin, dir, radius, body_out, t_out); if (rc) return rc;
-    if (n == 0) return PHYS_OK;
-    // staging: in = origin 3n | dir 3n | radius n | max_t n | ignore n [| query mask n u16], out = t n | body n | normal 3n
-    const size_t m = (size_t)n;
-    PHYS_HIP_TRY(w->qr_in.resize(query_mask ? 9 * m + (m + 1) / 2 : 9 * m));
-    PHYS_HIP_TRY(w->rc_out.resize(5 * m));
-    hipStream_t s = w->stream;
-    float* d_origin = w->qr_in.p;
-    float* d_dir = d_origin + 3 * m;
-    float* d_radius = d_dir + 3 * m;
-    float* d_max_t = max_t ? d_radius + m : nullptr;
-    uint32_t* d_ignore = ignore_body ? reinterpret_cast<uint32_t*>(d_radius + 2 * m) : nullptr;
-    float* d_t = w->rc_out.p;
-    uint32_t* d_body = reinterpret_cast<uint32_t*>(d_t + m);
-    float* d_normal = normal_out ? d_t + 2 * m : nullptr;
-    PHYS_HIP_TRY(hipMemcpyAsync(d_origin, origin, 12 * m, hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(d_dir, dir, 12 * m, hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(d_radius, radius, 4 * m, hipMemcpyHostToDevice, s));
-    if (d_max_t) PHYS_HIP_TRY(hipMemcpyAsync(d_max_t, max_t, 4 * m, hipMemcpyHostToDevice, s));
-    if (d_ignore) PHYS_HIP_TRY(hipMemcpyAsync(d_ignore, ignore_body, 4 * m, hipMemcpyHostToDevice, s));
-    uint16_t* d_qmask = query_mask ? reinterpret_cast<uint16_t*>(d_origin + 9 * m) : nullptr;
-    if (d_qmask) PHYS_HIP_TRY(hipMemcpyAsync(d_qmask, query_mask, 2 * m, hipMemcpyHostToDevice, s));
-    rc = launch_spherecast(w, n, d_origin, d_dir, d_radius, d_max_t, d_ignore, d_body, d_t, d_normal, d_qmask); if (rc) return rc;
-    rc = d2h(w, body_out, d_body, 4 * m); if (rc) return rc;
-    rc = d2h(w, t_out, d_t, 4 * m); if (rc) return rc;
-    if (normal_out) { rc = d2h(w, normal_out, d_normal, 12 * m); if (rc) return rc; }
-    PHYS_HIP_TRY(hipStreamSynchronize(s));
-    return PHYS_OK;
+    return cast_device(w, false, n_rays, origin, dir, nullptr, max_t, ignore_body, query_mask, body_out, t_out, normal_out);
 }
 
 int32_t phys_spherecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
                         const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    return spherecast_host(w, n, origin, dir, radius, max_t, ignore_body, nullptr, body_out, t_out, normal_out);
+    return cast_host(w, true, n, origin, dir, radius, max_t, ignore_body, nullptr, body_out, t_out, normal_out);
 }
 
 int32_t phys_spherecast_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius,
                                  const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out,
                                  float* t_out, float* normal_out) {
-    return spherecast_host(w, n, origin, dir, radius, max_t, ignore_body, query_mask, body_out, t_out, normal_out);
+    return cast_host(w, true, n, origin, dir, radius, max_t, ignore_body, query_mask, body_out, t_out, normal_out);
 }
 
 int32_t phys_spherecast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
                                const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    ENTER(w);
-    int32_t rc = spherecast_args(n, origin, dir, radius, body_out, t_out); if (rc) return rc;
-    if (n == 0) return PHYS_OK;
-    return launch_spherecast(w, n, origin, dir, radius, max_t, ignore_body, body_out, t_out, normal_out);
+    return cast_device(w, true, n, origin, dir, radius, max_t, ignore_body, nullptr, body_out, t_out, normal_out);
 }
 
 int32_t phys_spherecast_device_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius,
                                         const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask,
                                         uint32_t* body_out, float* t_out, float* normal_out) {
-    ENTER(w);
-    int32_t rc = spherecast_args(n, origin, dir, radius, body_out, t_out); if (rc) return rc;
-    if (n == 0) return PHYS_OK;
-    return launch_spherecast(w, n, origin, dir, radius, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
+    return cast_device(w, true, n, origin, dir, radius, max_t, ignore_body, query_mask, body_out, t_out, normal_out);
 }
 
 static int32_t overlap_host(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,
@@ -1037,23 +1002,15 @@ static int32_t overlap_host(phys_world* w, uint64_t n, const uint32_t* shape_typ
     if (cap && !ids_out) return fail(PHYS_ERR_INVALID_ARG, "phys_overlap: null ids_out with cap > 0");
     offsets_out[0] = 0;
     if (n == 0) return PHYS_OK;
-    // staging: type n | pos 3n | half extent 3n | ignore n | rot 4n (rot 16-byte aligned: read as float4) [| query mask n u16]
-    const size_t m = (size_t)n;
-    PHYS_HIP_TRY(w->qr_in.resize(query_mask ? 8 * m + 4 * m + 4 + (m + 1) / 2 : 8 * m + 4 * m + 4));
-    hipStream_t s = w->stream;
-    uint32_t* d_type = reinterpret_cast<uint32_t*>(w->qr_in.p);
-    float* d_pos = w->qr_in.p + m;
-    float* d_he = d_pos + 3 * m;
-    uint32_t* d_ignore = ignore_body ? reinterpret_cast<uint32_t*>(d_he + 3 * m) : nullptr;
-    float* d_rot = rot_ijkw ? w->qr_in.p + ((8 * m + 3) & ~(size_t)3) : nullptr;
-    PHYS_HIP_TRY(hipMemcpyAsync(d_type, shape_type, 4 * m, hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(d_pos, pos, 12 * m, hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(d_he, half_extent, 12 * m, hipMemcpyHostToDevice, s));
-    if (d_ignore) PHYS_HIP_TRY(hipMemcpyAsync(d_ignore, ignore_body, 4 * m, hipMemcpyHostToDevice, s));
-    if (d_rot) PHYS_HIP_TRY(hipMemcpyAsync(d_rot, rot_ijkw, 16 * m, hipMemcpyHostToDevice, s));
-    uint16_t* d_qmask = query_mask ? reinterpret_cast<uint16_t*>(w->qr_in.p + 8 * m + 4 * m + 4) : nullptr;
-    if (d_qmask) PHYS_HIP_TRY(hipMemcpyAsync(d_qmask, query_mask, 2 * m, hipMemcpyHostToDevice, s));
-    return launch_overlap(w, n, d_type, d_pos, d_rot, d_he, d_ignore, cap, offsets_out, ids_out, d_qmask);
+    Staging in{w, w->stage};
+    const auto s_type = in.add(shape_type, n);
+    const auto s_pos = in.add(pos, 3 * n), s_he = in.add(half_extent, 3 * n);
+    const auto s_ignore = in.add(ignore_body, n);
+    const auto s_rot = in.add(rot_ijkw, 4 * n, /*align=*/16);  // read as float4
+    const auto s_mask = in.add(query_mask, n);
+    int32_t rc = in.reserve(); if (rc) return rc;
+    rc = in.copy(hipMemcpyHostToDevice); if (rc) return rc;
+    return launch_overlap(w, n, in.at(s_type), in.at(s_pos), in.at(s_rot), in.at(s_he), in.at(s_ignore), cap, offsets_out, ids_out, in.at(s_mask));
 }
 
 int32_t phys_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,

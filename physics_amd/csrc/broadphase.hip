@@ -305,7 +305,7 @@ __device__ __forceinline__ void stage_flush(PairStage& st, uint32_t* __restrict_
     if (lane == 0) base = atomicAdd(&ctr->n_pairs, st.count);
     base = (uint32_t)__shfl((int)base, 0, 64);
     if ((uint64_t)base + st.count > max_pairs) {
-        if (lane == 0) flag_overflow(ctr, 1u);
+        if (lane == 0) flag_overflow(ctr, kOvfPairs);
     }
     for (uint32_t k = lane; k < st.count; k += 64) {
         const uint64_t dst = (uint64_t)base + k;
@@ -445,7 +445,7 @@ __device__ __forceinline__ void workgroup_flush(PairStage& st, uint32_t* s_cnt, 
     const bool go = total != 0u && (force || total >= (uint32_t)(2 * kBrickStagePerWave));  // workgroup-uniform
     if (go && threadIdx.x == 0) {
         const uint32_t base = atomicAdd(&ctr->n_pairs, total);
-        if ((uint64_t)base + total > max_pairs) flag_overflow(ctr, 1u);
+        if ((uint64_t)base + total > max_pairs) flag_overflow(ctr, kOvfPairs);
         *s_base = base;
     }
     __syncthreads();
@@ -799,8 +799,7 @@ int32_t collision_alloc(phys_world* w) {
         // one allocation, zeroed by one memset per step: [bucket counts | colouring state | StepCounters]
         const size_t b_bytes = ((size_t)T * 4 + 255) / 256 * 256;
         const size_t c_bytes = (w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY) ? 0 : ((size_t)4 * n * 8 + 255) / 256 * 256;
-        w->counters.free(); w->bucket_count.free(); w->color_state.free();
-        w->step_zero.free();
+        w->step_zero.free();  // a block of exactly this size
         PHYS_HIP_TRY(w->step_zero.resize(b_bytes + c_bytes + sizeof(StepCounters)));
         w->bucket_count.point_at(reinterpret_cast<uint32_t*>(w->step_zero.p), T);
         w->color_state.point_at(reinterpret_cast<unsigned long long*>(w->step_zero.p + b_bytes), c_bytes / 8);
@@ -847,15 +846,14 @@ int32_t collision_alloc(phys_world* w) {
             w->color_epoch = 0;
         }
         PHYS_HIP_TRY(w->color_block_hist.resize((size_t)kMaxColors * 512));
-        w->row_hdr.free(); w->row_n.free(); w->row_tb.free(); w->row_pt.free(); w->row_acc.free();
-        w->row_all.free();
+        w->row_all.free();  // exactly 16 planes of M rows
         PHYS_HIP_TRY(w->row_all.resize(64 * M));  // 16 planes x M x float4
         w->row_hdr.point_at(reinterpret_cast<uint32_t*>(w->row_all.p), 4 * M);
         w->row_n.point_at(w->row_all.p + 4 * M, 4 * M);
         w->row_tb.point_at(w->row_all.p + 8 * M, 8 * M);
         w->row_pt.point_at(w->row_all.p + 16 * M, 32 * M);
         w->row_acc.point_at(w->row_all.p + 48 * M, 16 * M);
-        w->flow_vel.free();
+        w->flow_vel.free();  // null unless allocated below: per-colour launches only
         // the dataflow solver addresses row_acc / flow_vel through 32-bit buffer offsets
         if (!(w->cfg.flags & PHYS_FLAG_SOLVER_PER_COLOR) && 64 * M < 0xFFFFFFFFull && 32 * n < 0xFFFFFFFFull) {
             PHYS_HIP_TRY(w->flow_vel.resize(8 * n));
@@ -1006,7 +1004,7 @@ void launch_broadphase(phys_world* w) {
 int32_t sorted_pairs_to_host(phys_world* w, uint32_t* pairs_out, uint64_t cap, uint64_t* n_pairs) {
     PHYS_HIP_TRY(hipMemcpyAsync(w->h_counters, w->counters.p, sizeof(StepCounters), hipMemcpyDeviceToHost, w->stream));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    if (w->h_counters->overflow & 1u) {
+    if (w->h_counters->overflow & kOvfPairs) {
         set_error("pair capacity exceeded: raise phys_config.max_pairs");
         return PHYS_ERR_CAPACITY;
     }

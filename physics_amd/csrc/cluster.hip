@@ -471,7 +471,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                     if (in >= gridDim.x) {
                         atomicCAS(&ctr->cluster_state[attempt], 0u, 1u);
                     } else if (wall_clock64() - t0 > arrive_ticks) {
-                        if (atomicCAS(&ctr->cluster_state[attempt], 0u, 2u) == 0u && last_attempt) flag_overflow(ctr, 16u);
+                        if (atomicCAS(&ctr->cluster_state[attempt], 0u, 2u) == 0u && last_attempt) flag_overflow(ctr, kOvfHandoff);
                     } else {
                         __builtin_amdgcn_s_sleep(16);
                     }
@@ -634,10 +634,10 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                         __builtin_amdgcn_s_sleep(kPollSleep);
                         if ((++sweeps & 63u) == 0u) {
                             const bool gone = (wall_clock64() - t_start > timeout_ticks) ||
-                                              (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 16u);
+                                              (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kOvfHandoff);
                             if (gone) {
                                 late = (needA ? 1u : 0u) | (needB ? 2u : 0u);
-                                flag_overflow(ctr, 16u); dead = true; needA = false; needB = false;
+                                flag_overflow(ctr, kOvfHandoff); dead = true; needA = false; needB = false;
                             }
                         }
                     }

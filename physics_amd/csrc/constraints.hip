@@ -374,10 +374,8 @@ extern "C" int32_t phys_block_spmv(int32_t device, uint64_t nrows, uint64_t ncol
         return PHYS_ERR_NO_DEVICE;
     }
     PHYS_HIP_TRY(hipSetDevice(device));
-    DevBuf<uint8_t> d_blk, d_data, d_vec, d_out;
+    DevBuf<uint8_t> d_blk, d_data, d_vec, d_out;  // freed on every way out
     DevBuf<uint32_t> d_ptr, d_eb, d_el;
-    struct Free { DevBuf<uint8_t>*a, *b, *c, *d; DevBuf<uint32_t>*e, *f, *g; ~Free() { a->free(); b->free(); c->free(); d->free(); e->free(); f->free(); g->free(); } }
-        cleanup{&d_blk, &d_data, &d_vec, &d_out, &d_ptr, &d_eb, &d_el};
     PHYS_HIP_TRY(d_blk.resize(std::max<size_t>(blk.size(), 1) * sizeof(BlockDesc)));
     PHYS_HIP_TRY(d_data.resize(std::max<size_t>(off, 1) * 4)); PHYS_HIP_TRY(d_vec.resize(std::max<size_t>(vec_len, 1) * 4)); PHYS_HIP_TRY(d_out.resize(n_out * 4));
     PHYS_HIP_TRY(d_ptr.resize(n_out + 1)); PHYS_HIP_TRY(d_eb.resize(entry_blk.size())); PHYS_HIP_TRY(d_el.resize(entry_loc.size()));

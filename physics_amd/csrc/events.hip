@@ -179,23 +179,17 @@ void launch_events(phys_world* w, uint32_t step) {
 
 using namespace phys;
 
-static int32_t ev_fail(int32_t code, const char* msg) {
-    set_error(msg);
-    return code;
-}
-
 extern "C" {
 
 int32_t phys_contact_events_enable(phys_world* w, uint64_t capacity) {
-    if (!w) return ev_fail(PHYS_ERR_INVALID_ARG, "null world");
-    PHYS_HIP_TRY(hipSetDevice(w->device));
-    if (capacity >= (1ull << 31)) return ev_fail(PHYS_ERR_INVALID_ARG, "phys_contact_events_enable: capacity must be below 2^31");
+    ENTER(w);
+    if (capacity >= (1ull << 31)) return fail(PHYS_ERR_INVALID_ARG, "phys_contact_events_enable: capacity must be below 2^31");
     if (!(w->cfg.flags & PHYS_FLAG_COLLISIONS) || (w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY))
-        return ev_fail(PHYS_ERR_UNSUPPORTED, "contact events need PHYS_FLAG_COLLISIONS without PHYS_FLAG_BROADPHASE_ONLY");
+        return fail(PHYS_ERR_UNSUPPORTED, "contact events need PHYS_FLAG_COLLISIONS without PHYS_FLAG_BROADPHASE_ONLY");
     // the previous update's records and the impulse records exist only in worlds with warm starting (w->warm once bodies are set)
     const uint64_t cap_cfg = w->cfg.max_manifolds;
     if ((w->cfg.flags & PHYS_FLAG_NO_WARM_START) || (w->n ? !w->warm : cap_cfg >= (1ull << 26)))
-        return ev_fail(PHYS_ERR_UNSUPPORTED, "contact events need warm starting: no PHYS_FLAG_NO_WARM_START, manifold capacity below 2^26");
+        return fail(PHYS_ERR_UNSUPPORTED, "contact events need warm starting: no PHYS_FLAG_NO_WARM_START, manifold capacity below 2^26");
     if (capacity == w->ev_capacity) return PHYS_OK;
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     const bool was_on = w->ev_capacity != 0;
@@ -222,11 +216,10 @@ int32_t phys_contact_events_enable(phys_world* w, uint64_t capacity) {
 }
 
 int32_t phys_get_contact_events(phys_world* w, phys_contact_event* out, uint64_t cap, uint64_t* n, uint64_t* n_dropped) {
-    if (!w) return ev_fail(PHYS_ERR_INVALID_ARG, "null world");
-    PHYS_HIP_TRY(hipSetDevice(w->device));
-    if (!n) return ev_fail(PHYS_ERR_INVALID_ARG, "phys_get_contact_events: null n");
-    if (cap && !out) return ev_fail(PHYS_ERR_INVALID_ARG, "phys_get_contact_events: null out with cap > 0");
-    if (w->ev_capacity == 0) return ev_fail(PHYS_ERR_UNSUPPORTED, "contact events are off (phys_contact_events_enable)");
+    ENTER(w);
+    if (!n) return fail(PHYS_ERR_INVALID_ARG, "phys_get_contact_events: null n");
+    if (cap && !out) return fail(PHYS_ERR_INVALID_ARG, "phys_get_contact_events: null out with cap > 0");
+    if (w->ev_capacity == 0) return fail(PHYS_ERR_UNSUPPORTED, "contact events are off (phys_contact_events_enable)");
     EventState h{};
     PHYS_HIP_TRY(hipMemcpyAsync(&h, w->ev_state.p, sizeof(h), hipMemcpyDeviceToHost, w->stream));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
@@ -234,7 +227,7 @@ int32_t phys_get_contact_events(phys_world* w, phys_contact_event* out, uint64_t
     *n = stored;
     if (n_dropped) *n_dropped = h.cursor - stored;
     if (!out && cap == 0) return PHYS_OK;  // count query: the buffer stays
-    if (stored > cap) return ev_fail(PHYS_ERR_CAPACITY, "phys_get_contact_events: more events stored than cap (*n says how many); nothing was drained");
+    if (stored > cap) return fail(PHYS_ERR_CAPACITY, "phys_get_contact_events: more events stored than cap (*n says how many); nothing was drained");
     if (stored) {
         PHYS_HIP_TRY(hipMemcpyAsync(out, w->ev_buf.p, stored * sizeof(phys_contact_event), hipMemcpyDeviceToHost, w->stream));
         PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
@@ -252,11 +245,10 @@ int32_t phys_get_contact_events(phys_world* w, phys_contact_event* out, uint64_t
 }
 
 int32_t phys_get_contact_impulses(phys_world* w, float* out, uint64_t cap, uint64_t* n_manifolds) {
-    if (!w) return ev_fail(PHYS_ERR_INVALID_ARG, "null world");
-    PHYS_HIP_TRY(hipSetDevice(w->device));
-    if (!n_manifolds) return ev_fail(PHYS_ERR_INVALID_ARG, "phys_get_contact_impulses: null n_manifolds");
+    ENTER(w);
+    if (!n_manifolds) return fail(PHYS_ERR_INVALID_ARG, "phys_get_contact_impulses: null n_manifolds");
     if (!w->warm || !(w->cfg.flags & PHYS_FLAG_COLLISIONS) || (w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY))
-        return ev_fail(PHYS_ERR_UNSUPPORTED, "contact impulses are kept only in worlds with collisions and warm starting");
+        return fail(PHYS_ERR_UNSUPPORTED, "contact impulses are kept only in worlds with collisions and warm starting");
     uint32_t counted = 0;
     PHYS_HIP_TRY(hipMemcpyAsync(&counted, &w->counters.p->n_manifolds, 4, hipMemcpyDeviceToHost, w->stream));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));

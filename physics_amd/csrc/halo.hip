@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void k_halo_pack(uint32_t n, const float* __re
             r.pad = 0;
             out[slot] = r;
         } else {
-            flag_overflow(ctr, 8u);
+            flag_overflow(ctr, kOvfHalo);
         }
     }
 }
@@ -72,7 +72,7 @@ __device__ __forceinline__ void emit_cross_pairs(bool hit, uint32_t j, uint32_t 
         if (hit) {
             const uint64_t slot = (uint64_t)base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
             if (slot < cap) { cross_pairs[2 * slot] = j; cross_pairs[2 * slot + 1] = rgid; }
-            else flag_overflow(ctr, 8u);
+            else flag_overflow(ctr, kOvfHalo);
         }
     }
 }
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256) void k_halo_pack_bodies(uint32_t n_owned, cons
     const bool take = boundary_body(i, n_owned, pos, shape, x_lo, x_hi, reach);
     const uint32_t slot = ordered_slot(take, block_counts, &ctr->n_halo);
     if (!take) return;
-    if (slot >= cap) { flag_overflow(ctr, 8u); return; }
+    if (slot >= cap) { flag_overflow(ctr, kOvfHalo); return; }
     const v3 x = ld3(pos, i), he = ld3(half_extent, i);
     const float4 q = reinterpret_cast<const float4*>(rot)[i];
     const BodyVel bv = ld_vel(vel, i);
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256) void k_halo_unpack(uint32_t n_records, uint32_
     const bool take = ghost_record(k, n_records, skip_first, skip_count, rec, x_lo, x_hi, reach);
     const uint32_t slot = ordered_slot(take, block_counts, &ctr->n_ghosts);
     if (!take) return;
-    if (slot >= max_ghosts) { flag_overflow(ctr, 8u); return; }
+    if (slot >= max_ghosts) { flag_overflow(ctr, kOvfHalo); return; }
     const uint32_t i = n_owned + slot;
     float4 q[6];
 #pragma unroll
@@ -405,7 +405,7 @@ int32_t halo_pack(phys_world* w, float x_lo, float x_hi, float reach, void* dev_
     if (!n_records) return PHYS_OK;  // asynchronous form: nothing returns to the host (phys_get_stats has the count)
     const int32_t rc = read_counters(w);
     if (rc != PHYS_OK) return rc;
-    if (w->h_counters->overflow & 8u) { set_error("halo buffer capacity exceeded"); return PHYS_ERR_CAPACITY; }
+    if (w->h_counters->overflow & kOvfHalo) { set_error("halo buffer capacity exceeded"); return PHYS_ERR_CAPACITY; }
     *n_records = w->h_counters->n_halo;
     return PHYS_OK;
 }
@@ -436,7 +436,7 @@ int32_t halo_pairs(phys_world* w, const void* dev_remote, uint64_t n_remote, uin
     if (!n_cross) return PHYS_OK;  // asynchronous form
     const int32_t rc = read_counters(w);
     if (rc != PHYS_OK) return rc;
-    if (w->h_counters->overflow & 8u) { set_error("cross-pair capacity exceeded"); return PHYS_ERR_CAPACITY; }
+    if (w->h_counters->overflow & kOvfHalo) { set_error("cross-pair capacity exceeded"); return PHYS_ERR_CAPACITY; }
     *n_cross = w->h_counters->n_cross_pairs;
     return PHYS_OK;
 }

@@ -128,7 +128,7 @@ __device__ __forceinline__ void color_table_insert(const ColorTableJob& job, uin
     // bounded (see the walk in k_narrowphase); a manifold that finds no slot would be coloured afresh next time where the
     // oracle keeps its colour: the update is flagged (bit 6), never a silent divergence
     for (uint32_t walked = 0; ; ++walked) {
-        if (walked == 4u * kColorTableMaxWalk) { flag_overflow(ctr, 64u); return; }
+        if (walked == 4u * kColorTableMaxWalk) { flag_overflow(ctr, kOvfColorTable); return; }
         unsigned long long* vp = &job.tab[h].y;
         const unsigned long long seen = __hip_atomic_load(vp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if ((uint32_t)(seen >> 32) != job.stamp && atomicCAS(vp, seen, val) == seen) {
@@ -298,14 +298,11 @@ int32_t static_set(phys_world* w, uint64_t n, const float* pos, const float* rot
 int32_t launch_static_pairs(phys_world* w);
 void static_narrow_args(const phys_world* w, uint64_t* cap, const uint32_t** pairs, const float** geo);
 
-// raycast.hip: builds the query's grid from the current poses and traces the rays (device pointers), all on w->stream
-int32_t launch_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
-                       const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out,
-                       const uint16_t* query_mask = nullptr /* device, n_rays; null: no filtering */);
-// ... the same walk for balls of radius[i] (the grid grown by the largest valid radius)
-int32_t launch_spherecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
-                          const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out,
-                          const uint16_t* query_mask = nullptr);
+// raycast.hip: builds the query's grid from the current poses and traces the rays (device pointers), all on w->stream; with
+// radius, the same walk for balls of radius[i] (the grid grown by the largest valid radius)
+int32_t launch_trace(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* radius /* null: rays */,
+                     const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out,
+                     const uint16_t* query_mask /* device, n_rays; null: no filtering */);
 // the query grid alone (rc_header, rc_start, rc_records), every body AABB grown by the largest valid value of the device
 // array grow_radius (null: not grown); *bits = log2 of the bucket table
 int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_radius, uint32_t* bits);

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
                     }
                     // a walk given up on might have passed over a colour the oracle's map keeps: never silently (bit 6: the
                     // update is flagged and its solve skipped, like any other capacity miss)
-                    if (!ended) flag_overflow(ctr, 64u);
+                    if (!ended) flag_overflow(ctr, kOvfColorTable);
                 }
                 if (col != kUncolored) {
                     bit = 1ull << col;
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
                 ub = (uint32_t)(got >> 32);
                 const uint64_t room = (uint64_t)bb < max_manifolds ? max_manifolds - bb : 0;
                 const uint32_t stored = (uint64_t)t <= room ? t : (uint32_t)room;
-                if (stored != t) flag_overflow(ctr, 2u);
+                if (stored != t) flag_overflow(ctr, kOvfManifolds);
                 acc_pts += tp; acc_ground += tg; acc_unc += tu;
             }
             block_base = bb;
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
                     // order-independent. A kept colour that was ALREADY in use at one of the bodies means the previous
                     // colouring was not proper (it saturated at PHYS_MAX_COLORS): two rows of one colour on one body
                     // would race in the solver, so the step is flagged like any other colour overflow (no solve)
-                    flag_overflow(ctr, 4u);
+                    flag_overflow(ctr, kOvfColors);
                 }
             }
             woff += (uint32_t)__popcll(mask[j]);
@@ -371,7 +371,7 @@ __device__ __forceinline__ uint32_t color_round_lanes(uint32_t first, uint32_t s
             mask |= mb;
             uint32_t c = 0;
             while (c < (uint32_t)(PHYS_MAX_COLORS - 1) && ((mask >> c) & 1ull)) ++c;
-            if (((mask >> c) & 1ull)) flag_overflow(ctr, 4u);  // more than PHYS_MAX_COLORS at one body
+            if (((mask >> c) & 1ull)) flag_overflow(ctr, kOvfColors);  // more than PHYS_MAX_COLORS at one body
             // the winner is the only manifold touching a or b that colours this round
             if (BYPASS_L1) {
                 __hip_atomic_store(&used[a], ma | (1ull << c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

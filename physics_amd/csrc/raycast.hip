@@ -464,7 +464,7 @@ int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_ra
 }
 
 // the walk shared by ray casts (radius == nullptr) and sphere casts
-static int32_t trace(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* radius, const float* max_t,
+int32_t launch_trace(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* radius, const float* max_t,
                      const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out, const uint16_t* query_mask) {
     hipStream_t s = w->stream;
     const uint64_t n = w->n_owned;
@@ -505,16 +505,6 @@ static int32_t trace(phys_world* w, uint64_t n_rays, const float* origin, const 
                 (unsigned long long)n_rays, h[0], h[1]);
     }
     return PHYS_OK;
-}
-
-int32_t launch_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
-                       const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out, const uint16_t* query_mask) {
-    return trace(w, n_rays, origin, dir, nullptr, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
-}
-
-int32_t launch_spherecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
-                          const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out, const uint16_t* query_mask) {
-    return trace(w, n, origin, dir, radius, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
 }
 
 }  // namespace phys

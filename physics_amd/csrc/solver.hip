@@ -466,8 +466,8 @@ __device__ __forceinline__ bool flow_backoff(StepCounters* ctr, bool done, uint3
     else __builtin_amdgcn_s_sleep(127);
     if ((++sweeps & 63u) != 0u) return false;
     const bool dead = (wall_clock64() - t_start > timeout_ticks) ||
-                      (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 16u);
-    if (dead && (threadIdx.x & 63u) == 0u) flag_overflow(ctr, 16u);  // wave-uniform: both inputs are
+                      (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kOvfHandoff);
+    if (dead && (threadIdx.x & 63u) == 0u) flag_overflow(ctr, kOvfHandoff);  // wave-uniform: both inputs are
     return dead;
 }
 
@@ -510,7 +510,7 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
     auto take = [&]() -> uint32_t {  // next work item in solve order (block-uniform)
         __syncthreads();
         if (threadIdx.x == 0)
-            s_item = (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 16u)
+            s_item = (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kOvfHandoff)
                          ? 0xFFFFFFFFu : atomicAdd(&ctr->flow_ticket, 1u);
         __syncthreads();
         return s_item;
@@ -881,7 +881,7 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
     // kernels; a workgroup that starts late delays its items (bounded spins: time-out after 3 s, never a silent hang).
     // k_solve_flow (one workgroup per CU at 370 registers) needs the whole chip for that and keeps its tickets.
     for (uint32_t L = blockIdx.x;; L += gridDim.x) {
-        if (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 16u) return;  // somebody gave up
+        if (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kOvfHandoff) return;  // somebody gave up
         if (L >= total) return;
         const uint32_t it = L / nchunks, chunk = L - it * nchunks;
         const bool last_it = it + 1 == iterations;
@@ -1010,7 +1010,7 @@ __global__ __launch_bounds__(256) void k_solve_color_quad(StepCounters* ctr, uin
         // whole node down): flag the step (bit 5) and skip the row
         const bool bad = live && (count > 4u || ha >= n_bodies || (!PHYS_IS_STATIC_PARTNER(hb) && hb >= n_bodies));
         if (bad) {
-            flag_overflow(ctr, 32u);
+            flag_overflow(ctr, kOvfCorruptRow);
             ctr->debug[0] = d; ctr->debug[1] = ha; ctr->debug[2] = hb; ctr->debug[3] = count;
             ctr->debug[4] = start; ctr->debug[5] = end; ctr->debug[6] = col; ctr->debug[7] = base;
         }

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(1024) void k_static_scan(uint32_t* __restrict__ blo
     if (threadIdx.x == 0) {
         const uint32_t total = s_carry;
         ctr->n_static_pairs = total;
-        if ((uint64_t)total > cap) flag_overflow(ctr, 1u);
+        if ((uint64_t)total > cap) flag_overflow(ctr, kOvfPairs);
     }
 }
 

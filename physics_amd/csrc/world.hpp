@@ -40,15 +40,33 @@ const char* get_error();
         }                                                                                           \
     } while (0)
 
+// host side of every extern "C" entry point: the error text and the code it returns with ...
+inline int32_t fail(int32_t code, const char* msg) {
+    set_error(msg);
+    return code;
+}
+// ... and its first line: a world, and its device current
+#define ENTER(w)                                                                    \
+    do {                                                                            \
+        if (!(w)) return phys::fail(PHYS_ERR_INVALID_ARG, "null world");            \
+        PHYS_HIP_TRY(hipSetDevice((w)->device));                                    \
+    } while (0)
+
+// A device allocation and its owner: freed by the destructor, never copied. A view (point_at) is a non-owning window into
+// another DevBuf's allocation (the per-step zeroed block, the solver's row planes) and frees nothing.
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
+    bool view = false;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { free(); }
+    // at least `count` elements; an allocation that is large enough stays (a view never does: it is dropped first)
     hipError_t resize(size_t count) {
-        if (count <= n && p) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
+        if (count <= n && p && !view) return hipSuccess;
+        free();
         if (count == 0) return hipSuccess;
         hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
         if (e == hipSuccess) n = count;
@@ -60,8 +78,6 @@ struct DevBuf {
         n = 0;
         view = false;
     }
-    // non-owning window into another allocation (the per-step zeroed block)
-    bool view = false;
     void point_at(T* ptr, size_t count) { free(); p = ptr; n = count; view = true; }
 };
 
@@ -77,7 +93,7 @@ struct StepCounters {
     uint32_t n_uncolored;    // manifolds still uncoloured (colouring loop)
     uint32_t n_colors;       // colours in use
     uint32_t color_rounds;
-    uint32_t overflow;       // bit 0 pairs, bit 1 manifolds, bit 2 colours, bit 3 cross pairs, bit 4 solver hand-off timeout, bit 5 corrupt solver row refused, bit 6 colour table walk given up
+    uint32_t overflow;       // kOvf* bits (below)
     uint32_t n_halo;         // halo records packed
     uint32_t n_cross_pairs;
     uint32_t n_ground_manifolds;
@@ -110,6 +126,14 @@ struct StepCounters {
 };
 static_assert(offsetof(StepCounters, n_manifolds) % 8 == 0 && offsetof(StepCounters, unc_count) == offsetof(StepCounters, n_manifolds) + 4,
               "n_manifolds | unc_count[0] are one aligned 64-bit word");
+// the bits of StepCounters::overflow / sticky_overflow (phys_stats.overflow shows them; phys_sync turns them into errors)
+constexpr uint32_t kOvfPairs = 1u;        // bit 0: candidate pairs or (body, static) pairs beyond their capacity
+constexpr uint32_t kOvfManifolds = 2u;    // bit 1: manifolds beyond max_manifolds
+constexpr uint32_t kOvfColors = 4u;       // bit 2: more than kMaxColors manifolds at one body
+constexpr uint32_t kOvfHalo = 8u;         // bit 3: halo records, ghosts or cross pairs beyond their capacity
+constexpr uint32_t kOvfHandoff = 16u;     // bit 4: solver hand-off timeout
+constexpr uint32_t kOvfCorruptRow = 32u;  // bit 5: corrupt solver row refused (StepCounters::debug says which)
+constexpr uint32_t kOvfColorTable = 64u;  // bit 6: colour table walk given up
 constexpr size_t kCountersStepResetBytes = offsetof(StepCounters, max_extent_bits);
 constexpr size_t kCountersExtentResetBytes = offsetof(StepCounters, sticky_overflow);
 
@@ -206,6 +230,9 @@ struct Constraint {
 }  // namespace phys
 
 struct phys_world {
+    // the whole teardown (abi.hip): stream drained, then events, pinned memory and the stream; every DevBuf below frees itself
+    // behind it, so a buffer added here needs no second mention anywhere
+    ~phys_world();
     phys_config cfg;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -343,11 +370,12 @@ struct phys_world {
     phys::DevBuf<uint32_t> rc_start;     // table + 1: exclusive scan of rc_count
     phys::DevBuf<uint32_t> rc_tile_sum;  // the scan's own scratch (scan_block_sums is the update's)
     phys::DevBuf<float> rc_records;      // 8N records of 48 bytes {centre, shape} {rot} {half extent, id}, bucket order
-    phys::DevBuf<float> rc_in;           // phys_raycast (host arrays): staged origin | dir | max_t | ignore (as u32 bits)
-    phys::DevBuf<float> rc_out;          // ... and the outputs body | t | normal
+    // the queries on host arrays (phys_raycast, phys_spherecast, phys_overlap): ONE staging buffer for the inputs of whichever
+    // runs - each synchronises the stream before it returns, so no two are ever in flight - laid out by the call's own
+    // declarations (abi.hip Staging); the casts' outputs body | t | normal the same way
+    phys::DevBuf<uint8_t> stage, rc_out;
     phys::DevBuf<unsigned long long> rc_stats;  // PHYS_DEBUG_RAYCAST_STATS: cells, candidates
-    // sphere casts and overlap queries (raycast.hip, query.hip): they walk the grid above; their own staging and output
-    phys::DevBuf<float> qr_in;           // phys_spherecast: origin | dir | radius | max_t | ignore; phys_overlap: type | pos | rot | half extent | ignore
+    // overlap queries (query.hip): they walk the grid above; their own output
     phys::DevBuf<uint32_t> qr_count;     // phys_overlap: targets per query (count pass)
     phys::DevBuf<unsigned long long> qr_off;  // ... their exclusive scan (n + 1)
     phys::DevBuf<uint32_t> qr_ids;       // ... the ids in walk order, then each query's ids ascending
