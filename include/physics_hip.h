@@ -477,6 +477,70 @@ int32_t phys_contact_events_enable(phys_world* w, uint64_t capacity);
 int32_t phys_get_contact_events(phys_world* w, phys_contact_event* out, uint64_t cap, uint64_t* n, uint64_t* n_dropped);
 int32_t phys_get_contact_impulses(phys_world* w, float* out /*12*cap*/, uint64_t cap, uint64_t* n_manifolds);
 
+/* --- trigger volumes: shapes that report which bodies are inside them, and which entered and left (new: the reference
+ * has none) ---
+ * A world keeps up to PHYS_MAX_TRIGGERS trigger volumes. Each is a SPHERE, BOX or CAPSULE with the bodies' half_extent
+ * conventions, a position, a unit quaternion and a u16 mask. Triggers are NOT bodies and NOT statics: nothing collides
+ * with them, and they appear in no manifold, pair, ray hit, overlap result, AABB, halo record or stat.
+ * Occupants. The occupants of trigger k after an update are the OWNED bodies with shape SPHERE, BOX or CAPSULE and a
+ *   finite pose whose closed shape intersects the trigger's closed shape at the poses phys_get_transforms would return
+ *   after that update. Ghost slots, PHYS_SHAPE_NONE bodies, statics and the ground are never occupants; in a sharded world
+ *   each rank reports its owned bodies. The exact test is phys_overlap's - the same device functions, the trigger as the
+ *   query shape and the body as the target - so both agree bit for bit on every (shape, body) pair.
+ * Masks. With a mask array body i is seen by trigger k iff (category[i] & mask[k]) != 0, as for phys_overlap_filtered
+ *   (category: phys_set_body_filters). A NULL mask array sees every body and loads no filter.
+ * When. The volumes are evaluated at the end of EVERY phys_update, and after each update of a phys_update_n batch, behind
+ *   the position step, whatever the world's flags: with or without PHYS_FLAG_COLLISIONS, dt = 0 included. phys_step and
+ *   phys_apply_gravity alone do not evaluate.
+ * Events. Update E raises PHYS_TRIGGER_ENTER for each (trigger, body) that is an occupant after E and was not after E - 1,
+ *   PHYS_TRIGGER_EXIT for the opposite transition, whatever the cause: the body moved, the trigger was moved, or the body's
+ *   filter changed.
+ * Resets and moves. phys_set_triggers and phys_set_bodies forget the occupancy and discard the pending trigger events: the
+ *   next update raises ENTER for every occupant and no EXIT. phys_set_trigger_poses keeps the history.
+ * No side effects. Nothing here writes anything an update, phys_broadphase or a query reads: updates are bit-identical with
+ *   and without triggers, and a world that never calls phys_set_triggers launches exactly what it launched before they
+ *   existed. Triggers neither raise nor clear the sticky update errors.
+ *
+ * phys_set_triggers: replaces the whole set; n = 0 clears it, frees its buffers and goes back to launching nothing.
+ *   rot_ijkw NULL = identity, mask NULL = see every body. PHYS_ERR_INVALID_ARG: n > PHYS_MAX_TRIGGERS, a shape other than
+ *   SPHERE, BOX or CAPSULE, a non-finite pose or half extent, a negative half extent, a NULL array that is required.
+ *   Synchronises the world's stream.
+ * phys_set_trigger_poses: new positions (and rotations; rot_ijkw NULL keeps them) for the set that is there, from the
+ *   next update on. PHYS_ERR_INVALID_ARG: n differs from the trigger count, NULL pos, a non-finite value.
+ * phys_trigger_events_enable / phys_get_trigger_events: phys_contact_events_enable / phys_get_contact_events rule for
+ *   rule. capacity 0 = off (buffer freed, pending events gone), a new capacity drops the pending events, the same one is a
+ *   no-op; PHYS_ERR_INVALID_ARG for capacity >= 2^31. Events accumulate on the device across updates and batches at no
+ *   host round trip; a full buffer counts events but stores nothing (no sticky error). The drain synchronises, returns the
+ *   stored events sorted by (step, kind, trigger, body) and empties the buffer; *n_dropped (may be NULL) = events raised
+ *   since the last drain that did not fit. More stored than cap: PHYS_ERR_CAPACITY with *n = the stored count, the
+ *   buffer kept. out == NULL with cap == 0 only counts. Events off: PHYS_ERR_UNSUPPORTED. The occupancy is tracked
+ *   whenever triggers are set, events on or off.
+ * phys_get_trigger_overlaps: the occupants as of the last update in phys_overlap's CSR convention: trigger k's body ids,
+ *   ascending, are ids_out[offsets_out[k] .. offsets_out[k + 1]); offsets_out (n_triggers + 1) is always written;
+ *   PHYS_ERR_CAPACITY when offsets_out[n_triggers] > cap. Before the first update since a reset every list is empty.
+ *   Synchronous and not a hot path: the occupancy bits are read back and listed on the host.
+ * Cost: one kernel per update, one lane per owned body. The occupancy is a bit matrix of 4 * ceil(n_triggers / 32) *
+ *   n_bodies bytes on the device (128 MB for 1M bodies and 1024 triggers). DESIGN.md section 17. Added without an ABI
+ *   version change (no struct changed): a library that predates them lacks the symbols. */
+#define PHYS_MAX_TRIGGERS 1024u
+#define PHYS_TRIGGER_ENTER 1u
+#define PHYS_TRIGGER_EXIT  2u
+typedef struct phys_trigger_event {   /* 16 bytes */
+    uint32_t trigger;         /* index into the set of phys_set_triggers */
+    uint32_t body;            /* owned body index */
+    uint32_t kind;            /* PHYS_TRIGGER_ENTER / PHYS_TRIGGER_EXIT */
+    uint32_t step;            /* as in phys_contact_event */
+} phys_trigger_event;
+
+int32_t phys_set_triggers(phys_world* w, uint64_t n, const uint32_t* shape_type /*n*/, const float* pos /*3n*/,
+                          const float* rot_ijkw /*4n, NULL = identity*/, const float* half_extent /*3n*/,
+                          const uint16_t* mask /*n, NULL = see every body*/);
+int32_t phys_set_trigger_poses(phys_world* w, uint64_t n /* == trigger count */, const float* pos /*3n*/,
+                               const float* rot_ijkw /*4n, NULL = keep*/);
+int32_t phys_trigger_events_enable(phys_world* w, uint64_t capacity);
+int32_t phys_get_trigger_events(phys_world* w, phys_trigger_event* out, uint64_t cap, uint64_t* n, uint64_t* n_dropped);
+int32_t phys_get_trigger_overlaps(phys_world* w, uint64_t cap, uint64_t* offsets_out /*n_triggers + 1*/, uint32_t* ids_out /*cap*/);
+
 /* --- per-stage device timing (HIP events on the world's stream), for bench.py's roofline --- */
 #define PHYS_STAGE_STEP_FULL 0u     /* gravity + RigidBody::step, one kernel (no collisions) */
 #define PHYS_STAGE_VELOCITY_AABB 1u /* gravity + velocity half + AABB */

@@ -34,6 +34,9 @@ FILTER_DEFAULT_CATEGORY = 0x0001
 FILTER_DEFAULT_MASK = 0xFFFF
 # contact events (include/physics_hip.h): phys_contact_event.kind
 CONTACT_BEGIN, CONTACT_END = 1, 2
+# trigger volumes (include/physics_hip.h): the most a world keeps, and phys_trigger_event.kind
+MAX_TRIGGERS = 1024
+TRIGGER_ENTER, TRIGGER_EXIT = 1, 2
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -121,6 +124,11 @@ class PhysContactEvent(C.Structure):
         ("normal", C.c_float * 3),
         ("reserved", C.c_uint32),
     ]
+
+
+class PhysTriggerEvent(C.Structure):
+    """struct phys_trigger_event (include/physics_hip.h), 16 bytes."""
+    _fields_ = [("trigger", C.c_uint32), ("body", C.c_uint32), ("kind", C.c_uint32), ("step", C.c_uint32)]
 
 
 def default_config(**overrides):
@@ -211,6 +219,11 @@ PROTOTYPES = {
     "phys_contact_events_enable": (C.c_int32, [C.c_void_p, C.c_uint64]),
     "phys_get_contact_events": (C.c_int32, [C.c_void_p, C.POINTER(PhysContactEvent), C.c_uint64, u64p, u64p]),
     "phys_get_contact_impulses": (C.c_int32, [C.c_void_p, f32p, C.c_uint64, u64p]),
+    "phys_set_triggers": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p, f32p, u16p]),
+    "phys_set_trigger_poses": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p]),
+    "phys_trigger_events_enable": (C.c_int32, [C.c_void_p, C.c_uint64]),
+    "phys_get_trigger_events": (C.c_int32, [C.c_void_p, C.POINTER(PhysTriggerEvent), C.c_uint64, u64p, u64p]),
+    "phys_get_trigger_overlaps": (C.c_int32, [C.c_void_p, C.c_uint64, u64p, u32p]),
     "phys_profile_enable": (C.c_int32, [C.c_void_p, C.c_int32]),
     "phys_profile_get": (C.c_int32, [C.c_void_p, C.POINTER(PhysProfile)]),
     "phys_get_device_view": (C.c_int32, [C.c_void_p, C.POINTER(PhysDeviceView)]),

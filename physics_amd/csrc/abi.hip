@@ -308,6 +308,7 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     w->body_materials_set = false;  // ... and the default material
     for (int k = 0; k < phys_world::kSnapRing; ++k) w->snap_pending[k] = false;  // the stream was synchronised above
     { const int32_t rc = events_reset(w); if (rc != PHYS_OK) return rc; }  // contact events: history and pending events are gone
+    { const int32_t rc = triggers_reset(w); if (rc != PHYS_OK) return rc; }  // trigger volumes: occupancy and pending events too
     if (n == 0) return PHYS_OK;
 
     // host staging with RigidBody::new defaults (rigid_body.rs:64-76); ghost slots: no shape, immovable
@@ -488,6 +489,7 @@ static int32_t enqueue_update(phys_world* w, float dt) {
         }
         launch_step_position(w, dt);
     }
+    if (w->n_triggers) launch_triggers(w, (uint32_t)(w->steps + 1));  // trigger volumes, against the poses just written
     PHYS_HIP_TRY(hipGetLastError());
     w->steps++;
     if (w->prof.on) { w->prof.steps++; if (w->prof.used > 4096) w->prof.collect(w->stream); }
@@ -1022,6 +1024,58 @@ int32_t phys_overlap_filtered(phys_world* w, uint64_t n, const uint32_t* shape_t
                               const float* half_extent, const uint32_t* ignore_body, const uint16_t* query_mask, uint64_t cap,
                               uint64_t* offsets_out, uint32_t* ids_out) {
     return overlap_host(w, n, shape_type, pos, rot_ijkw, half_extent, ignore_body, query_mask, cap, offsets_out, ids_out);
+}
+
+// ---- trigger volumes: the host arrays staged like a query's, the records built on the device ----
+static bool finite_all(const float* a, uint64_t count) {
+    bool f = true;
+    for (uint64_t k = 0; k < count; ++k) f = f && std::isfinite(a[k]);
+    return f;
+}
+
+int32_t phys_set_triggers(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,
+                          const float* half_extent, const uint16_t* mask) {
+    // the arguments first, as phys_set_static_bodies checks them
+    if (n > PHYS_MAX_TRIGGERS) return fail(PHYS_ERR_INVALID_ARG, "phys_set_triggers: more than PHYS_MAX_TRIGGERS trigger volumes");
+    if (n && (!shape_type || !pos || !half_extent)) return fail(PHYS_ERR_INVALID_ARG, "trigger volumes need shape_type, pos and half_extent");
+    for (uint64_t k = 0; k < n; ++k) {
+        if (shape_type[k] != PHYS_SHAPE_SPHERE && shape_type[k] != PHYS_SHAPE_BOX && shape_type[k] != PHYS_SHAPE_CAPSULE)
+            return fail(PHYS_ERR_INVALID_ARG, ("trigger " + std::to_string(k) + ": shape is neither SPHERE nor BOX nor CAPSULE").c_str());
+        if (!finite_all(pos + 3 * k, 3) || !finite_all(half_extent + 3 * k, 3) || (rot_ijkw && !finite_all(rot_ijkw + 4 * k, 4)))
+            return fail(PHYS_ERR_INVALID_ARG, ("trigger " + std::to_string(k) + ": non-finite pose or half extent").c_str());
+        if (half_extent[3 * k] < 0.0f || half_extent[3 * k + 1] < 0.0f || half_extent[3 * k + 2] < 0.0f)
+            return fail(PHYS_ERR_INVALID_ARG, ("trigger " + std::to_string(k) + ": negative half extent").c_str());
+    }
+    ENTER(w);
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // updates in flight read the set that is replaced
+    if (n == 0) return triggers_set(w, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+    Staging in{w, w->stage};
+    const auto s_type = in.add(shape_type, n);
+    const auto s_pos = in.add(pos, 3 * n), s_he = in.add(half_extent, 3 * n);
+    const auto s_rot = in.add(rot_ijkw, 4 * n, /*align=*/16);  // read as float4
+    const auto s_mask = in.add(mask, n);
+    int32_t rc = in.reserve(); if (rc) return rc;
+    rc = in.copy(hipMemcpyHostToDevice); if (rc) return rc;
+    rc = triggers_set(w, n, in.at(s_type), in.at(s_pos), in.at(s_rot), in.at(s_he), in.at(s_mask)); if (rc) return rc;
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // the staging buffer is the next query's
+    return PHYS_OK;
+}
+
+int32_t phys_set_trigger_poses(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw) {
+    ENTER(w);
+    if (n != w->n_triggers) return fail(PHYS_ERR_INVALID_ARG, "phys_set_trigger_poses: n must equal the trigger count");
+    if (n && !pos) return fail(PHYS_ERR_INVALID_ARG, "phys_set_trigger_poses: null pos");
+    if (n && (!finite_all(pos, 3 * n) || (rot_ijkw && !finite_all(rot_ijkw, 4 * n))))
+        return fail(PHYS_ERR_INVALID_ARG, "phys_set_trigger_poses: non-finite pose");
+    if (n == 0) return PHYS_OK;
+    Staging in{w, w->stage};
+    const auto s_pos = in.add(pos, 3 * n);
+    const auto s_rot = in.add(rot_ijkw, 4 * n, /*align=*/16);
+    int32_t rc = in.reserve(); if (rc) return rc;
+    rc = in.copy(hipMemcpyHostToDevice); if (rc) return rc;
+    rc = triggers_set_poses(w, in.at(s_pos), in.at(s_rot)); if (rc) return rc;  // behind the updates already enqueued
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    return PHYS_OK;
 }
 
 int32_t phys_set_global_ids(phys_world* w, const uint32_t* global_ids) {

@@ -251,6 +251,14 @@ void launch_events(phys_world* w, uint32_t step);
 int32_t events_alloc(phys_world* w);  // buffers for the current event and manifold capacities (frees them when events are off)
 int32_t events_reset(phys_world* w);  // forget the contact history and the pending events (a new body or static set)
 
+// trigger volumes (trigger.hip): one kernel behind the position step of every update, only in a world with triggers
+void launch_triggers(phys_world* w, uint32_t step);
+// the trigger set from staged device arrays (arguments checked by the caller; n = 0 clears and frees); forgets the occupancy
+int32_t triggers_set(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot, const float* half_extent,
+                     const uint16_t* mask);
+int32_t triggers_set_poses(phys_world* w, const float* pos, const float* rot /* null: keep */);  // staged device arrays; keeps the occupancy
+int32_t triggers_reset(phys_world* w);  // forget the occupancy and the pending events (a new trigger or body set)
+
 // constraints.hip
 int32_t constraints_alloc(phys_world* w);
 void launch_constraint_phase(phys_world* w, bool gravity_pending);  // Q = accumulators (+ gravity when still pending)

@@ -1,0 +1,328 @@
+// trigger.hip — trigger volumes: shapes that report which bodies are inside them and which
+// entered or left in an update. Not bodies, not statics: they are evaluated by a kernel of their own against the poses the
+// position step leaves, so nothing an update computes depends on them. A world without triggers launches nothing of
+// this file.
+//
+//   k_trigger_build  one lane per trigger: its record {AABB, shape, mask, centre, half extent, rotation matrix} from the
+//                    staged host arrays (phys_set_triggers) or from new poses (phys_set_trigger_poses)
+//   k_trigger_eval   one lane per owned body, a short loop over the triggers: the records travel through LDS in tiles of 32
+//                    (every lane reads the same record: a broadcast), a lane rejects by AABB and mask, runs the overlap
+//                    queries' exact test (shape_overlap.hpp: trigger = query, body = target), and builds its occupancy 32
+//                    triggers at a time. The word is XORed with the word of the previous update: the set bits are the
+//                    lane's events, ENTER where the new word has the bit.
+//
+// Occupancy is a bit matrix that lives across updates, plane-major: word (k / 32) of body i at [(k / 32) * n_owned + i], so
+// the loads and stores of one word by a wave are one contiguous 256-byte span. 4 * ceil(T / 32) * n_owned bytes: 128 MB
+// for 1M bodies and 1024 triggers.
+//
+// Events are appended like contact events (events.hip): one reservation per workgroup and trip - a wave prefix sum of
+// the lanes' event COUNTS (a lane may hold up to 32), per-wave totals in LDS, ONE global atomic - because same-address
+// atomics serialise chip-wide. Slots at or beyond the capacity are not written; the cursor keeps counting.
+#include <cmath>
+#include <vector>
+
+#include "shape_overlap.hpp"
+
+namespace phys {
+
+namespace {
+
+constexpr int kTgThreads = 256;
+constexpr int kTgWaves = kTgThreads / 64;
+constexpr uint32_t kTgTile = 32;      // triggers per LDS tile = bits per occupancy word
+constexpr uint32_t kTgRecVec = 6;     // float4 per trigger record
+static_assert(kTgTile * kTgRecVec <= (uint32_t)kTgThreads, "one float4 per thread stages a tile");
+
+// LDS of one reservation (events.hip EventAppend: the totals alternate between two sets)
+struct TriggerAppend {
+    uint32_t wave_total[2][kTgWaves];
+    unsigned long long base;
+};
+
+// the first slot of this lane's `count` events; every thread of the workgroup calls it, once per trip
+__device__ __forceinline__ unsigned long long trigger_reserve(uint32_t count, uint32_t trip, TriggerAppend& sh, unsigned long long* cursor) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, set = trip & 1u;
+    uint32_t incl = count;  // inclusive prefix sum over the wave
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint32_t below = __shfl_up(incl, d);
+        if (lane >= d) incl += below;
+    }
+    if (lane == 63u) sh.wave_total[set][wave] = incl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int k = 0; k < kTgWaves; ++k) t += sh.wave_total[set][k];
+        sh.base = t ? atomicAdd(cursor, (unsigned long long)t) : 0ull;
+    }
+    __syncthreads();
+    uint32_t off = 0;
+    for (uint32_t k = 0; k < wave; ++k) off += sh.wave_total[set][k];
+    return sh.base + off + (incl - count);
+}
+
+// type null: new poses for the records that are there (shape, half extent and mask stay); rot null: identity then, the
+// stored quaternion otherwise
+__global__ __launch_bounds__(kTgThreads) void k_trigger_build(uint32_t T, const uint32_t* __restrict__ type_in, const float* __restrict__ pos,
+                                                              const float* __restrict__ rot, const float* __restrict__ he,
+                                                              const uint16_t* __restrict__ mask, float4* __restrict__ rec,
+                                                              float4* __restrict__ rot_keep) {
+    const uint32_t k = blockIdx.x * kTgThreads + threadIdx.x;
+    if (k >= T) return;
+    float4* r = rec + kTgRecVec * (size_t)k;
+    uint32_t type, m;
+    v3 h;
+    float4 q4;
+    if (type_in) {
+        type = type_in[k];
+        h = ld3(he, k);
+        m = mask ? (uint32_t)mask[k] : 0xFFFFu;
+        q4 = rot ? reinterpret_cast<const float4*>(rot)[k] : make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    } else {
+        type = __float_as_uint(r[0].w);
+        m = __float_as_uint(r[1].w);
+        h = v3_make(r[2].w, r[3].w, r[4].w);
+        q4 = rot ? reinterpret_cast<const float4*>(rot)[k] : rot_keep[k];
+    }
+    const v3 c = ld3(pos, k);
+    aabb_t b;
+    if (!rc_aabb_of(c, q4, h, type, &b)) {  // (finite inputs whose box is not: touches nothing)
+        b.lo = v3_make(3.0e38f, 3.0e38f, 3.0e38f);
+        b.hi = v3_make(-3.0e38f, -3.0e38f, -3.0e38f);
+    }
+    const QShape Q = qs_make(type, c, q4, h);
+    rot_keep[k] = q4;
+    r[0] = make_float4(b.lo.x, b.lo.y, b.lo.z, __uint_as_float(type));
+    r[1] = make_float4(b.hi.x, b.hi.y, b.hi.z, __uint_as_float(m));
+    r[2] = make_float4(c.x, c.y, c.z, h.x);
+    r[3] = make_float4(Q.R.m[0], Q.R.m[1], Q.R.m[2], h.y);
+    r[4] = make_float4(Q.R.m[3], Q.R.m[4], Q.R.m[5], h.z);
+    r[5] = make_float4(Q.R.m[6], Q.R.m[7], Q.R.m[8], 0.0f);
+}
+
+// MASKED: the trigger set has masks - body i is seen by trigger k iff (category[i] & mask[k]) != 0; without it no filter is
+// loaded. EVENTS: trigger events are on (the occupancy is kept either way).
+template <bool MASKED, bool EVENTS>
+__global__ __launch_bounds__(kTgThreads) void k_trigger_eval(uint32_t n, const float* __restrict__ pos, const float* __restrict__ rot,
+                                                             const float* __restrict__ he, const uint32_t* __restrict__ shape,
+                                                             const uint2* __restrict__ filt, const float4* __restrict__ rec, uint32_t T,
+                                                             uint32_t* __restrict__ bits, uint32_t step,
+                                                             unsigned long long* __restrict__ cursor, uint4* __restrict__ ev_buf,
+                                                             uint64_t capacity) {
+    __shared__ float4 tile[kTgTile * kTgRecVec];
+    __shared__ TriggerAppend sh;
+    const uint32_t i = blockIdx.x * kTgThreads + threadIdx.x;
+    const bool live = i < n;  // (no early return: the tiles and the reservation have barriers)
+    bool shaped = false;      // SPHERE, BOX or CAPSULE at a finite pose: what can be an occupant at all
+    aabb_t ba;
+    ba.lo = ba.hi = v3_make(0.0f, 0.0f, 0.0f);
+    QShape B;
+    B.type = PHYS_SHAPE_NONE;
+    B.c = B.h = v3_make(0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) B.R.m[k] = 0.0f;
+    uint32_t category = 0xFFFFu;
+    if (live) {
+        const uint32_t type = shape[i];
+        const v3 c = ld3(pos, i), h = ld3(he, i);
+        const float4 q4 = reinterpret_cast<const float4*>(rot)[i];
+        shaped = rc_aabb_of(c, q4, h, type, &ba);
+        if (shaped) B = qs_make(type, c, q4, h);
+        if (MASKED) category = filt[i].x & 0xFFFFu;
+    }
+    const uint32_t words = (T + kTgTile - 1) / kTgTile;
+    for (uint32_t wd = 0; wd < words; ++wd) {
+        const uint32_t t0 = wd * kTgTile;
+        const uint32_t tn = min(kTgTile, T - t0);
+        __syncthreads();  // the previous tile has been read by everybody
+        if (threadIdx.x < tn * kTgRecVec) tile[threadIdx.x] = rec[kTgRecVec * (size_t)t0 + threadIdx.x];
+        __syncthreads();
+        uint32_t now = 0;
+        if (shaped) {
+#pragma unroll 1
+            for (uint32_t k = 0; k < tn; ++k) {
+                const float4 a0 = tile[kTgRecVec * k], a1 = tile[kTgRecVec * k + 1];
+                if (MASKED && (category & __float_as_uint(a1.w)) == 0u) continue;
+                if (!(a0.x <= ba.hi.x && ba.lo.x <= a1.x && a0.y <= ba.hi.y && ba.lo.y <= a1.y && a0.z <= ba.hi.z && ba.lo.z <= a1.z)) continue;
+                const float4 r2 = tile[kTgRecVec * k + 2], r3 = tile[kTgRecVec * k + 3], r4 = tile[kTgRecVec * k + 4],
+                             r5 = tile[kTgRecVec * k + 5];
+                QShape Q;
+                Q.type = __float_as_uint(a0.w);
+                Q.c = v3_make(r2.x, r2.y, r2.z);
+                Q.h = v3_make(r2.w, r3.w, r4.w);
+                Q.R.m[0] = r3.x; Q.R.m[1] = r3.y; Q.R.m[2] = r3.z;
+                Q.R.m[3] = r4.x; Q.R.m[4] = r4.y; Q.R.m[5] = r4.z;
+                Q.R.m[6] = r5.x; Q.R.m[7] = r5.y; Q.R.m[8] = r5.z;
+                if (qr_overlap(Q, B)) now |= 1u << k;
+            }
+        }
+        uint32_t diff = 0;
+        if (live) {
+            uint32_t* word = bits + (size_t)wd * n + i;
+            diff = *word ^ now;
+            if (diff) *word = now;
+        }
+        if (EVENTS) {
+            unsigned long long slot = trigger_reserve((uint32_t)__popc(diff), wd, sh, cursor);
+            while (diff) {
+                const uint32_t b = (uint32_t)__ffs((int)diff) - 1u;
+                diff &= diff - 1u;
+                if (slot < capacity) ev_buf[slot] = make_uint4(t0 + b, i, ((now >> b) & 1u) ? PHYS_TRIGGER_ENTER : PHYS_TRIGGER_EXIT, step);
+                ++slot;
+            }
+        }
+    }
+}
+
+void triggers_free(phys_world* w) {
+    w->n_triggers = 0;
+    w->tg_masked = false;
+    w->tg_rec.free(); w->tg_rot.free(); w->tg_bits.free();
+    w->tg_bits_bodies = 0;
+    if (w->tg_capacity == 0) w->tg_cursor.free();
+}
+
+}  // namespace
+
+// an empty occupancy for the world's current trigger and body counts, and no pending events
+int32_t triggers_reset(phys_world* w) {
+    if (w->tg_cursor.p) PHYS_HIP_TRY(hipMemsetAsync(w->tg_cursor.p, 0, sizeof(unsigned long long), w->stream));
+    if (w->n_triggers == 0) return PHYS_OK;
+    const size_t words = (size_t)((w->n_triggers + kTgTile - 1) / kTgTile) * (size_t)w->n_owned;
+    PHYS_HIP_TRY(w->tg_bits.resize(words));
+    w->tg_bits_bodies = w->n_owned;
+    if (words) PHYS_HIP_TRY(hipMemsetAsync(w->tg_bits.p, 0, 4 * words, w->stream));
+    return PHYS_OK;
+}
+
+int32_t triggers_set(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot, const float* half_extent,
+                     const uint16_t* mask) {
+    if (n == 0) {  // back to launching nothing
+        triggers_free(w);
+        return triggers_reset(w);
+    }
+    PHYS_HIP_TRY(w->tg_rec.resize(4 * kTgRecVec * (size_t)n));
+    PHYS_HIP_TRY(w->tg_rot.resize(4 * (size_t)n));
+    PHYS_HIP_TRY(w->tg_cursor.resize(1));
+    if (n != w->n_triggers) w->tg_bits.free();  // another word count: another layout
+    w->n_triggers = n;
+    w->tg_masked = mask != nullptr;
+    hipLaunchKernelGGL(k_trigger_build, dim3((unsigned)((n + kTgThreads - 1) / kTgThreads)), dim3(kTgThreads), 0, w->stream, (uint32_t)n,
+                       shape_type, pos, rot, half_extent, mask, reinterpret_cast<float4*>(w->tg_rec.p), reinterpret_cast<float4*>(w->tg_rot.p));
+    PHYS_HIP_TRY(hipGetLastError());
+    return triggers_reset(w);
+}
+
+int32_t triggers_set_poses(phys_world* w, const float* pos, const float* rot) {
+    const uint64_t n = w->n_triggers;
+    if (n == 0) return PHYS_OK;
+    hipLaunchKernelGGL(k_trigger_build, dim3((unsigned)((n + kTgThreads - 1) / kTgThreads)), dim3(kTgThreads), 0, w->stream, (uint32_t)n,
+                       (const uint32_t*)nullptr, pos, rot, (const float*)nullptr, (const uint16_t*)nullptr,
+                       reinterpret_cast<float4*>(w->tg_rec.p), reinterpret_cast<float4*>(w->tg_rot.p));
+    PHYS_HIP_TRY(hipGetLastError());
+    return PHYS_OK;
+}
+
+// `step`: phys_stats.steps after this update (low 32 bits)
+void launch_triggers(phys_world* w, uint32_t step) {
+    if (w->n_triggers == 0 || w->n_owned == 0) return;  // (tg_bits is laid out for n_owned: triggers_reset behind every change of either)
+    const unsigned blocks = (unsigned)((w->n_owned + kTgThreads - 1) / kTgThreads);
+    PHYS_PROF(w, PHYS_STAGE_MISC);
+    dispatch_bool(w->tg_masked, [&](auto masked) {
+        dispatch_bool(w->tg_capacity != 0, [&](auto events) {
+            hipLaunchKernelGGL((k_trigger_eval<decltype(masked)::value, decltype(events)::value>), dim3(blocks), dim3(kTgThreads), 0, w->stream,
+                               (uint32_t)w->n_owned, w->pos.p, w->rot.p, w->half_extent.p, w->shape.p,
+                               reinterpret_cast<const uint2*>(w->filt.p), reinterpret_cast<const float4*>(w->tg_rec.p),
+                               (uint32_t)w->n_triggers, w->tg_bits.p, step, w->tg_cursor.p, reinterpret_cast<uint4*>(w->tg_buf.p),
+                               w->tg_capacity);
+        });
+    });
+}
+
+}  // namespace phys
+
+using namespace phys;
+
+extern "C" {
+
+int32_t phys_trigger_events_enable(phys_world* w, uint64_t capacity) {
+    ENTER(w);
+    if (capacity >= (1ull << 31)) return fail(PHYS_ERR_INVALID_ARG, "phys_trigger_events_enable: capacity must be below 2^31");
+    if (capacity == w->tg_capacity) return PHYS_OK;
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    w->tg_capacity = capacity;
+    w->tg_buf.free();  // a new capacity: a buffer of exactly that size; off: freed, pending events gone
+    if (capacity == 0) {
+        if (w->n_triggers == 0) w->tg_cursor.free();
+    } else {
+        PHYS_HIP_TRY(w->tg_buf.resize(4 * (size_t)capacity));
+        PHYS_HIP_TRY(w->tg_cursor.resize(1));
+    }
+    // a new capacity drops the pending events, nothing else: the occupancy stays
+    if (w->tg_cursor.p) PHYS_HIP_TRY(hipMemsetAsync(w->tg_cursor.p, 0, sizeof(unsigned long long), w->stream));
+    return PHYS_OK;
+}
+
+int32_t phys_get_trigger_events(phys_world* w, phys_trigger_event* out, uint64_t cap, uint64_t* n, uint64_t* n_dropped) {
+    ENTER(w);
+    if (!n) return fail(PHYS_ERR_INVALID_ARG, "phys_get_trigger_events: null n");
+    if (cap && !out) return fail(PHYS_ERR_INVALID_ARG, "phys_get_trigger_events: null out with cap > 0");
+    if (w->tg_capacity == 0) return fail(PHYS_ERR_UNSUPPORTED, "trigger events are off (phys_trigger_events_enable)");
+    unsigned long long cursor = 0;
+    PHYS_HIP_TRY(hipMemcpyAsync(&cursor, w->tg_cursor.p, sizeof(cursor), hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    const uint64_t stored = cursor < w->tg_capacity ? cursor : w->tg_capacity;
+    *n = stored;
+    if (n_dropped) *n_dropped = cursor - stored;
+    if (!out && cap == 0) return PHYS_OK;  // count query: the buffer stays
+    if (stored > cap) return fail(PHYS_ERR_CAPACITY, "phys_get_trigger_events: more events stored than cap (*n says how many); nothing was drained");
+    if (stored) {
+        PHYS_HIP_TRY(hipMemcpyAsync(out, w->tg_buf.p, stored * sizeof(phys_trigger_event), hipMemcpyDeviceToHost, w->stream));
+        PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+        // device order is arbitrary; a read-out convenience as in phys_get_contact_events
+        std::sort(out, out + stored, [](const phys_trigger_event& x, const phys_trigger_event& y) {
+            if (x.step != y.step) return x.step < y.step;
+            if (x.kind != y.kind) return x.kind < y.kind;
+            if (x.trigger != y.trigger) return x.trigger < y.trigger;
+            return x.body < y.body;
+        });
+    }
+    // ordered on the world's stream in front of the next update's kernel
+    if (cursor) PHYS_HIP_TRY(hipMemsetAsync(w->tg_cursor.p, 0, sizeof(cursor), w->stream));
+    return PHYS_OK;
+}
+
+int32_t phys_get_trigger_overlaps(phys_world* w, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out) {
+    ENTER(w);
+    if (!offsets_out) return fail(PHYS_ERR_INVALID_ARG, "phys_get_trigger_overlaps: null offsets_out");
+    if (cap && !ids_out) return fail(PHYS_ERR_INVALID_ARG, "phys_get_trigger_overlaps: null ids_out with cap > 0");
+    const uint64_t T = w->n_triggers, nb = w->n_owned;
+    for (uint64_t k = 0; k <= T; ++k) offsets_out[k] = 0;
+    if (T == 0 || nb == 0 || !w->tg_bits.p || w->tg_bits_bodies != nb) return PHYS_OK;
+    // the bit matrix to the host, one plane of 32 triggers at a time; not a hot path
+    const uint64_t words = (T + kTgTile - 1) / kTgTile;
+    std::vector<uint32_t> h((size_t)(words * nb));
+    PHYS_HIP_TRY(hipMemcpyAsync(h.data(), w->tg_bits.p, 4 * h.size(), hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    std::vector<uint64_t> count((size_t)T, 0);
+    for (uint64_t wd = 0; wd < words; ++wd)
+        for (uint64_t i = 0; i < nb; ++i)
+            for (uint32_t m = h[(size_t)(wd * nb + i)]; m; m &= m - 1u) {
+                const uint64_t k = wd * kTgTile + (uint32_t)__builtin_ctz(m);
+                if (k < T) count[(size_t)k]++;
+            }
+    uint64_t run = 0;
+    for (uint64_t k = 0; k < T; ++k) { offsets_out[k] = run; run += count[(size_t)k]; }
+    offsets_out[T] = run;
+    if (run > cap) return fail(PHYS_ERR_CAPACITY, "phys_get_trigger_overlaps: the ids need offsets_out[n] slots, more than cap");
+    std::vector<uint64_t> at(offsets_out, offsets_out + T);
+    for (uint64_t wd = 0; wd < words; ++wd)
+        for (uint64_t i = 0; i < nb; ++i)  // bodies ascending: every list ascending
+            for (uint32_t m = h[(size_t)(wd * nb + i)]; m; m &= m - 1u) {
+                const uint64_t k = wd * kTgTile + (uint32_t)__builtin_ctz(m);
+                if (k < T) ids_out[at[(size_t)k]++] = (uint32_t)i;
+            }
+    return PHYS_OK;
+}
+
+}  // extern "C"

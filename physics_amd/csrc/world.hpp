@@ -404,6 +404,16 @@ struct phys_world {
     phys::DevBuf<uint32_t> ev_state;     // 4 words: the 64-bit event cursor and the manifold counts of the last two updates (events.hip EventState)
     uint32_t ev_stamp = 0;               // updates with events so far (never 0 once one ran; wrap: launch_events)
     uint32_t ev_parity = 0;              // which of the two count words the next update writes
+    // trigger volumes (trigger.hip): nothing below is allocated, and nothing launched, without triggers
+    uint64_t n_triggers = 0;
+    bool tg_masked = false;              // phys_set_triggers was given a mask array: the evaluation's filtered instance
+    phys::DevBuf<float> tg_rec;          // 24 floats per trigger: {AABB lo, shape} {AABB hi, mask} {centre, h.x} 3 x {matrix row, h.y | h.z | -}
+    phys::DevBuf<float> tg_rot;          // 4 per trigger: its quaternion (phys_set_trigger_poses with rot NULL keeps it)
+    phys::DevBuf<uint32_t> tg_bits;      // occupancy, plane-major: word (k / 32) of body i at [(k / 32) * n_owned + i], bit k % 32
+    uint64_t tg_bits_bodies = 0;         // the n_owned tg_bits was laid out for
+    uint64_t tg_capacity = 0;            // trigger events the device keeps between two drains (0: off)
+    phys::DevBuf<uint32_t> tg_buf;       // 4 words = one phys_trigger_event per slot
+    phys::DevBuf<unsigned long long> tg_cursor;  // trigger events raised since the last drain (allocated with the triggers or the events)
     // multi-GPU halo
     phys::DevBuf<uint32_t> cross_pairs;
     uint64_t max_cross_pairs = 0;

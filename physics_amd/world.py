@@ -5,11 +5,13 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import STAGE_NAMES, PhysContactEvent, PhysDeviceView, PhysProfile, PhysStats, f32p, i16p, u16p, u32p
+from ._abi import STAGE_NAMES, PhysContactEvent, PhysDeviceView, PhysProfile, PhysStats, PhysTriggerEvent, f32p, i16p, u16p, u32p
 
 # one phys_contact_event as a numpy record (the layout of _abi.PhysContactEvent, 48 bytes)
 CONTACT_EVENT_DTYPE = np.dtype([("body_a", "<u4"), ("body_b", "<u4"), ("kind", "<u4"), ("step", "<u4"), ("point", "<f4", (3,)),
                                 ("impulse", "<f4"), ("normal", "<f4", (3,)), ("reserved", "<u4")])
+# one phys_trigger_event as a numpy record (the layout of _abi.PhysTriggerEvent, 16 bytes)
+TRIGGER_EVENT_DTYPE = np.dtype([("trigger", "<u4"), ("body", "<u4"), ("kind", "<u4"), ("step", "<u4")])
 
 
 class PhysError(RuntimeError):
@@ -91,6 +93,7 @@ class World:
         self.h = C.c_void_p()
         self.n = 0
         self.n_static = 0
+        self.n_triggers = 0
         self._ck(self.lib.phys_create(C.byref(self.cfg), C.byref(self.h)))
 
     def _ck(self, rc):
@@ -474,6 +477,76 @@ class World:
         if n.value:
             self._ck(self.lib.phys_get_contact_impulses(self.h, _p(out), n.value, C.byref(n)))
         return out
+
+    # ---- trigger volumes (include/physics_hip.h): which bodies are inside a shape, and which entered / left per update
+    def set_triggers(self, shape_type, pos, rot=None, half_extent=None, mask=None):
+        """Replace the trigger volumes (phys_set_triggers): shape_type scalar or (n,) SHAPE_SPHERE / BOX / CAPSULE, pos (n, 3),
+        rot (n, 4) [i, j, k, w] or None (identity), half_extent (3,) or (n, 3) with the bodies' conventions, mask a scalar
+        or (n,) u16 or None: trigger k sees body i iff category[i] & mask[k] (None: every body). An empty pos clears the
+        set. Forgets the occupancy and the pending trigger events; at most MAX_TRIGGERS volumes (the library refuses more)."""
+        p = _f(pos).reshape(-1, 3)
+        n = p.shape[0]
+        if n and half_extent is None:
+            raise ValueError("half_extent is required")
+        st = np.asarray(shape_type if n else np.zeros(0, np.uint32))
+        if st.ndim > 1 or (st.ndim == 1 and st.shape[0] != n):
+            raise ValueError(f"shape_type: needs {n} values, got shape {st.shape}")
+        st = np.ascontiguousarray(np.broadcast_to(st.astype(np.uint32), (n,)))
+        he = np.asarray(half_extent if n else np.zeros((0, 3)), np.float32).reshape(-1, 3)
+        if he.shape[0] not in (1, n):
+            raise ValueError(f"half_extent: needs 3 or {n} x 3 values, got shape {np.shape(half_extent)}")
+        he = np.ascontiguousarray(np.broadcast_to(he, (n, 3)))
+        r = None if rot is None else _f(rot).reshape(-1, 4)
+        if r is not None and r.shape[0] != n:
+            raise ValueError("rot does not match the trigger count")
+        m = _filter_field(mask, n, "mask", 0, 0xFFFF, np.uint16)
+        self._ck(self.lib.phys_set_triggers(self.h, n, _p(st, u32p), _p(p), _p(r), _p(he), _p(m, u16p)))
+        self.n_triggers = n
+
+    def set_trigger_poses(self, pos, rot=None):
+        """New positions (n_triggers, 3) and, unless None, rotations (n_triggers, 4) of the trigger volumes
+        (phys_set_trigger_poses), from the next update on. Keeps the occupancy: a body left behind raises EXIT."""
+        p = _f(pos).reshape(-1, 3)
+        r = None if rot is None else _f(rot).reshape(-1, 4)
+        if p.shape[0] != self.n_triggers or (r is not None and r.shape[0] != self.n_triggers):
+            raise ValueError(f"pos / rot: need {self.n_triggers} rows (the trigger count)")
+        self._ck(self.lib.phys_set_trigger_poses(self.h, self.n_triggers, _p(p), _p(r)))
+
+    def enable_trigger_events(self, capacity):
+        """Keep up to `capacity` trigger events on the device between two drains (phys_trigger_events_enable); 0 turns
+        them off. A new capacity drops the events not yet drained; the occupancy is tracked either way."""
+        self._ck(self.lib.phys_trigger_events_enable(self.h, int(capacity)))
+
+    def get_trigger_events(self):
+        """(events, n_dropped): every trigger event stored since the last drain as a structured array (TRIGGER_EVENT_DTYPE:
+        trigger, body, kind TRIGGER_ENTER / TRIGGER_EXIT, step), sorted by (step, kind, trigger, body), and the number of
+        events that did not fit the device buffer. Empties the buffer."""
+        n, dropped = C.c_uint64(), C.c_uint64()
+        self._ck(self.lib.phys_get_trigger_events(self.h, None, 0, C.byref(n), C.byref(dropped)))  # count only
+        while True:
+            out = np.zeros(n.value, TRIGGER_EVENT_DTYPE)
+            rc = self.lib.phys_get_trigger_events(self.h, out.ctypes.data_as(C.POINTER(PhysTriggerEvent)), out.shape[0],
+                                                  C.byref(n), C.byref(dropped))
+            if rc != _abi.PHYS_ERR_CAPACITY:  # (more than counted: another thread stepped the world in between; resize)
+                self._ck(rc)
+                return out[:n.value], dropped.value
+
+    def get_trigger_overlaps(self, cap=None):
+        """(offsets u64[n_triggers + 1], ids u32[offsets[-1]]): the occupants of every trigger as of the last update
+        (phys_get_trigger_overlaps); trigger k's body ids, ascending, are ids[offsets[k]:offsets[k + 1]]. The first call
+        reserves `cap` ids (default 8 per trigger) and, if they do not fit, the call is repeated once with the reported total."""
+        n = self.n_triggers
+        offsets = np.zeros(n + 1, np.uint64)
+        cap = 8 * n + 64 if cap is None else int(cap)
+        for attempt in range(2):
+            ids = np.empty(max(cap, 1), np.uint32)
+            rc = self.lib.phys_get_trigger_overlaps(self.h, cap, _p(offsets, _abi.u64p), _p(ids, u32p))
+            if rc == _abi.PHYS_ERR_CAPACITY and attempt == 0:
+                cap = int(offsets[n])
+                continue
+            self._ck(rc)
+            break
+        return offsets, ids[:int(offsets[n])]
 
     def get_color_counts(self):
         out = np.zeros(64, np.uint32)

@@ -32,6 +32,10 @@ pub const PHYS_RAY_GROUND: u32 = 0xFFFF_FFFF;
 // contact events: phys_contact_event.kind
 pub const PHYS_CONTACT_BEGIN: u32 = 1;
 pub const PHYS_CONTACT_END: u32 = 2;
+// trigger volumes: the most a world keeps, and phys_trigger_event.kind
+pub const PHYS_MAX_TRIGGERS: u32 = 1024;
+pub const PHYS_TRIGGER_ENTER: u32 = 1;
+pub const PHYS_TRIGGER_EXIT: u32 = 2;
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -90,6 +94,17 @@ pub struct phys_contact_event {
     pub impulse: f32,
     pub normal: [f32; 3],
     pub reserved: u32,
+}
+
+/// One trigger event (16 bytes): owned body `body` became (ENTER) or stopped being (EXIT) an occupant of trigger volume
+/// `trigger` in update `step`
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct phys_trigger_event {
+    pub trigger: u32,
+    pub body: u32,
+    pub kind: u32,
+    pub step: u32,
 }
 
 #[repr(C)]
@@ -202,6 +217,11 @@ extern "C" {
     pub fn phys_contact_events_enable(w: *mut phys_world, capacity: u64) -> i32;
     pub fn phys_get_contact_events(w: *mut phys_world, out: *mut phys_contact_event, cap: u64, n: *mut u64, n_dropped: *mut u64) -> i32;
     pub fn phys_get_contact_impulses(w: *mut phys_world, out: *mut f32, cap: u64, n_manifolds: *mut u64) -> i32;
+    pub fn phys_set_triggers(w: *mut phys_world, n: u64, shape_type: *const u32, pos: *const f32, rot_ijkw: *const f32, half_extent: *const f32, mask: *const u16) -> i32;
+    pub fn phys_set_trigger_poses(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32) -> i32;
+    pub fn phys_trigger_events_enable(w: *mut phys_world, capacity: u64) -> i32;
+    pub fn phys_get_trigger_events(w: *mut phys_world, out: *mut phys_trigger_event, cap: u64, n: *mut u64, n_dropped: *mut u64) -> i32;
+    pub fn phys_get_trigger_overlaps(w: *mut phys_world, cap: u64, offsets_out: *mut u64, ids_out: *mut u32) -> i32;
     pub fn phys_profile_enable(w: *mut phys_world, on: i32) -> i32;
     pub fn phys_profile_get(w: *mut phys_world, out: *mut phys_profile) -> i32;
     pub fn phys_get_device_view(w: *mut phys_world, out: *mut phys_device_view) -> i32;
