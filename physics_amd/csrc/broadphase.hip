@@ -5,7 +5,7 @@
 //   1. k_cell_assign   body -> cell of a uniform grid whose cell edge is the largest AABB extent of the
 //                      step (x1.001), cell -> bucket by 3-D Morton interleave of the low cell bits
 //                      (neighbouring cells = neighbouring buckets = neighbouring memory), count per bucket.
-//   2. exclusive scan  bucket counts -> bucket starts (one launch up to 32768 buckets, else 3 small kernels).
+//   2. exclusive scan  bucket counts -> bucket starts (scan.hip: one launch up to 32768 buckets, else 3 small kernels).
 //   3. k_scatter       bodies grouped by bucket: ids + a bucket-ordered COPY of the AABBs (24 B each), so
 //                      the pair kernel streams candidates instead of gathering them.
 //   4. k_find_pairs    one lane per body (bucket order), half shell of 14 cells; overlap test; hits are
@@ -24,9 +24,7 @@ namespace phys {
 
 constexpr uint32_t kInvalid = 0xFFFFFFFFu;
 
-// ---- bucket of a cell: kernels.hpp (grid_bucket: brick-major, per-axis sizes) -------------------------------------
-__device__ __forceinline__ uint32_t bucket_of_cell(int cx, int cy, int cz, const GridShape& g) { return grid_bucket(cx, cy, cz, g); }
-__device__ __forceinline__ int cell_coord(float c, float inv_cell) { return grid_cell_coord(c, inv_cell); }
+// (bucket of a cell: kernels.hpp grid_bucket - brick-major, per-axis sizes)
 __device__ __forceinline__ float grid_inv_cell(const StepCounters* ctr) {
     const float ext = __uint_as_float(ctr->max_extent_bits);
     const float cell = ext > 0.0f ? ext * 1.001f : 1.0f;
@@ -43,158 +41,12 @@ __global__ __launch_bounds__(256) void k_cell_assign(uint32_t n, const float* __
     if (shape[i] == PHYS_SPEC_SHAPE_NONE) { bucket_of[i] = kInvalid; return; }
     const float inv_cell = grid_inv_cell(ctr);
     const v3 lo = ld3(aabb, 2 * i), hi = ld3(aabb, 2 * i + 1);
-    const int cx = cell_coord(0.5f * (lo.x + hi.x), inv_cell);
-    const int cy = cell_coord(0.5f * (lo.y + hi.y), inv_cell);
-    const int cz = cell_coord(0.5f * (lo.z + hi.z), inv_cell);
-    const uint32_t bk = bucket_of_cell(cx, cy, cz, axis_mask);
+    const int cx = grid_cell_coord(0.5f * (lo.x + hi.x), inv_cell);
+    const int cy = grid_cell_coord(0.5f * (lo.y + hi.y), inv_cell);
+    const int cz = grid_cell_coord(0.5f * (lo.z + hi.z), inv_cell);
+    const uint32_t bk = grid_bucket(cx, cy, cz, axis_mask);
     bucket_of[i] = bk;
     rank[i] = atomicAdd(&bucket_count[bk], 1u);  // order inside a bucket is irrelevant downstream
-}
-
-// ---- exclusive scan of the bucket counts ----------------------------------------------------------
-constexpr int kScanThreads = 256;
-constexpr int kScanItems = 8;
-constexpr int kScanChunk = kScanThreads * kScanItems;
-
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)v, off, 64);
-        if (lane >= off) v += o;
-    }
-    return v;
-}
-
-// `block_used` (bucket grid only): per block, how many of its counters are non-zero = buckets in use; k_scan_block_sums
-// adds them up. Bodies per bucket in use is how CROWDED the grid is, which decides the pair kernel of later updates
-// (launch_broadphase). (Counted here, where every counter is read anyway: one atomic per workgroup of k_cell_assign -
-// 3906 of them at 1M bodies - cost that kernel 36 us.)
-__global__ __launch_bounds__(kScanThreads) void k_scan_reduce(const uint32_t* __restrict__ in, uint32_t count,
-                                                              uint32_t* __restrict__ block_sums,
-                                                              uint32_t* __restrict__ block_used = nullptr) {
-    __shared__ uint32_t wsum[kScanThreads / 64], wused[kScanThreads / 64];
-    const uint32_t base = blockIdx.x * kScanChunk + threadIdx.x * kScanItems;
-    uint32_t s = 0, u = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        const uint32_t v = (base + k < count) ? in[base + k] : 0u;
-        s += v;
-        u += v != 0u ? 1u : 0u;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { s += (uint32_t)__shfl_xor((int)s, off, 64); u += (uint32_t)__shfl_xor((int)u, off, 64); }
-    if ((threadIdx.x & 63) == 0) { wsum[threadIdx.x >> 6] = s; wused[threadIdx.x >> 6] = u; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0, tu = 0;
-        for (int k = 0; k < kScanThreads / 64; ++k) { t += wsum[k]; tu += wused[k]; }
-        block_sums[blockIdx.x] = t;
-        if (block_used) block_used[blockIdx.x] = tu;
-    }
-}
-
-// one block: exclusive scan of the block sums in place (loops with a carry for long inputs)
-__global__ __launch_bounds__(1024) void k_scan_block_sums(uint32_t* __restrict__ sums, uint32_t count,
-                                                          const uint32_t* __restrict__ block_used = nullptr,
-                                                          StepCounters* __restrict__ ctr = nullptr) {
-    __shared__ uint32_t wtot[16];
-    __shared__ uint32_t carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    if (block_used) {  // buckets in use, summed over the blocks of k_scan_reduce (no atomics on the way)
-        uint32_t u = 0;
-        for (uint32_t k = threadIdx.x; k < count; k += 1024) u += block_used[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) u += (uint32_t)__shfl_xor((int)u, off, 64);
-        if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = u;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t t = 0;
-            for (int k = 0; k < 16; ++k) t += wtot[k];
-            ctr->n_used_buckets = t;
-        }
-    }
-    __syncthreads();
-    for (uint32_t base = 0; base < count; base += 1024) {
-        const uint32_t idx = base + threadIdx.x;
-        const uint32_t v = idx < count ? sums[idx] : 0u;
-        const uint32_t inc = wave_inclusive_scan(v);
-        if ((threadIdx.x & 63) == 63) wtot[threadIdx.x >> 6] = inc;
-        __syncthreads();
-        uint32_t woff = 0;
-        for (uint32_t k = 0; k < (threadIdx.x >> 6); ++k) woff += wtot[k];
-        const uint32_t carry = carry_s;
-        if (idx < count) sums[idx] = carry + woff + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = carry + woff + inc;
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(kScanThreads) void k_scan_final(const uint32_t* __restrict__ in, uint32_t count,
-                                                             const uint32_t* __restrict__ block_sums,
-                                                             uint32_t* __restrict__ out /*count + 1*/) {
-    __shared__ uint32_t wtot[kScanThreads / 64];
-    const uint32_t base = blockIdx.x * kScanChunk + threadIdx.x * kScanItems;
-    uint32_t v[kScanItems];
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) { v[k] = (base + k < count) ? in[base + k] : 0u; s += v[k]; }
-    const uint32_t inc = wave_inclusive_scan(s);
-    if ((threadIdx.x & 63) == 63) wtot[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    uint32_t off = block_sums[blockIdx.x];
-    for (uint32_t k = 0; k < (threadIdx.x >> 6); ++k) off += wtot[k];
-    uint32_t run = off + inc - s;
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        if (base + k < count) out[base + k] = run;
-        run += v[k];
-        if (base + k + 1 == count) out[count] = run;  // grand total in the extra slot
-    }
-}
-
-// small tables (<= 32768 counters): the whole exclusive scan in ONE workgroup, one launch instead of three
-// (measured at 64 items per thread, for the cluster solver's 672 x 64 segment table: 25.6 us - one workgroup's lanes read
-// 256-byte runs each, every line is touched by eight load instructions - against 3 x 4.8 us for the three launches)
-constexpr int kScanSmallThreads = 1024;
-constexpr int kScanSmallItems = 32;
-// ZERO_IN: the counters are left zeroed for their next use (a per-step histogram then needs no memset launch of its own)
-template <bool ZERO_IN>
-__global__ __launch_bounds__(kScanSmallThreads) void k_scan_small(uint32_t* __restrict__ in, uint32_t count /* multiple of 4 */,
-                                                                  uint32_t* __restrict__ out /*count + 1*/) {
-    __shared__ uint32_t wtot[kScanSmallThreads / 64];
-    const uint32_t base = threadIdx.x * kScanSmallItems;
-    uint4 v[kScanSmallItems / 4];
-    uint32_t sum = 0;
-#pragma unroll
-    for (int k = 0; k < kScanSmallItems / 4; ++k) {
-        v[k] = make_uint4(0u, 0u, 0u, 0u);
-        if (base + 4 * k < count) {
-            v[k] = *reinterpret_cast<const uint4*>(in + base + 4 * k);
-            if (ZERO_IN) *reinterpret_cast<uint4*>(in + base + 4 * k) = make_uint4(0u, 0u, 0u, 0u);
-        }
-        sum += v[k].x + v[k].y + v[k].z + v[k].w;
-    }
-    const uint32_t inc = wave_inclusive_scan(sum);
-    if ((threadIdx.x & 63) == 63) wtot[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    uint32_t run = inc - sum;
-    for (uint32_t k = 0; k < (threadIdx.x >> 6); ++k) run += wtot[k];
-#pragma unroll
-    for (int k = 0; k < kScanSmallItems / 4; ++k) {
-        if (base + 4 * k < count) {
-            uint4 o;
-            o.x = run; o.y = o.x + v[k].x; o.z = o.y + v[k].y; o.w = o.z + v[k].z;
-            *reinterpret_cast<uint4*>(out + base + 4 * k) = o;
-            run = o.w + v[k].w;
-        }
-    }
-    if (threadIdx.x == kScanSmallThreads - 1) {
-        uint32_t total = 0;
-        for (int k = 0; k < kScanSmallThreads / 64; ++k) total += wtot[k];
-        out[count] = total;  // grand total in the extra slot
-    }
 }
 
 // ---- group bodies by bucket -----------------------------------------------------------------------
@@ -234,10 +86,10 @@ __global__ __launch_bounds__(kGridSmallThreads) void k_grid_small(uint32_t n, co
         bk[k] = kInvalid; rk[k] = 0;
         if (i < n && shape[i] != PHYS_SPEC_SHAPE_NONE) {
             const v3 lo = ld3(aabb, 2 * i), hi = ld3(aabb, 2 * i + 1);
-            const int cx = cell_coord(0.5f * (lo.x + hi.x), inv_cell);
-            const int cy = cell_coord(0.5f * (lo.y + hi.y), inv_cell);
-            const int cz = cell_coord(0.5f * (lo.z + hi.z), inv_cell);
-            bk[k] = bucket_of_cell(cx, cy, cz, axis_mask);
+            const int cx = grid_cell_coord(0.5f * (lo.x + hi.x), inv_cell);
+            const int cy = grid_cell_coord(0.5f * (lo.y + hi.y), inv_cell);
+            const int cz = grid_cell_coord(0.5f * (lo.z + hi.z), inv_cell);
+            bk[k] = grid_bucket(cx, cy, cz, axis_mask);
             rk[k] = atomicAdd(&bucket_count[bk[k]], 1u);  // order inside a bucket is irrelevant downstream
         }
     }
@@ -326,11 +178,7 @@ __device__ __forceinline__ void stage_push(PairStage& st, bool hit, uint32_t a, 
     if (mask == 0ull) return;
     const uint32_t hits = (uint32_t)__popcll(mask);
     if (st.count + hits > (uint32_t)kStageCap) stage_flush(st, pairs, max_pairs, ctr);
-    if (hit) {
-        const int lane = threadIdx.x & 63;
-        const uint32_t r = st.count + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-        reinterpret_cast<uint2*>(st.lds)[r] = make_uint2(a, b);
-    }
+    if (hit) reinterpret_cast<uint2*>(st.lds)[st.count + lane_rank(mask)] = make_uint2(a, b);
     st.count += hits;
 }
 
@@ -363,9 +211,9 @@ __global__ __launch_bounds__(kPairThreads) void k_find_pairs(const uint32_t* __r
         i = sorted_ids[s];
         bi.lo = ld3(sorted_box, 2 * s);
         bi.hi = ld3(sorted_box, 2 * s + 1);
-        cx = cell_coord(0.5f * (bi.lo.x + bi.hi.x), inv_cell);
-        cy = cell_coord(0.5f * (bi.lo.y + bi.hi.y), inv_cell);
-        cz = cell_coord(0.5f * (bi.lo.z + bi.hi.z), inv_cell);
+        cx = grid_cell_coord(0.5f * (bi.lo.x + bi.hi.x), inv_cell);
+        cy = grid_cell_coord(0.5f * (bi.lo.y + bi.hi.y), inv_cell);
+        cz = grid_cell_coord(0.5f * (bi.lo.z + bi.hi.z), inv_cell);
     }
     // half shell: own cell (c = 0) + the 13 cells with (dz, dy, dx) > (0, 0, 0) lexicographically
     uint32_t t0[kCellsPerLane], t1[kCellsPerLane];
@@ -379,7 +227,7 @@ __global__ __launch_bounds__(kPairThreads) void k_find_pairs(const uint32_t* __r
         else { dx = (c - 5) % 3 - 1; dy = ((c - 5) / 3) % 3 - 1; dz = 1; }
         t0[k] = 0; t1[k] = 0;
         if (live && c < 14) {
-            const uint32_t bk = bucket_of_cell(cx + dx, cy + dy, cz + dz, axis_mask);
+            const uint32_t bk = grid_bucket(cx + dx, cy + dy, cz + dz, axis_mask);
             t0[k] = bucket_start[bk];
             t1[k] = bucket_start[bk + 1];
         }
@@ -573,9 +421,9 @@ __global__ __launch_bounds__(kPairThreads, 7) void k_find_pairs_brick(const uint
                 bi.hi = ld3(sorted_box, 2 * sidx + 1);
             }
             // the brick's origin is a multiple of four cells on every axis: the low two bits are the place in the brick
-            const uint32_t lx = (uint32_t)cell_coord(0.5f * (bi.lo.x + bi.hi.x), inv_cell) & 3u;
-            const uint32_t ly = (uint32_t)cell_coord(0.5f * (bi.lo.y + bi.hi.y), inv_cell) & 3u;
-            const uint32_t lz = (uint32_t)cell_coord(0.5f * (bi.lo.z + bi.hi.z), inv_cell) & 3u;
+            const uint32_t lx = (uint32_t)grid_cell_coord(0.5f * (bi.lo.x + bi.hi.x), inv_cell) & 3u;
+            const uint32_t ly = (uint32_t)grid_cell_coord(0.5f * (bi.lo.y + bi.hi.y), inv_cell) & 3u;
+            const uint32_t lz = (uint32_t)grid_cell_coord(0.5f * (bi.lo.z + bi.hi.z), inv_cell) & 3u;
 #pragma unroll
             for (int k = 0; k < (14 + kBrickLanesPerBody - 1) / kBrickLanesPerBody; ++k) {
                 const int c = (int)sub + kBrickLanesPerBody * k;
@@ -640,10 +488,10 @@ __global__ __launch_bounds__(256) void k_cell_insert(uint32_t n, const float* __
     if (i >= n || shape[i] == PHYS_SPEC_SHAPE_NONE) return;
     const float inv_cell = grid_inv_cell(ctr);
     const v3 lo = ld3(aabb, 2 * i), hi = ld3(aabb, 2 * i + 1);
-    const int cx = cell_coord(0.5f * (lo.x + hi.x), inv_cell);
-    const int cy = cell_coord(0.5f * (lo.y + hi.y), inv_cell);
-    const int cz = cell_coord(0.5f * (lo.z + hi.z), inv_cell);
-    const uint32_t bk = bucket_of_cell(cx, cy, cz, axis_mask);
+    const int cx = grid_cell_coord(0.5f * (lo.x + hi.x), inv_cell);
+    const int cy = grid_cell_coord(0.5f * (lo.y + hi.y), inv_cell);
+    const int cz = grid_cell_coord(0.5f * (lo.z + hi.z), inv_cell);
+    const uint32_t bk = grid_bucket(cx, cy, cz, axis_mask);
     const uint32_t r = atomicAdd(&bucket_count[bk], 1u);  // which slot is irrelevant downstream
     rank[i] = r;
     if (r < kSlotsPerBucket) {
@@ -683,9 +531,9 @@ __global__ __launch_bounds__(kPairThreads) void k_find_pairs_slots(uint32_t n, c
     if (live) {
         bi.lo = ld3(aabb, 2 * i);
         bi.hi = ld3(aabb, 2 * i + 1);
-        cx = cell_coord(0.5f * (bi.lo.x + bi.hi.x), inv_cell);
-        cy = cell_coord(0.5f * (bi.lo.y + bi.hi.y), inv_cell);
-        cz = cell_coord(0.5f * (bi.lo.z + bi.hi.z), inv_cell);
+        cx = grid_cell_coord(0.5f * (bi.lo.x + bi.hi.x), inv_cell);
+        cy = grid_cell_coord(0.5f * (bi.lo.y + bi.hi.y), inv_cell);
+        cz = grid_cell_coord(0.5f * (bi.lo.z + bi.hi.z), inv_cell);
         in_overflow = rank[i] >= kSlotsPerBucket;
     }
     // half shell: own cell (c = 0) + the 13 cells with (dz, dy, dx) > (0, 0, 0) lexicographically. A body of the
@@ -701,7 +549,7 @@ __global__ __launch_bounds__(kPairThreads) void k_find_pairs_slots(uint32_t n, c
         else { dx = (c - 5) % 3 - 1; dy = ((c - 5) / 3) % 3 - 1; dz = 1; }
         cnt[k] = 0; first[k] = 0;
         if (live && !in_overflow && c < 14) {
-            const uint32_t bk = bucket_of_cell(cx + dx, cy + dy, cz + dz, axis_mask);
+            const uint32_t bk = grid_bucket(cx + dx, cy + dy, cz + dz, axis_mask);
             const uint32_t have = bucket_count[bk];
             first[k] = kSlotsPerBucket * bk;
             cnt[k] = have < kSlotsPerBucket ? have : kSlotsPerBucket;
@@ -811,7 +659,7 @@ int32_t collision_alloc(phys_world* w) {
     PHYS_HIP_TRY(w->bucket_of.resize(n));
     PHYS_HIP_TRY(w->bucket_cursor.resize(n));  // rank of each body inside its bucket
     PHYS_HIP_TRY(w->bucket_start.resize((size_t)T + 1));
-    PHYS_HIP_TRY(w->scan_block_sums.resize(2 * std::max<size_t>((T + kScanChunk - 1) / kScanChunk + 1, 64)));  // sums | buckets in use
+    PHYS_HIP_TRY(w->scan_block_sums.resize(2 * std::max<size_t>(scan_scratch_words(T) + 1, 64)));  // sums | buckets in use
     PHYS_HIP_TRY(w->sorted_ids.resize(n));
     PHYS_HIP_TRY(w->slot_ids.resize((size_t)kSlotsPerBucket * T));
     PHYS_HIP_TRY(w->slot_box.resize((size_t)6 * kSlotsPerBucket * T));
@@ -867,35 +715,16 @@ int32_t collision_alloc(phys_world* w) {
     return PHYS_OK;
 }
 
-// exclusive scan of `count` (a multiple of 4) counters into out[count + 1] on the world's stream
-bool scan_is_one_launch(uint32_t count) { return count <= (uint32_t)(kScanSmallThreads * kScanSmallItems); }
-
-// zero_in: only honoured by the one-launch scan (scan_is_one_launch(count)); the caller zeroes the counters itself otherwise
-void launch_exclusive_scan(phys_world* w, uint32_t* in, uint32_t count, uint32_t* out, bool zero_in) {
-    hipStream_t s = w->stream;
-    if (scan_is_one_launch(count)) {
-        if (zero_in) hipLaunchKernelGGL(k_scan_small<true>, dim3(1), dim3(kScanSmallThreads), 0, s, in, count, out);
-        else hipLaunchKernelGGL(k_scan_small<false>, dim3(1), dim3(kScanSmallThreads), 0, s, in, count, out);
-        return;
-    }
-    const uint32_t nblk = (count + kScanChunk - 1) / kScanChunk;
-    hipLaunchKernelGGL(k_scan_reduce, dim3(nblk), dim3(kScanThreads), 0, s, in, count, w->scan_block_sums.p);
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, s, w->scan_block_sums.p, nblk);
-    hipLaunchKernelGGL(k_scan_final, dim3(nblk), dim3(kScanThreads), 0, s, in, count, w->scan_block_sums.p, out);
-}
-
 void zero_step_state(phys_world* w, bool including_extent) {
     PHYS_PROF(w, PHYS_STAGE_MISC);
     (void)hipMemsetAsync(w->step_zero.p, 0, including_extent ? w->step_zero_full_bytes : w->step_zero_reset_bytes, w->stream);
 }
 
-static GridShape grid_axis_mask(const phys_world* w) { return w->grid_shape; }
-
 // bucket_start / sorted_ids / sorted_box from the current AABBs; the bucket counts must be zero
 void build_sorted_grid(phys_world* w) {
     const uint32_t n = (uint32_t)w->n;
     const uint32_t T = w->grid_table_size;
-    const GridShape axis_mask = grid_axis_mask(w);
+    const GridShape axis_mask = w->grid_shape;
     hipStream_t s = w->stream;
     const dim3 gb((n + 255) / 256), tb(256);
     w->sorted_grid_valid = true;
@@ -907,17 +736,9 @@ void build_sorted_grid(phys_world* w) {
     }
     { PHYS_PROF(w, PHYS_STAGE_GRID); hipLaunchKernelGGL(k_cell_assign, gb, tb, 0, s, n, w->aabb.p, w->shape.p, w->counters.p, axis_mask, w->bucket_of.p,
                        w->bucket_cursor.p, w->bucket_count.p); }
-    if (T <= (uint32_t)(kScanSmallThreads * kScanSmallItems) && T % 4 == 0) {
-        PHYS_PROF(w, PHYS_STAGE_GRID);
-        hipLaunchKernelGGL(k_scan_small<false>, dim3(1), dim3(kScanSmallThreads), 0, s, w->bucket_count.p, T, w->bucket_start.p);
-    } else {
-        const uint32_t nblk = (T + kScanChunk - 1) / kScanChunk;
-        uint32_t* used = w->scan_block_sums.p + (w->scan_block_sums.n / 2);  // second half of the buffer
-        { PHYS_PROF(w, PHYS_STAGE_GRID); hipLaunchKernelGGL(k_scan_reduce, dim3(nblk), dim3(kScanThreads), 0, s, w->bucket_count.p, T, w->scan_block_sums.p, used); }
-        { PHYS_PROF(w, PHYS_STAGE_GRID); hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, s, w->scan_block_sums.p, nblk, (const uint32_t*)used, w->counters.p); }
-        { PHYS_PROF(w, PHYS_STAGE_GRID); hipLaunchKernelGGL(k_scan_final, dim3(nblk), dim3(kScanThreads), 0, s, w->bucket_count.p, T, w->scan_block_sums.p,
-                           w->bucket_start.p); }
-    }
+    // (the second half of the scratch: buckets in use per block of the three-launch scan, summed into n_used_buckets)
+    launch_exclusive_scan(w, w->bucket_count.p, T, w->bucket_start.p, false, w->scan_block_sums.p,
+                          w->scan_block_sums.p + w->scan_block_sums.n / 2, w->counters.p, PHYS_STAGE_GRID);
     { PHYS_PROF(w, PHYS_STAGE_GRID); hipLaunchKernelGGL(k_scatter, gb, tb, 0, s, n, w->aabb.p, w->bucket_of.p, w->bucket_cursor.p, w->bucket_start.p,
                        w->sorted_ids.p, w->sorted_box.p); }
 }
@@ -927,7 +748,7 @@ void launch_broadphase(phys_world* w) {
     if (n == 0) return;
     w->grid_valid = true;
     const uint32_t T = w->grid_table_size;
-    const GridShape axis_mask = grid_axis_mask(w);
+    const GridShape axis_mask = w->grid_shape;
     hipStream_t s = w->stream;
     if (n <= kSlotGridMaxBodies) {
         // slot grid: two launches for the whole broad phase

@@ -345,7 +345,7 @@ void launch_cluster_sort(phys_world* w, unsigned blocks, StepCounters* snap_out)
         hipLaunchKernelGGL(k_active_flags, g, b, 0, s, (uint32_t)w->n_owned, w->color_state.p, w->bucket_of.p, w->bucket_cursor.p,
                            w->bucket_start.p, w->active_flag.p);
         const uint32_t n4 = (n + 3u) & ~3u;  // the scans want a multiple of four; the total lands behind the last entry
-        launch_exclusive_scan(w, w->active_flag.p, n4, w->active_rank.p, false);
+        launch_exclusive_scan(w, w->active_flag.p, n4, w->active_rank.p, false, w->scan_block_sums.p);
         hipLaunchKernelGGL(k_cluster_homes, g, b, 0, s, n, (uint32_t)w->n_owned, w->color_state.p, w->bucket_of.p, w->bucket_cursor.p,
                            w->bucket_start.p, w->active_rank.p, n4, homes, w->cluster_slot.p, w->cluster_body.p, w->counters.p);
     }
@@ -363,7 +363,7 @@ void launch_cluster_sort(phys_world* w, unsigned blocks, StepCounters* snap_out)
     const unsigned key_blocks = (unsigned)std::min<uint64_t>(blocks, std::max<uint64_t>(1, key_trips));
     hipLaunchKernelGGL(k_cluster_keys, dim3(key_blocks), dim3(256), 0, s, w->max_manifolds, w->man_a.p, w->man_b.p, w->man_color.p,
                        w->cluster_slot.p, w->cluster_slots, w->cluster_count, seg_count, w->man_rank.p, w->body_shared.p, w->counters.p);
-    launch_exclusive_scan(w, seg_count, bins, w->seg_start.p, scan_is_one_launch(bins));
+    launch_exclusive_scan(w, seg_count, bins, w->seg_start.p, scan_is_one_launch(bins), w->scan_block_sums.p);
     hipLaunchKernelGGL(k_cluster_place, dim3(blocks), dim3(256), 0, s, w->max_manifolds, w->man_a.p, w->man_b.p, w->man_color.p,
                        w->cluster_slot.p, w->cluster_slots, w->cluster_count, w->seg_start.p, w->man_rank.p, w->row_src.p, w->counters.p, snap_out);
 }

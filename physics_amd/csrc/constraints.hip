@@ -88,8 +88,7 @@ __device__ __forceinline__ float dyn_dot8(const float* __restrict__ a, const flo
 __device__ __forceinline__ float block_amax(const float* __restrict__ v, uint32_t n, float* __restrict__ lds16) {
     float m = 0.0f;
     for (uint32_t i = threadIdx.x; i < n; i += kCgThreads) { const float e = det_absf(v[i]); m = e > m ? e : m; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const float o = __shfl_xor(m, off, 64); m = o > m ? o : m; }
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) lds16[threadIdx.x >> 6] = m;
     __syncthreads();
     float r = 0.0f;

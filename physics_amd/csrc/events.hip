@@ -9,8 +9,8 @@
 //   k_events_end    over the previous update's manifolds: one that nobody stamped raises END.
 //
 // Events are appended to one buffer that lives across updates (also inside a phys_update_n batch). The cursor is
-// reserved once per workgroup and trip - wave ballot + popcount, per-wave totals in LDS, ONE global atomic - because
-// same-address atomics serialise chip-wide (~88 per microsecond). Slots at or beyond the capacity are not written; the
+// reserved once per workgroup and trip (wave.hpp slots_reserve_flag: wave ballot + popcount, per-wave totals in LDS, ONE
+// global atomic) because same-address atomics serialise chip-wide (~88 per microsecond). Slots at or beyond the capacity are not written; the
 // cursor keeps counting, and the drain reports the difference as dropped.
 #include "kernels.hpp"
 
@@ -25,30 +25,6 @@ struct EventState {
     uint32_t count[2];          // stored manifolds of the last two updates with events, by the update's parity
 };
 
-// LDS of one reservation; the per-wave totals alternate between two sets, so that a wave which runs ahead into the
-// next trip does not overwrite totals a slower wave still adds up
-struct EventAppend {
-    uint32_t wave_total[2][kEventWaves];
-    unsigned long long base;
-};
-
-// the slot of this lane's event (meaningful where emit is true); every thread of the workgroup calls it, once per trip
-__device__ __forceinline__ unsigned long long event_reserve(bool emit, uint32_t trip, EventAppend& sh, EventState* st) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, set = trip & 1u;
-    const unsigned long long mask = __ballot(emit);
-    if (lane == 0) sh.wave_total[set][wave] = (uint32_t)__popcll(mask);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int k = 0; k < kEventWaves; ++k) t += sh.wave_total[set][k];
-        sh.base = t ? atomicAdd(&st->cursor, (unsigned long long)t) : 0ull;
-    }
-    __syncthreads();
-    uint32_t off = 0;
-    for (uint32_t k = 0; k < wave; ++k) off += sh.wave_total[set][k];
-    return sh.base + off + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-}
-
 __device__ __forceinline__ void event_store(uint32_t* __restrict__ ev_buf, unsigned long long slot, uint4 w0, uint4 w1, uint4 w2) {
     uint4* o = reinterpret_cast<uint4*>(ev_buf) + 3 * slot;  // 48 bytes = phys_contact_event
     o[0] = w0; o[1] = w1; o[2] = w2;
@@ -60,7 +36,7 @@ __global__ __launch_bounds__(kEventThreads) void k_events_begin(const StepCounte
                                                                 uint32_t* __restrict__ ev_matched, uint32_t stamp, uint32_t step,
                                                                 uint32_t parity, EventState* __restrict__ st,
                                                                 uint32_t* __restrict__ ev_buf, uint64_t capacity) {
-    __shared__ EventAppend sh;
+    __shared__ SlotAppend<kEventWaves> sh;
     const uint32_t n = ctr->n_manifolds;  // final: the narrow phase ended launches ago
     const uint32_t M = (uint64_t)n < max_manifolds ? n : (uint32_t)max_manifolds;
     if (blockIdx.x == 0 && threadIdx.x == 0) st->count[parity] = M;  // what the next update's k_events_end runs over
@@ -96,7 +72,7 @@ __global__ __launch_bounds__(kEventThreads) void k_events_begin(const StepCounte
                 w2 = make_uint4(__float_as_uint(r1.x), __float_as_uint(r1.y), __float_as_uint(r1.z), 0u);
             }
         }
-        const unsigned long long slot = event_reserve(emit, trip, sh, st);
+        const unsigned long long slot = slots_reserve_flag(emit, trip, sh, &st->cursor);
         if (emit && slot < capacity) event_store(ev_buf, slot, w0, w1, w2);
     }
 }
@@ -105,7 +81,7 @@ __global__ __launch_bounds__(kEventThreads) void k_events_end(uint64_t max_manif
                                                               const uint32_t* __restrict__ ev_matched, uint32_t stamp, uint32_t step,
                                                               uint32_t parity_prev, EventState* __restrict__ st,
                                                               uint32_t* __restrict__ ev_buf, uint64_t capacity) {
-    __shared__ EventAppend sh;
+    __shared__ SlotAppend<kEventWaves> sh;
     const uint32_t n = st->count[parity_prev];  // left by the previous update's k_events_begin; 0 after a reset
     const uint32_t M = (uint64_t)n < max_manifolds ? n : (uint32_t)max_manifolds;
     const uint32_t stride = gridDim.x * kEventThreads;
@@ -119,7 +95,7 @@ __global__ __launch_bounds__(kEventThreads) void k_events_end(uint64_t max_manif
             const uint2 ab = *reinterpret_cast<const uint2*>(man_geo_prev + 32 * (size_t)k);
             w0 = make_uint4(ab.x, ab.y, PHYS_CONTACT_END, step);
         }
-        const unsigned long long slot = event_reserve(emit, trip, sh, st);
+        const unsigned long long slot = slots_reserve_flag(emit, trip, sh, &st->cursor);
         if (emit && slot < capacity) event_store(ev_buf, slot, w0, make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0));
     }
 }

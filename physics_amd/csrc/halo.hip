@@ -22,9 +22,6 @@ struct HaloRecord {
 };
 static_assert(sizeof(HaloRecord) == 32, "halo record is 32 bytes");
 
-__device__ __forceinline__ uint32_t bucket_h(int cx, int cy, int cz, const GridShape& g) { return grid_bucket(cx, cy, cz, g); }
-__device__ __forceinline__ int cell_h(float c, float inv_cell) { return grid_cell_coord(c, inv_cell); }
-
 __global__ __launch_bounds__(256) void k_halo_pack(uint32_t n, const float* __restrict__ aabb,
                                                    const uint32_t* __restrict__ shape,
                                                    const uint32_t* __restrict__ global_id, float x_lo, float x_hi,
@@ -41,12 +38,9 @@ __global__ __launch_bounds__(256) void k_halo_pack(uint32_t n, const float* __re
     }
     const unsigned long long mask = __ballot(take);
     if (mask == 0ull) return;
-    const int lane = threadIdx.x & 63;
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(&ctr->n_halo, (uint32_t)__popcll(mask));
-    base = (uint32_t)__shfl((int)base, 0, 64);
+    const uint32_t base = wave_append_base(mask, &ctr->n_halo);
     if (take) {
-        const uint64_t slot = (uint64_t)base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+        const uint64_t slot = (uint64_t)base + lane_rank(mask);
         if (slot < cap) {
             HaloRecord r;
             r.lo[0] = lo.x; r.lo[1] = lo.y; r.lo[2] = lo.z;
@@ -63,14 +57,11 @@ __global__ __launch_bounds__(256) void k_halo_pack(uint32_t n, const float* __re
 // every lane of the wave calls this together: the hits are appended with one atomic per wave
 __device__ __forceinline__ void emit_cross_pairs(bool hit, uint32_t j, uint32_t rgid, uint32_t* __restrict__ cross_pairs,
                                                  uint64_t cap, StepCounters* __restrict__ ctr) {
-    const int lane = threadIdx.x & 63;
     const unsigned long long mask = __ballot(hit);
     if (mask) {
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&ctr->n_cross_pairs, (uint32_t)__popcll(mask));
-        base = (uint32_t)__shfl((int)base, 0, 64);
+        const uint32_t base = wave_append_base(mask, &ctr->n_cross_pairs);
         if (hit) {
-            const uint64_t slot = (uint64_t)base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+            const uint64_t slot = (uint64_t)base + lane_rank(mask);
             if (slot < cap) { cross_pairs[2 * slot] = j; cross_pairs[2 * slot + 1] = rgid; }
             else flag_overflow(ctr, kOvfHalo);
         }
@@ -107,8 +98,8 @@ __global__ __launch_bounds__(256) void k_halo_pairs(uint32_t n_remote, uint32_t 
         rgid = r.gid;
         // owned bodies are binned by AABB centre, and a centre lies within half a cell of its box
         for (int a = 0; a < 3; ++a) {
-            c0[a] = cell_h(r.lo[a] - 0.5f * cell, inv_cell);
-            c1[a] = cell_h(r.hi[a] + 0.5f * cell, inv_cell);
+            c0[a] = grid_cell_coord(r.lo[a] - 0.5f * cell, inv_cell);
+            c1[a] = grid_cell_coord(r.hi[a] + 0.5f * cell, inv_cell);
             if (c1[a] - c0[a] > 7) c1[a] = c0[a] + 7;  // bound of the sweep (a remote box is at most `reach` wide; buckets met twice on
                                                        // a short axis are harmless: a candidate counts only in its TRUE cell, below)
         }
@@ -116,10 +107,7 @@ __global__ __launch_bounds__(256) void k_halo_pairs(uint32_t n_remote, uint32_t 
     // wave-uniform sweep over the largest cell range in the wave
     int span[3];
     for (int a = 0; a < 3; ++a) {
-        int s = live ? c1[a] - c0[a] + 1 : 0;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(s, off, 64); s = o > s ? o : s; }
-        span[a] = s;
+        span[a] = wave_max(live ? c1[a] - c0[a] + 1 : 0);
     }
     for (int dz = 0; dz < span[2]; ++dz)
         for (int dy = 0; dy < span[1]; ++dy)
@@ -128,7 +116,7 @@ __global__ __launch_bounds__(256) void k_halo_pairs(uint32_t n_remote, uint32_t 
                 const bool in = live && cx <= c1[0] && cy <= c1[1] && cz <= c1[2];
                 uint32_t t = 0, t_end = 0;
                 if (in) {
-                    const uint32_t bk = bucket_h(cx, cy, cz, axis_mask);
+                    const uint32_t bk = grid_bucket(cx, cy, cz, axis_mask);
                     if (SLOTS) {
                         const uint32_t have = bucket_start[bk];
                         t = kSlots * bk;
@@ -147,9 +135,9 @@ __global__ __launch_bounds__(256) void k_halo_pairs(uint32_t n_remote, uint32_t 
                         bj.lo = ld3(sorted_box, 2 * t);
                         bj.hi = ld3(sorted_box, 2 * t + 1);
                         // the candidate must really live in the scanned cell (buckets alias distant cells)
-                        const bool same_cell = cell_h(0.5f * (bj.lo.x + bj.hi.x), inv_cell) == cx &&
-                                               cell_h(0.5f * (bj.lo.y + bj.hi.y), inv_cell) == cy &&
-                                               cell_h(0.5f * (bj.lo.z + bj.hi.z), inv_cell) == cz;
+                        const bool same_cell = grid_cell_coord(0.5f * (bj.lo.x + bj.hi.x), inv_cell) == cx &&
+                                               grid_cell_coord(0.5f * (bj.lo.y + bj.hi.y), inv_cell) == cy &&
+                                               grid_cell_coord(0.5f * (bj.lo.z + bj.hi.z), inv_cell) == cz;
                         hit = same_cell && aabb_overlap(rb, bj) && global_id[j] < rgid;
                         ++t;
                     }
@@ -214,27 +202,25 @@ __global__ __launch_bounds__(256) void k_halo_count(uint32_t n_items, uint32_t n
     const unsigned long long mask = __ballot(take);
     if ((threadIdx.x & 63u) == 0u) wc[threadIdx.x >> 6] = (uint32_t)__popcll(mask);
     __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = block_get<256>(wc, op_sum{});
 }
 
 // exclusive offset of this workgroup = sum of the counts of the workgroups in front of it (a few thousand at most:
 // one strided pass); returns this lane's slot, or ~0 when the lane has nothing to place
 __device__ __forceinline__ uint32_t ordered_slot(bool take, const uint32_t* __restrict__ block_counts, uint32_t* total_out) {
-    __shared__ uint32_t s_part[4], s_wc[4], s_base;
+    __shared__ uint32_t s_part[4], s_wc[4];  // (one barrier: one call per kernel, the arrays are not rewritten)
     uint32_t part = 0;
     for (uint32_t b = threadIdx.x; b < blockIdx.x; b += 256u) part += block_counts[b];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) part += (uint32_t)__shfl_xor((int)part, off, 64);
     const unsigned long long mask = __ballot(take);
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    if (lane == 0) { s_part[wave] = part; s_wc[wave] = (uint32_t)__popcll(mask); }
+    const uint32_t wave = threadIdx.x >> 6;
+    block_put(part, s_part, op_sum{});
+    if ((threadIdx.x & 63u) == 0u) s_wc[wave] = (uint32_t)__popcll(mask);
     __syncthreads();
-    if (threadIdx.x == 0) s_base = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-    __syncthreads();
+    const uint32_t base = block_get<256>(s_part, op_sum{});
     uint32_t woff = 0;
     for (uint32_t k = 0; k < wave; ++k) woff += s_wc[k];
-    if (total_out && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total_out = s_base + s_wc[0] + s_wc[1] + s_wc[2] + s_wc[3];
-    return take ? s_base + woff + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)) : 0xFFFFFFFFu;
+    if (total_out && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total_out = base + block_get<256>(s_wc, op_sum{});
+    return take ? base + woff + lane_rank(mask) : 0xFFFFFFFFu;
 }
 
 __global__ __launch_bounds__(256) void k_halo_pack_bodies(uint32_t n_owned, const float* __restrict__ pos,

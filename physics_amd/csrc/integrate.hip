@@ -159,12 +159,7 @@ __global__ __launch_bounds__(256) void k_step_velocity_aabb(StepParams sp, const
             ext = det_maxf(b.hi.x - b.lo.x, det_maxf(b.hi.y - b.lo.y, b.hi.z - b.lo.z));
     }
     // largest extent: wave max by shuffles, one atomic per wave (max is order-independent => deterministic)
-    uint32_t bits = __float_as_uint(ext > 0.0f ? ext : 0.0f);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)bits, off, 64);
-        bits = o > bits ? o : bits;
-    }
+    const uint32_t bits = wave_max(__float_as_uint(ext > 0.0f ? ext : 0.0f));
     // one same-address atomic per wave would serialise the whole launch (~88 atomics/us on one word):
     // only waves that can still raise the maximum issue it (the plain read may be stale-low, never wrong)
     if ((threadIdx.x & 63) == 0 && bits > ctr->max_extent_bits) atomicMax(&ctr->max_extent_bits, bits);
@@ -188,12 +183,7 @@ __global__ __launch_bounds__(256) void k_aabb_only(uint32_t n, const float* __re
         if (type != PHYS_SPEC_SHAPE_NONE)
             ext = det_maxf(b.hi.x - b.lo.x, det_maxf(b.hi.y - b.lo.y, b.hi.z - b.lo.z));
     }
-    uint32_t bits = __float_as_uint(ext > 0.0f ? ext : 0.0f);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)bits, off, 64);
-        bits = o > bits ? o : bits;
-    }
+    const uint32_t bits = wave_max(__float_as_uint(ext > 0.0f ? ext : 0.0f));
     // one same-address atomic per wave would serialise the whole launch (~88 atomics/us on one word):
     // only waves that can still raise the maximum issue it (the plain read may be stale-low, never wrong)
     if ((threadIdx.x & 63) == 0 && bits > ctr->max_extent_bits) atomicMax(&ctr->max_extent_bits, bits);

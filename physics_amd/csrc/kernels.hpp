@@ -10,6 +10,7 @@
 #include "../../include/spec/det_math.h"
 #include "../../include/spec/vec.h"
 #include "world.hpp"
+#include "wave.hpp"
 
 static_assert(PHYS_MAX_COLORS == phys::kMaxColors, "colour limit mismatch");
 
@@ -112,6 +113,7 @@ __device__ __forceinline__ v3 granule_v3(u32x4 g) {
 // Round 1-2a rebuilt a table per update inside k_rows_build (an atomic and two scattered stores per manifold, plus the
 // sparse clear of the other table): 0.26 of k_rows_build's 0.50 ms on C5. The layout depends on arrival order, the
 // answers (exact key + stamp matches) do not.
+constexpr uint32_t kUncolored = 0xFFFFFFFFu;   // man_color of a manifold that kept no colour (narrowphase.hip -> coloring.hip)
 constexpr uint32_t kColorTableMaxWalk = 4096;  // slots a look-up may walk before it gives up (a full table must not hang a wave)
 struct ColorTableJob {
     ulonglong2* tab;  // null: nothing to do
@@ -238,7 +240,7 @@ void launch_broadphase(phys_world* w);
 void build_sorted_grid(phys_world* w);  // bucket_start / sorted_ids / sorted_box from the current AABBs (bucket counts zeroed)
 int32_t sorted_pairs_to_host(phys_world* w, uint32_t* pairs_out, uint64_t cap, uint64_t* n_pairs);
 
-// narrowphase.hip / solver.hip
+// narrowphase.hip / coloring.hip / solver.hip
 void launch_narrowphase(phys_world* w);
 void launch_coloring(phys_world* w);
 void snapshot_counters_async(phys_world* w);  // abi.hip
@@ -294,8 +296,13 @@ __device__ __forceinline__ void counters_snapshot(const StepCounters* ctr, StepC
     }
 }
 #endif
-void launch_exclusive_scan(phys_world* w, uint32_t* in, uint32_t count, uint32_t* out, bool zero_in);  // broadphase.hip; count % 4 == 0
+// scan.hip: exclusive scan of `count` (a multiple of 4) counters into out[count + 1], on the world's stream. scratch:
+// scan_scratch_words(count) words of the caller's (unused by the one-launch scan)
+void launch_exclusive_scan(phys_world* w, uint32_t* in, uint32_t count, uint32_t* out, bool zero_in, uint32_t* scratch,
+                           uint32_t* block_used = nullptr /* as many words again: non-zero counters per block ... */,
+                           StepCounters* ctr = nullptr /* ... summed into n_used_buckets */, int prof_stage = -1);
 bool scan_is_one_launch(uint32_t count);  // ... in which case zero_in leaves the counters zeroed behind the scan
+size_t scan_scratch_words(uint32_t count);
 bool cluster_plan_dynamic(phys_world* w);  // cluster.hip: clusters / slots of this update from the hint (dynamic clusters)
 void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float friction, const float* inertia, uint32_t stride,
                           bool diag, long long timeout_ticks, bool materials /* the rows carry their own friction */);

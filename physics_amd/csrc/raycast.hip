@@ -56,9 +56,9 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_bounds(uint32_t n, const floa
     }
     __shared__ float red[kRcThreads / 64][7];
     __shared__ int any_wave[kRcThreads / 64];
+    const auto op_fmax = [](float a, float b) { return fmaxf(a, b); };  // (never a NaN here: either order of operands)
 #pragma unroll
-    for (int a = 0; a < 7; ++a)
-        for (int off = 32; off > 0; off >>= 1) k[a] = fmaxf(k[a], __shfl_xor(k[a], off));
+    for (int a = 0; a < 7; ++a) k[a] = wave_reduce(k[a], op_fmax);
     const bool wave_any = __any(any);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
@@ -113,21 +113,24 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_insert(uint32_t n, const floa
             }
 }
 
-// exclusive scan over 4096-bucket tiles: tile sums, one workgroup scans the tile sums, tiles scanned with their offsets
+// exclusive scan over 4096-bucket tiles: tile sums, one workgroup scans the tile sums, tiles scanned with their offsets.
+// (Three small launches at every table size: the one-launch scan of scan.hip was 3 us per call slower at 32768 buckets,
+// DESIGN.md section 18.) The lane's exclusive prefix over the workgroup and the workgroup's total: the wave scan, then
+// the four wave totals.
 __device__ __forceinline__ uint32_t rc_block_exclusive(uint32_t v, uint32_t* total) {
-    __shared__ uint32_t s[kRcThreads];
-    s[threadIdx.x] = v;
+    __shared__ uint32_t s_tot[kRcThreads / 64];
+    const uint32_t inc = wave_inclusive_scan(v), wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 63u) s_tot[wave] = inc;
     __syncthreads();
-    for (int off = 1; off < kRcThreads; off <<= 1) {
-        const uint32_t add = threadIdx.x >= (unsigned)off ? s[threadIdx.x - off] : 0u;
-        __syncthreads();
-        s[threadIdx.x] += add;
-        __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)(kRcThreads / 64); ++k) {
+        const uint32_t t = s_tot[k];
+        if (k < wave) before += t;
+        all += t;
     }
-    const uint32_t incl = s[threadIdx.x];
-    *total = s[kRcThreads - 1];
-    __syncthreads();
-    return incl - v;
+    *total = all;
+    return before + inc - v;  // (one call per kernel: s_tot is not rewritten)
 }
 
 __global__ __launch_bounds__(kRcThreads) void k_rc_scan_reduce(const uint32_t* __restrict__ count, uint32_t* __restrict__ tile_sum) {
@@ -141,16 +144,8 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_scan_reduce(const uint32_t* _
 }
 
 __global__ __launch_bounds__(kRcThreads) void k_rc_scan_tiles(uint32_t* __restrict__ tile_sum, uint32_t tiles) {
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < tiles; base += kRcThreads) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < tiles ? tile_sum[i] : 0u;
-        uint32_t total;
-        const uint32_t ex = rc_block_exclusive(v, &total);
-        if (i < tiles) tile_sum[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) tile_sum[tiles] = carry;
+    const uint32_t total = block_scan_in_place<kRcThreads>(tile_sum, tiles);
+    if (threadIdx.x == 0) tile_sum[tiles] = total;
 }
 
 __global__ __launch_bounds__(kRcThreads) void k_rc_scan_final(const uint32_t* __restrict__ count, const uint32_t* __restrict__ tile_sum,
@@ -411,15 +406,11 @@ __global__ __launch_bounds__(kRcThreads) void k_sc_grow(uint32_t n, const float*
         const float r = radius[i];
         if (r >= 0.0f && r <= 3.4e38f) m = fmaxf(m, fminf(r, kScMaxGrow));
     }
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    const auto op_fmax = [](float a, float b) { return fmaxf(a, b); };
     __shared__ float red[kRcThreads / 64];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    block_put(m, red, op_fmax);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        float v = 0.0f;
-        for (int w = 0; w < kRcThreads / 64; ++w) v = fmaxf(v, red[w]);
-        atomicMax(&hdr->grow, __float_as_uint(v));
-    }
+    if (threadIdx.x == 0) atomicMax(&hdr->grow, __float_as_uint(block_get<kRcThreads>(red, op_fmax)));
 }
 
 }  // namespace

@@ -81,18 +81,6 @@ __device__ __forceinline__ void st_visit(const StaticGrid& g, v3 lo, v3 hi, F&& 
             }
 }
 
-// sum of v over the workgroup (kStThreads lanes); every lane gets it
-__device__ __forceinline__ uint32_t st_block_sum(uint32_t v, uint32_t* s_wave) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
-    if ((threadIdx.x & 63u) == 0u) s_wave[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t t = 0;
-#pragma unroll
-    for (int k = 0; k < kStThreads / 64; ++k) t += s_wave[k];
-    return t;
-}
-
 __global__ __launch_bounds__(kStThreads) void k_static_count(uint32_t n, const float* __restrict__ aabb, StaticGrid g,
                                                              uint32_t* __restrict__ count, uint32_t* __restrict__ block_total) {
     __shared__ uint32_t s_wave[kStThreads / 64];
@@ -102,7 +90,7 @@ __global__ __launch_bounds__(kStThreads) void k_static_count(uint32_t n, const f
         st_visit(g, ld3(aabb, 2 * i), ld3(aabb, 2 * i + 1), [&](uint32_t) { ++c; });
         count[i] = c;
     }
-    const uint32_t t = st_block_sum(c, s_wave);
+    const uint32_t t = block_sum<kStThreads>(c, s_wave);
     if (threadIdx.x == 0) block_total[blockIdx.x] = t;
 }
 
@@ -110,34 +98,8 @@ __global__ __launch_bounds__(kStThreads) void k_static_count(uint32_t n, const f
 // the overflow bit 0 when the pairs do not fit)
 __global__ __launch_bounds__(1024) void k_static_scan(uint32_t* __restrict__ block_total, uint32_t nb, uint64_t cap,
                                                       StepCounters* __restrict__ ctr) {
-    __shared__ uint32_t s_wave[16];
-    __shared__ uint32_t s_carry;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < nb; base += 1024u) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < nb ? block_total[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = (uint32_t)__shfl_up((int)inc, off, 64);
-            if (lane >= (uint32_t)off) inc += o;
-        }
-        if (lane == 63u) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t before = s_carry, all = 0;
-        for (uint32_t k = 0; k < 16u; ++k) {
-            if (k < wave) before += s_wave[k];
-            all += s_wave[k];
-        }
-        if (i < nb) block_total[i] = before + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 0) s_carry += all;
-        __syncthreads();
-    }
+    const uint32_t total = block_scan_in_place<1024>(block_total, nb);
     if (threadIdx.x == 0) {
-        const uint32_t total = s_carry;
         ctr->n_static_pairs = total;
         if ((uint64_t)total > cap) flag_overflow(ctr, kOvfPairs);
     }
@@ -151,12 +113,7 @@ __global__ __launch_bounds__(kStThreads) void k_static_fill(uint32_t n, const fl
     const uint32_t c = i < n ? count[i] : 0u;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     // the lane's exclusive prefix: inside the wave by a shuffle scan, across the waves from their totals
-    uint32_t inc = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)inc, off, 64);
-        if (lane >= (uint32_t)off) inc += o;
-    }
+    const uint32_t inc = wave_inclusive_scan(c);
     if (lane == 63u) s_wave[wave] = inc;
     __syncthreads();
     uint32_t off = block_off[blockIdx.x] + inc - c;

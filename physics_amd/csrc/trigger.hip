@@ -15,9 +15,9 @@
 // the loads and stores of one word by a wave are one contiguous 256-byte span. 4 * ceil(T / 32) * n_owned bytes: 128 MB
 // for 1M bodies and 1024 triggers.
 //
-// Events are appended like contact events (events.hip): one reservation per workgroup and trip - a wave prefix sum of
-// the lanes' event COUNTS (a lane may hold up to 32), per-wave totals in LDS, ONE global atomic - because same-address
-// atomics serialise chip-wide. Slots at or beyond the capacity are not written; the cursor keeps counting.
+// Events are appended like contact events (events.hip): one reservation per workgroup and trip (wave.hpp
+// slots_reserve_count: a wave prefix sum of the lanes' event COUNTS - a lane may hold up to 32 -, per-wave totals in LDS,
+// ONE global atomic) because same-address atomics serialise chip-wide. Slots at or beyond the capacity are not written; the cursor keeps counting.
 #include <cmath>
 #include <vector>
 
@@ -32,34 +32,6 @@ constexpr int kTgWaves = kTgThreads / 64;
 constexpr uint32_t kTgTile = 32;      // triggers per LDS tile = bits per occupancy word
 constexpr uint32_t kTgRecVec = 6;     // float4 per trigger record
 static_assert(kTgTile * kTgRecVec <= (uint32_t)kTgThreads, "one float4 per thread stages a tile");
-
-// LDS of one reservation (events.hip EventAppend: the totals alternate between two sets)
-struct TriggerAppend {
-    uint32_t wave_total[2][kTgWaves];
-    unsigned long long base;
-};
-
-// the first slot of this lane's `count` events; every thread of the workgroup calls it, once per trip
-__device__ __forceinline__ unsigned long long trigger_reserve(uint32_t count, uint32_t trip, TriggerAppend& sh, unsigned long long* cursor) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, set = trip & 1u;
-    uint32_t incl = count;  // inclusive prefix sum over the wave
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t below = __shfl_up(incl, d);
-        if (lane >= d) incl += below;
-    }
-    if (lane == 63u) sh.wave_total[set][wave] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int k = 0; k < kTgWaves; ++k) t += sh.wave_total[set][k];
-        sh.base = t ? atomicAdd(cursor, (unsigned long long)t) : 0ull;
-    }
-    __syncthreads();
-    uint32_t off = 0;
-    for (uint32_t k = 0; k < wave; ++k) off += sh.wave_total[set][k];
-    return sh.base + off + (incl - count);
-}
 
 // type null: new poses for the records that are there (shape, half extent and mask stay); rot null: identity then, the
 // stored quaternion otherwise
@@ -110,7 +82,7 @@ __global__ __launch_bounds__(kTgThreads) void k_trigger_eval(uint32_t n, const f
                                                              unsigned long long* __restrict__ cursor, uint4* __restrict__ ev_buf,
                                                              uint64_t capacity) {
     __shared__ float4 tile[kTgTile * kTgRecVec];
-    __shared__ TriggerAppend sh;
+    __shared__ SlotAppend<kTgWaves> sh;
     const uint32_t i = blockIdx.x * kTgThreads + threadIdx.x;
     const bool live = i < n;  // (no early return: the tiles and the reservation have barriers)
     bool shaped = false;      // SPHERE, BOX or CAPSULE at a finite pose: what can be an occupant at all
@@ -163,7 +135,7 @@ __global__ __launch_bounds__(kTgThreads) void k_trigger_eval(uint32_t n, const f
             if (diff) *word = now;
         }
         if (EVENTS) {
-            unsigned long long slot = trigger_reserve((uint32_t)__popc(diff), wd, sh, cursor);
+            unsigned long long slot = slots_reserve_count<kTgWaves>((uint32_t)__popc(diff), wd, sh, cursor);
             while (diff) {
                 const uint32_t b = (uint32_t)__ffs((int)diff) - 1u;
                 diff &= diff - 1u;

@@ -543,3 +543,32 @@ def test_first_update_sizes_the_pairs_of_a_tiled_floor():
     p = w.get_transforms()[0]
     assert np.abs(p[:, 1] - 0.5).max() < 0.02
     w.close()
+
+
+def test_pair_offsets_carry_past_1024_workgroups():
+    """k_static_scan scans the per-workgroup pair counts 1024 at a time with a carry: the second trip starts at workgroup
+    1024 = body 1024 * 256. One body more than that, on a sparse lattice, with one static box through five of them - the
+    last body (the second trip: its offset is the carry) and four spread over the first trip. The pair count and the
+    pair set (every pair here penetrates, so each is a manifold against the static) must equal a numpy AABB-overlap
+    count over the same arrays."""
+    n = 1024 * 256 + 1
+    k = np.arange(64 * 64 * 65)[:n]
+    pos = (3.0 * np.column_stack([k % 64, (k // 64) % 64, k // 4096]) + [0.0, 0.0, 30.0]).astype(np.float32)
+    touched = np.array([5, 70_000, 200_000, n - 2, n - 1])
+    pos[touched] = [[3.0 * j, 0.0, 0.0] for j in range(5)]  # a row of their own, clear of the lattice
+    box_c, box_h = np.array([6.0, 0.0, 0.0]), np.array([6.2, 0.3, 0.3])
+    w = physics_amd.World(physics_amd.default_config(flags=COLL, gravity_offset=(0, 0, 0)))  # (contact margin: MARGIN)
+    w.set_bodies(pos, shape_type=np.full(n, BOX, np.uint32), half_extent=np.full((n, 3), 0.5, np.float32))
+    _set(w, _statics(boxes=[(box_c, box_h)]))
+    w.update(DT)
+    w.sync()
+    aabb = w.get_aabbs()
+    lo, hi = aabb[:, :3], aabb[:, 3:]
+    hit = np.all((lo <= box_c + box_h + MARGIN) & (hi >= box_c - box_h - MARGIN), axis=1)
+    assert sorted(np.flatnonzero(hit)) == sorted(touched), "the scene is not the one the test describes"
+    n_st, n_pairs, n_man = w.get_static_stats()
+    assert (n_st, n_pairs, n_man) == (1, int(hit.sum()), int(hit.sum()))
+    ids = w.get_manifolds()[0]
+    got = sorted((int(a), int(b)) for a, b in ids if b & BIT)
+    assert got == [(int(i), BIT | 0) for i in sorted(touched)]
+    w.close()
