@@ -39,18 +39,54 @@ StepCounters* snapshot_acquire(phys_world* w) {
     }
     return w->h_snap[k];
 }
-void snapshot_commit(phys_world* w) {
+void snapshot_commit(phys_world* w, bool full) {
     const uint32_t k = w->snap_next;
     (void)hipEventRecord(w->snap_event[k], w->stream);
     w->snap_pending[k] = true;
-    w->snap_full[k] = w->snap_tag_full;  // was this update a full re-colouring?
+    w->snap_full[k] = full;  // was this update a full re-colouring?
     w->snap_next = (k + 1) % phys_world::kSnapRing;
 }
-void snapshot_counters_async(phys_world* w) {
+void snapshot_counters_async(phys_world* w, bool full) {
     StepCounters* slot = snapshot_acquire(w);
     if (!slot) return;
     (void)hipMemcpyAsync(slot, w->counters.p, sizeof(StepCounters), hipMemcpyDeviceToHost, w->stream);
-    snapshot_commit(w);
+    snapshot_commit(w, full);
+}
+
+// Counters become the hint. The colouring rounds: a full re-colouring and an incremental update need very different counts,
+// and the incremental count fluctuates, so the full count is remembered by itself, and of the incremental ones the maximum
+// over a ring of the last eight snapshots (with it, the most new manifolds of one update). The two callers differ in the
+// ring: poll_snapshots pushes every incremental snapshot into it; the Probe path of launch_coloring (`exact`: hint invalid,
+// the update has just waited for its own counters) writes color_rounds alone and leaves the ring and n_new as they are. That
+// is the behaviour both had as separate copies and it is kept: an exact incremental count only arises when no snapshot has
+// been adopted since phys_set_bodies (an update that overflowed leaves a colour table but no hint), the ring is empty then,
+// and the next incremental snapshot replaces the count by the ring's maximum - so the exact count serves the updates in
+// between and never enters the maximum.
+void hint_adopt(StepHint& hint, const StepCounters& c, bool full, bool exact) {
+    hint.valid = true;
+    hint.n_manifolds = c.n_manifolds;
+    hint.n_pairs = c.n_pairs;
+    hint.n_contacts = c.n_contacts;
+    if (c.max_region) hint.max_region = c.max_region;
+    hint.n_used_buckets = c.n_used_buckets;
+    hint.n_colors = c.n_colors;
+    if (c.n_active) hint.n_active = c.n_active;  // counted only in the updates that deal out the dynamic homes
+    if (full) {
+        hint.full_rounds = c.color_rounds;
+    } else if (exact) {
+        hint.color_rounds = c.color_rounds;
+    } else {
+        hint.recent_new[hint.recent_pos % 8] = c.n_new_manifolds;
+        hint.recent_rounds[hint.recent_pos++ % 8] = c.color_rounds;
+        uint32_t mx = 0, mn = 0;
+        for (int q = 0; q < 8; ++q) {
+            mx = hint.recent_rounds[q] > mx ? hint.recent_rounds[q] : mx;
+            mn = hint.recent_new[q] > mn ? hint.recent_new[q] : mn;
+        }
+        hint.color_rounds = mx;
+        hint.n_new = mn;
+    }
+    for (int q = 0; q < kMaxColors; ++q) hint.color_count[q] = c.color_count[q];
 }
 
 // adopt every snapshot whose copy has completed (oldest first, so the newest complete one wins)
@@ -67,30 +103,7 @@ void poll_snapshots(phys_world* w) {
         w->host_sticky_overflow |= c.overflow | c.sticky_overflow;  // latched until phys_sync reports it
         if (c.n_static_pairs > w->static_pairs_seen) w->static_pairs_seen = c.n_static_pairs;  // sizes the static pairs (static.hip)
         if (c.overflow) continue;
-        w->hint.valid = true;
-        w->hint.n_manifolds = c.n_manifolds;
-        w->hint.n_pairs = c.n_pairs;
-        w->hint.n_contacts = c.n_contacts;
-        if (c.max_region) w->hint.max_region = c.max_region;
-        w->hint.n_used_buckets = c.n_used_buckets;
-        w->hint.n_colors = c.n_colors;
-        if (c.n_active) w->hint.n_active = c.n_active;  // counted only in the updates that deal out the dynamic homes
-        // colouring rounds: a full re-colouring and an incremental update need very different counts, and the
-        // incremental count fluctuates: remember the full count, and the maximum of the recent incremental ones
-        if (w->snap_full[k]) {
-            w->hint.full_rounds = c.color_rounds;
-        } else {
-            w->hint.recent_new[w->hint.recent_pos % 8] = c.n_new_manifolds;
-            w->hint.recent_rounds[w->hint.recent_pos++ % 8] = c.color_rounds;
-            uint32_t mx = 0, mn = 0;
-            for (int q = 0; q < 8; ++q) {
-                mx = w->hint.recent_rounds[q] > mx ? w->hint.recent_rounds[q] : mx;
-                mn = w->hint.recent_new[q] > mn ? w->hint.recent_new[q] : mn;
-            }
-            w->hint.color_rounds = mx;
-            w->hint.n_new = mn;
-        }
-        for (int q = 0; q < kMaxColors; ++q) w->hint.color_count[q] = c.color_count[q];
+        hint_adopt(w->hint, c, w->snap_full[k], /*exact=*/false);
     }
 }
 }  // namespace phys
@@ -100,6 +113,35 @@ static std::atomic<int> g_worlds[64];
 int worlds_on_device(int device) { return g_worlds[device & 63].load(std::memory_order_relaxed); }
 bool gpu_is_exclusive(const phys_world* w) {
     return (w->cfg.flags & PHYS_FLAG_EXCLUSIVE_GPU) && !(w->cfg.flags & PHYS_FLAG_SHARED_GPU) && worlds_on_device(w->device) == 1;
+}
+
+// what the plan reads of the world (plan.hpp), as the world stands now
+static PlanInputs plan_inputs(const phys_world* w) {
+    PlanInputs in;
+    in.flags = w->cfg.flags; in.solver_iterations = w->cfg.solver_iterations;
+    in.n = w->n; in.n_owned = w->n_owned; in.max_manifolds = w->max_manifolds;
+    in.grid_table_size = w->grid_table_size;
+    in.cus = w->cus;
+    in.exclusive = gpu_is_exclusive(w);
+    in.warm = w->warm;
+    in.flow_vel = w->flow_vel.p != nullptr;
+    in.cluster_count = w->cluster_count; in.cluster_dynamic = w->cluster_dynamic;
+    in.ctab_valid = w->ctab_valid; in.color_epoch = w->color_epoch;
+    uint64_t st_cap = 0;
+    const uint32_t* st_pairs = nullptr;
+    const float* st_geo = nullptr;
+    static_narrow_args(w, &st_cap, &st_pairs, &st_geo);
+    const uint64_t n_ground = (w->cfg.flags & PHYS_FLAG_GROUND_PLANE) ? (uint32_t)w->n : 0u;
+    in.statics = st_pairs != nullptr;
+    // Capsules: the capsule variant wherever one can meet the narrow phase - an owned body (phys_set_bodies), a static in
+    // use, or any ghost slot: ghosts arrive on the device with the shapes of another rank, which the host never sees
+    in.capsules = w->body_capsules || (in.statics && w->static_capsules) || w->max_ghosts > 0;
+    // Filters: the filtered variant once any filter was set since its reset (whatever the values), and
+    // in every world with ghost slots: their filters arrive with the halo records, which the host never sees
+    in.filters = w->body_filters_set || (in.statics && w->static_filters_set) || (n_ground && w->ground_filter_set) || w->max_ghosts > 0;
+    in.materials = materials_active(w);
+    in.np_items = n_ground + w->max_pairs + st_cap;
+    return in;
 }
 
 // the value of a switch, parsed by `parse`; std::nullopt when the variable is not set
@@ -253,9 +295,12 @@ int32_t phys_create(const phys_config* cfg, phys_world** out) {
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(PHYS_ERR_NO_DEVICE, "device is not gfx950 (MI355X); this library carries gfx950 code only");
     PHYS_HIP_TRY(hipSetDevice(cfg->device));
+    int cus = 0;
+    PHYS_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device));
     phys_world* w = new phys_world();
     w->cfg = *cfg;
     w->device = cfg->device;
+    w->cus = cus;
     hipError_t e = hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete w; return fail(PHYS_ERR_HIP, "hipStreamCreate failed"); }  // ~phys_world: whatever exists by then
     e = w->counters.resize(1);
@@ -454,10 +499,14 @@ int32_t phys_step(phys_world* w, uint64_t dt_nanos) {
 }
 
 // one PhysicsState::update (physics.rs:41-55), enqueued without synchronising
+// The collision stages in their order: poll the snapshots, plan (plan.hpp), launch. The plan is made where its inputs stand:
+// the pair search and the colouring up front, the narrow phase behind the static pairs (which size its work), the solver
+// behind the colouring stage (which, on its Probe path, has adopted exact counters as the hint by then).
 static int32_t enqueue_update(phys_world* w, float dt) {
     // a zero-length step has no contact problem to solve (the bias terms divide by dt): plain RigidBody::step then
     const bool collisions = (w->cfg.flags & PHYS_FLAG_COLLISIONS) != 0 && dt > 0.0f;
     if (collisions) poll_snapshots(w);
+    const DebugSwitches& dbg = debug_switches();
     const bool have_constraints = !w->constraints.empty();
     bool gravity_pending = true;
     if (have_constraints) {
@@ -476,16 +525,21 @@ static int32_t enqueue_update(phys_world* w, float dt) {
         const bool restart_extent = w->steps % 32 == 0 || w->step_zero_reset_bytes % 16 != 0 || (w->step_zero_reset_bytes >> 36) != 0;
         if (restart_extent) zero_step_state(w, /*including_extent=*/true);
         launch_step_velocity_aabb(w, dt, gravity_pending, /*zero_step=*/!restart_extent, have_constraints);
-        launch_broadphase(w);
+        launch_broadphase(w, plan_pairs(plan_inputs(w), w->hint, dbg));
         if (!(w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY)) {
             const int32_t rc = launch_static_pairs(w);  // static colliders only (phys_set_static_bodies): nothing otherwise
             if (rc != PHYS_OK) return rc;
-            launch_narrowphase(w);
-            launch_coloring(w);
-            launch_solver(w, dt);
-            if (w->ev_capacity) launch_events(w, (uint32_t)(w->steps + 1));  // contact events: nothing in a world without them
+            const PlanInputs in = plan_inputs(w);
+            launch_narrowphase(w, plan_narrowphase(in, w->hint, dbg));
+            const ColorPlan coloring = plan_coloring(in, w->hint, dbg);
+            // dynamic clusters are remade from this update's bodies every few updates, and may not fit: their answer is an input
+            const bool cluster = coloring.wants_cluster && (!w->cluster_dynamic || cluster_plan_dynamic(w, w->hint, dbg));
+            launch_coloring(w, coloring, cluster);
+            launch_solver(w, dt, plan_solver(in, w->hint, dbg, cluster), coloring);  // (the hint may be the exact one now)
+            // contact events: nothing in a world without them
+            if (w->ev_capacity) launch_events(w, (uint32_t)(w->steps + 1), plan_event_blocks(in, w->hint));
         } else {
-            snapshot_counters_async(w);  // launch-size hints of later updates (the colouring stage takes it otherwise)
+            snapshot_counters_async(w, /*full=*/false);  // launch-size hints of later updates (the colouring stage takes it otherwise)
         }
         launch_step_position(w, dt);
     }
@@ -641,7 +695,7 @@ int32_t phys_broadphase(phys_world* w, uint32_t* pairs_out, uint64_t cap, uint64
     if (w->n == 0) { *n_pairs = 0; return PHYS_OK; }
     zero_step_state(w, true);
     launch_aabb_only(w);
-    launch_broadphase(w);
+    launch_broadphase(w, plan_pairs(plan_inputs(w), w->hint, debug_switches()));
     PHYS_HIP_TRY(hipGetLastError());
     return sorted_pairs_to_host(w, pairs_out, cap, n_pairs);
 }

@@ -141,7 +141,6 @@ __global__ __launch_bounds__(kGridSmallThreads) void k_grid_small(uint32_t n, co
 }
 
 // ---- candidate pairs ------------------------------------------------------------------------------
-constexpr int kPairThreads = 256;
 constexpr int kStagePerWave = 512;  // pairs staged in LDS per wave before a flush (4 KiB)
 
 struct PairStage {
@@ -272,7 +271,6 @@ __global__ __launch_bounds__(kPairThreads) void k_find_pairs(const uint32_t* __r
 // XCD (blockIdx % 8) cover one contiguous eighth of the table: a box is fetched into ONE L2, and again only by the
 // neighbour XCDs along the eighth's two faces. Same pair SET as k_find_pairs (each pair found by the body whose cell
 // comes first in the half-shell order; own-cell pairs by id order).
-constexpr int kRegX = 6, kRegY = 6, kRegZ = 5, kRegCells = kRegX * kRegY * kRegZ;  // 180
 constexpr int kBrickLanesPerBody = 4;
 // pairs staged per wave: 256 (2 KiB) where a body has many pairs (C5: 12 - at 128 the flushes, one same-address atomic
 // each, made its search 0.244 ms instead of 0.069), 128 where it has few (C4: 1.3; a seventh workgroup per CU fits)
@@ -477,7 +475,6 @@ __global__ __launch_bounds__(kPairThreads, 7) void k_find_pairs_brick(const uint
 // pair kernel reads the neighbours' slots directly. A body that finds the eight slots taken goes to a short overflow list that every body also tests against, so the pair SET is the same as with the
 // sorted grid whatever the occupancy; only the speed depends on it.
 constexpr uint32_t kSlotsPerBucket = 8;
-constexpr uint32_t kSlotGridMaxBodies = 32768;  // beyond, streaming the sorted boxes is as fast
 
 __global__ __launch_bounds__(256) void k_cell_insert(uint32_t n, const float* __restrict__ aabb,
                                                      const uint32_t* __restrict__ shape, StepCounters* __restrict__ ctr,
@@ -743,81 +740,47 @@ void build_sorted_grid(phys_world* w) {
                        w->sorted_ids.p, w->sorted_box.p); }
 }
 
-void launch_broadphase(phys_world* w) {
+void launch_broadphase(phys_world* w, const PairPlan& plan) {
     const uint32_t n = (uint32_t)w->n;
     if (n == 0) return;
     w->grid_valid = true;
     const uint32_t T = w->grid_table_size;
     const GridShape axis_mask = w->grid_shape;
     hipStream_t s = w->stream;
-    if (n <= kSlotGridMaxBodies) {
+    const dim3 wgs(plan.wgs), tb(kPairThreads);
+    if (plan.kernel == PairKernel::Slots) {
         // slot grid: two launches for the whole broad phase
         w->sorted_grid_valid = false;
         { PHYS_PROF(w, PHYS_STAGE_GRID); hipLaunchKernelGGL(k_cell_insert, dim3((n + 255) / 256), dim3(256), 0, s, n, w->aabb.p, w->shape.p, w->counters.p,
                            axis_mask, w->bucket_cursor.p, w->bucket_count.p, w->slot_ids.p, w->slot_box.p, w->grid_ovf.p); }
         PHYS_PROF(w, PHYS_STAGE_PAIRS);
-        hipLaunchKernelGGL((k_find_pairs_slots<4>), dim3((unsigned)(((uint64_t)n * 4 + kPairThreads - 1) / kPairThreads)), dim3(kPairThreads), 0, s,
+        hipLaunchKernelGGL((k_find_pairs_slots<4>), wgs, tb, 0, s,
                            n, w->aabb.p, w->shape.p, w->bucket_cursor.p, w->bucket_count.p, w->slot_ids.p, w->slot_box.p, w->grid_ovf.p, axis_mask,
                            w->pairs.p, w->max_pairs, w->counters.p);
         return;
     }
     build_sorted_grid(w);
-    // small scenes are latency-bound: 4 lanes per body shorten the dependent chain; large scenes are
-    // throughput-bound: one lane per body does the least total work
-    // (measured: one lane per body is the faster one already at 100k bodies - C3: 0.051 against 0.089 ms)
-    // PHYS_DEBUG_PAIR_LANES=1|4 and PHYS_DEBUG_PAIR_KERNEL=body / brick force one (measurements; same pair set)
-    const DebugSwitches& dbg = debug_switches();
-    // The brick kernel wins where the grid is sparsely filled - lattices, stacks of aligned boxes: many bricks of few
-    // records (C4 204 -> 119 us, C5 135 -> 73) - and loses where cells are crowded (one tumbled cube sets the cell size for
-    // everybody: 1M falling cubes 89 -> 102 us, C3 51 -> 82: few bricks, each a long walk for the one workgroup that has
-    // it). Crowding = bodies per bucket in use, counted by k_cell_assign of an earlier update.
-    const bool crowded = w->hint.valid && w->hint.n_used_buckets && (uint64_t)w->n * 10ull > (uint64_t)w->hint.n_used_buckets * 21ull;
-    const bool brick = dbg.pair_kernel_brick.value_or(!crowded);
-    if (brick && !dbg.pair_lanes) {
+    if (plan.kernel == PairKernel::Brick128 || plan.kernel == PairKernel::Brick256) {
+        static bool attr_set[64] = {};
+        (void)allow_dynamic_lds(attr_set, w->device, {reinterpret_cast<const void*>(&k_find_pairs_brick<128>),
+                                                      reinterpret_cast<const void*>(&k_find_pairs_brick<256>)}, 150 * 1024);
         const uint32_t n_bricks = T >> 6;
-        // records staged per brick: a quarter more than the largest region of an earlier update (C4: ~400 records, a pile
-        // of tumbled cubes: ~1500), 1024 while nothing is known, at most what one workgroup may have of a CU's LDS
-        constexpr uint32_t kCapMax = 5000;  // 137 KiB
-        uint32_t cap = w->hint.valid && w->hint.max_region ? w->hint.max_region + w->hint.max_region / 4 : 1024u;
-        cap = std::min(std::max((cap + 63u) & ~63u, 256u), kCapMax);
-        const size_t dyn = (size_t)cap * 28;
-        // few pairs per body (of an earlier update): the small stage, which leaves room for a seventh workgroup per CU
-        // (PHYS_DEBUG_BRICK_STAGE=128|256 forces one: measurements)
-        const bool small_stage = dbg.brick_stage ? dbg.brick_stage == 128 : (w->hint.valid && (uint64_t)w->hint.n_pairs < 3ull * w->n);
-        const size_t fixed = (kPairThreads / 64) * (small_stage ? 128 : 256) * 8 + kRegCells * 8 + 64;
-        // persistent workgroups, as many as are resident at once (the LDS decides), never more than there are bricks
-        // at most seven per CU (66 registers: seven waves per SIMD). Measured, us (C4 / 1M cubes in mid-fall / C5): 3 per CU
-        // 173 / 145 / 74, 4: 137 / 114 / 72, 5: 117 / 100 / 69, 6: 105 / 89 / 70, 7 (small stage): 103 / 83 / -; asked for 8
-        // (not all resident: the late ones start on a drained chip) 131 / 109 / 69
-        constexpr size_t kBrickPerCuMax = 7;
-        uint32_t per_cu = (uint32_t)std::min<size_t>(kBrickPerCuMax, (160 * 1024) / (((dyn + fixed) + 1023) / 1024 * 1024));
-        uint32_t wgs = 256u * std::max(per_cu, 1u);
-        while (wgs > n_bricks) wgs >>= 1;
-        static bool attr_set[64] = {};  // per device (function attributes are): more than 64 KiB of dynamic LDS needs it
-        if (!attr_set[w->device & 63]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_find_pairs_brick<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&k_find_pairs_brick<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess)
-                attr_set[w->device & 63] = true;
-            else (void)hipGetLastError();
-        }
         PHYS_PROF(w, PHYS_STAGE_PAIRS);
-        if (small_stage)
-            hipLaunchKernelGGL(k_find_pairs_brick<128>, dim3(wgs), dim3(kPairThreads), dyn, s, w->bucket_start.p, n_bricks, axis_mask,
-                               w->sorted_ids.p, w->sorted_box.p, w->pairs.p, w->max_pairs, w->counters.p, cap);
+        if (plan.kernel == PairKernel::Brick128)
+            hipLaunchKernelGGL(k_find_pairs_brick<128>, wgs, tb, plan.lds, s, w->bucket_start.p, n_bricks, axis_mask,
+                               w->sorted_ids.p, w->sorted_box.p, w->pairs.p, w->max_pairs, w->counters.p, plan.cap);
         else
-            hipLaunchKernelGGL(k_find_pairs_brick<256>, dim3(wgs), dim3(kPairThreads), dyn, s, w->bucket_start.p, n_bricks, axis_mask,
-                               w->sorted_ids.p, w->sorted_box.p, w->pairs.p, w->max_pairs, w->counters.p, cap);
+            hipLaunchKernelGGL(k_find_pairs_brick<256>, wgs, tb, plan.lds, s, w->bucket_start.p, n_bricks, axis_mask,
+                               w->sorted_ids.p, w->sorted_box.p, w->pairs.p, w->max_pairs, w->counters.p, plan.cap);
         return;
     }
-    if (dbg.pair_lanes ? dbg.pair_lanes == 4 : n <= 65536u) {
-        PHYS_PROF(w, PHYS_STAGE_PAIRS);
-        hipLaunchKernelGGL((k_find_pairs<4>), dim3((unsigned)(((uint64_t)n * 4 + kPairThreads - 1) / kPairThreads)), dim3(kPairThreads), 0, s,
+    PHYS_PROF(w, PHYS_STAGE_PAIRS);
+    if (plan.kernel == PairKernel::Lanes4)
+        hipLaunchKernelGGL((k_find_pairs<4>), wgs, tb, 0, s,
                            w->bucket_start.p, T, axis_mask, w->sorted_ids.p, w->sorted_box.p, w->pairs.p, w->max_pairs, w->counters.p);
-    } else {
-        PHYS_PROF(w, PHYS_STAGE_PAIRS);
-        hipLaunchKernelGGL((k_find_pairs<1>), dim3((n + kPairThreads - 1) / kPairThreads), dim3(kPairThreads), 0, s,
+    else
+        hipLaunchKernelGGL((k_find_pairs<1>), wgs, tb, 0, s,
                            w->bucket_start.p, T, axis_mask, w->sorted_ids.p, w->sorted_box.p, w->pairs.p, w->max_pairs, w->counters.p);
-    }
 }
 
 // phys_broadphase read-out: pairs sorted by (i, j). The sort is a host-side convenience of this

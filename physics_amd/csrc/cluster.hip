@@ -73,9 +73,7 @@ int32_t cluster_assign(phys_world* w, const float* pos /* host, 3 * n_owned */) 
     w->cluster_dynamic = false;
     w->cluster_homes_valid = false;
     if (dbg.no_cluster || n_owned < kClusterMinBodies || !w->flow_vel.p) return PHYS_OK;
-    int cus = 0;
-    PHYS_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, w->device));
-    w->cluster_cus = cus;
+    const int cus = w->cus;
     // one workgroup per cluster, several per CU (their phases interleave: one waits for its rows while the others
     // solve); an eighth of the chip to spare: EVERY workgroup must be resident (the kernel's occupancy bound admits
     // kClusterPerCu* of them per CU; a workgroup that found no room would be waited for until the time-out)
@@ -157,7 +155,7 @@ int32_t cluster_assign(phys_world* w, const float* pos /* host, 3 * n_owned */) 
 }
 
 // ---- dynamic clusters: plan (host, from the lagged count of active bodies) and assignment (device, this update) ----
-bool cluster_plan_dynamic(phys_world* w) {
+bool cluster_plan_dynamic(phys_world* w, const StepHint& h, const DebugSwitches& dbg) {
     if (!w->cluster_dynamic) return false;
     if (!w->sorted_grid_valid) return false;  // the deal reads the bucket order of this update's broad phase (sorted grid only)
     // the homes stay for kClusterDynamicPeriod cluster steps (a pile changes slowly; the deal is three passes over all
@@ -168,13 +166,12 @@ bool cluster_plan_dynamic(phys_world* w) {
     // (between half as many and twice as many; a world seeded with a mid-fall state - 1M cubes, 360k manifolds, 250k
     // active bodies - never got a first deal with the upper bound). Too low a guess leaves some bodies without a home for
     // one period (slower, never wrong), and the deal itself then counts them.
-    uint64_t active = w->hint.n_active;
-    if (active == 0) active = std::min<uint64_t>(w->n_owned, (uint64_t)w->hint.n_manifolds);
+    uint64_t active = h.n_active;
+    if (active == 0) active = std::min<uint64_t>(w->n_owned, (uint64_t)h.n_manifolds);
     if (active == 0) return false;
-    const DebugSwitches& dbg = debug_switches();
     const int per_cu_max = w->all_diag_inertia ? kClusterPerCuDiag : kClusterPerCuFull;
     int per_cu = dbg.clusters_per_cu ? std::min(per_cu_max, std::max(1, *dbg.clusters_per_cu)) : per_cu_max;
-    const int cus = w->cluster_cus;
+    const int cus = w->cus;
     // homes for a quarter more bodies than the last known count; what does not get one is served as "another cluster's
     // body" (slower, never wrong), so this is a matter of speed only
     uint64_t want = active + active / 4;
@@ -237,7 +234,6 @@ __global__ __launch_bounds__(256) void k_cluster_homes(uint32_t n, uint32_t n_ow
 }
 
 // ---- per step: rows sorted by (owner cluster, colour); bodies touched by a row of another cluster ----------
-constexpr int kKeysItems = 4;        // manifolds per lane and trip
 constexpr int kKeysSlots = 2048;     // LDS table of the (cluster, colour) keys of one trip (<= 1024 of them)
 __global__ __launch_bounds__(256) void k_cluster_keys(uint64_t max_manifolds, const uint32_t* __restrict__ man_a,
                                                       const uint32_t* __restrict__ man_b, const uint32_t* __restrict__ man_color,
@@ -328,7 +324,7 @@ __global__ __launch_bounds__(256) void k_cluster_place(uint64_t max_manifolds, c
 
 
 // called by launch_coloring in place of the colour-major placement
-void launch_cluster_sort(phys_world* w, unsigned blocks, StepCounters* snap_out) {
+void launch_cluster_sort(phys_world* w, const ColorPlan& plan, StepCounters* snap_out) {
     hipStream_t s = w->stream;
     const uint32_t bins = w->cluster_count * PHYS_MAX_COLORS;  // a multiple of 64
     PHYS_PROF(w, PHYS_STAGE_ROWS);
@@ -358,13 +354,10 @@ void launch_cluster_sort(phys_world* w, unsigned blocks, StepCounters* snap_out)
     uint32_t* seg_count = w->body_shared.p + seg_count_offset(w->n);
     (void)hipMemsetAsync(w->body_shared.p, 0, self_zeroing ? (size_t)w->n * 8 : (seg_count_offset(w->n) + (size_t)std::max<uint32_t>(bins, w->seg_count_bins)) * 4, s);
     w->seg_count_bins = bins;
-    // (a trip of k_cluster_keys is 1024 manifolds: as many workgroups as the last known count needs, any number is correct)
-    const uint64_t key_trips = w->hint.valid ? ((uint64_t)w->hint.n_manifolds * 5 / 4) / (256u * kKeysItems) + 1 : blocks;
-    const unsigned key_blocks = (unsigned)std::min<uint64_t>(blocks, std::max<uint64_t>(1, key_trips));
-    hipLaunchKernelGGL(k_cluster_keys, dim3(key_blocks), dim3(256), 0, s, w->max_manifolds, w->man_a.p, w->man_b.p, w->man_color.p,
+    hipLaunchKernelGGL(k_cluster_keys, dim3(plan.cluster_key_blocks), dim3(256), 0, s, w->max_manifolds, w->man_a.p, w->man_b.p, w->man_color.p,
                        w->cluster_slot.p, w->cluster_slots, w->cluster_count, seg_count, w->man_rank.p, w->body_shared.p, w->counters.p);
     launch_exclusive_scan(w, seg_count, bins, w->seg_start.p, scan_is_one_launch(bins), w->scan_block_sums.p);
-    hipLaunchKernelGGL(k_cluster_place, dim3(blocks), dim3(256), 0, s, w->max_manifolds, w->man_a.p, w->man_b.p, w->man_color.p,
+    hipLaunchKernelGGL(k_cluster_place, dim3(plan.cluster_sort_blocks), dim3(256), 0, s, w->max_manifolds, w->man_a.p, w->man_b.p, w->man_color.p,
                        w->cluster_slot.p, w->cluster_slots, w->cluster_count, w->seg_start.p, w->man_rank.p, w->row_src.p, w->counters.p, snap_out);
 }
 
@@ -720,8 +713,8 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
     }
 }
 
-void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float friction, const float* inertia, uint32_t stride,
-                          bool diag, long long timeout_ticks, bool materials) {
+void launch_solve_cluster(phys_world* w, const SolverPlan& plan, void* row_all, uint64_t cap, float friction, const float* inertia,
+                          uint32_t stride, bool diag) {
     const uint32_t warm_sweep = w->warm ? 1u : 0u;
     const uint32_t sweeps = w->cfg.solver_iterations + warm_sweep;
     ClusterRowArrays rows;
@@ -736,20 +729,14 @@ void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float fric
     static hipEvent_t chain_event[64] = {};
     std::lock_guard<std::mutex> hold(chain_lock);
     {
-        // more than the default 64 KiB of dynamic LDS needs the attribute: once per kernel AND DEVICE (function attributes
-        // are per device: a world on a second device of this process - phys_comm_create_local - needs its own), under the
-        // lock (two host threads), the current device being the world's (ENTER of the ABI call) - ADVICE r2
+        // (under the lock: two host threads - ADVICE r2)
         static bool attr_set[64] = {};
-        if (!attr_set[w->device & 63]) {
-            hipError_t e = hipSuccess;
-            auto allow = [&](const void* f) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); };
-            allow(reinterpret_cast<const void*>(&k_solve_cluster<true, true, false>)); allow(reinterpret_cast<const void*>(&k_solve_cluster<true, false, false>));
-            allow(reinterpret_cast<const void*>(&k_solve_cluster<false, true, false>)); allow(reinterpret_cast<const void*>(&k_solve_cluster<false, false, false>));
-            allow(reinterpret_cast<const void*>(&k_solve_cluster<true, true, true>)); allow(reinterpret_cast<const void*>(&k_solve_cluster<true, false, true>));
-            allow(reinterpret_cast<const void*>(&k_solve_cluster<false, true, true>)); allow(reinterpret_cast<const void*>(&k_solve_cluster<false, false, true>));
-            if (e != hipSuccess) { (void)hipGetLastError(); set_error(std::string("hipFuncSetAttribute(k_solve_cluster): ") + hipGetErrorString(e)); }
-            else attr_set[w->device & 63] = true;
-        }
+        const hipError_t e = allow_dynamic_lds(attr_set, w->device, {
+            reinterpret_cast<const void*>(&k_solve_cluster<true, true, false>), reinterpret_cast<const void*>(&k_solve_cluster<true, false, false>),
+            reinterpret_cast<const void*>(&k_solve_cluster<false, true, false>), reinterpret_cast<const void*>(&k_solve_cluster<false, false, false>),
+            reinterpret_cast<const void*>(&k_solve_cluster<true, true, true>), reinterpret_cast<const void*>(&k_solve_cluster<true, false, true>),
+            reinterpret_cast<const void*>(&k_solve_cluster<false, true, true>), reinterpret_cast<const void*>(&k_solve_cluster<false, false, true>)}, 160 * 1024);
+        if (e != hipSuccess) set_error(std::string("hipFuncSetAttribute(k_solve_cluster): ") + hipGetErrorString(e));
     }
     hipEvent_t& ev = chain_event[w->device & 63];
     if (ev) (void)hipStreamWaitEvent(w->stream, ev, 0);
@@ -760,8 +747,7 @@ void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float fric
     // run one after the other, every launch starts on an idle device, the count - 0.04 ms per update on C5 and on the
     // 1M cubes (tools/guard_cost.py) - is skipped). The guarded start is the default since round 3: a drop-in behind a render loop shares its GPU
     // with the renderer, and the unguarded launch's failure mode there is a 3 s spin.
-    const bool guarded = !gpu_is_exclusive(w);
-    dispatch_bool(diag, [&](auto diag_t) { dispatch_bool(guarded, [&](auto guarded_t) { dispatch_bool(materials, [&](auto mat_t) {
+    dispatch_bool(diag, [&](auto diag_t) { dispatch_bool(plan.guarded, [&](auto guarded_t) { dispatch_bool(plan.materials, [&](auto mat_t) {
         constexpr bool D = decltype(diag_t)::value, G = decltype(guarded_t)::value, MT = decltype(mat_t)::value;
         const uint32_t kAttempts = G ? 2u : 1u;
         for (uint32_t attempt = 0; attempt < kAttempts; ++attempt) {
@@ -770,7 +756,7 @@ void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float fric
             const long long arrive_ticks = !G ? -1ll : (attempt == 0 ? 50000ll : 2000000ll);
             hipLaunchKernelGGL((k_solve_cluster<D, G, MT>), g, b, lds, w->stream, w->counters.p, sweeps, w->flow_epoch, rows, friction,
                                inertia, stride, w->vel.p, w->pos.p, w->flow_vel.p, (uint32_t)w->n, w->cluster_body.p,
-                               w->body_shared.p, w->seg_start.p, w->cluster_slots, timeout_ticks, attempt, last, arrive_ticks,
+                               w->body_shared.p, w->seg_start.p, w->cluster_slots, plan.timeout_ticks, attempt, last, arrive_ticks,
                                warm_sweep, w->row_src.p, w->warm ? w->man_imp.p : (float*)nullptr);
         }
     }); }); });

@@ -16,7 +16,6 @@ __device__ __forceinline__ uint32_t stored_manifolds(const StepCounters* ctr, ui
     return (uint64_t)m < max_manifolds ? m : (uint32_t)max_manifolds;
 }
 
-constexpr int kColorThreads = 1024;
 constexpr int kColorStage = 8192;  // losers of one workgroup and round staged in LDS (k_color_round)
 
 // Ordering between the waves of ONE workgroup that talk through global memory (single-workgroup colouring
@@ -224,8 +223,6 @@ __global__ __launch_bounds__(kColorThreads) void k_color_finish(uint32_t round, 
 // ---- colour-major renumbering: counting sort of the manifolds by colour ---------------------------
 // hist (per-workgroup colour histogram) -> offsets (one workgroup scans colour-major) -> place.
 // No global atomics; the order inside a colour is (workgroup, arrival), which nothing depends on.
-constexpr int kSortBlocksMax = 512;  // most workgroups of the hist / place kernels (the launch picks nb <= this)
-constexpr int kSortChunk = 4096;   // manifolds per workgroup trip
 
 __global__ __launch_bounds__(1024) void k_color_hist(uint64_t max_manifolds, const uint32_t* __restrict__ man_color,
                                                      uint32_t* __restrict__ block_hist /*[colour][nb]*/, uint32_t nb,
@@ -346,7 +343,6 @@ __global__ __launch_bounds__(1024) void k_color_place(uint64_t max_manifolds, co
 // only the new ones), the colour-major counting sort, and the snapshot of the counters into pinned host memory
 // (the launch-size hints of later steps) - instead of ~3 round launches + finish + sort + a copy.
 constexpr int kSmallList = 6144;  // ids per list; two lists: the uncoloured of this round / of the next
-constexpr int kSmallTrips = 40;  // manifolds per thread kept in registers: 40 x 1024 = the `small` limit of launch_coloring
 __global__ __launch_bounds__(kColorThreads) void k_color_small(uint64_t max_manifolds, const uint32_t* __restrict__ man_a,
                                                               const uint32_t* __restrict__ man_b, uint32_t* man_color,
                                                               const uint64_t* __restrict__ man_prio,
@@ -509,142 +505,82 @@ static void launch_color_round(phys_world* w, uint32_t round, unsigned blocks) {
                        w->unc_list.p + ((round + 1u) & 1u) * w->max_manifolds, w->counters.p);
 }
 
-// Colouring + colour-major renumbering, entirely device-driven: `rounds` round launches (the previous
-// steps' round count + 2: surplus launches exit at once), one finish launch that completes whatever is
-// left, then histogram / offsets / place. No host check. A snapshot of the counters is copied to pinned
-// memory asynchronously; later steps use it only as a HINT for launch sizes.
-void launch_coloring(phys_world* w) {
+// a pinned snapshot slot as the device sees it, for a kernel that writes the counters out itself; null: the copy path takes over
+static StepCounters* snapshot_slot_for_kernel(phys_world* w) {
+    StepCounters* slot = snapshot_acquire(w);
+    StepCounters* d_slot = nullptr;
+    if (slot && hipHostGetDevicePointer((void**)&d_slot, slot, 0) != hipSuccess) {
+        d_slot = nullptr;
+        (void)hipGetLastError();  // an answer handled here (the copy path takes over), not an error to leave behind
+    }
+    return d_slot;
+}
+
+// Colouring + colour-major renumbering, entirely device-driven: the plan's round launches (surplus launches exit at
+// once), one finish launch that completes whatever is left, then histogram / offsets / place. No host check, except on the
+// Probe path. A snapshot of the counters goes to pinned memory asynchronously; later steps use it only as a HINT for launch sizes.
+void launch_coloring(phys_world* w, const ColorPlan& plan, bool cluster) {
     const uint64_t n = w->n;
     if (n == 0) return;
     hipStream_t s = w->stream;
-    uint64_t blocks64 = (w->max_manifolds + kColorThreads - 1) / kColorThreads;
-    if (blocks64 > 512) blocks64 = 512;
-    if (w->hint.valid) {
-        const uint64_t want = ((uint64_t)w->hint.n_manifolds * 5 / 4 + kColorThreads) / kColorThreads;
-        if (want < blocks64) blocks64 = want ? want : 1;
-    }
-    const unsigned blocks = (unsigned)blocks64;
-    uint32_t rounds = 0;
-    // a full colouring (the first update after phys_set_bodies: nothing to keep) needs far more rounds than an incremental one
-    const bool full = !w->ctab_valid;
-    // every PHYS_COLOR_CACHE_PERIOD-th update the colour TABLE is rebuilt: emptied here - the narrow phase of this update
-    // has taken what it keeps from it already - and refilled by k_rows_build with every manifold of this update instead of
-    // the new ones only. That purges the dead entries (chains never shrink otherwise) and changes no colour.
-    const bool rebuild = full || (w->color_epoch % PHYS_COLOR_CACHE_PERIOD) == 0;
-    w->snap_tag_full = full;
-    const bool known = w->hint.valid && (!full || w->hint.full_rounds > 0);
-    const bool small = w->hint.valid && w->hint.n_manifolds <= (uint32_t)(kSmallTrips * kColorThreads);
     bool snapshot_done = false;
-    // cluster solver this update? (decided here because it decides the ORDER of the rows: by (cluster, colour)
-    // instead of by colour). PHYS_DEBUG_CLUSTER_MIN=<manifolds> moves the threshold (measurements; same bits either way).
-    const DebugSwitches& dbg = debug_switches();
-    const bool cluster_forced = (w->cfg.flags & PHYS_FLAG_SOLVER_CLUSTER) != 0u;
-    const uint64_t cluster_min = cluster_forced ? 0 : dbg.cluster_min.value_or(kClusterMinManifolds);
-    // worth it where contacts are dense (C5: 11 rows per body): velocities stay in LDS for many rows each. Sparse piles
-    // (the 1M-cube scene: 0.4-0.5 rows per body, contacts in the bottom layers only) leave most clusters idle and a few
-    // overloaded - they keep the dataflow / per-colour kernels, which spread rows evenly over the chip
-    // (dynamic clusters hold only the bodies that have manifolds: nothing idles, the row count alone decides)
-    const bool dense = cluster_forced || dbg.cluster_min.has_value() || w->cluster_dynamic || 2ull * w->hint.n_manifolds >= 3ull * w->n_owned;
-    w->cluster_step = (w->cluster_count > 0 || w->cluster_dynamic) && w->hint.valid && !small && dense &&
-                      w->hint.n_manifolds >= cluster_min && !(w->cfg.flags & PHYS_FLAG_SOLVER_PER_COLOR) &&
-                      w->cfg.solver_iterations > 0 && w->cfg.solver_iterations < 1000 && w->hint.n_colors > 0;
-    // ... unless the dataflow kernel is the faster one for this many rows and colours (kernels.hpp; only where it may take
-    // the whole chip: PHYS_FLAG_EXCLUSIVE_GPU, one world on the device)
-    w->flow_wide = gpu_is_exclusive(w);  // (PHYS_DEBUG_NO_FLOW_PREFERENCE: never; measurements, same bits)
-    if (w->cluster_step && !cluster_forced && !dbg.cluster_min.has_value() && !dbg.no_flow_preference && w->flow_wide && w->hint.n_manifolds <= kFlowWideMaxManifolds &&
-        flow_quad_beats_cluster(w->hint.n_manifolds, w->hint.n_contacts, w->hint.n_colors))
-        w->cluster_step = false;
-    if (w->cluster_step && w->cluster_dynamic) w->cluster_step = cluster_plan_dynamic(w);  // clusters and slots (every few updates)
-    if (small) {
+    if (plan.path == ColorPath::Small) {
         // one workgroup does the whole stage, snapshot of the counters included
-        StepCounters* slot = snapshot_acquire(w);
-        StepCounters* d_slot = nullptr;
-        if (slot && hipHostGetDevicePointer((void**)&d_slot, slot, 0) != hipSuccess) {
-            d_slot = nullptr;
-            (void)hipGetLastError();  // an answer handled here (the copy path takes over), not an error to leave behind
-        }
+        StepCounters* d_slot = snapshot_slot_for_kernel(w);
         { PHYS_PROF(w, PHYS_STAGE_COLOR);
           hipLaunchKernelGGL(k_color_small, dim3(1), dim3(kColorThreads), 0, s, w->max_manifolds, w->man_a.p, w->man_b.p,
                              w->man_color.p, w->man_prio.p, w->color_state.p, (uint64_t)n, w->row_src.p, w->counters.p, d_slot); }
-        if (d_slot) { snapshot_commit(w); snapshot_done = true; }
+        if (d_slot) { snapshot_commit(w, plan.full); snapshot_done = true; }
     } else {
-    if (known) {
-        const uint32_t base = full ? w->hint.full_rounds : w->hint.color_rounds;
-        // as many launches as the last update of this kind needed; k_color_finish runs what is still missing over the
-        // same lists (measured: handing it the second half of the rounds - one workgroup, ~10 us per round with a few
-        // thousand manifolds left - is slower than the launches it saves, and far slower on a full re-colouring)
-        rounds = base;
-        for (uint32_t r = 0; r < rounds; ++r) launch_color_round(w, r, blocks);
-    } else {
-        // first step after phys_set_bodies: nothing is known about the scene yet, so this one step asks the
-        // device (a single-workgroup finish / tail over millions of manifolds would take seconds)
-        for (int guard = 0; guard < 4096; ++guard) {
-            for (uint32_t k = 0; k < 8; ++k) launch_color_round(w, rounds++, blocks);
-            (void)hipMemcpyAsync(w->h_counters, w->counters.p, sizeof(StepCounters), hipMemcpyDeviceToHost, s);
-            (void)hipStreamSynchronize(s);
-            if (w->prof.on) w->prof.collect(s);
-            if (w->h_counters->n_uncolored == 0 || w->h_counters->overflow) break;
+        uint32_t rounds = plan.rounds;
+        for (uint32_t r = 0; r < rounds; ++r) launch_color_round(w, r, plan.round_blocks);
+        if (plan.path == ColorPath::Probe) {
+            // first step after phys_set_bodies: nothing is known about the scene yet, so this one step asks the
+            // device (a single-workgroup finish / tail over millions of manifolds would take seconds)
+            for (int guard = 0; guard < 4096; ++guard) {
+                for (uint32_t k = 0; k < 8; ++k) launch_color_round(w, rounds++, plan.round_blocks);
+                (void)hipMemcpyAsync(w->h_counters, w->counters.p, sizeof(StepCounters), hipMemcpyDeviceToHost, s);
+                (void)hipStreamSynchronize(s);
+                if (w->prof.on) w->prof.collect(s);
+                if (w->h_counters->n_uncolored == 0 || w->h_counters->overflow) break;
+            }
         }
-    }
-    { PHYS_PROF(w, PHYS_STAGE_COLOR); hipLaunchKernelGGL(k_color_finish, dim3(1), dim3(kColorThreads), 0, s, rounds, w->max_manifolds, w->man_a.p, w->man_b.p, w->man_color.p, w->man_prio.p, w->color_state.p, (uint64_t)n, w->unc_list.p, w->counters.p); }
-    // workgroups of the colour sort: sized from the hint (any value is correct: the kernels stride)
-    uint32_t nb = kSortBlocksMax;
-    if (w->hint.valid) {
-        const uint64_t want = ((uint64_t)w->hint.n_manifolds * 5 / 4) / kSortChunk + 1;
-        nb = 1;
-        while (nb < want && nb < (uint32_t)kSortBlocksMax) nb <<= 1;
-    }
-    // the snapshot of the counters (launch-size hints of later updates) is written by the last kernel of the sort itself,
-    // into a host-mapped slot: the copy engine's turn between two kernels of the stream cost 4.4 us per update
-    StepCounters* d_snap = nullptr;
-    if (known) {
-        StepCounters* slot = snapshot_acquire(w);
-        if (slot && hipHostGetDevicePointer((void**)&d_snap, slot, 0) != hipSuccess) {
-            d_snap = nullptr;
-            (void)hipGetLastError();  // an answer handled here (the copy path takes over), not an error to leave behind
+        { PHYS_PROF(w, PHYS_STAGE_COLOR);
+          hipLaunchKernelGGL(k_color_finish, dim3(1), dim3(kColorThreads), 0, s, rounds, w->max_manifolds, w->man_a.p, w->man_b.p,
+                             w->man_color.p, w->man_prio.p, w->color_state.p, (uint64_t)n, w->unc_list.p, w->counters.p); }
+        // the snapshot of the counters (launch-size hints of later updates) is written by the last kernel of the sort itself,
+        // into a host-mapped slot: the copy engine's turn between two kernels of the stream cost 4.4 us per update
+        StepCounters* d_snap = plan.path == ColorPath::Known ? snapshot_slot_for_kernel(w) : nullptr;
+        if (cluster) {
+            launch_cluster_sort(w, plan, d_snap);  // rows by (owner cluster, colour); counts the colours too
+        } else {
+            const uint32_t nb = plan.sort_blocks;
+            { PHYS_PROF(w, PHYS_STAGE_ROWS);
+              hipLaunchKernelGGL(k_color_hist, dim3(nb), dim3(1024), 0, s, w->max_manifolds, w->man_color.p, w->color_block_hist.p, nb, w->counters.p); }
+            { PHYS_PROF(w, PHYS_STAGE_ROWS);
+              hipLaunchKernelGGL(k_color_offsets, dim3(1), dim3(1024), 0, s, w->color_block_hist.p, nb, w->counters.p); }
+            // (n_colors and the per-colour counts are final here: k_color_place below may copy the counters out)
+            { PHYS_PROF(w, PHYS_STAGE_ROWS);
+              hipLaunchKernelGGL(k_color_place, dim3(nb), dim3(1024), 0, s, w->max_manifolds, w->man_color.p, w->color_block_hist.p, nb,
+                                 w->row_src.p, w->counters.p, d_snap); }
         }
+        if (d_snap) { snapshot_commit(w, plan.full); snapshot_done = true; }
     }
-    if (w->cluster_step) {
-        launch_cluster_sort(w, blocks * (kColorThreads / 256), d_snap);  // rows by (owner cluster, colour); counts the colours too
-    } else {
-    { PHYS_PROF(w, PHYS_STAGE_ROWS); hipLaunchKernelGGL(k_color_hist, dim3(nb), dim3(1024), 0, s, w->max_manifolds, w->man_color.p, w->color_block_hist.p, nb, w->counters.p); }
-    { PHYS_PROF(w, PHYS_STAGE_ROWS); hipLaunchKernelGGL(k_color_offsets, dim3(1), dim3(1024), 0, s, w->color_block_hist.p, nb, w->counters.p); }
-    // (n_colors and the per-colour counts are final here: k_color_place below may copy the counters out)
-    { PHYS_PROF(w, PHYS_STAGE_ROWS); hipLaunchKernelGGL(k_color_place, dim3(nb), dim3(1024), 0, s, w->max_manifolds, w->man_color.p, w->color_block_hist.p, nb, w->row_src.p, w->counters.p, d_snap); }
+    // the new manifolds of this update go into the colour table in k_rows_build (launch_solver, which takes the plan's stamp
+    // and `rebuild`): one launch less
+    if (plan.rebuild) {  // start from an empty table: every manifold of this update is inserted
+        PHYS_PROF(w, PHYS_STAGE_ROWS);
+        (void)hipMemsetAsync(w->ctab.p, 0xFF, ((size_t)w->ctab_mask + 1) * 16, s);
     }
-    if (d_snap) { snapshot_commit(w); snapshot_done = true; }
-    }
-    {
-        // the new manifolds of this update go into the colour table in k_rows_build (launch_solver): one launch less
-        if (rebuild) {  // start from an empty table: every manifold of this update is inserted
-            PHYS_PROF(w, PHYS_STAGE_ROWS);
-            (void)hipMemsetAsync(w->ctab.p, 0xFF, ((size_t)w->ctab_mask + 1) * 16, s);
-        }
-        w->ctab_job_pending = true;
-        w->ctab_job_all = rebuild;
-        w->ctab_job_stamp = (uint32_t)w->color_epoch + 1u;
-        w->ctab_valid = true;
-        w->color_epoch++;
-    }
-    if (!known && !small) {
-        // ... and adopts the exact counters as the first hint (the solver launches right after use them)
+    w->ctab_valid = true;
+    w->color_epoch++;
+    if (plan.path == ColorPath::Probe) {
+        // ... and adopts the exact counters as the first hint (the solver launches right after are planned from them)
         (void)hipMemcpyAsync(w->h_counters, w->counters.p, sizeof(StepCounters), hipMemcpyDeviceToHost, s);
         (void)hipStreamSynchronize(s);
-        const StepCounters& c = *w->h_counters;
-        if (!c.overflow) {
-            w->hint.valid = true;
-            w->hint.n_manifolds = c.n_manifolds;
-            w->hint.n_pairs = c.n_pairs;
-            w->hint.n_contacts = c.n_contacts;
-            if (c.max_region) w->hint.max_region = c.max_region;
-            w->hint.n_used_buckets = c.n_used_buckets;
-            w->hint.n_colors = c.n_colors;
-            if (c.n_active) w->hint.n_active = c.n_active;
-            if (full) w->hint.full_rounds = c.color_rounds; else w->hint.color_rounds = c.color_rounds;
-            for (int q = 0; q < kMaxColors; ++q) w->hint.color_count[q] = c.color_count[q];
-        }
+        if (!w->h_counters->overflow) hint_adopt(w->hint, *w->h_counters, plan.full, /*exact=*/true);
     } else if (!snapshot_done) {
-        snapshot_counters_async(w);
+        snapshot_counters_async(w, plan.full);
     }
 }
 

@@ -16,7 +16,6 @@
 
 namespace phys {
 
-constexpr int kEventThreads = 256;
 constexpr int kEventWaves = kEventThreads / 64;
 
 // device words of the event state: {cursor (64 bits), manifold count of the even updates, ... of the odd updates}
@@ -126,7 +125,7 @@ int32_t events_reset(phys_world* w) {
 }
 
 // `step`: phys_stats.steps after this update (low 32 bits)
-void launch_events(phys_world* w, uint32_t step) {
+void launch_events(phys_world* w, uint32_t step, uint32_t blocks) {
     if (w->ev_capacity == 0 || !w->ev_matched.p || w->n == 0) return;
     // The stamp that says "matched in THIS update": a 32-bit count of the updates with events of this world, never 0 (the
     // value of a fresh ev_matched). At its wrap - 2^32 updates, months of stepping - the words are zeroed and the count
@@ -138,16 +137,12 @@ void launch_events(phys_world* w, uint32_t step) {
     }
     const uint32_t parity = w->ev_parity;
     w->ev_parity ^= 1u;
-    // any grid is correct (the kernels stride); sized from an earlier update's count where one is known
-    const uint64_t m_guess = w->hint.valid ? (uint64_t)w->hint.n_manifolds * 5 / 4 + kEventThreads : w->max_manifolds;
-    uint64_t blocks = (std::min<uint64_t>(m_guess, w->max_manifolds) + kEventThreads - 1) / kEventThreads;
-    blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, 2048));
     EventState* st = reinterpret_cast<EventState*>(w->ev_state.p);
     { PHYS_PROF(w, PHYS_STAGE_MISC);
-      hipLaunchKernelGGL(k_events_begin, dim3((unsigned)blocks), dim3(kEventThreads), 0, w->stream, w->counters.p, w->max_manifolds,
+      hipLaunchKernelGGL(k_events_begin, dim3(blocks), dim3(kEventThreads), 0, w->stream, w->counters.p, w->max_manifolds,
                          w->man_geo.p, w->man_imp.p, w->ev_matched.p, w->ev_stamp, step, parity, st, w->ev_buf.p, w->ev_capacity); }
     { PHYS_PROF(w, PHYS_STAGE_MISC);
-      hipLaunchKernelGGL(k_events_end, dim3((unsigned)blocks), dim3(kEventThreads), 0, w->stream, w->max_manifolds, w->man_geo_prev.p,
+      hipLaunchKernelGGL(k_events_end, dim3(blocks), dim3(kEventThreads), 0, w->stream, w->max_manifolds, w->man_geo_prev.p,
                          w->ev_matched.p, w->ev_stamp, step, parity ^ 1u, st, w->ev_buf.p, w->ev_capacity); }
 }
 

@@ -2,6 +2,7 @@
 // of libphysics_hip.so. Every launch_* enqueues on w->stream and returns without synchronising.
 #pragma once
 #include <algorithm>
+#include <initializer_list>
 #include <type_traits>
 #include <hip/hip_runtime.h>
 
@@ -13,6 +14,7 @@
 #include "wave.hpp"
 
 static_assert(PHYS_MAX_COLORS == phys::kMaxColors, "colour limit mismatch");
+static_assert(PHYS_COLOR_CACHE_PERIOD == phys::kColorCachePeriod, "colour table period mismatch");
 
 #define PHYS_PROF_CAT2(a, b) a##b
 #define PHYS_PROF_CAT(a, b) PHYS_PROF_CAT2(a, b)
@@ -24,6 +26,19 @@ namespace phys {
 template <class F>
 inline void dispatch_bool(bool b, F&& f) {
     if (b) f(std::true_type{}); else f(std::false_type{});
+}
+
+// More than the default 64 KiB of dynamic LDS needs the function attribute: once per kernel AND DEVICE (function attributes
+// are per device: a world on a second device of this process needs its own), the current device being the world's (ENTER of
+// the ABI call). `done`: the launch site's own per-device flags. A refusal is returned, not left behind as the thread's error.
+inline hipError_t allow_dynamic_lds(bool (&done)[64], int device, std::initializer_list<const void*> kernels, int bytes) {
+    if (done[device & 63]) return hipSuccess;
+    for (const void* f : kernels) {
+        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); return e; }
+    }
+    done[device & 63] = true;
+    return hipSuccess;
 }
 
 // 12-byte packed attribute access as ONE dwordx3 memory instruction per lane (a wave then covers one
@@ -236,20 +251,27 @@ void launch_instance_matrices(phys_world* w, float* d_out);
 int32_t collision_alloc(phys_world* w);
 void grid_plan(phys_world* w, const float* host_pos, const float* host_half_extent);  // table size and its split over the axes
 void zero_step_state(phys_world* w, bool including_extent);  // ONE memset: counters + bucket counts + colouring state
-void launch_broadphase(phys_world* w);
+void launch_broadphase(phys_world* w, const PairPlan& plan);
 void build_sorted_grid(phys_world* w);  // bucket_start / sorted_ids / sorted_box from the current AABBs (bucket counts zeroed)
 int32_t sorted_pairs_to_host(phys_world* w, uint32_t* pairs_out, uint64_t cap, uint64_t* n_pairs);
 
 // narrowphase.hip / coloring.hip / solver.hip
-void launch_narrowphase(phys_world* w);
-void launch_coloring(phys_world* w);
-void snapshot_counters_async(phys_world* w);  // abi.hip
+void launch_narrowphase(phys_world* w, const NarrowPlan& plan);
+// `cluster`: this update's rows go in (cluster, colour) order. On the Probe path the stage synchronises and adopts the exact
+// counters as the first hint (abi.hip hint_adopt), so what follows it is planned from those.
+void launch_coloring(phys_world* w, const ColorPlan& plan, bool cluster);
+// `full`: the update is a full re-colouring (its round count is remembered as that)
+void snapshot_counters_async(phys_world* w, bool full);  // abi.hip
 StepCounters* snapshot_acquire(phys_world* w);  // abi.hip: pinned slot a kernel may fill itself ...
-void snapshot_commit(phys_world* w);             // ... then mark it in flight
+void snapshot_commit(phys_world* w, bool full);  // ... then mark it in flight
 void poll_snapshots(phys_world* w);           // abi.hip
-void launch_solver(phys_world* w, float dt);
+// The one adoption of counters as the hint (abi.hip). `full`: they are a full re-colouring's. `exact`: read by the update that
+// waited for them (the Probe path), not a snapshot of an earlier one.
+void hint_adopt(StepHint& hint, const StepCounters& c, bool full, bool exact);
+// `table`: the colouring stage's job for k_rows_build - this update's manifolds go into the colour table (ColorPlan: stamp, rebuild)
+void launch_solver(phys_world* w, float dt, const SolverPlan& plan, const ColorPlan& table);
 // contact events (events.hip): two kernels behind the solve, only in a world with events on
-void launch_events(phys_world* w, uint32_t step);
+void launch_events(phys_world* w, uint32_t step, uint32_t blocks /* plan_event_blocks */);
 int32_t events_alloc(phys_world* w);  // buffers for the current event and manifold capacities (frees them when events are off)
 int32_t events_reset(phys_world* w);  // forget the contact history and the pending events (a new body or static set)
 
@@ -272,19 +294,7 @@ int32_t halo_pairs(phys_world* w, const void* dev_remote, uint64_t n_remote, uin
 
 // cluster.hip
 int32_t cluster_assign(phys_world* w, const float* host_pos);
-// Which single-launch solver for a dense scene whose GPU is the world's alone (PHYS_FLAG_EXCLUSIVE_GPU: the dataflow kernel may
-// then fill the chip with three workgroups per CU, like the cluster kernel). Fitted to measurements of this build, ms per
-// sweep: the four-lane dataflow kernel at 672 workgroups 8.4e-8 M + 1.86e-8 K + 0.0009 C (C3 0.325 ms per solve, a 182k
-// tower 0.380, the 1M cubes in mid-fall 0.405, C5 1.07); the cluster kernel max(0.0041 C, 6.9e-8 M) + 10 % (C3 0.513, the
-// tower 0.636, the 1M cubes 0.235, C5 0.63): rows cost the dataflow kernel throughput, colours cost the cluster kernel
-// its chain. (Both give the same bits: the choice may change from update to update.)
-inline bool flow_quad_beats_cluster(uint32_t manifolds, uint32_t contacts, uint32_t colors) {
-    if (!colors || !contacts) return false;
-    const double flow = 8.4e-8 * manifolds + 1.86e-8 * contacts + 0.0009 * colors;
-    const double cluster = 1.1 * std::max(0.0041 * colors, 6.9e-8 * manifolds);
-    return flow < cluster;
-}
-void launch_cluster_sort(phys_world* w, unsigned blocks, StepCounters* snap_out /* host-mapped slot for the counters, or null */);
+void launch_cluster_sort(phys_world* w, const ColorPlan& plan, StepCounters* snap_out /* host-mapped slot for the counters, or null */);
 #ifdef __HIPCC__
 // the step counters copied out to a host-mapped slot by the first workgroup of a kernel that runs after their last writer
 __device__ __forceinline__ void counters_snapshot(const StepCounters* ctr, StepCounters* snap_out) {
@@ -303,9 +313,10 @@ void launch_exclusive_scan(phys_world* w, uint32_t* in, uint32_t count, uint32_t
                            StepCounters* ctr = nullptr /* ... summed into n_used_buckets */, int prof_stage = -1);
 bool scan_is_one_launch(uint32_t count);  // ... in which case zero_in leaves the counters zeroed behind the scan
 size_t scan_scratch_words(uint32_t count);
-bool cluster_plan_dynamic(phys_world* w);  // cluster.hip: clusters / slots of this update from the hint (dynamic clusters)
-void launch_solve_cluster(phys_world* w, void* row_all, uint64_t cap, float friction, const float* inertia, uint32_t stride,
-                          bool diag, long long timeout_ticks, bool materials /* the rows carry their own friction */);
+// cluster.hip: clusters / slots of this update from the hint (dynamic clusters); false: no cluster step in this update
+bool cluster_plan_dynamic(phys_world* w, const StepHint& h, const DebugSwitches& dbg);
+void launch_solve_cluster(phys_world* w, const SolverPlan& plan, void* row_all, uint64_t cap, float friction, const float* inertia,
+                          uint32_t stride, bool diag);
 
 // static.hip: the static set (arguments checked by the caller), the per-update (body, static) pairs, and what k_narrowphase
 // takes of them (cap 0 / null pointers: no static colliders)

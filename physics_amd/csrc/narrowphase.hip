@@ -303,7 +303,7 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
     if (kStatics && (threadIdx.x & 63) == 0 && acc_static) atomicAdd(&ctr->n_static_manifolds, acc_static);
 }
 
-void launch_narrowphase(phys_world* w) {
+void launch_narrowphase(phys_world* w, const NarrowPlan& plan) {
     const uint32_t n = (uint32_t)w->n;
     if (n == 0) return;
     // ghost bodies of a sharded world (slots behind the owned bodies) are dynamic bodies of this world for one update
@@ -315,76 +315,36 @@ void launch_narrowphase(phys_world* w) {
     const uint32_t* st_pairs = nullptr;
     const float* st_geo = nullptr;
     static_narrow_args(w, &st_cap, &st_pairs, &st_geo);
-    const uint64_t work = (uint64_t)n_ground + w->max_pairs + st_cap;
     // colouring state of the step: used masks + three rotating priority buffers (one memset); the narrow
     // phase publishes round 0's per-body maxima as it emits manifolds
     // persistent colouring: colours of the previous update are kept (contact_solve.h)
     const uint32_t cache_mask = w->ctab_valid ? w->ctab_mask : 0u;
     const uint32_t stamp = (uint32_t)w->color_epoch + 1u;  // never 0xFFFFFFFF (the stamp of an empty slot) in a world's life
-    // the colour-table entry of a pair is asked for ahead of the shape test where at least half of the pairs become manifolds
-    const DebugSwitches& dbg = debug_switches();  // PHYS_DEBUG_NP_EARLY_PROBE=0 / 1 forces it (measurements; same bits)
-    const uint32_t early_probe = dbg.np_early_probe.value_or(!w->hint.valid || 2ull * w->hint.n_manifolds >= (uint64_t)w->hint.n_pairs);
     if (w->warm) {  // last update's records become "previous": what this update's kept manifolds start from
         std::swap(w->man_geo.p, w->man_geo_prev.p);
         std::swap(w->man_imp.p, w->man_imp_prev.p);
     }
-    PHYS_PROF(w, PHYS_STAGE_NARROW);
-#define PHYS_NP_LAUNCH(T, S, CAP, FLT, ...)                                                                             \
-    do {                                                                                                               \
-        uint64_t blocks = (work + T - 1) / T;                                                                          \
-        if (blocks > 256 * 16) blocks = 256 * 16;                                                                      \
-        hipLaunchKernelGGL((k_narrowphase<T, 1, S, CAP, FLT>), dim3((unsigned)blocks), dim3(T), 0, w->stream, n_ground, n_owned, w->pairs.p, \
-                           w->max_pairs, w->geo.p, w->cfg.contact_margin, \
-                           w->cfg.ground_height, w->max_manifolds, w->man_a.p, w->man_b.p,                             \
-                           w->man_color.p, w->man_geo.p, w->man_prio.p, w->color_state.p,                              \
-                           w->color_state.p + n, reinterpret_cast<ulonglong2*>(w->ctab.p), cache_mask, early_probe, stamp, \
-                           w->unc_list.p, w->warm ? w->man_prev.p : nullptr, w->man_imp.p, w->counters.p,              \
-                           st_cap, st_pairs, st_geo, ##__VA_ARGS__);                                                   \
-    } while (0)
-    // 128 threads only while the whole stage is a few workgroups (C2: 10k manifolds); measured at 230k manifolds (C3):
-    // 0.175 ms with 128 threads, 0.133 with 256; at 2.9M (C5): 0.86 vs 0.55 (round 2)
-    const bool few = w->hint.valid ? w->hint.n_manifolds <= 32768u : n <= 200000u;
-    // Workgroup shape (all variants: same manifolds, emission order is arbitrary anyway). A trip ends in one reservation
-    // behind two barriers, and the waves a CU holds are what hides a trip's round trips from each other; the in-place
-    // clipper's LDS slice (33 dwords per lane) admits 16 waves per CU at 118 registers. Measured, ms per update
-    // (C5 / 1M cubes in mid-fall / settled 1M pile / C3):
-    //   256 threads, one item per lane (4 workgroups per CU)            0.251 / 0.081 / 0.812 / 0.091
-    //   256 threads, two items per lane (151 registers: 12 waves)       0.230 / 0.067 / 0.917 / 0.093
-    //   512 threads, one item (2 workgroups per CU, half the atomics)   0.206 / 0.069 / 0.836 / 0.075   <- the default
-    //   1024 threads, one item (a barrier over 16 waves)                0.231 / 0.084 / 0.937 / 0.080
-    // Only the two the library picks are built; PHYS_DEBUG_NP_THREADS=128|512 picks one by hand.
-    const int threads = dbg.np_threads ? dbg.np_threads : (few ? 128 : 512);
-    // (worlds without static colliders run the kernel they always ran: the static work items are compiled out of it)
-    // Capsules: the capsule variant wherever one can meet the narrow phase - an owned body (phys_set_bodies), a static in
-    // use, or any ghost slot: ghosts arrive on the device with the shapes of another rank, which the host never sees
-    const bool capsules = w->body_capsules || (st_pairs && w->static_capsules) || w->max_ghosts > 0;
-    // Filters: the filtered variant once any filter was set since its reset (whatever the values), and
-    // in every world with ghost slots: their filters arrive with the halo records, which the host never sees
-    const bool filters = w->body_filters_set || (st_pairs && w->static_filters_set) || (n_ground && w->ground_filter_set) ||
-                         w->max_ghosts > 0;
     NpFilters flt{};
     flt.body = reinterpret_cast<const uint2*>(w->filt.p);
     flt.st = st_pairs ? reinterpret_cast<const uint2*>(w->st_filt.p) : nullptr;
     flt.ground = make_uint2(w->ground_filt, 0u);
-    // (the filtered instance takes `flt` as one more argument; the unfiltered one is launched exactly as before filters)
-#define PHYS_NP_PICK(S, CAP)                                                                                           \
-    do {                                                                                                               \
-        if constexpr (kF) { if (threads == 128) PHYS_NP_LAUNCH(128, S, CAP, true, flt); else PHYS_NP_LAUNCH(512, S, CAP, true, flt); } \
-        else { if (threads == 128) PHYS_NP_LAUNCH(128, S, CAP, false); else PHYS_NP_LAUNCH(512, S, CAP, false); }           \
-    } while (0)
-    dispatch_bool(filters, [&](auto fl) {
-        constexpr bool kF = decltype(fl)::value;
-        if (capsules) {
-            if (st_pairs) PHYS_NP_PICK(true, true);
-            else PHYS_NP_PICK(false, true);
-        } else if (st_pairs) {
-            PHYS_NP_PICK(true, false);
-        } else {
-            PHYS_NP_PICK(false, false);
-        }
-    });
-#undef PHYS_NP_PICK
-#undef PHYS_NP_LAUNCH
+    PHYS_PROF(w, PHYS_STAGE_NARROW);
+    // the instance of the plan (plan.hpp: worlds without static colliders run the kernel they always ran, the static work
+    // items are compiled out of it; capsules wherever one can meet the narrow phase; filters once any was set)
+    dispatch_bool(plan.threads == 128, [&](auto few_t) { dispatch_bool(plan.statics, [&](auto st_t) {
+    dispatch_bool(plan.capsules, [&](auto cap_t) { dispatch_bool(plan.filters, [&](auto flt_t) {
+        constexpr int T = decltype(few_t)::value ? 128 : 512;
+        constexpr bool S = decltype(st_t)::value, CAP = decltype(cap_t)::value, FLT = decltype(flt_t)::value;
+        // (the filtered instance takes `flt` as one more argument; the unfiltered one is launched exactly as before filters)
+        auto launch = [&](auto... filters) {
+            hipLaunchKernelGGL((k_narrowphase<T, 1, S, CAP, FLT>), dim3(plan.blocks), dim3(T), 0, w->stream, n_ground, n_owned, w->pairs.p,
+                               w->max_pairs, w->geo.p, w->cfg.contact_margin, w->cfg.ground_height, w->max_manifolds, w->man_a.p, w->man_b.p,
+                               w->man_color.p, w->man_geo.p, w->man_prio.p, w->color_state.p, w->color_state.p + n,
+                               reinterpret_cast<ulonglong2*>(w->ctab.p), cache_mask, plan.early_probe, stamp, w->unc_list.p,
+                               w->warm ? w->man_prev.p : nullptr, w->man_imp.p, w->counters.p, st_cap, st_pairs, st_geo, filters...);
+        };
+        if constexpr (FLT) launch(flt); else launch();
+    }); }); }); });
 }
 
 }  // namespace phys

@@ -471,12 +471,6 @@ __device__ __forceinline__ bool flow_backoff(StepCounters* ctr, bool done, uint3
     return dead;
 }
 
-constexpr long long kFlowTimeoutTicks = 300000000ll;  // 3 s of the 100 MHz wall clock (fault injection: 20 ms)
-constexpr uint64_t kFlowMaxManifolds = 400000;        // above: one launch per colour streams better
-// below: four lanes per manifold (k_solve_flow_quad). Measured again with its statically dealt items (tools/cluster_crossover.py
-// --path flow, solve ms quad / one lane): towers 92k manifolds 0.371 / 0.466, 182k 0.645 / 0.670, 256k 0.914 / 0.903; mixed piles
-// 91k 0.308 / 0.405, 155k 0.444 / 0.502 (round 2, with tickets: 45k +13 %, 108k -32 %)
-constexpr uint64_t kFlowQuadMaxManifolds = 200000;
 
 // Work items are SOFTWARE-PIPELINED inside a workgroup: while item k waits for its bodies and is solved, the rows of
 // item k + 1 (its ticket is taken one item ahead) are already on their way, and so are - issued once those rows have
@@ -973,7 +967,6 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
 //   * quad_lane_setup / quad_lane_solve as in k_solve_flow_quad: a third of the VALU chain per lane, four times the
 //     waves to overlap memory with arithmetic, and a gather of ONE 16-byte half record per lane.
 // Rows of one colour share no body, so the plain loads / stores of `vel` need no ordering inside a launch.
-constexpr int kQuadRowsPerGroup = 64;
 template <bool DIAG, bool MAT>
 __global__ __launch_bounds__(256) void k_solve_color_quad(StepCounters* ctr, uint32_t col, RowArrays rows,
                                                           float friction, const float* __restrict__ inv_inertia,
@@ -1043,11 +1036,10 @@ __global__ __launch_bounds__(256) void k_solve_color_quad(StepCounters* ctr, uin
     }
 }
 
-// Launch sizes come from the HINT (counters of an earlier step, read back asynchronously); every kernel
-// takes its real ranges from the device-side counters, so a stale hint costs speed, never correctness.
-void launch_solver(phys_world* w, float dt) {
+// Launch sizes come from the plan (plan.hpp plan_solver: the HINT, counters of an earlier step read back asynchronously);
+// every kernel takes its real ranges from the device-side counters, so a stale hint costs speed, never correctness.
+void launch_solver(phys_world* w, float dt, const SolverPlan& plan, const ColorPlan& coloring) {
     if (w->n == 0) return;
-    const StepHint& h = w->hint;
     solve_params_t sp;
     sp.dt = dt;
     sp.baumgarte = w->cfg.baumgarte;
@@ -1069,28 +1061,7 @@ void launch_solver(phys_world* w, float dt) {
     rows.tb = reinterpret_cast<float4*>(w->row_tb.p);
     rows.acc = reinterpret_cast<float4*>(w->row_acc.p);
     rows.cap = cap;
-    auto grid_for_count = [&](uint64_t count) {
-        uint64_t b = (count * 5 / 4 + 255) / 256 + 1;
-        const uint64_t hi = (cap + 255) / 256;
-        if (b > hi) b = hi;
-        if (b > 4096) b = 4096;
-        return dim3((unsigned)(b ? b : 1));
-    };
-    const uint64_t m_hint = h.valid ? h.n_manifolds : cap;
-    // the dataflow kernel wins while a colour class is too small to fill the chip (launch / latency bound);
-    // beyond that the per-colour launches stream better. Both give the same bits, so the choice may change
-    // from step to step.
-    // (tickets are 16-bit: iterations x 64 colours must stay below 65536)
-    // PHYS_DEBUG_FLOW_MAX=<manifolds>: move the dataflow / per-colour crossover (measurements only; same bits either way)
-    const DebugSwitches& dbg = debug_switches();
-    const uint64_t flow_max = dbg.flow_max.value_or(kFlowMaxManifolds);
-    const bool cluster = w->cluster_step;  // decided by launch_coloring: this update's rows are in (cluster, colour) order
-    const bool flow = cluster || (w->flow_vel.p && h.valid && m_hint <= flow_max && w->cfg.solver_iterations > 0 &&
-                                  w->cfg.solver_iterations < 1000);
-    // fault injection for tests/test_gpu_full_size.py: one row gets a ticket nobody will ever publish, so the bounded
-    // spin of the dataflow kernels must give up, flag the step (overflow bit 4) and let the launch end
-    const bool stall = dbg.flow_stall;
-    const long long timeout_ticks = stall ? 2000000ll : kFlowTimeoutTicks;
+    const bool cluster = plan.path == SolverPath::Cluster, flow = plan.flow();
     // warm starting (contact_solve.h): one sweep more, in front - it applies the impulses the rows start from
     WarmJob warm{};
     if (w->warm) {
@@ -1099,15 +1070,13 @@ void launch_solver(phys_world* w, float dt) {
     }
     const uint32_t warm_sweep = w->warm ? 1u : 0u;
     const uint32_t sweeps = w->cfg.solver_iterations + warm_sweep;
+    // the colouring stage's job for k_rows_build: this update's new manifolds - all of them on a rebuild - go into the colour table
     ColorTableJob table{};
-    if (w->ctab_job_pending) {
-        table.tab = reinterpret_cast<ulonglong2*>(w->ctab.p);
-        table.mask = w->ctab_mask;
-        table.stamp = w->ctab_job_stamp;
-        table.all = w->ctab_job_all ? 1u : 0u;
-        table.man_color = w->man_color.p; table.man_prio = w->man_prio.p;
-        w->ctab_job_pending = false;
-    }
+    table.tab = reinterpret_cast<ulonglong2*>(w->ctab.p);
+    table.mask = w->ctab_mask;
+    table.stamp = coloring.stamp;
+    table.all = coloring.rebuild ? 1u : 0u;
+    table.man_color = w->man_color.p; table.man_prio = w->man_prio.p;
     if (flow && ++w->flow_epoch > 0xFFFFu) {
         // tags would repeat: forget every old one. AHEAD of k_rows_build: on a cluster step that kernel writes the constants
         // of foreign bodies into planes 12-15 = row_acc (with flow != 0 it never writes the impulses there), and a memset
@@ -1120,90 +1089,52 @@ void launch_solver(phys_world* w, float dt) {
     // materials: once a material call was made, the material instances of every kernel below - same
     // path choice, same launch sizes; they take the friction from the row. With every material at its default they give the
     // plain instances' bits.
-    const bool materials = materials_active(w);
     RowMaterials mats{};
     mats.body = reinterpret_cast<const float2*>(w->mat.p);
     mats.st = reinterpret_cast<const float2*>(w->st_mat.p);
     mats.ground = make_float2(w->ground_mat_set ? w->ground_mat[0] : w->cfg.friction, w->ground_mat_set ? w->ground_mat[1] : 0.0f);
     mats.threshold = w->restitution_threshold;
-    dispatch_bool(diag, [&](auto diag_t) { dispatch_bool(materials, [&](auto mat_t) {  // every kernel below in this world's instantiation
+    dispatch_bool(diag, [&](auto diag_t) { dispatch_bool(plan.materials, [&](auto mat_t) {  // every kernel below in this world's instantiation
         constexpr bool DIAG = decltype(diag_t)::value, MAT = decltype(mat_t)::value;
         { PHYS_PROF(w, PHYS_STAGE_ROWS);
           auto rows_build = [&](auto... mat) {
-              hipLaunchKernelGGL((k_rows_build<DIAG, MAT, decltype(mat)...>), grid_for_count(m_hint), tb, 0, s, w->counters.p, rows, sp, w->row_src.p, w->man_geo.p,
+              hipLaunchKernelGGL((k_rows_build<DIAG, MAT, decltype(mat)...>), dim3(plan.rows_blocks), tb, 0, s, w->counters.p, rows, sp, w->row_src.p, w->man_geo.p,
                                  w->pos.p, w->vel.p, inertia, stride, w->man_color.p,
-                                 w->color_state.p, flow ? (stall ? 2 : 1) : 0, table, w->cluster_slot.p, w->body_shared.p,
-                                 w->cluster_step ? w->cluster_slots : 0u, w->cluster_count, warm, mat...);
+                                 w->color_state.p, flow ? (plan.stall ? 2 : 1) : 0, table, w->cluster_slot.p, w->body_shared.p,
+                                 cluster ? w->cluster_slots : 0u, w->cluster_count, warm, mat...);
           };
           if constexpr (MAT) rows_build(mats); else rows_build(); }
+        if (cluster) {
+            PHYS_PROF(w, PHYS_STAGE_SOLVE_CLUSTER);
+            launch_solve_cluster(w, plan, rows.all, cap, sp.friction, inertia, stride, diag);
+            return;
+        }
         if (flow) {
-            if (cluster) {
-                PHYS_PROF(w, PHYS_STAGE_SOLVE_CLUSTER);
-                launch_solve_cluster(w, rows.all, cap, sp.friction, inertia, stride, diag, timeout_ticks, MAT);
-                return;
-            }
-            // about one wave per SIMD or less: waiting waves must not crowd out the ones that can run
-            // four lanes per manifold while the hop latency is everything - and, where the launch may take the whole chip
-            // (w->flow_wide: three workgroups per CU, 672 of them), all the way up: 155k manifolds 0.250 ms against 0.446 with
-            // 224 workgroups, C3's 216k 0.325 (cluster kernel 0.513), the 1M cubes' 379k 0.405 (cluster kernel 0.235)
-            const bool quad = m_hint <= (dbg.flow_quad_max ? dbg.flow_quad_max : (w->flow_wide ? kFlowMaxManifolds : kFlowQuadMaxManifolds));
-            const uint32_t threads = 256u;
-            const uint32_t rows_per_item = quad ? threads / 4 : threads;
-            uint64_t items = (uint64_t)sweeps * ((m_hint * 5 / 4 + rows_per_item - 1) / rows_per_item) + 1;
-            int cus = 256;
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, w->device);
-            // statically dealt items need every workgroup running: a third of the chip's slots by default (beside other
-            // streams' kernels), seven eighths of them - the cluster kernel's share - where the GPU is this world's alone
-            // (small scenes are a chain of hand-offs, not throughput: C2's 10k manifolds 0.053 ms at 224 workgroups, 0.058 at 672)
-            const uint64_t most = quad ? (w->flow_wide && m_hint > 32768u ? (uint64_t)(3 * (cus - cus / 8)) : 224) : 256;
-            if (items > most) items = most;  // the remaining items are taken by the same workgroups
+            const dim3 items(plan.items), threads(256);
             PHYS_PROF(w, PHYS_STAGE_SOLVE_FLOW);
-            // look one work item ahead (k_solve_flow) while a colour class keeps a good part of the launch busy; below that the
-            // solve is a chain of hand-offs and an item held ahead only waits (C3: 16k rows per colour, 65k lanes: +10 %;
-            // 1M cubes: 41k rows per colour: -10 %). PHYS_DEBUG_FLOW_PIPELINE=0/1 forces it (measurements; same bits).
-            const uint64_t per_color = m_hint / (h.valid && h.n_colors ? h.n_colors : 1u);
-            const uint32_t pipeline = (uint32_t)dbg.flow_pipeline.value_or(4 * per_color >= threads * items);
-            if (quad)
-                hipLaunchKernelGGL((k_solve_flow_quad<DIAG, MAT>), dim3((unsigned)items), dim3(threads), 0, s, w->counters.p, sweeps, w->flow_epoch,
-                                   rows, sp.friction, inertia, stride, w->vel.p, w->flow_vel.p, (uint32_t)w->n, timeout_ticks, warm_sweep, warm);
+            if (plan.path == SolverPath::FlowQuad)
+                hipLaunchKernelGGL((k_solve_flow_quad<DIAG, MAT>), items, threads, 0, s, w->counters.p, sweeps, w->flow_epoch,
+                                   rows, sp.friction, inertia, stride, w->vel.p, w->flow_vel.p, (uint32_t)w->n, plan.timeout_ticks, warm_sweep, warm);
             else
-                hipLaunchKernelGGL((k_solve_flow<DIAG, MAT>), dim3((unsigned)items), dim3(threads), 0, s, w->counters.p, sweeps, w->flow_epoch,
-                                   rows, sp.friction, inertia, stride, w->vel.p, w->flow_vel.p, (uint32_t)w->n, timeout_ticks, pipeline,
+                hipLaunchKernelGGL((k_solve_flow<DIAG, MAT>), items, threads, 0, s, w->counters.p, sweeps, w->flow_epoch,
+                                   rows, sp.friction, inertia, stride, w->vel.p, w->flow_vel.p, (uint32_t)w->n, plan.timeout_ticks, plan.pipeline,
                                    warm_sweep, warm);
             return;
         }
         // colours [0, big) get a launch each; [big, n_colours) go through the single-workgroup tail
-        constexpr uint32_t kTailMax = 512;  // manifolds per colour the tail should take: one trip of the workgroup
-        uint32_t big = 0;
-        if (h.valid) {
-            big = h.n_colors;
-            while (big > 0 && h.color_count[big - 1] <= kTailMax) --big;
-            if (h.n_colors - big < 2) big = h.n_colors;  // a tail of one colour is just a slower launch
-        }
-        // four lanes per manifold while a colour is too small to fill the chip with one lane per manifold (measured
-        // crossover ~30k rows: 15k rows 10.2 vs 11.9 us per launch, 53k rows 18.3 vs 16.7, 85k rows 21.5 vs 18.7).
-        // PHYS_DEBUG_COLOR_KERNEL=lane / quad: one of them for every colour (A/B measurements, parity tests)
-        constexpr uint32_t kQuadColorMaxRows = 32768;
-        auto grid_for_quads = [&](uint64_t count) {
-            uint64_t b = (count * 5 / 4 + kQuadRowsPerGroup - 1) / kQuadRowsPerGroup + 1;
-            const uint64_t hi = (cap + kQuadRowsPerGroup - 1) / kQuadRowsPerGroup;
-            if (b > hi) b = hi;
-            if (b > 16384) b = 16384;
-            return dim3((unsigned)(b ? b : 1));
-        };
         for (uint32_t it = 0; it < sweeps; ++it) {
             const int apply_only = warm_sweep && it == 0 ? 1 : 0, last = it + 1 == sweeps ? 1 : 0;
-            for (uint32_t col = 0; col < big; ++col) {
+            for (uint32_t col = 0; col < plan.big; ++col) {
                 PHYS_PROF(w, PHYS_STAGE_SOLVE);
-                if (!dbg.color_kernel_lane.value_or(h.color_count[col] > kQuadColorMaxRows))  // four lanes per manifold
-                    hipLaunchKernelGGL((k_solve_color_quad<DIAG, MAT>), grid_for_quads(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
+                if (plan.color_quad[col])  // four lanes per manifold
+                    hipLaunchKernelGGL((k_solve_color_quad<DIAG, MAT>), dim3(plan.color_blocks[col]), tb, 0, s, w->counters.p, col, rows,
                                        sp.friction, inertia, stride, w->vel.p, (uint32_t)w->n, apply_only, last, warm);
                 else
-                    hipLaunchKernelGGL((k_solve_color<DIAG, MAT>), grid_for_count(h.color_count[col]), tb, 0, s, w->counters.p, col, rows,
+                    hipLaunchKernelGGL((k_solve_color<DIAG, MAT>), dim3(plan.color_blocks[col]), tb, 0, s, w->counters.p, col, rows,
                                        sp.friction, inertia, stride, w->vel.p, apply_only, last, warm);
             }
             PHYS_PROF(w, PHYS_STAGE_SOLVE_TAIL);
-            hipLaunchKernelGGL((k_solve_tail<DIAG, MAT>), dim3(1), dim3(kTailThreads), 0, s, w->counters.p, big, rows, sp.friction,
+            hipLaunchKernelGGL((k_solve_tail<DIAG, MAT>), dim3(1), dim3(kTailThreads), 0, s, w->counters.p, plan.big, rows, sp.friction,
                                inertia, stride, w->vel.p, apply_only, last, warm);
         }
     }); });

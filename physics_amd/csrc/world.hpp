@@ -13,19 +13,12 @@
 #include <vector>
 
 #include "../../include/physics_hip.h"
+#include "plan.hpp"
 
 namespace phys {
 
-constexpr int kMaxColors = 64;  // == PHYS_MAX_COLORS of include/spec/contact_solve.h
-constexpr uint64_t kClusterMinBodies = 32768;  // below: the dataflow kernels win anyway (few launches' worth of rows)
 constexpr uint32_t kClusterDynamicPeriod = 8;  // cluster steps between two deals of the dynamic homes (a body that became active
                                                // since has none and is served as another cluster's body: slower, never wrong)
-// measured with tools/cluster_crossover.py (solve + rows, ms: cluster / four-lane dataflow kernel with statically dealt items):
-// mixed piles 91k manifolds 0.518 / 0.353, 145k 0.519 / 0.486, 155k 0.535 / 0.494, 216k (C3) 0.576 / 0.696; towers 92k 0.647 /
-// 0.415, 182k 0.699 / 0.700, 256k 0.712 / 0.984 - the cluster kernel's time is its chain (nearly the same at every size), the
-// dataflow kernel's grows with the rows
-constexpr uint64_t kClusterMinManifolds = 170000;
-constexpr uint64_t kFlowWideMaxManifolds = 400000;  // the dataflow kernels' upper end (solver.hip kFlowMaxManifolds)
 constexpr uint32_t kClusterMaxSlots = 2496;    // bodies per cluster whose {v, w, x, I^-1} fit one CU's LDS (64 B each: 156 KiB; 13-bit slot field)
 
 void set_error(const std::string& msg);
@@ -181,21 +174,6 @@ struct ProfScope {
     ~ProfScope() { if (p.on) p.end(s); }
 };
 
-// launch-size hints taken from an EARLIER step's counters (asynchronous read-back); never needed for
-// correctness
-struct StepHint {
-    bool valid = false;
-    uint32_t n_manifolds = 0, n_colors = 0, n_pairs = 0, max_region = 0, n_used_buckets = 0, n_contacts = 0;
-    uint32_t n_active = 0;         // owned bodies with a manifold (0 = unknown)
-    uint32_t color_rounds = 0;     // max over the recent INCREMENTAL updates
-    uint32_t full_rounds = 0;      // rounds of the last full re-colouring (0 = unknown)
-    uint32_t recent_rounds[8] = {};
-    uint32_t recent_pos = 0;
-    uint32_t n_new = 0xFFFFFFFFu;  // most manifolds without a kept colour in one of the recent incremental updates (~0: unknown)
-    uint32_t recent_new[8] = {};
-    uint32_t color_count[kMaxColors] = {};
-};
-
 // split of the broad phase's bucket table over the three axes (kernels.hpp: grid_bucket)
 struct GridShape {
     uint32_t mx = 7, my = 7, mz = 7;  // per-axis masks: cells per axis - 1 (each >= 3)
@@ -204,21 +182,9 @@ struct GridShape {
 
 // worlds alive per device in this process (abi.hip): two of them step on two streams, i.e. beside each other
 int worlds_on_device(int device);
-// PHYS_FLAG_EXCLUSIVE_GPU, no PHYS_FLAG_SHARED_GPU, no other world on the device: asked afresh at each use (abi.hip)
+// PHYS_FLAG_EXCLUSIVE_GPU, no PHYS_FLAG_SHARED_GPU, no other world on the device: asked afresh for every update's plan (abi.hip)
 bool gpu_is_exclusive(const phys_world* w);
-// PHYS_DEBUG_* switches, parsed once per process by the first debug_switches() (abi.hip). Unset: false / 0 / nullopt
-struct DebugSwitches {
-    bool no_cluster = false, cluster_dynamic = false, no_flow_preference = false, flow_stall = false;
-    std::optional<uint64_t> cluster_min, flow_max;
-    std::optional<int> clusters_per_cu;
-    uint64_t cluster_cap = 0, flow_quad_max = 0, ctab_slots = 0;
-    uint32_t flow_epoch = 0;
-    int np_threads = 0, pair_lanes = 0, brick_stage = 0;
-    bool raycast_stats = false;  // PHYS_DEBUG_RAYCAST_STATS: phys_raycast counts the cells and candidates its rays visit (stderr)
-    std::optional<bool> flow_pipeline, np_early_probe;  // the value begins with '1'
-    std::optional<bool> color_kernel_lane;              // the value begins with 'l' (four lanes otherwise)
-    std::optional<bool> pair_kernel_brick;              // brick, unless the value is 'b' followed by anything but 'r'
-};
+// PHYS_DEBUG_* switches (plan.hpp DebugSwitches), parsed once per process by the first call (abi.hip)
 const DebugSwitches& debug_switches();
 
 struct Constraint {
@@ -235,6 +201,7 @@ struct phys_world {
     ~phys_world();
     phys_config cfg;
     int device = 0;
+    int cus = 0;  // its CU count (phys_create)
     hipStream_t stream = nullptr;
     uint64_t n = 0;        // body slots the kernels run over = n_owned + max_ghosts
     uint64_t n_owned = 0;  // bodies of phys_set_bodies: every host-facing size and index check
@@ -327,9 +294,6 @@ struct phys_world {
     uint32_t ctab_mask = 0;     // capacity - 1 (power of two >= 1.5 * max_manifolds)
     bool ctab_valid = false;    // a table of the previous update exists
     uint64_t color_epoch = 0;   // updates with collisions since phys_set_bodies
-    bool ctab_job_pending = false;  // launch_coloring prepared a table build for launch_solver's k_rows_build
-    uint32_t ctab_job_stamp = 0;    // the stamp its entries get
-    bool ctab_job_all = false;      // table rebuild: every manifold of the update is inserted, not only the new ones
     phys::DevBuf<uint32_t> color_block_hist;  // [colour][workgroup] histogram / offsets of the colour sort
     // colouring state
     phys::DevBuf<unsigned long long> color_state;  // 4n: used masks | three rotating per-body priority buffers
@@ -350,15 +314,12 @@ struct phys_world {
     // cluster solver (cluster.hip): spatial clusters fixed at phys_set_bodies, rows sorted by (cluster, colour) per step
     uint32_t cluster_count = 0, cluster_slots = 0;  // 0 clusters: not available for this scene (dynamic: set per update)
     bool cluster_dynamic = false;           // clusters are remade every update from the bodies that have manifolds (cluster.hip)
-    int cluster_cus = 0;                    // CUs of the device (dynamic planning)
     uint32_t cluster_age = 0;               // cluster steps since the homes were dealt out (dynamic: remade every kClusterDynamicPeriod)
     bool cluster_homes_valid = false;
     phys::DevBuf<uint32_t> active_flag, active_rank;  // n + 4 each: flag / exclusive rank in the broad phase's bucket order
-    bool cluster_step = false;                      // this update's rows are in (cluster, colour) order
     phys::DevBuf<uint32_t> cluster_slot;   // body -> cluster * slots + slot
     phys::DevBuf<uint32_t> cluster_body;   // cluster * slots + slot -> body (0xFFFFFFFF: empty)
     phys::DevBuf<uint32_t> body_shared;    // 2 per body: 64-bit mask of the colours in which ANOTHER cluster's row updates it
-    bool flow_wide = false;          // this update: the four-lane dataflow kernel may use three workgroups per CU (exclusive GPU)
     bool seg_count_dirty = false;    // the (cluster, colour) counters were left non-zero by the last cluster step (three-launch scan)
     uint32_t seg_count_bins = 0;     // ... which used this many of them
     phys::DevBuf<uint32_t> seg_count, seg_start;  // rows per (cluster, colour) - kept behind body_shared, seg_count itself is unused - and their exclusive scan
@@ -424,7 +385,6 @@ struct phys_world {
     hipEvent_t snap_event[kSnapRing] = {};
     bool snap_pending[kSnapRing] = {};
     bool snap_full[kSnapRing] = {};
-    bool snap_tag_full = false;
     uint32_t snap_next = 0;
     phys::Profiler prof;
     uint32_t host_sticky_overflow = 0;  // overflow bits seen in counter snapshots (poll_snapshots), until phys_sync
