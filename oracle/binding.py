@@ -40,6 +40,7 @@ def load():
         "oracle_apply_force_centre_of_gravity": (C.c_int32, [vp, C.c_uint64, f32p]),
         "oracle_apply_force_at_position": (C.c_int32, [vp, C.c_uint64, f32p, f32p]),
         "oracle_apply_force_at_offset": (C.c_int32, [vp, C.c_uint64, f32p, f32p]),
+        "oracle_set_forces": (C.c_int32, [vp, f32p, f32p]),
         "oracle_apply_gravity": (C.c_int32, [vp]),
         "oracle_step": (C.c_int32, [vp, C.c_uint64]),
         "oracle_update": (C.c_int32, [vp, C.c_uint64]),
@@ -146,6 +147,10 @@ class OracleWorld:
     def apply_force_at_offset(self, body, force, offset):
         f, o = _f(force), _f(offset)
         self._ck(self.lib.oracle_apply_force_at_offset(self.h, body, _p(f), _p(o)))
+
+    def set_forces(self, force=None, torque=None):
+        f, t = _f(force), _f(torque)
+        self._ck(self.lib.oracle_set_forces(self.h, _p(f), _p(t)))
 
     def apply_gravity(self):
         self._ck(self.lib.oracle_apply_gravity(self.h))

@@ -119,6 +119,17 @@ int32_t oracle_apply_force_at_offset(oracle_world* w, uint64_t body, const float
     return PHYS_OK;
 }
 
+// phys_set_forces: overwrite the force and / or torque accumulators of every body; a null array leaves its side alone
+int32_t oracle_set_forces(oracle_world* w, const float* force, const float* torque) {
+    if (!w) return fail(PHYS_ERR_INVALID_ARG, "null argument");
+    for (size_t i = 0; i < w->state.entities.size(); ++i) {
+        RigidBody& b = w->state.entities[i];
+        if (force) for (int k = 0; k < 3; ++k) b.force[k] = force[3 * i + k];
+        if (torque) for (int k = 0; k < 3; ++k) b.torque[k] = torque[3 * i + k];
+    }
+    return PHYS_OK;
+}
+
 int32_t oracle_apply_gravity(oracle_world* w) { w->state.apply_gravity(); return PHYS_OK; }
 
 int32_t oracle_step(oracle_world* w, uint64_t dt_nanos) {
