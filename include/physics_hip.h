@@ -583,12 +583,17 @@ int32_t phys_get_device_view(phys_world* w, phys_device_view* out);
  * record is 32 B: {min xyz, max xyz, global id, pad}. phys_halo_pack writes to DEVICE memory the records of
  * owned bodies whose fattened AABB reaches outside [x_lo + reach, x_hi - reach] and returns the count;
  * reach must be >= the largest AABB edge on ANY rank (all-reduce phys_stats.max_extent), reach <= 0
- * means this rank's own grid cell. Both calls use the AABBs / grid of the last update or phys_broadphase.
+ * means this rank's own grid cell. A record may be any number of the receiving rank's grid cells wide (the cell is
+ * that rank's own largest extent, not the all-reduced one): phys_halo_pairs tests it against the owned bodies of every
+ * cell it covers. Both calls use the AABBs / grid of the last update or phys_broadphase.
  * phys_halo_pack first fills the whole buffer with 0xFF (empty slot = global id 0xFFFFFFFF). phys_halo_pairs
  * ignores records [skip_first, skip_first + skip_count): the caller's own block of an all-gathered buffer.
  * With n_records / n_cross_pairs == NULL both calls only ENQUEUE work on the world's stream and return
  * (no host synchronisation; phys_get_stats reports the counts later): the per-step exchange then costs no
- * host round trip when the collective is enqueued on the same stream (phys_device_view.stream). phys_halo_pairs takes the gathered records of the OTHER ranks (device
+ * host round trip when the collective is enqueued on the same stream (phys_device_view.stream). With a pointer they
+ * return PHYS_ERR_CAPACITY when THIS call's records / pairs did not fit (cap, or max(4 n_bodies, 4096) cross pairs;
+ * what fitted is written, nothing behind the capacity is): the same call with enough room succeeds right after. The
+ * overflow also stays in phys_stats.overflow bit 3 until phys_sync reports it. phys_halo_pairs takes the gathered records of the OTHER ranks (device
  * memory) and appends owned-vs-remote candidate pairs (local index, global id of the remote body)
  * under the ownership rule "emitted by the rank owning the body with the smaller global id". */
 int32_t phys_set_global_ids(phys_world* w, const uint32_t* global_ids /*n*/);

@@ -90,7 +90,8 @@ __global__ __launch_bounds__(256) void k_halo_pairs(uint32_t n_remote, uint32_t 
     const bool live = k < n_remote && (k < skip_first || k >= skip_first + skip_count) && remote[k].gid != 0xFFFFFFFFu;
     aabb_t rb;
     uint32_t rgid = 0;
-    int c0[3] = {0, 0, 0}, c1[3] = {-1, -1, -1};
+    int c0[3] = {0, 0, 0}, c1[3] = {-1, -1, -1}, sweep[3] = {0, 0, 0};
+    const int axis_cells[3] = {(int)axis_mask.mx + 1, (int)axis_mask.my + 1, (int)axis_mask.mz + 1};
     if (live) {
         const HaloRecord r = remote[k];
         rb.lo = v3_make(r.lo[0], r.lo[1], r.lo[2]);
@@ -100,20 +101,26 @@ __global__ __launch_bounds__(256) void k_halo_pairs(uint32_t n_remote, uint32_t 
         for (int a = 0; a < 3; ++a) {
             c0[a] = grid_cell_coord(r.lo[a] - 0.5f * cell, inv_cell);
             c1[a] = grid_cell_coord(r.hi[a] + 0.5f * cell, inv_cell);
-            if (c1[a] - c0[a] > 7) c1[a] = c0[a] + 7;  // bound of the sweep (a remote box is at most `reach` wide; buckets met twice on
-                                                       // a short axis are harmless: a candidate counts only in its TRUE cell, below)
+            // The record's cells [c0, c1] are as many as the REMOTE box is wide in LOCAL cells: `reach` bounds the box by the
+            // largest extent of any rank, the cell is this rank's own, so a rank of small bodies beside a large one sees
+            // records of any width. Cells wrap modulo the axis size, so one pass over the axis meets every bucket: the
+            // sweep is the cell range or the whole axis, whichever is shorter, and a candidate counts where its TRUE
+            // cell lies in [c0, c1] (a bucket is met once; its bodies of other, aliased cells are not the record's).
+            // The loops below run to the widest record of the wave: one record wider than the table costs all 64 lanes
+            // of its wave one pass over the whole table, and no more than that.
+            sweep[a] = c1[a] - c0[a] + 1 < axis_cells[a] ? c1[a] - c0[a] + 1 : axis_cells[a];
         }
     }
     // wave-uniform sweep over the largest cell range in the wave
     int span[3];
     for (int a = 0; a < 3; ++a) {
-        span[a] = wave_max(live ? c1[a] - c0[a] + 1 : 0);
+        span[a] = wave_max(sweep[a]);
     }
     for (int dz = 0; dz < span[2]; ++dz)
         for (int dy = 0; dy < span[1]; ++dy)
             for (int dx = 0; dx < span[0]; ++dx) {
                 const int cx = c0[0] + dx, cy = c0[1] + dy, cz = c0[2] + dz;
-                const bool in = live && cx <= c1[0] && cy <= c1[1] && cz <= c1[2];
+                const bool in = live && dx < sweep[0] && dy < sweep[1] && dz < sweep[2];
                 uint32_t t = 0, t_end = 0;
                 if (in) {
                     const uint32_t bk = grid_bucket(cx, cy, cz, axis_mask);
@@ -134,11 +141,13 @@ __global__ __launch_bounds__(256) void k_halo_pairs(uint32_t n_remote, uint32_t 
                         aabb_t bj;
                         bj.lo = ld3(sorted_box, 2 * t);
                         bj.hi = ld3(sorted_box, 2 * t + 1);
-                        // the candidate must really live in the scanned cell (buckets alias distant cells)
-                        const bool same_cell = grid_cell_coord(0.5f * (bj.lo.x + bj.hi.x), inv_cell) == cx &&
-                                               grid_cell_coord(0.5f * (bj.lo.y + bj.hi.y), inv_cell) == cy &&
-                                               grid_cell_coord(0.5f * (bj.lo.z + bj.hi.z), inv_cell) == cz;
-                        hit = same_cell && aabb_overlap(rb, bj) && global_id[j] < rgid;
+                        // the candidate must really live in a cell of the record (buckets alias distant cells). Its bucket
+                        // is met once by this sweep, so this is the one place it can count.
+                        const int tx = grid_cell_coord(0.5f * (bj.lo.x + bj.hi.x), inv_cell);
+                        const int ty = grid_cell_coord(0.5f * (bj.lo.y + bj.hi.y), inv_cell);
+                        const int tz = grid_cell_coord(0.5f * (bj.lo.z + bj.hi.z), inv_cell);
+                        const bool in_cells = tx >= c0[0] && tx <= c1[0] && ty >= c0[1] && ty <= c1[1] && tz >= c0[2] && tz <= c1[2];
+                        hit = in_cells && aabb_overlap(rb, bj) && global_id[j] < rgid;
                         ++t;
                     }
                     emit_cross_pairs(hit, j, rgid, cross_pairs, cap, ctr);
@@ -370,6 +379,14 @@ int32_t halo_unpack_ghosts(phys_world* w, const void* dev_records, uint64_t n_re
     return PHYS_OK;
 }
 
+// The start of a phys_halo_pack / phys_halo_pairs call: its count back to zero, and the halo bit of the step's overflow
+// word cleared, so that the synchronous forms report the overflow of THEIR call and a caller who resizes and calls again
+// is not told of the call before. The sticky word keeps every bit for phys_sync and phys_get_stats.
+__global__ void k_halo_begin(StepCounters* __restrict__ ctr, bool pairs) {
+    if (pairs) ctr->n_cross_pairs = 0; else ctr->n_halo = 0;
+    atomicAnd(&ctr->overflow, ~kOvfHalo);
+}
+
 static int32_t read_counters(phys_world* w) {
     PHYS_HIP_TRY(hipMemcpyAsync(w->h_counters, w->counters.p, sizeof(StepCounters), hipMemcpyDeviceToHost, w->stream));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
@@ -381,7 +398,7 @@ int32_t halo_pack(phys_world* w, float x_lo, float x_hi, float reach, void* dev_
     if (!(w->cfg.flags & PHYS_FLAG_COLLISIONS)) { set_error("world created without PHYS_FLAG_COLLISIONS"); return PHYS_ERR_UNSUPPORTED; }
     if (!w->grid_valid) { set_error("phys_halo_pack needs the AABBs of an update or phys_broadphase first"); return PHYS_ERR_UNSUPPORTED; }
     const uint32_t n = (uint32_t)w->n;
-    PHYS_HIP_TRY(hipMemsetAsync(&w->counters.p->n_halo, 0, 4, w->stream));
+    hipLaunchKernelGGL(k_halo_begin, dim3(1), dim3(1), 0, w->stream, w->counters.p, false);
     PHYS_HIP_TRY(hipMemsetAsync(dev_out, 0xFF, cap * sizeof(HaloRecord), w->stream));  // unused slots: id 0xFFFFFFFF
     if (n) {
         PHYS_PROF(w, PHYS_STAGE_MISC);
@@ -404,7 +421,7 @@ int32_t halo_pairs(phys_world* w, const void* dev_remote, uint64_t n_remote, uin
         w->max_cross_pairs = std::max<uint64_t>(4 * w->n, 4096);
         PHYS_HIP_TRY(w->cross_pairs.resize(2 * w->max_cross_pairs));
     }
-    PHYS_HIP_TRY(hipMemsetAsync(&w->counters.p->n_cross_pairs, 0, 4, w->stream));
+    hipLaunchKernelGGL(k_halo_begin, dim3(1), dim3(1), 0, w->stream, w->counters.p, true);
     if (n_remote && w->n) {
         const uint32_t T = w->grid_table_size;
         PHYS_PROF(w, PHYS_STAGE_MISC);
