@@ -343,7 +343,6 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     w->n_owned = n;
     w->max_ghosts = nt - n;
     w->forces_dirty = false;
-    w->have_lambda = false;  // previous_solution: None
     w->aabbs_valid = false;
     w->grid_valid = false;
     w->sorted_grid_valid = false;
@@ -352,80 +351,41 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     w->body_filters_set = false;    // every body slot gets the default filter below
     w->body_materials_set = false;  // ... and the default material
     for (int k = 0; k < phys_world::kSnapRing; ++k) w->snap_pending[k] = false;  // the stream was synchronised above
-    { const int32_t rc = events_reset(w); if (rc != PHYS_OK) return rc; }  // contact events: history and pending events are gone
-    { const int32_t rc = triggers_reset(w); if (rc != PHYS_OK) return rc; }  // trigger volumes: occupancy and pending events too
+    PHYS_TRY(events_reset(w));    // contact events: history and pending events are gone
+    PHYS_TRY(triggers_reset(w));  // trigger volumes: occupancy and pending events too
     if (n == 0) return PHYS_OK;
 
-    // host staging with RigidBody::new defaults (rigid_body.rs:64-76); ghost slots: no shape, immovable
-    std::vector<float> h_pos(3 * nt, 0.0f), h_rot(4 * nt), h_vel(8 * nt), h_inv(9 * nt, 0.0f), h_diag(4 * nt, 0.0f), h_he(3 * nt, 0.0f);
-    std::vector<uint32_t> h_shape(nt, PHYS_SHAPE_NONE), h_gid(nt, 0xFFFFFFFFu), h_filt(2 * nt, 0u);
-    for (uint64_t i = 0; i < nt; ++i) h_filt[2 * i] = kFilterDefaultWord;
-    std::vector<float> h_mat(2 * nt, 0.0f);
-    for (uint64_t i = 0; i < nt; ++i) h_mat[2 * i] = w->cfg.friction;
-    std::memcpy(h_pos.data(), pos, 12 * n);
-    w->singular_inertia = false;
-    w->all_diag_inertia = true;
-    w->uniform_inertia = true;
-    w->body_capsules = false;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (rot) std::memcpy(&h_rot[4 * i], rot + 4 * i, 16);
-        else { h_rot[4 * i] = 0.0f; h_rot[4 * i + 1] = 0.0f; h_rot[4 * i + 2] = 0.0f; h_rot[4 * i + 3] = 1.0f; }
-        const float m_i = mass ? mass[i] : 1.0f;
-        for (int k = 0; k < 3; ++k) { h_vel[8 * i + k] = lin ? lin[3 * i + k] : 0.0f; h_vel[8 * i + 4 + k] = ang ? ang[3 * i + k] : 0.0f; }
-        h_vel[8 * i + 3] = 1.0f / m_i;  // constraints.rs:75
-        h_vel[8 * i + 7] = m_i;
-        m33 I, inv;
-        for (int k = 0; k < 9; ++k) I.m[k] = inertia ? inertia[9 * i + k] : ((k % 4 == 0) ? 1.0f : 0.0f);
-        // The reference inverts the (constant, world-frame) tensor every step (rigid_body.rs:31, quirk Q5);
-        // inverting once gives the same bits.
-        if (!m33_try_inverse(&I, &inv)) {
-            w->singular_inertia = true;
-            for (int k = 0; k < 9; ++k) inv.m[k] = 0.0f;
-        }
-        for (int k = 0; k < 9; ++k) {
-            h_inv[9 * i + k] = inv.m[k];
-            if (k % 4 != 0 && inv.m[k] != 0.0f) w->all_diag_inertia = false;
-        }
-        h_diag[4 * i] = inv.m[0]; h_diag[4 * i + 1] = inv.m[4]; h_diag[4 * i + 2] = inv.m[8];
-        if (h_diag[4 * i] != h_diag[0] || h_diag[4 * i + 1] != h_diag[1] || h_diag[4 * i + 2] != h_diag[2]) w->uniform_inertia = false;
-        if (shape_type) h_shape[i] = shape_type[i];
-        if (h_shape[i] == PHYS_SHAPE_CAPSULE) w->body_capsules = true;
-        if (half_extent) std::memcpy(&h_he[3 * i], half_extent + 3 * i, 12);
-        h_gid[i] = (uint32_t)i;
-    }
-    for (uint64_t i = n; i < nt; ++i) {  // ghost slots: identity pose, inverse mass 0, mass +inf (F / m = 0), inverse inertia 0
-        h_rot[4 * i + 3] = 1.0f;
-        h_vel[8 * i + 3] = 0.0f;
-        h_vel[8 * i + 7] = std::numeric_limits<float>::infinity();
-    }
-    if (nt > n) w->uniform_inertia = false;  // the ghosts' zero tensors differ from everybody's
+    // host staging with RigidBody::new defaults (setup.hpp); ghost slots: no shape, immovable
+    const BodyStaging h = stage_bodies(n, nt - n, pos, rot, lin, ang, mass, inertia, shape_type, half_extent, w->cfg.friction);
+    w->singular_inertia = h.singular_inertia;
+    w->all_diag_inertia = h.all_diag_inertia;
+    w->uniform_inertia = h.uniform_inertia;
+    w->body_capsules = h.body_capsules;
     hipStream_t s = w->stream;
-    PHYS_HIP_TRY(hipMemcpyAsync(w->pos.p, h_pos.data(), 12 * nt, hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->rot.p, h_rot.data(), 16 * nt, hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->vel.p, h_vel.data(), 32 * nt, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->pos.p, h.pos.data(), 12 * nt, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->rot.p, h.rot.data(), 16 * nt, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->vel.p, h.vel.data(), 32 * nt, hipMemcpyHostToDevice, s));
     PHYS_HIP_TRY(hipMemsetAsync(w->force.p, 0, 12 * nt, s));
     PHYS_HIP_TRY(hipMemsetAsync(w->torque.p, 0, 12 * nt, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->inv_inertia.p, h_inv.data(), 36 * nt, hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->inv_inertia_diag.p, h_diag.data(), 16 * nt, hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->half_extent.p, h_he.data(), 12 * nt, hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->shape.p, h_shape.data(), 4 * nt, hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->global_id.p, h_gid.data(), 4 * nt, hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->filt.p, h_filt.data(), 8 * nt, hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->mat.p, h_mat.data(), 8 * nt, hipMemcpyHostToDevice, s));
-    if (!w->all_diag_inertia) w->uniform_inertia = false;
-    PHYS_HIP_TRY(hipStreamSynchronize(s));  // staging vectors die here
+    PHYS_HIP_TRY(hipMemcpyAsync(w->inv_inertia.p, h.inv_inertia.data(), 36 * nt, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->inv_inertia_diag.p, h.inv_inertia_diag.data(), 16 * nt, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->half_extent.p, h.half_extent.data(), 12 * nt, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->shape.p, h.shape.data(), 4 * nt, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->global_id.p, h.global_id.data(), 4 * nt, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->filt.p, h.filt.data(), 8 * nt, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->mat.p, h.mat.data(), 8 * nt, hipMemcpyHostToDevice, s));
+    PHYS_HIP_TRY(hipStreamSynchronize(s));  // the staged arrays are done with
     if (w->cfg.flags & PHYS_FLAG_COLLISIONS) {
-        grid_plan(w, pos, half_extent);
-        int32_t rc = collision_alloc(w);
-        if (rc != PHYS_OK) return rc;
+        const GridPlan grid = grid_plan(w->n, w->n_owned, pos, half_extent, w->cfg.contact_margin);
+        w->grid_table_size = grid.table_size;
+        w->grid_shape = grid.shape;
+        PHYS_TRY(collision_alloc(w));
         if (!(w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY)) {
-            rc = cluster_assign(w, pos);  // spatial clusters of the cluster solver (large scenes only)
-            if (rc != PHYS_OK) return rc;
+            PHYS_TRY(cluster_assign(w, pos));  // spatial clusters of the cluster solver (large scenes only)
             // contact events follow the manifold capacity; a body set too large for warm starting turns them off
             // (phys_get_contact_events then answers PHYS_ERR_UNSUPPORTED)
             if (w->ev_capacity && !w->warm) w->ev_capacity = 0;
-            rc = events_alloc(w);
-            if (rc != PHYS_OK) return rc;
+            PHYS_TRY(events_alloc(w));
         }
     }
     return PHYS_OK;
@@ -452,7 +412,6 @@ int32_t phys_clear_constraints(phys_world* w) {
     ENTER(w);
     w->constraints.clear();
     w->constraints_dirty = true;
-    w->have_lambda = false;
     return PHYS_OK;
 }
 
@@ -513,8 +472,7 @@ static int32_t enqueue_update(phys_world* w, float dt) {
         // the constraint right-hand side reads Q = force/torque accumulators including gravity (constraints.rs:92-104):
         // the constraint kernel adds gravity to the accumulators of the bodies it reads, and the step kernel adds
         // J^T lambda to entity 0 behind its own gravity addition - the reference's order, without a pass over all bodies
-        const int32_t rc = constraints_alloc(w);
-        if (rc != PHYS_OK) return rc;
+        PHYS_TRY(constraints_alloc(w));
         launch_constraint_phase(w, gravity_pending);
     }
     if (!collisions) {
@@ -527,8 +485,7 @@ static int32_t enqueue_update(phys_world* w, float dt) {
         launch_step_velocity_aabb(w, dt, gravity_pending, /*zero_step=*/!restart_extent, have_constraints);
         launch_broadphase(w, plan_pairs(plan_inputs(w), w->hint, dbg));
         if (!(w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY)) {
-            const int32_t rc = launch_static_pairs(w);  // static colliders only (phys_set_static_bodies): nothing otherwise
-            if (rc != PHYS_OK) return rc;
+            PHYS_TRY(launch_static_pairs(w));  // static colliders only (phys_set_static_bodies): nothing otherwise
             const PlanInputs in = plan_inputs(w);
             launch_narrowphase(w, plan_narrowphase(in, w->hint, dbg));
             const ColorPlan coloring = plan_coloring(in, w->hint, dbg);
@@ -555,27 +512,17 @@ int32_t phys_update_n(phys_world* w, uint64_t dt_nanos, uint32_t n) {
     if (w->n == 0) return fail(PHYS_ERR_NO_BODIES, "update with no bodies (reference: index panic, physics.rs:48)");
     if (w->singular_inertia) return fail(PHYS_ERR_SINGULAR_INERTIA, "singular inertia tensor (reference: unwrap panic, rigid_body.rs:31)");
     const float dt = duration_as_secs_f32(dt_nanos);
-    for (uint32_t k = 0; k < n; ++k) {
-        const int32_t rc = enqueue_update(w, dt);
-        if (rc != PHYS_OK) return rc;
-    }
+    for (uint32_t k = 0; k < n; ++k) PHYS_TRY(enqueue_update(w, dt));
     return PHYS_OK;
 }
 
 int32_t phys_update(phys_world* w, uint64_t dt_nanos) { return phys_update_n(w, dt_nanos, 1); }
 
-static int32_t fetch_counters(phys_world* w) {
-    PHYS_HIP_TRY(hipMemcpyAsync(w->h_counters, w->counters.p, sizeof(StepCounters), hipMemcpyDeviceToHost, w->stream));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    return PHYS_OK;
-}
-
 // Device-side errors are STICKY: every overflow bit raised by any step since the last phys_sync is reported here
 // (StepCounters::sticky_overflow; the per-step word is zeroed by the next step), then cleared.
 int32_t phys_sync(phys_world* w) {
     ENTER(w);
-    const int32_t rc = fetch_counters(w);
-    if (rc != PHYS_OK) return rc;
+    PHYS_TRY(fetch_counters(w));
     poll_snapshots(w);  // the stream is idle: every snapshot in flight is adopted now, none can bring reported bits back later
     const uint32_t bits = w->h_counters->overflow | w->h_counters->sticky_overflow | w->host_sticky_overflow;
     if (w->h_counters->n_static_pairs > w->static_pairs_seen) w->static_pairs_seen = w->h_counters->n_static_pairs;
@@ -584,43 +531,13 @@ int32_t phys_sync(phys_world* w) {
         PHYS_HIP_TRY(hipMemsetAsync(&w->counters.p->sticky_overflow, 0, sizeof(uint32_t), w->stream));
         PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     }
-    if (bits & kOvfCorruptRow) {
-        const uint32_t* g = w->h_counters->debug;
-        return fail(PHYS_ERR_HIP, ("internal error: a solver row names no body of this world and was refused (row " +
-                                   std::to_string(g[0]) + ": a " + std::to_string(g[1]) + ", b " + std::to_string(g[2]) + ", points " +
-                                   std::to_string(g[3]) + "; colour " + std::to_string(g[6]) + " rows [" + std::to_string(g[4]) + ", " +
-                                   std::to_string(g[5]) + "), tile base " + std::to_string(g[7]) + ")").c_str());
-    }
-    if (w->h_counters->debug[0] != 0u) {  // reported below: the next event may leave its own note
+    // (a refused row keeps its note on the device) reported below: the next event may leave its own note
+    if (!(bits & kOvfCorruptRow) && w->h_counters->debug[0] != 0u) {
         PHYS_HIP_TRY(hipMemsetAsync(w->counters.p->debug, 0, sizeof(w->counters.p->debug), w->stream));
         PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     }
-    if ((bits & kOvfHandoff) && w->h_counters->debug[0] == 0xC1u) {
-        const uint32_t* g = w->h_counters->debug;  // what the first lane of k_solve_cluster to give up was waiting for
-        return fail(PHYS_ERR_HIP, ("contact solver hand-off timed out (k_solve_cluster) in a step since the last phys_sync; velocities "
-                                   "are invalid from that step on. First lane to give up: cluster " + std::to_string(g[1] & 0xFFFFu) + " of " + std::to_string(g[1] >> 16) + ", row " +
-                                   std::to_string(g[2]) + ", bodies " + std::to_string(g[3]) + " / " + std::to_string(g[4]) +
-                                   ", tickets " + std::to_string(g[5] & 0xFFFFu) + " / " + std::to_string(g[5] >> 16) + ", waiting A/B " +
-                                   std::to_string(g[6] & 1u) + "/" + std::to_string((g[6] >> 1) & 1u) + ", modes " +
-                                   std::to_string((g[6] >> 4) & 3u) + "/" + std::to_string((g[6] >> 8) & 3u) + ", iteration " +
-                                   std::to_string((g[7] >> 8) & 0xFFu) + ", colour " + std::to_string(g[7] & 0xFFu) +
-                                   ". If other work shares this GPU with phys_update, create the world WITHOUT PHYS_FLAG_EXCLUSIVE_GPU").c_str());
-    }
-    if (bits & kOvfHandoff)
-        return fail(PHYS_ERR_HIP, "contact solver hand-off timed out (k_solve_flow) in a step since the last phys_sync; "
-                                  "velocities are invalid from that step on");
-    if (bits & kOvfColors)
-        return fail(PHYS_ERR_CAPACITY, "a body has more than 64 contact manifolds (PHYS_MAX_COLORS): the contact solve of "
-                                       "that step was skipped. This limit is not configurable");
-    if (bits & kOvfHalo)
-        return fail(PHYS_ERR_CAPACITY, "halo record / cross-pair capacity exceeded in a step since the last phys_sync");
-    if (bits & kOvfColorTable)
-        return fail(PHYS_ERR_CAPACITY, "the persistent colour table is full (a look-up or an insert gave up after thousands of "
-                                       "slots): the contact solve of that step was skipped. Raise phys_config.max_manifolds");
-    if (bits)
-        return fail(PHYS_ERR_CAPACITY, "pair / manifold capacity exceeded in a step since the last phys_sync (the contact "
-                                       "solve of that step was skipped): raise phys_config.max_pairs / max_manifolds");
-    return PHYS_OK;
+    const SyncError err = sync_error(bits, w->h_counters->debug);
+    return err.code == PHYS_OK ? PHYS_OK : fail(err.code, err.message.c_str());
 }
 
 static int32_t d2h(phys_world* w, void* dst, const void* src, size_t bytes) {
@@ -631,8 +548,8 @@ static int32_t d2h(phys_world* w, void* dst, const void* src, size_t bytes) {
 
 int32_t phys_get_transforms(phys_world* w, float* pos_out, float* rot_out) {
     ENTER(w);
-    int32_t rc = d2h(w, pos_out, w->pos.p, 12 * w->n_owned); if (rc) return rc;
-    rc = d2h(w, rot_out, w->rot.p, 16 * w->n_owned); if (rc) return rc;
+    PHYS_TRY(d2h(w, pos_out, w->pos.p, 12 * w->n_owned));
+    PHYS_TRY(d2h(w, rot_out, w->rot.p, 16 * w->n_owned));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     return PHYS_OK;
 }
@@ -646,8 +563,8 @@ int32_t phys_get_velocities(phys_world* w, float* lin_out, float* ang_out) {
 }
 int32_t phys_get_forces(phys_world* w, float* force_out, float* torque_out) {
     ENTER(w);
-    int32_t rc = d2h(w, force_out, w->force.p, 12 * w->n_owned); if (rc) return rc;
-    rc = d2h(w, torque_out, w->torque.p, 12 * w->n_owned); if (rc) return rc;
+    PHYS_TRY(d2h(w, force_out, w->force.p, 12 * w->n_owned));
+    PHYS_TRY(d2h(w, torque_out, w->torque.p, 12 * w->n_owned));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     return PHYS_OK;
 }
@@ -683,7 +600,7 @@ int32_t phys_get_aabbs(phys_world* w, float* out) {
     ENTER(w);
     if (!out) return fail(PHYS_ERR_INVALID_ARG, "null output");
     launch_aabb_only(w);
-    int32_t rc = d2h(w, out, w->aabb.p, 24 * w->n_owned); if (rc) return rc;
+    PHYS_TRY(d2h(w, out, w->aabb.p, 24 * w->n_owned));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     return PHYS_OK;
 }
@@ -704,29 +621,27 @@ int32_t phys_get_manifolds(phys_world* w, uint32_t* ids_out, uint32_t* counts_ou
                            float* points_out, uint64_t cap, uint64_t* n_manifolds) {
     ENTER(w);
     if (!n_manifolds) return fail(PHYS_ERR_INVALID_ARG, "null n_manifolds");
-    int32_t rc = fetch_counters(w); if (rc) return rc;
+    PHYS_TRY(fetch_counters(w));
     const uint64_t m = w->h_counters->n_manifolds < w->max_manifolds ? w->h_counters->n_manifolds : w->max_manifolds;
     *n_manifolds = m;
     if (m == 0 || (!ids_out && !counts_out && !normals_out && !points_out)) return PHYS_OK;
     // read back in storage order, sort by (a, b) on the host (a read-out convenience, not the hot path)
-    std::vector<uint32_t> a(m), b(m), c(m);
+    std::vector<uint32_t> ab(2 * m), c(m);
     std::vector<float> nrm(3 * m), pts(16 * m);
     {
         std::vector<float> geo(32 * m);  // 128-byte records: {a, b, count, -} {normal, -} 4 x {point, depth} + 32 spare bytes
         PHYS_HIP_TRY(hipMemcpy(geo.data(), w->man_geo.p, 128 * m, hipMemcpyDeviceToHost));
         for (uint64_t k = 0; k < m; ++k) {
             const float* g = &geo[32 * k];
-            std::memcpy(&a[k], g, 4); std::memcpy(&b[k], g + 1, 4); std::memcpy(&c[k], g + 2, 4);
+            std::memcpy(&ab[2 * k], g, 8); std::memcpy(&c[k], g + 2, 4);
             std::memcpy(&nrm[3 * k], g + 4, 12);
             std::memcpy(&pts[16 * k], g + 8, 64);
         }
     }
-    std::vector<uint64_t> order(m);
-    for (uint64_t k = 0; k < m; ++k) order[k] = k;
-    std::sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) { return a[x] < a[y] || (a[x] == a[y] && b[x] < b[y]); });
+    const std::vector<uint64_t> order = manifold_order(ab.data(), 2, m);
     for (uint64_t k = 0; k < m && k < cap; ++k) {
         const uint64_t s = order[k];
-        if (ids_out) { ids_out[2 * k] = a[s]; ids_out[2 * k + 1] = b[s]; }
+        if (ids_out) { ids_out[2 * k] = ab[2 * s]; ids_out[2 * k + 1] = ab[2 * s + 1]; }
         if (counts_out) counts_out[k] = c[s];
         if (normals_out) std::memcpy(normals_out + 3 * k, &nrm[3 * s], 12);
         if (points_out) std::memcpy(points_out + 16 * k, &pts[16 * s], 64);
@@ -737,7 +652,7 @@ int32_t phys_get_manifolds(phys_world* w, uint32_t* ids_out, uint32_t* counts_ou
 int32_t phys_get_stats(phys_world* w, phys_stats* out) {
     ENTER(w);
     if (!out) return fail(PHYS_ERR_INVALID_ARG, "null output");
-    int32_t rc = fetch_counters(w); if (rc) return rc;
+    PHYS_TRY(fetch_counters(w));
     std::memset(out, 0, sizeof(*out));
     const StepCounters& c = *w->h_counters;
     out->n_bodies = w->n_owned;
@@ -771,19 +686,8 @@ int32_t phys_set_static_bodies(phys_world* w, uint64_t n, const float* pos, cons
     // the arguments first: they are checked without a world or a device
     if (n >= 0x7FFFFFFEull) return fail(PHYS_ERR_INVALID_ARG, "too many static colliders (ids are PHYS_STATIC_ID_BIT | k below 0x7FFFFFFE)");
     if (n && (!pos || !shape_type || !half_extent)) return fail(PHYS_ERR_INVALID_ARG, "static colliders need pos, shape_type and half_extent");
-    for (uint64_t k = 0; k < n; ++k) {
-        if (shape_type[k] != PHYS_SHAPE_SPHERE && shape_type[k] != PHYS_SHAPE_BOX && shape_type[k] != PHYS_SHAPE_CAPSULE)
-            return fail(PHYS_ERR_INVALID_ARG, ("static collider " + std::to_string(k) + ": shape is neither SPHERE nor BOX nor CAPSULE").c_str());
-        bool finite = true, negative = false;
-        for (int a = 0; a < 3; ++a) {
-            finite = finite && std::isfinite(pos[3 * k + a]) && std::isfinite(half_extent[3 * k + a]);
-            negative = negative || half_extent[3 * k + a] < 0.0f;
-        }
-        if (rot)
-            for (int a = 0; a < 4; ++a) finite = finite && std::isfinite(rot[4 * k + a]);
-        if (!finite) return fail(PHYS_ERR_INVALID_ARG, ("static collider " + std::to_string(k) + ": non-finite pose or half extent").c_str());
-        if (negative) return fail(PHYS_ERR_INVALID_ARG, ("static collider " + std::to_string(k) + ": negative half extent").c_str());
-    }
+    std::string bad;
+    if (shape_set_error("static collider", n, shape_type, pos, rot, half_extent, bad)) return fail(PHYS_ERR_INVALID_ARG, bad.c_str());
     ENTER(w);
     // the colour table and the warm-start records name static ids, which are stale now (as phys_set_bodies does); also
     // when the new set fails to upload below (the world then holds no statics)
@@ -792,22 +696,12 @@ int32_t phys_set_static_bodies(phys_world* w, uint64_t n, const float* pos, cons
     w->static_pairs_seen = 0;
     w->static_filters_set = false;  // the new set starts with the default filters (static_set)
     w->static_materials_set = false;  // ... and the default materials
-    { const int32_t rc = events_reset(w); if (rc != PHYS_OK) return rc; }  // contact events name static ids too
+    PHYS_TRY(events_reset(w));  // contact events name static ids too
     return static_set(w, n, pos, rot, shape_type, half_extent);
 }
 
 // ---- collision filters ----
-// {category | mask << 16, (u32)group} per item; a NULL array gives that field its default
-static void pack_filters(uint64_t n, const uint16_t* category, const uint16_t* mask, const int16_t* group, std::vector<uint32_t>& out) {
-    out.resize(2 * n);
-    for (uint64_t k = 0; k < n; ++k) {
-        const uint32_t c = category ? category[k] : PHYS_FILTER_DEFAULT_CATEGORY;
-        const uint32_t m = mask ? mask[k] : PHYS_FILTER_DEFAULT_MASK;
-        out[2 * k] = c | (m << 16);
-        out[2 * k + 1] = group ? (uint32_t)(int32_t)group[k] : 0u;
-    }
-}
-
+// (pack_filters: setup.hpp)
 static int32_t set_filters(phys_world* w, DevBuf<uint32_t>& dst, uint64_t expected, bool& set_flag, const char* wrong_count,
                            uint64_t n, const uint16_t* category, const uint16_t* mask, const int16_t* group) {
     if (n != expected) return fail(PHYS_ERR_INVALID_ARG, wrong_count);
@@ -830,7 +724,7 @@ int32_t phys_set_static_filters(phys_world* w, uint64_t n, const uint16_t* categ
 int32_t phys_get_body_filters(phys_world* w, uint16_t* category_out, uint16_t* mask_out, int16_t* group_out) {
     ENTER(w);
     std::vector<uint32_t> h;
-    const int32_t rc = download_body_pairs(w, w->filt, h); if (rc) return rc;
+    PHYS_TRY(download_body_pairs(w, w->filt, h));
     for (uint64_t k = 0; k < w->n_owned; ++k) {
         if (category_out) category_out[k] = (uint16_t)(h[2 * k] & 0xFFFFu);
         if (mask_out) mask_out[k] = (uint16_t)(h[2 * k] >> 16);
@@ -847,16 +741,7 @@ int32_t phys_set_ground_filter(phys_world* w, uint16_t category, uint16_t mask) 
 }
 
 // ---- materials ----
-// {friction, restitution} per item; a NULL array gives that field its default. false: a value out of range
-static bool pack_materials(uint64_t n, const float* friction, const float* restitution, float default_friction, std::vector<float>& out) {
-    out.resize(2 * n);
-    for (uint64_t k = 0; k < n; ++k) {
-        const float f = friction ? friction[k] : default_friction, e = restitution ? restitution[k] : 0.0f;
-        if (!std::isfinite(f) || f < 0.0f || !(e >= 0.0f && e <= 1.0f)) return false;
-        out[2 * k] = f; out[2 * k + 1] = e;
-    }
-    return true;
-}
+// (pack_materials: setup.hpp)
 static const char* const kMaterialRange = "a friction must be finite and >= 0, a restitution in [0, 1]";
 // materials do not cross slab cuts (the halo record has no room for them): a sharded world refuses the calls
 #define PHYS_NO_MATERIALS_WHEN_SHARDED(w) \
@@ -886,7 +771,7 @@ int32_t phys_get_body_materials(phys_world* w, float* friction_out, float* resti
     ENTER(w);
     PHYS_NO_MATERIALS_WHEN_SHARDED(w);
     std::vector<float> h;
-    const int32_t rc = download_body_pairs(w, w->mat, h); if (rc) return rc;
+    PHYS_TRY(download_body_pairs(w, w->mat, h));
     for (uint64_t k = 0; k < w->n_owned; ++k) {
         if (friction_out) friction_out[k] = h[2 * k];
         if (restitution_out) restitution_out[k] = h[2 * k + 1];
@@ -914,7 +799,7 @@ int32_t phys_set_restitution_threshold(phys_world* w, float v) {
 
 int32_t phys_get_static_stats(phys_world* w, uint64_t* n_static, uint64_t* n_static_pairs, uint64_t* n_static_manifolds) {
     ENTER(w);
-    int32_t rc = fetch_counters(w); if (rc) return rc;
+    PHYS_TRY(fetch_counters(w));
     const StepCounters& c = *w->h_counters;
     const bool on = w->n_static != 0;  // (the counters of an update before the set was cleared say nothing about it)
     if (n_static) *n_static = w->n_static;
@@ -926,7 +811,7 @@ int32_t phys_get_static_stats(phys_world* w, uint64_t* n_static, uint64_t* n_sta
 int32_t phys_get_color_counts(phys_world* w, uint32_t* counts_out) {
     ENTER(w);
     if (!counts_out) return fail(PHYS_ERR_INVALID_ARG, "null output");
-    int32_t rc = fetch_counters(w); if (rc) return rc;
+    PHYS_TRY(fetch_counters(w));
     for (int k = 0; k < kMaxColors; ++k) counts_out[k] = k < (int)w->h_counters->n_colors ? w->h_counters->color_count[k] : 0u;
     return PHYS_OK;
 }
@@ -976,7 +861,7 @@ static int32_t cast_device(phys_world* w, bool sphere, uint64_t n, const float* 
                            const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
                            float* normal_out) {
     ENTER(w);
-    const int32_t rc = cast_args(sphere, n, origin, dir, radius, body_out, t_out); if (rc) return rc;
+    PHYS_TRY(cast_args(sphere, n, origin, dir, radius, body_out, t_out));
     if (n == 0) return PHYS_OK;
     return launch_trace(w, n, origin, dir, radius, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
 }
@@ -985,7 +870,7 @@ static int32_t cast_device(phys_world* w, bool sphere, uint64_t n, const float* 
 static int32_t cast_host(phys_world* w, bool sphere, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
                          const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out) {
     ENTER(w);
-    int32_t rc = cast_args(sphere, n, origin, dir, radius, body_out, t_out); if (rc) return rc;
+    PHYS_TRY(cast_args(sphere, n, origin, dir, radius, body_out, t_out));
     if (n == 0) return PHYS_OK;
     Staging in{w, w->stage}, out{w, w->rc_out};
     const auto s_origin = in.add(origin, 3 * n), s_dir = in.add(dir, 3 * n), s_radius = in.add(radius, n), s_max_t = in.add(max_t, n);
@@ -993,13 +878,12 @@ static int32_t cast_host(phys_world* w, bool sphere, uint64_t n, const float* or
     const auto s_mask = in.add(query_mask, n);
     const auto s_body = out.add(body_out, n);
     const auto s_t = out.add(t_out, n), s_normal = out.add(normal_out, 3 * n);
-    rc = in.reserve(); if (rc) return rc;
-    rc = out.reserve(); if (rc) return rc;
-    rc = in.copy(hipMemcpyHostToDevice); if (rc) return rc;
-    rc = launch_trace(w, n, in.at(s_origin), in.at(s_dir), in.at(s_radius), in.at(s_max_t), in.at(s_ignore), out.at(s_body), out.at(s_t),
-                      out.at(s_normal), in.at(s_mask));
-    if (rc) return rc;
-    rc = out.copy(hipMemcpyDeviceToHost); if (rc) return rc;
+    PHYS_TRY(in.reserve());
+    PHYS_TRY(out.reserve());
+    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
+    PHYS_TRY(launch_trace(w, n, in.at(s_origin), in.at(s_dir), in.at(s_radius), in.at(s_max_t), in.at(s_ignore), out.at(s_body), out.at(s_t),
+                          out.at(s_normal), in.at(s_mask)));
+    PHYS_TRY(out.copy(hipMemcpyDeviceToHost));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     return PHYS_OK;
 }
@@ -1064,8 +948,8 @@ static int32_t overlap_host(phys_world* w, uint64_t n, const uint32_t* shape_typ
     const auto s_ignore = in.add(ignore_body, n);
     const auto s_rot = in.add(rot_ijkw, 4 * n, /*align=*/16);  // read as float4
     const auto s_mask = in.add(query_mask, n);
-    int32_t rc = in.reserve(); if (rc) return rc;
-    rc = in.copy(hipMemcpyHostToDevice); if (rc) return rc;
+    PHYS_TRY(in.reserve());
+    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
     return launch_overlap(w, n, in.at(s_type), in.at(s_pos), in.at(s_rot), in.at(s_he), in.at(s_ignore), cap, offsets_out, ids_out, in.at(s_mask));
 }
 
@@ -1092,14 +976,8 @@ int32_t phys_set_triggers(phys_world* w, uint64_t n, const uint32_t* shape_type,
     // the arguments first, as phys_set_static_bodies checks them
     if (n > PHYS_MAX_TRIGGERS) return fail(PHYS_ERR_INVALID_ARG, "phys_set_triggers: more than PHYS_MAX_TRIGGERS trigger volumes");
     if (n && (!shape_type || !pos || !half_extent)) return fail(PHYS_ERR_INVALID_ARG, "trigger volumes need shape_type, pos and half_extent");
-    for (uint64_t k = 0; k < n; ++k) {
-        if (shape_type[k] != PHYS_SHAPE_SPHERE && shape_type[k] != PHYS_SHAPE_BOX && shape_type[k] != PHYS_SHAPE_CAPSULE)
-            return fail(PHYS_ERR_INVALID_ARG, ("trigger " + std::to_string(k) + ": shape is neither SPHERE nor BOX nor CAPSULE").c_str());
-        if (!finite_all(pos + 3 * k, 3) || !finite_all(half_extent + 3 * k, 3) || (rot_ijkw && !finite_all(rot_ijkw + 4 * k, 4)))
-            return fail(PHYS_ERR_INVALID_ARG, ("trigger " + std::to_string(k) + ": non-finite pose or half extent").c_str());
-        if (half_extent[3 * k] < 0.0f || half_extent[3 * k + 1] < 0.0f || half_extent[3 * k + 2] < 0.0f)
-            return fail(PHYS_ERR_INVALID_ARG, ("trigger " + std::to_string(k) + ": negative half extent").c_str());
-    }
+    std::string bad;
+    if (shape_set_error("trigger", n, shape_type, pos, rot_ijkw, half_extent, bad)) return fail(PHYS_ERR_INVALID_ARG, bad.c_str());
     ENTER(w);
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // updates in flight read the set that is replaced
     if (n == 0) return triggers_set(w, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
@@ -1108,9 +986,9 @@ int32_t phys_set_triggers(phys_world* w, uint64_t n, const uint32_t* shape_type,
     const auto s_pos = in.add(pos, 3 * n), s_he = in.add(half_extent, 3 * n);
     const auto s_rot = in.add(rot_ijkw, 4 * n, /*align=*/16);  // read as float4
     const auto s_mask = in.add(mask, n);
-    int32_t rc = in.reserve(); if (rc) return rc;
-    rc = in.copy(hipMemcpyHostToDevice); if (rc) return rc;
-    rc = triggers_set(w, n, in.at(s_type), in.at(s_pos), in.at(s_rot), in.at(s_he), in.at(s_mask)); if (rc) return rc;
+    PHYS_TRY(in.reserve());
+    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
+    PHYS_TRY(triggers_set(w, n, in.at(s_type), in.at(s_pos), in.at(s_rot), in.at(s_he), in.at(s_mask)));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // the staging buffer is the next query's
     return PHYS_OK;
 }
@@ -1125,9 +1003,9 @@ int32_t phys_set_trigger_poses(phys_world* w, uint64_t n, const float* pos, cons
     Staging in{w, w->stage};
     const auto s_pos = in.add(pos, 3 * n);
     const auto s_rot = in.add(rot_ijkw, 4 * n, /*align=*/16);
-    int32_t rc = in.reserve(); if (rc) return rc;
-    rc = in.copy(hipMemcpyHostToDevice); if (rc) return rc;
-    rc = triggers_set_poses(w, in.at(s_pos), in.at(s_rot)); if (rc) return rc;  // behind the updates already enqueued
+    PHYS_TRY(in.reserve());
+    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
+    PHYS_TRY(triggers_set_poses(w, in.at(s_pos), in.at(s_rot)));  // behind the updates already enqueued
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     return PHYS_OK;
 }
@@ -1180,16 +1058,13 @@ int32_t phys_get_global_ids(phys_world* w, uint32_t* out) {
 int32_t phys_get_cross_pairs(phys_world* w, uint32_t* pairs_out, uint64_t cap, uint64_t* n_pairs) {
     ENTER(w);
     if (!n_pairs) return fail(PHYS_ERR_INVALID_ARG, "null n_pairs");
-    int32_t rc = fetch_counters(w); if (rc) return rc;
+    PHYS_TRY(fetch_counters(w));
     const uint64_t m = w->h_counters->n_cross_pairs < w->max_cross_pairs ? w->h_counters->n_cross_pairs : w->max_cross_pairs;
     *n_pairs = m;
     if (pairs_out && m) {
-        std::vector<uint64_t> keys(m);
         std::vector<uint32_t> raw(2 * m);
         PHYS_HIP_TRY(hipMemcpy(raw.data(), w->cross_pairs.p, 8 * m, hipMemcpyDeviceToHost));
-        for (uint64_t k = 0; k < m; ++k) keys[k] = ((uint64_t)raw[2 * k] << 32) | raw[2 * k + 1];
-        std::sort(keys.begin(), keys.end());
-        for (uint64_t k = 0; k < m && k < cap; ++k) { pairs_out[2 * k] = (uint32_t)(keys[k] >> 32); pairs_out[2 * k + 1] = (uint32_t)keys[k]; }
+        sort_pairs(raw.data(), m, pairs_out, cap);
     }
     return PHYS_OK;
 }

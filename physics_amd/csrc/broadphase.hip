@@ -589,69 +589,27 @@ __global__ __launch_bounds__(kPairThreads) void k_find_pairs_slots(uint32_t n, c
 }
 
 // ---- host side -------------------------------------------------------------------------------------
-static uint32_t table_bits_for(uint64_t n) {
-    uint32_t bits = 9;  // 512 buckets = 8 bricks at least
-    while ((1ull << bits) < 2 * n && bits < 27) ++bits;
-    return bits;
-}
-
-// Table size (>= 2 buckets per body, a power of two) and its split over the axes, from the scene as uploaded: every axis
-// starts with 2 bits (one brick of 4 cells) and the rest go, one at a time, to the axis with the most cells per bucket
-// row - cells estimated as extent of the body centres / the largest bounding diameter. Any split is correct (cells wrap
-// modulo the axis size); a good one keeps far-apart cells out of the same bucket. Bodies move, the split stays: a pile
-// that compresses or spreads by a factor of two costs one bit of accuracy, not correctness.
-void grid_plan(phys_world* w, const float* pos, const float* half_extent) {
-    const uint64_t n = w->n_owned;
-    const uint32_t bits = table_bits_for(w->n);
-    w->grid_table_size = 1u << bits;
-    float lo[3] = {3e38f, 3e38f, 3e38f}, hi[3] = {-3e38f, -3e38f, -3e38f}, diam = 0.0f;
-    for (uint64_t i = 0; i < n; ++i) {
-        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], pos[3 * i + a]); hi[a] = std::max(hi[a], pos[3 * i + a]); }
-        if (half_extent) {
-            const float* h = half_extent + 3 * i;
-            diam = std::max(diam, 2.0f * std::max(h[0], std::max(h[1], h[2])));
-        }
-    }
-    const float cell = (diam > 0.0f ? diam : 1.0f) * 1.05f + 2.0f * w->cfg.contact_margin;
-    double cells[3];
-    for (int a = 0; a < 3; ++a) cells[a] = n ? std::max(1.0, (double)(hi[a] - lo[a]) / cell + 1.0) : 1.0;
-    uint32_t ab[3] = {2, 2, 2};
-    for (uint32_t left = bits - 6; left > 0; --left) {
-        int best = 0;
-        double worst = -1.0;
-        for (int a = 0; a < 3; ++a) {
-            const double load = cells[a] / (double)(1u << ab[a]);
-            if (load > worst && ab[a] < 20) { worst = load; best = a; }
-        }
-        ab[best] += 1;
-    }
-    GridShape g;
-    g.mx = (1u << ab[0]) - 1u; g.my = (1u << ab[1]) - 1u; g.mz = (1u << ab[2]) - 1u;
-    g.sx = ab[0] - 2u; g.sy = ab[1] - 2u;
-    w->grid_shape = g;
-}
-
 int32_t collision_alloc(phys_world* w) {
     const uint64_t n = w->n;
-    w->max_pairs = w->cfg.max_pairs ? w->cfg.max_pairs : std::max<uint64_t>(24 * n, 4096);
-    w->max_manifolds = w->cfg.max_manifolds ? w->cfg.max_manifolds : std::max<uint64_t>(17 * n, 4096);
-    if (w->max_pairs > 0xFFFFFFF0ull || w->max_manifolds > 0xFFFFFFF0ull) {
+    const CollisionSizes sz = collision_sizes(w->cfg, n, debug_switches());
+    w->max_pairs = sz.max_pairs;
+    w->max_manifolds = sz.max_manifolds;
+    if (!sz.ok) {
         set_error("max_pairs / max_manifolds exceed u32 indexing");
         return PHYS_ERR_INVALID_ARG;
     }
     const uint32_t T = w->grid_table_size;  // grid_plan (phys_set_bodies), before this
     {
         // one allocation, zeroed by one memset per step: [bucket counts | colouring state | StepCounters]
-        const size_t b_bytes = ((size_t)T * 4 + 255) / 256 * 256;
-        const size_t c_bytes = (w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY) ? 0 : ((size_t)4 * n * 8 + 255) / 256 * 256;
+        const size_t b_bytes = sz.bucket_bytes, c_bytes = sz.color_bytes;
         w->step_zero.free();  // a block of exactly this size
-        PHYS_HIP_TRY(w->step_zero.resize(b_bytes + c_bytes + sizeof(StepCounters)));
+        PHYS_HIP_TRY(w->step_zero.resize(b_bytes + c_bytes + sz.counter_bytes));
         w->bucket_count.point_at(reinterpret_cast<uint32_t*>(w->step_zero.p), T);
         w->color_state.point_at(reinterpret_cast<unsigned long long*>(w->step_zero.p + b_bytes), c_bytes / 8);
         w->counters.point_at(reinterpret_cast<StepCounters*>(w->step_zero.p + b_bytes + c_bytes), 1);
         w->step_zero_reset_bytes = b_bytes + c_bytes + kCountersStepResetBytes;
         w->step_zero_full_bytes = b_bytes + c_bytes + kCountersExtentResetBytes;  // not the sticky word behind it
-        PHYS_HIP_TRY(hipMemsetAsync(w->step_zero.p, 0, b_bytes + c_bytes + sizeof(StepCounters), w->stream));  // sticky word too
+        PHYS_HIP_TRY(hipMemsetAsync(w->step_zero.p, 0, b_bytes + c_bytes + sz.counter_bytes, w->stream));  // sticky word too
     }
     PHYS_HIP_TRY(w->bucket_of.resize(n));
     PHYS_HIP_TRY(w->bucket_cursor.resize(n));  // rank of each body inside its bucket
@@ -669,7 +627,7 @@ int32_t collision_alloc(phys_world* w) {
         PHYS_HIP_TRY(w->man_a.resize(M)); PHYS_HIP_TRY(w->man_b.resize(M));
         PHYS_HIP_TRY(w->man_color.resize(M));
         PHYS_HIP_TRY(w->man_geo.resize(32 * M));
-        w->warm = !(w->cfg.flags & PHYS_FLAG_NO_WARM_START) && M < (1ull << 26);  // the colour table's value word holds 26 bits of index
+        w->warm = sz.warm;
         if (w->warm) {
             PHYS_HIP_TRY(w->man_geo_prev.resize(32 * M));
             PHYS_HIP_TRY(w->man_imp.resize(12 * M));
@@ -679,17 +637,10 @@ int32_t collision_alloc(phys_world* w) {
         PHYS_HIP_TRY(w->man_prio.resize(M));
         PHYS_HIP_TRY(w->row_src.resize(M));
         PHYS_HIP_TRY(w->unc_list.resize(2 * M));
-        {
-            uint64_t cap = 4096;
-            while (cap < M + M / 2) cap <<= 1;
-            // PHYS_DEBUG_CTAB_SLOTS=<power of two>: a smaller table (tests of the bounded walks: crowded and overfull tables)
-            const uint64_t slots = debug_switches().ctab_slots;
-            if (slots >= 64 && (slots & (slots - 1)) == 0) cap = slots;
-            PHYS_HIP_TRY(w->ctab.resize(2 * cap));
-            w->ctab_mask = (uint32_t)(cap - 1);
-            w->ctab_valid = false;
-            w->color_epoch = 0;
-        }
+        PHYS_HIP_TRY(w->ctab.resize(2 * sz.ctab_slots));
+        w->ctab_mask = (uint32_t)(sz.ctab_slots - 1);
+        w->ctab_valid = false;
+        w->color_epoch = 0;
         PHYS_HIP_TRY(w->color_block_hist.resize((size_t)kMaxColors * 512));
         w->row_all.free();  // exactly 16 planes of M rows
         PHYS_HIP_TRY(w->row_all.resize(64 * M));  // 16 planes x M x float4
@@ -699,8 +650,7 @@ int32_t collision_alloc(phys_world* w) {
         w->row_pt.point_at(w->row_all.p + 16 * M, 32 * M);
         w->row_acc.point_at(w->row_all.p + 48 * M, 16 * M);
         w->flow_vel.free();  // null unless allocated below: per-colour launches only
-        // the dataflow solver addresses row_acc / flow_vel through 32-bit buffer offsets
-        if (!(w->cfg.flags & PHYS_FLAG_SOLVER_PER_COLOR) && 64 * M < 0xFFFFFFFFull && 32 * n < 0xFFFFFFFFull) {
+        if (sz.flow_buffers) {
             PHYS_HIP_TRY(w->flow_vel.resize(8 * n));
             // tags of an earlier scene must never look like tags of this one
             PHYS_HIP_TRY(hipMemsetAsync(w->flow_vel.p, 0, 8 * n * sizeof(float), w->stream));
@@ -786,8 +736,7 @@ void launch_broadphase(phys_world* w, const PairPlan& plan) {
 // phys_broadphase read-out: pairs sorted by (i, j). The sort is a host-side convenience of this
 // read-out call; the per-step pipeline never sorts (nothing downstream depends on pair order).
 int32_t sorted_pairs_to_host(phys_world* w, uint32_t* pairs_out, uint64_t cap, uint64_t* n_pairs) {
-    PHYS_HIP_TRY(hipMemcpyAsync(w->h_counters, w->counters.p, sizeof(StepCounters), hipMemcpyDeviceToHost, w->stream));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    PHYS_TRY(fetch_counters(w));
     if (w->h_counters->overflow & kOvfPairs) {
         set_error("pair capacity exceeded: raise phys_config.max_pairs");
         return PHYS_ERR_CAPACITY;
@@ -795,17 +744,9 @@ int32_t sorted_pairs_to_host(phys_world* w, uint32_t* pairs_out, uint64_t cap, u
     const uint64_t m = w->h_counters->n_pairs;
     *n_pairs = m;
     if (!pairs_out || m == 0) return PHYS_OK;
-    std::vector<uint64_t> keys(m);
-    {
-        std::vector<uint32_t> raw(2 * m);
-        PHYS_HIP_TRY(hipMemcpy(raw.data(), w->pairs.p, 8 * m, hipMemcpyDeviceToHost));
-        for (uint64_t k = 0; k < m; ++k) keys[k] = ((uint64_t)raw[2 * k] << 32) | raw[2 * k + 1];
-    }
-    std::sort(keys.begin(), keys.end());
-    for (uint64_t k = 0; k < m && k < cap; ++k) {
-        pairs_out[2 * k] = (uint32_t)(keys[k] >> 32);
-        pairs_out[2 * k + 1] = (uint32_t)keys[k];
-    }
+    std::vector<uint32_t> raw(2 * m);
+    PHYS_HIP_TRY(hipMemcpy(raw.data(), w->pairs.p, 8 * m, hipMemcpyDeviceToHost));
+    sort_pairs(raw.data(), m, pairs_out, cap);
     return PHYS_OK;
 }
 

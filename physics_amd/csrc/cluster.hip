@@ -36,12 +36,7 @@
 
 namespace phys {
 
-// occupancy asked for: three workgroups per CU (3 waves per SIMD, <= 168 VGPRs; at 128 the kernel spills 2) with diagonal
-// tensors, two otherwise. Measured on C5, same bits: 1 per CU 3.48 ms, 2 per CU 2.70, 3 per CU 2.20
-constexpr int kClusterPerCuDiag = 3, kClusterPerCuFull = 2;
-constexpr size_t kClusterLdsPerCu = 160 * 1024;
-constexpr size_t kClusterSlotBytesDecl = 64;  // == kClusterSlotBytes below
-size_t cluster_lds_bytes(uint32_t slots);
+// (occupancy, LDS budget and slot size - kClusterPerCu*, kClusterLdsPerCu, kClusterSlotBytes, cluster_lds_bytes: setup.hpp)
 
 // per-row side info packed into row_n.w (as bits): slot (16) | mode (2) per side
 //   mode 0: own cluster, never shared -> LDS only          1: own cluster, shared -> LDS while its tag is current, else granule
@@ -49,20 +44,8 @@ size_t cluster_lds_bytes(uint32_t slots);
 __host__ __device__ __forceinline__ uint32_t side_info(uint32_t slot, uint32_t mode) { return (slot & 0x3FFFu) | (mode << 14); }
 
 // ---- host: spatial clusters from the positions at upload ------------------------------------------------------
-static uint32_t spread10(uint32_t x) {
-    x &= 0x3ffu;
-    x = (x ^ (x << 16)) & 0xff0000ffu;
-    x = (x ^ (x << 8)) & 0x0300f00fu;
-    x = (x ^ (x << 4)) & 0x030c30c3u;
-    x = (x ^ (x << 2)) & 0x09249249u;
-    return x;
-}
-
 // the (cluster, colour) counters sit behind the 2 n mask words of body_shared, on a 16-byte boundary (the scans read uint4)
 static size_t seg_count_offset(uint64_t n) { return ((size_t)2 * n + 3) & ~(size_t)3; }
-
-// workgroups of a cluster grid of per_cu per CU, an eighth of the chip spared (at least 8)
-static uint32_t clusters_on_chip(int per_cu, int cus) { return (uint32_t)std::max(8, per_cu * (cus - cus / 8)); }
 
 int32_t cluster_assign(phys_world* w, const float* pos /* host, 3 * n_owned */) {
     w->cluster_count = 0;
@@ -73,32 +56,19 @@ int32_t cluster_assign(phys_world* w, const float* pos /* host, 3 * n_owned */) 
     w->cluster_dynamic = false;
     w->cluster_homes_valid = false;
     if (dbg.no_cluster || n_owned < kClusterMinBodies || !w->flow_vel.p) return PHYS_OK;
-    const int cus = w->cus;
     // one workgroup per cluster, several per CU (their phases interleave: one waits for its rows while the others
     // solve); an eighth of the chip to spare: EVERY workgroup must be resident (the kernel's occupancy bound admits
     // kClusterPerCu* of them per CU; a workgroup that found no room would be waited for until the time-out)
-    const int per_cu_max = w->all_diag_inertia ? kClusterPerCuDiag : kClusterPerCuFull;
-    int per_cu = dbg.clusters_per_cu ? std::min(per_cu_max, std::max(1, *dbg.clusters_per_cu)) : per_cu_max;
+    const int per_cu_max = cluster_per_cu_max(w->all_diag_inertia);
     // PHYS_DEBUG_CLUSTER_DYNAMIC: dynamic clusters even where the static ones fit; PHYS_DEBUG_CLUSTER_CAP=<bodies>: fewer
     // homes than the LDS would hold, so that some bodies stay homeless (tests of exactly that; same bits)
-    uint32_t slots = 0;
-    bool fits = !dbg.cluster_dynamic;
-    // ... and the LDS of a CU must hold all of its workgroups' bodies (64 B per slot + the segment table, in 1 KiB
-    // allocation units), or the grid would not be resident: fewer, larger clusters per CU until it does
-    for (; fits; --per_cu) {
-        const uint32_t max_clusters = clusters_on_chip(per_cu, cus);
-        slots = (uint32_t)((n_owned + max_clusters - 1) / max_clusters);
-        slots = (slots + 63u) / 64u * 64u;
-        const size_t per_wg = (cluster_lds_bytes(slots) + 1023) / 1024 * 1024;
-        if (per_wg * (size_t)per_cu <= kClusterLdsPerCu && slots <= kClusterMaxSlots) break;
-        if (per_cu == 1) fits = false;  // the owned bodies do not fit the chip's LDS
-    }
-    if (!fits) {
+    const ClusterFit fit = cluster_fit(n_owned, cluster_per_cu_first(per_cu_max, dbg), w->cus, 0u);
+    if (dbg.cluster_dynamic || !fit.ok) {
         // DYNAMIC clusters: homes are dealt out every update, to the bodies that have a manifold in it, in the broad
         // phase's bucket order (launch_cluster_sort); their number and size follow the count of such bodies
         // (cluster_plan_dynamic). Needs the sorted grid of the broad phase (n > 32768: always the case here).
-        const uint32_t clusters_max = clusters_on_chip(per_cu_max, cus);
-        const size_t homes_max = (size_t)cus * (kClusterLdsPerCu / kClusterSlotBytesDecl) + 64;
+        const uint32_t clusters_max = clusters_on_chip(per_cu_max, w->cus);
+        const size_t homes_max = (size_t)w->cus * (kClusterLdsPerCu / kClusterSlotBytes) + 64;
         PHYS_HIP_TRY(w->cluster_slot.resize(n));
         PHYS_HIP_TRY(w->cluster_body.resize(homes_max));
         // (the per-(cluster, colour) counters live behind the bodies' masks: both are zeroed every update, by ONE memset)
@@ -113,44 +83,20 @@ int32_t cluster_assign(phys_world* w, const float* pos /* host, 3 * n_owned */) 
         w->cluster_slots = 0;
         return PHYS_OK;
     }
-    const uint32_t clusters = (uint32_t)((n_owned + slots - 1) / slots);
-    // isotropic Morton key over the bounding box of the owned bodies. Ghost bodies (sharded worlds) get no home in
-    // any cluster: a row never has one as body A, as body B it is 'another cluster's body' for everybody (slot ~0 maps
-    // to a cluster nobody runs), and no workgroup is spent on clusters that own no rows
-    float lo[3] = {3e38f, 3e38f, 3e38f}, hi[3] = {-3e38f, -3e38f, -3e38f};
-    for (uint64_t i = 0; i < n_owned; ++i)
-        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], pos[3 * i + a]); hi[a] = std::max(hi[a], pos[3 * i + a]); }
-    const float span = std::max(std::max(hi[0] - lo[0], hi[1] - lo[1]), std::max(hi[2] - lo[2], 1e-6f));
-    const float scale = 1023.0f / span;
-    std::vector<uint64_t> keyed(n_owned);
-    for (uint64_t i = 0; i < n_owned; ++i) {
-        uint32_t q[3];
-        for (int a = 0; a < 3; ++a) {
-            const float t = (pos[3 * i + a] - lo[a]) * scale;
-            q[a] = t <= 0.0f ? 0u : (t >= 1023.0f ? 1023u : (uint32_t)t);
-        }
-        const uint64_t key = spread10(q[0]) | (spread10(q[1]) << 1) | (spread10(q[2]) << 2);
-        keyed[i] = (key << 32) | i;
-    }
-    std::sort(keyed.begin(), keyed.end());
-    std::vector<uint32_t> cslot(n, 0xFFFFFFFFu), body_of((size_t)clusters * slots, 0xFFFFFFFFu);
-    for (uint64_t r = 0; r < n_owned; ++r) {
-        const uint32_t i = (uint32_t)keyed[r];
-        cslot[i] = (uint32_t)r;  // = cluster * slots + slot
-        body_of[r] = i;
-    }
+    const ClusterHomes homes = cluster_homes(n, n_owned, pos, fit.slots);
+    const uint32_t clusters = homes.clusters;
     PHYS_HIP_TRY(w->cluster_slot.resize(n));
-    PHYS_HIP_TRY(w->cluster_body.resize(body_of.size()));
+    PHYS_HIP_TRY(w->cluster_body.resize(homes.cluster_body.size()));
     // 64-bit mask of remote colours per body; behind them the per-(cluster, colour) counters (zeroed together: one memset)
     PHYS_HIP_TRY(w->body_shared.resize(seg_count_offset(n) + (size_t)clusters * PHYS_MAX_COLORS + 4));
     PHYS_HIP_TRY(hipMemsetAsync(w->body_shared.p, 0, (seg_count_offset(n) + (size_t)clusters * PHYS_MAX_COLORS + 4) * 4, w->stream));
     PHYS_HIP_TRY(w->seg_start.resize((size_t)clusters * PHYS_MAX_COLORS + 4));
     PHYS_HIP_TRY(w->man_rank.resize(w->max_manifolds));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->cluster_slot.p, cslot.data(), 4 * n, hipMemcpyHostToDevice, w->stream));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->cluster_body.p, body_of.data(), 4 * body_of.size(), hipMemcpyHostToDevice, w->stream));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->cluster_slot.p, homes.cluster_slot.data(), 4 * n, hipMemcpyHostToDevice, w->stream));
+    PHYS_HIP_TRY(hipMemcpyAsync(w->cluster_body.p, homes.cluster_body.data(), 4 * homes.cluster_body.size(), hipMemcpyHostToDevice, w->stream));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     w->cluster_count = clusters;
-    w->cluster_slots = slots;
+    w->cluster_slots = fit.slots;
     return PHYS_OK;
 }
 
@@ -162,42 +108,11 @@ bool cluster_plan_dynamic(phys_world* w, const StepHint& h, const DebugSwitches&
     // bodies); the plan is only made when they are dealt out again
     if (w->cluster_homes_valid && w->cluster_age < kClusterDynamicPeriod) return true;
     w->cluster_homes_valid = false;
-    // the count of the last deal; before the first one: a pile has about as many bodies in contact as it has manifolds
-    // (between half as many and twice as many; a world seeded with a mid-fall state - 1M cubes, 360k manifolds, 250k
-    // active bodies - never got a first deal with the upper bound). Too low a guess leaves some bodies without a home for
-    // one period (slower, never wrong), and the deal itself then counts them.
-    uint64_t active = h.n_active;
-    if (active == 0) active = std::min<uint64_t>(w->n_owned, (uint64_t)h.n_manifolds);
-    if (active == 0) return false;
-    const int per_cu_max = w->all_diag_inertia ? kClusterPerCuDiag : kClusterPerCuFull;
-    int per_cu = dbg.clusters_per_cu ? std::min(per_cu_max, std::max(1, *dbg.clusters_per_cu)) : per_cu_max;
-    const int cus = w->cus;
-    // homes for a quarter more bodies than the last known count; what does not get one is served as "another cluster's
-    // body" (slower, never wrong), so this is a matter of speed only
-    uint64_t want = active + active / 4;
-    if (dbg.cluster_cap && want > dbg.cluster_cap) want = dbg.cluster_cap;
-    for (;; --per_cu) {
-        const uint32_t clusters = clusters_on_chip(per_cu, cus);
-        uint32_t slots = (uint32_t)((want + clusters - 1) / clusters);
-        slots = std::max(64u, (slots + 63u) / 64u * 64u);
-        const size_t per_wg = (cluster_lds_bytes(slots) + 1023) / 1024 * 1024;
-        const bool ok = per_wg * (size_t)per_cu <= kClusterLdsPerCu && slots <= kClusterMaxSlots;
-        if (ok || per_cu == 1) {
-            // Only while the homes fit with the FULL number of workgroups per CU. Measured on the growing 1M-cube pile: the
-            // moment the plan has to go to two or one larger workgroups per CU the per-colour launches are faster (2.10
-            // against 2.33 ms at 430k active bodies, 2.66 against 3.30 at 500k; with half the bodies homeless 3.61 against
-            // 4.08) - fewer workgroups hide less of each other's colour steps. (A capacity set for tests is obeyed.)
-            if ((!ok || per_cu < per_cu_max) && !dbg.cluster_cap && !dbg.clusters_per_cu) return false;
-            // (PHYS_DEBUG_CLUSTERS_PER_CU asks for fewer, larger workgroups - never for homes that do not fit: with the
-            // switch set, the growing 1M-cube pile once ran one 160 KiB workgroup per CU with half its bodies homeless and
-            // ended in the hand-off time-out)
-            if (!ok && !dbg.cluster_cap) return false;
-            if (!ok) slots = kClusterMaxSlots / 64u * 64u;  // one workgroup per CU, as many homes as its LDS holds
-            w->cluster_count = clusters;
-            w->cluster_slots = slots;
-            return true;
-        }
-    }
+    const std::optional<ClusterShape> shape = plan_dynamic_clusters(w->n_owned, w->all_diag_inertia, w->cus, h, dbg);
+    if (!shape) return false;
+    w->cluster_count = shape->clusters;
+    w->cluster_slots = shape->slots;
+    return true;
 }
 
 // position of an owned body in the broad phase's bucket order (what k_scatter computed), or ~0
@@ -382,8 +297,6 @@ void launch_cluster_sort(phys_world* w, const ColorPlan& plan, StepCounters* sna
 // on a cluster step, and a 4-point row is 240 bytes per iteration instead of 320.
 struct ClusterRowArrays { float4* all; uint64_t cap; };
 constexpr int kClusterPlaneHdr = 0, kClusterPlaneN = 1, kClusterPlaneGeo = 2, kClusterPlaneAcc = 6, kClusterPlaneMass = 9, kClusterPlaneForeign = 12;
-constexpr uint32_t kClusterSlotBytes = 64;  // LDS per body slot: {v, tag} {w, 1/m} {x, -} {inverse inertia diagonal, -}
-size_t cluster_lds_bytes(uint32_t slots) { return (size_t)slots * kClusterSlotBytes + (PHYS_MAX_COLORS + 1) * 4 + 12; }
 
 constexpr int kClusterThreads = 256;
 #ifndef PHYS_POLL_SLEEP

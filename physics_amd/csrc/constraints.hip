@@ -238,20 +238,8 @@ int32_t constraints_alloc(phys_world* w) {
     if (!w->constraints_dirty && w->d_constraints.p) return PHYS_OK;
     const size_t C = w->constraints.size();
     const size_t n = 3 * C;
-    // distinct selected columns, each with its selecting rows in constraint order
-    std::vector<std::pair<uint32_t, uint32_t>> sel(n);  // (column, row)
-    for (size_t c = 0; c < C; ++c)
-        for (uint32_t k = 0; k < 3; ++k) sel[3 * c + k] = {6u * w->constraints[c].body + 3u * w->constraints[c].kind + k, (uint32_t)(3 * c + k)};
-    std::vector<std::pair<uint32_t, uint32_t>> sorted = sel;
-    std::stable_sort(sorted.begin(), sorted.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    std::vector<uint32_t> col_id, col_ptr, col_rows(n), row_cidx(n);
-    for (size_t k = 0; k < n; ++k) {
-        if (k == 0 || sorted[k].first != sorted[k - 1].first) { col_id.push_back(sorted[k].first); col_ptr.push_back((uint32_t)k); }
-        col_rows[k] = sorted[k].second;
-        row_cidx[sorted[k].second] = (uint32_t)col_id.size() - 1;
-    }
-    col_ptr.push_back((uint32_t)n);
-    const size_t U = col_id.size();
+    const ConstraintColumns cols = constraint_columns(w->constraints);
+    const size_t U = cols.col_id.size();
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     PHYS_HIP_TRY(w->d_constraints.resize(C));
     PHYS_HIP_TRY(w->cg_cols.resize(U + (U + 1) + n + n));
@@ -262,10 +250,10 @@ int32_t constraints_alloc(phys_world* w) {
     PHYS_HIP_TRY(w->cg_jl.resize(8));
     uint32_t* base = w->cg_cols.p;
     PHYS_HIP_TRY(hipMemcpy(w->d_constraints.p, w->constraints.data(), C * sizeof(Constraint), hipMemcpyHostToDevice));
-    PHYS_HIP_TRY(hipMemcpy(base, col_id.data(), U * 4, hipMemcpyHostToDevice));
-    PHYS_HIP_TRY(hipMemcpy(base + U, col_ptr.data(), (U + 1) * 4, hipMemcpyHostToDevice));
-    PHYS_HIP_TRY(hipMemcpy(base + 2 * U + 1, col_rows.data(), n * 4, hipMemcpyHostToDevice));
-    PHYS_HIP_TRY(hipMemcpy(base + 2 * U + 1 + n, row_cidx.data(), n * 4, hipMemcpyHostToDevice));
+    PHYS_HIP_TRY(hipMemcpy(base, cols.col_id.data(), U * 4, hipMemcpyHostToDevice));
+    PHYS_HIP_TRY(hipMemcpy(base + U, cols.col_ptr.data(), (U + 1) * 4, hipMemcpyHostToDevice));
+    PHYS_HIP_TRY(hipMemcpy(base + 2 * U + 1, cols.col_rows.data(), n * 4, hipMemcpyHostToDevice));
+    PHYS_HIP_TRY(hipMemcpy(base + 2 * U + 1 + n, cols.row_cidx.data(), n * 4, hipMemcpyHostToDevice));
     // a changed constraint list resets the warm start (the reference would panic on the shape mismatch)
     PHYS_HIP_TRY(hipMemset(w->cg_status.p, 0, 16));
     w->cg_n_cols = (uint32_t)U;

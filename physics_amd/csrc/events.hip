@@ -167,7 +167,7 @@ int32_t phys_contact_events_enable(phys_world* w, uint64_t capacity) {
     w->ev_capacity = capacity;
     if (capacity == 0) return events_alloc(w);  // off: buffers freed, pending events gone
     w->ev_buf.free();  // a new capacity: a buffer of exactly that size
-    int32_t rc = events_alloc(w); if (rc) return rc;
+    PHYS_TRY(events_alloc(w));
     EventState h{};
     if (was_on) {
         PHYS_HIP_TRY(hipMemcpyAsync(&h, w->ev_state.p, sizeof(h), hipMemcpyDeviceToHost, w->stream));
@@ -191,28 +191,9 @@ int32_t phys_get_contact_events(phys_world* w, phys_contact_event* out, uint64_t
     if (!n) return fail(PHYS_ERR_INVALID_ARG, "phys_get_contact_events: null n");
     if (cap && !out) return fail(PHYS_ERR_INVALID_ARG, "phys_get_contact_events: null out with cap > 0");
     if (w->ev_capacity == 0) return fail(PHYS_ERR_UNSUPPORTED, "contact events are off (phys_contact_events_enable)");
-    EventState h{};
-    PHYS_HIP_TRY(hipMemcpyAsync(&h, w->ev_state.p, sizeof(h), hipMemcpyDeviceToHost, w->stream));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    const uint64_t stored = h.cursor < w->ev_capacity ? h.cursor : w->ev_capacity;
-    *n = stored;
-    if (n_dropped) *n_dropped = h.cursor - stored;
-    if (!out && cap == 0) return PHYS_OK;  // count query: the buffer stays
-    if (stored > cap) return fail(PHYS_ERR_CAPACITY, "phys_get_contact_events: more events stored than cap (*n says how many); nothing was drained");
-    if (stored) {
-        PHYS_HIP_TRY(hipMemcpyAsync(out, w->ev_buf.p, stored * sizeof(phys_contact_event), hipMemcpyDeviceToHost, w->stream));
-        PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-        // device order is arbitrary; a read-out convenience as in phys_get_manifolds
-        std::sort(out, out + stored, [](const phys_contact_event& x, const phys_contact_event& y) {
-            if (x.step != y.step) return x.step < y.step;
-            if (x.kind != y.kind) return x.kind < y.kind;
-            if (x.body_a != y.body_a) return x.body_a < y.body_a;
-            return x.body_b < y.body_b;
-        });
-    }
-    // the cursor word only; ordered on the world's stream in front of the next update's kernels
-    if (h.cursor) PHYS_HIP_TRY(hipMemsetAsync(w->ev_state.p, 0, sizeof(h.cursor), w->stream));
-    return PHYS_OK;
+    static_assert(offsetof(EventState, cursor) == 0, "the cursor is the first word of the event state");
+    return drain_events(w, w->ev_state.p, w->ev_capacity, w->ev_buf.p, out, cap, n, n_dropped,
+                        "phys_get_contact_events: more events stored than cap (*n says how many); nothing was drained");
 }
 
 int32_t phys_get_contact_impulses(phys_world* w, float* out, uint64_t cap, uint64_t* n_manifolds) {
@@ -232,12 +213,7 @@ int32_t phys_get_contact_impulses(phys_world* w, float* out, uint64_t cap, uint6
     PHYS_HIP_TRY(hipMemcpy2DAsync(head.data(), 16, w->man_geo.p, 128, 16, m, hipMemcpyDeviceToHost, w->stream));
     PHYS_HIP_TRY(hipMemcpyAsync(imp.data(), w->man_imp.p, 48 * m, hipMemcpyDeviceToHost, w->stream));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    std::vector<uint64_t> order(m);
-    for (uint64_t k = 0; k < m; ++k) order[k] = k;
-    // phys_get_manifolds' order: pairs are unique, so (a, b) fixes it
-    std::sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) {
-        return head[4 * x] < head[4 * y] || (head[4 * x] == head[4 * y] && head[4 * x + 1] < head[4 * y + 1]);
-    });
+    const std::vector<uint64_t> order = manifold_order(head.data(), 4, m);  // phys_get_manifolds' order
     for (uint64_t k = 0; k < m && k < cap; ++k) {
         const uint64_t s = order[k];
         const uint32_t count = head[4 * s + 2];

@@ -336,8 +336,7 @@ int32_t halo_pack_bodies_faces(phys_world* w, void* dev_out, uint64_t cap, float
     if (!(w->slab_reach > 0.0f)) { set_error("phys_set_slab first"); return PHYS_ERR_UNSUPPORTED; }
     if (cap >= 0xFFFFFFFFull) { set_error("record capacity exceeds u32"); return PHYS_ERR_INVALID_ARG; }
     const uint32_t n = (uint32_t)w->n_owned;
-    const int32_t rc = halo_counts_room(w, n);
-    if (rc != PHYS_OK) return rc;
+    PHYS_TRY(halo_counts_room(w, n));
     PHYS_PROF(w, PHYS_STAGE_MISC);
     PHYS_HIP_TRY(hipMemsetAsync(dev_out, 0xFF, cap * sizeof(BodyRecord), w->stream));  // unused slots: global id 0xFFFFFFFF
     if (n) {
@@ -358,8 +357,7 @@ int32_t halo_unpack_ghosts(phys_world* w, const void* dev_records, uint64_t n_re
     if (w->max_ghosts == 0) { set_error("world created without phys_config.max_ghosts"); return PHYS_ERR_UNSUPPORTED; }
     if (!(w->slab_reach > 0.0f)) { set_error("phys_set_slab first"); return PHYS_ERR_UNSUPPORTED; }
     if (n_records >= 0xFFFFFFFFull) { set_error("record count exceeds u32"); return PHYS_ERR_INVALID_ARG; }
-    const int32_t rc = halo_counts_room(w, n_records);
-    if (rc != PHYS_OK) return rc;
+    PHYS_TRY(halo_counts_room(w, n_records));
     PHYS_PROF(w, PHYS_STAGE_MISC);
     const uint32_t G = (uint32_t)w->max_ghosts, n_owned = (uint32_t)w->n_owned;
     hipLaunchKernelGGL(k_ghost_clear, dim3((G + 255) / 256), dim3(256), 0, w->stream, n_owned, (uint32_t)w->n, w->shape.p,
@@ -387,12 +385,6 @@ __global__ void k_halo_begin(StepCounters* __restrict__ ctr, bool pairs) {
     atomicAnd(&ctr->overflow, ~kOvfHalo);
 }
 
-static int32_t read_counters(phys_world* w) {
-    PHYS_HIP_TRY(hipMemcpyAsync(w->h_counters, w->counters.p, sizeof(StepCounters), hipMemcpyDeviceToHost, w->stream));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    return PHYS_OK;
-}
-
 int32_t halo_pack(phys_world* w, float x_lo, float x_hi, float reach, void* dev_out, uint64_t cap, uint64_t* n_records) {
     if (!dev_out) { set_error("null argument"); return PHYS_ERR_INVALID_ARG; }
     if (!(w->cfg.flags & PHYS_FLAG_COLLISIONS)) { set_error("world created without PHYS_FLAG_COLLISIONS"); return PHYS_ERR_UNSUPPORTED; }
@@ -406,8 +398,7 @@ int32_t halo_pack(phys_world* w, float x_lo, float x_hi, float reach, void* dev_
                            w->global_id.p, x_lo, x_hi, reach, (HaloRecord*)dev_out, cap, w->counters.p);
     }
     if (!n_records) return PHYS_OK;  // asynchronous form: nothing returns to the host (phys_get_stats has the count)
-    const int32_t rc = read_counters(w);
-    if (rc != PHYS_OK) return rc;
+    PHYS_TRY(fetch_counters(w));
     if (w->h_counters->overflow & kOvfHalo) { set_error("halo buffer capacity exceeded"); return PHYS_ERR_CAPACITY; }
     *n_records = w->h_counters->n_halo;
     return PHYS_OK;
@@ -437,8 +428,7 @@ int32_t halo_pairs(phys_world* w, const void* dev_remote, uint64_t n_remote, uin
                                w->max_cross_pairs, w->counters.p);
     }
     if (!n_cross) return PHYS_OK;  // asynchronous form
-    const int32_t rc = read_counters(w);
-    if (rc != PHYS_OK) return rc;
+    PHYS_TRY(fetch_counters(w));
     if (w->h_counters->overflow & kOvfHalo) { set_error("cross-pair capacity exceeded"); return PHYS_ERR_CAPACITY; }
     *n_cross = w->h_counters->n_cross_pairs;
     return PHYS_OK;

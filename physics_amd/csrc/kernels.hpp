@@ -11,6 +11,7 @@
 #include "../../include/spec/det_math.h"
 #include "../../include/spec/vec.h"
 #include "world.hpp"
+#include "readout.hpp"
 #include "wave.hpp"
 
 static_assert(PHYS_MAX_COLORS == phys::kMaxColors, "colour limit mismatch");
@@ -161,7 +162,7 @@ __device__ __forceinline__ void color_table_insert(const ColorTableJob& job, uin
 // A filter is {category | mask << 16, (uint32_t)(int32_t)group}: one 8-byte load per body or static. The defaults
 // (category 0x0001, mask 0xFFFF, group 0) let everything collide. Two filters collide unless the rule says otherwise:
 // the same nonzero group decides by its sign, anything else needs each category in the other's mask.
-constexpr uint32_t kFilterDefaultWord = 0xFFFF0001u;  // category 0x0001 | mask 0xFFFF << 16
+// (kFilterDefaultWord: setup.hpp)
 __host__ __device__ __forceinline__ bool filter_pass(uint2 fa, uint2 fb) {
     if (fa.y == fb.y && fa.y != 0u) return (int32_t)fa.y > 0;
     return (fa.x & (fb.x >> 16)) != 0u && (fb.x & (fa.x >> 16)) != 0u;
@@ -208,7 +209,7 @@ inline bool materials_active(const phys_world* w) { return w->body_materials_set
 // Buckets are numbered BRICK-major: a brick is 4 x 4 x 4 cells = 64 consecutive buckets (the low two bits of each
 // coordinate interleaved), bricks x-fastest. So the bodies of a brick are one contiguous run of the bucket-sorted
 // arrays, which is what lets one workgroup stage a brick and its half-shell halo in LDS (k_find_pairs_brick).
-// (struct GridShape: world.hpp)
+// (struct GridShape: setup.hpp)
 __host__ __device__ __forceinline__ uint32_t grid_bucket_masked(uint32_t x, uint32_t y, uint32_t z, const GridShape& g) {
     const uint32_t brick = ((((z >> 2) << g.sy) | (y >> 2)) << g.sx) | (x >> 2);
     const uint32_t local = (x & 1u) | ((y & 1u) << 1) | ((z & 1u) << 2) | ((x & 2u) << 2) | ((y & 2u) << 3) | ((z & 2u) << 4);
@@ -238,6 +239,37 @@ __device__ __forceinline__ uint32_t cluster_row_owner(uint32_t a, uint32_t home_
     return ((a * 2654435761u) >> 7) % clusters;
 }
 
+// the step counters into the pinned host mirror w->h_counters, and wait: the one copy-and-wait of every read-out call
+inline int32_t fetch_counters(phys_world* w) {
+    PHYS_HIP_TRY(hipMemcpyAsync(w->h_counters, w->counters.p, sizeof(StepCounters), hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    return PHYS_OK;
+}
+
+// The one drain of phys_get_contact_events and phys_get_trigger_events (the rules: readout.hpp drain_rules). cursor_dev: the
+// 64-bit count of events raised since the last drain; buf_dev: the first `capacity` of them. Only the cursor word is cleared,
+// ordered on the world's stream in front of the next update's kernels.
+template <class Record>
+int32_t drain_events(phys_world* w, void* cursor_dev, uint64_t capacity, const void* buf_dev, Record* out, uint64_t cap, uint64_t* n,
+                     uint64_t* n_dropped, const char* too_many) {
+    unsigned long long cursor = 0;
+    PHYS_HIP_TRY(hipMemcpyAsync(&cursor, cursor_dev, sizeof(cursor), hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    const EventDrain d = drain_rules(cursor, capacity, out != nullptr, cap);
+    *n = d.stored;
+    if (n_dropped) *n_dropped = d.dropped;
+    if (d.count_only) return PHYS_OK;  // the buffer stays
+    if (d.too_many) return fail(PHYS_ERR_CAPACITY, too_many);
+    if (d.stored) {
+        PHYS_HIP_TRY(hipMemcpyAsync(out, buf_dev, d.stored * sizeof(Record), hipMemcpyDeviceToHost, w->stream));
+        PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+        // device order is arbitrary; a read-out convenience as in phys_get_manifolds
+        std::sort(out, out + d.stored, [](const Record& x, const Record& y) { return event_before(x, y); });
+    }
+    if (d.clear_cursor) PHYS_HIP_TRY(hipMemsetAsync(cursor_dev, 0, sizeof(cursor), w->stream));
+    return PHYS_OK;
+}
+
 // integrate.hip
 void launch_step_full(phys_world* w, float dt, bool gravity, bool constraints = false);  // constraints: entity 0 += J^T lambda of this update
 void launch_step_velocity_aabb(phys_world* w, float dt, bool gravity, bool zero_step, bool constraints = false);  // zero_step: also zero the per-step state
@@ -248,8 +280,7 @@ void launch_apply_force_one(phys_world* w, uint32_t body, int mode, const float 
 void launch_instance_matrices(phys_world* w, float* d_out);
 
 // broadphase.hip
-int32_t collision_alloc(phys_world* w);
-void grid_plan(phys_world* w, const float* host_pos, const float* host_half_extent);  // table size and its split over the axes
+int32_t collision_alloc(phys_world* w);  // buffers for setup.hpp collision_sizes; the table of grid_plan is set before
 void zero_step_state(phys_world* w, bool including_extent);  // ONE memset: counters + bucket counts + colouring state
 void launch_broadphase(phys_world* w, const PairPlan& plan);
 void build_sorted_grid(phys_world* w);  // bucket_start / sorted_ids / sorted_box from the current AABBs (bucket counts zeroed)
@@ -313,7 +344,7 @@ void launch_exclusive_scan(phys_world* w, uint32_t* in, uint32_t count, uint32_t
                            StepCounters* ctr = nullptr /* ... summed into n_used_buckets */, int prof_stage = -1);
 bool scan_is_one_launch(uint32_t count);  // ... in which case zero_in leaves the counters zeroed behind the scan
 size_t scan_scratch_words(uint32_t count);
-// cluster.hip: clusters / slots of this update from the hint (dynamic clusters); false: no cluster step in this update
+// cluster.hip: clusters / slots of this update (setup.hpp plan_dynamic_clusters) while the dealt homes last; false: no cluster step in this update
 bool cluster_plan_dynamic(phys_world* w, const StepHint& h, const DebugSwitches& dbg);
 void launch_solve_cluster(phys_world* w, const SolverPlan& plan, void* row_all, uint64_t cap, float friction, const float* inertia,
                           uint32_t stride, bool diag);

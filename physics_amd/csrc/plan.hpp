@@ -2,6 +2,8 @@
 // (PlanInputs, StepHint, DebugSwitches). Nothing of HIP in here: a host compiler reads it alone, and tests/cpp/plan_probe.cpp
 // holds every threshold to a table (tests/test_plan_cpu.py). The launch_* functions take their part of the plan and only
 // launch. Every path gives the same bits: a plan is a matter of speed, never of correctness.
+// What is decided once per body set, static set or constraint list - and the one per-update decision that needs the cluster
+// geometry, plan_dynamic_clusters - is in setup.hpp, in the same style.
 #pragma once
 #include <algorithm>
 #include <cstddef>

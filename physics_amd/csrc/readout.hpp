@@ -1,0 +1,135 @@
+// readout.hpp — what the read-out calls compute on the host once the bytes are there: sorted pair lists, the (a, b) order of
+// manifolds, the rules and the order of an event drain, the trigger occupancy as CSR, and phys_sync's error text. Host-only like
+// setup.hpp (no HIP, no phys_world), held to tests/cpp/setup_probe.cpp. The callers keep the copies and the clears.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "setup.hpp"
+
+namespace phys {
+
+// m pairs {i, j} in device order -> the first min(m, cap) of them in (i, j) order. A convenience of the read-out calls
+// (phys_broadphase, phys_get_cross_pairs); the per-step pipeline never sorts.
+inline void sort_pairs(const uint32_t* raw, uint64_t m, uint32_t* out, uint64_t cap) {
+    std::vector<uint64_t> keys(m);
+    for (uint64_t k = 0; k < m; ++k) keys[k] = ((uint64_t)raw[2 * k] << 32) | raw[2 * k + 1];
+    std::sort(keys.begin(), keys.end());
+    for (uint64_t k = 0; k < m && k < cap; ++k) {
+        out[2 * k] = (uint32_t)(keys[k] >> 32);
+        out[2 * k + 1] = (uint32_t)keys[k];
+    }
+}
+
+// the permutation that puts m manifolds in (a, b) order; a and b are words 0 and 1 of records `stride` words apart (pairs are
+// unique, so (a, b) fixes it: phys_get_manifolds and phys_get_contact_impulses agree)
+inline std::vector<uint64_t> manifold_order(const uint32_t* ab, size_t stride, uint64_t m) {
+    std::vector<uint64_t> order(m);
+    for (uint64_t k = 0; k < m; ++k) order[k] = k;
+    std::sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) {
+        return ab[stride * x] < ab[stride * y] || (ab[stride * x] == ab[stride * y] && ab[stride * x + 1] < ab[stride * y + 1]);
+    });
+    return order;
+}
+
+// the order events are handed out in (device order is arbitrary)
+inline bool event_before(const phys_contact_event& x, const phys_contact_event& y) {
+    if (x.step != y.step) return x.step < y.step;
+    if (x.kind != y.kind) return x.kind < y.kind;
+    if (x.body_a != y.body_a) return x.body_a < y.body_a;
+    return x.body_b < y.body_b;
+}
+inline bool event_before(const phys_trigger_event& x, const phys_trigger_event& y) {
+    if (x.step != y.step) return x.step < y.step;
+    if (x.kind != y.kind) return x.kind < y.kind;
+    if (x.trigger != y.trigger) return x.trigger < y.trigger;
+    return x.body < y.body;
+}
+
+// The rules of an event drain (phys_get_contact_events, phys_get_trigger_events), from the cursor - events raised since the
+// last drain - and the capacity the device keeps: a count query (no buffer, cap 0) leaves everything as it is; more events
+// stored than cap drains nothing; else the stored records are copied out, and only the cursor word is cleared (if non-zero).
+struct EventDrain {
+    uint64_t stored = 0, dropped = 0;
+    bool count_only = false;  // nothing is copied, nothing cleared
+    bool too_many = false;    // PHYS_ERR_CAPACITY: nothing is copied, nothing cleared
+    bool clear_cursor = false;
+};
+inline EventDrain drain_rules(uint64_t cursor, uint64_t capacity, bool have_out, uint64_t cap) {
+    EventDrain d;
+    d.stored = cursor < capacity ? cursor : capacity;
+    d.dropped = cursor - d.stored;
+    d.count_only = !have_out && cap == 0;
+    d.too_many = !d.count_only && d.stored > cap;
+    d.clear_cursor = !d.count_only && !d.too_many && cursor != 0;
+    return d;
+}
+
+// Trigger occupancy, plane-major bit matrix (word wd of body i at bits[wd * n_bodies + i], bit k % 32 of word k / 32 is trigger
+// k) -> CSR: offsets[T + 1] always; the body ids of every trigger, ascending, when they fit in cap (the return value). Bits of
+// triggers >= T (padding of the last word) are ignored.
+inline bool trigger_bits_to_csr(const uint32_t* bits, uint64_t words, uint64_t n_bodies, uint64_t T, uint64_t cap, uint64_t* offsets,
+                                uint32_t* ids) {
+    std::vector<uint64_t> count((size_t)T, 0);
+    for (uint64_t wd = 0; wd < words; ++wd)
+        for (uint64_t i = 0; i < n_bodies; ++i)
+            for (uint32_t m = bits[(size_t)(wd * n_bodies + i)]; m; m &= m - 1u) {
+                const uint64_t k = wd * 32u + (uint32_t)__builtin_ctz(m);
+                if (k < T) count[(size_t)k]++;
+            }
+    uint64_t run = 0;
+    for (uint64_t k = 0; k < T; ++k) { offsets[k] = run; run += count[(size_t)k]; }
+    offsets[T] = run;
+    if (run > cap) return false;
+    std::vector<uint64_t> at(offsets, offsets + T);
+    for (uint64_t wd = 0; wd < words; ++wd)
+        for (uint64_t i = 0; i < n_bodies; ++i)  // bodies ascending: every list ascending
+            for (uint32_t m = bits[(size_t)(wd * n_bodies + i)]; m; m &= m - 1u) {
+                const uint64_t k = wd * 32u + (uint32_t)__builtin_ctz(m);
+                if (k < T) ids[at[(size_t)k]++] = (uint32_t)i;
+            }
+    return true;
+}
+
+// phys_sync: the overflow bits raised since the last call (kOvf*) and the eight debug words -> the code and the text. One error
+// per call, in this precedence: corrupt row, hand-off time-out (with k_solve_cluster's note when debug[0] == 0xC1), colours,
+// halo, colour table, then pairs / manifolds.
+struct SyncError {
+    int32_t code = PHYS_OK;
+    std::string message;
+};
+inline SyncError sync_error(uint32_t bits, const uint32_t g[8]) {
+    if (bits & kOvfCorruptRow)
+        return {PHYS_ERR_HIP, "internal error: a solver row names no body of this world and was refused (row " +
+                              std::to_string(g[0]) + ": a " + std::to_string(g[1]) + ", b " + std::to_string(g[2]) + ", points " +
+                              std::to_string(g[3]) + "; colour " + std::to_string(g[6]) + " rows [" + std::to_string(g[4]) + ", " +
+                              std::to_string(g[5]) + "), tile base " + std::to_string(g[7]) + ")"};
+    if ((bits & kOvfHandoff) && g[0] == 0xC1u)  // what the first lane of k_solve_cluster to give up was waiting for
+        return {PHYS_ERR_HIP, "contact solver hand-off timed out (k_solve_cluster) in a step since the last phys_sync; velocities "
+                              "are invalid from that step on. First lane to give up: cluster " + std::to_string(g[1] & 0xFFFFu) + " of " + std::to_string(g[1] >> 16) + ", row " +
+                              std::to_string(g[2]) + ", bodies " + std::to_string(g[3]) + " / " + std::to_string(g[4]) +
+                              ", tickets " + std::to_string(g[5] & 0xFFFFu) + " / " + std::to_string(g[5] >> 16) + ", waiting A/B " +
+                              std::to_string(g[6] & 1u) + "/" + std::to_string((g[6] >> 1) & 1u) + ", modes " +
+                              std::to_string((g[6] >> 4) & 3u) + "/" + std::to_string((g[6] >> 8) & 3u) + ", iteration " +
+                              std::to_string((g[7] >> 8) & 0xFFu) + ", colour " + std::to_string(g[7] & 0xFFu) +
+                              ". If other work shares this GPU with phys_update, create the world WITHOUT PHYS_FLAG_EXCLUSIVE_GPU"};
+    if (bits & kOvfHandoff)
+        return {PHYS_ERR_HIP, "contact solver hand-off timed out (k_solve_flow) in a step since the last phys_sync; "
+                              "velocities are invalid from that step on"};
+    if (bits & kOvfColors)
+        return {PHYS_ERR_CAPACITY, "a body has more than 64 contact manifolds (PHYS_MAX_COLORS): the contact solve of "
+                                   "that step was skipped. This limit is not configurable"};
+    if (bits & kOvfHalo)
+        return {PHYS_ERR_CAPACITY, "halo record / cross-pair capacity exceeded in a step since the last phys_sync"};
+    if (bits & kOvfColorTable)
+        return {PHYS_ERR_CAPACITY, "the persistent colour table is full (a look-up or an insert gave up after thousands of "
+                                   "slots): the contact solve of that step was skipped. Raise phys_config.max_manifolds"};
+    if (bits)
+        return {PHYS_ERR_CAPACITY, "pair / manifold capacity exceeded in a step since the last phys_sync (the contact "
+                                   "solve of that step was skipped): raise phys_config.max_pairs / max_manifolds"};
+    return {};
+}
+
+}  // namespace phys

@@ -15,8 +15,6 @@
 //                    the wave totals); each lane writes its body's pairs with ascending static ids
 //   So the list is ordered by (body, static) and its bits never depend on timing: no atomic decides a position.
 #include <algorithm>
-#include <cmath>
-#include <cstring>
 #include <vector>
 
 #include "kernels.hpp"
@@ -26,18 +24,7 @@ namespace phys {
 namespace {
 
 constexpr int kStThreads = 256;
-constexpr uint32_t kStMaxDim = 1024;    // cells per axis: three 10-bit cell coordinates pack into one word
-constexpr uint32_t kStLargeCells = 64;  // a static covering more cells than this is tested by every body instead
-
-// cell of coordinate x along one axis, clamped to [0, dim - 1] (NaN: cell 0). Host and device run these operations
-// alike (no contraction: -ffp-contract=off), and the result is monotone in x.
-__host__ __device__ __forceinline__ uint32_t st_cell(float x, float org, float inv, uint32_t dim) {
-    float t = floorf((x - org) * inv);
-    if (!(t >= 0.0f)) t = 0.0f;
-    const float top = (float)(dim - 1u);
-    t = t > top ? top : t;
-    return (uint32_t)t;
-}
+// (kStMaxDim, kStLargeCells and st_cell, which the host build and st_visit both run: setup.hpp)
 
 struct StaticGrid {
     const float4* __restrict__ box;  // 2 per static: {lo, packed first cell} {hi, -}
@@ -146,7 +133,8 @@ StaticGrid static_grid(const phys_world* w) {
 
 }  // namespace
 
-// Replaces the static set (arguments checked by the caller). Builds the records and the grid on the host.
+// Replaces the static set (arguments checked by the caller). The records and the grid are built on the host (setup.hpp
+// build_static_set); here they are uploaded and committed.
 int32_t static_set(phys_world* w, uint64_t n, const float* pos, const float* rot, const uint32_t* shape, const float* he) {
     hipStream_t s = w->stream;
     PHYS_HIP_TRY(hipStreamSynchronize(s));  // no update in flight reads the buffers replaced below
@@ -158,132 +146,29 @@ int32_t static_set(phys_world* w, uint64_t n, const float* pos, const float* rot
     w->st_dim[0] = w->st_dim[1] = w->st_dim[2] = 0;
     w->static_pairs_sized = false;
     if (n == 0) return PHYS_OK;
-    const float margin = w->cfg.contact_margin;
-    std::vector<float> geo(16 * n, 0.0f), rc(12 * n, 0.0f), box(8 * n, 0.0f);
-    std::vector<float> lo(3 * n), hi(3 * n), edge(n);
-    for (uint64_t k = 0; k < n; ++k) {
-        quat q;
-        if (rot) { q.i = rot[4 * k]; q.j = rot[4 * k + 1]; q.k = rot[4 * k + 2]; q.w = rot[4 * k + 3]; }
-        else { q.i = 0.0f; q.j = 0.0f; q.k = 0.0f; q.w = 1.0f; }
-        const v3 c = v3_make(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]);
-        const v3 h = v3_make(he[3 * k], he[3 * k + 1], he[3 * k + 2]);
-        const uint32_t id = PHYS_STATIC_ID_BIT | (uint32_t)k;
-        const float g[16] = {c.x, c.y, c.z, 0.0f, q.i, q.j, q.k, q.w, h.x, h.y, h.z, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        std::memcpy(&geo[16 * k], g, sizeof(g));
-        std::memcpy(&geo[16 * k + 3], &shape[k], 4);
-        std::memcpy(&rc[12 * k], g, 48);
-        std::memcpy(&rc[12 * k + 3], &shape[k], 4);
-        std::memcpy(&rc[12 * k + 11], &id, 4);
-        if (shape[k] == PHYS_SHAPE_CAPSULE) w->static_capsules = true;
-        // fattened by the contact margin like the bodies' boxes (a capsule's from its segment and radius, collide.h): a pair
-        // is a candidate wherever body-body pairs would be
-        const aabb_t b = body_aabb(c, q, h, shape[k], margin);
-        lo[3 * k] = b.lo.x; lo[3 * k + 1] = b.lo.y; lo[3 * k + 2] = b.lo.z;
-        hi[3 * k] = b.hi.x; hi[3 * k + 1] = b.hi.y; hi[3 * k + 2] = b.hi.z;
-        edge[k] = std::max(b.hi.x - b.lo.x, std::max(b.hi.y - b.lo.y, b.hi.z - b.lo.z));
-    }
-    // cell edge: the median extent (a few huge statics do not coarsen the grid; they go to the large list)
-    std::vector<float> sorted_edge(edge);
-    std::nth_element(sorted_edge.begin(), sorted_edge.begin() + n / 2, sorted_edge.end());
-    double cell = sorted_edge[n / 2];
-    if (!(cell > 0.0) || !std::isfinite(cell)) cell = 1.0;
-    auto covered = [&](uint64_t k, double cl) {  // cells of static k at edge cl (an upper bound: two partial cells per axis)
-        double cells = 1.0;
-        for (int a = 0; a < 3; ++a) cells *= std::floor((double)(hi[3 * k + a] - lo[3 * k + a]) / cl) + 2.0;
-        return cells;
-    };
-    std::vector<uint8_t> is_large(n, 0);
-    std::vector<uint32_t> large;
-    double blo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, bhi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    uint64_t n_small = 0;
-    for (uint64_t k = 0; k < n; ++k) {
-        if (covered(k, cell) > (double)kStLargeCells) { is_large[k] = 1; large.push_back((uint32_t)k); continue; }
-        ++n_small;
-        for (int a = 0; a < 3; ++a) { blo[a] = std::min(blo[a], (double)lo[3 * k + a]); bhi[a] = std::max(bhi[a], (double)hi[3 * k + a]); }
-    }
-    std::vector<uint32_t> cell_start(2, 0), cell_ids;
-    uint32_t dim[3] = {0, 0, 0};
-    float org[3] = {0.0f, 0.0f, 0.0f}, inv = 0.0f;
-    if (n_small) {
-        // at most kStMaxDim cells per axis and a few cells per small static in all: far-flung statics coarsen the grid
-        const double max_cells = std::max<double>(4096.0, 8.0 * (double)n_small);
-        for (int guard = 0; guard < 200; ++guard) {
-            double total = 1.0;
-            bool fits = true;
-            for (int a = 0; a < 3; ++a) {
-                const double d = std::floor((bhi[a] - blo[a]) / cell) + 1.0;
-                if (d > (double)kStMaxDim) fits = false;
-                total *= d;
-            }
-            if (fits && total <= max_cells) break;
-            cell *= 1.25;
-        }
-        inv = (float)(1.0 / cell);
-        for (int a = 0; a < 3; ++a) {
-            org[a] = (float)blo[a];
-            // the span at the float cell edge, +1 for rounding; clamped by st_cell anyway
-            dim[a] = (uint32_t)std::min<double>(kStMaxDim, std::floor((bhi[a] - blo[a]) * (double)inv) + 2.0);
-        }
-        const uint64_t cells = (uint64_t)dim[0] * dim[1] * dim[2];
-        std::vector<uint32_t> cnt(cells + 1, 0), range(6 * n, 0);
-        for (uint64_t k = 0; k < n; ++k) {
-            if (is_large[k]) continue;
-            uint32_t* r = &range[6 * k];
-            for (int a = 0; a < 3; ++a) {
-                r[a] = st_cell(lo[3 * k + a], org[a], inv, dim[a]);
-                r[3 + a] = st_cell(hi[3 * k + a], org[a], inv, dim[a]);
-            }
-            const uint32_t p = r[0] | (r[1] << 10) | (r[2] << 20);
-            std::memcpy(&box[8 * k + 3], &p, 4);
-            for (uint32_t z = r[2]; z <= r[5]; ++z)
-                for (uint32_t y = r[1]; y <= r[4]; ++y)
-                    for (uint32_t x = r[0]; x <= r[3]; ++x) cnt[(z * dim[1] + y) * dim[0] + x]++;
-        }
-        cell_start.assign(cells + 1, 0);
-        for (uint64_t c = 0; c < cells; ++c) cell_start[c + 1] = cell_start[c] + cnt[c];
-        cell_ids.assign(cell_start[cells] ? cell_start[cells] : 1, 0);
-        std::vector<uint32_t> cur(cell_start.begin(), cell_start.end() - 1);
-        for (uint64_t k = 0; k < n; ++k) {  // ascending k: every cell's list is ascending
-            if (is_large[k]) continue;
-            const uint32_t* r = &range[6 * k];
-            for (uint32_t z = r[2]; z <= r[5]; ++z)
-                for (uint32_t y = r[1]; y <= r[4]; ++y)
-                    for (uint32_t x = r[0]; x <= r[3]; ++x) cell_ids[cur[(z * dim[1] + y) * dim[0] + x]++] = (uint32_t)k;
-        }
-    }
-    for (uint64_t k = 0; k < n; ++k) {
-        box[8 * k] = lo[3 * k]; box[8 * k + 1] = lo[3 * k + 1]; box[8 * k + 2] = lo[3 * k + 2];
-        box[8 * k + 4] = hi[3 * k]; box[8 * k + 5] = hi[3 * k + 1]; box[8 * k + 6] = hi[3 * k + 2];
-    }
-    if (cell_ids.empty()) cell_ids.assign(1, 0);
-    if (large.empty()) large.assign(1, 0);  // (never read: st_n_large is 0)
-    PHYS_HIP_TRY(w->st_geo.resize(16 * n));
-    PHYS_HIP_TRY(w->st_rc.resize(12 * n));
-    PHYS_HIP_TRY(w->st_box.resize(8 * n));
-    PHYS_HIP_TRY(w->st_cell_start.resize(cell_start.size()));
-    PHYS_HIP_TRY(w->st_cell_ids.resize(cell_ids.size()));
-    PHYS_HIP_TRY(w->st_large.resize(large.size()));
-    // every static starts with the default collision filter (phys_set_static_filters changes them)
-    std::vector<uint32_t> filt(2 * n);
-    for (uint64_t k = 0; k < n; ++k) { filt[2 * k] = kFilterDefaultWord; filt[2 * k + 1] = 0u; }
-    PHYS_HIP_TRY(w->st_filt.resize(2 * n));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->st_filt.p, filt.data(), 4 * filt.size(), hipMemcpyHostToDevice, s));
-    // ... and the default material {cfg.friction, 0} (phys_set_static_materials)
-    std::vector<float> mat(2 * n, 0.0f);
-    for (uint64_t k = 0; k < n; ++k) mat[2 * k] = w->cfg.friction;
-    PHYS_HIP_TRY(w->st_mat.resize(2 * n));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->st_mat.p, mat.data(), 4 * mat.size(), hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->st_geo.p, geo.data(), 4 * geo.size(), hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->st_rc.p, rc.data(), 4 * rc.size(), hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->st_box.p, box.data(), 4 * box.size(), hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->st_cell_start.p, cell_start.data(), 4 * cell_start.size(), hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->st_cell_ids.p, cell_ids.data(), 4 * cell_ids.size(), hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipMemcpyAsync(w->st_large.p, large.data(), 4 * large.size(), hipMemcpyHostToDevice, s));
-    PHYS_HIP_TRY(hipStreamSynchronize(s));  // staging vectors die here
-    w->st_n_large = is_large.empty() ? 0u : (uint32_t)std::count(is_large.begin(), is_large.end(), (uint8_t)1);
-    for (int a = 0; a < 3; ++a) { w->st_org[a] = org[a]; w->st_dim[a] = dim[a]; }
-    w->st_inv_cell = inv;
-    if (n_small == 0) w->st_dim[0] = w->st_dim[1] = w->st_dim[2] = 0;
+    const StaticSet set = build_static_set(n, pos, rot, shape, he, w->cfg.contact_margin, w->cfg.friction);
+    w->static_capsules = set.capsules;
+    PHYS_HIP_TRY(w->st_geo.resize(set.geo.size()));
+    PHYS_HIP_TRY(w->st_rc.resize(set.rc.size()));
+    PHYS_HIP_TRY(w->st_box.resize(set.box.size()));
+    PHYS_HIP_TRY(w->st_cell_start.resize(set.cell_start.size()));
+    PHYS_HIP_TRY(w->st_cell_ids.resize(set.cell_ids.size()));
+    PHYS_HIP_TRY(w->st_large.resize(set.large.size()));
+    auto up = [&](auto& dst, const auto& src) { return hipMemcpyAsync(dst.p, src.data(), 4 * src.size(), hipMemcpyHostToDevice, s); };
+    PHYS_HIP_TRY(w->st_filt.resize(set.filt.size()));
+    PHYS_HIP_TRY(up(w->st_filt, set.filt));
+    PHYS_HIP_TRY(w->st_mat.resize(set.mat.size()));
+    PHYS_HIP_TRY(up(w->st_mat, set.mat));
+    PHYS_HIP_TRY(up(w->st_geo, set.geo));
+    PHYS_HIP_TRY(up(w->st_rc, set.rc));
+    PHYS_HIP_TRY(up(w->st_box, set.box));
+    PHYS_HIP_TRY(up(w->st_cell_start, set.cell_start));
+    PHYS_HIP_TRY(up(w->st_cell_ids, set.cell_ids));
+    PHYS_HIP_TRY(up(w->st_large, set.large));
+    PHYS_HIP_TRY(hipStreamSynchronize(s));  // the staged set dies here
+    w->st_n_large = set.n_large;
+    for (int a = 0; a < 3; ++a) { w->st_org[a] = set.org[a]; w->st_dim[a] = set.dim[a]; }
+    w->st_inv_cell = set.inv_cell;
     w->n_static = n;  // committed last
     return PHYS_OK;
 }

@@ -240,28 +240,8 @@ int32_t phys_get_trigger_events(phys_world* w, phys_trigger_event* out, uint64_t
     if (!n) return fail(PHYS_ERR_INVALID_ARG, "phys_get_trigger_events: null n");
     if (cap && !out) return fail(PHYS_ERR_INVALID_ARG, "phys_get_trigger_events: null out with cap > 0");
     if (w->tg_capacity == 0) return fail(PHYS_ERR_UNSUPPORTED, "trigger events are off (phys_trigger_events_enable)");
-    unsigned long long cursor = 0;
-    PHYS_HIP_TRY(hipMemcpyAsync(&cursor, w->tg_cursor.p, sizeof(cursor), hipMemcpyDeviceToHost, w->stream));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    const uint64_t stored = cursor < w->tg_capacity ? cursor : w->tg_capacity;
-    *n = stored;
-    if (n_dropped) *n_dropped = cursor - stored;
-    if (!out && cap == 0) return PHYS_OK;  // count query: the buffer stays
-    if (stored > cap) return fail(PHYS_ERR_CAPACITY, "phys_get_trigger_events: more events stored than cap (*n says how many); nothing was drained");
-    if (stored) {
-        PHYS_HIP_TRY(hipMemcpyAsync(out, w->tg_buf.p, stored * sizeof(phys_trigger_event), hipMemcpyDeviceToHost, w->stream));
-        PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-        // device order is arbitrary; a read-out convenience as in phys_get_contact_events
-        std::sort(out, out + stored, [](const phys_trigger_event& x, const phys_trigger_event& y) {
-            if (x.step != y.step) return x.step < y.step;
-            if (x.kind != y.kind) return x.kind < y.kind;
-            if (x.trigger != y.trigger) return x.trigger < y.trigger;
-            return x.body < y.body;
-        });
-    }
-    // ordered on the world's stream in front of the next update's kernel
-    if (cursor) PHYS_HIP_TRY(hipMemsetAsync(w->tg_cursor.p, 0, sizeof(cursor), w->stream));
-    return PHYS_OK;
+    return drain_events(w, w->tg_cursor.p, w->tg_capacity, w->tg_buf.p, out, cap, n, n_dropped,
+                        "phys_get_trigger_events: more events stored than cap (*n says how many); nothing was drained");
 }
 
 int32_t phys_get_trigger_overlaps(phys_world* w, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out) {
@@ -276,24 +256,8 @@ int32_t phys_get_trigger_overlaps(phys_world* w, uint64_t cap, uint64_t* offsets
     std::vector<uint32_t> h((size_t)(words * nb));
     PHYS_HIP_TRY(hipMemcpyAsync(h.data(), w->tg_bits.p, 4 * h.size(), hipMemcpyDeviceToHost, w->stream));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    std::vector<uint64_t> count((size_t)T, 0);
-    for (uint64_t wd = 0; wd < words; ++wd)
-        for (uint64_t i = 0; i < nb; ++i)
-            for (uint32_t m = h[(size_t)(wd * nb + i)]; m; m &= m - 1u) {
-                const uint64_t k = wd * kTgTile + (uint32_t)__builtin_ctz(m);
-                if (k < T) count[(size_t)k]++;
-            }
-    uint64_t run = 0;
-    for (uint64_t k = 0; k < T; ++k) { offsets_out[k] = run; run += count[(size_t)k]; }
-    offsets_out[T] = run;
-    if (run > cap) return fail(PHYS_ERR_CAPACITY, "phys_get_trigger_overlaps: the ids need offsets_out[n] slots, more than cap");
-    std::vector<uint64_t> at(offsets_out, offsets_out + T);
-    for (uint64_t wd = 0; wd < words; ++wd)
-        for (uint64_t i = 0; i < nb; ++i)  // bodies ascending: every list ascending
-            for (uint32_t m = h[(size_t)(wd * nb + i)]; m; m &= m - 1u) {
-                const uint64_t k = wd * kTgTile + (uint32_t)__builtin_ctz(m);
-                if (k < T) ids_out[at[(size_t)k]++] = (uint32_t)i;
-            }
+    if (!trigger_bits_to_csr(h.data(), words, nb, T, cap, offsets_out, ids_out))
+        return fail(PHYS_ERR_CAPACITY, "phys_get_trigger_overlaps: the ids need offsets_out[n] slots, more than cap");
     return PHYS_OK;
 }
 

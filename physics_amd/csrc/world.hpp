@@ -14,12 +14,9 @@
 
 #include "../../include/physics_hip.h"
 #include "plan.hpp"
+#include "setup.hpp"
 
 namespace phys {
-
-constexpr uint32_t kClusterDynamicPeriod = 8;  // cluster steps between two deals of the dynamic homes (a body that became active
-                                               // since has none and is served as another cluster's body: slower, never wrong)
-constexpr uint32_t kClusterMaxSlots = 2496;    // bodies per cluster whose {v, w, x, I^-1} fit one CU's LDS (64 B each: 156 KiB; 13-bit slot field)
 
 void set_error(const std::string& msg);
 const char* get_error();
@@ -31,6 +28,12 @@ const char* get_error();
             phys::set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                     \
             return PHYS_ERR_HIP;                                                                    \
         }                                                                                           \
+    } while (0)
+// ... and for a call of the library's own that answers a PHYS_* code (which has set the error text)
+#define PHYS_TRY(expr)                                                                              \
+    do {                                                                                            \
+        const int32_t _rc = (expr);                                                                 \
+        if (_rc != PHYS_OK) return _rc;                                                             \
     } while (0)
 
 // host side of every extern "C" entry point: the error text and the code it returns with ...
@@ -74,62 +77,7 @@ struct DevBuf {
     void point_at(T* ptr, size_t count) { free(); p = ptr; n = count; view = true; }
 };
 
-// device-side counters of the collision pipeline (one 256-B block, zeroed per step by one memset)
-struct StepCounters {
-    // the first two words are reserved TOGETHER by the narrow phase: one 64-bit atomic per workgroup trip adds the trip's
-    // manifolds to the low word and its uncoloured manifolds to the high one (same-address atomics serialise chip-wide;
-    // two of them per trip was two places in that queue)
-    uint32_t n_manifolds;    // manifolds written (body-body + ground)
-    uint32_t unc_count[3];   // colouring rounds: length of the list of uncoloured manifolds read / written / cleared (rotating)
-    uint32_t n_pairs;        // candidate pairs written
-    uint32_t n_contacts;     // contact points
-    uint32_t n_uncolored;    // manifolds still uncoloured (colouring loop)
-    uint32_t n_colors;       // colours in use
-    uint32_t color_rounds;
-    uint32_t overflow;       // kOvf* bits (below)
-    uint32_t n_halo;         // halo records packed
-    uint32_t n_cross_pairs;
-    uint32_t n_ground_manifolds;
-    uint32_t flow_ticket;    // k_solve_flow: next (iteration, row chunk) item to hand to a workgroup
-    uint32_t n_grid_ovf;     // slot grid: bodies that found their bucket's four slots taken
-    uint32_t n_active;       // owned bodies with at least one manifold in this update (dynamic clusters, cluster.hip)
-    uint32_t n_used_buckets; // buckets of the sorted grid holding at least one body (k_cell_assign)
-    uint32_t max_region;     // k_find_pairs_brick: most records in the region of one brick (sizes the LDS stage of later updates)
-    uint32_t n_new_manifolds;  // manifolds that kept no colour in this update (= the colouring's work; never counted down)
-    uint32_t n_static_pairs;      // (body, static) pairs of this update, all of them (k_static_fill; only max_static_pairs are stored)
-    uint32_t n_static_manifolds;  // manifolds against a static collider (subset of n_manifolds)
-    uint32_t cluster_arrived[2][8];  // k_solve_cluster, per attempt: workgroups that have begun (eight counters: same-address
-                                     // atomics serialise chip-wide) ...
-    uint32_t cluster_state[2];       // ... and the launch's one decision: 0 undecided, 1 go (all are resident), 2 called off
-    uint32_t color_count[kMaxColors];  // manifolds per colour
-    uint32_t color_start[kMaxColors + 1];
-    // LAST member: survives the per-step reset (only the bytes before it are zeroed), so a wave issues the
-    // same-address atomicMax only when it RAISES the bound. It is a running upper bound of the largest
-    // fattened-AABB edge (float bits; positive floats order as uints), re-derived from zero every 32 steps.
-    // Any upper bound is a valid grid cell size: the pair SET does not depend on it.
-    alignas(16) uint32_t max_extent_bits;
-    // Every overflow bit ever raised since the host last looked (phys_sync reports and clears it). `overflow` above
-    // is per step - the first kernel of the next step zeroes it - so a capacity miss or a hand-off timeout in an
-    // EARLY step of a phys_update_n batch would otherwise be gone by the time the host synchronises. Zeroed by
-    // neither the per-step reset nor the extent restart (both stop short of it).
-    uint32_t sticky_overflow;
-    uint32_t n_ghosts;   // ghost slots filled by the last phys_halo_unpack_ghosts (set before the update: not part of the per-step reset)
-    uint32_t n_halo_low; // neighbour exchange: records of the LOW-face block (n_halo then counts the high-face block; the stats add them)
-    uint32_t debug[8];  // what a kernel that refused a corrupt row saw (overflow bit 5); never read by device code
-};
-static_assert(offsetof(StepCounters, n_manifolds) % 8 == 0 && offsetof(StepCounters, unc_count) == offsetof(StepCounters, n_manifolds) + 4,
-              "n_manifolds | unc_count[0] are one aligned 64-bit word");
-// the bits of StepCounters::overflow / sticky_overflow (phys_stats.overflow shows them; phys_sync turns them into errors)
-constexpr uint32_t kOvfPairs = 1u;        // bit 0: candidate pairs or (body, static) pairs beyond their capacity
-constexpr uint32_t kOvfManifolds = 2u;    // bit 1: manifolds beyond max_manifolds
-constexpr uint32_t kOvfColors = 4u;       // bit 2: more than kMaxColors manifolds at one body
-constexpr uint32_t kOvfHalo = 8u;         // bit 3: halo records, ghosts or cross pairs beyond their capacity
-constexpr uint32_t kOvfHandoff = 16u;     // bit 4: solver hand-off timeout
-constexpr uint32_t kOvfCorruptRow = 32u;  // bit 5: corrupt solver row refused (StepCounters::debug says which)
-constexpr uint32_t kOvfColorTable = 64u;  // bit 6: colour table walk given up
-constexpr size_t kCountersStepResetBytes = offsetof(StepCounters, max_extent_bits);
-constexpr size_t kCountersExtentResetBytes = offsetof(StepCounters, sticky_overflow);
-
+// (struct StepCounters and its kOvf* bits: setup.hpp)
 // raise overflow bits: this step's word (the solver kernels of the step look at it) and the sticky one
 __device__ __forceinline__ void flag_overflow(StepCounters* ctr, uint32_t bits) {
     atomicOr(&ctr->overflow, bits);
@@ -174,24 +122,12 @@ struct ProfScope {
     ~ProfScope() { if (p.on) p.end(s); }
 };
 
-// split of the broad phase's bucket table over the three axes (kernels.hpp: grid_bucket)
-struct GridShape {
-    uint32_t mx = 7, my = 7, mz = 7;  // per-axis masks: cells per axis - 1 (each >= 3)
-    uint32_t sx = 1, sy = 1;          // bits of the brick coordinates along x and y (= axis bits - 2)
-};
-
 // worlds alive per device in this process (abi.hip): two of them step on two streams, i.e. beside each other
 int worlds_on_device(int device);
 // PHYS_FLAG_EXCLUSIVE_GPU, no PHYS_FLAG_SHARED_GPU, no other world on the device: asked afresh for every update's plan (abi.hip)
 bool gpu_is_exclusive(const phys_world* w);
 // PHYS_DEBUG_* switches (plan.hpp DebugSwitches), parsed once per process by the first call (abi.hip)
 const DebugSwitches& debug_switches();
-
-struct Constraint {
-    uint32_t kind;  // 0 fix point, 1 fix orientation
-    uint32_t body;
-    float target[3];
-};
 
 }  // namespace phys
 
@@ -245,19 +181,16 @@ struct phys_world {
     std::vector<phys::Constraint> constraints;
     phys::DevBuf<phys::Constraint> d_constraints;
     bool constraints_dirty = false;
-    bool have_lambda = false;  // previous_solution.is_some()
     phys::DevBuf<float> cg_x, cg_r, cg_p, cg_ap, cg_rhs, cg_c, cg_scratch;
     phys::DevBuf<float> cg_jl;         // J^T lambda of entity 0 (6 floats), added by the step kernel behind gravity (quirk Q3)
     phys::DevBuf<uint32_t> cg_status;  // [0] converged flag, [1] iterations, [2] previous_solution.is_some()
     phys::DevBuf<uint32_t> cg_cols;    // col_id | col_ptr | col_rows | row_cidx (constraints.hip)
     uint32_t cg_n_cols = 0;
-    uint32_t last_cg_iterations = 0;
-    int32_t last_cg_converged = 1;
 
     // collision pipeline (A10-A12)
     uint64_t max_pairs = 0, max_manifolds = 0;
     uint32_t grid_table_size = 0;  // hashed-grid buckets (power of two)
-    phys::GridShape grid_shape{};  // its split over the three axes (kernels.hpp GridShape; set by grid_plan)
+    phys::GridShape grid_shape{};  // its split over the three axes (setup.hpp grid_plan)
     // counters, bucket_count and color_state are windows into ONE allocation (step_zero) laid out
     // [bucket counts | colouring state | StepCounters], so one memset per step zeroes all three (up to, not
     // including, StepCounters::max_extent_bits at the very end)
@@ -322,7 +255,7 @@ struct phys_world {
     phys::DevBuf<uint32_t> body_shared;    // 2 per body: 64-bit mask of the colours in which ANOTHER cluster's row updates it
     bool seg_count_dirty = false;    // the (cluster, colour) counters were left non-zero by the last cluster step (three-launch scan)
     uint32_t seg_count_bins = 0;     // ... which used this many of them
-    phys::DevBuf<uint32_t> seg_count, seg_start;  // rows per (cluster, colour) - kept behind body_shared, seg_count itself is unused - and their exclusive scan
+    phys::DevBuf<uint32_t> seg_start;      // exclusive scan of the rows per (cluster, colour), which are counted behind body_shared
     phys::DevBuf<uint32_t> man_rank;       // manifold -> arrival rank inside its segment
     uint32_t flow_epoch = 0;         // solves since the buffers were cleared (upper half of every tag)
     // ray-cast query (raycast.hip): its own grid, rebuilt from the current poses by every call; nothing an update reads
@@ -388,7 +321,6 @@ struct phys_world {
     uint32_t snap_next = 0;
     phys::Profiler prof;
     uint32_t host_sticky_overflow = 0;  // overflow bits seen in counter snapshots (poll_snapshots), until phys_sync
-    phys_stats stats{};
     // pinned host mirror of the counters for read-back
     phys::StepCounters* h_counters = nullptr;
 };
