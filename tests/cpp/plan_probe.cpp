@@ -138,6 +138,45 @@ static void pairs() {
     }
 }
 
+// The (body count, switches) of tests/test_gpu_pairs_independent.py: which kernel each gives without a hint, with the hint of a
+// sparsely filled grid and few pairs (left alone: the brick kernel, small stage) and with that of a crowded grid and many pairs
+// (left alone: lanes per body) - worked out from plan_pairs as written: PAIR_LANES wins over everything above the slot grid,
+// PAIR_KERNEL=brick over the crowding, BRICK_STAGE over the pair count.
+static void pair_variants() {
+    const StepHint none;
+    StepHint sparse = hint(30000);   // 30000 pairs < 3 x 33000; 33000 x 10 <= 30000 x 21
+    sparse.n_used_buckets = 30000;
+    StepHint crowded = hint(30000);  // 33000 x 10 > 2000 x 21
+    crowded.n_pairs = 1000000;
+    crowded.n_used_buckets = 2000;
+    DebugSwitches off, lanes4, lanes1, brick128, brick256;
+    lanes4.pair_lanes = 4;
+    lanes1.pair_lanes = 1;
+    brick128.pair_kernel_brick = true; brick128.brick_stage = 128;
+    brick256.pair_kernel_brick = true; brick256.brick_stage = 256;
+    const struct { const char* what; uint64_t n; const DebugSwitches* d; PairKernel no_hint, sparse, crowded; } t[] = {
+        {"33000, PAIR_LANES=4", 33000, &lanes4, PairKernel::Lanes4, PairKernel::Lanes4, PairKernel::Lanes4},
+        {"33000, PAIR_LANES=1", 33000, &lanes1, PairKernel::Lanes1, PairKernel::Lanes1, PairKernel::Lanes1},
+        {"33000, PAIR_KERNEL=brick BRICK_STAGE=128", 33000, &brick128, PairKernel::Brick128, PairKernel::Brick128, PairKernel::Brick128},
+        {"33000, PAIR_KERNEL=brick BRICK_STAGE=256", 33000, &brick256, PairKernel::Brick256, PairKernel::Brick256, PairKernel::Brick256},
+        {"33000, no switch", 33000, &off, PairKernel::Brick256, PairKernel::Brick128, PairKernel::Lanes4},
+        {"32769, no switch", 32769, &off, PairKernel::Brick256, PairKernel::Brick128, PairKernel::Lanes4},
+        {"32768, no switch", 32768, &off, PairKernel::Slots, PairKernel::Slots, PairKernel::Slots},
+    };
+    for (const auto& c : t) {
+        PlanInputs in = world(c.n);
+        in.grid_table_size = 1u << 17;  // what grid_plan gives these body counts
+        CHECK(c.what, plan_pairs(in, none, *c.d).kernel, c.no_hint);
+        CHECK(c.what, plan_pairs(in, sparse, *c.d).kernel, c.sparse);
+        CHECK(c.what, plan_pairs(in, crowded, *c.d).kernel, c.crowded);
+    }
+    // a sparse grid with many pairs keeps the large stage
+    sparse.n_pairs = 99000;
+    CHECK("33000, 3 pairs per body", plan_pairs(world(33000), sparse, off).kernel, PairKernel::Brick256);
+    sparse.n_pairs = 98999;
+    CHECK("33000, fewer", plan_pairs(world(33000), sparse, off).kernel, PairKernel::Brick128);
+}
+
 static void narrow() {
     const DebugSwitches off;
     const StepHint none;
@@ -484,6 +523,7 @@ static void switches_stay_in_their_lane() {
 
 int main() {
     pairs();
+    pair_variants();
     narrow();
     coloring();
     solver();

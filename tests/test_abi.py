@@ -99,7 +99,8 @@ def test_independent_gpu_checks_share_no_code_with_the_spec_or_the_oracle():
     the product's Python host, and the second one also tests/contact_ref.py - which itself imports numpy only."""
     imports = r"^\s*(?:from|import)\s+([A-Za-z0-9_\.]+)"
     for name, extra in (("test_gpu_independent.py", set()), ("test_gpu_solver_independent.py", {"contact_ref"}),
-                        ("test_gpu_halo_independent.py", {"halo_ref", "ctypes", "torch"})):
+                        ("test_gpu_halo_independent.py", {"halo_ref", "ctypes", "torch"}),
+                        ("test_gpu_pairs_independent.py", {"pair_ref", "functools", "os", "subprocess", "sys"})):
         txt = open(os.path.join(ROOT, "tests", name)).read()
         mods = set(re.findall(imports, txt, flags=re.M))
         assert mods <= {"numpy", "pytest", "physics_amd"} | extra, (name, mods)
@@ -108,6 +109,9 @@ def test_independent_gpu_checks_share_no_code_with_the_spec_or_the_oracle():
     assert set(re.findall(imports, txt, flags=re.M)) == {"numpy"}
     assert "liboracle" not in txt and "oracle" not in txt.split('"""', 2)[2]
     txt = open(os.path.join(ROOT, "tests", "halo_ref.py")).read()  # the sharding kernels' reference: numpy only
+    assert set(re.findall(imports, txt, flags=re.M)) == {"numpy"}
+    assert "oracle" not in txt and "include/spec" not in txt
+    txt = open(os.path.join(ROOT, "tests", "pair_ref.py")).read()  # the pair search's reference: the same rule
     assert set(re.findall(imports, txt, flags=re.M)) == {"numpy"}
     assert "oracle" not in txt and "include/spec" not in txt
 
