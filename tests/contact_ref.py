@@ -362,6 +362,74 @@ def random_heap(seed, n=512):
                 inertia=None, shape_type=shape, half_extent=he.astype(np.float32))
 
 
+SHAPE_CAPSULE = 3
+TOWER_MU = 0.5  # the default friction, which varied_tower's census of friction rows is taken with
+
+
+def varied_tower(seed, inertia, dims=(16, 130, 16), p_sphere=0.25, p_capsule=0.2, p_tilt=0.3, tilt=0.02, slide=3.0, spin=0.6):
+    """A tower whose bodies are all different, for the kernels that move body constants about: the 16 x 130 x 16 lattice of
+    spacing 2 (x fastest, then z, then y; lowest centres at y = 1: resting contact all round), 33 280 bodies.
+      masses   log-uniform in [0.25, 4], independent per body;
+      inertia  "uniform": one diagonal tensor (0.6, 1.7, 2.9) for everybody; "diag": three distinct entries per body;
+               "full": symmetric positive definite with off-diagonal entries (_inertia);
+      shapes   boxes of half extent 1, spheres of radius 1 and capsules (radius 1, core half-length 0.05) lying along x or
+               z; some boxes tilted by up to `tilt` radians: manifolds of 1, 2 and 4 points;
+      motion   horizontal speeds of 0 to `slide` units/s, up to 0.3 up or down, angular velocities of scale `spin`: some
+               friction rows end at the +-mu pn box, others inside it.
+    Returns the set_bodies arguments. Seeds and amplitudes are pinned by tests/test_contact_ref_cpu.py's censuses."""
+    rng = np.random.default_rng(seed)
+    nx, ny, nz = dims
+    n = nx * ny * nz
+    idx = np.arange(n)
+    pos = np.stack([(idx % nx - (nx - 1) / 2.0) * 2.0, 1.0 + (idx // (nx * nz)) * 2.0, ((idx // nx) % nz - (nz - 1) / 2.0) * 2.0], 1)
+    u = rng.random(n)
+    shape = np.where(u < p_sphere, SHAPE_SPHERE, np.where(u < p_sphere + p_capsule, SHAPE_CAPSULE, SHAPE_BOX)).astype(np.uint32)
+    he = np.ones((n, 3))
+    he[shape == SHAPE_CAPSULE] = (1.0, 0.05, 0.0)
+    rot = np.zeros((n, 4), np.float32)
+    rot[:, 3] = 1.0
+    tilted = (shape == SHAPE_BOX) & (rng.random(n) < p_tilt)
+    rot[tilted] = _small_tilts(rng, int(tilted.sum()), tilt)
+    s = np.float32(np.sqrt(0.5))
+    caps = np.flatnonzero(shape == SHAPE_CAPSULE)
+    along_x = rng.random(len(caps)) < 0.5
+    rot[caps] = (0, 0, 0, s)
+    rot[caps[along_x], 2] = s   # 90 degrees about z: the core (local y) along -x
+    rot[caps[~along_x], 0] = s  # 90 degrees about x: the core along +z
+    heading = rng.uniform(0.0, 2.0 * np.pi, n)
+    speed = rng.uniform(0.0, slide, n)
+    lin = np.stack([speed * np.cos(heading), rng.uniform(-0.3, 0.3, n), speed * np.sin(heading)], 1)
+    ang = rng.normal(scale=spin, size=(n, 3))
+    mass = np.exp(rng.uniform(np.log(0.25), np.log(4.0), n))
+    if inertia == "uniform":
+        tensor = np.tile(np.diag([0.6, 1.7, 2.9]).reshape(1, 9), (n, 1)).astype(np.float32)
+    else:
+        tensor = _inertia(rng, n, inertia)
+    return dict(pos=pos.astype(np.float32), rot=rot, lin_vel=lin.astype(np.float32), ang_vel=ang.astype(np.float32),
+                mass=mass.astype(np.float32), inertia=tensor, shape_type=shape, half_extent=he.astype(np.float32))
+
+
+VARIED_SEED = 11
+VARIED_UPDATES = 4
+# id -> (inertia, warm start, iterations): the solves the cluster kernel is held to on the varied tower (CPU: the float32
+# solve of the host, tests/test_contact_ref_cpu.py; GPU: tests/test_gpu_solver_independent.py, tests/test_gpu_cluster_variants.py)
+VARIED_CASES = {"diag": ("diag", True, 8), "uniform": ("uniform", True, 8), "full": ("full", True, 8),
+                "diag_cold": ("diag", False, 8), "diag_cold_1": ("diag", False, 1), "diag_warm_1": ("diag", True, 1),
+                "full_warm_2": ("full", True, 2), "full_cold_2": ("full", False, 2)}
+# the worst float32-against-float64 velocity error of the host's float32 solve over every case above, four updates each: measured
+# 3.33e-6 (diag, update 4; uniform 2.32e-6, full 3.09e-6, diag_cold 1.43e-6, diag_cold_1 7.66e-7, diag_warm_1 1.32e-6,
+# full_warm_2 1.26e-6, full_cold_2 9.25e-7), rounded up to two digits. tests/test_contact_ref_cpu.py prints each
+# and asserts that none exceeds this figure; the kernels get 4 x (the margin of tests/dynamics_ref.py)
+MEASURED_VARIED = 3.4e-6
+TOL_VARIED = 4.0 * MEASURED_VARIED
+
+
+def point_count_shares(count):
+    """Shares of the manifolds with 1, 2 and 4 points."""
+    count = np.asarray(count)
+    return tuple(float((count == k).mean()) for k in (1, 2, 4))
+
+
 def quat_matrices(rot):
     """World = R @ local for quaternions [i, j, k, w]."""
     q = np.asarray(rot, np.float64).reshape(-1, 4)

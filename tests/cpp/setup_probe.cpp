@@ -248,6 +248,17 @@ static void dynamic() {
         d.cluster_cap = 2000000;  // with a cap as well: the fallback
         check_dyn("CLUSTERS_PER_CU=1 and a cap", plan_dynamic_clusters(n, true, 256, active(1000000), d), 224, 2496);
     }
+    {   // the 33 280-body tower of tests/test_gpu_cluster_variants.py, everybody in contact, on 256 CUs: homes = clusters x slots.
+        // The floor of 64 slots makes 672 x 64 = 43 008 homes of PHYS_DEBUG_CLUSTER_CAP=9000 with diagonal tensors -
+        // nobody is homeless; with full tensors (two per CU) 28 672, and with one workgroup per CU 14 336, either kind
+        DebugSwitches d;
+        d.cluster_cap = 9000;
+        check_dyn("tower, cap 9000", plan_dynamic_clusters(33280, true, 256, active(33280), d), 672, 64);
+        check_dyn("tower, cap 9000, full tensors", plan_dynamic_clusters(33280, false, 256, active(33280), d), 448, 64);
+        d.clusters_per_cu = 1;
+        check_dyn("tower, cap 9000, one per CU", plan_dynamic_clusters(33280, true, 256, active(33280), d), 224, 64);
+        check_dyn("tower, cap 9000, one per CU, full tensors", plan_dynamic_clusters(33280, false, 256, active(33280), d), 224, 64);
+    }
     {   // the six scenes of plan_probe.cpp (no count of active bodies yet: min(n_owned, manifolds) + 25 %), on 256 CUs
         const struct { uint64_t n; uint32_t manifolds; long long c0, s0, c1, s1, c2, s2; } t[6] = {
             //                       no switch      CLUSTER_CAP=200000   CLUSTERS_PER_CU=1

@@ -96,9 +96,10 @@ def test_product_code_never_touches_the_oracle():
 def test_independent_gpu_checks_share_no_code_with_the_spec_or_the_oracle():
     """tests/test_gpu_independent.py and tests/test_gpu_solver_independent.py are where the collision and solver
     arithmetic is checked against something that is NOT compiled from include/spec: they may import numpy, pytest and
-    the product's Python host, and the second one also tests/contact_ref.py - which itself imports numpy only."""
+    the product's Python host, and the second one also tests/contact_ref.py - which itself imports numpy only - and
+    tests/material_ref.py, which imports numpy and contact_ref."""
     imports = r"^\s*(?:from|import)\s+([A-Za-z0-9_\.]+)"
-    for name, extra in (("test_gpu_independent.py", set()), ("test_gpu_solver_independent.py", {"contact_ref"}),
+    for name, extra in (("test_gpu_independent.py", set()), ("test_gpu_solver_independent.py", {"contact_ref", "material_ref"}),
                         ("test_gpu_halo_independent.py", {"halo_ref", "ctypes", "torch"}),
                         ("test_gpu_pairs_independent.py", {"pair_ref", "functools", "os", "subprocess", "sys"})):
         txt = open(os.path.join(ROOT, "tests", name)).read()
@@ -107,6 +108,9 @@ def test_independent_gpu_checks_share_no_code_with_the_spec_or_the_oracle():
         assert "liboracle" not in txt and "include/spec" not in txt.split('"""')[2], name
     txt = open(os.path.join(ROOT, "tests", "contact_ref.py")).read()
     assert set(re.findall(imports, txt, flags=re.M)) == {"numpy"}
+    assert "liboracle" not in txt and "oracle" not in txt.split('"""', 2)[2]
+    txt = open(os.path.join(ROOT, "tests", "material_ref.py")).read()  # contact_ref with a friction per manifold
+    assert set(re.findall(imports, txt, flags=re.M)) == {"numpy", "contact_ref"}
     assert "liboracle" not in txt and "oracle" not in txt.split('"""', 2)[2]
     txt = open(os.path.join(ROOT, "tests", "halo_ref.py")).read()  # the sharding kernels' reference: numpy only
     assert set(re.findall(imports, txt, flags=re.M)) == {"numpy"}

@@ -245,3 +245,68 @@ def test_cluster_tower_against_the_oracle(ob):
     print(f"\nC5(16,130,16) tower: {len(out['a'])} manifolds, largest velocity error {worst:.3g}")
     assert len(out["a"]) > 90_000
     assert worst < 2e-5
+
+
+# ---------------------------------------------------------------- the varied tower: unequal bodies, cold and short solves
+def test_varied_tower_gives_every_body_constants_of_its_own():
+    """The lattice is C5(16, 130, 16)'s; masses are log-uniform in [0.25, 4] and differ between neighbours; `uniform` is
+    one diagonal tensor that is not the identity, `diag` three distinct entries per body, `full` has off-diagonals."""
+    sc = scenes.c5(16, 130, 16)
+    for kind in ("uniform", "diag", "full"):
+        b = cr.varied_tower(cr.VARIED_SEED, kind)
+        assert np.array_equal(b["pos"], sc.pos) and len(b["pos"]) == 33_280
+        m = b["mass"].astype(np.float64)
+        assert 0.25 <= m.min() < 0.26 and 3.9 < m.max() <= 4.0
+        hist = np.histogram(np.log(m), bins=8, range=(np.log(0.25), np.log(4.0)))[0]
+        assert hist.min() > 0.8 * len(m) / 8 and hist.max() < 1.2 * len(m) / 8
+        assert (m[1:] != m[:-1]).all() and (m[256:] != m[:-256]).all() and (m[16:] != m[:-16]).all()
+        I = b["inertia"].reshape(-1, 3, 3)
+        d = np.stack([I[:, 0, 0], I[:, 1, 1], I[:, 2, 2]], 1)
+        off = I - d[:, :, None] * np.eye(3, dtype=np.float32)
+        if kind == "uniform":
+            assert (I == I[0]).all() and not off.any() and (d[0] != 1).all()
+        elif kind == "diag":
+            assert not off.any() and (d[:, 0] != d[:, 1]).all() and (d[:, 1] != d[:, 2]).all() and (d[:, 0] != d[:, 2]).all()
+            assert (d[1:] != d[:-1]).all()
+        else:
+            assert (np.abs(off).max(axis=(1, 2)) > 1e-3).all() and np.array_equal(I, I.transpose(0, 2, 1))
+            assert (np.linalg.eigvalsh(I.astype(np.float64)) > 1.0).all()
+        assert {int(s) for s in np.unique(b["shape_type"])} == {cr.SHAPE_SPHERE, cr.SHAPE_BOX, cr.SHAPE_CAPSULE}
+
+
+@pytest.mark.parametrize("case", list(cr.VARIED_CASES))
+def test_varied_tower_against_the_oracle(ob, case):
+    """VARIED_UPDATES updates of the varied tower per case of contact_ref.VARIED_CASES, the oracle's float32 solve against
+    the reference. Pins, for the reference alone, what the GPU tests rely on: more than 40 960 manifolds in every update
+    (the cluster plan's floor), at least 6 colours, manifolds of 1, 2 and 4 points at least 2 % each, ambiguous manifolds
+    within 1 %, and friction rows at the +-mu pn box and inside it, at least 10 % each, in every update of the warm
+    eight-iteration solves and in update 1 of the cold one (the sliding the builder sets dies down: with nothing carried, a
+    cold solve of update 3 leaves 9.8 % of the rows at the clamp; one or two iterations from rest leave hardly any).
+    The error printed here, at its worst over the cases, is contact_ref.MEASURED_VARIED; TOL_VARIED is four times that."""
+    inertia, warm, iterations = cr.VARIED_CASES[case]
+    bodies = cr.varied_tower(cr.VARIED_SEED, inertia)
+    n = len(bodies["pos"])
+    o = oracle_world(ob, bodies, flags=FLAG_COLLISIONS | FLAG_GROUND_PLANE | (0 if warm else FLAG_NO_WARM_START),
+                     gravity=(0, -9.81, 0), solver_iterations=iterations)
+    ref = cr.SolverRef(n, cr.Params(DT_S), iterations, warm=warm)
+    worst = 0.0
+    for u, (out, lin1, ang1, _) in enumerate(run(o, ref, cr.VARIED_UPDATES, *cr.body_inverses(n, bodies["mass"], bodies["inertia"]), GRAVITY)):
+        _check_colors(o, out)
+        err, amb = cr.velocity_error(out, lin1, ang1)
+        worst = max(worst, err)
+        m = len(out["a"])
+        shares = cr.point_count_shares(out["count"])
+        clamped, inside = cr.friction_row_states(out, cr.TOWER_MU)
+        carried = int((np.abs(out["P0"]) > 0).any(axis=(1, 2)).sum()) if warm else 0
+        print(f"\nvaried tower {case} update {u + 1}: {m} manifolds, {out['n_colors']} colours, 1/2/4 points "
+              f"{shares[0]:.3f}/{shares[1]:.3f}/{shares[2]:.3f}, friction rows clamped {clamped} inside {inside}, "
+              f"carrying impulses {carried}, {amb} ambiguous, error {err:.3g}")
+        assert m > 40_960 and out["n_colors"] >= 6
+        assert min(shares) >= 0.02
+        assert amb <= 0.01 * m
+        if iterations == 8 and (warm or u == 0):
+            assert clamped >= 0.1 * (clamped + inside) and inside >= 0.1 * (clamped + inside)
+        if warm and u:
+            assert carried > 0.5 * m
+    print(f"varied tower {case}: largest velocity error {worst:.3g} (MEASURED_VARIED {cr.MEASURED_VARIED:.3g}, TOL_VARIED {cr.TOL_VARIED:.3g})")
+    assert worst <= cr.TOL_VARIED / 4

@@ -568,7 +568,9 @@ def test_dynamic_clusters_equal_the_per_colour_kernels(cap):
     update to the bodies that have a manifold in it, in the broad phase's bucket order; a row belongs to the home of its
     body A, else of B; a body without a home (more active bodies than homes) is served as "another cluster's body" on
     whichever side it stands. Forced here on a 33k tower in a fresh process (the library reads the switches once), with
-    homes for everybody and with homes for 9000 of the 33 280 bodies: the same bits as the per-colour kernels."""
+    homes for everybody and with PHYS_DEBUG_CLUSTER_CAP=9000: the same bits as the per-colour kernels. (A cluster has 64
+    slots at least, so on 256 CUs the cap still leaves 672 x 64 homes with these diagonal tensors - nobody is homeless;
+    tests/test_gpu_cluster_variants.py has the combinations of switches that leave bodies without a home.)"""
     import os
     import subprocess
     import sys

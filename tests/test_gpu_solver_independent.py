@@ -5,7 +5,8 @@ own float64 impulses from update to update. Each test asserts from profile_get()
 
 Tolerances come from tests/test_contact_ref_cpu.py, which measures the same float32-against-float64 spread on the CPU
 oracle (bit-equal to the device on every solver path): at most 2.3e-6 on isolated manifolds, 3.9e-6 on coupled piles,
-5.1e-7 on the C5(16, 130, 16) tower."""
+5.1e-7 on the C5(16, 130, 16) tower, 3.33e-6 on the varied tower (every body with its own mass and inertia, cold and
+short solves: section (d); the tolerance there is contact_ref.TOL_VARIED = 4 x that spread)."""
 import numpy as np
 import pytest
 
@@ -38,6 +39,8 @@ ALT = dict(baumgarte=0.35, slop=0.003, friction=0.9, max_bias=1.25)
 
 
 def make_world(bodies, flags=0, gravity=(0, 0, 0), **cfg):
+    """A world of `bodies` (set_bodies arguments) with collisions and the ground; cfg: solver_iterations and the solver's
+    parameters, as default_config takes them."""
     import physics_amd
     w = physics_amd.World(physics_amd.default_config(flags=physics_amd.FLAG_COLLISIONS | physics_amd.FLAG_GROUND_PLANE | flags,
                                                      gravity_force=gravity, gravity_offset=(0, 0, 0), **cfg))
@@ -45,9 +48,10 @@ def make_world(bodies, flags=0, gravity=(0, 0, 0), **cfg):
     return w
 
 
-def checked_updates(w, ref, n_updates, inv_m, inv_I, force=None, cold=None):
+def checked_updates(w, ref, n_updates, inv_m, inv_I, force=None, cold=None, **ref_args):
     """Per update: (reference output, device velocities, solver stages that ran[, cold reference output]). Both
-    references start from the device's poses and velocities of that update."""
+    references start from the device's poses and velocities of that update. ref_args: further arguments of ref.update
+    (material_ref's `materials`)."""
     for _ in range(n_updates):
         pos, _ = w.get_transforms()
         lin, ang = w.get_velocities()
@@ -57,7 +61,7 @@ def checked_updates(w, ref, n_updates, inv_m, inv_I, force=None, cold=None):
         stages = set(w.profile_get()[0]) & SOLVER_STAGES
         man = w.get_manifolds()
         lin1, ang1 = w.get_velocities()
-        out = ref.update(man, pos, lin, ang, inv_m, inv_I, force)
+        out = ref.update(man, pos, lin, ang, inv_m, inv_I, force, **ref_args)
         extra = (cold.update(man, pos, lin, ang, inv_m, inv_I, force),) if cold is not None else ()
         yield (out, lin1, ang1, stages) + extra
 
@@ -194,14 +198,22 @@ def test_persistent_colouring_of_a_churning_scene():
     assert stages_seen and stages_seen <= SOLVER_STAGES - {"solve_cluster"}, stages_seen
 
 
-def _coupled(bodies, n_updates=6, flags=0, expect=("solve_flow",)):
+def _coupled(bodies, n_updates=6, flags=0, expect=("solve_flow",), iterations=8, ref=None, prepare=None, each=None, **ref_args):
+    """n_updates of a world of `bodies` under gravity with `flags` and `iterations`, each against `ref` (default: a warm
+    SolverRef of as many iterations): colour counts, n_colors, color_rounds, n_new_manifolds, the stages that ran and the
+    share of ambiguous manifolds are asserted here; returns (largest velocity error, most colours, manifolds of the last
+    update). prepare(world) runs once behind set_bodies; each(u, world, out, lin1, ang1) once per update."""
     n = len(bodies["pos"])
-    w = make_world(bodies, flags=flags, gravity=(0, -9.81, 0))
-    ref = cr.SolverRef(n, cr.Params(DT_S), 8)
+    w = make_world(bodies, flags=flags, gravity=(0, -9.81, 0), solver_iterations=iterations)
+    if prepare is not None:
+        prepare(w)
+    if ref is None:
+        ref = cr.SolverRef(n, cr.Params(DT_S), iterations)
     worst, colors = 0.0, 0
     for u, (out, lin1, ang1, stages) in enumerate(checked_updates(w, ref, n_updates, *cr.body_inverses(n, bodies.get("mass"),
-                                                                                                       bodies.get("inertia")), GRAVITY)):
+                                                                                                       bodies.get("inertia")), GRAVITY, **ref_args)):
         st = w.get_stats()
+        assert st.overflow == 0, (u, st.overflow)
         assert np.array_equal(w.get_color_counts(), cr.color_counts(out["colors"]))
         assert (st.n_colors, st.color_rounds, st.n_new_manifolds) == (out["n_colors"], out["color_rounds"], out["n_new_manifolds"])
         # (update 1 may take another family: the cluster plan needs the counts of an update before)
@@ -209,6 +221,9 @@ def _coupled(bodies, n_updates=6, flags=0, expect=("solve_flow",)):
         err, amb = cr.velocity_error(out, lin1, ang1)
         assert amb <= 0.01 * len(out["a"])
         worst, colors = max(worst, err), max(colors, out["n_colors"])
+        if each is not None:
+            each(u, w, out, lin1, ang1)
+    w.close()
     return worst, colors, len(out["a"])
 
 
@@ -245,3 +260,82 @@ def test_cluster_kernels_on_the_tower():
     print(f"\nC5 tower (cluster): {m} manifolds, {colors} colours, error {worst:.3g} (tolerance {TOL_TOWER})")
     assert m > 90_000
     assert worst < TOL_TOWER
+
+
+# ---------------------------------------------------------------- (d) the cluster kernel with unequal bodies, cold and short
+def varied_flags(warm, exclusive=False):
+    import physics_amd
+    return (physics_amd.FLAG_SOLVER_CLUSTER | (0 if warm else physics_amd.FLAG_NO_WARM_START) |
+            (physics_amd.FLAG_EXCLUSIVE_GPU if exclusive else 0))
+
+
+def varied_materials(n):
+    """Seeded friction in [0.1, 1] and restitution 0 per body (the ground keeps the default 0.5)."""
+    return np.random.default_rng(cr.VARIED_SEED + 1).uniform(0.1, 1.0, n).astype(np.float32)
+
+
+def _warm_run_leaves_the_cold_solve(bodies, iterations, cold_front, cold_out):
+    """Negative control of a cold case: the same bodies WITH warm starting. Update 1 carries nothing, so update 2 starts
+    with the cold world's bits; what the warm world makes of them must lie far from the cold reference."""
+    w = make_world(bodies, flags=varied_flags(True), gravity=(0, -9.81, 0), solver_iterations=iterations)
+    w.update(DT)
+    w.sync()
+    front = (w.get_transforms()[0],) + tuple(w.get_velocities())
+    assert all(np.array_equal(a, b) for a, b in zip(front, cold_front)), "update 1 of a warm world carries no impulses"
+    w.update(DT)
+    w.sync()
+    lin1, ang1 = w.get_velocities()
+    w.close()
+    return max(np.abs(lin1 - cold_out["lin"]).max(), np.abs(ang1 - cold_out["ang"]).max())
+
+
+VARIED_GPU_CASES = [(case, False) for case in cr.VARIED_CASES] + [("full", True)]
+
+
+@pytest.mark.parametrize("case,exclusive", VARIED_GPU_CASES, ids=[c + ("_exclusive" if x else "") for c, x in VARIED_GPU_CASES])
+def test_cluster_kernel_on_the_varied_tower(case, exclusive):
+    """contact_ref.varied_tower with PHYS_FLAG_SOLVER_CLUSTER: every body has its own mass and inertia (one shared
+    diagonal, a diagonal per body, full tensors: k_solve_cluster<true, ...> with stride 0 and 1, <false, ...>), guarded
+    and unguarded starts, warm and cold solves of 8, 2 and 1 iterations. Updates 2 to 4 run the cluster kernel alone;
+    every update is held to the float64 reference under TOL_VARIED (4 x the oracle's spread, test_contact_ref_cpu).
+    Cold cases: a warm world on the same bodies does NOT match the cold reference (the flag is live)."""
+    inertia, warm, iterations = cr.VARIED_CASES[case]
+    bodies = cr.varied_tower(cr.VARIED_SEED, inertia)
+    n = len(bodies["pos"])
+    seen = {}
+
+    def each(u, w, out, lin1, ang1):
+        assert len(out["a"]) > 40_960
+        if u == 1:
+            seen["out"] = out
+        if u == 0:
+            seen["front"] = (w.get_transforms()[0], lin1, ang1)
+
+    worst, colors, m = _coupled(bodies, n_updates=cr.VARIED_UPDATES, flags=varied_flags(warm, exclusive), expect=("solve_cluster",),
+                                iterations=iterations, ref=cr.SolverRef(n, cr.Params(DT_S), iterations, warm=warm), each=each)
+    print(f"\nvaried tower {case}{' exclusive' if exclusive else ''}: {m} manifolds, {colors} colours, error {worst:.3g} (tolerance {cr.TOL_VARIED:.3g})")
+    assert colors >= 6
+    assert worst < cr.TOL_VARIED
+    if not warm:
+        off = _warm_run_leaves_the_cold_solve(bodies, iterations, seen["front"], seen["out"])
+        print(f"  a warm world differs from the cold reference by up to {off:.3g}")
+        assert off > 10 * cr.TOL_VARIED
+
+
+def test_cluster_kernel_with_materials_on_the_varied_tower():
+    """k_solve_cluster<false, *, true>: full tensors and a friction coefficient per body (restitution 0), against
+    tests/material_ref.py's solver - the contact reference with a friction per manifold."""
+    import material_ref as mr
+    bodies = cr.varied_tower(cr.VARIED_SEED, "full")
+    n = len(bodies["pos"])
+    fr = varied_materials(n)
+    mats = mr.Materials(fr, np.zeros(n))
+    mus = []
+    worst, colors, m = _coupled(bodies, n_updates=cr.VARIED_UPDATES, flags=varied_flags(True), expect=("solve_cluster",),
+                                ref=mr.MaterialSolverRef(n, cr.Params(DT_S), 8), prepare=lambda w: w.set_body_materials(friction=fr, restitution=0.0),
+                                each=lambda u, w, out, lin1, ang1: mus.append(out["mu"]), materials=mats)
+    print(f"\nvaried tower with materials: {m} manifolds, {colors} colours, mu {min(x.min() for x in mus):.3f} to "
+          f"{max(x.max() for x in mus):.3f}, error {worst:.3g} (tolerance {cr.TOL_VARIED:.3g})")
+    assert m > 40_960 and colors >= 6
+    assert min(x.min() for x in mus) < 0.2 and max(x.max() for x in mus) > 0.9
+    assert worst < cr.TOL_VARIED
