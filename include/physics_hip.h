@@ -166,7 +166,9 @@ int32_t phys_step(phys_world* w, uint64_t dt_nanos);
 int32_t phys_update_n(phys_world* w, uint64_t dt_nanos, uint32_t n);
 /* block until all queued device work of this world is done. Device-side errors are sticky: a capacity overflow or a
  * solver time-out in ANY update since the previous phys_sync (also an early one of a phys_update_n batch) is reported
- * here once - PHYS_ERR_CAPACITY / PHYS_ERR_HIP - and then cleared. The contact solve of an overflowing update is
+ * here once - PHYS_ERR_CAPACITY / PHYS_ERR_HIP - and then cleared; only the bits of the LAST update stay, as in
+ * phys_stats.overflow, until the next update, and a phys_sync with no update in between reports those again.
+ * The contact solve of an overflowing update is
  * skipped (never run on a truncated contact set); bodies are still integrated.
  * Limit: at most 64 contact manifolds per body (one solver colour each). */
 int32_t phys_sync(phys_world* w);

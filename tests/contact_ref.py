@@ -10,18 +10,20 @@ the bodies at the START of the update. One call is one update with collisions an
   * pre-solve velocities: v + dt F / m (gravity is a force, quirk Q2), angular velocity unchanged;
   * persistent colouring: a pair that had a manifold in the previous call keeps its colour, the new ones go through
     Jones-Plassmann rounds on priority = splitmix64 finaliser of (a << 32 | b) against `used` masks seeded with the kept
-    colours (the ground is no body; colours capped at 63);
+    colours (the ground is no body, and neither is a static collider - a partner id with STATIC_ID_BIT set: its rows are
+    one-sided, it has no entry in `used` or `top`, and the priority still hashes the full pair; colours capped at 63);
   * warm starting: each point takes the impulses of the first untaken remembered point within 0.05 (normal impulse if
     the normals agree to a cosine of 0.999, friction only if both tangents do too); sweep 0 applies them unclamped;
   * `iterations` Gauss-Seidel sweeps, colour by colour ascending, per point in index order: tangent 1, tangent 2,
     normal. Friction is a box clamp: each tangent to +-mu * pn of that point at that moment. Effective masses use the
-    inverse inertia as given (world frame, never rotated: quirk Q5); the ground is a static body B.
+    inverse inertia as given (world frame, never rotated: quirk Q5); the ground and a static collider are a static body B.
 The returned dict holds lin / ang after the solve, colours, n_colors, color_rounds, n_new_manifolds, the final impulses
 (m, 4, 3) in the order (t1, t2, n) and per-manifold `ambiguous` flags: a warm-start decision within 1e-5 of its
 threshold, or a normal within 1e-6 of the tangent-basis switch, where float32 rounding may decide the other way."""
 import numpy as np
 
 GROUND = 0xFFFFFFFF
+STATIC_ID_BIT = 0x80000000  # partner STATIC_ID_BIT | k: static collider k (the ground's id has the bit as well)
 MAX_COLORS = 64
 WARM_DIST2 = 0.05 ** 2
 WARM_DOT = 0.999
@@ -34,6 +36,11 @@ class Params:
     def __init__(self, dt, baumgarte=0.2, slop=0.01, friction=0.5, max_bias=3.0):
         self.dt, self.baumgarte, self.slop, self.friction, self.max_bias = (float(dt), float(baumgarte), float(slop),
                                                                            float(friction), float(max_bias))
+
+
+def is_body(b):
+    """The partner of a manifold is a body that moves: neither the ground nor a static collider."""
+    return (np.asarray(b, np.int64) & STATIC_ID_BIT) == 0
 
 
 # ---------------------------------------------------------------- colouring
@@ -66,7 +73,7 @@ def color_manifolds(a, b, n_bodies, prev_keys=None, prev_colors=None):
     a = np.asarray(a, np.int64)
     b = np.asarray(b, np.int64)
     M = len(a)
-    dyn = b != GROUND
+    dyn = is_body(b)
     bb = np.where(dyn, b, 0)
     prio = color_priority(a, b)
     color = np.full(M, -1, np.int64)
@@ -165,7 +172,7 @@ def build_rows(a, b, count, normal32, pts, depth, x, inv_mass, inv_inertia, p):
     """Velocity-independent part of every row: directions D (m, 3 [t1, t2, n], 3), angular Jacobians aA / aB and their
     images under the inverse inertia mA / mB (m, 4, 3, 3), inverse masses, row masses (m, 4, 3), bias (m, 4)."""
     M = len(a)
-    dyn = b != GROUND
+    dyn = is_body(b)
     bb = np.where(dyn, b, 0)
     t1, t2, amb = tangent_basis(normal32)
     n = normal32.astype(np.float64)
@@ -193,7 +200,7 @@ def solve(a, b, count, colors, n_colors, rows, lin, ang, friction, iterations, P
     w = np.array(ang, np.float64)
     M = len(a)
     P = np.zeros((M, 4, 3)) if P0 is None else np.array(P0, np.float64)
-    dyn = b != GROUND
+    dyn = is_body(b)
     bb = np.where(dyn, b, 0)
     groups = []
     for c in range(n_colors):
@@ -362,6 +369,74 @@ def random_heap(seed, n=512):
                 inertia=None, shape_type=shape, half_extent=he.astype(np.float32))
 
 
+def body_boxes(bodies):
+    """Float64 boxes [lo, hi] (n, 6) of boxes and spheres as set_bodies takes them, without a margin."""
+    R = np.abs(quat_matrices(bodies["rot"]))
+    he = np.asarray(bodies["half_extent"], np.float64)
+    e = np.where((np.asarray(bodies["shape_type"]) == SHAPE_SPHERE)[:, None], he[:, :1], np.einsum("nab,nb->na", R, he))
+    c = np.asarray(bodies["pos"], np.float64)
+    return np.concatenate([c - e, c + e], 1)
+
+
+CONTAINER_GAP = 0.004  # of a wall segment to the nearest body: inside the contact margin of 0.02, and no overlap
+
+
+def heap_container(bodies, pitch=1.9, top=0.0):
+    """A static container for random_heap's bodies: a floor slab whose top is the plane y = `top`, and four walls of one
+    box segment per lattice column (1 long, 0.5 thick, as high as the heap). Each segment's face stands CONTAINER_GAP
+    outside the farthest-reaching body among those it faces, so no body starts in overlap with a wall and the nearest
+    body of every segment starts with a speculative manifold against it; bodies of the lowest layer among those touch
+    floor and wall. Returns (pos, shape_type, half_extent) of set_static_bodies (identity rotations); the slab is static 0."""
+    box = body_boxes(bodies)
+    lo, hi = box[:, :3].min(0), box[:, 3:].max(0)
+    mid, half = 0.5 * (lo + hi), 0.5 * (hi - lo)
+    pos = [[mid[0], top - 0.5, mid[2]]]
+    he = [[half[0] + 3.0, 0.5, half[2] + 3.0]]
+    centres = np.asarray(bodies["pos"], np.float64)
+    height = 0.5 * (hi[1] - top) + 0.5
+    for axis, along in ((0, 2), (2, 0)):
+        cols = np.unique(np.round(centres[:, along] / pitch).astype(np.int64))
+        for c in cols * pitch:
+            faces = (box[:, along] <= c + 0.5) & (box[:, 3 + along] >= c - 0.5)
+            for side in (-1.0, 1.0):
+                reach = box[faces, axis].min() if side < 0 else box[faces, 3 + axis].max()
+                p = [0.0, top + height - 0.5, 0.0]
+                p[axis], p[along] = reach + side * (CONTAINER_GAP + 0.25), c
+                h = [0.0, height, 0.0]
+                h[axis], h[along] = 0.25, 0.5
+                pos.append(p); he.append(h)
+    return dict(pos=np.asarray(pos, np.float32), shape_type=np.full(len(pos), SHAPE_BOX, np.uint32), half_extent=np.asarray(he, np.float32))
+
+
+def static_boxes(seed=21, n_st=120):
+    """Sliding and spinning boxes and spheres on static boxes 12 apart, ONE body on each static (a third of the boxes with
+    a second box on top). Returns (set_bodies arguments, set_static_bodies arguments)."""
+    rng = np.random.default_rng(seed)
+    st_pos = np.column_stack([np.arange(n_st) % 12 * 12.0, np.zeros(n_st), np.arange(n_st) // 12 * 12.0])
+    st_he = np.column_stack([rng.uniform(1.5, 2.5, n_st), np.full(n_st, 0.5), rng.uniform(1.5, 2.5, n_st)])
+    pos, rot, shape, he = [], [], [], []
+    for k in range(n_st):
+        c = st_pos[k]
+        sphere = k % 4 == 3
+        r = rng.uniform(0.4, 0.7)
+        h = np.array([r, r, r]) if sphere else rng.uniform(0.4, 0.7, 3)
+        off = rng.uniform(-0.6, 0.6, 2)
+        pos.append([c[0] + off[0], 0.5 + h[1] - rng.uniform(-0.015, 0.03), c[2] + off[1]])
+        q = np.array([*(rng.normal(size=3) * 0.02), 1.0]) if not sphere else np.array([0, 0, 0, 1.0])
+        rot.append(q / np.linalg.norm(q)); shape.append(SHAPE_SPHERE if sphere else SHAPE_BOX); he.append(h)
+        if k % 3 == 0 and not sphere:  # a box on top: a body-body manifold coloured against the static one
+            h2 = rng.uniform(0.3, 0.5, 3)
+            pos.append([pos[-1][0] + rng.uniform(-0.2, 0.2), pos[-1][1] + h[1] + h2[1] - 0.01, pos[-1][2]])
+            rot.append(np.array([0, 0, 0, 1.0])); shape.append(SHAPE_BOX); he.append(h2)
+    pos, rot, he = (np.asarray(x, np.float32) for x in (pos, rot, he))
+    n = len(pos)
+    lin = np.column_stack([rng.uniform(-4, 4, n), np.zeros(n), rng.uniform(-4, 4, n)]).astype(np.float32)
+    ang = (rng.normal(size=(n, 3)) * 0.5).astype(np.float32)
+    bodies = dict(pos=pos, rot=rot, lin_vel=lin, ang_vel=ang, shape_type=np.asarray(shape, np.uint32), half_extent=he)
+    statics = dict(pos=st_pos.astype(np.float32), shape_type=np.full(n_st, SHAPE_BOX, np.uint32), half_extent=st_he.astype(np.float32))
+    return bodies, statics
+
+
 SHAPE_CAPSULE = 3
 TOWER_MU = 0.5  # the default friction, which varied_tower's census of friction rows is taken with
 
@@ -467,7 +542,7 @@ def velocity_error(out, lin, ang):
     amb = out["ambiguous"]
     skip[out["a"][amb]] = True
     bb = out["b"][amb]
-    skip[bb[bb != GROUND]] = True
+    skip[bb[is_body(bb)]] = True
     keep = ~skip
     err = max(np.abs(np.asarray(lin, np.float64)[keep] - out["lin"][keep]).max(initial=0.0),
               np.abs(np.asarray(ang, np.float64)[keep] - out["ang"][keep]).max(initial=0.0))

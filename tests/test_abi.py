@@ -101,7 +101,9 @@ def test_independent_gpu_checks_share_no_code_with_the_spec_or_the_oracle():
     imports = r"^\s*(?:from|import)\s+([A-Za-z0-9_\.]+)"
     for name, extra in (("test_gpu_independent.py", set()), ("test_gpu_solver_independent.py", {"contact_ref", "material_ref"}),
                         ("test_gpu_halo_independent.py", {"halo_ref", "ctypes", "torch"}),
-                        ("test_gpu_pairs_independent.py", {"pair_ref", "functools", "os", "subprocess", "sys"})):
+                        ("test_gpu_pairs_independent.py", {"pair_ref", "functools", "os", "subprocess", "sys"}),
+                        ("test_gpu_static_independent.py", {"static_ref", "pair_ref", "shape_pair_ref", "contact_ref", "os", "subprocess",
+                                                            "sys", "ctypes"})):
         txt = open(os.path.join(ROOT, "tests", name)).read()
         mods = set(re.findall(imports, txt, flags=re.M))
         assert mods <= {"numpy", "pytest", "physics_amd"} | extra, (name, mods)
@@ -117,6 +119,9 @@ def test_independent_gpu_checks_share_no_code_with_the_spec_or_the_oracle():
     assert "oracle" not in txt and "include/spec" not in txt
     txt = open(os.path.join(ROOT, "tests", "pair_ref.py")).read()  # the pair search's reference: the same rule
     assert set(re.findall(imports, txt, flags=re.M)) == {"numpy"}
+    assert "oracle" not in txt and "include/spec" not in txt
+    txt = open(os.path.join(ROOT, "tests", "static_ref.py")).read()  # the static pair search's reference: numpy and pair_ref
+    assert set(re.findall(imports, txt, flags=re.M)) == {"numpy", "pair_ref"}
     assert "oracle" not in txt and "include/spec" not in txt
 
 

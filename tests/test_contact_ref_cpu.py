@@ -310,3 +310,93 @@ def test_varied_tower_against_the_oracle(ob, case):
             assert carried > 0.5 * m
     print(f"varied tower {case}: largest velocity error {worst:.3g} (MEASURED_VARIED {cr.MEASURED_VARIED:.3g}, TOL_VARIED {cr.TOL_VARIED:.3g})")
     assert worst <= cr.TOL_VARIED / 4
+
+
+# ---------------------------------------------------------------- static colliders as partners
+def _relabelled(man, n):
+    """The manifolds of a world that holds the statics as bodies n + k: those of a body with a body or a static, the
+    static's id written as STATIC_ID_BIT | k (the order by pair stays: n + k and BIT | k sort alike behind every body)."""
+    ids, counts, normals, points = man
+    ids = np.asarray(ids, np.int64)
+    keep = ids[:, 0] < n
+    ids = ids[keep].copy()
+    st = ids[:, 1] >= n
+    ids[st, 1] = cr.STATIC_ID_BIT | (ids[st, 1] - n)
+    return ids, np.asarray(counts)[keep], np.asarray(normals)[keep], np.asarray(points)[keep]
+
+
+def test_static_partners_native_equal_the_extra_body_wrapper(ob):
+    """contact_ref with a static as what it is (a partner id with STATIC_ID_BIT: no body, like the ground) against the
+    wrapper of tests/test_gpu_static.py that models static k as extra body n + k of infinite mass - right under ITS
+    condition of one manifold per static, which this scene meets. Manifolds from the oracle's body path, relabelled:
+    identical colours and velocities."""
+    from test_gpu_static import _ref_update_with_statics
+    bodies, statics = cr.static_boxes(21, 120)
+    n, k = len(bodies["pos"]), len(statics["pos"])
+    both = {key: np.concatenate([bodies[key], statics[key]]) for key in ("pos", "shape_type", "half_extent")}
+    both["rot"] = np.concatenate([bodies["rot"], np.tile(np.float32([0, 0, 0, 1]), (k, 1))])
+    o = oracle_world(ob, both, flags=FLAG_COLLISIONS)
+    o.collide_now()
+    man = _relabelled(o.get_manifolds(), n)
+    b = man[0][:, 1]
+    st_b = b[(b & cr.STATIC_ID_BIT) != 0]
+    assert len(st_b) >= 100 and len(np.unique(st_b)) == len(st_b), "one manifold per static (the wrapper's condition)"
+    assert ((b & cr.STATIC_ID_BIT) == 0).sum() >= 20, "body-body manifolds on top of the static ones"
+    inv_m, inv_I = cr.body_inverses(n)
+    force = np.tile(GRAVITY, (n, 1))
+    pos, lin, ang = (bodies[key].astype(np.float64) for key in ("pos", "lin_vel", "ang_vel"))
+    native = cr.SolverRef(n, cr.Params(DT_S), 8).update(man, pos, lin, ang, inv_m, inv_I, force)
+    wrapped = _ref_update_with_statics(cr.SolverRef(n + k, cr.Params(DT_S), 8), n, statics["pos"].astype(np.float64), man, pos, lin, ang,
+                                       inv_m, inv_I, force)
+    assert np.array_equal(native["colors"], wrapped["colors"]) and native["n_colors"] == wrapped["n_colors"] >= 2
+    assert (native["color_rounds"], native["n_new_manifolds"]) == (wrapped["color_rounds"], wrapped["n_new_manifolds"])
+    assert np.array_equal(native["lin"], wrapped["lin"][:n]) and np.array_equal(native["ang"], wrapped["ang"][:n])
+    assert not wrapped["lin"][n:].any() and np.abs(native["lin"] - lin).max() > 0.1
+    assert np.array_equal(native["impulses"], wrapped["impulses"])
+
+
+def test_statics_shared_by_several_bodies_take_no_colour_of_their_own():
+    """Where the wrapper's condition fails - a slab under many bodies - the two differ, and the native handling is the
+    documented one: bodies on one static share no body, so all their manifolds take colour 0 in one round."""
+    m = 40
+    a = np.arange(m)
+    b = np.full(m, cr.STATIC_ID_BIT | 7)
+    colors, n_colors, rounds, n_new = cr.color_manifolds(a, b, m)
+    assert (colors == 0).all() and (n_colors, rounds, n_new) == (1, 1, m)
+    # a body on the slab and against a wall, with a neighbour: three manifolds at body 0, three colours
+    a = np.array([0, 0, 0, 1])
+    b = np.array([1, cr.STATIC_ID_BIT | 0, cr.STATIC_ID_BIT | 3, cr.STATIC_ID_BIT | 0])
+    colors, n_colors, _, _ = cr.color_manifolds(a, b, 2)
+    assert sorted(colors[:3]) == [0, 1, 2] and colors[3] != colors[0] and n_colors == 3
+    # the priority hashes the full pair: the id of the static matters
+    assert cr.color_priority(0, cr.STATIC_ID_BIT | 0) != cr.color_priority(0, cr.STATIC_ID_BIT | 3) != cr.color_priority(0, cr.GROUND)
+
+
+def test_heap_container_and_its_twin_on_the_ground_plane(ob):
+    """The scene of test_gpu_solver_independent.py::test_heap_in_a_static_container_against_the_float64_solver: no body
+    starts in overlap with a wall segment, every segment has a body within the margin, and the oracle's float32 spread on
+    the twin - the same heap on the ground plane at the slab's height, where a static row has the form of a ground row -
+    is what TOL_COUPLED was taken from."""
+    bodies = cr.random_heap(5)
+    n = len(bodies["pos"])
+    st = cr.heap_container(bodies)
+    box = cr.body_boxes(bodies)
+    he, c = st["half_extent"].astype(np.float64), st["pos"].astype(np.float64)
+    slo, shi = c - he, c + he
+    assert len(c) == 1 + 4 * 12 and shi[0, 1] == 0.0
+    near = 0
+    for k in range(1, len(c)):
+        gap = np.maximum(box[:, :3] - shi[k], slo[k] - box[:, 3:]).max(1)  # boxes against an axis-aligned wall: exact
+        assert gap.min() > 0.5 * cr.CONTAINER_GAP, "no body starts in overlap with a wall"
+        near += int((gap < 0.02 - 1e-3).sum())
+        assert gap.min() < 2 * cr.CONTAINER_GAP
+    low = box[:, 1] < 0.0
+    print(f"\nheap container: {near} bodies within the margin of a wall segment, {int(low.sum())} bodies reach into the slab")
+    assert near >= 48 and low.sum() >= 50
+    o = oracle_world(ob, bodies, gravity=(0, -9.81, 0))
+    ref = cr.SolverRef(n, cr.Params(DT_S), 8)
+    worst = 0.0
+    for out, lin1, ang1, _ in run(o, ref, 6, *cr.body_inverses(n, bodies.get("mass"), bodies.get("inertia")), GRAVITY):
+        worst = max(worst, cr.velocity_error(out, lin1, ang1)[0])
+    print(f"twin of the heap container (ground plane at the slab's height): oracle's spread {worst:.3g}; TOL_COUPLED is 2e-5")
+    assert worst < 2e-5

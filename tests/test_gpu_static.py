@@ -446,29 +446,9 @@ def _ref_update_with_statics(ref_obj, n, st_pos, man, pos, lin, ang, inv_m, inv_
 def test_one_update_on_static_boxes_against_the_float64_solver(solver):
     """Sliding and spinning boxes and spheres on static boxes (some with a second box on top): one update of the
     device's solver against contact_ref.SolverRef, tolerance of the coupled piles of test_gpu_solver_independent."""
-    rng = np.random.default_rng(21)
-    n_st = 120
-    st_pos = np.column_stack([np.arange(n_st) % 12 * 12.0, np.zeros(n_st), np.arange(n_st) // 12 * 12.0])
-    st_he = np.column_stack([rng.uniform(1.5, 2.5, n_st), np.full(n_st, 0.5), rng.uniform(1.5, 2.5, n_st)])
-    pos, rot, shape, he = [], [], [], []
-    for k in range(n_st):
-        c = st_pos[k]
-        sphere = k % 4 == 3
-        r = rng.uniform(0.4, 0.7)
-        h = np.array([r, r, r]) if sphere else rng.uniform(0.4, 0.7, 3)
-        off = rng.uniform(-0.6, 0.6, 2)
-        pos.append([c[0] + off[0], 0.5 + h[1] - rng.uniform(-0.015, 0.03), c[2] + off[1]])
-        q = np.array([*(rng.normal(size=3) * 0.02), 1.0]) if not sphere else np.array([0, 0, 0, 1.0])
-        rot.append(q / np.linalg.norm(q)); shape.append(SPHERE if sphere else BOX); he.append(h)
-        if k % 3 == 0 and not sphere:  # a box on top: a body-body manifold coloured against the static one
-            h2 = rng.uniform(0.3, 0.5, 3)
-            pos.append([pos[-1][0] + rng.uniform(-0.2, 0.2), pos[-1][1] + h[1] + h2[1] - 0.01, pos[-1][2]])
-            rot.append(np.array([0, 0, 0, 1.0])); shape.append(BOX); he.append(h2)
-    pos, rot, he = (np.asarray(x, np.float32) for x in (pos, rot, he))
-    shape = np.asarray(shape, np.uint32)
-    n = len(pos)
-    lin = np.column_stack([rng.uniform(-4, 4, n), np.zeros(n), rng.uniform(-4, 4, n)]).astype(np.float32)
-    ang = (rng.normal(size=(n, 3)) * 0.5).astype(np.float32)
+    bodies, statics = cr.static_boxes(21, 120)  # (the scene moved there as it was: tests/test_contact_ref_cpu.py runs it too)
+    pos, rot, lin, ang, shape, he = (bodies[k] for k in ("pos", "rot", "lin_vel", "ang_vel", "shape_type", "half_extent"))
+    st_pos, st_he, n_st, n = statics["pos"].astype(np.float64), statics["half_extent"], len(statics["pos"]), len(pos)
     flags = COLL | (physics_amd.FLAG_SOLVER_PER_COLOR if solver == "per_color" else 0)
     w = physics_amd.World(physics_amd.default_config(flags=flags, gravity_offset=(0, 0, 0)))
     w.set_bodies(pos, rot=rot, lin_vel=lin, ang_vel=ang, shape_type=shape, half_extent=he)
