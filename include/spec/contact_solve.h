@@ -205,34 +205,40 @@ typedef struct {
     jac_row_t j[4][3];
 } solver_jac_t;
 
-PHYS_HD void jac_row_make(const solver_manifold_t* sm, int k, v3 dir, const m33* IA, const m33* IB, jac_row_t* j) {
+PHYS_HD void jac_row_make(v3 rA, v3 rB, int has_b, v3 dir, const m33* IA, const m33* IB, jac_row_t* j) {
     const v3 zero = v3_make(0.0f, 0.0f, 0.0f);
-    j->aA = v3_cross_f(sm->row[k].rA, dir);
+    j->aA = v3_cross_f(rA, dir);
     j->mA = inertia_mul(IA, j->aA);
-    if (sm->has_b) {
-        j->aB = v3_cross_f(sm->row[k].rB, dir);
+    if (has_b) {
+        j->aB = v3_cross_f(rB, dir);
         j->mB = inertia_mul(IB, j->aB);
     } else {
         j->aB = zero; j->mB = zero;
     }
 }
 
-PHYS_HD void solver_jacobians(const solver_manifold_t* sm, float invMA, const m33* IA, float invMB, const m33* IB,
-                              solver_jac_t* J) {
+/* dir * inverse mass of the two bodies, for d = 0: t1, 1: t2, 2: n (zero for a body B that does not move) */
+PHYS_HD void linear_responses(v3 t1, v3 t2, v3 n, int has_b, float invMA, float invMB, v3 lA[3], v3 lB[3]) {
     const v3 zero = v3_make(0.0f, 0.0f, 0.0f);
     PHYS_UNROLL
     for (int d = 0; d < 3; ++d) {
-        const v3 dir = d == 0 ? sm->t1 : (d == 1 ? sm->t2 : sm->n);
-        J->lA[d] = v3_scale(dir, invMA);
-        J->lB[d] = sm->has_b ? v3_scale(dir, invMB) : zero;
+        const v3 dir = d == 0 ? t1 : (d == 1 ? t2 : n);
+        lA[d] = v3_scale(dir, invMA);
+        lB[d] = has_b ? v3_scale(dir, invMB) : zero;
     }
+}
+
+PHYS_HD void solver_jacobians(const solver_manifold_t* sm, float invMA, const m33* IA, float invMB, const m33* IB,
+                              solver_jac_t* J) {
+    const v3 zero = v3_make(0.0f, 0.0f, 0.0f);
+    linear_responses(sm->t1, sm->t2, sm->n, sm->has_b, invMA, invMB, J->lA, J->lB);
     PHYS_UNROLL
     for (int k = 0; k < 4; ++k) {
         PHYS_UNROLL
         for (int d = 0; d < 3; ++d) {
             jac_row_t* j = &J->j[k][d];
             if (k < sm->count) {
-                jac_row_make(sm, k, d == 0 ? sm->t1 : (d == 1 ? sm->t2 : sm->n), IA, IB, j);
+                jac_row_make(sm->row[k].rA, sm->row[k].rB, sm->has_b, d == 0 ? sm->t1 : (d == 1 ? sm->t2 : sm->n), IA, IB, j);
             } else {
                 j->aA = zero; j->aB = zero; j->mA = zero; j->mB = zero;
             }
@@ -296,6 +302,24 @@ PHYS_HD void warm_match(const manifold_t* m, const warm_t* w, float* pn, float* 
     }
 }
 
+/* The impulse update of a row, the normative arithmetic of the solver: the accumulated impulse moves by the row's lambda
+ * and is clamped - a friction row to the box +-maxf (maxf = friction * the point's normal impulse), a normal row to
+ * >= 0. Returns the lambda that was applied. */
+PHYS_HD float friction_impulse(float mass, float vrel, float maxf, float* acc) {
+    const float lambda = -mass * vrel;
+    const float old = *acc;
+    const float np = det_maxf(-maxf, det_minf(old + lambda, maxf));
+    *acc = np;
+    return np - old;
+}
+PHYS_HD float normal_impulse(float mass, float vrel, float bias, float* acc) {
+    const float lambda = mass * (bias - vrel);
+    const float old = *acc;
+    const float np = det_maxf(old + lambda, 0.0f);
+    *acc = np;
+    return np - old;
+}
+
 /* one row: friction direction t (0, 1) or the normal (t = 2) of point k */
 PHYS_HD void solve_row_dir(solver_manifold_t* sm, int k, int t, const jac_row_t* j, v3 lA, v3 lB, float friction, v3* vA,
                            v3* wA, v3* vB, v3* wB, int apply_only) {
@@ -308,21 +332,10 @@ PHYS_HD void solve_row_dir(solver_manifold_t* sm, int k, int t, const jac_row_t*
     if (t < 2) {
         const v3 dir = t == 0 ? sm->t1 : sm->t2;
         const float vt = row_velocity(dir, j, has_b, *vA, *wA, *vB, *wB);
-        float lambda = -r->tangent_mass[t] * vt;
-        const float maxf = friction * r->pn;
-        const float old = r->pt[t];
-        const float np = det_maxf(-maxf, det_minf(old + lambda, maxf));
-        lambda = np - old;
-        r->pt[t] = np;
-        row_apply(lambda, lA, lB, j, has_b, vA, wA, vB, wB);
+        row_apply(friction_impulse(r->tangent_mass[t], vt, friction * r->pn, &r->pt[t]), lA, lB, j, has_b, vA, wA, vB, wB);
     } else {
         const float vn = row_velocity(sm->n, j, has_b, *vA, *wA, *vB, *wB);
-        float lambda = r->normal_mass * (r->bias - vn);
-        const float old = r->pn;
-        const float np = det_maxf(old + lambda, 0.0f);
-        lambda = np - old;
-        r->pn = np;
-        row_apply(lambda, lA, lB, j, has_b, vA, wA, vB, wB);
+        row_apply(normal_impulse(r->normal_mass, vn, r->bias, &r->pn), lA, lB, j, has_b, vA, wA, vB, wB);
     }
 }
 
@@ -343,21 +356,15 @@ PHYS_HD void solve_manifold(solver_manifold_t* sm, const solver_jac_t* J, float 
 /* ... or made row by row on the way (one quarter of the registers; same values, same results) */
 PHYS_HD void solve_manifold_lazy(solver_manifold_t* sm, float friction, float invMA, const m33* IA, float invMB,
                                  const m33* IB, v3* vA, v3* wA, v3* vB, v3* wB, int apply_only) {
-    const v3 zero = v3_make(0.0f, 0.0f, 0.0f);
     v3 lA[3], lB[3];
-    PHYS_UNROLL
-    for (int d = 0; d < 3; ++d) {
-        const v3 dir = d == 0 ? sm->t1 : (d == 1 ? sm->t2 : sm->n);
-        lA[d] = v3_scale(dir, invMA);
-        lB[d] = sm->has_b ? v3_scale(dir, invMB) : zero;
-    }
+    linear_responses(sm->t1, sm->t2, sm->n, sm->has_b, invMA, invMB, lA, lB);
     PHYS_UNROLL
     for (int k = 0; k < 4; ++k) {
         if (k < sm->count) {
             PHYS_UNROLL
             for (int t = 0; t < 3; ++t) {
                 jac_row_t j;
-                jac_row_make(sm, k, t == 0 ? sm->t1 : (t == 1 ? sm->t2 : sm->n), IA, IB, &j);
+                jac_row_make(sm->row[k].rA, sm->row[k].rB, sm->has_b, t == 0 ? sm->t1 : (t == 1 ? sm->t2 : sm->n), IA, IB, &j);
                 solve_row_dir(sm, k, t, &j, lA[t], lB[t], friction, vA, wA, vB, wB, apply_only);
             }
         }
@@ -385,12 +392,7 @@ PHYS_HD void solve_manifold_geo(geo_manifold_t* gm, int make_masses, int apply_o
     const v3 zero = v3_make(0.0f, 0.0f, 0.0f);
     const int has_b = gm->has_b;
     v3 lA[3], lB[3];
-    PHYS_UNROLL
-    for (int d = 0; d < 3; ++d) {
-        const v3 dir = d == 0 ? gm->t1 : (d == 1 ? gm->t2 : gm->n);
-        lA[d] = v3_scale(dir, invMA);
-        lB[d] = has_b ? v3_scale(dir, invMB) : zero;
-    }
+    linear_responses(gm->t1, gm->t2, gm->n, has_b, invMA, invMB, lA, lB);
     PHYS_UNROLL
     for (int k = 0; k < 4; ++k) {
         if (k < gm->count) {
@@ -400,14 +402,7 @@ PHYS_HD void solve_manifold_geo(geo_manifold_t* gm, int make_masses, int apply_o
             for (int t = 0; t < 3; ++t) {
                 const v3 dir = t == 0 ? gm->t1 : (t == 1 ? gm->t2 : gm->n);
                 jac_row_t j;
-                j.aA = v3_cross_f(rA, dir);                      /* jac_row_make */
-                j.mA = inertia_mul(IA, j.aA);
-                if (has_b) {
-                    j.aB = v3_cross_f(rB, dir);
-                    j.mB = inertia_mul(IB, j.aB);
-                } else {
-                    j.aB = zero; j.mB = zero;
-                }
+                jac_row_make(rA, rB, has_b, dir, IA, IB, &j);
                 if (make_masses) {                               /* direction_mass: its ra, IA ra are aA, mA */
                     float km = invMA + v3_dot_f(j.mA, j.aA);
                     if (has_b) km = (km + invMB) + v3_dot_f(j.mB, j.aB);
@@ -419,22 +414,8 @@ PHYS_HD void solve_manifold_geo(geo_manifold_t* gm, int make_masses, int apply_o
                 }
                 const float mass = gm->mass[k][t];
                 const float vrel = row_velocity(dir, &j, has_b, *vA, *wA, *vB, *wB);
-                float lambda;
-                if (t < 2) {                                     /* solve_row_dir */
-                    float* acc = t == 0 ? &gm->pt0[k] : &gm->pt1[k];
-                    lambda = -mass * vrel;
-                    const float maxf = friction * gm->pn[k];
-                    const float old = *acc;
-                    const float np = det_maxf(-maxf, det_minf(old + lambda, maxf));
-                    lambda = np - old;
-                    *acc = np;
-                } else {
-                    lambda = mass * (gm->bias[k] - vrel);
-                    const float old = gm->pn[k];
-                    const float np = det_maxf(old + lambda, 0.0f);
-                    lambda = np - old;
-                    gm->pn[k] = np;
-                }
+                const float lambda = t < 2 ? friction_impulse(mass, vrel, friction * gm->pn[k], t == 0 ? &gm->pt0[k] : &gm->pt1[k])
+                                           : normal_impulse(mass, vrel, gm->bias[k], &gm->pn[k]);
                 row_apply(lambda, lA[t], lB[t], &j, has_b, vA, wA, vB, wB);
             }
         }

@@ -629,13 +629,14 @@ int32_t phys_get_manifolds(phys_world* w, uint32_t* ids_out, uint32_t* counts_ou
     std::vector<uint32_t> ab(2 * m), c(m);
     std::vector<float> nrm(3 * m), pts(16 * m);
     {
-        std::vector<float> geo(32 * m);  // 128-byte records: {a, b, count, -} {normal, -} 4 x {point, depth} + 32 spare bytes
-        PHYS_HIP_TRY(hipMemcpy(geo.data(), w->man_geo.p, 128 * m, hipMemcpyDeviceToHost));
+        std::vector<float> geo(kManifoldFloats * m);  // the manifold records (records.hpp)
+        PHYS_HIP_TRY(hipMemcpy(geo.data(), w->man_geo.p, kManifoldBytes * m, hipMemcpyDeviceToHost));
+        static_assert(kManifoldWordB == kManifoldWordA + 1, "a and b are copied as one pair");
         for (uint64_t k = 0; k < m; ++k) {
-            const float* g = &geo[32 * k];
-            std::memcpy(&ab[2 * k], g, 8); std::memcpy(&c[k], g + 2, 4);
-            std::memcpy(&nrm[3 * k], g + 4, 12);
-            std::memcpy(&pts[16 * k], g + 8, 64);
+            const float* g = &geo[kManifoldFloats * k];
+            std::memcpy(&ab[2 * k], g + kManifoldWordA, 8); std::memcpy(&c[k], g + kManifoldWordCount, 4);
+            std::memcpy(&nrm[3 * k], g + kManifoldWordNormal, 12);
+            std::memcpy(&pts[16 * k], g + kManifoldWordPoints, 64);
         }
     }
     const std::vector<uint64_t> order = manifold_order(ab.data(), 2, m);

@@ -551,12 +551,12 @@ int32_t collision_alloc(phys_world* w) {
         const uint64_t M = w->max_manifolds;
         PHYS_HIP_TRY(w->man_a.resize(M)); PHYS_HIP_TRY(w->man_b.resize(M));
         PHYS_HIP_TRY(w->man_color.resize(M));
-        PHYS_HIP_TRY(w->man_geo.resize(32 * M));
+        PHYS_HIP_TRY(w->man_geo.resize(kManifoldFloats * M));
         w->warm = sz.warm;
         if (w->warm) {
-            PHYS_HIP_TRY(w->man_geo_prev.resize(32 * M));
-            PHYS_HIP_TRY(w->man_imp.resize(12 * M));
-            PHYS_HIP_TRY(w->man_imp_prev.resize(12 * M));
+            PHYS_HIP_TRY(w->man_geo_prev.resize(kManifoldFloats * M));
+            PHYS_HIP_TRY(w->man_imp.resize(kImpulseFloats * M));
+            PHYS_HIP_TRY(w->man_imp_prev.resize(kImpulseFloats * M));
             PHYS_HIP_TRY(w->man_prev.resize(4));  // only its address is used: "warm starting is on" (the index itself is in man_geo)
         }
         PHYS_HIP_TRY(w->man_prio.resize(M));
@@ -567,19 +567,14 @@ int32_t collision_alloc(phys_world* w) {
         w->ctab_valid = false;
         w->color_epoch = 0;
         PHYS_HIP_TRY(w->color_block_hist.resize((size_t)kMaxColors * 512));
-        w->row_all.free();  // exactly 16 planes of M rows
-        PHYS_HIP_TRY(w->row_all.resize(64 * M));  // 16 planes x M x float4
-        w->row_hdr.point_at(reinterpret_cast<uint32_t*>(w->row_all.p), 4 * M);
-        w->row_n.point_at(w->row_all.p + 4 * M, 4 * M);
-        w->row_tb.point_at(w->row_all.p + 8 * M, 8 * M);
-        w->row_pt.point_at(w->row_all.p + 16 * M, 32 * M);
-        w->row_acc.point_at(w->row_all.p + 48 * M, 16 * M);
+        w->row_all.free();  // exactly kRowPlanes planes of M rows
+        PHYS_HIP_TRY(w->row_all.resize(row_plane_floats(kRowPlanes, M)));
         w->flow_vel.free();  // null unless allocated below: per-colour launches only
         if (sz.flow_buffers) {
             PHYS_HIP_TRY(w->flow_vel.resize(8 * n));
             // tags of an earlier scene must never look like tags of this one
             PHYS_HIP_TRY(hipMemsetAsync(w->flow_vel.p, 0, 8 * n * sizeof(float), w->stream));
-            PHYS_HIP_TRY(hipMemsetAsync(w->row_acc.p, 0, 16 * M * sizeof(float), w->stream));
+            PHYS_HIP_TRY(hipMemsetAsync(w->row_all.p + row_plane_floats(kRowPlaneAcc, M), 0, row_plane_floats(kRowAccPlanes, M) * sizeof(float), w->stream));
             // PHYS_DEBUG_FLOW_EPOCH=<n>: start the tag epoch near its wrap (test of the 16-bit epoch reset)
             w->flow_epoch = debug_switches().flow_epoch;
         }

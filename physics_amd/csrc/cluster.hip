@@ -38,11 +38,6 @@ namespace phys {
 
 // (occupancy, LDS budget and slot size - kClusterPerCu*, kClusterLdsPerCu, kClusterSlotBytes, cluster_lds_bytes: setup.hpp)
 
-// per-row side info packed into row_n.w (as bits): slot (16) | mode (2) per side
-//   mode 0: own cluster, never shared -> LDS only          1: own cluster, shared -> LDS while its tag is current, else granule
-//   mode 2: another cluster's body   -> granules only       3: no body (ground)
-__host__ __device__ __forceinline__ uint32_t side_info(uint32_t slot, uint32_t mode) { return (slot & 0x3FFFu) | (mode << 14); }
-
 // ---- host: spatial clusters from the positions at upload ------------------------------------------------------
 // the (cluster, colour) counters sit behind the 2 n mask words of body_shared, on a 16-byte boundary (the scans read uint4)
 static size_t seg_count_offset(uint64_t n) { return ((size_t)2 * n + 3) & ~(size_t)3; }
@@ -278,25 +273,16 @@ void launch_cluster_sort(phys_world* w, const ColorPlan& plan, StepCounters* sna
 
 // ---- the solver ----------------------------------------------------------------------------------------------
 // Rows of a cluster step are COMPACT (k_rows_build writes them so when cluster_slots != 0): what the solver streams
-// per iteration is 9 planes of 16 bytes instead of 16 -
-//     plane 0      hdr {body a, body b, point count, tickets}
-//     plane 1      n   {normal, per-side slot | publish | mode}
-//     planes 2-5   geo {contact point k (world), bias k}
-//     planes 6-8   acc the 12 accumulated impulses {pn, pt0, pt1} x 4, packed
-//     planes 9-11  the 12 row masses {t1, t2, n} x 4, packed: written by the solver itself in iteration 0, read after
-//     planes 12-13 rows whose body B belongs to ANOTHER cluster: {position of B, 1/m} {inverse inertia diagonal of B}
-//                  (what never changes during a solve; gathering it by body id after the row has arrived was a second
-//                  dependent round trip to memory in the chain of every colour step: 2.08 -> ~1.2 ms on C5)
-// Material worlds (k_rows_build's MAT instance) pack planes 0 differently - no plane more, no load more:
-//     plane 0      hdr {body a, body b, the manifold's friction mu (float bits), tickets | point count}
-//                  the count sits in ticket bits that are never set: bits 6-7 (its low two bits; a rank is below 64) and
-//                  bit 15 (its bit 2; a degree is at most 64)
+// per iteration is 9 planes of 16 bytes instead of 16 (the compact-row planes: records.hpp). The
+// foreign planes hold what never changes during a solve of a body that belongs to ANOTHER cluster: gathering it by body id
+// after the row has arrived was a second dependent round trip to memory in the chain of every colour step (2.08 -> ~1.2 ms
+// on C5). Material worlds (k_rows_build's MAT instance) put the friction into the header and the point
+// count into the ticket word - no plane more, no load more -
 // and everything else solver_prep would have stored (the lever arms) is remade from the contact point and the two body
 // POSITIONS, which live in LDS beside the velocities (solve_manifold_geo: same operations, same bits;
 // tests/test_collide_kat.py holds the three drivers against each other). So k_rows_build reads nothing of the bodies
 // on a cluster step, and a 4-point row is 240 bytes per iteration instead of 320.
-struct ClusterRowArrays { float4* all; uint64_t cap; };
-constexpr int kClusterPlaneHdr = 0, kClusterPlaneN = 1, kClusterPlaneGeo = 2, kClusterPlaneAcc = 6, kClusterPlaneMass = 9, kClusterPlaneForeign = 12;
+struct ClusterRowArrays { float4* all; uint64_t cap; };  // (the planes: records.hpp)
 
 constexpr int kClusterThreads = 256;
 #ifndef PHYS_POLL_SLEEP
@@ -419,8 +405,8 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
         const float4* row = rows.all + d;
         hraw = row[kClusterPlaneHdr * cap];
         nn = row[kClusterPlaneN * cap];
-        fb = row[kClusterPlaneForeign * cap];  // stale (and ignored) unless body B is another cluster's
-        if (DIAG) fi = row[(kClusterPlaneForeign + 1) * cap];
+        fb = row[kClusterPlaneForeignB * cap];  // stale (and ignored) unless body B is another cluster's
+        if (DIAG) fi = row[(kClusterPlaneForeignB + 1) * cap];
 #pragma unroll
         for (int k = 0; k < 4; ++k) geo[k] = row[(kClusterPlaneGeo + k) * cap];
 #pragma unroll
@@ -447,35 +433,33 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
             // the lane's row is never of an earlier colour of this iteration (it would have been solved then)
             while (have && lit == it && d < seg_hi) {
                 const uint32_t d_row = d;
-                // MAT: hdr.z is the row's friction, the point count rides in spare ticket bits (layout above)
+                // MAT: hdr.z is the row's friction, the point count rides in the ticket word
                 const uint32_t hw = __float_as_uint(hraw.w);
-                const uint4 h = MAT ? make_uint4(__float_as_uint(hraw.x), __float_as_uint(hraw.y), ((hw >> 6) & 3u) | ((hw >> 13) & 4u), hw & 0xFFFF7F3Fu)
+                const uint4 h = MAT ? make_uint4(__float_as_uint(hraw.x), __float_as_uint(hraw.y), ticket_count(hw), ticket_without_count(hw))
                                     : make_uint4(__float_as_uint(hraw.x), __float_as_uint(hraw.y), __float_as_uint(hraw.z), hw);
-                const uint32_t info = __float_as_uint(nn.w);
-                // slot (13 bits) | publish (1) | mode (2) per side. publish: the NEXT update of this (shared, own) body is
-                // made by another workgroup, so this update must reach the granules; otherwise it stays in LDS
-                const uint32_t modeA = (info >> 14) & 3u, modeB = (info >> 30) & 3u;
-                const uint32_t slotA = info & 0x1FFFu, slotB = (info >> 16) & 0x1FFFu;
-                const bool pubA = (info >> 13) & 1u, pubB = (info >> 29) & 1u;
+                // the side word. publish: the NEXT update of this (shared, own) body is made by another workgroup, so this
+                // update must reach the granules; otherwise it stays in LDS
+                const ClusterSide sideA = cluster_side_decode(__float_as_uint(nn.w), false), sideB = cluster_side_decode(__float_as_uint(nn.w), true);
+                const uint32_t modeA = sideA.mode, modeB = sideB.mode, slotA = sideA.slot, slotB = sideB.slot;
+                const bool pubA = sideA.publish, pubB = sideB.publish;
                 geo_manifold_t gm;
                 gm.count = (int)h.z;
                 gm.has_b = !PHYS_IS_STATIC_PARTNER(h.y);
                 gm.n = v3_make(nn.x, nn.y, nn.z);
                 tangent_basis(gm.n, &gm.t1, &gm.t2);
+                impulses_unpack(acc[0], acc[1], acc[2], gm.pn, gm.pt0, gm.pt1);
                 {
-                    const float flat[12] = {acc[0].x, acc[0].y, acc[0].z, acc[0].w, acc[1].x, acc[1].y, acc[1].z, acc[1].w,
-                                            acc[2].x, acc[2].y, acc[2].z, acc[2].w};
-                    const float flam[12] = {mas[0].x, mas[0].y, mas[0].z, mas[0].w, mas[1].x, mas[1].y, mas[1].z, mas[1].w,
-                                            mas[2].x, mas[2].y, mas[2].z, mas[2].w};
+                    float m_t1[4], m_t2[4], m_n[4];  // the row masses travel in the impulse record's packing
+                    impulses_unpack(mas[0], mas[1], mas[2], m_t1, m_t2, m_n);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         gm.pt[k] = v3_make(geo[k].x, geo[k].y, geo[k].z);
                         gm.bias[k] = geo[k].w;
-                        gm.pn[k] = flat[3 * k]; gm.pt0[k] = flat[3 * k + 1]; gm.pt1[k] = flat[3 * k + 2];
-                        gm.mass[k][0] = flam[3 * k]; gm.mass[k][1] = flam[3 * k + 1]; gm.mass[k][2] = flam[3 * k + 2];
+                        gm.mass[k][0] = m_t1[k]; gm.mass[k][1] = m_t2[k]; gm.mass[k][2] = m_n[k];
                     }
                 }
-                const uint32_t rankA = h.w & 0xFFu, degA = (h.w >> 8) & 0xFFu, rankB = (h.w >> 16) & 0xFFu, degB = h.w >> 24;
+                const RowTicket tk = ticket_decode(h.w);
+                const uint32_t rankA = tk.rankA, degA = tk.degA, rankB = tk.rankB, degB = tk.degB;
                 const uint32_t tA = it * degA + rankA, tB = it * degB + rankB;
                 const bool finalA = last_it && rankA + 1 == degA, finalB = last_it && rankB + 1 == degB;
                 // ---- the two bodies
@@ -487,33 +471,33 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                 for (int k = 0; k < 9; ++k) { IA.m[k] = 0.0f; IB.m[k] = 0.0f; }
                 v3 vA0 = v3_make(0.0f, 0.0f, 0.0f);
                 vA = vA0; wA = vA0; xA = vA0; ima = 0.0f;
-                if (modeA == 0u || modeA == 1u) {  // A at home here (always, unless it has no home at all)
+                if (cluster_side_at_home(modeA)) {  // A at home here (always, unless it has no home at all)
                     const float4* sa = s_body + 4 * slotA;
                     const float4 la = sa[0], lb = sa[1], lc = sa[2];
                     vA = v3_make(la.x, la.y, la.z); wA = v3_make(lb.x, lb.y, lb.z); ima = lb.w;
                     xA = v3_make(lc.x, lc.y, lc.z);
                     if (DIAG) { const float4 li = sa[3]; IA.m[0] = li.x; IA.m[4] = li.y; IA.m[8] = li.z; }
-                    if (modeA == 1u) needA = __float_as_uint(la.w) != (etag | tA);  // a remote row made the update before this one
+                    if (modeA == kSideShared) needA = __float_as_uint(la.w) != (etag | tA);  // a remote row made the update before this one
                 } else {
                     // a body without a home (dynamic clusters beyond their capacity): like a foreign body B, its constants
-                    // came with the row (planes 14, 15) - fetched here, not ahead: the case is rare by construction
-                    const float4 fa = rows.all[(size_t)(kClusterPlaneForeign + 2) * cap + d_row];
+                    // came with the row - fetched here, not ahead: the case is rare by construction
+                    const float4 fa = rows.all[(size_t)kClusterPlaneForeignA * cap + d_row];
                     xA = v3_make(fa.x, fa.y, fa.z); ima = fa.w;
                     if (DIAG) {
-                        const float4 fia = rows.all[(size_t)(kClusterPlaneForeign + 3) * cap + d_row];
+                        const float4 fia = rows.all[(size_t)(kClusterPlaneForeignA + 1) * cap + d_row];
                         IA.m[0] = fia.x; IA.m[4] = fia.y; IA.m[8] = fia.z;
                     }
                     if (tA == 0u) { const BodyVel A0 = ld_vel(vel, h.x); vA = A0.v; wA = A0.w; }
                     needA = tA != 0u;
                 }
-                if (modeB == 0u || modeB == 1u) {
+                if (cluster_side_at_home(modeB)) {
                     const float4* sb = s_body + 4 * slotB;
                     const float4 la = sb[0], lb = sb[1], lc = sb[2];
                     vB = v3_make(la.x, la.y, la.z); wB = v3_make(lb.x, lb.y, lb.z); imb = lb.w;
                     xB = v3_make(lc.x, lc.y, lc.z);
                     if (DIAG) { const float4 li = sb[3]; IB.m[0] = li.x; IB.m[4] = li.y; IB.m[8] = li.z; }
-                    if (modeB == 1u) needB = __float_as_uint(la.w) != (etag | tB);
-                } else if (modeB == 2u) {
+                    if (modeB == kSideShared) needB = __float_as_uint(la.w) != (etag | tB);
+                } else if (modeB == kSideForeign) {
                     xB = v3_make(fb.x, fb.y, fb.z); imb = fb.w;  // came with the row
                     if (DIAG) { IB.m[0] = fi.x; IB.m[4] = fi.y; IB.m[8] = fi.z; }
                     if (tB == 0u) {  // first update of that body in this solve (iteration 0 only): its state is still in `vel`
@@ -548,50 +532,52 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                         }
                     }
                 }
-                if (GUARDED && late && atomicCAS(&ctr->debug[0], 0u, 0xC1u) == 0u) {
+                if (GUARDED && late && atomicCAS(&ctr->debug[0], 0u, kClusterTimeoutMark) == 0u) {
                     // the first lane to give up says what it waited for (outside the poll loop, and without reading the granules again:
                     // cold code in the row path costs the whole kernel 1-2 % at its register limit - so only in the guarded variant,
                     // where a time-out is a defect; in the other one it means PHYS_FLAG_EXCLUSIVE_GPU was set on a GPU that is shared)
-                    ctr->debug[1] = cluster | (gridDim.x << 16);
-                    ctr->debug[2] = d_row; ctr->debug[3] = h.x; ctr->debug[4] = h.y;
-                    ctr->debug[5] = (tA & 0xFFFFu) | (tB << 16);
-                    ctr->debug[6] = late | (modeA << 4) | (modeB << 8);
-                    ctr->debug[7] = (col & 0xFFu) | ((it & 0xFFu) << 8);
+                    cluster_timeout_note_encode(ClusterTimeoutNote{cluster, gridDim.x, d_row, h.x, h.y, tA, tB, late & 1u, late >> 1, modeA, modeB, col, it},
+                                                ctr->debug);
                 }
                 if (!dead) {
                     solve_manifold_geo(&gm, it == 0u, (warm_sweep != 0u && it == 0u) ? 1 : 0, MAT ? hraw.z : friction, xA, ima, &IA, xB, imb, &IB, &vA, &wA, &vB, &wB);
                     // ---- write back
-                    if (modeA == 0u || modeA == 1u) {
+                    if (cluster_side_at_home(modeA)) {
                         s_body[4 * slotA] = make_float4(vA.x, vA.y, vA.z, __uint_as_float(etag | (tA + 1u)));
                         s_body[4 * slotA + 1] = make_float4(wA.x, wA.y, wA.z, ima);
                     }
-                    if (modeA == 1u || modeA == 2u) {
+                    if (modeA == kSideShared || modeA == kSideForeign) {
                         if (finalA) { st3(vel + 8 * (size_t)h.x, 0, vA); st3(vel + 8 * (size_t)h.x + 4, 0, wA); }  // the masses stay where they are
-                        else if (modeA == 2u || pubA) { st_granule(rv, h.x * 32u, vA, etag | (tA + 1u)); st_granule(rv, h.x * 32u + 16u, wA, etag | (tA + 1u)); }
+                        else if (modeA == kSideForeign || pubA) { st_granule(rv, h.x * 32u, vA, etag | (tA + 1u)); st_granule(rv, h.x * 32u + 16u, wA, etag | (tA + 1u)); }
                     }
-                    if (modeB == 0u || modeB == 1u) {
+                    if (cluster_side_at_home(modeB)) {
                         s_body[4 * slotB] = make_float4(vB.x, vB.y, vB.z, __uint_as_float(etag | (tB + 1u)));
                         s_body[4 * slotB + 1] = make_float4(wB.x, wB.y, wB.z, imb);
                     }
-                    if (modeB == 1u || modeB == 2u) {
+                    if (modeB == kSideShared || modeB == kSideForeign) {
                         if (finalB) { st3(vel + 8 * (size_t)h.y, 0, vB); st3(vel + 8 * (size_t)h.y + 4, 0, wB); }
-                        else if (modeB == 2u || pubB) { st_granule(rv, h.y * 32u, vB, etag | (tB + 1u)); st_granule(rv, h.y * 32u + 16u, wB, etag | (tB + 1u)); }
+                        else if (modeB == kSideForeign || pubB) { st_granule(rv, h.y * 32u, vB, etag | (tB + 1u)); st_granule(rv, h.y * 32u + 16u, wB, etag | (tB + 1u)); }
                     }
+                    float4 a0, a1, a2;  // the impulses as the record and the compact rows pack them
+                    impulses_pack(gm.pn, gm.pt0, gm.pt1, a0, a1, a2);
                     if (last_it && man_imp) {  // the solve's last sweep: remembered for the next update (contact_solve.h)
-                        float4* o = reinterpret_cast<float4*>(man_imp) + 3 * (size_t)row_src[d_row];
-                        o[0] = make_float4(gm.pn[0], gm.pt0[0], gm.pt1[0], gm.pn[1]);
-                        o[1] = make_float4(gm.pt0[1], gm.pt1[1], gm.pn[2], gm.pt0[2]);
-                        o[2] = make_float4(gm.pt1[2], gm.pn[3], gm.pt0[3], gm.pt1[3]);
+                        float4* o = reinterpret_cast<float4*>(man_imp) + kImpulseVecs * (size_t)row_src[d_row];
+                        o[0] = a0; o[1] = a1; o[2] = a2;
                     }
                     if (!last_it) {  // impulses of points beyond the count are whatever came in: never used
                         float4* out = rows.all + d_row;
-                        out[(kClusterPlaneAcc + 0) * cap] = make_float4(gm.pn[0], gm.pt0[0], gm.pt1[0], gm.pn[1]);
-                        if (gm.count > 1) out[(kClusterPlaneAcc + 1) * cap] = make_float4(gm.pt0[1], gm.pt1[1], gm.pn[2], gm.pt0[2]);
-                        if (gm.count > 2) out[(kClusterPlaneAcc + 2) * cap] = make_float4(gm.pt1[2], gm.pn[3], gm.pt0[3], gm.pt1[3]);
+                        out[(kClusterPlaneAcc + 0) * cap] = a0;
+                        if (gm.count > 1) out[(kClusterPlaneAcc + 1) * cap] = a1;
+                        if (gm.count > 2) out[(kClusterPlaneAcc + 2) * cap] = a2;
                         if (it == 0u) {
-                            out[(kClusterPlaneMass + 0) * cap] = make_float4(gm.mass[0][0], gm.mass[0][1], gm.mass[0][2], gm.mass[1][0]);
-                            if (gm.count > 1) out[(kClusterPlaneMass + 1) * cap] = make_float4(gm.mass[1][1], gm.mass[1][2], gm.mass[2][0], gm.mass[2][1]);
-                            if (gm.count > 2) out[(kClusterPlaneMass + 2) * cap] = make_float4(gm.mass[2][2], gm.mass[3][0], gm.mass[3][1], gm.mass[3][2]);
+                            const float m_t1[4] = {gm.mass[0][0], gm.mass[1][0], gm.mass[2][0], gm.mass[3][0]};
+                            const float m_t2[4] = {gm.mass[0][1], gm.mass[1][1], gm.mass[2][1], gm.mass[3][1]};
+                            const float m_n[4] = {gm.mass[0][2], gm.mass[1][2], gm.mass[2][2], gm.mass[3][2]};
+                            float4 m0, m1, m2;
+                            impulses_pack(m_t1, m_t2, m_n, m0, m1, m2);
+                            out[(kClusterPlaneMass + 0) * cap] = m0;
+                            if (gm.count > 1) out[(kClusterPlaneMass + 1) * cap] = m1;
+                            if (gm.count > 2) out[(kClusterPlaneMass + 2) * cap] = m2;
                         }
                     }
                 }

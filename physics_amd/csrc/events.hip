@@ -46,27 +46,30 @@ __global__ __launch_bounds__(kEventThreads) void k_events_begin(const StepCounte
         bool emit = false;
         uint4 w0 = make_uint4(0, 0, 0, 0), w1 = w0, w2 = w0;
         if (m < M) {
-            const float4* rec = reinterpret_cast<const float4*>(man_geo) + 8 * (size_t)m;
-            const float4 r0 = rec[0], r1 = rec[1];
-            const uint32_t prev_m = __float_as_uint(r1.w);
-            if (prev_m != 0xFFFFFFFFu) {
+            const float4* rec = reinterpret_cast<const float4*>(man_geo) + kManifoldVecs * (size_t)m;
+            const float4 r0 = rec[kManifoldVecHead], r1 = rec[kManifoldVecNormal];
+            const uint32_t prev_m = manifold_prev_index(r1);
+            if (prev_m != kNoPrevManifold) {
                 // pairs are unique: no two lanes write one word
                 if ((uint64_t)prev_m < max_manifolds) ev_matched[prev_m] = stamp;
             } else {
                 emit = true;
-                const uint32_t count = __float_as_uint(r0.z);
-                const float4 p0 = rec[2], p1 = rec[3], p2 = rec[4], p3 = rec[5];
-                const float4* imp = reinterpret_cast<const float4*>(man_imp) + 3 * (size_t)m;
-                const float4 i0 = imp[0], i1 = imp[1], i2 = imp[2];  // {pn, pt0, pt1} x 4, packed
+                const ManifoldHead head = manifold_head_decode(r0);
+                const uint32_t count = head.count;
+                const float4 p0 = rec[kManifoldVecPoint], p1 = rec[kManifoldVecPoint + 1], p2 = rec[kManifoldVecPoint + 2], p3 = rec[kManifoldVecPoint + 3];
+                const float4* imp = reinterpret_cast<const float4*>(man_imp) + kImpulseVecs * (size_t)m;
+                const float4 i0 = imp[0], i1 = imp[1], i2 = imp[2];
+                const float pn[4] = {impulses_float(i0, i1, i2, impulses_point_offset(0)), impulses_float(i0, i1, i2, impulses_point_offset(1)),
+                                     impulses_float(i0, i1, i2, impulses_point_offset(2)), impulses_float(i0, i1, i2, impulses_point_offset(3))};
                 // the deepest point: largest depth, lowest index on a tie
                 float4 best = p0;
                 if (count > 1u && p1.w > best.w) best = p1;
                 if (count > 2u && p2.w > best.w) best = p2;
                 if (count > 3u && p3.w > best.w) best = p3;
-                const float n0 = count > 0u ? i0.x : 0.0f, n1 = count > 1u ? i0.w : 0.0f;
-                const float n2 = count > 2u ? i1.z : 0.0f, n3 = count > 3u ? i2.y : 0.0f;
+                const float n0 = count > 0u ? pn[0] : 0.0f, n1 = count > 1u ? pn[1] : 0.0f;
+                const float n2 = count > 2u ? pn[2] : 0.0f, n3 = count > 3u ? pn[3] : 0.0f;
                 const float impulse = ((n0 + n1) + n2) + n3;
-                w0 = make_uint4(__float_as_uint(r0.x), __float_as_uint(r0.y), PHYS_CONTACT_BEGIN, step);
+                w0 = make_uint4(head.a, head.b, PHYS_CONTACT_BEGIN, step);
                 w1 = make_uint4(__float_as_uint(best.x), __float_as_uint(best.y), __float_as_uint(best.z), __float_as_uint(impulse));
                 w2 = make_uint4(__float_as_uint(r1.x), __float_as_uint(r1.y), __float_as_uint(r1.z), 0u);
             }
@@ -91,7 +94,8 @@ __global__ __launch_bounds__(kEventThreads) void k_events_end(uint64_t max_manif
         uint4 w0 = make_uint4(0, 0, 0, 0);
         if (k < M && ev_matched[k] != stamp) {
             emit = true;
-            const uint2 ab = *reinterpret_cast<const uint2*>(man_geo_prev + 32 * (size_t)k);
+            static_assert(kManifoldWordA == 0 && kManifoldWordB == 1, "a and b are the record's first eight bytes");
+            const uint2 ab = *reinterpret_cast<const uint2*>(man_geo_prev + kManifoldFloats * (size_t)k);
             w0 = make_uint4(ab.x, ab.y, PHYS_CONTACT_END, step);
         }
         const unsigned long long slot = slots_reserve_flag(emit, trip, sh, &st->cursor);
@@ -207,17 +211,18 @@ int32_t phys_get_contact_impulses(phys_world* w, float* out, uint64_t cap, uint6
     const uint64_t m = (uint64_t)counted < w->max_manifolds ? counted : w->max_manifolds;
     *n_manifolds = m;
     if (!out || m == 0) return PHYS_OK;
-    // {a, b, count, -} of every record (16 bytes out of each 128-byte line) and the 48-byte impulse records, storage order
+    // the head element of every manifold record and the impulse records (records.hpp), storage order
     std::vector<uint32_t> head(4 * m);
-    std::vector<float> imp(12 * m);
-    PHYS_HIP_TRY(hipMemcpy2DAsync(head.data(), 16, w->man_geo.p, 128, 16, m, hipMemcpyDeviceToHost, w->stream));
-    PHYS_HIP_TRY(hipMemcpyAsync(imp.data(), w->man_imp.p, 48 * m, hipMemcpyDeviceToHost, w->stream));
+    std::vector<float> imp(kImpulseFloats * m);
+    PHYS_HIP_TRY(hipMemcpy2DAsync(head.data(), 16, w->man_geo.p + 4 * kManifoldVecHead, kManifoldBytes, 16, m, hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipMemcpyAsync(imp.data(), w->man_imp.p, kImpulseFloats * sizeof(float) * m, hipMemcpyDeviceToHost, w->stream));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    const std::vector<uint64_t> order = manifold_order(head.data(), 4, m);  // phys_get_manifolds' order
+    const std::vector<uint64_t> order = manifold_order(head.data() + kManifoldWordA, 4, m);  // phys_get_manifolds' order
     for (uint64_t k = 0; k < m && k < cap; ++k) {
         const uint64_t s = order[k];
-        const uint32_t count = head[4 * s + 2];
-        for (uint32_t q = 0; q < 12; ++q) out[12 * k + q] = q / 3 < count ? imp[12 * s + q] : 0.0f;
+        const uint32_t count = head[4 * s + kManifoldWordCount];
+        for (uint32_t q = 0; q < kImpulseFloats; ++q)
+            out[kImpulseFloats * k + q] = q / kImpulseFloatsPerPoint < count ? imp[kImpulseFloats * s + q] : 0.0f;
     }
     return PHYS_OK;
 }

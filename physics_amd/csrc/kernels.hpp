@@ -12,6 +12,7 @@
 #include "../../include/spec/vec.h"
 #include "world.hpp"
 #include "readout.hpp"
+#include "records.hpp"
 #include "wave.hpp"
 
 static_assert(PHYS_MAX_COLORS == phys::kMaxColors, "colour limit mismatch");
@@ -111,7 +112,7 @@ __device__ __forceinline__ v3 granule_v3(u32x4 g) {
 }
 
 // Persistent colouring: ONE hash table (a << 32 | b) -> {colour, update stamp} that lives across updates. Open addressing,
-// linear probing, 16-byte entries {key, stamp << 32 | manifold index << 6 | colour} (the index of the pair's manifold in
+// linear probing, 16-byte entries {key, value word (records.hpp: stamp, manifold index, colour)} (the index of the pair's manifold in
 // the update that stamped the entry: what the next update warm-starts from); at least 1.5 slots per manifold SLOT.
 //   * the narrow phase of update E looks every manifold up: an exact key match whose stamp is E - 1 ("was there in the
 //     previous update") keeps its colour and is re-stamped E on the spot - one 8-byte store to the line the probe has
@@ -129,7 +130,6 @@ __device__ __forceinline__ v3 granule_v3(u32x4 g) {
 // Round 1-2a rebuilt a table per update inside k_rows_build (an atomic and two scattered stores per manifold, plus the
 // sparse clear of the other table): 0.26 of k_rows_build's 0.50 ms on C5. The layout depends on arrival order, the
 // answers (exact key + stamp matches) do not.
-constexpr uint32_t kUncolored = 0xFFFFFFFFu;   // man_color of a manifold that kept no colour (narrowphase.hip -> coloring.hip)
 constexpr uint32_t kColorTableMaxWalk = 4096;  // slots a look-up may walk before it gives up (a full table must not hang a wave)
 struct ColorTableJob {
     ulonglong2* tab;  // null: nothing to do
@@ -141,7 +141,7 @@ struct ColorTableJob {
 
 __device__ __forceinline__ void color_table_insert(const ColorTableJob& job, uint32_t a, uint32_t b, uint32_t m, StepCounters* ctr) {
     const unsigned long long key = ((unsigned long long)a << 32) | b;
-    const unsigned long long val = ((unsigned long long)job.stamp << 32) | ((unsigned long long)(m & 0x3FFFFFFu) << 6) | (job.man_color[m] & 63u);
+    const unsigned long long val = table_value_encode(job.stamp, m, table_color_field(job.man_color[m]));
     uint32_t h = (uint32_t)(job.man_prio[m] >> 20) & job.mask;
     // bounded (see the walk in k_narrowphase); a manifold that finds no slot would be coloured afresh next time where the
     // oracle keeps its colour: the update is flagged (bit 6), never a silent divergence
@@ -149,11 +149,11 @@ __device__ __forceinline__ void color_table_insert(const ColorTableJob& job, uin
         if (walked == 4u * kColorTableMaxWalk) { flag_overflow(ctr, kOvfColorTable); return; }
         unsigned long long* vp = &job.tab[h].y;
         const unsigned long long seen = __hip_atomic_load(vp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((uint32_t)(seen >> 32) != job.stamp && atomicCAS(vp, seen, val) == seen) {
+        if (table_value_stamp(seen) != job.stamp && atomicCAS(vp, seen, val) == seen) {
             job.tab[h].x = key;
             return;
         }
-        if ((uint32_t)(__hip_atomic_load(vp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32) == job.stamp) h = (h + 1) & job.mask;
+        if (table_value_stamp(__hip_atomic_load(vp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == job.stamp) h = (h + 1) & job.mask;
         // else: somebody else's CAS on a dead slot failed too, or the value changed under us - look at the slot again
     }
 }

@@ -170,9 +170,11 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
                         const ulonglong2 e = (have_early && h == early_h) ? early : cache[h];
                         have_early = false;
                         if (e.x == key) {
-                            if ((uint32_t)(e.y >> 32) + 1u == stamp) {
-                                col = (uint32_t)e.y & 63u;
-                                prev_m = ((uint32_t)e.y >> 6);  // the pair's manifold of the previous update
+                            if (table_value_stamp(e.y) + 1u == stamp) {
+                                // (the fields by the header's constants, not through table_value_color / _index: with the
+                                // calls hipcc loads the value word in a second, dependent round trip after the key matched)
+                                col = (uint32_t)e.y & kTableColorMask;
+                                prev_m = (uint32_t)e.y >> kTableColorBits;  // the pair's manifold of the previous update
                                 kept_h = h;                     // re-stamped below, once this update's slot is known
                             }
                             ended = true;
@@ -258,23 +260,21 @@ __global__ __launch_bounds__(kNpThreads) void k_narrowphase(
                     man_prio[slot] = it.prio;
                     man_color[slot] = col;
                     // a kept entry is re-stamped with this update's manifold index (one 8-byte store to the line the probe read)
-                    if (col != kUncolored) cache[it.kept_h].y = ((unsigned long long)stamp << 32) | ((unsigned long long)((uint32_t)slot & 0x3FFFFFFu) << 6) | col;
+                    if (col != kUncolored) cache[it.kept_h].y = table_value_encode(stamp, (uint32_t)slot, col);
                     if (man_prev) {
-                        float4* imp = reinterpret_cast<float4*>(man_imp) + 3 * slot;
-                        imp[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); imp[1] = imp[0]; imp[2] = imp[0];
+                        float4* imp = reinterpret_cast<float4*>(man_imp) + kImpulseVecs * slot;
+                        for (uint32_t k = 0; k < kImpulseVecs; ++k) imp[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                     }
                     // (Measured and dropped: staging the records of a wave in LDS and copying them out as whole 128-byte lines -
                     // 4.5 write requests per manifold become 2 - left the kernel at 0.52 ms on C5: it waits on its chain of
                     // dependent round trips, not on the write path.)
-                    float4* o = reinterpret_cast<float4*>(man_geo) + 8 * slot;  // one 128-byte line per manifold, 96 bytes used
-                    // {a, b, count, kept colour + 1 (0: new in this update, coloured later: man_color)} {normal, index of the pair's
-                    // manifold in the previous update or ~0}: what k_rows_build would otherwise gather, 4 bytes out of a 64-byte
-                    // sector each, from two more arrays through the row permutation
-                    o[0] = make_float4(__uint_as_float(a), __uint_as_float(b), __uint_as_float((uint32_t)m.count),
-                                       __uint_as_float(col != kUncolored ? col + 1u : 0u));
-                    o[1] = make_float4(m.normal.x, m.normal.y, m.normal.z, __uint_as_float(it.prev_m));
+                    float4* o = reinterpret_cast<float4*>(man_geo) + kManifoldVecs * slot;  // one 128-byte line per manifold (records.hpp)
+                    // ids, count, kept colour and the previous update's index ride in the record: k_rows_build would otherwise
+                    // gather them, 4 bytes out of a 64-byte sector each, from two more arrays through the row permutation
+                    manifold_head_encode(ManifoldHead{a, b, (uint32_t)m.count, col}, o[kManifoldVecHead]);  // (one 16-byte store)
+                    o[kManifoldVecNormal] = make_float4(m.normal.x, m.normal.y, m.normal.z, __uint_as_float(it.prev_m));
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) o[2 + k] = make_float4(m.pt[k].x, m.pt[k].y, m.pt[k].z, m.depth[k]);
+                    for (int k = 0; k < 4; ++k) o[kManifoldVecPoint + k] = make_float4(m.pt[k].x, m.pt[k].y, m.pt[k].z, m.depth[k]);
                 }
                 if (it.uncolored) {
                     // (a manifold beyond the capacity - update flagged, never solved - names the last slot: the list must hold

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "records.hpp"
 #include "setup.hpp"
 
 namespace phys {
@@ -94,27 +95,29 @@ inline bool trigger_bits_to_csr(const uint32_t* bits, uint64_t words, uint64_t n
 }
 
 // phys_sync: the overflow bits raised since the last call (kOvf*) and the eight debug words -> the code and the text. One error
-// per call, in this precedence: corrupt row, hand-off time-out (with k_solve_cluster's note when debug[0] == 0xC1), colours,
+// per call, in this precedence: corrupt row, hand-off time-out (with k_solve_cluster's note; both notes: records.hpp), colours,
 // halo, colour table, then pairs / manifolds.
 struct SyncError {
     int32_t code = PHYS_OK;
     std::string message;
 };
 inline SyncError sync_error(uint32_t bits, const uint32_t g[8]) {
-    if (bits & kOvfCorruptRow)
-        return {PHYS_ERR_HIP, "internal error: a solver row names no body of this world and was refused (row " +
-                              std::to_string(g[0]) + ": a " + std::to_string(g[1]) + ", b " + std::to_string(g[2]) + ", points " +
-                              std::to_string(g[3]) + "; colour " + std::to_string(g[6]) + " rows [" + std::to_string(g[4]) + ", " +
-                              std::to_string(g[5]) + "), tile base " + std::to_string(g[7]) + ")"};
-    if ((bits & kOvfHandoff) && g[0] == 0xC1u)  // what the first lane of k_solve_cluster to give up was waiting for
+    const auto s = [](uint32_t v) { return std::to_string(v); };
+    if (bits & kOvfCorruptRow) {
+        const CorruptRowNote n = corrupt_row_note_decode(g);
+        return {PHYS_ERR_HIP, "internal error: a solver row names no body of this world and was refused (row " + s(n.row) + ": a " + s(n.a) +
+                              ", b " + s(n.b) + ", points " + s(n.count) + "; colour " + s(n.color) + " rows [" + s(n.color_start) + ", " +
+                              s(n.color_end) + "), tile base " + s(n.tile_base) + ")"};
+    }
+    if ((bits & kOvfHandoff) && g[0] == kClusterTimeoutMark) {  // what the first lane of k_solve_cluster to give up was waiting for
+        const ClusterTimeoutNote n = cluster_timeout_note_decode(g);
         return {PHYS_ERR_HIP, "contact solver hand-off timed out (k_solve_cluster) in a step since the last phys_sync; velocities "
-                              "are invalid from that step on. First lane to give up: cluster " + std::to_string(g[1] & 0xFFFFu) + " of " + std::to_string(g[1] >> 16) + ", row " +
-                              std::to_string(g[2]) + ", bodies " + std::to_string(g[3]) + " / " + std::to_string(g[4]) +
-                              ", tickets " + std::to_string(g[5] & 0xFFFFu) + " / " + std::to_string(g[5] >> 16) + ", waiting A/B " +
-                              std::to_string(g[6] & 1u) + "/" + std::to_string((g[6] >> 1) & 1u) + ", modes " +
-                              std::to_string((g[6] >> 4) & 3u) + "/" + std::to_string((g[6] >> 8) & 3u) + ", iteration " +
-                              std::to_string((g[7] >> 8) & 0xFFu) + ", colour " + std::to_string(g[7] & 0xFFu) +
+                              "are invalid from that step on. First lane to give up: cluster " + s(n.cluster) + " of " + s(n.clusters) + ", row " +
+                              s(n.row) + ", bodies " + s(n.a) + " / " + s(n.b) + ", tickets " + s(n.ticketA) + " / " + s(n.ticketB) +
+                              ", waiting A/B " + s(n.waitA) + "/" + s(n.waitB) + ", modes " + s(n.modeA) + "/" + s(n.modeB) + ", iteration " +
+                              s(n.iteration) + ", colour " + s(n.color) +
                               ". If other work shares this GPU with phys_update, create the world WITHOUT PHYS_FLAG_EXCLUSIVE_GPU"};
+    }
     if (bits & kOvfHandoff)
         return {PHYS_ERR_HIP, "contact solver hand-off timed out (k_solve_flow) in a step since the last phys_sync; "
                               "velocities are invalid from that step on"};

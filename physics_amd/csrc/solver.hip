@@ -9,13 +9,8 @@
 // colour). Everything a solve needs per row is kept as 16-BYTE elements in plane-major arrays over d (stride =
 // cap), so a lane fetches a row with ~10 dwordx4 loads (a wave: 1 KiB contiguous per load) instead of ~45
 // dword loads - the row solve is a long dependent chain at one wave per SIMD, and the number of memory
-// instructions in front of it is what its latency is made of:
-//     row_hdr uint4  [d]              {body a, body b, point count, update tickets (k_solve_flow)}
-//     row_n   float4 [d]              {normal xyz, 0}; material worlds: {normal xyz, the manifold's friction mu} (k_rows_build)
-//     row_pt  float4 [(2k)*cap + d]   {rA xyz, normal mass}          point k = 0..3
-//                    [(2k+1)*cap + d] {rB xyz, tangent mass 0}
-//     row_tb  float4 [d]              {tangent mass 1, bias} of points 0 and 1;  [cap + d]: points 2 and 3
-//     row_acc float4 [k*cap + d]      {pn, pt0, pt1, tag}            accumulated impulses of point k
+// instructions in front of it is what its latency is made of. The planes and what each element holds: records.hpp
+// (the prepared rows).
 // Only the body velocities (32-byte records) and the inverse inertia are gathered by body id.
 // Algorithmic bytes per manifold per iteration: ids, count, normal 24 + per point 40 (rA, rB,
 // masses, bias) + 12 R + 12 W (accumulated impulses), + per body 48 (v, w R+W) + 4 (inv mass) + 12 / 36
@@ -34,15 +29,22 @@ struct WarmJob {
     float* imp;                // this update's (written by the last sweep of whichever solver kernel runs)
     const uint32_t* row_src;   // row -> manifold
 };
-__device__ __forceinline__ void store_final_impulses(const WarmJob& wj, uint32_t d, const float pn[4], const float pt0[4], const float pt1[4]) {
-    float4* o = reinterpret_cast<float4*>(wj.imp) + 3 * (size_t)wj.row_src[d];
-    o[0] = make_float4(pn[0], pt0[0], pt1[0], pn[1]);
-    o[1] = make_float4(pt0[1], pt1[1], pn[2], pt0[2]);
-    o[2] = make_float4(pt1[2], pn[3], pt0[3], pt1[3]);
+__device__ __forceinline__ void store_final_impulses(const WarmJob& wj, uint32_t d, const solver_manifold_t& sm) {
+    const float pn[4] = {sm.row[0].pn, sm.row[1].pn, sm.row[2].pn, sm.row[3].pn};
+    const float pt0[4] = {sm.row[0].pt[0], sm.row[1].pt[0], sm.row[2].pt[0], sm.row[3].pt[0]};
+    const float pt1[4] = {sm.row[0].pt[1], sm.row[1].pt[1], sm.row[2].pt[1], sm.row[3].pt[1]};
+    float4 o0, o1, o2;
+    impulses_pack(pn, pt0, pt1, o0, o1, o2);
+    float4* o = reinterpret_cast<float4*>(wj.imp) + kImpulseVecs * (size_t)wj.row_src[d];
+    o[0] = o0; o[1] = o1; o[2] = o2;
+}
+// ... and lane q of a four-lane kernel: point q's three floats of that record (zeros beyond the count)
+__device__ __forceinline__ void store_final_point_impulses(const WarmJob& wj, uint32_t d, uint32_t q, v3 imp) {
+    st3(wj.imp + kImpulseFloats * (size_t)wj.row_src[d] + impulses_point_offset(q), 0, imp);
 }
 
 struct RowArrays {
-    float4* all;  // the 16 planes in one piece: plane p of row d = all[p * cap + d] (0 hdr, 1 n, 2-3 tb, 4-11 pt, 12-15 acc)
+    float4* all;  // the kRowPlanes planes in one piece: plane p of row d = all[p * cap + d]; below, where its groups begin (records.hpp)
     uint4* hdr;
     float4* n;
     float4* pt;
@@ -80,14 +82,15 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
     for (uint32_t d = blockIdx.x * blockDim.x + threadIdx.x; d < M; d += gridDim.x * blockDim.x) {
         const uint32_t m = row_src[d];
         manifold_t g;
-        const float4* rec = reinterpret_cast<const float4*>(man_geo) + 8 * (size_t)m;  // ONE line through the row permutation
-        const float4 r0 = rec[0], r1 = rec[1];
-        const uint32_t a = __float_as_uint(r0.x), b = __float_as_uint(r0.y);
-        g.count = (int)__float_as_uint(r0.z);
+        const float4* rec = reinterpret_cast<const float4*>(man_geo) + kManifoldVecs * (size_t)m;  // ONE line through the row permutation
+        const float4 r1 = rec[kManifoldVecNormal];
+        const ManifoldHead head = manifold_head_decode(rec[kManifoldVecHead]);
+        const uint32_t a = head.a, b = head.b;
+        g.count = (int)head.count;
         g.normal = v3_make(r1.x, r1.y, r1.z);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float4 p = rec[2 + k];
+            const float4 p = rec[kManifoldVecPoint + k];
             g.pt[k] = v3_make(p.x, p.y, p.z);
             g.depth[k] = p.w;
         }
@@ -96,41 +99,36 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
         // with, matched point by point (contact_solve.h warm_match); zero for a new pair or with warm starting off
         float w_pn[4] = {0.0f, 0.0f, 0.0f, 0.0f}, w_pt0[4] = {0.0f, 0.0f, 0.0f, 0.0f}, w_pt1[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (warm.man_prev) {
-            const uint32_t pm = __float_as_uint(r1.w);  // index of the pair's manifold in the previous update (narrow phase)
-            if (pm != 0xFFFFFFFFu) {
-                const float4* prec = reinterpret_cast<const float4*>(warm.geo_prev) + 8 * (size_t)pm;
-                const float4* pimp = reinterpret_cast<const float4*>(warm.imp_prev) + 3 * (size_t)pm;
-                const float4 q0 = prec[0], q1 = prec[1], i0 = pimp[0], i1 = pimp[1], i2 = pimp[2];
+            const uint32_t pm = manifold_prev_index(r1);  // index of the pair's manifold in the previous update (narrow phase)
+            if (pm != kNoPrevManifold) {
+                const float4* prec = reinterpret_cast<const float4*>(warm.geo_prev) + kManifoldVecs * (size_t)pm;
+                const float4* pimp = reinterpret_cast<const float4*>(warm.imp_prev) + kImpulseVecs * (size_t)pm;
+                const float4 q0 = prec[kManifoldVecHead], q1 = prec[kManifoldVecNormal], i0 = pimp[0], i1 = pimp[1], i2 = pimp[2];
                 warm_t wt;
-                wt.count = (int)__float_as_uint(q0.z);
+                wt.count = (int)manifold_head_decode(q0).count;
                 wt.normal = v3_make(q1.x, q1.y, q1.z);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) { const float4 p = prec[2 + k]; wt.pt[k] = v3_make(p.x, p.y, p.z); }
-                wt.pn[0] = i0.x; wt.pt0[0] = i0.y; wt.pt1[0] = i0.z; wt.pn[1] = i0.w;
-                wt.pt0[1] = i1.x; wt.pt1[1] = i1.y; wt.pn[2] = i1.z; wt.pt0[2] = i1.w;
-                wt.pt1[2] = i2.x; wt.pn[3] = i2.y; wt.pt0[3] = i2.z; wt.pt1[3] = i2.w;
+                for (int k = 0; k < 4; ++k) { const float4 p = prec[kManifoldVecPoint + k]; wt.pt[k] = v3_make(p.x, p.y, p.z); }
+                impulses_unpack(i0, i1, i2, wt.pn, wt.pt0, wt.pt1);
                 warm_match(&g, &wt, w_pn, w_pt0, w_pt1);
             }
         }
         // persistent colouring: a manifold that is new in this update enters the colour table (kernels.hpp)
-        if (table.tab && (table.all || __float_as_uint(r0.w) == 0u)) color_table_insert(table, a, b, m, ctr);
+        if (table.tab && (table.all || head.color == kUncolored)) color_table_insert(table, a, b, m, ctr);
         // a kept colour came with the record; a new manifold's was made by the colouring rounds since
-        const uint32_t color_m = __float_as_uint(r0.w) != 0u ? __float_as_uint(r0.w) - 1u : man_color[m];
-        // Ticket word: rank A (bits 0-5) | degree A (8-14) | rank B (16-21) | degree B (24-30). A rank is below PHYS_MAX_COLORS and
-        // a degree at most PHYS_MAX_COLORS, so bits 6, 7 and 15 are never set: they are RESERVED for the point count of the
-        // compact rows of material worlds (below; cluster.hip). A change of this format must keep them clear.
-        static_assert(PHYS_MAX_COLORS <= 64, "ticket bits 6, 7 and 15 hold the point count of material compact rows");
-        uint32_t ticket = 0;
+        const uint32_t color_m = head.color != kUncolored ? head.color : man_color[m];
+        uint32_t ticket = 0;  // the ticket word (records.hpp)
         if (flow) {
             // the colours in use at a body are exactly the colours of its manifolds (all distinct), so the rank of
             // this row among the body's manifolds in solve order = number of its colours below this one
             const unsigned long long below = (1ull << color_m) - 1ull;
             const unsigned long long ua = used[a];
-            ticket = (uint32_t)__popcll(ua & below) | ((uint32_t)__popcll(ua) << 8);
+            RowTicket tk{(uint32_t)__popcll(ua & below), (uint32_t)__popcll(ua), 0u, 0u};
             if (has_b) {
                 const unsigned long long ub = used[b];
-                ticket |= ((uint32_t)__popcll(ub & below) << 16) | ((uint32_t)__popcll(ub) << 24);
+                tk.rankB = (uint32_t)__popcll(ub & below); tk.degB = (uint32_t)__popcll(ub);
             }
+            ticket = ticket_encode(tk);
             if (flow == 2 && d == 0) ticket += 1;  // fault injection (PHYS_DEBUG_FLOW_STALL): row 0 waits for a turn that never comes
         }
         // materials: the manifold's friction and restitution; a row that bounces needs the velocities the solve starts from
@@ -164,8 +162,8 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
             return contact_bias(depth, &sp);
         };
         if constexpr (MAT) {
-            if (cluster_slots)  // compact rows: mu takes hdr.z; the count goes to ticket bits that are never set (rank < 64, degree <= 64)
-                rows.hdr[d] = make_uint4(a, b, __float_as_uint(mu), ticket | (((uint32_t)g.count & 3u) << 6) | (((uint32_t)g.count >> 2) << 15));
+            if (cluster_slots)  // compact rows: mu takes hdr.z; the count rides in the ticket word
+                rows.hdr[d] = make_uint4(a, b, __float_as_uint(mu), ticket_with_count(ticket, (uint32_t)g.count));
             else
                 rows.hdr[d] = make_uint4(a, b, (uint32_t)g.count, ticket);
         } else {
@@ -173,9 +171,7 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
         }
         uint32_t info = 0;
         if (cluster_slots) {
-            // cluster solver (cluster.hip): where each side's velocity lives. Per side: slot (13 bits) | publish (1) |
-            // mode (2): 0 own cluster, never updated by another workgroup (LDS only); 1 own cluster, shared (LDS while its
-            // tag is current, granules otherwise); 2 another cluster's body (granules only); 3 no body (ground).
+            // cluster solver (cluster.hip): where each side's velocity lives - the side word (records.hpp).
             // publish: the body's NEXT update in solve order (next colour in use at the body, cyclically) belongs to a
             // remote row, so this update must be written to the granules for it
             const unsigned long long bitc = 1ull << color_m;
@@ -184,7 +180,7 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
             const uint32_t owner = cluster_row_owner(a, ha, hb, cluster_count);
             // one side: {slot | publish | mode} of body x whose home is `hx`
             auto side = [&](uint32_t x, uint32_t hx) -> uint32_t {
-                if (hx != owner) return 2u << 14;  // homeless, or at home elsewhere
+                if (hx != owner) return cluster_side_encode(0u, 0u, kSideForeign);  // homeless, or at home elsewhere
                 const unsigned long long rem = ((unsigned long long)body_shared[2 * (size_t)x + 1] << 32) | body_shared[2 * (size_t)x];
                 uint32_t pub = 0;
                 if (rem) {
@@ -193,11 +189,9 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
                     const unsigned long long next = above ? (above & (~above + 1ull)) : (ux & (~ux + 1ull));  // lowest colour above, else the first
                     pub = (rem & next) ? 1u : 0u;
                 }
-                return (cluster_slot[x] - hx * cluster_slots) | (pub << 13) | ((rem ? 1u : 0u) << 14);
+                return cluster_side_encode(cluster_slot[x] - hx * cluster_slots, pub, rem ? kSideShared : kSideOwn);
             };
-            info = side(a, ha);
-            const uint32_t ib = has_b ? side(b, hb) : (3u << 14);
-            info |= ib << 16;
+            info = cluster_sides_encode(side(a, ha), has_b ? side(b, hb) : cluster_side_encode(0u, 0u, kSideNone));
         }
         if constexpr (MAT) rows.n[d] = make_float4(g.normal.x, g.normal.y, g.normal.z, cluster_slots ? __uint_as_float(info) : mu);
         else rows.n[d] = make_float4(g.normal.x, g.normal.y, g.normal.z, __uint_as_float(info));
@@ -207,24 +201,26 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (k < g.count)
-                    rows.all[(size_t)(2 + k) * cap + d] = make_float4(g.pt[k].x, g.pt[k].y, g.pt[k].z, MAT ? point_bias(g.pt[k], g.depth[k]) : contact_bias(g.depth[k], &sp));
-            if (warm.man_prev) {  // the starting impulses, packed like the solver packs them (planes 6-8; read in sweep 0)
-                rows.all[(size_t)6 * cap + d] = make_float4(w_pn[0], w_pt0[0], w_pt1[0], w_pn[1]);
-                rows.all[(size_t)7 * cap + d] = make_float4(w_pt0[1], w_pt1[1], w_pn[2], w_pt0[2]);
-                rows.all[(size_t)8 * cap + d] = make_float4(w_pt1[2], w_pn[3], w_pt0[3], w_pt1[3]);
+                    rows.all[(size_t)(kClusterPlaneGeo + k) * cap + d] = make_float4(g.pt[k].x, g.pt[k].y, g.pt[k].z, MAT ? point_bias(g.pt[k], g.depth[k]) : contact_bias(g.depth[k], &sp));
+            if (warm.man_prev) {  // the starting impulses, packed like the solver packs them (read in sweep 0)
+                float4 a0, a1, a2;
+                impulses_pack(w_pn, w_pt0, w_pt1, a0, a1, a2);
+                rows.all[(size_t)(kClusterPlaneAcc + 0) * cap + d] = a0;
+                rows.all[(size_t)(kClusterPlaneAcc + 1) * cap + d] = a1;
+                rows.all[(size_t)(kClusterPlaneAcc + 2) * cap + d] = a2;
             }
-            if (((info >> 30) & 3u) == 2u) {
-                // body B belongs to another cluster: what does not change during the solve rides with the row (planes 12,
-                // 13), or fetching it by body id would be a second dependent round trip in every colour step of the solver
+            if (cluster_side_rides(info, true)) {
+                // body B belongs to another cluster: what does not change during the solve rides with the row, or fetching
+                // it by body id would be a second dependent round trip in every colour step of the solver
                 const v3 xb = ld3(pos, b);
-                rows.all[(size_t)12 * cap + d] = make_float4(xb.x, xb.y, xb.z, vel[8 * (size_t)b + 3]);
-                if (DIAG) rows.all[(size_t)13 * cap + d] = reinterpret_cast<const float4*>(inv_inertia)[b * inertia_stride];
+                rows.all[(size_t)kClusterPlaneForeignB * cap + d] = make_float4(xb.x, xb.y, xb.z, vel[8 * (size_t)b + 3]);
+                if (DIAG) rows.all[(size_t)(kClusterPlaneForeignB + 1) * cap + d] = reinterpret_cast<const float4*>(inv_inertia)[b * inertia_stride];
             }
-            if (((info >> 14) & 3u) == 2u) {
-                // body A has no home (dynamic clusters beyond their capacity): the same for A in planes 14, 15
+            if (cluster_side_rides(info, false)) {
+                // body A has no home (dynamic clusters beyond their capacity): the same for A
                 const v3 xa = ld3(pos, a);
-                rows.all[(size_t)14 * cap + d] = make_float4(xa.x, xa.y, xa.z, vel[8 * (size_t)a + 3]);
-                if (DIAG) rows.all[(size_t)15 * cap + d] = reinterpret_cast<const float4*>(inv_inertia)[a * inertia_stride];
+                rows.all[(size_t)kClusterPlaneForeignA * cap + d] = make_float4(xa.x, xa.y, xa.z, vel[8 * (size_t)a + 3]);
+                if (DIAG) rows.all[(size_t)(kClusterPlaneForeignA + 1) * cap + d] = reinterpret_cast<const float4*>(inv_inertia)[a * inertia_stride];
             }
             continue;
         }
@@ -244,20 +240,26 @@ __global__ __launch_bounds__(256) void k_rows_build(StepCounters* __restrict__ c
             for (int k = 0; k < 4; ++k)
                 if (k < sm.count) sm.row[k].bias = point_bias(g.pt[k], g.depth[k]);
         }
+        RowPoint rp[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
+            const contact_row_t& c = sm.row[k];
+            rp[k] = RowPoint{{c.rA.x, c.rA.y, c.rA.z}, {c.rB.x, c.rB.y, c.rB.z}, c.normal_mass, c.tangent_mass[0], c.tangent_mass[1], c.bias};
             if (k < sm.count) {
-                const contact_row_t& c = sm.row[k];
-                rows.pt[(size_t)(2 * k) * cap + d] = make_float4(c.rA.x, c.rA.y, c.rA.z, c.normal_mass);
-                rows.pt[(size_t)(2 * k + 1) * cap + d] = make_float4(c.rB.x, c.rB.y, c.rB.z, c.tangent_mass[0]);
+                float4 pa, pb;
+                row_point_encode(rp[k], pa, pb);
+                rows.pt[(size_t)row_pt_plane_a(k) * cap + d] = pa;
+                rows.pt[(size_t)row_pt_plane_b(k) * cap + d] = pb;
                 // accumulated impulses of point k: zero, or where the previous update left off. (The dataflow kernels read
                 // these with plain loads in their first sweep only when warm starting is on; tag 0 = no epoch ever.)
                 if (!flow || warm.man_prev) rows.acc[(size_t)k * cap + d] = make_float4(w_pn[k], w_pt0[k], w_pt1[k], 0.0f);
             }
         }
-        rows.tb[d] = make_float4(sm.row[0].tangent_mass[1], sm.row[0].bias, sm.row[1].tangent_mass[1], sm.row[1].bias);
-        if (sm.count > 2)
-            rows.tb[cap + d] = make_float4(sm.row[2].tangent_mass[1], sm.row[2].bias, sm.row[3].tangent_mass[1], sm.row[3].bias);
+        float4 t01, t23;
+        row_tb_encode(rp[0], rp[1], t01);
+        row_tb_encode(rp[2], rp[3], t23);
+        rows.tb[(size_t)row_tb_plane(0) * cap + d] = t01;
+        if (sm.count > 2) rows.tb[(size_t)row_tb_plane(2) * cap + d] = t23;
     }
 }
 
@@ -266,61 +268,78 @@ struct RowRegs {
     uint32_t a, b, ticket;
     solver_manifold_t sm;
 };
+// ... and as its planes come from memory: header, normal, the two tb planes, the eight pt planes
+struct FlowRowRaw { uint4 h; float4 nn, t01, t23, p[8]; };
 
-// everything of a row that does NOT depend on body velocities. ACC: also the accumulated impulses (plain loads;
-// k_solve_flow receives them as tagged granules instead)
-// EAGER: every plane of the row is fetched at once, whatever the point count turns out to be (planes beyond it hold
-// stale but readable data that is then ignored): no load waits for the header. For the per-colour kernel of large
-// scenes, where a launch is one wave per SIMD and a second dependent round trip to memory is ~1.5 us of every launch.
-// Returns row_n.w: the manifold's friction where the material instance of k_rows_build wrote the row (0 in plain rows).
-template <bool ACC, bool EAGER = false>
-__device__ __forceinline__ float load_row(RowRegs& R, uint32_t d, const RowArrays& rows) {
-    const uint64_t cap = rows.cap;
-    float4 e_p0[4], e_p1[4], e_acc[4], e_t23;
-    if (EAGER) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            e_p0[k] = rows.pt[(size_t)(2 * k) * cap + d];
-            e_p1[k] = rows.pt[(size_t)(2 * k + 1) * cap + d];
-            if (ACC) e_acc[k] = rows.acc[(size_t)k * cap + d];
-        }
-        e_t23 = rows.tb[cap + d];
-    }
-    const uint4 h = rows.hdr[d];
-    R.a = h.x; R.b = h.y; R.ticket = h.w;
+// The ONE unpack of a prepared row: everything of it that does not depend on body velocities. ACC: with the accumulated
+// impulses out of the acc elements of its points; otherwise they start at zero and `acc` is not looked at (k_solve_flow
+// receives them as tagged granules). Elements of points beyond the count are not looked at either. live = false: a lane
+// without a row (no points, no body B). (A template flag, not a pointer that may be null: the arrays went to scratch memory for that.)
+template <bool ACC>
+__device__ __forceinline__ void row_unpack(const FlowRowRaw& raw, const float4 (&acc)[4], bool live, RowRegs& R) {
+    R.a = raw.h.x; R.b = raw.h.y; R.ticket = raw.h.w;
     solver_manifold_t& sm = R.sm;
-    sm.count = (int)h.z;
-    sm.has_b = !PHYS_IS_STATIC_PARTNER(R.b);
-    const float4 nn = rows.n[d];
-    sm.n = v3_make(nn.x, nn.y, nn.z);
+    sm.count = live ? (int)raw.h.z : 0;
+    sm.has_b = live && !PHYS_IS_STATIC_PARTNER(R.b);
+    sm.n = v3_make(raw.nn.x, raw.nn.y, raw.nn.z);
+    if (!live) sm.n = v3_make(0.0f, 1.0f, 0.0f);
     tangent_basis(sm.n, &sm.t1, &sm.t2);  // same inputs as solver_prep => same bits as the basis used there
-    const float4 t01 = rows.tb[d];
-    float4 t23 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (sm.count > 2) t23 = EAGER ? e_t23 : rows.tb[cap + d];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         contact_row_t& c = sm.row[k];
         if (k < sm.count) {
-            const float4 p0 = EAGER ? e_p0[k] : rows.pt[(size_t)(2 * k) * cap + d];
-            const float4 p1 = EAGER ? e_p1[k] : rows.pt[(size_t)(2 * k + 1) * cap + d];
-            c.rA = v3_make(p0.x, p0.y, p0.z); c.normal_mass = p0.w;
-            c.rB = v3_make(p1.x, p1.y, p1.z); c.tangent_mass[0] = p1.w;
-            const float4 t = k < 2 ? t01 : t23;
-            c.tangent_mass[1] = (k & 1) ? t.z : t.x;
-            c.bias = (k & 1) ? t.w : t.y;
-            if (ACC) {
-                const float4 acc = EAGER ? e_acc[k] : rows.acc[(size_t)k * cap + d];
-                c.pn = acc.x; c.pt[0] = acc.y; c.pt[1] = acc.z;
-            } else {
-                c.pn = 0.0f; c.pt[0] = 0.0f; c.pt[1] = 0.0f;
-            }
+            const RowPoint p = row_point_decode(k, raw.p[row_pt_plane_a(k)], raw.p[row_pt_plane_b(k)], row_tb_plane(k) == 0 ? raw.t01 : raw.t23);
+            c.rA = v3_make(p.rA[0], p.rA[1], p.rA[2]); c.normal_mass = p.normal_mass;
+            c.rB = v3_make(p.rB[0], p.rB[1], p.rB[2]); c.tangent_mass[0] = p.tangent_mass0;
+            c.tangent_mass[1] = p.tangent_mass1;
+            c.bias = p.bias;
+            if (ACC) { c.pn = acc[k].x; c.pt[0] = acc[k].y; c.pt[1] = acc[k].z; }
+            else { c.pn = 0.0f; c.pt[0] = 0.0f; c.pt[1] = 0.0f; }
         } else {
+            c.pn = 0.0f; c.pt[0] = 0.0f; c.pt[1] = 0.0f;
             c.rA = v3_make(0.0f, 0.0f, 0.0f); c.rB = v3_make(0.0f, 0.0f, 0.0f);
             c.normal_mass = 0.0f; c.tangent_mass[0] = 0.0f; c.tangent_mass[1] = 0.0f; c.bias = 0.0f;
-            c.pn = 0.0f; c.pt[0] = 0.0f; c.pt[1] = 0.0f;
         }
     }
-    return nn.w;
+}
+
+// row d from memory. ACC: also the accumulated impulses (plain loads; k_solve_flow receives them as tagged granules instead)
+// EAGER: every plane of the row is fetched at once, whatever the point count turns out to be (planes beyond it hold
+// stale but readable data that is then ignored): no load waits for the header. For the per-colour kernel of large
+// scenes, where a launch is one wave per SIMD and a second dependent round trip to memory is ~1.5 us of every launch.
+// Returns the normal element's .w: the manifold's friction where the material instance of k_rows_build wrote the row (0 in plain rows).
+template <bool ACC, bool EAGER = false>
+__device__ __forceinline__ float load_row(RowRegs& R, uint32_t d, const RowArrays& rows) {
+    const uint64_t cap = rows.cap;
+    FlowRowRaw raw;  // (elements of points beyond the count stay unset: row_unpack does not look at them)
+    float4 acc[4], e_t23;
+    if (EAGER) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            raw.p[row_pt_plane_a(k)] = rows.pt[(size_t)row_pt_plane_a(k) * cap + d];
+            raw.p[row_pt_plane_b(k)] = rows.pt[(size_t)row_pt_plane_b(k) * cap + d];
+            if (ACC) acc[k] = rows.acc[(size_t)k * cap + d];
+        }
+        e_t23 = rows.tb[(size_t)row_tb_plane(2) * cap + d];
+    }
+    raw.h = rows.hdr[d];
+    raw.nn = rows.n[d];
+    raw.t01 = rows.tb[(size_t)row_tb_plane(0) * cap + d];
+    const int count = (int)raw.h.z;
+    raw.t23 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (count > 2) raw.t23 = EAGER ? e_t23 : rows.tb[(size_t)row_tb_plane(2) * cap + d];
+    if (!EAGER) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k < count) {
+                raw.p[row_pt_plane_a(k)] = rows.pt[(size_t)row_pt_plane_a(k) * cap + d];
+                raw.p[row_pt_plane_b(k)] = rows.pt[(size_t)row_pt_plane_b(k) * cap + d];
+                if (ACC) acc[k] = rows.acc[(size_t)k * cap + d];
+            }
+        }
+    }
+    row_unpack<ACC>(raw, acc, true, R);
+    return raw.nn.w;
 }
 
 // gather the two bodies, solve_manifold, write velocities and accumulated impulses back
@@ -358,12 +377,7 @@ __device__ __forceinline__ void solve_row(uint32_t d, const RowArrays& rows, flo
             if (k < sm.count)
                 rows.acc[(size_t)k * rows.cap + d] = make_float4(sm.row[k].pn, sm.row[k].pt[0], sm.row[k].pt[1], 0.0f);
     }
-    if (last && wj.man_prev) {
-        const float pn[4] = {sm.row[0].pn, sm.row[1].pn, sm.row[2].pn, sm.row[3].pn};
-        const float p0[4] = {sm.row[0].pt[0], sm.row[1].pt[0], sm.row[2].pt[0], sm.row[3].pt[0]};
-        const float p1[4] = {sm.row[0].pt[1], sm.row[1].pt[1], sm.row[2].pt[1], sm.row[3].pt[1]};
-        store_final_impulses(wj, d, pn, p0, p1);
-    }
+    if (last && wj.man_prev) store_final_impulses(wj, d, sm);
 }
 
 // Tiles of `tile_rows` consecutive items handed to the workgroups of a launch so that the workgroups sharing an XCD
@@ -481,7 +495,6 @@ __device__ __forceinline__ bool flow_backoff(StepCounters* ctr, bool done, uint3
 // the current one is done: holding an item ahead means it cannot go to whichever workgroup is free first, and where a
 // colour class is much smaller than the launch (C3: 64 items per colour, 256 workgroups) the solve is bound by the
 // chain of hand-offs, not by item throughput - there the look-ahead costs 10 % instead of saving it (launch_solver).
-struct FlowRowRaw { uint4 h; float4 nn, t01, t23, p[8]; };
 struct FlowBodies { m33 IA, IB; float ima, imb, massA, massB; v3 vA, wA, vB, wB; };
 
 template <bool DIAG, bool MAT>
@@ -498,7 +511,7 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
     const uint32_t total = nchunks * iterations;
     const uint32_t cap = (uint32_t)rows.cap;  // collision_alloc: 64 * cap < 4 GiB (32-bit buffer offsets)
     const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(flow_vel, 0, n_bodies * 32u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(rows.acc, 0, cap * 64u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(rows.acc, 0, cap * (16u * kRowAccPlanes), 0x00020000);
     const uint32_t etag = epoch << 16;
     const long long t_start = wall_clock64();
     auto take = [&]() -> uint32_t {  // next work item in solve order (block-uniform)
@@ -518,10 +531,10 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
         // every plane at once, whatever the point count turns out to be: ONE round trip
         r.h = rows.hdr[d];
         r.nn = rows.n[d];
-        r.t01 = rows.tb[d];
-        r.t23 = rows.tb[cap + d];
+        r.t01 = rows.tb[(uint32_t)row_tb_plane(0) * cap + d];
+        r.t23 = rows.tb[(uint32_t)row_tb_plane(2) * cap + d];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) r.p[k] = rows.pt[(size_t)k * cap + d];
+        for (int k = 0; k < kRowPtPlanes; ++k) r.p[k] = rows.pt[(size_t)k * cap + d];
     };
     auto fetch_bodies = [&](const FlowRowRaw& r, FlowBodies& g) {
         // everything of the two bodies that is constant during the solve; v, w are the body's state only for ticket 0
@@ -563,36 +576,14 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
             d_next = row_of(L_next);
             if (d_next < M) fetch_row(d_next, raw_next);
         }
-        // ---- item L: unpack the row (same values as load_row)
+        // ---- item L: unpack the row
         const uint32_t it = L / nchunks;
         const bool last_it = it + 1 == iterations;
         const uint32_t d = (L - it * nchunks) * blockDim.x + threadIdx.x;
         bool done = d >= M;
         RowRegs R;
-        R.a = raw.h.x; R.b = raw.h.y; R.ticket = raw.h.w;
-        {
-            solver_manifold_t& sm = R.sm;
-            sm.count = done ? 0 : (int)raw.h.z;
-            sm.has_b = !done && !PHYS_IS_STATIC_PARTNER(R.b);
-            sm.n = v3_make(raw.nn.x, raw.nn.y, raw.nn.z);
-            if (done) sm.n = v3_make(0.0f, 1.0f, 0.0f);
-            tangent_basis(sm.n, &sm.t1, &sm.t2);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                contact_row_t& c = sm.row[k];
-                c.rA = v3_make(0.0f, 0.0f, 0.0f); c.rB = c.rA;
-                c.normal_mass = 0.0f; c.tangent_mass[0] = 0.0f; c.tangent_mass[1] = 0.0f; c.bias = 0.0f;
-                c.pn = 0.0f; c.pt[0] = 0.0f; c.pt[1] = 0.0f;
-                if (k < sm.count) {
-                    const float4 p0 = raw.p[2 * k], p1 = raw.p[2 * k + 1];
-                    c.rA = v3_make(p0.x, p0.y, p0.z); c.normal_mass = p0.w;
-                    c.rB = v3_make(p1.x, p1.y, p1.z); c.tangent_mass[0] = p1.w;
-                    const float4 t = k < 2 ? raw.t01 : raw.t23;
-                    c.tangent_mass[1] = (k & 1) ? t.z : t.x;
-                    c.bias = (k & 1) ? t.w : t.y;
-                }
-            }
-        }
+        float4 no_acc[4];  // (never read)
+        row_unpack<false>(raw, no_acc, !done, R);
         const bool apply_only = warm_sweep != 0u && it == 0u;
         if (apply_only && !done) {  // the starting impulses k_rows_build left in the impulse planes (plain loads: an earlier kernel wrote them)
 #pragma unroll
@@ -601,8 +592,8 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
                 R.sm.row[k].pn = a0.x; R.sm.row[k].pt[0] = a0.y; R.sm.row[k].pt[1] = a0.z;
             }
         }
-        const uint32_t rankA = R.ticket & 0xFFu, degA = (R.ticket >> 8) & 0xFFu;
-        const uint32_t rankB = (R.ticket >> 16) & 0xFFu, degB = R.ticket >> 24;
+        const RowTicket tk = ticket_decode(R.ticket);
+        const uint32_t rankA = tk.rankA, degA = tk.degA, rankB = tk.rankB, degB = tk.degB;
         const uint32_t tA = done ? 0u : it * degA + rankA, tB = (done || !R.sm.has_b) ? 0u : it * degB + rankB;
         const bool finalA = !done && last_it && rankA + 1 == degA, finalB = !done && R.sm.has_b && last_it && rankB + 1 == degB;
         const m33 IA = bod.IA, IB = bod.IB;
@@ -675,10 +666,7 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
                             st_granule(ra, (k * cap + d) * 16u, v3_make(R.sm.row[k].pn, R.sm.row[k].pt[0], R.sm.row[k].pt[1]),
                                        etag | (it + 1u));
                     } else if (wj.man_prev) {  // the solve's last sweep: remembered for the next update
-                        const float fpn[4] = {R.sm.row[0].pn, R.sm.row[1].pn, R.sm.row[2].pn, R.sm.row[3].pn};
-                        const float fp0[4] = {R.sm.row[0].pt[0], R.sm.row[1].pt[0], R.sm.row[2].pt[0], R.sm.row[3].pt[0]};
-                        const float fp1[4] = {R.sm.row[0].pt[1], R.sm.row[1].pt[1], R.sm.row[2].pt[1], R.sm.row[3].pt[1]};
-                        store_final_impulses(wj, d, fpn, fp0, fp1);
+                        store_final_impulses(wj, d, R.sm);
                     }
                     done = true;
                 }
@@ -738,9 +726,9 @@ struct QuadLane {
     }
 };
 
-// lane q (0 vA, 1 wA, 2 vB, 3 wB) of row {a, b, count} with normal `nn`, tangent masses and biases t01 / t23 (t23 read
-// by the caller only for count > 2) and the point planes pt(j) = {rA, normal mass} of point k at j = 2k, {rB, tangent
-// mass 0} at 2k + 1, read for the points below `count` only. The accumulated impulses are left to the caller.
+// lane q (0 vA, 1 wA, 2 vB, 3 wB) of row {a, b, count} with normal `nn`, the tb elements t01 / t23 (t23 read by the
+// caller only for count > 2) and the pt planes (records.hpp), read for the points below `count` only. The accumulated
+// impulses are left to the caller.
 template <bool DIAG>
 __device__ __forceinline__ void quad_lane_setup(QuadLane& s, uint32_t q, uint32_t a, uint32_t b, uint32_t count, float4 nn,
                                                 float4 t01, float4 t23, const float4* pt, uint32_t pt_stride, const float* vel,
@@ -767,12 +755,12 @@ __device__ __forceinline__ void quad_lane_setup(QuadLane& s, uint32_t q, uint32_
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         if (k < (int)count) {
-            const float4 p0 = pt[(size_t)(2 * k) * pt_stride], p1 = pt[(size_t)(2 * k + 1) * pt_stride];
-            s.nm[k] = p0.w; s.tm0[k] = p1.w;
-            const float4 tt = k < 2 ? t01 : t23;
-            s.tm1[k] = (k & 1) ? tt.z : tt.x;
-            s.bias[k] = (k & 1) ? tt.w : tt.y;
-            const v3 r = side_a ? v3_make(p0.x, p0.y, p0.z) : v3_make(p1.x, p1.y, p1.z);
+            const RowPoint p = row_point_decode(k, pt[(size_t)row_pt_plane_a(k) * pt_stride], pt[(size_t)row_pt_plane_b(k) * pt_stride],
+                                                row_tb_plane(k) == 0 ? t01 : t23);
+            s.nm[k] = p.normal_mass; s.tm0[k] = p.tangent_mass0;
+            s.tm1[k] = p.tangent_mass1;
+            s.bias[k] = p.bias;
+            const v3 r = side_a ? v3_make(p.rA[0], p.rA[1], p.rA[2]) : v3_make(p.rB[0], p.rB[1], p.rB[2]);
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
                 if (has_body) {
@@ -810,22 +798,8 @@ __device__ __forceinline__ void quad_lane_solve(QuadLane& s, float friction, boo
                 const float mine = part + quad_perm<kQuadXor1>(part);
                 const float other = quad_perm<kQuadXor2>(mine);
                 const float vrel = side_a ? other - mine : mine - other;
-                if (t < 2) {  // solve_row_dir, friction
-                    const float mass = t == 0 ? s.tm0[k] : s.tm1[k];
-                    float& acc = t == 0 ? s.pt0[k] : s.pt1[k];
-                    lambda = -mass * vrel;
-                    const float maxf = friction * s.pn[k];
-                    const float old = acc;
-                    const float np = det_maxf(-maxf, det_minf(old + lambda, maxf));
-                    lambda = np - old;
-                    acc = np;
-                } else {      // normal
-                    lambda = s.nm[k] * (s.bias[k] - vrel);
-                    const float old = s.pn[k];
-                    const float np = det_maxf(old + lambda, 0.0f);
-                    lambda = np - old;
-                    s.pn[k] = np;
-                }
+                if (t < 2) lambda = friction_impulse(t == 0 ? s.tm0[k] : s.tm1[k], vrel, friction * s.pn[k], t == 0 ? &s.pt0[k] : &s.pt1[k]);
+                else lambda = normal_impulse(s.nm[k], vrel, s.bias[k], &s.pn[k]);
                 x = v3_madd(x, s.Rs[k][t], lambda);  // row_apply
             }
         }
@@ -857,7 +831,7 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
     const uint32_t total = nchunks * iterations;
     const uint32_t cap = (uint32_t)rows.cap;
     const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(flow_vel, 0, n_bodies * 32u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(rows.acc, 0, cap * 64u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(rows.acc, 0, cap * (16u * kRowAccPlanes), 0x00020000);
     const uint32_t etag = epoch << 16;
     const uint32_t q = threadIdx.x & 3u;      // 0: vA, 1: wA, 2: vB, 3: wB
     const bool side_a = q < 2u, angular = (q & 1u) != 0u;
@@ -887,13 +861,13 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
         float mu = friction;  // MAT: the row's own
         if (!done) {
             const uint4 h = rows.hdr[d];
-            const uint32_t tk = side_a ? h.w : (h.w >> 16);
-            const uint32_t rank = tk & 0xFFu, deg = (tk >> 8) & 0xFFu;
+            const uint32_t tk = ticket_side(h.w, !side_a);
+            const uint32_t rank = ticket_side_rank(tk), deg = ticket_side_degree(tk);
             ticket = it * deg + rank;
             final_update = last_it && rank + 1 == deg;
-            const float4 nn = rows.n[d], t01 = rows.tb[d];
+            const float4 nn = rows.n[d], t01 = rows.tb[(uint32_t)row_tb_plane(0) * cap + d];
             float4 t23 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (h.z > 2) t23 = rows.tb[cap + d];
+            if (h.z > 2) t23 = rows.tb[(uint32_t)row_tb_plane(2) * cap + d];
             if constexpr (MAT) mu = nn.w;
             quad_lane_setup<DIAG>(s, q, h.x, h.y, h.z, nn, t01, t23, rows.pt + d, cap,
                                   vel, inv_inertia, inertia_stride);
@@ -945,8 +919,7 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
                         st_granule(rv, s.body * 32u + (angular ? 16u : 0u), s.x, etag | (ticket + 1u));
                 }
                 if (!last_it && q < s.count) st_granule(ra, (q * cap + d) * 16u, quad_point_impulses(s, q), etag | (it + 1u));
-                if (last_it && wj.man_prev)  // lane q remembers point q's impulses (zeros beyond the count)
-                    st3(wj.imp + 12 * (size_t)wj.row_src[d] + 3u * q, 0, quad_point_impulses(s, q));
+                if (last_it && wj.man_prev) store_final_point_impulses(wj, d, q, quad_point_impulses(s, q));
                 done = true;
             }
             if (__all(done)) break;
@@ -972,17 +945,19 @@ __global__ __launch_bounds__(256) void k_solve_color_quad(StepCounters* ctr, uin
                                                           float friction, const float* __restrict__ inv_inertia,
                                                           uint32_t inertia_stride, float* __restrict__ vel, uint32_t n_bodies,
                                                           int apply_only, int last, WarmJob wj) {
-    __shared__ float4 s_rows[16][kQuadRowsPerGroup];  // [plane][row of this workgroup]
+    __shared__ float4 s_rows[kRowPlanes][kQuadRowsPerGroup];  // [plane][row of this workgroup]
+    constexpr uint32_t kPlanesPerWave = kRowPlanes / 4;       // four waves stage the planes
+    static_assert(kPlanesPerWave == 4, "a wave stages four planes below");
     if (ctr->overflow) return;
     const uint32_t start = ctr->color_start[col], end = ctr->color_start[col + 1];
     const uint32_t cap = (uint32_t)rows.cap;
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t q = threadIdx.x & 3u, r = threadIdx.x >> 2;  // q: 0 vA, 1 wA, 2 vB, 3 wB
     const bool side_a = q < 2u, angular = (q & 1u) != 0u;
-    // the four planes this wave stages: 4 * wave + j of the ONE row allocation (0 hdr, 1 n, 2-3 tb, 4-11 pt, 12-15 acc).
+    // the four planes this wave stages: kPlanesPerWave * wave + j of the ONE row allocation.
     // Plain arithmetic on purpose: written as `if (wave == 0) {pointers..} else if ..` over the five arrays, hipcc
     // (ROCm 7.2) lost one case of the pointer selection (wave 3 staged from a null pointer: memory access fault)
-    const float4* pl = rows.all + (size_t)(4u * wave) * cap;
+    const float4* pl = rows.all + (size_t)(kPlanesPerWave * wave) * cap;
     for (XcdTiles tl(end - start, kQuadRowsPerGroup); tl.valid(); tl.next()) {  // XCD-aware: see k_solve_color
         const uint32_t base = start + tl.tile * kQuadRowsPerGroup;
         {
@@ -990,38 +965,37 @@ __global__ __launch_bounds__(256) void k_solve_color_quad(StepCounters* ctr, uin
             uint32_t e = base + lane;
             e = e < cap ? e : cap - 1u;
             const float4 t0 = pl[e], t1 = pl[(size_t)cap + e], t2 = pl[2 * (size_t)cap + e], t3 = pl[3 * (size_t)cap + e];
-            s_rows[4 * wave + 0][lane] = t0; s_rows[4 * wave + 1][lane] = t1;
-            s_rows[4 * wave + 2][lane] = t2; s_rows[4 * wave + 3][lane] = t3;
+            s_rows[kPlanesPerWave * wave + 0][lane] = t0; s_rows[kPlanesPerWave * wave + 1][lane] = t1;
+            s_rows[kPlanesPerWave * wave + 2][lane] = t2; s_rows[kPlanesPerWave * wave + 3][lane] = t3;
         }
         __syncthreads();
         const uint32_t d = base + r;
         const bool live = d < end;  // the same for the four lanes of a quad
         QuadLane s;
-        const float4 hraw = s_rows[0][r];
+        const float4 hraw = s_rows[kRowPlaneHdr][r];
         const uint32_t ha = __float_as_uint(hraw.x), hb = __float_as_uint(hraw.y), count = __float_as_uint(hraw.z);
         // a row header that names no body of this world must never become an address (a faulting kernel can take the
         // whole node down): flag the step (bit 5) and skip the row
         const bool bad = live && (count > 4u || ha >= n_bodies || (!PHYS_IS_STATIC_PARTNER(hb) && hb >= n_bodies));
         if (bad) {
             flag_overflow(ctr, kOvfCorruptRow);
-            ctr->debug[0] = d; ctr->debug[1] = ha; ctr->debug[2] = hb; ctr->debug[3] = count;
-            ctr->debug[4] = start; ctr->debug[5] = end; ctr->debug[6] = col; ctr->debug[7] = base;
+            corrupt_row_note_encode(CorruptRowNote{d, ha, hb, count, start, end, col, base}, ctr->debug);
         }
         if (live && !bad) {
             float4 t23 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (count > 2) t23 = s_rows[3][r];
-            quad_lane_setup<DIAG>(s, q, ha, hb, count, s_rows[1][r], s_rows[2][r], t23, &s_rows[4][r], kQuadRowsPerGroup,
+            if (count > 2) t23 = s_rows[kRowPlaneTb + row_tb_plane(2)][r];
+            quad_lane_setup<DIAG>(s, q, ha, hb, count, s_rows[kRowPlaneN][r], s_rows[kRowPlaneTb + row_tb_plane(0)][r], t23, &s_rows[kRowPlanePt][r], kQuadRowsPerGroup,
                                   vel, inv_inertia, inertia_stride);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (k < (int)count) {  // the accumulated impulses of point k
-                    const float4 ac = s_rows[12 + k][r];
+                    const float4 ac = s_rows[kRowPlaneAcc + k][r];
                     s.pn[k] = ac.x; s.pt0[k] = ac.y; s.pt1[k] = ac.z;
                 }
             }
         }
         // dead quads carry zeros (and, MAT, a clean friction: their slot of the tile holds another colour's row or stale memory)
-        quad_lane_solve(s, MAT ? (live ? s_rows[1][r].w : 0.0f) : friction, apply_only != 0, side_a);
+        quad_lane_solve(s, MAT ? (live ? s_rows[kRowPlaneN][r].w : 0.0f) : friction, apply_only != 0, side_a);
         if (live) {
             if (s.has_body)
                 reinterpret_cast<float4*>(vel)[2 * (size_t)s.body + (angular ? 1 : 0)] = make_float4(s.x.x, s.x.y, s.x.z, s.keep_w);
@@ -1029,8 +1003,7 @@ __global__ __launch_bounds__(256) void k_solve_color_quad(StepCounters* ctr, uin
                 const v3 mine = quad_point_impulses(s, q);
                 rows.acc[(size_t)q * cap + d] = make_float4(mine.x, mine.y, mine.z, 0.0f);
             }
-            if (last && wj.man_prev)  // lane q remembers point q's impulses (zeros beyond the count)
-                st3(wj.imp + 12 * (size_t)wj.row_src[d] + 3u * q, 0, quad_point_impulses(s, q));
+            if (last && wj.man_prev) store_final_point_impulses(wj, d, q, quad_point_impulses(s, q));
         }
         __syncthreads();  // the LDS tile is restaged by the next trip
     }
@@ -1055,11 +1028,11 @@ void launch_solver(phys_world* w, float dt, const SolverPlan& plan, const ColorP
     const uint32_t stride = diag && w->uniform_inertia ? 0u : 1u;
     RowArrays rows;
     rows.all = reinterpret_cast<float4*>(w->row_all.p);
-    rows.hdr = reinterpret_cast<uint4*>(w->row_hdr.p);
-    rows.n = reinterpret_cast<float4*>(w->row_n.p);
-    rows.pt = reinterpret_cast<float4*>(w->row_pt.p);
-    rows.tb = reinterpret_cast<float4*>(w->row_tb.p);
-    rows.acc = reinterpret_cast<float4*>(w->row_acc.p);
+    rows.hdr = reinterpret_cast<uint4*>(rows.all + (size_t)kRowPlaneHdr * cap);
+    rows.n = rows.all + (size_t)kRowPlaneN * cap;
+    rows.tb = rows.all + (size_t)kRowPlaneTb * cap;
+    rows.pt = rows.all + (size_t)kRowPlanePt * cap;
+    rows.acc = rows.all + (size_t)kRowPlaneAcc * cap;
     rows.cap = cap;
     const bool cluster = plan.path == SolverPath::Cluster, flow = plan.flow();
     // warm starting (contact_solve.h): one sweep more, in front - it applies the impulses the rows start from
@@ -1079,11 +1052,11 @@ void launch_solver(phys_world* w, float dt, const SolverPlan& plan, const ColorP
     table.man_color = w->man_color.p; table.man_prio = w->man_prio.p;
     if (flow && ++w->flow_epoch > 0xFFFFu) {
         // tags would repeat: forget every old one. AHEAD of k_rows_build: on a cluster step that kernel writes the constants
-        // of foreign bodies into planes 12-15 = row_acc (with flow != 0 it never writes the impulses there), and a memset
+        // of foreign bodies into the impulse planes (with flow != 0 it never writes the impulses there), and a memset
         // behind it wiped them - every 65535th solve ran with x = 0, 1/m = 0, I^-1 = 0 for those rows
         PHYS_PROF(w, PHYS_STAGE_MISC);
         (void)hipMemsetAsync(w->flow_vel.p, 0, 8 * w->n * sizeof(float), s);
-        (void)hipMemsetAsync(w->row_acc.p, 0, 16 * cap * sizeof(float), s);
+        (void)hipMemsetAsync(rows.acc, 0, row_plane_floats(kRowAccPlanes, cap) * sizeof(float), s);
         w->flow_epoch = 1;
     }
     // materials: once a material call was made, the material instances of every kernel below - same

@@ -230,16 +230,11 @@ struct phys_world {
     phys::DevBuf<uint32_t> color_block_hist;  // [colour][workgroup] histogram / offsets of the colour sort
     // colouring state
     phys::DevBuf<unsigned long long> color_state;  // 4n: used masks | three rotating per-body priority buffers
-    // solver rows, colour-major, plane-major arrays of 16-byte elements (layout: solver.hip)
+    // solver rows, colour-major, plane-major arrays of 16-byte elements (layout: records.hpp)
     phys::DevBuf<uint32_t> row_src;  // row -> manifold (the colour sort)
-    // ONE allocation of 16 planes of cap float4 each; the arrays below are windows into it (plane 0 hdr, 1 n, 2-3 tb,
-    // 4-11 pt, 12-15 acc), so a kernel can address plane p of row d as all[p * cap + d] without choosing a pointer
+    // ONE allocation of 16 planes of cap float4 each (the two plane numberings: records.hpp), so a kernel can address
+    // plane p of row d as all[p * cap + d] without choosing a pointer
     phys::DevBuf<float> row_all;
-    phys::DevBuf<uint32_t> row_hdr;  // 4 per row: body a, body b, point count, update tickets
-    phys::DevBuf<float> row_n;       // 4 per row
-    phys::DevBuf<float> row_pt;      // 8 planes of float4
-    phys::DevBuf<float> row_tb;      // 2 planes of float4
-    phys::DevBuf<float> row_acc;     // 4 planes of float4 {pn, pt0, pt1, tag}
     // single-launch dataflow solver (k_solve_flow): in-flight body velocities travel between workgroups as
     // 16-byte granules {x, y, z, tag} (the tag says WHICH update of that body the data is: the data is its own
     // ready flag)

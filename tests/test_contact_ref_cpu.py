@@ -400,3 +400,44 @@ def test_heap_container_and_its_twin_on_the_ground_plane(ob):
         worst = max(worst, cr.velocity_error(out, lin1, ang1)[0])
     print(f"twin of the heap container (ground plane at the slab's height): oracle's spread {worst:.3g}; TOL_COUPLED is 2e-5")
     assert worst < 2e-5
+
+
+# ---------------------------------------------------------------- the oracle's bits, pinned
+def _contact_bits(ob):
+    """SHA-256 of what the oracle holds after 20 updates of four small scenes: poses, velocities and manifolds. (The
+    oracle reads no impulses out; in the warm-started scenes every update starts from the impulses of the one before, so
+    they are in the velocities.) The oracle has neither materials nor static colliders: the scene with restitution is
+    stood in for by the friction pairs (slop, max_bias cap, speculative points, clamped and sticking friction rows), the
+    static partners by static_boxes' bodies on a ground plane at the statics' top (a static row has a ground row's form)."""
+    import hashlib
+    rng = np.random.default_rng(9)
+    heap = cr.random_heap(5, n=128)
+    heap["inertia"] = cr._inertia(rng, 128, "full")
+    on_statics, _ = cr.static_boxes(21, 24)
+    scenes_ = {
+        "heap_full_inertia_warm": (heap, dict(gravity=(0, -9.81, 0))),
+        "heap_full_inertia_cold": (heap, dict(gravity=(0, -9.81, 0), flags=FLAG_COLLISIONS | FLAG_GROUND_PLANE | FLAG_NO_WARM_START)),
+        "friction_pairs_full_inertia": (cr.friction_pairs(3, 20, "full"), dict(gravity=(0, -9.81, 0))),
+        "bodies_on_a_plane_at_the_statics_top": (on_statics, dict(gravity=(0, -9.81, 0), ground_height=0.5)),
+    }
+    out = {}
+    for name, (bodies, kw) in scenes_.items():
+        w = oracle_world(ob, bodies, **kw)
+        w.set_threads(1)
+        w.update_n(DT, 20)
+        h = hashlib.sha256()
+        for arr in (*w.get_transforms(), *w.get_velocities(), *w.get_manifolds()):
+            h.update(np.ascontiguousarray(arr).tobytes())
+        assert w.get_stats().n_manifolds > 20, name
+        out[name] = h.hexdigest()
+    return out
+
+
+def test_oracle_bits_of_four_small_scenes_are_the_recorded_ones(ob):
+    """Oracle and kernels compile the same include/spec/contact_solve.h, so GPU-equals-oracle cannot see a slip made in
+    that header: tests/golden/contact_bits.json holds the hashes recorded before its row arithmetic was last restated."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(__file__), "golden", "contact_bits.json")) as f:
+        want = json.load(f)
+    assert _contact_bits(ob) == want

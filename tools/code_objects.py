@@ -2,6 +2,10 @@
 its kernels and their scratch (private segment), LDS, VGPR and SGPR use.
 
     python tools/code_objects.py [path/to/libphysics_hip.so]
+    python tools/code_objects.py --diff OTHER.so [path/to/libphysics_hip.so]
+
+--diff: per kernel, whether the disassembly (instruction text without addresses and comments) equals OTHER.so's; where it
+does not, the instruction counts and VGPR, SGPR, LDS and scratch of both, OTHER's first.
 
 Used by tests/test_build_rules.py for the "no kernel uses scratch memory" rule."""
 import os
@@ -68,9 +72,54 @@ def count_instructions(lib, mnemonics):
     return total
 
 
+def disassembly(lib):
+    """{kernel name: [instruction text without addresses and comments]} of every kernel in the library."""
+    names = {k["name"] for k in kernels(lib)}
+    out, cur = {}, None
+    for image in code_objects(lib):
+        with tempfile.NamedTemporaryFile(suffix=".elf") as f:
+            f.write(image)
+            f.flush()
+            text = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", f.name], check=True,
+                                  capture_output=True, text=True).stdout
+        for line in text.splitlines():
+            m = re.match(r"^[0-9a-f]* ?<(.+)>:$", line)
+            if m:
+                cur = out.setdefault(m.group(1), []) if m.group(1) in names else None
+            elif cur is not None and line.startswith(("\t", " ")) and line.strip():
+                cur.append(re.sub(r"\s*//.*$", "", line).strip())
+    return out
+
+
+def diff(lib, other):
+    """Print the --diff table; returns the number of kernels whose disassembly differs or that only one side has."""
+    mine, theirs = disassembly(lib), disassembly(other)
+    res = {side: {k["name"]: k for k in kernels(path)} for side, path in (("mine", lib), ("theirs", other))}
+    differ = 0
+    for name in sorted(set(mine) | set(theirs)):
+        short = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.split("(")[0].strip()[:70]
+        if name not in mine or name not in theirs:
+            differ += 1
+            print(f"{short:70s} only in {'this library' if name in mine else 'OTHER'}")
+        elif mine[name] == theirs[name]:
+            print(f"{short:70s} identical ({len(mine[name])} instructions)")
+        else:
+            differ += 1
+            a, b = res["theirs"][name], res["mine"][name]
+            print(f"{short:70s} DIFFERS: instructions {len(theirs[name])} -> {len(mine[name])}, vgprs {a['vgprs']} -> {b['vgprs']}, "
+                  f"sgprs {a['sgprs']} -> {b['sgprs']}, lds {a['lds']} -> {b['lds']}, scratch {a['scratch']} -> {b['scratch']}")
+    print(f"{len(set(mine) | set(theirs))} kernels, {differ} differ")
+    return differ
+
+
 if __name__ == "__main__":
     here = os.path.dirname(os.path.abspath(__file__))
     args = [a for a in sys.argv[1:] if a != "--check"]
+    other = None
+    if "--diff" in args:
+        at = args.index("--diff")
+        other = args[at + 1]
+        del args[at:at + 2]
     lib = args[0] if args else os.path.join(here, "..", "physics_amd", "csrc", "libphysics_hip.so")
     if "--check" in sys.argv:
         # the build's own gate (csrc/Makefile): the two rules of DESIGN.md section 8 hold on the code objects just linked,
@@ -80,6 +129,9 @@ if __name__ == "__main__":
         if packed or bad:
             print(f"code object rules violated: {packed} packed fp32 arithmetic instructions; scratch / spills: {bad}", file=sys.stderr)
             sys.exit(1)
+        sys.exit(0)
+    if other:
+        diff(lib, other)
         sys.exit(0)
     ks = kernels(lib)
     for k in sorted(ks, key=lambda k: k["name"]):
