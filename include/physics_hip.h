@@ -543,6 +543,67 @@ int32_t phys_trigger_events_enable(phys_world* w, uint64_t capacity);
 int32_t phys_get_trigger_events(phys_world* w, phys_trigger_event* out, uint64_t cap, uint64_t* n, uint64_t* n_dropped);
 int32_t phys_get_trigger_overlaps(phys_world* w, uint64_t cap, uint64_t* offsets_out /*n_triggers + 1*/, uint32_t* ids_out /*cap*/);
 
+/* --- force fields: volumes that push, drag and attract the bodies inside (new: the reference has one global gravity) ---
+ * A world keeps up to PHYS_MAX_FORCE_FIELDS force fields. A field is a volume plus a law. The volume is a SPHERE, BOX or
+ * CAPSULE with the bodies' half_extent conventions at pos with the unit quaternion rot_ijkw. Fields are NOT bodies: nothing
+ * collides with them and no query sees them. They add to the force / torque accumulators, nothing else.
+ * Who. Field k acts on OWNED body i iff the body's position (its centre of mass, pos[i]) lies in the closed volume, that
+ *   position is finite, and (category[i] & mask[k]) != 0 (the triggers' rule; category: phys_set_body_filters; a NULL mask
+ *   array means every body and loads no filter). The test uses the centre, not the shape: PHYS_SHAPE_NONE bodies - the
+ *   reference's own, and every body of a world without PHYS_FLAG_COLLISIONS - are affected too, and a fall-off with
+ *   distance has one meaning.
+ * Laws. Each field has a 3-vector vec, two coefficients coef[0..1] and an integer exponent:
+ *   PHYS_FIELD_ACCEL   F += mass * vec. A true acceleration: a zero-gravity room (for unit masses vec = -gravity_force), a
+ *                      directed well, a conveyor of air. (The global gravity stays the reference's: the same FORCE on
+ *                      every body.)
+ *   PHYS_FIELD_DRAG    F += -coef[0] * (v - vec), T += -coef[1] * w, with v, w the body's linear and angular velocity at the
+ *                      start of the update and vec the medium's velocity (wind); coef[0], coef[1] >= 0. One field over the
+ *                      whole scene is linear and angular damping.
+ *   PHYS_FIELD_RADIAL  with d = x - c (c = the field's pos) and r = |d|:
+ *                      F += coef[0] * (r0 / max(r, r0))^exponent * d / r, r0 = coef[1] > 0, exponent 0, 1 or 2 (by
+ *                      multiplication, no pow). r == 0 gives nothing. coef[0] > 0 pushes outward (held for one update: an
+ *                      impulse F * dt), coef[0] < 0 attracts; the magnitude never exceeds |coef[0]|.
+ * Order. A body's sums start from its accumulators and take the contributions in ascending field index, each formed
+ *   completely before it is added; all arithmetic is float32 in the operation order of include/spec/force_field.h (which a
+ *   host compiler reads alone). A body's result depends on that body, the field set and the world state only: the same bits
+ *   across runs, batch sizes and launch shapes. Accumulators of bodies no field acts on are not touched.
+ * When. At the start of EVERY phys_update, and of each update of a phys_update_n batch, before the constraint phase (whose
+ *   right-hand side reads the accumulators: a pinned body in a wind feels it) and the velocity half, from the poses and
+ *   velocities the previous update left. phys_step alone applies none, as it applies no gravity; its companion is
+ *   phys_apply_force_fields, the twin of phys_apply_gravity: it evaluates the fields now, into the accumulators, where
+ *   phys_get_forces reads them and the next phys_step or phys_update consumes them (an update adds its own evaluation on
+ *   top). A world without fields launches exactly what it launched before they existed.
+ *
+ * phys_set_force_fields: replaces the whole set; n = 0 clears it and frees its buffers. rot_ijkw NULL = identity, mask
+ *   NULL = every body, exponent NULL = 0. PHYS_ERR_INVALID_ARG, the message naming the field and the reason: an unknown
+ *   kind or shape, a non-finite number, a negative half extent, a negative drag coefficient, r0 <= 0, an exponent above 2;
+ *   also n > PHYS_MAX_FORCE_FIELDS and a NULL array that is required. Synchronises the world's stream. The set names no body
+ *   and survives phys_set_bodies.
+ * phys_set_force_field_poses: new positions (and rotations; rot_ijkw NULL keeps them) for the set that is there, from the
+ *   next evaluation on: a moving wind zone, an attractor carried by something. PHYS_ERR_INVALID_ARG: n differs from the
+ *   field count, NULL pos, a non-finite value.
+ * phys_set_force_field_params: new vec and coef for the set that is there (kinds, volumes and exponents stay), held to
+ *   each field's law as above; a strength of 0 switches a field off without rebuilding the set. PHYS_ERR_INVALID_ARG: n
+ *   differs from the field count, a NULL array, a value the law refuses.
+ * Sharded worlds (phys_config.max_ghosts > 0) answer all four calls with PHYS_ERR_UNSUPPORTED, like the material calls.
+ * Cost: one kernel per update, one lane per owned body, only in a world with fields; 12 bytes of position per body, 32 more
+ *   with a DRAG field, 8 more with masks, and 48 of accumulators for the bodies a field acts on. DESIGN.md section 22.
+ *   Added without an ABI version change (no struct changed): a library that predates them lacks the symbols. */
+#define PHYS_MAX_FORCE_FIELDS 1024u
+#define PHYS_FIELD_ACCEL  0u
+#define PHYS_FIELD_DRAG   1u
+#define PHYS_FIELD_RADIAL 2u
+
+int32_t phys_set_force_fields(phys_world* w, uint64_t n, const uint32_t* kind /*n*/, const uint32_t* shape_type /*n*/,
+                              const float* pos /*3n*/, const float* rot_ijkw /*4n, NULL = identity*/,
+                              const float* half_extent /*3n*/, const uint16_t* mask /*n, NULL = every body*/,
+                              const float* vec /*3n*/, const float* coef /*2n*/, const uint32_t* exponent /*n, NULL = 0*/);
+int32_t phys_set_force_field_poses(phys_world* w, uint64_t n /* == field count */, const float* pos /*3n*/,
+                                   const float* rot_ijkw /*4n, NULL = keep*/);
+int32_t phys_set_force_field_params(phys_world* w, uint64_t n /* == field count */, const float* vec /*3n*/,
+                                    const float* coef /*2n*/);
+int32_t phys_apply_force_fields(phys_world* w);
+
 /* --- per-stage device timing (HIP events on the world's stream), for bench.py's roofline --- */
 #define PHYS_STAGE_STEP_FULL 0u     /* gravity + RigidBody::step, one kernel (no collisions) */
 #define PHYS_STAGE_VELOCITY_AABB 1u /* gravity + velocity half + AABB */

@@ -37,6 +37,9 @@ CONTACT_BEGIN, CONTACT_END = 1, 2
 # trigger volumes (include/physics_hip.h): the most a world keeps, and phys_trigger_event.kind
 MAX_TRIGGERS = 1024
 TRIGGER_ENTER, TRIGGER_EXIT = 1, 2
+# force fields (include/physics_hip.h): the most a world keeps, and the kinds of law
+MAX_FORCE_FIELDS = 1024
+FIELD_ACCEL, FIELD_DRAG, FIELD_RADIAL = 0, 1, 2
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -224,6 +227,10 @@ PROTOTYPES = {
     "phys_trigger_events_enable": (C.c_int32, [C.c_void_p, C.c_uint64]),
     "phys_get_trigger_events": (C.c_int32, [C.c_void_p, C.POINTER(PhysTriggerEvent), C.c_uint64, u64p, u64p]),
     "phys_get_trigger_overlaps": (C.c_int32, [C.c_void_p, C.c_uint64, u64p, u32p]),
+    "phys_set_force_fields": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, u32p, f32p, f32p, f32p, u16p, f32p, f32p, u32p]),
+    "phys_set_force_field_poses": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p]),
+    "phys_set_force_field_params": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p]),
+    "phys_apply_force_fields": (C.c_int32, [C.c_void_p]),
     "phys_profile_enable": (C.c_int32, [C.c_void_p, C.c_int32]),
     "phys_profile_get": (C.c_int32, [C.c_void_p, C.POINTER(PhysProfile)]),
     "phys_get_device_view": (C.c_int32, [C.c_void_p, C.POINTER(PhysDeviceView)]),

@@ -468,6 +468,7 @@ static int32_t enqueue_update(phys_world* w, float dt) {
     const DebugSwitches& dbg = debug_switches();
     const bool have_constraints = !w->constraints.empty();
     bool gravity_pending = true;
+    if (w->n_fields) launch_force_fields(w);  // force fields: into the accumulators, from the poses and velocities as they stand
     if (have_constraints) {
         // the constraint right-hand side reads Q = force/torque accumulators including gravity (constraints.rs:92-104):
         // the constraint kernel adds gravity to the accumulators of the bodies it reads, and the step kernel adds
@@ -1008,6 +1009,55 @@ int32_t phys_set_trigger_poses(phys_world* w, uint64_t n, const float* pos, cons
     PHYS_TRY(in.copy(hipMemcpyHostToDevice));
     PHYS_TRY(triggers_set_poses(w, in.at(s_pos), in.at(s_rot)));  // behind the updates already enqueued
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    return PHYS_OK;
+}
+
+// ---- force fields: checked and staged on the host (setup.hpp), the records built on the device ----
+// who pushes a ghost is a question for a sharded scene that needs it: a sharded world refuses the calls, like the materials
+#define PHYS_NO_FIELDS_WHEN_SHARDED(w) \
+    do { if ((w)->cfg.max_ghosts > 0) return fail(PHYS_ERR_UNSUPPORTED, "force fields are not supported in a world with max_ghosts > 0"); } while (0)
+
+int32_t phys_set_force_fields(phys_world* w, uint64_t n, const uint32_t* kind, const uint32_t* shape_type, const float* pos,
+                              const float* rot_ijkw, const float* half_extent, const uint16_t* mask, const float* vec, const float* coef,
+                              const uint32_t* exponent) {
+    // the arguments first, as phys_set_triggers checks them
+    if (n > PHYS_MAX_FORCE_FIELDS) return fail(PHYS_ERR_INVALID_ARG, "phys_set_force_fields: more than PHYS_MAX_FORCE_FIELDS force fields");
+    if (n && (!kind || !shape_type || !pos || !half_extent || !vec || !coef))
+        return fail(PHYS_ERR_INVALID_ARG, "force fields need kind, shape_type, pos, half_extent, vec and coef");
+    std::string bad;
+    if (field_set_error(n, kind, shape_type, pos, rot_ijkw, half_extent, vec, coef, exponent, bad)) return fail(PHYS_ERR_INVALID_ARG, bad.c_str());
+    ENTER(w);
+    PHYS_NO_FIELDS_WHEN_SHARDED(w);
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // updates in flight read the set that is replaced
+    return fields_set(w, stage_fields(n, kind, shape_type, pos, rot_ijkw, half_extent, mask, vec, coef, exponent));
+}
+
+int32_t phys_set_force_field_poses(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw) {
+    ENTER(w);
+    PHYS_NO_FIELDS_WHEN_SHARDED(w);
+    if (n != w->n_fields) return fail(PHYS_ERR_INVALID_ARG, "phys_set_force_field_poses: n must equal the force field count");
+    if (n && !pos) return fail(PHYS_ERR_INVALID_ARG, "phys_set_force_field_poses: null pos");
+    if (n == 0) return PHYS_OK;
+    if (!restage_field_poses(w->ff_host, pos, rot_ijkw)) return fail(PHYS_ERR_INVALID_ARG, "phys_set_force_field_poses: non-finite pose");
+    return fields_rebuild(w);
+}
+
+int32_t phys_set_force_field_params(phys_world* w, uint64_t n, const float* vec, const float* coef) {
+    ENTER(w);
+    PHYS_NO_FIELDS_WHEN_SHARDED(w);
+    if (n != w->n_fields) return fail(PHYS_ERR_INVALID_ARG, "phys_set_force_field_params: n must equal the force field count");
+    if (n && (!vec || !coef)) return fail(PHYS_ERR_INVALID_ARG, "phys_set_force_field_params: null vec or coef");
+    if (n == 0) return PHYS_OK;
+    std::string bad;
+    if (restage_field_params(w->ff_host, vec, coef, bad)) return fail(PHYS_ERR_INVALID_ARG, bad.c_str());
+    return fields_rebuild(w);
+}
+
+int32_t phys_apply_force_fields(phys_world* w) {
+    ENTER(w);
+    PHYS_NO_FIELDS_WHEN_SHARDED(w);
+    launch_force_fields(w);
+    PHYS_HIP_TRY(hipGetLastError());
     return PHYS_OK;
 }
 

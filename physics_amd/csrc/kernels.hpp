@@ -314,6 +314,13 @@ int32_t triggers_set(phys_world* w, uint64_t n, const uint32_t* shape_type, cons
 int32_t triggers_set_poses(phys_world* w, const float* pos, const float* rot /* null: keep */);  // staged device arrays; keeps the occupancy
 int32_t triggers_reset(phys_world* w);  // forget the occupancy and the pending events (a new trigger or body set)
 
+// force fields (fields.hip): one kernel in front of every update, only in a world with fields; it adds to the force / torque
+// accumulators and marks them dirty, so the step kernels' FORCES instances read and zero them
+void launch_force_fields(phys_world* w);
+// the set from its staged form (setup.hpp stage_fields; arguments checked by the caller; empty: clears and frees)
+int32_t fields_set(phys_world* w, FieldStaging&& staged);
+int32_t fields_rebuild(phys_world* w);  // w->ff_host was patched (poses, params): send it again and rebuild the records
+
 // constraints.hip
 int32_t constraints_alloc(phys_world* w);
 void launch_constraint_phase(phys_world* w, bool gravity_pending);  // Q = accumulators (+ gravity when still pending)

@@ -1,6 +1,6 @@
 // setup.hpp — what the host computes ONCE per body set, static set or constraint list, as pure functions of host arrays and a
 // few scalars: table sizes, capacities, cluster shapes and homes, the static colliders' grid, the staged body arrays, the
-// constraint column tables, argument validation. Nothing of HIP in here and no phys_world: a host compiler reads it alone,
+// constraint column tables, the staged force fields, argument validation. Nothing of HIP in here and no phys_world: a host compiler reads it alone,
 // and tests/cpp/setup_probe.cpp holds every function to hand-worked values or a brute-force restatement
 // (tests/test_setup_cpu.py). The .hip files keep the allocations, the copies and the launches.
 #pragma once
@@ -19,6 +19,7 @@
 #include "../../include/spec/collide.h"
 #include "../../include/spec/contact_solve.h"
 #include "../../include/spec/det_math.h"
+#include "../../include/spec/force_field.h"
 #include "../../include/spec/vec.h"
 #include "plan.hpp"
 
@@ -567,6 +568,104 @@ inline bool pack_materials(uint64_t n, const float* friction, const float* resti
         out[2 * k] = f; out[2 * k + 1] = e;
     }
     return true;
+}
+
+// ---- force fields: the checks and the staged form of phys_set_force_fields and its two updates --------
+// null when every field has a known kind, a SPHERE, BOX or CAPSULE volume, finite numbers, a non-negative half extent, and
+// coefficients its law admits; else the message for the FIRST offending field (held by msg): its kind first, then its shape,
+// then non-finite, then a negative half extent, then the law. rot / exponent null: not checked (identity / 0).
+inline const char* field_law_error(uint32_t kind, const float* coef2, uint32_t exponent) {
+    if (kind == PHYS_FIELD_DRAG && (coef2[0] < 0.0f || coef2[1] < 0.0f)) return ": negative drag coefficient";
+    if (kind == PHYS_FIELD_RADIAL && !(coef2[1] > 0.0f)) return ": r0 (coef[1]) must be above 0";
+    if (exponent > 2u) return ": exponent above 2";
+    return nullptr;
+}
+inline const char* field_set_error(uint64_t n, const uint32_t* kind, const uint32_t* shape, const float* pos, const float* rot, const float* he,
+                                   const float* vec, const float* coef, const uint32_t* exponent, std::string& msg) {
+    for (uint64_t k = 0; k < n; ++k) {
+        const char* what = nullptr;
+        if (kind[k] != PHYS_FIELD_ACCEL && kind[k] != PHYS_FIELD_DRAG && kind[k] != PHYS_FIELD_RADIAL) {
+            what = ": kind is neither ACCEL nor DRAG nor RADIAL";
+        } else if (shape[k] != PHYS_SHAPE_SPHERE && shape[k] != PHYS_SHAPE_BOX && shape[k] != PHYS_SHAPE_CAPSULE) {
+            what = ": shape is neither SPHERE nor BOX nor CAPSULE";
+        } else {
+            bool finite = std::isfinite(coef[2 * k]) && std::isfinite(coef[2 * k + 1]), negative = false;
+            for (int a = 0; a < 3; ++a) {
+                finite = finite && std::isfinite(pos[3 * k + a]) && std::isfinite(he[3 * k + a]) && std::isfinite(vec[3 * k + a]);
+                negative = negative || he[3 * k + a] < 0.0f;
+            }
+            if (rot)
+                for (int a = 0; a < 4; ++a) finite = finite && std::isfinite(rot[4 * k + a]);
+            if (!finite) what = ": non-finite number";
+            else if (negative) what = ": negative half extent";
+            else what = field_law_error(kind[k], coef + 2 * k, exponent ? exponent[k] : 0u);
+        }
+        if (what) {
+            msg = "force field " + std::to_string(k) + what;
+            return msg.c_str();
+        }
+    }
+    return nullptr;
+}
+
+// The set as the device keeps it (include/spec/force_field.h ff_staged, 80 bytes per field) and what selects the evaluation's
+// instance: a mask array was given; some field is a DRAG (the velocity record is read); some field is an ACCEL (the mass is).
+struct FieldStaging {
+    std::vector<ff_staged> staged;
+    bool masked = false, drag = false, accel = false;
+};
+// n fields (arguments checked by field_set_error); rot null: identity, mask null: every body, exponent null: 0
+inline FieldStaging stage_fields(uint64_t n, const uint32_t* kind, const uint32_t* shape, const float* pos, const float* rot, const float* he,
+                                 const uint16_t* mask, const float* vec, const float* coef, const uint32_t* exponent) {
+    FieldStaging out;
+    out.staged.resize(n);
+    out.masked = n != 0 && mask != nullptr;
+    for (uint64_t k = 0; k < n; ++k) {
+        quat q;
+        if (rot) { q.i = rot[4 * k]; q.j = rot[4 * k + 1]; q.k = rot[4 * k + 2]; q.w = rot[4 * k + 3]; }
+        else { q.i = 0.0f; q.j = 0.0f; q.k = 0.0f; q.w = 1.0f; }
+        out.staged[k] = ff_stage(kind[k], shape[k], mask ? (uint32_t)mask[k] : 0xFFFFu, exponent ? exponent[k] : 0u,
+                                 v3_make(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]), q, v3_make(he[3 * k], he[3 * k + 1], he[3 * k + 2]),
+                                 v3_make(vec[3 * k], vec[3 * k + 1], vec[3 * k + 2]), coef[2 * k], coef[2 * k + 1]);
+        if (kind[k] == PHYS_FIELD_DRAG) out.drag = true;
+        if (kind[k] == PHYS_FIELD_ACCEL) out.accel = true;
+    }
+    return out;
+}
+// phys_set_force_field_poses: new centres and, unless rot is null, rotations of the staged set; false: a non-finite value
+// (nothing changed then)
+inline bool restage_field_poses(std::vector<ff_staged>& staged, const float* pos, const float* rot) {
+    const size_t n = staged.size();
+    for (size_t k = 0; k < 3 * n; ++k)
+        if (!std::isfinite(pos[k])) return false;
+    for (size_t k = 0; rot && k < 4 * n; ++k)
+        if (!std::isfinite(rot[k])) return false;
+    for (size_t k = 0; k < n; ++k) {
+        staged[k].s[1] = ff_f4_make(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2], 0.0f);
+        if (rot) staged[k].s[2] = ff_f4_make(rot[4 * k], rot[4 * k + 1], rot[4 * k + 2], rot[4 * k + 3]);
+    }
+    return true;
+}
+// phys_set_force_field_params: new vec and coef of the staged set, each held to its field's law (kind and exponent stay);
+// null, or the message for the first offending field (nothing changed then)
+inline const char* restage_field_params(std::vector<ff_staged>& staged, const float* vec, const float* coef, std::string& msg) {
+    const size_t n = staged.size();
+    for (size_t k = 0; k < n; ++k) {
+        const char* what = nullptr;
+        if (!(std::isfinite(vec[3 * k]) && std::isfinite(vec[3 * k + 1]) && std::isfinite(vec[3 * k + 2]) && std::isfinite(coef[2 * k]) &&
+              std::isfinite(coef[2 * k + 1])))
+            what = ": non-finite number";
+        else what = field_law_error(ff_f2u(staged[k].s[0].x), coef + 2 * k, ff_f2u(staged[k].s[0].w));
+        if (what) {
+            msg = "force field " + std::to_string(k) + what;
+            return msg.c_str();
+        }
+    }
+    for (size_t k = 0; k < n; ++k) {
+        staged[k].s[3].w = coef[2 * k];
+        staged[k].s[4] = ff_f4_make(vec[3 * k], vec[3 * k + 1], vec[3 * k + 2], coef[2 * k + 1]);
+    }
+    return nullptr;
 }
 
 }  // namespace phys

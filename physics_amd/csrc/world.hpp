@@ -303,6 +303,13 @@ struct phys_world {
     uint64_t tg_capacity = 0;            // trigger events the device keeps between two drains (0: off)
     phys::DevBuf<uint32_t> tg_buf;       // 4 words = one phys_trigger_event per slot
     phys::DevBuf<unsigned long long> tg_cursor;  // trigger events raised since the last drain (allocated with the triggers or the events)
+    // force fields (fields.hip): nothing below is allocated, and nothing launched, without fields
+    uint64_t n_fields = 0;
+    bool ff_masked = false;              // phys_set_force_fields was given a mask array: the evaluation's filtered instance
+    bool ff_drag = false, ff_accel = false;  // some field is a DRAG (the velocity record is read) / an ACCEL (the mass is)
+    std::vector<ff_staged> ff_host;      // the set as staged (setup.hpp stage_fields): poses and params are patched here, then sent again
+    phys::DevBuf<float> ff_stage;        // 20 floats per field: the device copy of ff_host
+    phys::DevBuf<float> ff_rec;          // 28 floats per field: the record the evaluation reads (include/spec/force_field.h ff_record)
     // multi-GPU halo
     phys::DevBuf<uint32_t> cross_pairs;
     uint64_t max_cross_pairs = 0;

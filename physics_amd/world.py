@@ -61,6 +61,14 @@ def _material_field(a, n, name, hi):
     return v
 
 
+def _field_law_check(kind, coef):
+    """What each force field's law asks of its coefficients (n kinds, (n, 2) coef): DRAG >= 0, RADIAL r0 > 0."""
+    if ((kind == _abi.FIELD_DRAG)[:, None] & (coef < 0)).any():
+        raise ValueError("coef: a DRAG field's coefficients must be >= 0")
+    if ((kind == _abi.FIELD_RADIAL) & ~(coef[:, 1] > 0)).any():
+        raise ValueError("coef: a RADIAL field's r0 (coef[1]) must be above 0")
+
+
 def _query_mask(mask, n):
     """The per-query mask of a _filtered query: a scalar or (n,) integers in [0, 0xFFFF]."""
     return _filter_field(mask, n, "mask", 0, 0xFFFF, np.uint16)
@@ -94,6 +102,7 @@ class World:
         self.n = 0
         self.n_static = 0
         self.n_triggers = 0
+        self.n_fields, self._field_kinds = 0, np.zeros(0, np.uint32)
         self._ck(self.lib.phys_create(C.byref(self.cfg), C.byref(self.h)))
 
     def _ck(self, rc):
@@ -511,6 +520,89 @@ class World:
         if p.shape[0] != self.n_triggers or (r is not None and r.shape[0] != self.n_triggers):
             raise ValueError(f"pos / rot: need {self.n_triggers} rows (the trigger count)")
         self._ck(self.lib.phys_set_trigger_poses(self.h, self.n_triggers, _p(p), _p(r)))
+
+    # ---- force fields (include/physics_hip.h): volumes that push, drag and attract the bodies whose centre is inside
+    def set_force_fields(self, kind, shape_type, pos, rot=None, half_extent=None, mask=None, vec=None, coef=None, exponent=None):
+        """Replace the force fields (phys_set_force_fields): kind scalar or (n,) FIELD_ACCEL / FIELD_DRAG / FIELD_RADIAL,
+        shape_type scalar or (n,) SHAPE_SPHERE / BOX / CAPSULE, pos (n, 3), rot (n, 4) [i, j, k, w] or None (identity),
+        half_extent (3,) or (n, 3) with the bodies' conventions, mask a scalar or (n,) u16 or None (every body), vec (3,) or
+        (n, 3) (None: zeros), coef (2,) or (n, 2) (ACCEL: unused; DRAG: linear and angular coefficient, >= 0; RADIAL: strength
+        and r0 > 0), exponent a scalar or (n,) in 0..2 or None (0). An empty pos clears the set. At most MAX_FORCE_FIELDS."""
+        p = _f(pos).reshape(-1, 3)
+        n = p.shape[0]
+        if n > _abi.MAX_FORCE_FIELDS:
+            raise ValueError(f"at most {_abi.MAX_FORCE_FIELDS} force fields")
+        if n and (half_extent is None or coef is None):
+            raise ValueError("half_extent and coef are required")
+
+        def words(a, name, known):
+            v = np.asarray(a if n else np.zeros(0, np.uint32))
+            if v.dtype.kind not in "iub":
+                raise ValueError(f"{name}: needs integers")
+            if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != n):
+                raise ValueError(f"{name}: needs {n} values, got shape {v.shape}")
+            if v.size and not np.isin(v, known).all():
+                raise ValueError(f"{name}: values must be among {known}")
+            return np.ascontiguousarray(np.broadcast_to(v.astype(np.uint32), (n,)))
+
+        def rows(a, cols, name):
+            v = np.asarray(a if n else np.zeros((0, cols)), np.float32).reshape(-1, cols)
+            if v.shape[0] not in (1, n):
+                raise ValueError(f"{name}: needs {cols} or {n} x {cols} values, got shape {np.shape(a)}")
+            v = np.ascontiguousarray(np.broadcast_to(v, (n, cols)))
+            if not np.isfinite(v).all():
+                raise ValueError(f"{name}: non-finite value")
+            return v
+
+        kd = words(kind, "kind", (_abi.FIELD_ACCEL, _abi.FIELD_DRAG, _abi.FIELD_RADIAL))
+        st = words(shape_type, "shape_type", (_abi.SHAPE_SPHERE, _abi.SHAPE_BOX, _abi.SHAPE_CAPSULE))
+        ex = None if exponent is None else words(exponent, "exponent", (0, 1, 2))
+        he = rows(half_extent, 3, "half_extent")
+        vc = rows(np.zeros(3, np.float32) if vec is None else vec, 3, "vec")
+        cf = rows(coef, 2, "coef")
+        r = None if rot is None else _f(rot).reshape(-1, 4)
+        if r is not None and r.shape[0] != n:
+            raise ValueError("rot does not match the force field count")
+        if not np.isfinite(p).all() or (r is not None and not np.isfinite(r).all()):
+            raise ValueError("pos / rot: non-finite value")
+        if (he < 0).any():
+            raise ValueError("half_extent: negative value")
+        _field_law_check(kd, cf)
+        m = _filter_field(mask, n, "mask", 0, 0xFFFF, np.uint16)
+        self._ck(self.lib.phys_set_force_fields(self.h, n, _p(kd, u32p), _p(st, u32p), _p(p), _p(r), _p(he), _p(m, u16p), _p(vc), _p(cf),
+                                                _p(ex, u32p)))
+        self.n_fields, self._field_kinds = n, kd
+
+    def set_force_field_poses(self, pos, rot=None):
+        """New positions (n_fields, 3) and, unless None, rotations (n_fields, 4) of the force fields
+        (phys_set_force_field_poses), from the next update on."""
+        p = _f(pos).reshape(-1, 3)
+        r = None if rot is None else _f(rot).reshape(-1, 4)
+        if p.shape[0] != self.n_fields or (r is not None and r.shape[0] != self.n_fields):
+            raise ValueError(f"pos / rot: need {self.n_fields} rows (the force field count)")
+        if not np.isfinite(p).all() or (r is not None and not np.isfinite(r).all()):
+            raise ValueError("pos / rot: non-finite value")
+        self._ck(self.lib.phys_set_force_field_poses(self.h, self.n_fields, _p(p), _p(r)))
+
+    def set_force_field_params(self, vec, coef):
+        """New vec (3,) or (n_fields, 3) and coef (2,) or (n_fields, 2) of the force fields (phys_set_force_field_params);
+        kinds, volumes and exponents stay. A strength of 0 switches a field off without rebuilding the set."""
+        n = self.n_fields
+        v = np.asarray(vec, np.float32).reshape(-1, 3)
+        c = np.asarray(coef, np.float32).reshape(-1, 2)
+        if v.shape[0] not in (1, n) or c.shape[0] not in (1, n):
+            raise ValueError(f"vec / coef: need one row or {n} rows (the force field count)")
+        v = np.ascontiguousarray(np.broadcast_to(v, (n, 3)))
+        c = np.ascontiguousarray(np.broadcast_to(c, (n, 2)))
+        if not (np.isfinite(v).all() and np.isfinite(c).all()):
+            raise ValueError("vec / coef: non-finite value")
+        _field_law_check(self._field_kinds, c)
+        self._ck(self.lib.phys_set_force_field_params(self.h, n, _p(v), _p(c)))
+
+    def apply_force_fields(self):
+        """Evaluate the force fields now, into the force / torque accumulators (phys_apply_force_fields): the twin of
+        apply_gravity for a caller that steps with step()."""
+        self._ck(self.lib.phys_apply_force_fields(self.h))
 
     def enable_trigger_events(self, capacity):
         """Keep up to `capacity` trigger events on the device between two drains (phys_trigger_events_enable); 0 turns

@@ -36,6 +36,11 @@ pub const PHYS_CONTACT_END: u32 = 2;
 pub const PHYS_MAX_TRIGGERS: u32 = 1024;
 pub const PHYS_TRIGGER_ENTER: u32 = 1;
 pub const PHYS_TRIGGER_EXIT: u32 = 2;
+// force fields: the most a world keeps, and the kinds of law
+pub const PHYS_MAX_FORCE_FIELDS: u32 = 1024;
+pub const PHYS_FIELD_ACCEL: u32 = 0;
+pub const PHYS_FIELD_DRAG: u32 = 1;
+pub const PHYS_FIELD_RADIAL: u32 = 2;
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -222,6 +227,10 @@ extern "C" {
     pub fn phys_trigger_events_enable(w: *mut phys_world, capacity: u64) -> i32;
     pub fn phys_get_trigger_events(w: *mut phys_world, out: *mut phys_trigger_event, cap: u64, n: *mut u64, n_dropped: *mut u64) -> i32;
     pub fn phys_get_trigger_overlaps(w: *mut phys_world, cap: u64, offsets_out: *mut u64, ids_out: *mut u32) -> i32;
+    pub fn phys_set_force_fields(w: *mut phys_world, n: u64, kind: *const u32, shape_type: *const u32, pos: *const f32, rot_ijkw: *const f32, half_extent: *const f32, mask: *const u16, vec: *const f32, coef: *const f32, exponent: *const u32) -> i32;
+    pub fn phys_set_force_field_poses(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32) -> i32;
+    pub fn phys_set_force_field_params(w: *mut phys_world, n: u64, vec: *const f32, coef: *const f32) -> i32;
+    pub fn phys_apply_force_fields(w: *mut phys_world) -> i32;
     pub fn phys_profile_enable(w: *mut phys_world, on: i32) -> i32;
     pub fn phys_profile_get(w: *mut phys_world, out: *mut phys_profile) -> i32;
     pub fn phys_get_device_view(w: *mut phys_world, out: *mut phys_device_view) -> i32;
