@@ -2,9 +2,9 @@
  * section 22): a volume plus a law that adds to the force / torque accumulators of the bodies whose centre lies inside.
  *
  * The reference (martingoe/physics) has one global gravity force and nothing local, so this header is the specification
- * itself: the point-in-volume tests, the three laws, the record a field is evaluated from, and the per-body accumulation
- * over a record array, as scalar f32 functions with a fixed operation order. The HIP kernels (physics_amd/csrc/fields.hip)
- * call exactly these functions, and a host compiler reads the header alone (tests/cpp/field_probe.cpp), so a GPU run and a
+ * itself: the point-in-volume tests, the three laws, what a field adds to the volume record of volume.h, and the per-body
+ * accumulation over a record array, as scalar f32 functions with a fixed operation order. The HIP kernel (physics_amd/csrc/
+ * fields.hip) calls exactly these functions, and a host compiler reads the header alone (tests/cpp/field_probe.cpp), so a GPU run and a
  * sequential CPU run agree bit for bit. Build with -ffp-contract=off; no pow, no libm beyond the correctly rounded sqrt.
  *
  * Order: a body's sums start from its accumulators and take the fields' contributions in ascending field index, each
@@ -15,27 +15,21 @@
 
 #include <stdint.h>
 
-#include "collide.h"
+#include "volume.h"
 
 #define PHYS_SPEC_FIELD_ACCEL 0u
 #define PHYS_SPEC_FIELD_DRAG 1u
 #define PHYS_SPEC_FIELD_RADIAL 2u
 
-/* 16 bytes, aligned: one vector load or store on the device */
-typedef struct __attribute__((aligned(16))) { float x, y, z, w; } ff_f4;
+/* One field as the evaluation reads it, 112 bytes: the volume's record (volume.h) with kind | shape << 8 | exponent << 16 in
+ * its word r[0].w and coef[0] in r[5].w, followed by law = {vec, coef[1]}. */
+#define FF_REC_VEC (VOL_REC_VEC + 1)
+typedef struct { vol_record vol; vol_f4 law; } ff_record;
 
-/* One field as the evaluation reads it, 112 bytes:
- *   r[0] = {AABB lo, kind | shape << 8 | exponent << 16}   r[1] = {AABB hi, mask}
- *   r[2] = {centre, h.x}   r[3] = {R row 0, h.y}   r[4] = {R row 1, h.z}   r[5] = {R row 2, coef[0]}   r[6] = {vec, coef[1]}
- * The AABB is the volume's exact box (body_aabb, margin 0); a volume whose box is not finite gets an inverted one and acts
- * on nothing. Integers travel as the bits of a float. */
-#define FF_REC_VEC 7
-typedef struct { ff_f4 r[FF_REC_VEC]; } ff_record;
-
-/* What the host stages per field (phys_set_force_fields) and the device keeps, 80 bytes = 20 words:
+/* What the host stages and keeps per field (phys_set_force_fields; poses and params are patched here), 80 bytes = 20 words:
  *   {kind, shape, mask, exponent} {pos, -} {rot ijkw} {half extent, coef[0]} {vec, coef[1]} */
 #define FF_STAGE_VEC 5
-typedef struct { ff_f4 s[FF_STAGE_VEC]; } ff_staged;
+typedef struct { vol_f4 s[FF_STAGE_VEC]; } ff_staged;
 
 /* what a field reads of one body: centre, velocities at the start of the update, mass, filter category */
 typedef struct {
@@ -50,9 +44,8 @@ typedef struct {
     int acted;
 } ff_sum;
 
-PHYS_HD float ff_u2f(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
-PHYS_HD uint32_t ff_f2u(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
-PHYS_HD ff_f4 ff_f4_make(float x, float y, float z, float w) { ff_f4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
+PHYS_HD float ff_u2f(uint32_t u) { return vol_u2f(u); }
+PHYS_HD uint32_t ff_f2u(float f) { return vol_f2u(f); }
 
 /* ---- the closed volumes: d = point - centre (world), R the volume's rotation matrix, h its half extents ---- */
 PHYS_HD int ff_in_sphere(v3 d, v3 h) { return v3_dot(d, d) <= h.x * h.x; }
@@ -91,58 +84,42 @@ PHYS_HD int ff_law_radial(v3 d, float coef0, float r0, uint32_t exponent, v3* F)
 }
 
 /* ---- records ---- */
-PHYS_HD ff_staged ff_stage(uint32_t kind, uint32_t shape, uint32_t mask, uint32_t exponent, v3 c, quat q, v3 h, v3 vec, float coef0,
+PHYS_HD ff_staged ff_staged_make(uint32_t kind, uint32_t shape, uint32_t mask, uint32_t exponent, v3 c, quat q, v3 h, v3 vec, float coef0,
                            float coef1) {
     ff_staged s;
-    s.s[0] = ff_f4_make(ff_u2f(kind), ff_u2f(shape), ff_u2f(mask), ff_u2f(exponent));
-    s.s[1] = ff_f4_make(c.x, c.y, c.z, 0.0f);
-    s.s[2] = ff_f4_make(q.i, q.j, q.k, q.w);
-    s.s[3] = ff_f4_make(h.x, h.y, h.z, coef0);
-    s.s[4] = ff_f4_make(vec.x, vec.y, vec.z, coef1);
+    s.s[0] = vol_f4_make(ff_u2f(kind), ff_u2f(shape), ff_u2f(mask), ff_u2f(exponent));
+    s.s[1] = vol_f4_make(c.x, c.y, c.z, 0.0f);
+    s.s[2] = vol_f4_make(q.i, q.j, q.k, q.w);
+    s.s[3] = vol_f4_make(h.x, h.y, h.z, coef0);
+    s.s[4] = vol_f4_make(vec.x, vec.y, vec.z, coef1);
     return s;
 }
 
 PHYS_HD ff_record ff_record_make(const ff_staged* s) {
     const uint32_t kind = ff_f2u(s->s[0].x), shape = ff_f2u(s->s[0].y), mask = ff_f2u(s->s[0].z), exponent = ff_f2u(s->s[0].w);
-    const v3 c = v3_make(s->s[1].x, s->s[1].y, s->s[1].z);
     quat q;
     q.i = s->s[2].x; q.j = s->s[2].y; q.k = s->s[2].z; q.w = s->s[2].w;
-    const v3 h = v3_make(s->s[3].x, s->s[3].y, s->s[3].z);
-    aabb_t b = body_aabb(c, q, h, shape, 0.0f);
-    const float sum = ((b.lo.x + b.lo.y) + (b.lo.z + b.hi.x)) + (b.hi.y + b.hi.z);
-    if (!(det_absf(sum) <= 3.0e38f)) { /* NaN or infinite: touches nothing */
-        b.lo = v3_make(3.0e38f, 3.0e38f, 3.0e38f);
-        b.hi = v3_make(-3.0e38f, -3.0e38f, -3.0e38f);
-    }
-    m33 R;
-    quat_to_m33(q, &R);
     ff_record r;
-    r.r[0] = ff_f4_make(b.lo.x, b.lo.y, b.lo.z, ff_u2f(kind | (shape << 8) | (exponent << 16)));
-    r.r[1] = ff_f4_make(b.hi.x, b.hi.y, b.hi.z, ff_u2f(mask));
-    r.r[2] = ff_f4_make(c.x, c.y, c.z, h.x);
-    r.r[3] = ff_f4_make(R.m[0], R.m[1], R.m[2], h.y);
-    r.r[4] = ff_f4_make(R.m[3], R.m[4], R.m[5], h.z);
-    r.r[5] = ff_f4_make(R.m[6], R.m[7], R.m[8], s->s[3].w);
-    r.r[6] = s->s[4];
+    r.vol = vol_record_make(shape, mask, v3_make(s->s[1].x, s->s[1].y, s->s[1].z), q, v3_make(s->s[3].x, s->s[3].y, s->s[3].z));
+    r.vol.r[0].w = ff_u2f(kind | (shape << 8) | (exponent << 16));
+    r.vol.r[5].w = s->s[3].w;
+    r.law = s->s[4];
     return r;
 }
 
 /* ---- one field on one body: 1 and its complete contribution, or 0 (filtered, outside, non-finite centre, r == 0).
  * masked == 0: the set has no masks and the category is not looked at. A non-finite centre fails the AABB comparisons. */
 PHYS_HD int ff_contribution(const ff_record* rec, const ff_body* b, int masked, v3* dF, v3* dT) {
-    const ff_f4 a0 = rec->r[0], a1 = rec->r[1];
-    if (masked && (b->category & ff_f2u(a1.w)) == 0u) return 0;
+    const vol_f4 a0 = rec->vol.r[0], a1 = rec->vol.r[1];
+    if (masked && (b->category & vol_mask(a1)) == 0u) return 0;
     const v3 x = b->x;
-    if (!(a0.x <= x.x && x.x <= a1.x && a0.y <= x.y && x.y <= a1.y && a0.z <= x.z && x.z <= a1.z)) return 0;
-    const ff_f4 r2 = rec->r[2], r3 = rec->r[3], r4 = rec->r[4], r5 = rec->r[5], r6 = rec->r[6];
-    const uint32_t word = ff_f2u(a0.w);
+    if (!vol_box_meets(a0, a1, x, x)) return 0;
+    const vol_f4 r2 = rec->vol.r[2], r3 = rec->vol.r[3], r4 = rec->vol.r[4], r5 = rec->vol.r[5], r6 = rec->law;
+    const uint32_t word = vol_word(a0);
     const uint32_t kind = word & 0xFFu, shape = (word >> 8) & 0xFFu, exponent = word >> 16;
-    m33 R;
-    R.m[0] = r3.x; R.m[1] = r3.y; R.m[2] = r3.z;
-    R.m[3] = r4.x; R.m[4] = r4.y; R.m[5] = r4.z;
-    R.m[6] = r5.x; R.m[7] = r5.y; R.m[8] = r5.z;
-    const v3 d = v3_sub(x, v3_make(r2.x, r2.y, r2.z));
-    if (!ff_in_volume(shape, &R, d, v3_make(r2.w, r3.w, r4.w))) return 0;
+    const m33 R = vol_rotation(r3, r4, r5);
+    const v3 d = v3_sub(x, vol_centre(r2));
+    if (!ff_in_volume(shape, &R, d, vol_half_extent(r2, r3, r4))) return 0;
     const v3 vec = v3_make(r6.x, r6.y, r6.z);
     *dT = v3_make(0.0f, 0.0f, 0.0f);
     if (kind == PHYS_SPEC_FIELD_ACCEL) {

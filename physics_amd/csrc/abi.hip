@@ -966,13 +966,7 @@ int32_t phys_overlap_filtered(phys_world* w, uint64_t n, const uint32_t* shape_t
     return overlap_host(w, n, shape_type, pos, rot_ijkw, half_extent, ignore_body, query_mask, cap, offsets_out, ids_out);
 }
 
-// ---- trigger volumes: the host arrays staged like a query's, the records built on the device ----
-static bool finite_all(const float* a, uint64_t count) {
-    bool f = true;
-    for (uint64_t k = 0; k < count; ++k) f = f && std::isfinite(a[k]);
-    return f;
-}
-
+// ---- trigger volumes: checked and staged on the host (setup.hpp), where the records are built too ----
 int32_t phys_set_triggers(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,
                           const float* half_extent, const uint16_t* mask) {
     // the arguments first, as phys_set_static_bodies checks them
@@ -982,37 +976,19 @@ int32_t phys_set_triggers(phys_world* w, uint64_t n, const uint32_t* shape_type,
     if (shape_set_error("trigger", n, shape_type, pos, rot_ijkw, half_extent, bad)) return fail(PHYS_ERR_INVALID_ARG, bad.c_str());
     ENTER(w);
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // updates in flight read the set that is replaced
-    if (n == 0) return triggers_set(w, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
-    Staging in{w, w->stage};
-    const auto s_type = in.add(shape_type, n);
-    const auto s_pos = in.add(pos, 3 * n), s_he = in.add(half_extent, 3 * n);
-    const auto s_rot = in.add(rot_ijkw, 4 * n, /*align=*/16);  // read as float4
-    const auto s_mask = in.add(mask, n);
-    PHYS_TRY(in.reserve());
-    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
-    PHYS_TRY(triggers_set(w, n, in.at(s_type), in.at(s_pos), in.at(s_rot), in.at(s_he), in.at(s_mask)));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // the staging buffer is the next query's
-    return PHYS_OK;
+    return triggers_set(w, stage_triggers(n, shape_type, pos, rot_ijkw, half_extent, mask));
 }
 
 int32_t phys_set_trigger_poses(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw) {
     ENTER(w);
     if (n != w->n_triggers) return fail(PHYS_ERR_INVALID_ARG, "phys_set_trigger_poses: n must equal the trigger count");
     if (n && !pos) return fail(PHYS_ERR_INVALID_ARG, "phys_set_trigger_poses: null pos");
-    if (n && (!finite_all(pos, 3 * n) || (rot_ijkw && !finite_all(rot_ijkw, 4 * n))))
-        return fail(PHYS_ERR_INVALID_ARG, "phys_set_trigger_poses: non-finite pose");
     if (n == 0) return PHYS_OK;
-    Staging in{w, w->stage};
-    const auto s_pos = in.add(pos, 3 * n);
-    const auto s_rot = in.add(rot_ijkw, 4 * n, /*align=*/16);
-    PHYS_TRY(in.reserve());
-    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
-    PHYS_TRY(triggers_set_poses(w, in.at(s_pos), in.at(s_rot)));  // behind the updates already enqueued
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    return PHYS_OK;
+    if (!restage_trigger_poses(w->tg_host, pos, rot_ijkw)) return fail(PHYS_ERR_INVALID_ARG, "phys_set_trigger_poses: non-finite pose");
+    return triggers_rebuild(w);
 }
 
-// ---- force fields: checked and staged on the host (setup.hpp), the records built on the device ----
+// ---- force fields: checked and staged on the host (setup.hpp), where the records are built too ----
 // who pushes a ghost is a question for a sharded scene that needs it: a sharded world refuses the calls, like the materials
 #define PHYS_NO_FIELDS_WHEN_SHARDED(w) \
     do { if ((w)->cfg.max_ghosts > 0) return fail(PHYS_ERR_UNSUPPORTED, "force fields are not supported in a world with max_ghosts > 0"); } while (0)

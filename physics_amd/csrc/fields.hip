@@ -1,10 +1,8 @@
 // fields.hip — force fields: volumes that add to the force / torque accumulators of the bodies whose
 // centre lies inside them. The writing twin of the trigger volumes (trigger.hip): evaluated by a kernel of their own in front
 // of every update, so no kernel of the step changes - the step kernels' FORCES instances read and zero what this one adds. A
-// world without fields launches nothing of this file.
+// world without fields launches nothing of this file. The records (ff_record) are built on the host (setup.hpp field_records).
 //
-//   k_field_build  one lane per field: its record {AABB, kind, shape, exponent, mask, centre, rotation matrix, half extent,
-//                  vec, coefs} from the staged set (phys_set_force_fields, or the set patched by new poses or params)
 //   k_field_apply  one lane per owned body, a loop over the fields: the records travel through LDS in tiles of 32 (every lane
 //                  reads the same record: a broadcast), a lane rejects by mask, then by its centre against the record's AABB,
 //                  then runs the exact point test and the law. A lane loads its accumulators when the first field acts on it
@@ -21,14 +19,7 @@ namespace {
 constexpr int kFfThreads = 256;
 constexpr uint32_t kFfTile = 32;  // fields per LDS tile
 static_assert(kFfTile * FF_REC_VEC <= (uint32_t)kFfThreads, "one 16-byte vector per thread stages a tile");
-static_assert(sizeof(ff_record) == 16 * FF_REC_VEC && sizeof(ff_staged) == 16 * FF_STAGE_VEC, "records are whole 16-byte vectors");
-
-__global__ __launch_bounds__(kFfThreads) void k_field_build(uint32_t T, const ff_staged* __restrict__ staged, ff_record* __restrict__ rec) {
-    const uint32_t k = blockIdx.x * kFfThreads + threadIdx.x;
-    if (k >= T) return;
-    const ff_staged s = staged[k];
-    rec[k] = ff_record_make(&s);
-}
+static_assert(sizeof(ff_record) == 16 * FF_REC_VEC, "records are whole 16-byte vectors");
 
 // MASKED: the set has masks - field k acts on body i only if (category[i] & mask[k]) != 0; without it no filter is loaded.
 // VEL: the set holds a DRAG field; without it the 32-byte velocity record is not loaded (need_mass: an ACCEL field wants the
@@ -61,26 +52,13 @@ __global__ __launch_bounds__(kFfThreads) void k_field_apply(uint32_t n, const fl
     const v3* acc_T = reinterpret_cast<const v3*>(torque) + (live ? i : 0u);
     for (uint32_t t0 = 0; t0 < T; t0 += kFfTile) {
         const uint32_t tn = min(kFfTile, T - t0);
-        __syncthreads();  // the previous tile has been read by everybody
-        if (threadIdx.x < tn * FF_REC_VEC)
-            reinterpret_cast<ff_f4*>(tile)[threadIdx.x] = reinterpret_cast<const ff_f4*>(rec + t0)[threadIdx.x];
-        __syncthreads();
+        tile_stage<FF_REC_VEC>(reinterpret_cast<vol_f4*>(tile), reinterpret_cast<const vol_f4*>(rec), t0, tn);
         if (live) ff_accumulate(tile, tn, &b, MASKED ? 1 : 0, acc_F, acc_T, &sum);
     }
     if (sum.acted) {
         st3(force, i, sum.F);
         st3(torque, i, sum.T);
     }
-}
-
-int32_t fields_upload_and_build(phys_world* w) {
-    const uint64_t n = w->n_fields;
-    PHYS_HIP_TRY(hipMemcpyAsync(w->ff_stage.p, w->ff_host.data(), sizeof(ff_staged) * n, hipMemcpyHostToDevice, w->stream));
-    hipLaunchKernelGGL(k_field_build, dim3((unsigned)((n + kFfThreads - 1) / kFfThreads)), dim3(kFfThreads), 0, w->stream, (uint32_t)n,
-                       reinterpret_cast<const ff_staged*>(w->ff_stage.p), reinterpret_cast<ff_record*>(w->ff_rec.p));
-    PHYS_HIP_TRY(hipGetLastError());
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // ff_host may change as soon as the call returns
-    return PHYS_OK;
 }
 
 }  // namespace
@@ -91,18 +69,17 @@ int32_t fields_set(phys_world* w, FieldStaging&& staged) {
     w->ff_masked = staged.masked; w->ff_drag = staged.drag; w->ff_accel = staged.accel;
     w->ff_host = std::move(staged.staged);
     if (n == 0) {  // back to launching nothing
-        w->ff_stage.free(); w->ff_rec.free();
+        w->ff_rec.free();
         return PHYS_OK;
     }
-    PHYS_HIP_TRY(w->ff_stage.resize(4 * FF_STAGE_VEC * (size_t)n));
-    PHYS_HIP_TRY(w->ff_rec.resize(4 * FF_REC_VEC * (size_t)n));
+    PHYS_TRY(upload_records(w, w->ff_rec, field_records(w->ff_host)));
     w->n_fields = n;
-    return fields_upload_and_build(w);
+    return PHYS_OK;
 }
 
 int32_t fields_rebuild(phys_world* w) {
     if (w->n_fields == 0) return PHYS_OK;
-    return fields_upload_and_build(w);  // on the world's stream: behind the updates already enqueued
+    return upload_records(w, w->ff_rec, field_records(w->ff_host));  // on the world's stream: behind the updates already enqueued
 }
 
 void launch_force_fields(phys_world* w) {

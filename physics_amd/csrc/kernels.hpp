@@ -306,12 +306,21 @@ void launch_events(phys_world* w, uint32_t step, uint32_t blocks /* plan_event_b
 int32_t events_alloc(phys_world* w);  // buffers for the current event and manifold capacities (frees them when events are off)
 int32_t events_reset(phys_world* w);  // forget the contact history and the pending events (a new body or static set)
 
+// Host-built records (setup.hpp trigger_records, field_records) to `dst`, on the world's stream - behind the updates already
+// enqueued - and waited for: the host vector may change as soon as the call returns.
+template <typename R>
+int32_t upload_records(phys_world* w, DevBuf<float>& dst, const std::vector<R>& rec) {
+    PHYS_HIP_TRY(dst.resize(sizeof(R) / sizeof(float) * rec.size()));
+    PHYS_HIP_TRY(hipMemcpyAsync(dst.p, rec.data(), sizeof(R) * rec.size(), hipMemcpyHostToDevice, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    return PHYS_OK;
+}
+
 // trigger volumes (trigger.hip): one kernel behind the position step of every update, only in a world with triggers
 void launch_triggers(phys_world* w, uint32_t step);
-// the trigger set from staged device arrays (arguments checked by the caller; n = 0 clears and frees); forgets the occupancy
-int32_t triggers_set(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot, const float* half_extent,
-                     const uint16_t* mask);
-int32_t triggers_set_poses(phys_world* w, const float* pos, const float* rot /* null: keep */);  // staged device arrays; keeps the occupancy
+// the set from its staged form (setup.hpp stage_triggers; arguments checked by the caller; empty: clears and frees); forgets the occupancy
+int32_t triggers_set(phys_world* w, TriggerStaging&& staged);
+int32_t triggers_rebuild(phys_world* w);  // w->tg_host was patched (poses): build the records again and send them; keeps the occupancy
 int32_t triggers_reset(phys_world* w);  // forget the occupancy and the pending events (a new trigger or body set)
 
 // force fields (fields.hip): one kernel in front of every update, only in a world with fields; it adds to the force / torque
@@ -319,7 +328,7 @@ int32_t triggers_reset(phys_world* w);  // forget the occupancy and the pending 
 void launch_force_fields(phys_world* w);
 // the set from its staged form (setup.hpp stage_fields; arguments checked by the caller; empty: clears and frees)
 int32_t fields_set(phys_world* w, FieldStaging&& staged);
-int32_t fields_rebuild(phys_world* w);  // w->ff_host was patched (poses, params): send it again and rebuild the records
+int32_t fields_rebuild(phys_world* w);  // w->ff_host was patched (poses, params): build the records again and send them
 
 // constraints.hip
 int32_t constraints_alloc(phys_world* w);

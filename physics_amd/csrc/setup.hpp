@@ -1,6 +1,6 @@
 // setup.hpp — what the host computes ONCE per body set, static set or constraint list, as pure functions of host arrays and a
 // few scalars: table sizes, capacities, cluster shapes and homes, the static colliders' grid, the staged body arrays, the
-// constraint column tables, the staged force fields, argument validation. Nothing of HIP in here and no phys_world: a host compiler reads it alone,
+// constraint column tables, the staged force fields and trigger volumes with their records, argument validation. Nothing of HIP in here and no phys_world: a host compiler reads it alone,
 // and tests/cpp/setup_probe.cpp holds every function to hand-worked values or a brute-force restatement
 // (tests/test_setup_cpu.py). The .hip files keep the allocations, the copies and the launches.
 #pragma once
@@ -320,6 +320,13 @@ struct StaticSet {
     std::vector<uint32_t> filt;   // 2 words per static: the default collision filter
     std::vector<float> mat;       // 2 floats per static: the default material {default_friction, 0}
 };
+// rot null: identity
+inline quat quat_at(const float* rot, uint64_t k) {
+    quat q;
+    if (rot) { q.i = rot[4 * k]; q.j = rot[4 * k + 1]; q.k = rot[4 * k + 2]; q.w = rot[4 * k + 3]; }
+    else { q.i = 0.0f; q.j = 0.0f; q.k = 0.0f; q.w = 1.0f; }
+    return q;
+}
 // n > 0 statics (arguments checked by shape_set_error); rot null: identity
 inline StaticSet build_static_set(uint64_t n, const float* pos, const float* rot, const uint32_t* shape, const float* he, float margin,
                                   float default_friction) {
@@ -328,9 +335,7 @@ inline StaticSet build_static_set(uint64_t n, const float* pos, const float* rot
     geo.assign(16 * n, 0.0f); rc.assign(12 * n, 0.0f); box.assign(8 * n, 0.0f);
     std::vector<float> lo(3 * n), hi(3 * n), edge(n);
     for (uint64_t k = 0; k < n; ++k) {
-        quat q;
-        if (rot) { q.i = rot[4 * k]; q.j = rot[4 * k + 1]; q.k = rot[4 * k + 2]; q.w = rot[4 * k + 3]; }
-        else { q.i = 0.0f; q.j = 0.0f; q.k = 0.0f; q.w = 1.0f; }
+        const quat q = quat_at(rot, k);
         const v3 c = v3_make(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]);
         const v3 h = v3_make(he[3 * k], he[3 * k + 1], he[3 * k + 2]);
         const uint32_t id = PHYS_STATIC_ID_BIT | (uint32_t)k;
@@ -608,7 +613,16 @@ inline const char* field_set_error(uint64_t n, const uint32_t* kind, const uint3
     return nullptr;
 }
 
-// The set as the device keeps it (include/spec/force_field.h ff_staged, 80 bytes per field) and what selects the evaluation's
+// the new poses of n staged volumes (phys_set_force_field_poses, phys_set_trigger_poses) are finite; rot null: not looked at
+inline bool poses_finite(size_t n, const float* pos, const float* rot) {
+    for (size_t k = 0; k < 3 * n; ++k)
+        if (!std::isfinite(pos[k])) return false;
+    for (size_t k = 0; rot && k < 4 * n; ++k)
+        if (!std::isfinite(rot[k])) return false;
+    return true;
+}
+
+// The set as the host keeps it (include/spec/force_field.h ff_staged, 80 bytes per field) and what selects the evaluation's
 // instance: a mask array was given; some field is a DRAG (the velocity record is read); some field is an ACCEL (the mass is).
 struct FieldStaging {
     std::vector<ff_staged> staged;
@@ -621,12 +635,10 @@ inline FieldStaging stage_fields(uint64_t n, const uint32_t* kind, const uint32_
     out.staged.resize(n);
     out.masked = n != 0 && mask != nullptr;
     for (uint64_t k = 0; k < n; ++k) {
-        quat q;
-        if (rot) { q.i = rot[4 * k]; q.j = rot[4 * k + 1]; q.k = rot[4 * k + 2]; q.w = rot[4 * k + 3]; }
-        else { q.i = 0.0f; q.j = 0.0f; q.k = 0.0f; q.w = 1.0f; }
-        out.staged[k] = ff_stage(kind[k], shape[k], mask ? (uint32_t)mask[k] : 0xFFFFu, exponent ? exponent[k] : 0u,
-                                 v3_make(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]), q, v3_make(he[3 * k], he[3 * k + 1], he[3 * k + 2]),
-                                 v3_make(vec[3 * k], vec[3 * k + 1], vec[3 * k + 2]), coef[2 * k], coef[2 * k + 1]);
+        out.staged[k] = ff_staged_make(kind[k], shape[k], mask ? (uint32_t)mask[k] : 0xFFFFu, exponent ? exponent[k] : 0u,
+                                       v3_make(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]), quat_at(rot, k),
+                                       v3_make(he[3 * k], he[3 * k + 1], he[3 * k + 2]), v3_make(vec[3 * k], vec[3 * k + 1], vec[3 * k + 2]),
+                                       coef[2 * k], coef[2 * k + 1]);
         if (kind[k] == PHYS_FIELD_DRAG) out.drag = true;
         if (kind[k] == PHYS_FIELD_ACCEL) out.accel = true;
     }
@@ -635,14 +647,10 @@ inline FieldStaging stage_fields(uint64_t n, const uint32_t* kind, const uint32_
 // phys_set_force_field_poses: new centres and, unless rot is null, rotations of the staged set; false: a non-finite value
 // (nothing changed then)
 inline bool restage_field_poses(std::vector<ff_staged>& staged, const float* pos, const float* rot) {
-    const size_t n = staged.size();
-    for (size_t k = 0; k < 3 * n; ++k)
-        if (!std::isfinite(pos[k])) return false;
-    for (size_t k = 0; rot && k < 4 * n; ++k)
-        if (!std::isfinite(rot[k])) return false;
-    for (size_t k = 0; k < n; ++k) {
-        staged[k].s[1] = ff_f4_make(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2], 0.0f);
-        if (rot) staged[k].s[2] = ff_f4_make(rot[4 * k], rot[4 * k + 1], rot[4 * k + 2], rot[4 * k + 3]);
+    if (!poses_finite(staged.size(), pos, rot)) return false;
+    for (size_t k = 0; k < staged.size(); ++k) {
+        staged[k].s[1] = vol_f4_make(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2], 0.0f);
+        if (rot) staged[k].s[2] = vol_f4_make(rot[4 * k], rot[4 * k + 1], rot[4 * k + 2], rot[4 * k + 3]);
     }
     return true;
 }
@@ -663,9 +671,44 @@ inline const char* restage_field_params(std::vector<ff_staged>& staged, const fl
     }
     for (size_t k = 0; k < n; ++k) {
         staged[k].s[3].w = coef[2 * k];
-        staged[k].s[4] = ff_f4_make(vec[3 * k], vec[3 * k + 1], vec[3 * k + 2], coef[2 * k + 1]);
+        staged[k].s[4] = vol_f4_make(vec[3 * k], vec[3 * k + 1], vec[3 * k + 2], coef[2 * k + 1]);
     }
     return nullptr;
+}
+
+// ---- trigger volumes: staged like the fields - the set as the host keeps it, its poses, its records ---
+struct TriggerVolume { uint32_t shape, mask; v3 c; quat q; v3 h; };
+struct TriggerStaging { std::vector<TriggerVolume> staged; bool masked = false; /* a mask array was given: the filtered instance */ };
+// n triggers (arguments checked by shape_set_error); rot null: identity, mask null: every body
+inline TriggerStaging stage_triggers(uint64_t n, const uint32_t* shape, const float* pos, const float* rot, const float* he,
+                                     const uint16_t* mask) {
+    TriggerStaging out;
+    out.staged.resize(n);
+    out.masked = n != 0 && mask != nullptr;
+    for (uint64_t k = 0; k < n; ++k)
+        out.staged[k] = {shape[k], mask ? (uint32_t)mask[k] : 0xFFFFu, v3_make(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]), quat_at(rot, k),
+                         v3_make(he[3 * k], he[3 * k + 1], he[3 * k + 2])};
+    return out;
+}
+// phys_set_trigger_poses: as restage_field_poses
+inline bool restage_trigger_poses(std::vector<TriggerVolume>& staged, const float* pos, const float* rot) {
+    if (!poses_finite(staged.size(), pos, rot)) return false;
+    for (size_t k = 0; k < staged.size(); ++k) {
+        staged[k].c = v3_make(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]);
+        if (rot) staged[k].q = quat_at(rot, k);
+    }
+    return true;
+}
+// the records the evaluations read (trigger.hip, fields.hip), built where the sets were checked
+inline std::vector<vol_record> trigger_records(const std::vector<TriggerVolume>& staged) {
+    std::vector<vol_record> rec(staged.size());
+    for (size_t k = 0; k < staged.size(); ++k) rec[k] = vol_record_make(staged[k].shape, staged[k].mask, staged[k].c, staged[k].q, staged[k].h);
+    return rec;
+}
+inline std::vector<ff_record> field_records(const std::vector<ff_staged>& staged) {
+    std::vector<ff_record> rec(staged.size());
+    for (size_t k = 0; k < staged.size(); ++k) rec[k] = ff_record_make(&staged[k]);
+    return rec;
 }
 
 }  // namespace phys

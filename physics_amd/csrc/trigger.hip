@@ -1,10 +1,8 @@
 // trigger.hip — trigger volumes: shapes that report which bodies are inside them and which
 // entered or left in an update. Not bodies, not statics: they are evaluated by a kernel of their own against the poses the
 // position step leaves, so nothing an update computes depends on them. A world without triggers launches nothing of
-// this file.
+// this file. The records (include/spec/volume.h vol_record) are built on the host (setup.hpp trigger_records) and copied here.
 //
-//   k_trigger_build  one lane per trigger: its record {AABB, shape, mask, centre, half extent, rotation matrix} from the
-//                    staged host arrays (phys_set_triggers) or from new poses (phys_set_trigger_poses)
 //   k_trigger_eval   one lane per owned body, a short loop over the triggers: the records travel through LDS in tiles of 32
 //                    (every lane reads the same record: a broadcast), a lane rejects by AABB and mask, runs the overlap
 //                    queries' exact test (shape_overlap.hpp: trigger = query, body = target), and builds its occupancy 32
@@ -30,47 +28,8 @@ namespace {
 constexpr int kTgThreads = 256;
 constexpr int kTgWaves = kTgThreads / 64;
 constexpr uint32_t kTgTile = 32;      // triggers per LDS tile = bits per occupancy word
-constexpr uint32_t kTgRecVec = 6;     // float4 per trigger record
-static_assert(kTgTile * kTgRecVec <= (uint32_t)kTgThreads, "one float4 per thread stages a tile");
-
-// type null: new poses for the records that are there (shape, half extent and mask stay); rot null: identity then, the
-// stored quaternion otherwise
-__global__ __launch_bounds__(kTgThreads) void k_trigger_build(uint32_t T, const uint32_t* __restrict__ type_in, const float* __restrict__ pos,
-                                                              const float* __restrict__ rot, const float* __restrict__ he,
-                                                              const uint16_t* __restrict__ mask, float4* __restrict__ rec,
-                                                              float4* __restrict__ rot_keep) {
-    const uint32_t k = blockIdx.x * kTgThreads + threadIdx.x;
-    if (k >= T) return;
-    float4* r = rec + kTgRecVec * (size_t)k;
-    uint32_t type, m;
-    v3 h;
-    float4 q4;
-    if (type_in) {
-        type = type_in[k];
-        h = ld3(he, k);
-        m = mask ? (uint32_t)mask[k] : 0xFFFFu;
-        q4 = rot ? reinterpret_cast<const float4*>(rot)[k] : make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-    } else {
-        type = __float_as_uint(r[0].w);
-        m = __float_as_uint(r[1].w);
-        h = v3_make(r[2].w, r[3].w, r[4].w);
-        q4 = rot ? reinterpret_cast<const float4*>(rot)[k] : rot_keep[k];
-    }
-    const v3 c = ld3(pos, k);
-    aabb_t b;
-    if (!rc_aabb_of(c, q4, h, type, &b)) {  // (finite inputs whose box is not: touches nothing)
-        b.lo = v3_make(3.0e38f, 3.0e38f, 3.0e38f);
-        b.hi = v3_make(-3.0e38f, -3.0e38f, -3.0e38f);
-    }
-    const QShape Q = qs_make(type, c, q4, h);
-    rot_keep[k] = q4;
-    r[0] = make_float4(b.lo.x, b.lo.y, b.lo.z, __uint_as_float(type));
-    r[1] = make_float4(b.hi.x, b.hi.y, b.hi.z, __uint_as_float(m));
-    r[2] = make_float4(c.x, c.y, c.z, h.x);
-    r[3] = make_float4(Q.R.m[0], Q.R.m[1], Q.R.m[2], h.y);
-    r[4] = make_float4(Q.R.m[3], Q.R.m[4], Q.R.m[5], h.z);
-    r[5] = make_float4(Q.R.m[6], Q.R.m[7], Q.R.m[8], 0.0f);
-}
+static_assert(kTgTile * VOL_REC_VEC <= (uint32_t)kTgThreads, "one 16-byte vector per thread stages a tile");
+static_assert(sizeof(vol_record) == 16 * VOL_REC_VEC, "records are whole 16-byte vectors");
 
 // MASKED: the trigger set has masks - body i is seen by trigger k iff (category[i] & mask[k]) != 0; without it no filter is
 // loaded. EVENTS: trigger events are on (the occupancy is kept either way).
@@ -81,7 +40,7 @@ __global__ __launch_bounds__(kTgThreads) void k_trigger_eval(uint32_t n, const f
                                                              uint32_t* __restrict__ bits, uint32_t step,
                                                              unsigned long long* __restrict__ cursor, uint4* __restrict__ ev_buf,
                                                              uint64_t capacity) {
-    __shared__ float4 tile[kTgTile * kTgRecVec];
+    __shared__ vol_f4 tile[kTgTile * VOL_REC_VEC];
     __shared__ SlotAppend<kTgWaves> sh;
     const uint32_t i = blockIdx.x * kTgThreads + threadIdx.x;
     const bool live = i < n;  // (no early return: the tiles and the reservation have barriers)
@@ -106,25 +65,21 @@ __global__ __launch_bounds__(kTgThreads) void k_trigger_eval(uint32_t n, const f
     for (uint32_t wd = 0; wd < words; ++wd) {
         const uint32_t t0 = wd * kTgTile;
         const uint32_t tn = min(kTgTile, T - t0);
-        __syncthreads();  // the previous tile has been read by everybody
-        if (threadIdx.x < tn * kTgRecVec) tile[threadIdx.x] = rec[kTgRecVec * (size_t)t0 + threadIdx.x];
-        __syncthreads();
+        tile_stage<VOL_REC_VEC>(tile, reinterpret_cast<const vol_f4*>(rec), t0, tn);
         uint32_t now = 0;
         if (shaped) {
 #pragma unroll 1
             for (uint32_t k = 0; k < tn; ++k) {
-                const float4 a0 = tile[kTgRecVec * k], a1 = tile[kTgRecVec * k + 1];
-                if (MASKED && (category & __float_as_uint(a1.w)) == 0u) continue;
-                if (!(a0.x <= ba.hi.x && ba.lo.x <= a1.x && a0.y <= ba.hi.y && ba.lo.y <= a1.y && a0.z <= ba.hi.z && ba.lo.z <= a1.z)) continue;
-                const float4 r2 = tile[kTgRecVec * k + 2], r3 = tile[kTgRecVec * k + 3], r4 = tile[kTgRecVec * k + 4],
-                             r5 = tile[kTgRecVec * k + 5];
+                const vol_f4 a0 = tile[VOL_REC_VEC * k], a1 = tile[VOL_REC_VEC * k + 1];
+                if (MASKED && (category & vol_mask(a1)) == 0u) continue;
+                if (!vol_box_meets(a0, a1, ba.lo, ba.hi)) continue;
+                const vol_f4 r2 = tile[VOL_REC_VEC * k + 2], r3 = tile[VOL_REC_VEC * k + 3], r4 = tile[VOL_REC_VEC * k + 4],
+                             r5 = tile[VOL_REC_VEC * k + 5];
                 QShape Q;
-                Q.type = __float_as_uint(a0.w);
-                Q.c = v3_make(r2.x, r2.y, r2.z);
-                Q.h = v3_make(r2.w, r3.w, r4.w);
-                Q.R.m[0] = r3.x; Q.R.m[1] = r3.y; Q.R.m[2] = r3.z;
-                Q.R.m[3] = r4.x; Q.R.m[4] = r4.y; Q.R.m[5] = r4.z;
-                Q.R.m[6] = r5.x; Q.R.m[7] = r5.y; Q.R.m[8] = r5.z;
+                Q.type = vol_word(a0);
+                Q.c = vol_centre(r2);
+                Q.h = vol_half_extent(r2, r3, r4);
+                Q.R = vol_rotation(r3, r4, r5);
                 if (qr_overlap(Q, B)) now |= 1u << k;
             }
         }
@@ -146,14 +101,6 @@ __global__ __launch_bounds__(kTgThreads) void k_trigger_eval(uint32_t n, const f
     }
 }
 
-void triggers_free(phys_world* w) {
-    w->n_triggers = 0;
-    w->tg_masked = false;
-    w->tg_rec.free(); w->tg_rot.free(); w->tg_bits.free();
-    w->tg_bits_bodies = 0;
-    if (w->tg_capacity == 0) w->tg_cursor.free();
-}
-
 }  // namespace
 
 // an empty occupancy for the world's current trigger and body counts, and no pending events
@@ -167,32 +114,27 @@ int32_t triggers_reset(phys_world* w) {
     return PHYS_OK;
 }
 
-int32_t triggers_set(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot, const float* half_extent,
-                     const uint16_t* mask) {
+int32_t triggers_set(phys_world* w, TriggerStaging&& staged) {
+    const uint64_t n = staged.staged.size();
+    if (n != w->n_triggers) w->tg_bits.free();  // another word count: another layout
+    w->n_triggers = 0;  // (a failure below leaves a world without triggers, not half a set)
+    w->tg_masked = staged.masked;
+    w->tg_host = std::move(staged.staged);
     if (n == 0) {  // back to launching nothing
-        triggers_free(w);
+        w->tg_rec.free();
+        w->tg_bits_bodies = 0;
+        if (w->tg_capacity == 0) w->tg_cursor.free();
         return triggers_reset(w);
     }
-    PHYS_HIP_TRY(w->tg_rec.resize(4 * kTgRecVec * (size_t)n));
-    PHYS_HIP_TRY(w->tg_rot.resize(4 * (size_t)n));
     PHYS_HIP_TRY(w->tg_cursor.resize(1));
-    if (n != w->n_triggers) w->tg_bits.free();  // another word count: another layout
+    PHYS_TRY(upload_records(w, w->tg_rec, trigger_records(w->tg_host)));
     w->n_triggers = n;
-    w->tg_masked = mask != nullptr;
-    hipLaunchKernelGGL(k_trigger_build, dim3((unsigned)((n + kTgThreads - 1) / kTgThreads)), dim3(kTgThreads), 0, w->stream, (uint32_t)n,
-                       shape_type, pos, rot, half_extent, mask, reinterpret_cast<float4*>(w->tg_rec.p), reinterpret_cast<float4*>(w->tg_rot.p));
-    PHYS_HIP_TRY(hipGetLastError());
     return triggers_reset(w);
 }
 
-int32_t triggers_set_poses(phys_world* w, const float* pos, const float* rot) {
-    const uint64_t n = w->n_triggers;
-    if (n == 0) return PHYS_OK;
-    hipLaunchKernelGGL(k_trigger_build, dim3((unsigned)((n + kTgThreads - 1) / kTgThreads)), dim3(kTgThreads), 0, w->stream, (uint32_t)n,
-                       (const uint32_t*)nullptr, pos, rot, (const float*)nullptr, (const uint16_t*)nullptr,
-                       reinterpret_cast<float4*>(w->tg_rec.p), reinterpret_cast<float4*>(w->tg_rot.p));
-    PHYS_HIP_TRY(hipGetLastError());
-    return PHYS_OK;
+int32_t triggers_rebuild(phys_world* w) {
+    if (w->n_triggers == 0) return PHYS_OK;
+    return upload_records(w, w->tg_rec, trigger_records(w->tg_host));  // on the world's stream: behind the updates already enqueued
 }
 
 // `step`: phys_stats.steps after this update (low 32 bits)

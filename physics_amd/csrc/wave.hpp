@@ -98,6 +98,17 @@ __device__ __forceinline__ uint32_t block_scan_in_place(uint32_t* __restrict__ p
     return carry;
 }
 
+// ---- a tile of records through LDS ---------------------------------------------------------------------------------------
+// Records [t0, t0 + tn) of VEC 16-byte vectors each (V: the vector type) from `rec` into `tile`, one vector per thread - the
+// caller asserts that a whole tile is no more than that -, a barrier in front (the previous tile has been read by everybody)
+// and one behind. Every thread of the workgroup calls it.
+template <uint32_t VEC, class V>
+__device__ __forceinline__ void tile_stage(V* tile, const V* __restrict__ rec, uint32_t t0, uint32_t tn) {
+    __syncthreads();
+    if (threadIdx.x < tn * VEC) tile[threadIdx.x] = rec[VEC * (size_t)t0 + threadIdx.x];
+    __syncthreads();
+}
+
 // ---- slots of an append-only buffer, reserved once per workgroup and trip ------------------------------------------------
 // LDS of one reservation; the per-wave totals alternate between two sets, so that a wave which runs ahead into the
 // next trip does not overwrite totals a slower wave still adds up

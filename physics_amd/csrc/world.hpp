@@ -296,8 +296,8 @@ struct phys_world {
     // trigger volumes (trigger.hip): nothing below is allocated, and nothing launched, without triggers
     uint64_t n_triggers = 0;
     bool tg_masked = false;              // phys_set_triggers was given a mask array: the evaluation's filtered instance
-    phys::DevBuf<float> tg_rec;          // 24 floats per trigger: {AABB lo, shape} {AABB hi, mask} {centre, h.x} 3 x {matrix row, h.y | h.z | -}
-    phys::DevBuf<float> tg_rot;          // 4 per trigger: its quaternion (phys_set_trigger_poses with rot NULL keeps it)
+    std::vector<phys::TriggerVolume> tg_host;  // the set as staged (setup.hpp stage_triggers): poses are patched here, the records built from it
+    phys::DevBuf<float> tg_rec;          // 24 floats per trigger: the record the evaluation reads (include/spec/volume.h vol_record)
     phys::DevBuf<uint32_t> tg_bits;      // occupancy, plane-major: word (k / 32) of body i at [(k / 32) * n_owned + i], bit k % 32
     uint64_t tg_bits_bodies = 0;         // the n_owned tg_bits was laid out for
     uint64_t tg_capacity = 0;            // trigger events the device keeps between two drains (0: off)
@@ -307,8 +307,7 @@ struct phys_world {
     uint64_t n_fields = 0;
     bool ff_masked = false;              // phys_set_force_fields was given a mask array: the evaluation's filtered instance
     bool ff_drag = false, ff_accel = false;  // some field is a DRAG (the velocity record is read) / an ACCEL (the mass is)
-    std::vector<ff_staged> ff_host;      // the set as staged (setup.hpp stage_fields): poses and params are patched here, then sent again
-    phys::DevBuf<float> ff_stage;        // 20 floats per field: the device copy of ff_host
+    std::vector<ff_staged> ff_host;      // the set as staged (setup.hpp stage_fields): poses and params are patched here, the records built from it
     phys::DevBuf<float> ff_rec;          // 28 floats per field: the record the evaluation reads (include/spec/force_field.h ff_record)
     // multi-GPU halo
     phys::DevBuf<uint32_t> cross_pairs;

@@ -3,7 +3,9 @@
 // come from: worked out BY HAND from the functions' text as it stood inside the .hip files before the
 // headers existed (grid_plan, collision_alloc, cluster_assign, cluster_plan_dynamic, phys_set_bodies, constraints_alloc, the
 // validation loops, the read-outs, phys_sync) - or, for the static colliders' grid, from a BRUTE-FORCE restatement in this
-// file (every static against every query box). Never from running the functions and pasting what they gave.
+// file (every static against every query box) - or, for the volume records (include/spec/volume.h), bit by bit from the float32
+// arithmetic of body_aabb and quat_to_m33, the derivation written next to the case. Never from running the functions and
+// pasting what they gave.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -604,6 +606,120 @@ static void validation() {
     }
 }
 
+// ---- volumes: include/spec/volume.h vol_record_make, stage_triggers, restage_trigger_poses, trigger_records, field_records ------
+// The rotation used below is 90 degrees about z: q = (0, 0, s, s) with s = float(sqrt(1/2)) = 0x3F3504F3 = 11863283 * 2^-24.
+// quat_to_m33 by hand: s * s = 140737483538089 * 2^-48 = 1/2 - 0.574 * 2^-25, which rounds to a = 1/2 - 2^-25 (0x3EFFFFFF), so
+// ww = kk = a and ii = jj = 0; wk = (s * s) * 2 = b = 1 - 2^-24 (0x3F7FFFFF), every other product is +0. The matrix:
+//   m0 = (a + 0 - 0) - a = +0   m1 = 0 - b = -b   m2 = 0      m3 = b + 0 = b   m4 = (a - 0 + 0) - a = +0   m5 = 0
+//   m6 = 0   m7 = 0   m8 = (a - 0 - 0) + a = b
+static void check_words(const char* what, const void* got, std::initializer_list<uint32_t> want) {
+    std::vector<uint32_t> g(want.size());
+    std::memcpy(g.data(), got, 4 * want.size());
+    size_t k = 0;
+    for (uint32_t w : want) {
+        ++g_checks;
+        if (g[k] != w) { std::printf("MISMATCH %s: word %zu = %08x, expected %08x\n", what, k, g[k], w); std::exit(1); }
+        ++k;
+    }
+}
+static void volumes() {
+    const uint32_t one = 0x3F800000u, m_one = 0xBF800000u, b = 0x3F7FFFFFu, m_b = 0xBF7FFFFFu, s = 0x3F3504F3u;
+    const float sf = vol_u2f(s), nan = std::numeric_limits<float>::quiet_NaN();
+    CHECK("sizes", sizeof(vol_record), 96); CHECK("sizes", sizeof(ff_record), 112); CHECK("sizes", sizeof(vol_f4), 16);
+    {   // a unit sphere at the origin, rot NULL and mask NULL: box -+1 (e = (1, 1, 1); (0 - 1) - 0, (0 + 1) + 0), the identity matrix
+        // (ww = 1, every other term +0), mask 0xFFFF
+        const uint32_t shape[1] = {PHYS_SHAPE_SPHERE};
+        const float pos[3] = {0.0f, 0.0f, 0.0f}, he[3] = {1.0f, 0.0f, 0.0f};
+        const TriggerStaging st = stage_triggers(1, shape, pos, nullptr, he, nullptr);
+        CHECK("sphere", st.masked, false); CHECK("sphere", st.staged.size(), 1);
+        CHECK("sphere", st.staged[0].q.i == 0.0f && st.staged[0].q.j == 0.0f && st.staged[0].q.k == 0.0f && st.staged[0].q.w == 1.0f, true);
+        const std::vector<vol_record> rec = trigger_records(st.staged);
+        CHECK("sphere", rec.size(), 1);
+        check_words("sphere", rec.data(), {m_one, m_one, m_one, 1u, /**/ one, one, one, 0xFFFFu, /**/ 0, 0, 0, one,
+                                           /**/ one, 0, 0, 0, /**/ 0, one, 0, 0, /**/ 0, 0, one, 0});
+        CHECK("accessors", vol_word(rec[0].r[0]), PHYS_SHAPE_SPHERE); CHECK("accessors", vol_mask(rec[0].r[1]), 0xFFFFu);
+        CHECK("accessors", vol_lo(rec[0].r[0]).y == -1.0f && vol_hi(rec[0].r[1]).z == 1.0f, true);
+        CHECK("accessors", vol_half_extent(rec[0].r[2], rec[0].r[3], rec[0].r[4]).x == 1.0f, true);
+        CHECK("accessors", vol_rotation(rec[0].r[3], rec[0].r[4], rec[0].r[5]).m[4] == 1.0f, true);
+        const v3 in = v3_make(1.0f, -1.0f, 0.0f), out = v3_make(0.0f, 1.5f, 0.0f), bad = v3_make(nan, 0.0f, 0.0f);
+        CHECK("box", vol_box_meets(rec[0].r[0], rec[0].r[1], in, in), 1); CHECK("box", vol_box_meets(rec[0].r[0], rec[0].r[1], out, out), 0);
+        CHECK("box", vol_box_meets(rec[0].r[0], rec[0].r[1], bad, bad), 0); CHECK("box", vol_box_meets(rec[0].r[0], rec[0].r[1], in, out), 1);
+        CHECK("none", stage_triggers(0, nullptr, nullptr, nullptr, nullptr, nullptr).masked, false);
+    }
+    // three triggers with rotations and masks: a sphere, a box (1, 2, 3) at the origin and a capsule (r 0.5, hl 1) at (10, 20, 30),
+    // the last two turned 90 degrees about z.
+    //   box: e.x = (0 * 1 + b * 2) + 0 * 3 = 2 - 2^-23 (0x3FFFFFFF), e.y = (b * 1 + 0) + 0 = b, e.z = (0 + 0) + b * 3 = 3 - 0.75 * 2^-22,
+    //        which rounds to 3 - 2^-22 (0x403FFFFF); lo = (0 - e) - 0 = -e, hi = e: +-(2, 1, 3) to the rounding of the matrix
+    //   capsule: e.x = b * 1 + 0.5 = 1.5 - 2^-24, a tie that rounds to the even 1.5; e.y = e.z = 0 * 1 + 0.5: lo = (8.5, 19.5, 29.5),
+    //        hi = (11.5, 20.5, 30.5), all exact
+    const uint32_t shape[3] = {PHYS_SHAPE_SPHERE, PHYS_SHAPE_BOX, PHYS_SHAPE_CAPSULE};
+    const float pos[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 10.0f, 20.0f, 30.0f};
+    const float rot[12] = {0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, sf, sf, 0.0f, 0.0f, sf, sf};
+    const float he[9] = {1.0f, 0.0f, 0.0f, 1.0f, 2.0f, 3.0f, 0.5f, 1.0f, 0.0f};
+    const uint16_t mask[3] = {1, 0x00F0, 0x8000};
+    TriggerStaging st = stage_triggers(3, shape, pos, rot, he, mask);
+    CHECK("three", st.masked, true);
+    std::vector<vol_record> rec = trigger_records(st.staged);
+    check_words("three: sphere", &rec[0], {m_one, m_one, m_one, 1u, one, one, one, 1u, 0, 0, 0, one, one, 0, 0, 0, 0, one, 0, 0, 0, 0, one, 0});
+    check_words("three: box", &rec[1], {0xBFFFFFFFu, m_b, 0xC03FFFFFu, 2u, /**/ 0x3FFFFFFFu, b, 0x403FFFFFu, 0x00F0u, /**/ 0, 0, 0, one,
+                                        /**/ 0, m_b, 0, 0x40000000u, /**/ b, 0, 0, 0x40400000u, /**/ 0, 0, b, 0});
+    check_words("three: capsule", &rec[2], {0x41080000u, 0x419C0000u, 0x41EC0000u, 3u, /**/ 0x41380000u, 0x41A40000u, 0x41F40000u, 0x8000u,
+                                            /**/ 0x41200000u, 0x41A00000u, 0x41F00000u, 0x3F000000u, /**/ 0, m_b, 0, one, /**/ b, 0, 0, 0,
+                                            /**/ 0, 0, b, 0});
+    {   // new poses with rot NULL: the stored quaternions stay, and so do rows 3 to 5; the centres and the boxes move (the capsule
+        // to the origin: lo = (-1.5, -0.5, -0.5), hi = (1.5, 0.5, 0.5))
+        const float pos2[9] = {4.0f, 0.0f, 0.0f, 0.0f, 8.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        CHECK("poses", restage_trigger_poses(st.staged, pos2, nullptr), true);
+        const std::vector<vol_record> moved = trigger_records(st.staged);
+        for (int k = 0; k < 3; ++k) CHECK("poses: rows 3 to 5", std::memcmp(&moved[k].r[3], &rec[k].r[3], 48), 0);
+        CHECK("poses", st.staged[1].q.k == sf && st.staged[1].q.w == sf && st.staged[1].c.y == 8.0f, true);
+        check_words("poses: capsule", &moved[2], {0xBFC00000u, 0xBF000000u, 0xBF000000u, 3u, 0x3FC00000u, 0x3F000000u, 0x3F000000u, 0x8000u, 0, 0, 0, 0x3F000000u});
+        check_words("poses: sphere", &moved[0], {0x40400000u, m_one, m_one, 1u, 0x40A00000u, one, one, 1u, 0x40800000u, 0, 0, one});  // 3, 5 | 4
+        // a NaN in pos, or in rot, is refused and the set is what it was
+        float pos3[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, rot3[12] = {0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+        pos3[4] = nan;
+        CHECK("poses: NaN", restage_trigger_poses(st.staged, pos3, rot3), false);
+        pos3[4] = 0.0f; rot3[11] = std::numeric_limits<float>::infinity();
+        CHECK("poses: inf in rot", restage_trigger_poses(st.staged, pos3, rot3), false);
+        const std::vector<vol_record> after = trigger_records(st.staged);
+        CHECK("poses: refused, unchanged", std::memcmp(after.data(), moved.data(), 3 * sizeof(vol_record)), 0);
+        rot3[11] = 1.0f;  // identity rotations: the box's matrix is the identity now, its box (1, 2, 3) about the origin
+        CHECK("poses: rot", restage_trigger_poses(st.staged, pos3, rot3), true);
+        const std::vector<vol_record> turned = trigger_records(st.staged);
+        check_words("poses: box", &turned[1], {m_one, 0xC0000000u, 0xC0400000u, 2u, one, 0x40000000u, 0x40400000u, 0x00F0u, 0, 0, 0, one,
+                                               one, 0, 0, 0x40000000u, 0, one, 0, 0x40400000u, 0, 0, one, 0});
+    }
+    {   // a finite volume whose box is not: pos 3e38, half extent 3e38 - hi = 3e38 + 3e38 = +inf, the sum of the six is +inf: the
+        // inverted box. And a field of the same volume: ff_record_make's first six vectors are vol_record_make's but for the two
+        // words the field packs for itself; the same for the turned box above
+        const uint32_t big = vol_f2u(3.0e38f), m_big = vol_f2u(-3.0e38f);
+        CHECK("3e38", big, 0x7F61B1E6u);  // 3e38 / 2^127 = 1.7632415: mantissa 0.7632415 * 2^23 = 6402534 = 0x61B1E6
+        const uint32_t shape1[2] = {PHYS_SHAPE_BOX, PHYS_SHAPE_BOX};
+        const float pos1[6] = {3.0e38f, 3.0e38f, 3.0e38f, 0.0f, 0.0f, 0.0f}, he1[6] = {3.0e38f, 3.0e38f, 3.0e38f, 1.0f, 2.0f, 3.0f};
+        const float rot1[8] = {0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, sf, sf};
+        const std::vector<vol_record> v = trigger_records(stage_triggers(2, shape1, pos1, rot1, he1, nullptr).staged);
+        check_words("overflow", &v[0], {big, big, big, 2u, m_big, m_big, m_big, 0xFFFFu, big, big, big, big, one, 0, 0, big, 0, one, 0, big, 0, 0, one, 0});
+        CHECK("overflow", vol_box_meets(v[0].r[0], v[0].r[1], v3_make(3.0e38f, 3.0e38f, 3.0e38f), v3_make(3.0e38f, 3.0e38f, 3.0e38f)), 0);
+        CHECK("turned box", std::memcmp(&v[1], &rec[1], 28) == 0 && std::memcmp(&v[1].r[2], &rec[1].r[2], 64) == 0, true);  // (the masks differ)
+        const uint32_t kind[2] = {PHYS_FIELD_DRAG, PHYS_FIELD_RADIAL}, ex[2] = {0, 2};
+        const float vec[6] = {1.0f, 2.0f, 3.0f, 0.0f, 0.0f, 0.0f}, coef[4] = {0.25f, 0.5f, -4.0f, 1.5f};
+        const uint16_t fmask[2] = {0x0F0F, 3};
+        const FieldStaging fs = stage_fields(2, kind, shape1, pos1, rot1, he1, fmask, vec, coef, ex);
+        const std::vector<ff_record> f = field_records(fs.staged);
+        CHECK("fields", f.size(), 2);
+        for (int k = 0; k < 2; ++k) {
+            uint32_t fw[28], vw[24];
+            std::memcpy(fw, &f[k], 112); std::memcpy(vw, &v[k], 96);
+            for (int i = 0; i < 24; ++i)
+                if (i != 3 && i != 7 && i != 23) CHECK("field = volume", fw[i], vw[i]);
+            CHECK("field: mask", fw[7], fmask[k]);
+            CHECK("field: word", fw[3], kind[k] | (PHYS_SHAPE_BOX << 8) | (ex[k] << 16));
+            CHECK("field: coef 0", fw[23], vol_f2u(coef[2 * k])); CHECK("field: coef 1", fw[27], vol_f2u(coef[2 * k + 1]));
+            CHECK("field: vec", std::memcmp(&fw[24], &vec[3 * k], 12), 0);
+        }
+    }
+}
+
 // ---- readout.hpp -------------------------------------------------------------------------------------------------------------
 static void readout() {
     {
@@ -728,6 +844,7 @@ int main() {
     bodies();
     constraints();
     validation();
+    volumes();
     readout();
     std::printf("setup_probe: %d checks passed\n", g_checks);
     return 0;

@@ -3,8 +3,8 @@ reference of tests/trigger_ref.py, against phys_overlap, and against themselves.
 
 Hand scenes; the random soup per update; occupancy-word and tail boundaries (33 and 70 triggers, 193 bodies, a list longer
 than a wave); batches and a full event buffer; updates bit-identical with and without triggers; masks and filters; the
-history rules of phys_set_triggers / phys_set_bodies / phys_set_trigger_poses; ghost slots; argument errors and the capacity
-protocol of both getters."""
+history rules of phys_set_triggers / phys_set_bodies / phys_set_trigger_poses, kept rotations; ghost slots; argument errors
+and the capacity protocol of both getters."""
 import ctypes as C
 
 import numpy as np
@@ -316,6 +316,35 @@ def test_history_moves_resets_and_clearing():
     assert steps == 4 and after == {k: (after[k][0], v[1]) for k, v in base.items()}
     off, ids = w.get_trigger_overlaps()
     assert list(off) == [0] and len(ids) == 0 and len(w.get_trigger_events()[0]) == 0
+    w.close()
+
+
+def test_poses_without_rotations_keep_the_rotations_of_set_triggers():
+    """The quaternions phys_set_triggers was given live on the host; phys_set_trigger_poses(rot = NULL) builds the records from
+    them again. Two volumes that are not rotation-symmetric - a box (2, 0.5, 0.5) turned 45 degrees about z, a capsule (r 0.3,
+    hl 1.5) turned 90 degrees about z, its axis along x then - and four small spheres at rest: one in each volume's turned tip,
+    0.5 and 1.1 clear of the volume as the identity rotation would leave it, and one at each centre."""
+    pa = _pa()
+    w = pa.World(pa.default_config(flags=0, gravity_force=(0.0, 0.0, 0.0)))
+    d = 1.6 * np.sqrt(0.5)
+    pos = np.array([[d, d, 0], [0, 0, 0], [11.5, 0, 0], [10, 0, 0]], np.float32)
+    w.set_bodies(pos, shape_type=np.full(4, pa.SHAPE_SPHERE, np.uint32), half_extent=np.full((4, 3), 0.1, np.float32))
+    tpos = np.array([[0, 0, 0], [10, 0, 0]], np.float32)
+    rot = np.array([[0, 0, 0.38268343, 0.92387953], [0, 0, 0.70710678, 0.70710678]], np.float32)
+    w.set_triggers(np.array([pa.SHAPE_BOX, pa.SHAPE_CAPSULE], np.uint32), tpos, rot=rot,
+                   half_extent=np.array([[2, 0.5, 0.5], [0.3, 1.5, 0]], np.float32))
+    w.enable_trigger_events(64)
+    w.update(DT)
+    everybody = {(0, 0), (0, 1), (1, 2), (1, 3)}
+    assert _gpu_pairs(w) == everybody
+    assert _event_list(w.get_trigger_events()[0]) == tr.events(set(), everybody)
+    w.set_trigger_poses(tpos, rot=None)
+    w.update(DT)
+    assert _gpu_pairs(w) == everybody and len(w.get_trigger_events()[0]) == 0
+    w.set_trigger_poses(tpos, rot=[[0, 0, 0, 1], [0, 0, 0, 1]])
+    w.update(DT)
+    assert _gpu_pairs(w) == {(0, 1), (1, 3)}
+    assert sorted(_event_list(w.get_trigger_events()[0])) == [(pa.TRIGGER_EXIT, 0, 0), (pa.TRIGGER_EXIT, 1, 2)]
     w.close()
 
 

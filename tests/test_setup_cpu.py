@@ -1,6 +1,7 @@
 """World set-up and read-out arithmetic (physics_amd/csrc/setup.hpp, readout.hpp) without a GPU: both headers compile with a
 host compiler alone, and tests/cpp/setup_probe.cpp holds every function to values worked out by hand from the code the headers
-replaced, or to a brute-force restatement. The validation messages are also reached through the
+replaced, to a brute-force restatement, or - the volume records of include/spec/volume.h - to bits derived by hand (DESIGN.md
+sections 17 and 20). The validation messages are also reached through the
 library: phys_set_static_bodies and phys_set_triggers check their arguments before they look at the world."""
 import ctypes as C
 import os
