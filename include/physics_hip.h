@@ -239,10 +239,16 @@ int32_t phys_get_color_counts(phys_world* w, uint32_t* counts_out /*64*/);
  *   - no bodies: every ray misses or hits the ground. n_rays == 0 is a no-op.
  *   - PHYS_ERR_INVALID_ARG: a NULL origin, dir, body_out or t_out, or n_rays >= 2^31.
  * Grid: e = the largest exact AABB edge of the bodies above, M = the largest |coordinate| of
- * their bounds [lo, hi], pad p = 2^-16 (M + e), cell edge (e + 2p)(1 + 2^-10) - coarser if the padded bounds would span
- * more than 2^20 cells along an axis - with cell corners at lo - p + k * cell. The cell edge follows the largest body:
- * one huge body coarsens the grid, and far-flung bodies mean long walks through empty cells. Results stay correct in
- * both cases; only speed suffers. */
+ * their bounds [lo, hi], pad p = 2^-16 (M + e), cell edge (e + 2p)(1 + 2^-10), with cell corners at lo - p + k * cell.
+ * The pad bounds the grid: the cell is at least 2p >= 2^-15 M and the padded bounds span at most 2M + 2p, so there are
+ * never more than 65 474 cells along an axis (the kernels' clamp to 2^20 cells is a guard that no input reaches). The
+ * cell edge follows the largest body: one huge body coarsens the grid, and far-flung bodies mean long walks through
+ * empty cells. Results stay correct in both cases; only speed suffers.
+ * Accuracy: every candidate is tested in coordinates relative to its own centre c, so the distance of the scene from
+ * the origin costs nothing: t is good to about 1e-5 (1 + |origin - c| + t) and normals to 1e-4, at 2e5 from the origin as
+ * near it. What float32 cannot give is a hit point finer than 2^-23 (|origin - c| + t): a ray that travels 3e6 finds the
+ * right target and t within 0.25, and the face of a box it enters square on, but no meaningful normal on a sphere, a
+ * capsule or near a box's edge once that distance reaches the size of the target. */
 #define PHYS_RAY_MISS 0xFFFFFFFEu   /* no hit within max_t */
 #define PHYS_RAY_GROUND 0xFFFFFFFFu /* the ground plane (same id the manifolds use for it) */
 /* host arrays; synchronous (returns with the outputs written) */

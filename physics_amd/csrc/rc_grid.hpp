@@ -59,7 +59,7 @@ __device__ __forceinline__ RcGrid rc_grid(const RcHeader* __restrict__ h) {
     const float sx = (hx + g.pad) - g.lox, sy = (hy + g.pad) - g.loy, sz = (hz + g.pad) - g.loz;
     float cell = (e + 2.0f * g.pad) * (1.0f + 0x1p-10f);
     const float span = fmaxf(sx, fmaxf(sy, sz));
-    if (span * 0x1p-20f > cell) cell = span * 0x1p-20f;  // at most 2^20 cells per axis (far-flung scenes: coarser cells)
+    if (span * 0x1p-20f > cell) cell = span * 0x1p-20f;  // a guard: cell >= 2 pad >= 2^-15 m already keeps an axis below 65 474 cells
     g.cell = fmaxf(cell, 1.0e-30f);
     g.inv = 1.0f / g.cell;
     g.nx = g.valid ? rc_dim(sx, g.inv) : 1;
@@ -172,7 +172,12 @@ __device__ __forceinline__ bool ray_capsule(float px, float py, float pz, float 
     const float B = (ax * bx + ay * by) + az * bz;
     const float C = ((bx * bx + by * by) + bz * bz) - rr;
     if (A > 1.0e-12f && B < 0.0f) {
-        const float disc = B * B - A * C;
+        // B^2 - A C = A (r^2 - |l|^2), l = b - (B / A) a the part of b across the ray: as in ray_ball, the distance of the
+        // line from the axis without cancellation (B^2 and A C are both |p|^2-sized: from 200 away their difference had
+        // lost all but two digits of a radius of 0.5)
+        const float s = B / A;
+        const float lx = bx - s * ax, ly = by - s * ay, lz = bz - s * az;
+        const float disc = A * (rr - ((lx * lx + ly * ly) + lz * lz));
         if (disc >= 0.0f) {
             const float q = -B + sqrtf(disc);  // > 0; the near root is C / q (no cancellation)
             const float tc = C / q;

@@ -155,7 +155,9 @@ __device__ __forceinline__ bool qr_overlap(const QShape& Q, const QShape& T) {
         qs_core(Q, &wq, &hq, &rq);
         qs_core(T, &wt, &ht, &rt);
         const float rr = rq + rt;
-        return qr_seg_seg_d2(Q.c, wq, hq, T.c, wt, ht) <= rr * rr;
+        // relative to the target's centre, like the two box tests: the end points c +- hl w rounded to the ulp of world
+        // coordinates (1/64 at 2e5 from the origin) would cost the distance its digits
+        return qr_seg_seg_d2(v3_sub(Q.c, T.c), wq, hq, v3_make(0.0f, 0.0f, 0.0f), wt, ht) <= rr * rr;
     }
     return qb ? qr_round_box(T, Q) : qr_round_box(Q, T);
 }

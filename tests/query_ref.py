@@ -2,11 +2,14 @@
 written for the tests: every query against every target, numpy only. An independent restatement: the kernel grows the
 targets and casts a ray; this reference walks the exact distance of the ball's centre to each target instead.
 
-    hits = spherecast(origins, dirs, radius, targets, max_t=None, ignore=None, ground=None)
-    sets = overlap(shape_type, pos, rot, half_extent, targets, ignore=None, ground=None)
+    hits = spherecast(origins, dirs, radius, targets, max_t=None, ignore=None, ground=None, centre=None)
+    sets = overlap(shape_type, pos, rot, half_extent, targets, ignore=None, ground=None, centre=None)
 
 targets = dict(pos (m, 3), rot (m, 4) [i, j, k, w], half_extent (m, 3), shape (m,), id (m,)): bodies and statics
-together, each with the id the query reports (body index or STATIC_ID_BIT | k). ground = the plane height or None."""
+together, each with the id the query reports (body index or STATIC_ID_BIT | k). ground = the plane height or None.
+centre = a point subtracted in float64 from every query and target position (and its height from the ground) before
+anything else: exact for float32 inputs, so that a scene far from the origin costs the reference no digits; the o of the
+result and its targets (tg) are measured from it."""
 import numpy as np
 
 from raycast_ref import GROUND, MISS, rotation_matrices
@@ -76,11 +79,19 @@ def _bound(he, shape):
                     np.where(shape == SHAPE_CAPSULE, he[:, 0] + he[:, 1], np.linalg.norm(he, axis=1)))
 
 
-def spherecast(origins, dirs, radius, tg, max_t=None, ignore=None, ground=None, iters=80):
+def _centred(tg, centre, ground):
+    c = np.asarray(centre, np.float64).reshape(3)
+    return c, dict(tg, pos=np.asarray(tg["pos"], np.float64) - c), None if ground is None else ground - c[1]
+
+
+def spherecast(origins, dirs, radius, tg, max_t=None, ignore=None, ground=None, iters=80, centre=None):
     """Per ball: dict(body, t, normal, t2 = second-best t, valid). The first t with dist(centre(t), target) <= radius:
     the distance along a line is convex, so a golden-section search finds its minimum and a bisection the first touch."""
     o = np.asarray(origins, np.float64).reshape(-1, 3)
     dv = np.asarray(dirs, np.float64).reshape(-1, 3)
+    if centre is not None:
+        c, tg, ground = _centred(tg, centre, ground)
+        o = o - c
     n = len(o)
     rad = np.broadcast_to(np.asarray(radius, np.float64), (n,)).copy()
     with np.errstate(all="ignore"):
@@ -162,7 +173,7 @@ def spherecast(origins, dirs, radius, tg, max_t=None, ignore=None, ground=None, 
         else:
             k = which[i]
             normal[i] = closest_normal(o[i] + tb[i] * u[i], tg["pos"][k], R[k], tg["half_extent"][k], tg["shape"][k])
-    return dict(body=body, t=tb, normal=normal, t2=t2, valid=valid, u=u, o=o, which=which)
+    return dict(body=body, t=tb, normal=normal, t2=t2, valid=valid, u=u, o=o, which=which, tg=tg)
 
 
 def _seg(pos, R, he, shape):
@@ -241,9 +252,12 @@ def lowest(shape, pos, R, he):
     return pos[1] - np.abs(R[1]) @ he
 
 
-def overlap(shape_type, pos, rot, half_extent, tg, ignore=None, ground=None):
+def overlap(shape_type, pos, rot, half_extent, tg, ignore=None, ground=None, centre=None):
     """Per query: (sorted list of ids, dict id -> separation of the pairs within 1e-3 of touching, both sides)."""
     pos = np.asarray(pos, np.float64).reshape(-1, 3)
+    if centre is not None:
+        c, tg, ground = _centred(tg, centre, ground)
+        pos = pos - c
     n = len(pos)
     st = np.broadcast_to(np.asarray(shape_type), (n,))
     he = np.broadcast_to(np.asarray(half_extent, np.float64).reshape(-1, 3), (n, 3))

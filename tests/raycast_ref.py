@@ -1,17 +1,24 @@
 """Float64 brute force of the ray-cast query (include/physics_hip.h, phys_raycast), written for the tests: every ray
 against every body, with the header's semantics. numpy only.
 
-    hits = cast(origins, dirs, bodies, max_t=None, ignore=None, ground=None)
+    hits = cast(origins, dirs, bodies, max_t=None, ignore=None, ground=None, statics=None, centre=None)
 
-bodies = dict(pos (m, 3), rot (m, 4) [i, j, k, w], half_extent (m, 3), shape (m,)); ground = the plane height or None.
-Returns a dict of per-ray arrays: body (MISS / GROUND / index), t (+inf on a miss), normal (zero on a miss), t2 (the
+bodies = dict(pos (m, 3), rot (m, 4) [i, j, k, w], half_extent (m, 3), shape (m,)): spheres, boxes and capsules (radius
+half_extent[0], core half-length half_extent[1] along the local y axis); statics = the same for the static colliders
+(rot may be None), further targets with the ids STATIC_ID_BIT | k that ignore never names; ground = the plane height or
+None; centre = a point subtracted in float64 from every origin and position (and its height from the ground) before
+anything else: exact for float32 inputs, so a scene far from the origin costs the reference no digits, and o, pos and
+|o| of the result are measured from it.
+Returns a dict of per-ray arrays: body (MISS / GROUND / id), t (+inf on a miss), normal (zero on a miss), t2 (the
 second-best t over every target, +inf if none), span (length of the best target's interval along the ray: short =
-grazing) and valid (direction and origin usable)."""
+grazing) and valid (direction and origin usable); and the targets (pos, R, he, shape, ids: row k of a body is k, of
+static k it is n_bodies + k)."""
 import numpy as np
 
 MISS = 0xFFFFFFFE
 GROUND = 0xFFFFFFFF
-SHAPE_NONE, SHAPE_SPHERE, SHAPE_BOX = 0, 1, 2
+SHAPE_NONE, SHAPE_SPHERE, SHAPE_BOX, SHAPE_CAPSULE = 0, 1, 2, 3
+STATIC_ID_BIT = 0x80000000
 
 
 def rotation_matrices(rot):
@@ -72,7 +79,40 @@ def _intersect(o, u, pos, R, he, shape):
             hit = inside | ((tn <= tf) & (tn >= 0))
             t[box] = np.where(hit, np.where(inside, 0.0, tn), np.inf)
             span[box] = np.where(hit, tf - np.maximum(tn, 0), 0.0)
+        cap = shape == SHAPE_CAPSULE
+        if cap.any():
+            pc, uc, w, r, hl = p[cap], u[cap], R[cap][:, :, 1], he[cap, 0], he[cap, 1]
+            tin = _capsule_entry(pc, uc, w, r, hl)
+            # the capsule is convex: its interval ends where the reversed ray, started beyond it, enters
+            far = np.linalg.norm(pc, axis=1) + r + hl + 1.0
+            tout = far - _capsule_entry(pc + far[:, None] * uc, -uc, w, r, hl)
+            t[cap] = tin
+            span[cap] = np.where(np.isfinite(tin) & np.isfinite(tout), np.maximum(tout - tin, 0.0), 0.0)
     return t, span
+
+
+def _capsule_entry(p, u, w, r, hl):
+    """First t >= 0 at which the ray p + t u (u unit, p relative to the centre) is inside the closed capsule of radius r
+    around the core +- hl w: 0 from inside, else the least of the closed-form roots of the cylinder's side (kept where the
+    hit lies between the end planes) and of the two end balls; inf on a miss."""
+    pd, ud = (p * w).sum(1), (u * w).sum(1)
+    s = np.clip(pd, -hl, hl)
+    inside = np.linalg.norm(p - s[:, None] * w, axis=1) <= r
+    t = np.full(len(p), np.inf)
+    a, b = u - ud[:, None] * w, p - pd[:, None] * w
+    A, B, C = (a * a).sum(1), (a * b).sum(1), (b * b).sum(1) - r * r
+    disc = B * B - A * C
+    ok = (A > 1e-24) & (disc >= 0)
+    ts = (-B - np.sqrt(np.where(ok, disc, 0.0))) / np.where(ok, A, 1.0)
+    ok &= (ts >= 0) & (np.abs(pd + ts * ud) <= hl)
+    t = np.where(ok, ts, t)
+    for end in (-1.0, 1.0):
+        pe = p - (end * hl)[:, None] * w
+        bb, cc = (pe * u).sum(1), (pe * pe).sum(1) - r * r
+        disc = bb * bb - cc
+        te = -bb - np.sqrt(np.maximum(disc, 0.0))
+        t = np.where((disc >= 0) & (te >= 0), np.minimum(t, te), t)
+    return np.where(inside, 0.0, t)
 
 
 def normal_of(o, u, t, pos, R, he, shape):
@@ -83,6 +123,10 @@ def normal_of(o, u, t, pos, R, he, shape):
     hp = o + t * u - pos
     if shape == SHAPE_SPHERE:
         return [hp / np.linalg.norm(hp)]
+    if shape == SHAPE_CAPSULE:  # from the closest point of the core to the hit
+        w = R[:, 1]
+        v = hp - np.clip(hp @ w, -he[1], he[1]) * w
+        return [v / np.linalg.norm(v)]
     l = R.T @ hp
     out = []
     for a in range(3):
@@ -94,21 +138,39 @@ def normal_of(o, u, t, pos, R, he, shape):
     return out
 
 
-def cast(origins, dirs, bodies, max_t=None, ignore=None, ground=None, chunk_elems=4_000_000):
+def _targets(bodies, statics):
+    """bodies then statics as one set of targets: pos, rot, half_extent, shape, ids"""
+    parts = []
+    for d, base in ((bodies, 0), (statics, STATIC_ID_BIT)):
+        if d is None:
+            continue
+        pos = np.asarray(d["pos"], np.float64).reshape(-1, 3)
+        k = len(pos)
+        rot = np.tile([0.0, 0.0, 0.0, 1.0], (k, 1)) if d.get("rot") is None else np.asarray(d["rot"], np.float64).reshape(-1, 4)
+        parts.append((pos, rot, np.asarray(d["half_extent"], np.float64).reshape(-1, 3),
+                      np.asarray(d["shape"]).reshape(-1).astype(np.int64), base + np.arange(k, dtype=np.int64)))
+    return [np.concatenate(x) for x in zip(*parts)]
+
+
+def cast(origins, dirs, bodies, max_t=None, ignore=None, ground=None, chunk_elems=4_000_000, statics=None, centre=None):
     o, u, valid = _unit(origins, dirs)
     n = len(o)
-    pos = np.asarray(bodies["pos"], np.float64).reshape(-1, 3)
+    pos, rot, he, shape, ids = _targets(bodies, statics)
     m = len(pos)
-    he = np.asarray(bodies["half_extent"], np.float64).reshape(-1, 3)
-    shape = np.asarray(bodies["shape"]).reshape(-1)
-    R = rotation_matrices(bodies["rot"]) if m else np.zeros((0, 3, 3))
+    n_bodies = len(np.asarray(bodies["pos"]).reshape(-1, 3))
+    if centre is not None:
+        c = np.asarray(centre, np.float64).reshape(3)
+        o, pos = o - c, pos - c
+        ground = None if ground is None else ground - c[1]
+    R = rotation_matrices(rot) if m else np.zeros((0, 3, 3))
     mt = np.full(n, np.inf) if max_t is None else np.asarray(max_t, np.float64).reshape(-1)
     ig = np.full(n, -1, np.int64) if ignore is None else np.asarray(ignore, np.int64).reshape(-1)
+    ig = np.where(ig < n_bodies, ig, -1)  # names a body or nothing
     ok = valid & (mt >= 0)
     # candidates: rays passing within the bounding sphere of a body (two matrix products per chunk of rays), then the
     # exact test on those pairs only
-    rad = np.where(shape == SHAPE_SPHERE, he[:, 0], np.linalg.norm(he, axis=1))
-    rad = np.where((shape == SHAPE_SPHERE) | (shape == SHAPE_BOX), rad, -1.0)
+    rad = np.where(shape == SHAPE_SPHERE, he[:, 0], np.where(shape == SHAPE_CAPSULE, he[:, 0] + he[:, 1], np.linalg.norm(he, axis=1)))
+    rad = np.where((shape == SHAPE_SPHERE) | (shape == SHAPE_BOX) | (shape == SHAPE_CAPSULE), rad, -1.0)
     cc = (pos * pos).sum(1)
     ri_all, mi_all = [], []
     step = max(1, chunk_elems // max(m, 1))
@@ -118,7 +180,8 @@ def cast(origins, dirs, bodies, max_t=None, ignore=None, ground=None, chunk_elem
         b = (oo * uu).sum(1)[:, None] - uu @ pos.T  # (o - c).u: > 0 moving away from the centre
         pp = (oo * oo).sum(1)[:, None] - 2 * (oo @ pos.T) + cc[None, :]  # |o - c|^2
         d2 = pp - b * b
-        slack = 1e-9 * (pp + 1.0) + 1e-6
+        # (the expanded square is good to a few ulp of |o|^2 + |c|^2: far-flung targets keep their candidates)
+        slack = 1e-9 * (pp + 1.0) + 1e-6 + 1e-14 * ((oo * oo).sum(1)[:, None] + cc[None, :])
         cand = (rad[None, :] >= 0) & (d2 <= (rad * 1.001)[None, :] ** 2 + slack) & ((b <= 0) | (pp <= (rad * 1.001)[None, :] ** 2 + slack))
         cand &= ok[s:e, None]
         r_, m_ = np.nonzero(cand)
@@ -127,20 +190,22 @@ def cast(origins, dirs, bodies, max_t=None, ignore=None, ground=None, chunk_elem
     ri = np.concatenate(ri_all) if ri_all else np.zeros(0, np.int64)
     mi = np.concatenate(mi_all) if mi_all else np.zeros(0, np.int64)
     t, span = _intersect(o[ri], u[ri], pos[mi], R[mi], he[mi], shape[mi])
-    t[(t > mt[ri]) | (ig[ri] == mi)] = np.inf
+    tid = ids[mi]
+    t[(t > mt[ri]) | (ig[ri] == tid)] = np.inf
     # the ground as one more target, id GROUND (larger than every body id: it loses ties)
     if ground is not None:
         with np.errstate(all="ignore"):
             tg = np.where(o[:, 1] <= ground, 0.0, np.where(u[:, 1] < 0, (ground - o[:, 1]) / u[:, 1], np.inf))
         tg = np.where(ok & (tg <= mt), tg, np.inf)
         ri = np.concatenate([ri, np.arange(n)])
-        mi = np.concatenate([mi, np.full(n, GROUND, np.int64)])
+        mi = np.concatenate([mi, np.full(n, -1, np.int64)])
+        tid = np.concatenate([tid, np.full(n, GROUND, np.int64)])
         t = np.concatenate([t, tg])
         span = np.concatenate([span, np.full(n, np.inf)])
     keep = np.isfinite(t)
-    ri, mi, t, span = ri[keep], mi[keep], t[keep], span[keep]
-    order = np.lexsort((mi, t, ri))
-    ri, mi, t, span = ri[order], mi[order], t[order], span[order]
+    ri, mi, tid, t, span = ri[keep], mi[keep], tid[keep], t[keep], span[keep]
+    order = np.lexsort((tid, t, ri))
+    ri, mi, tid, t, span = ri[order], mi[order], tid[order], t[order], span[order]
     first = np.ones(len(ri), bool)
     first[1:] = ri[1:] != ri[:-1]
     second = np.zeros(len(ri), bool)
@@ -149,30 +214,40 @@ def cast(origins, dirs, bodies, max_t=None, ignore=None, ground=None, chunk_elem
     tb = np.full(n, np.inf)
     t2 = np.full(n, np.inf)
     sp = np.zeros(n)
-    body[ri[first]], tb[ri[first]], sp[ri[first]] = mi[first], t[first], span[first]
+    row = np.full(n, -1, np.int64)
+    body[ri[first]], tb[ri[first]], sp[ri[first]], row[ri[first]] = tid[first], t[first], span[first], mi[first]
     t2[ri[second]] = t[second]
     normal = np.zeros((n, 3))
     for i in np.nonzero(body != MISS)[0]:
         if body[i] == GROUND:
             normal[i] = -u[i] if tb[i] == 0 else (0.0, 1.0, 0.0)
         else:
-            k = body[i]
+            k = row[i]
             normal[i] = normal_of(o[i], u[i], tb[i], pos[k], R[k], he[k], shape[k])[0]
-    return dict(body=body, t=tb, normal=normal, t2=t2, span=sp, valid=valid, u=u, o=o, R=R, pos=pos, he=he, shape=shape)
+    return dict(body=body, t=tb, normal=normal, t2=t2, span=sp, valid=valid, u=u, o=o, R=R, pos=pos, he=he, shape=shape, ids=ids,
+                n_bodies=n_bodies, ground=ground)
+
+
+def row_of(hits, target_id):
+    """Row of a body or static id in the hits' target arrays (pos, R, he, shape)."""
+    return int(target_id) if target_id < STATIC_ID_BIT else hits["n_bodies"] + (int(target_id) - STATIC_ID_BIT)
 
 
 def t_of(hits, ray, body_id):
     """Float64 t of ray `ray` against body `body_id` (inf on a miss), for judging a different id."""
     o, u = hits["o"][ray:ray + 1], hits["u"][ray:ray + 1]
-    b = body_id
+    b = row_of(hits, body_id)
     t, _ = _intersect(o, u, hits["pos"][b:b + 1], hits["R"][b:b + 1], hits["he"][b:b + 1], hits["shape"][b:b + 1])
     return float(t[0])
 
 
 def near_body(hits, ray, body_id, t, tol):
     """The point at t on the ray lies within tol of body `body_id` (a grazing hit the float64 test calls a miss)."""
-    b = body_id
+    b = row_of(hits, body_id)
     q = hits["o"][ray] + t * hits["u"][ray] - hits["pos"][b]
     if hits["shape"][b] == SHAPE_SPHERE:
         return abs(np.linalg.norm(q) - hits["he"][b, 0]) <= tol or np.linalg.norm(q) <= hits["he"][b, 0]
+    if hits["shape"][b] == SHAPE_CAPSULE:
+        w = hits["R"][b][:, 1]
+        return np.linalg.norm(q - np.clip(q @ w, -hits["he"][b, 1], hits["he"][b, 1]) * w) <= hits["he"][b, 0] + tol
     return bool((np.abs(hits["R"][b].T @ q) <= hits["he"][b] + tol).all())

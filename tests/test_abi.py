@@ -123,6 +123,13 @@ def test_independent_gpu_checks_share_no_code_with_the_spec_or_the_oracle():
     txt = open(os.path.join(ROOT, "tests", "static_ref.py")).read()  # the static pair search's reference: numpy and pair_ref
     assert set(re.findall(imports, txt, flags=re.M)) == {"numpy", "pair_ref"}
     assert "oracle" not in txt and "include/spec" not in txt
+    # the read-only queries' references, scenes, query sets and acceptance: numpy and each other
+    for name, mods in (("raycast_ref.py", {"numpy"}), ("query_ref.py", {"numpy", "raycast_ref"}), ("query_scenes.py", {"numpy", "functools"}),
+                       ("query_cases.py", {"numpy", "functools", "query_ref", "query_scenes", "raycast_ref"}),
+                       ("query_accept.py", {"numpy", "math", "query_ref", "raycast_ref"})):
+        txt = open(os.path.join(ROOT, "tests", name)).read()
+        assert set(re.findall(imports, txt, flags=re.M)) == mods, name
+        assert "oracle" not in txt and "physics_amd" not in txt.split('"""', 2)[2], name
 
 
 def test_rust_shim_declares_every_header_symbol_once():

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import query_ref as ref
+from query_accept import compare_casts, compare_overlaps  # noqa: F401 (tests/test_gpu_filter.py reads them here too)
 
 pytestmark = pytest.mark.gpu
 
@@ -68,78 +69,6 @@ def _casts(rng, n, extent):
     d = (aim - o).astype(np.float32)
     d[: n // 4] = rng.normal(size=(n // 4, 3))
     return o, d
-
-
-def compare_casts(w, tg, o, d, rad, ground=0.0, ignore=None, out=None, label=""):
-    """same id -> |dt| <= 1e-5 (1 + |o|_inf + t), normal within 1e-4; another id only at a near tie (both ids' float64 t
-    within tolerance) or a grazing contact (the second target's float64 t near the GPU's); counted and asserted rare"""
-    body, t, nrm = out if out is not None else w.spherecast(o, d, rad, ignore=ignore)
-    h = ref.spherecast(o, d, rad, tg, ignore=ignore, ground=ground)
-    n = len(body)
-    odd, bad, odd_cases = 0, [], []
-    for i in range(n):
-        rb, rt, gb, gt = int(h["body"][i]), float(h["t"][i]), int(body[i]), float(t[i])
-        oinf = float(np.abs(h["o"][i]).max()) if h["valid"][i] else 0.0
-        tol = 1e-5 * (1.0 + oinf + (rt if math.isfinite(rt) else (gt if math.isfinite(gt) else 0.0)))
-        if gb == rb:
-            if rb == ref.MISS:
-                if not (gt == math.inf and not nrm[i].any()):
-                    bad.append((i, "miss with t / normal"))
-            elif abs(gt - rt) > tol:
-                bad.append((i, "t", gb, gt, rt))
-            elif np.abs(nrm[i] - h["normal"][i]).max() > 1e-4 and rt > 0:
-                # a contact at an edge: the normal turns fast along t; judge at the GPU's t
-                k = h["which"][i]
-                if gb == ref.GROUND or k < 0:
-                    bad.append((i, "normal", nrm[i], h["normal"][i]))
-                else:
-                    alt = ref.closest_normal(h["o"][i] + gt * h["u"][i], tg["pos"][k], ref._frames(tg)[k],
-                                             tg["half_extent"][k], tg["shape"][k])
-                    if abs(float(h["normal"][i] @ h["u"][i])) < 0.1:
-                        odd += 1  # a grazing contact: the normal turns fast with t there
-                    elif np.abs(nrm[i] - alt).max() > 1e-3:
-                        bad.append((i, "normal", nrm[i], h["normal"][i]))
-            continue
-        # another id: a near tie (the second-best float64 t is within tolerance) or a grazing contact
-        if math.isfinite(rt) and abs(float(h["t2"][i]) - rt) <= 4 * tol and abs(gt - rt) <= 4 * tol:
-            odd_cases.append((i, "tie", gb, gt, rb, rt))
-            continue
-        if gb == ref.MISS and not math.isfinite(float(h["t2"][i])) and rt > 0:
-            odd_cases.append((i, "gpu miss", rb, rt))  # the float64 contact is the only one: a grazing touch float32 missed
-            continue
-        if gb != ref.MISS and gb != ref.GROUND and math.isfinite(gt):
-            # a grazing touch of the GPU's target that float64 calls a miss or a later contact
-            k = int(np.nonzero(tg["id"] == gb)[0][0])
-            c = (h["o"][i] + gt * h["u"][i])[None]
-            r_i = float(np.broadcast_to(np.asarray(rad, np.float64), (n,))[i])
-            dist = ref.point_dist(c, tg["pos"][k:k + 1], ref._frames(tg)[k:k + 1], tg["half_extent"][k:k + 1],
-                                  tg["shape"][k:k + 1])[0]
-            if dist <= r_i + tol and gt <= rt + tol:
-                odd_cases.append((i, "graze", gb, gt, rb, rt))
-                continue
-        bad.append((i, "id", gb, gt, rb, rt))
-    assert not bad, f"{label}: {len(bad)} of {n}: {bad[:8]}"
-    odd = len(odd_cases) + odd
-    assert odd <= max(3, n // 200), f"{label}: {odd} near ties / grazing contacts of {n}: {odd_cases[:8]}"
-    return body, t, nrm
-
-
-def compare_overlaps(w, tg, st, pos, rot, he, ground=0.0, ignore=None, label=""):
-    off, ids = w.overlap(st, pos, rot, he, ignore=ignore)
-    want = ref.overlap(st, pos, rot, he, tg, ignore=ignore, ground=ground)
-    n = len(pos)
-    assert len(off) == n + 1 and off[0] == 0 and off[n] == len(ids)
-    near = 0
-    for i in range(n):
-        got = [int(x) for x in ids[off[i]:off[i + 1]]]
-        assert got == sorted(set(got)), (label, i, got)
-        exp, close = want[i]
-        diff = set(got) ^ set(exp)
-        for k in diff:
-            assert k in close and abs(close[k]) <= 1e-4, (label, i, k, got, exp, close.get(k))
-            near += 1
-    assert near <= max(2, n // 200), f"{label}: {near} pairs within 1e-4 of touching of {n} queries"
-    return off, ids
 
 
 # ---- 1. hand scenes --------------------------------------------------------------------------------------------------

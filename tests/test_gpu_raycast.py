@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import raycast_ref as ref
+from query_accept import compare
 
 pytestmark = pytest.mark.gpu
 
@@ -35,68 +36,6 @@ def _world(pos, shape, he, rot=None, flags=None, lin_vel=None, **cfg):
 def _bodies(w, shape, he):
     pos, rot = w.get_transforms()
     return dict(pos=pos, rot=rot, half_extent=np.asarray(he, np.float32).reshape(-1, 3), shape=np.asarray(shape).reshape(-1))
-
-
-def _normal_ok(h, i, gb, gt, nrm):
-    u = h["u"][i]
-    if gt == 0:
-        opts = [-u]
-    elif gb == ref.GROUND:
-        opts = [np.array([0.0, 1.0, 0.0])]
-    else:
-        opts = ref.normal_of(h["o"][i], u, gt, h["pos"][gb], h["R"][gb], h["he"][gb], h["shape"][gb])
-        if h["t"][i] != gt:  # judged at the float64 t as well
-            opts += ref.normal_of(h["o"][i], u, h["t"][i], h["pos"][gb], h["R"][gb], h["he"][gb], h["shape"][gb])
-    return any(np.abs(nrm - o).max() <= 1e-4 for o in opts)
-
-
-def compare(w, bodies, o, d, max_t=None, ignore=None, ground=0.0, label="", out=None):
-    """The acceptance of the issue: same id -> |dt| <= 1e-5 (1 + |o|_inf + t), normal to 1e-4 (either face at an edge);
-    another id only for a near tie or a grazing ray; hit against miss only for grazing rays (counted, asserted tiny)."""
-    body, t, nrm = out if out is not None else w.raycast(o, d, max_t, ignore)
-    h = ref.cast(o, d, bodies, max_t, ignore, ground)
-    n = len(body)
-    grazing, bad = 0, []
-    for i in range(n):
-        rb, rt = int(h["body"][i]), float(h["t"][i])
-        gb, gt = int(body[i]), float(t[i])
-        oinf = float(np.abs(h["o"][i]).max()) if h["valid"][i] else 0.0
-        tol = 1e-5 * (1.0 + oinf + (rt if math.isfinite(rt) else (gt if math.isfinite(gt) else 0.0)))
-        if gb == rb:
-            if rb == ref.MISS:
-                if not (gt == math.inf and not nrm[i].any()):
-                    bad.append((i, "miss with t / normal", gt, nrm[i]))
-            elif abs(gt - rt) > tol:
-                bad.append((i, "t", gb, gt, rt))
-            elif not _normal_ok(h, i, gb, gt, nrm[i]):
-                bad.append((i, "normal", gb, nrm[i], h["normal"][i]))
-            continue
-        if gb != ref.MISS and rb != ref.MISS:
-            if gb == ref.GROUND:
-                u = h["u"][i]
-                tg64 = 0.0 if h["o"][i][1] <= ground else ((ground - h["o"][i][1]) / u[1] if u[1] < 0 else math.inf)
-            else:
-                tg64 = ref.t_of(h, i, gb)
-            if abs(tg64 - rt) <= tol and abs(gt - rt) <= tol:
-                continue  # near tie
-            if h["span"][i] <= tol or (gb != ref.GROUND and not math.isfinite(tg64) and ref.near_body(h, i, gb, gt, tol)):
-                grazing += 1
-                continue
-            bad.append((i, "id", gb, gt, rb, rt, tg64))
-        elif gb == ref.MISS:
-            if h["span"][i] <= tol:
-                grazing += 1
-            else:
-                bad.append((i, "gpu miss", rb, rt, h["span"][i]))
-        else:
-            if gb != ref.GROUND and ref.near_body(h, i, gb, gt, tol):
-                grazing += 1
-            else:
-                bad.append((i, "ref miss", gb, gt))
-    print(f"{label}: {n} rays, {int((h['body'] != ref.MISS).sum())} hits, grazing disagreements {grazing}")
-    assert not bad, f"{label}: {len(bad)} mismatches, first {bad[:8]}"
-    assert grazing <= max(2, n // 1000), f"{label}: {grazing} grazing disagreements"
-    return body, t, nrm
 
 
 # ---- 1. hand scene ---------------------------------------------------------------------------------------------------
