@@ -291,6 +291,44 @@ int32_t phys_spherecast(phys_world* w, uint64_t n, const float* origin /*3n*/, c
 int32_t phys_spherecast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius,
                                const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out,
                                float* normal_out);
+/* phys_capsulecast: a capsule moves from origin[i] along dir[i] / |dir[i]| without turning. Its core is the segment
+ * centre +- half_length[i] * a, a the y axis turned by rot_ijkw[i] (NULL = identity; used as given, like phys_overlap's rot),
+ * its radius radius[i]. The result is the first target the closed capsule touches and the distance t its centre travelled.
+ * Ids, ties, ignore_body, max_t and the miss value are phys_spherecast's; a query also misses on a non-finite rot and on a
+ * negative, NaN or infinite radius or half_length.
+ *   - normal: the unit vector from the target's closest point to the capsule's core at the contact; -dir / |dir| for a cast
+ *     that starts touching (t = 0); (0, 1, 0) on the ground.
+ *   - point_out (may be NULL): the touched point of the target's surface, i.e. the target's closest point to the capsule's
+ *     core (for a sphere or capsule target: its core's closest point plus r * normal); on the ground the lower end of the
+ *     core (the centre when a.y == 0) projected onto the plane; zeros at t = 0 and on a miss. Where the contact is a line or
+ *     an area (a capsule flat on a face, parallel cores) it is some point of it.
+ *   - half_length == 0 is a sphere cast: body, t and normal are phys_spherecast's bit for bit.
+ *   - the tests are closed forms in float32, a ray from the capsule's centre against the Minkowski sum of the target and
+ *     the capsule: a sphere becomes a capsule, a capsule a thickened parallelogram (four edge capsules and two faces), a box
+ *     a thickened zonotope of four generators (six face pairs and the edge capsules along every generator).
+ *   - the grid is grown by the call's largest valid radius + half_length (capped at 2^100), as phys_spherecast's is by the
+ *     radius.
+ *   - PHYS_ERR_INVALID_ARG: n >= 2^31, a NULL origin, dir, radius, half_length, body_out or t_out. n == 0 is a no-op.
+ * phys_capsulecast takes host arrays and returns with the outputs written; phys_capsulecast_device takes device pointers and
+ * only enqueues on the world's stream. The _filtered calls take a query_mask as phys_spherecast_filtered does. */
+int32_t phys_capsulecast(phys_world* w, uint64_t n, const float* origin /*3n*/, const float* dir /*3n*/,
+                         const float* rot_ijkw /*4n, NULL = identity*/, const float* radius /*n*/, const float* half_length /*n*/,
+                         const float* max_t /*n, NULL = +inf*/, const uint32_t* ignore_body /*n, NULL = none*/,
+                         uint32_t* body_out /*n*/, float* t_out /*n*/, float* normal_out /*3n, may be NULL*/,
+                         float* point_out /*3n, may be NULL*/);
+int32_t phys_capsulecast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
+                                const float* radius, const float* half_length, const float* max_t, const uint32_t* ignore_body,
+                                uint32_t* body_out, float* t_out, float* normal_out, float* point_out);
+int32_t phys_capsulecast_filtered(phys_world* w, uint64_t n, const float* origin /*3n*/, const float* dir /*3n*/,
+                                  const float* rot_ijkw /*4n, NULL = identity*/, const float* radius /*n*/,
+                                  const float* half_length /*n*/, const float* max_t /*n, NULL = +inf*/,
+                                  const uint32_t* ignore_body /*n, NULL = none*/, const uint16_t* query_mask /*n, NULL = no filtering*/,
+                                  uint32_t* body_out /*n*/, float* t_out /*n*/, float* normal_out /*3n, may be NULL*/,
+                                  float* point_out /*3n, may be NULL*/);
+int32_t phys_capsulecast_device_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
+                                         const float* radius, const float* half_length, const float* max_t,
+                                         const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
+                                         float* normal_out, float* point_out);
 /* phys_overlap: for each query shape (shape_type SPHERE, BOX or CAPSULE with the bodies' half_extent conventions, at pos
  * with the unit quaternion rot_ijkw, NULL = identity), every target whose closed shape intersects it (touching counts).
  *   - output (CSR): query i's ids are ids_out[offsets_out[i] .. offsets_out[i + 1]), ascending and each once: bodies,

@@ -200,6 +200,11 @@ PROTOTYPES = {
     "phys_spherecast": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, u32p, u32p, f32p, f32p]),
     "phys_spherecast_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "phys_capsulecast": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, f32p, f32p, u32p, u32p, f32p, f32p, f32p]),
+    "phys_capsulecast_device": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 11),
+    "phys_capsulecast_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, f32p, f32p, u32p, u16p, u32p, f32p,
+                                              f32p, f32p]),
+    "phys_capsulecast_device_filtered": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 12),
     "phys_overlap": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p, f32p, u32p, C.c_uint64, u64p, u32p]),
     "phys_set_static_bodies": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, u32p, f32p]),
     "phys_set_body_filters": (C.c_int32, [C.c_void_p, C.c_uint64, u16p, u16p, i16p]),

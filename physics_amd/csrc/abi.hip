@@ -229,7 +229,7 @@ struct Staging {
     struct Slot { size_t offset; bool there; };  // what add() gives and at() takes: where an array of T lies, if it is there
     phys_world* w;
     DevBuf<uint8_t>& buf;
-    Array arrays[6] = {};
+    Array arrays[8] = {};
     int count = 0;
     size_t total = 0;
     // `n` elements at the next multiple of `align` bytes; a null array takes no room
@@ -932,6 +932,77 @@ int32_t phys_spherecast_device_filtered(phys_world* w, uint64_t n, const float* 
                                         const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask,
                                         uint32_t* body_out, float* t_out, float* normal_out) {
     return cast_device(w, true, n, origin, dir, radius, max_t, ignore_body, query_mask, body_out, t_out, normal_out);
+}
+
+// ---- capsule casts: the casts' checks and staging with rot, half_length and point_out besides ----
+static int32_t capsulecast_args(uint64_t n, const float* origin, const float* dir, const float* radius, const float* half_length,
+                                const uint32_t* body_out, const float* t_out) {
+    if (n >= (1ull << 31)) return fail(PHYS_ERR_INVALID_ARG, "phys_capsulecast: n must be below 2^31");
+    if (n && (!origin || !dir || !radius || !half_length || !body_out || !t_out))
+        return fail(PHYS_ERR_INVALID_ARG, "phys_capsulecast: null origin, dir, radius, half_length, body_out or t_out");
+    return PHYS_OK;
+}
+
+static int32_t capsulecast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
+                                  const float* radius, const float* half_length, const float* max_t, const uint32_t* ignore_body,
+                                  const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out, float* point_out) {
+    ENTER(w);
+    PHYS_TRY(capsulecast_args(n, origin, dir, radius, half_length, body_out, t_out));
+    if (n == 0) return PHYS_OK;
+    return launch_capsulecast(w, n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body, body_out, t_out, normal_out, point_out,
+                              query_mask);
+}
+
+static int32_t capsulecast_host(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw, const float* radius,
+                                const float* half_length, const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask,
+                                uint32_t* body_out, float* t_out, float* normal_out, float* point_out) {
+    ENTER(w);
+    PHYS_TRY(capsulecast_args(n, origin, dir, radius, half_length, body_out, t_out));
+    if (n == 0) return PHYS_OK;
+    Staging in{w, w->stage}, out{w, w->rc_out};
+    const auto s_origin = in.add(origin, 3 * n), s_dir = in.add(dir, 3 * n), s_rot = in.add(rot_ijkw, 4 * n);
+    const auto s_radius = in.add(radius, n), s_half = in.add(half_length, n), s_max_t = in.add(max_t, n);
+    const auto s_ignore = in.add(ignore_body, n);
+    const auto s_mask = in.add(query_mask, n);
+    const auto s_body = out.add(body_out, n);
+    const auto s_t = out.add(t_out, n), s_normal = out.add(normal_out, 3 * n), s_point = out.add(point_out, 3 * n);
+    PHYS_TRY(in.reserve());
+    PHYS_TRY(out.reserve());
+    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
+    PHYS_TRY(launch_capsulecast(w, n, in.at(s_origin), in.at(s_dir), in.at(s_rot), in.at(s_radius), in.at(s_half), in.at(s_max_t),
+                                in.at(s_ignore), out.at(s_body), out.at(s_t), out.at(s_normal), out.at(s_point), in.at(s_mask)));
+    PHYS_TRY(out.copy(hipMemcpyDeviceToHost));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    return PHYS_OK;
+}
+
+int32_t phys_capsulecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw, const float* radius,
+                         const float* half_length, const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out,
+                         float* normal_out, float* point_out) {
+    return capsulecast_host(w, n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body, nullptr, body_out, t_out, normal_out,
+                            point_out);
+}
+
+int32_t phys_capsulecast_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
+                                  const float* radius, const float* half_length, const float* max_t, const uint32_t* ignore_body,
+                                  const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out, float* point_out) {
+    return capsulecast_host(w, n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body, query_mask, body_out, t_out, normal_out,
+                            point_out);
+}
+
+int32_t phys_capsulecast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
+                                const float* radius, const float* half_length, const float* max_t, const uint32_t* ignore_body,
+                                uint32_t* body_out, float* t_out, float* normal_out, float* point_out) {
+    return capsulecast_device(w, n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body, nullptr, body_out, t_out, normal_out,
+                              point_out);
+}
+
+int32_t phys_capsulecast_device_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
+                                         const float* radius, const float* half_length, const float* max_t, const uint32_t* ignore_body,
+                                         const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out,
+                                         float* point_out) {
+    return capsulecast_device(w, n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body, query_mask, body_out, t_out, normal_out,
+                              point_out);
 }
 
 static int32_t overlap_host(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,

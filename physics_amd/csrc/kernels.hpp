@@ -185,6 +185,13 @@ struct QueryFilters {
 // arguments it reads - and compiles to the instructions it had before filters.
 template <typename T>
 __device__ __forceinline__ T filter_arg(T f) { return f; }
+// what a capsule cast adds to the arguments of the cast kernel (k_rc_trace): in the same pack, in front of the filters, so
+// that the ray and ball instances keep their arguments and their instructions
+struct CapsuleArgs {
+    const float* rot;          // [i, j, k, w] per query; null: identity
+    const float* half_length;  // per query
+    float* point_out;          // 3 per query; null: not wanted
+};
 
 // ---- materials ---------------------------------------------------------------------------------
 // One {friction, restitution} per body slot and per static collider: one 8-byte load per side of a manifold, made by
@@ -376,9 +383,16 @@ void static_narrow_args(const phys_world* w, uint64_t* cap, const uint32_t** pai
 int32_t launch_trace(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* radius /* null: rays */,
                      const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out,
                      const uint16_t* query_mask /* device, n_rays; null: no filtering */);
+// the same walk for capsules (phys_capsulecast): core origin +- half_length * (rot's y axis), radius[i];
+// the grid grown by the largest valid radius + half_length. rot (4 per query), normal_out and point_out may be null.
+int32_t launch_capsulecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot, const float* radius,
+                           const float* half_length, const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out,
+                           float* normal_out, float* point_out, const uint16_t* query_mask /* device, n; null: no filtering */);
 // the query grid alone (rc_header, rc_start, rc_records), every body AABB grown by the largest valid value of the device
-// array grow_radius (null: not grown); *bits = log2 of the bucket table
-int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_radius, uint32_t* bits);
+// array grow_radius (null: not grown), plus grow_half_length's of the same query where that is given (a capsule reaches
+// radius + half_length from its centre); *bits = log2 of the bucket table
+int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_radius, uint32_t* bits,
+                          const float* grow_half_length = nullptr);
 // query.hip: overlap queries on staged device arrays; writes the host offsets (n + 1) and, when they fit in cap, the ids
 int32_t launch_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot, const float* half_extent,
                        const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out,

@@ -23,9 +23,12 @@
 // Sphere casts (k_rc_trace<, true>) run the same walk for the ball's centre over a grid whose body AABBs were grown by the
 // call's largest valid radius (k_sc_grow writes it into the header before k_rc_bounds; ray casts leave it zero, which
 // changes no arithmetic), and test each candidate with sc_test: the ray against the target grown by the ball's radius.
+// Capsule casts (phys_capsulecast) are a third instance of the same kernel, chosen by a CapsuleArgs in
+// its argument pack: the grid grown by the largest valid radius + half-length, every candidate tested with cc_test
+// (capsule_cast.hpp); a capsule of half-length 0 is a ball and calls sc_test.
 #include <cstdio>
 
-#include "rc_grid.hpp"
+#include "capsule_cast.hpp"
 
 namespace phys {
 
@@ -304,7 +307,9 @@ __device__ __forceinline__ float rc_plane_t(int i, bool up, float lo, float cell
 // SWEEP: a sphere cast (radius per ray; the grid was grown by the largest valid radius, so the walk of the centre line
 // meets every target the ball can touch); otherwise a ray cast (radius unused, the arithmetic of the ray cast unchanged).
 // FILT: the _filtered calls (one QueryFilters argument, the pack `filt`): a target whose category misses the query's mask
-// is skipped before its exact test; without it the pack is empty and the kernel is the one it was before filters
+// is skipped before its exact test; without it the pack is empty and the kernel is the one it was before filters.
+// A CapsuleArgs in front of the pack (SWEEP instances only) makes the instance the capsule cast: lanes with a half-length
+// above 0 test with cc_test and find their contact after the walk, the others are sphere casts with a touched point.
 template <bool STATS, bool SWEEP, bool FILT, typename... Filt>
 __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const float* __restrict__ origin, const float* __restrict__ dir,
                                                         const float* __restrict__ radius,
@@ -314,7 +319,11 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
                                                         const float4* __restrict__ st_rec, uint32_t n_static,
                                                         uint32_t* __restrict__ body_out, float* __restrict__ t_out, float* __restrict__ normal_out,
                                                         unsigned long long* __restrict__ stats, Filt... filt) {
-    static_assert(sizeof...(Filt) == (FILT ? 1u : 0u), "one QueryFilters argument exactly in the filtered instance");
+    constexpr bool CAPS = has_capsule_args<Filt...>::value;
+    static_assert(sizeof...(Filt) == (FILT ? 1u : 0u) + (CAPS ? 1u : 0u), "one QueryFilters argument exactly in the filtered instance");
+    static_assert(SWEEP || !CAPS, "a capsule cast is a sweep");
+    CapsuleArgs ca{};
+    if constexpr (CAPS) ca = capsule_arg(filt...);
     const uint32_t r = blockIdx.x * kRcThreads + threadIdx.x;
     if (r >= n_rays) return;
     QueryFilters qf{};
@@ -330,10 +339,26 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
     const float sum = ((o.x + o.y) + (o.z + d.x)) + (d.y + d.z);
     const float rad = SWEEP ? radius[r] : 0.0f;
     const bool rad_ok = !SWEEP || (rad >= 0.0f && rad <= 3.4e38f);  // a negative, NaN or infinite radius misses
-    if (len > 0.0f && len <= 3.0e38f && isfinite(sum) && tmax >= 0.0f && rad_ok) {
+    // the capsule's core: half-length hq along a, the y axis of rot (used as given); a bad half-length or rot misses
+    float hq = 0.0f, ax = 0.0f, ay = 1.0f, az = 0.0f;
+    bool cap_ok = true, best_st = false;
+    uint32_t best_k = 0;
+    v3 point = v3_make(0.0f, 0.0f, 0.0f);
+    if constexpr (CAPS) {
+        hq = ca.half_length[r];
+        cap_ok = hq >= 0.0f && hq <= 3.4e38f;
+        if (ca.rot) {
+            const float4 q4 = make_float4(ca.rot[4 * (size_t)r], ca.rot[4 * (size_t)r + 1], ca.rot[4 * (size_t)r + 2], ca.rot[4 * (size_t)r + 3]);
+            cap_ok = cap_ok && isfinite(q4.x) && isfinite(q4.y) && isfinite(q4.z) && isfinite(q4.w);
+            rc_capsule_axis(q4, ax, ay, az);
+        }
+    }
+    if (len > 0.0f && len <= 3.0e38f && isfinite(sum) && tmax >= 0.0f && rad_ok && cap_ok) {
         const float ux = d.x / len, uy = d.y / len, uz = d.z / len;
-        // the ground: the solid half-space y <= ground_y (for a ball: its centre reaches y = ground_y + rad)
-        const float gy = SWEEP ? ground_y + rad : ground_y;
+        // the ground: the solid half-space y <= ground_y (for a ball: its centre reaches y = ground_y + rad; for a capsule:
+        // its lowest point, hq |a.y| + rad below the centre)
+        float gy = SWEEP ? ground_y + rad : ground_y;
+        if (CAPS && hq > 0.0f) gy = ground_y + (rad + hq * fabsf(ay));
         if (ground && (!FILT || (qf.ground & qm) != 0u)) {
             float tg = -1.0f;
             if (o.y <= gy) { tg = 0.0f; best.nx = -ux; best.ny = -uy; best.nz = -uz; }
@@ -345,7 +370,8 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
         // walk so that a static hit shortens it; bodies still win exact ties (smaller ids), the ground loses them
         for (uint32_t k = 0; k < n_static; ++k) {
             if (FILT && (qf.st[k].x & qm) == 0u) continue;
-            if (SWEEP) sc_test(st_rec, k, o.x, o.y, o.z, ux, uy, uz, rad, tmax, 0xFFFFFFFFu, best);
+            if (CAPS && hq > 0.0f) cc_test(st_rec, k, true, o.x, o.y, o.z, ux, uy, uz, ax, ay, az, hq, rad, tmax, 0xFFFFFFFFu, best, best_k, best_st);
+            else if (SWEEP) sc_test(st_rec, k, o.x, o.y, o.z, ux, uy, uz, rad, tmax, 0xFFFFFFFFu, best);
             else rc_test(st_rec, k, o.x, o.y, o.z, ux, uy, uz, tmax, 0xFFFFFFFFu, best);
         }
         const RcGrid g = rc_grid(hdr);
@@ -379,7 +405,8 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
                 if (STATS) { cells += 1; cands += b1 - b0; }
                 for (uint32_t k = b0; k < b1; ++k) {
                     if (FILT && (qf.body[__float_as_uint(rec[3 * (size_t)k + 2].w)].x & qm) == 0u) continue;
-                    if (SWEEP) sc_test(rec, k, o.x, o.y, o.z, ux, uy, uz, rad, tlim, ign, best);
+                    if (CAPS && hq > 0.0f) cc_test(rec, k, false, o.x, o.y, o.z, ux, uy, uz, ax, ay, az, hq, rad, tlim, ign, best, best_k, best_st);
+                    else if (SWEEP) sc_test(rec, k, o.x, o.y, o.z, ux, uy, uz, rad, tlim, ign, best);
                     else rc_test(rec, k, o.x, o.y, o.z, ux, uy, uz, tlim, ign, best);
                 }
                 if (best.t <= texit || texit > t1) break;
@@ -391,20 +418,34 @@ __global__ __launch_bounds__(kRcThreads) void k_rc_trace(uint32_t n_rays, const 
                 tz = az ? rc_plane_t(iz, upz, g.loz, g.cell, o.z, iuz) : tz;
             }
         }
+        if constexpr (CAPS) {
+            // the contact, once per query: the touched point and, for a capsule, the normal from the closest points at t
+            if (best.id == kRayGround && best.t > 0.0f) {
+                // the lower end of the core (the centre for a level one) at t, projected onto the plane
+                const float e = ay > 0.0f ? -hq : (ay < 0.0f ? hq : 0.0f);
+                point = v3_make((o.x + best.t * ux) + e * ax, ground_y, (o.z + best.t * uz) + e * az);
+            } else if (best.id != kRayMiss && best.t > 0.0f) {
+                if (hq > 0.0f) cc_contact(best_st ? st_rec : rec, best_k, o.x, o.y, o.z, ux, uy, uz, ax, ay, az, hq, rad, best.t, best.nx, best.ny, best.nz, point);
+                else point = v3_make(o.x + (best.t * ux - rad * best.nx), o.y + (best.t * uy - rad * best.ny), o.z + (best.t * uz - rad * best.nz));
+            }
+        }
     }
     body_out[r] = best.id;
     t_out[r] = best.t;
     if (normal_out) st3(normal_out, r, v3_make(best.nx, best.ny, best.nz));
+    if constexpr (CAPS) { if (ca.point_out) st3(ca.point_out, r, point); }
     if (STATS) { atomicAdd(&stats[0], (unsigned long long)cells); atomicAdd(&stats[1], (unsigned long long)cands); }
 }
 
 // the largest valid (finite, non-negative) radius of a sphere cast into the header's grow slot, capped at kScMaxGrow:
 // non-negative floats order as their bits, so one atomicMax per workgroup
-__global__ __launch_bounds__(kRcThreads) void k_sc_grow(uint32_t n, const float* __restrict__ radius, RcHeader* __restrict__ hdr) {
+// (a capsule cast: the largest radius + half-length over the queries in which both are valid)
+__global__ __launch_bounds__(kRcThreads) void k_sc_grow(uint32_t n, const float* __restrict__ radius, const float* __restrict__ half_length,
+                                                       RcHeader* __restrict__ hdr) {
     float m = 0.0f;
     for (uint32_t i = blockIdx.x * kRcThreads + threadIdx.x; i < n; i += gridDim.x * kRcThreads) {
-        const float r = radius[i];
-        if (r >= 0.0f && r <= 3.4e38f) m = fmaxf(m, fminf(r, kScMaxGrow));
+        const float r = radius[i], h = half_length ? half_length[i] : 0.0f;
+        if (r >= 0.0f && r <= 3.4e38f && h >= 0.0f && h <= 3.4e38f) m = fmaxf(m, fminf(half_length ? r + h : r, kScMaxGrow));
     }
     const auto op_fmax = [](float a, float b) { return fmaxf(a, b); };
     __shared__ float red[kRcThreads / 64];
@@ -417,7 +458,7 @@ __global__ __launch_bounds__(kRcThreads) void k_sc_grow(uint32_t n, const float*
 
 unsigned rc_blocks(uint64_t n) { return (unsigned)((n + kRcThreads - 1) / kRcThreads); }
 
-int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_radius, uint32_t* bits_out) {
+int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_radius, uint32_t* bits_out, const float* grow_half_length) {
     hipStream_t s = w->stream;
     const uint64_t n = w->n_owned;
     PHYS_HIP_TRY(w->rc_header.resize(sizeof(RcHeader) / 4));
@@ -437,7 +478,7 @@ int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_ra
         const uint32_t nn = (uint32_t)n;
         if (grow_radius && n_radius)
             hipLaunchKernelGGL(k_sc_grow, dim3(std::min<unsigned>(rc_blocks(n_radius), kRcMaxBoundsBlocks)), dim3(kRcThreads), 0, s,
-                               (uint32_t)n_radius, grow_radius, reinterpret_cast<RcHeader*>(w->rc_header.p));
+                               (uint32_t)n_radius, grow_radius, grow_half_length, reinterpret_cast<RcHeader*>(w->rc_header.p));
         const unsigned bb = std::min<unsigned>(rc_blocks(n), kRcMaxBoundsBlocks);
         hipLaunchKernelGGL(k_rc_bounds, dim3(bb), dim3(kRcThreads), 0, s, nn, w->pos.p, w->rot.p, w->half_extent.p, w->shape.p,
                            reinterpret_cast<RcHeader*>(w->rc_header.p));
@@ -454,13 +495,14 @@ int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_ra
     return PHYS_OK;
 }
 
-// the walk shared by ray casts (radius == nullptr) and sphere casts
-int32_t launch_trace(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* radius, const float* max_t,
-                     const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out, const uint16_t* query_mask) {
+// the walk shared by ray casts (radius == nullptr), sphere casts and capsule casts (caps != nullptr)
+static int32_t trace(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* radius, const CapsuleArgs* caps,
+                     const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out,
+                     const uint16_t* query_mask) {
     hipStream_t s = w->stream;
     const uint64_t n = w->n_owned;
     uint32_t bits = 12;
-    int32_t rc = launch_query_grid(w, radius, radius ? n_rays : 0, &bits); if (rc) return rc;
+    int32_t rc = launch_query_grid(w, radius, radius ? n_rays : 0, &bits, caps ? caps->half_length : nullptr); if (rc) return rc;
     const RcHeader* hdr = reinterpret_cast<const RcHeader*>(w->rc_header.p);
     const bool stats = debug_switches().raycast_stats;
     if (stats) {
@@ -473,29 +515,48 @@ int32_t launch_trace(phys_world* w, uint64_t n_rays, const float* origin, const 
     qf.body = reinterpret_cast<const uint2*>(w->filt.p);
     qf.st = reinterpret_cast<const uint2*>(w->st_filt.p);
     qf.ground = w->ground_filt & 0xFFFFu;
-    dispatch_bool(stats, [&](auto st) {
-        dispatch_bool(radius != nullptr, [&](auto sw) {
-            constexpr bool kSt = decltype(st)::value, kSw = decltype(sw)::value;
-#define PHYS_RC_LAUNCH(FILT, ...)                                                                                            \
-    hipLaunchKernelGGL((k_rc_trace<kSt, kSw, FILT>), dim3(rc_blocks(n_rays)), dim3(kRcThreads), 0, s, (uint32_t)n_rays, origin, dir,  \
+#define PHYS_RC_LAUNCH(SW, FILT, ...)                                                                                        \
+    hipLaunchKernelGGL((k_rc_trace<kSt, SW, FILT>), dim3(rc_blocks(n_rays)), dim3(kRcThreads), 0, s, (uint32_t)n_rays, origin, dir,   \
                        radius, max_t, ignore_body, hdr, bits, (const uint32_t*)w->rc_start.p,                                      \
                        reinterpret_cast<const float4*>(w->rc_records.p), (uint32_t)n, ground, w->cfg.ground_height,               \
                        reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static, body_out, t_out, normal_out,           \
                        w->rc_stats.p, ##__VA_ARGS__)
-            if (query_mask) PHYS_RC_LAUNCH(true, qf);
-            else PHYS_RC_LAUNCH(false);
-#undef PHYS_RC_LAUNCH
+    dispatch_bool(stats, [&](auto st) {
+        constexpr bool kSt = decltype(st)::value;
+        if (caps) {
+            if (query_mask) PHYS_RC_LAUNCH(true, true, *caps, qf);
+            else PHYS_RC_LAUNCH(true, false, *caps);
+            return;
+        }
+        dispatch_bool(radius != nullptr, [&](auto sw) {
+            constexpr bool kSw = decltype(sw)::value;
+            if (query_mask) PHYS_RC_LAUNCH(kSw, true, qf);
+            else PHYS_RC_LAUNCH(kSw, false);
         });
     });
+#undef PHYS_RC_LAUNCH
     PHYS_HIP_TRY(hipGetLastError());
     if (stats) {
         unsigned long long h[2] = {0, 0};
         PHYS_HIP_TRY(hipMemcpyAsync(h, w->rc_stats.p, 16, hipMemcpyDeviceToHost, s));
         PHYS_HIP_TRY(hipStreamSynchronize(s));
-        fprintf(stderr, "%s rays=%llu cells=%llu candidates=%llu\n", radius ? "PHYS_SPHERECAST_STATS" : "PHYS_RAYCAST_STATS",
+        fprintf(stderr, "%s rays=%llu cells=%llu candidates=%llu\n",
+                caps ? "PHYS_CAPSULECAST_STATS" : (radius ? "PHYS_SPHERECAST_STATS" : "PHYS_RAYCAST_STATS"),
                 (unsigned long long)n_rays, h[0], h[1]);
     }
     return PHYS_OK;
+}
+
+int32_t launch_trace(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* radius, const float* max_t,
+                     const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out, const uint16_t* query_mask) {
+    return trace(w, n_rays, origin, dir, radius, nullptr, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
+}
+
+int32_t launch_capsulecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot, const float* radius,
+                           const float* half_length, const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out,
+                           float* normal_out, float* point_out, const uint16_t* query_mask) {
+    const CapsuleArgs caps{rot, half_length, point_out};
+    return trace(w, n, origin, dir, radius, &caps, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
 }
 
 }  // namespace phys

@@ -195,6 +195,12 @@ class PhysicsState:
         self._push()
         return self._world.spherecast(origins, dirs, radius, max_t, ignore, mask=mask)
 
+    def capsulecast(self, origins, dirs, radius, half_length, rot=None, max_t=None, ignore=None, mask=None):
+        """First target per moving capsule against the entities as they are now (World.capsulecast): (body index or
+        RAY_MISS / RAY_GROUND, t, normal, touched point)."""
+        self._push()
+        return self._world.capsulecast(origins, dirs, radius, half_length, rot, max_t, ignore, mask=mask)
+
     def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None, mask=None):
         """Every entity each query shape intersects, as they are now (World.overlap): (offsets, ascending ids)."""
         self._push()

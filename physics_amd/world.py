@@ -408,6 +408,54 @@ class World:
         else:
             self._ck(self.lib.phys_spherecast_device_filtered(self.h, n, *args, _device_mask(mask, n), *out))
 
+    def capsulecast(self, origins, dirs, radius, half_length, rot=None, max_t=None, ignore=None, mask=None):
+        """First target a moving capsule touches, per capsule (phys_capsulecast): origins / dirs (n, 3), radius and
+        half_length scalar or (n,), rot (n, 4) [i, j, k, w] or None (upright: the core along y), max_t (n,) or None
+        (= +inf), ignore (n,) body ids or None. Returns (body u32[n], t f32[n], normal f32[n, 3], point f32[n, 3]): t is
+        the distance the centre travelled, normal runs from the target's closest point to the capsule's core (-dir from an
+        overlap at t = 0), point is the touched point of the target's surface (zeros at t = 0 and on a miss); a miss is
+        (RAY_MISS, +inf, 0, 0). mask: as for raycast (phys_capsulecast_filtered)."""
+        o = _f(origins).reshape(-1, 3)
+        d = _f(dirs).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError("origins and dirs differ in length")
+        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)))
+        hl = np.ascontiguousarray(np.broadcast_to(np.asarray(half_length, np.float32), (n,)))
+        r = None if rot is None else _f(rot).reshape(-1, 4)
+        mt = None if max_t is None else _f(max_t).reshape(-1)
+        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.uint32).reshape(-1)
+        for a, k in ((r, 4), (mt, 1), (ig, 1)):
+            if a is not None and a.size != n * k:
+                raise ValueError("rot / max_t / ignore do not match the capsule count")
+        qm = _query_mask(mask, n)
+        body = np.empty(n, np.uint32)
+        t = np.empty(n, np.float32)
+        normal = np.empty((n, 3), np.float32)
+        point = np.empty((n, 3), np.float32)
+        if n and qm is None:
+            self._ck(self.lib.phys_capsulecast(self.h, n, _p(o), _p(d), _p(r), _p(rad), _p(hl), _p(mt), _p(ig, u32p),
+                                               _p(body, u32p), _p(t), _p(normal), _p(point)))
+        elif n:
+            self._ck(self.lib.phys_capsulecast_filtered(self.h, n, _p(o), _p(d), _p(r), _p(rad), _p(hl), _p(mt), _p(ig, u32p),
+                                                        _p(qm, u16p), _p(body, u32p), _p(t), _p(normal), _p(point)))
+        return body, t, normal, point
+
+    def capsulecast_device(self, origins, dirs, radius, half_length, body_out, t_out, normal_out=None, point_out=None, rot=None,
+                           max_t=None, ignore=None, mask=None):
+        """phys_capsulecast_device on contiguous torch tensors of the world's device, as spherecast_device; radius and
+        half_length float32 (n,), rot float32 (n, 4) or None, point_out float32 (n, 3) or None. Only enqueues on the
+        world's stream (device_view().stream)."""
+        n = int(origins.shape[0])
+        args = _device_args(n, (("origins", origins, 3), ("dirs", dirs, 3), ("rot", rot, 4), ("radius", radius, 1),
+                                ("half_length", half_length, 1), ("max_t", max_t, 1), ("ignore", ignore, 1)))
+        out = _device_args(n, (("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3),
+                               ("point_out", point_out, 3)))
+        if mask is None:
+            self._ck(self.lib.phys_capsulecast_device(self.h, n, *args, *out))
+        else:
+            self._ck(self.lib.phys_capsulecast_device_filtered(self.h, n, *args, _device_mask(mask, n), *out))
+
     def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None, cap=None, mask=None):
         """Every target each query shape intersects (phys_overlap): shape_type scalar or (n,) SHAPE_SPHERE / BOX / CAPSULE,
         pos (n, 3), rot (n, 4) [i, j, k, w] or None (identity), half_extent (3,) or (n, 3) with the bodies' conventions,

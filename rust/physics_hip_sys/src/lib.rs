@@ -190,6 +190,20 @@ extern "C" {
     pub fn phys_spherecast_device(w: *mut phys_world, n: u64, origin: *const f32, dir: *const f32, radius: *const f32,
                                   max_t: *const f32, ignore_body: *const u32, body_out: *mut u32, t_out: *mut f32,
                                   normal_out: *mut f32) -> i32;
+    pub fn phys_capsulecast(w: *mut phys_world, n: u64, origin: *const f32, dir: *const f32, rot_ijkw: *const f32, radius: *const f32,
+                            half_length: *const f32, max_t: *const f32, ignore_body: *const u32, body_out: *mut u32, t_out: *mut f32,
+                            normal_out: *mut f32, point_out: *mut f32) -> i32;
+    pub fn phys_capsulecast_device(w: *mut phys_world, n: u64, origin: *const f32, dir: *const f32, rot_ijkw: *const f32,
+                                   radius: *const f32, half_length: *const f32, max_t: *const f32, ignore_body: *const u32,
+                                   body_out: *mut u32, t_out: *mut f32, normal_out: *mut f32, point_out: *mut f32) -> i32;
+    pub fn phys_capsulecast_filtered(w: *mut phys_world, n: u64, origin: *const f32, dir: *const f32, rot_ijkw: *const f32,
+                                     radius: *const f32, half_length: *const f32, max_t: *const f32, ignore_body: *const u32,
+                                     query_mask: *const u16, body_out: *mut u32, t_out: *mut f32, normal_out: *mut f32,
+                                     point_out: *mut f32) -> i32;
+    pub fn phys_capsulecast_device_filtered(w: *mut phys_world, n: u64, origin: *const f32, dir: *const f32, rot_ijkw: *const f32,
+                                            radius: *const f32, half_length: *const f32, max_t: *const f32, ignore_body: *const u32,
+                                            query_mask: *const u16, body_out: *mut u32, t_out: *mut f32, normal_out: *mut f32,
+                                            point_out: *mut f32) -> i32;
     pub fn phys_overlap(w: *mut phys_world, n: u64, shape_type: *const u32, pos: *const f32, rot_ijkw: *const f32,
                         half_extent: *const f32, ignore_body: *const u32, cap: u64, offsets_out: *mut u64, ids_out: *mut u32) -> i32;
     pub fn phys_set_static_bodies(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32, shape_type: *const u32,
