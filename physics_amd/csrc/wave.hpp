@@ -16,7 +16,11 @@ __device__ __forceinline__ T wave_reduce(T v, Op op) {
     return v;
 }
 struct op_sum { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; } };
-// `b > a ? b : a`: a NaN operand b is ignored (constraints.hip block_amax relies on it)
+// `b > a ? b : a`: a NaN in operand b is ignored, a NaN in operand a is KEPT. In wave_reduce a is the lane's own value: a
+// lane that holds a NaN ends with NaN, and the values that would have reached another lane through it are lost to that
+// lane - a lane without NaN ends with the maximum over SOME of the wave's non-NaN lanes, its own among them, not
+// necessarily all of them (block_get then drops a wave whose lane 0 held a NaN). So these are maxima of values that are
+// never NaN: a caller folds NaN away per thread first (constraints.hip block_amax: `e > m ? e : m` from 0).
 struct op_max { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return b > a ? b : a; } };
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return wave_reduce(v, op_sum{}); }
 template <class T>  // uint32_t, int, float
