@@ -194,29 +194,12 @@ PROTOTYPES = {
     "phys_get_manifolds": (C.c_int32, [C.c_void_p, u32p, u32p, f32p, f32p, C.c_uint64, u64p]),
     "phys_get_stats": (C.c_int32, [C.c_void_p, C.POINTER(PhysStats)]),
     "phys_get_color_counts": (C.c_int32, [C.c_void_p, u32p]),
-    "phys_raycast": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, u32p, u32p, f32p, f32p]),
-    "phys_raycast_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]),
-    "phys_spherecast": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, u32p, u32p, f32p, f32p]),
-    "phys_spherecast_device": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]),
-    "phys_capsulecast": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, f32p, f32p, u32p, u32p, f32p, f32p, f32p]),
-    "phys_capsulecast_device": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 11),
-    "phys_capsulecast_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, f32p, f32p, u32p, u16p, u32p, f32p,
-                                              f32p, f32p]),
-    "phys_capsulecast_device_filtered": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 12),
     "phys_overlap": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p, f32p, u32p, C.c_uint64, u64p, u32p]),
     "phys_set_static_bodies": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, u32p, f32p]),
     "phys_set_body_filters": (C.c_int32, [C.c_void_p, C.c_uint64, u16p, u16p, i16p]),
     "phys_get_body_filters": (C.c_int32, [C.c_void_p, u16p, u16p, i16p]),
     "phys_set_static_filters": (C.c_int32, [C.c_void_p, C.c_uint64, u16p, u16p, i16p]),
     "phys_set_ground_filter": (C.c_int32, [C.c_void_p, C.c_uint16, C.c_uint16]),
-    "phys_raycast_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, u32p, u16p, u32p, f32p, f32p]),
-    "phys_raycast_device_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "phys_spherecast_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, u32p, u16p, u32p, f32p, f32p]),
-    "phys_spherecast_device_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "phys_overlap_filtered": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p, f32p, u32p, u16p, C.c_uint64, u64p, u32p]),
     "phys_set_body_materials": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p]),
     "phys_get_body_materials": (C.c_int32, [C.c_void_p, f32p, f32p]),
@@ -259,6 +242,24 @@ PROTOTYPES = {
     "phys_slab_cuts": (C.c_int32, [u64p, C.c_uint32, C.c_float, C.c_float, C.c_int32, f32p]),
     "phys_slab_owners": (C.c_int32, [f32p, C.c_uint64, f32p, C.c_int32, C.POINTER(C.c_int32)]),
 }
+
+# The casts: per kind its input arrays and its output arrays, in the order of the call (the header's names; rot and ignore
+# are its rot_ijkw and ignore_body). Every array is float32 but those of CAST_TYPES. Each kind comes four times: on host
+# arrays or on device arrays (_device: every array a c_void_p), plain or _filtered (a u16 query_mask behind the inputs).
+CASTS = {
+    "raycast": (("origin", "dir", "max_t", "ignore"), ("body_out", "t_out", "normal_out")),
+    "spherecast": (("origin", "dir", "radius", "max_t", "ignore"), ("body_out", "t_out", "normal_out")),
+    "capsulecast": (("origin", "dir", "rot", "radius", "half_length", "max_t", "ignore"),
+                    ("body_out", "t_out", "normal_out", "point_out")),
+}
+CAST_TYPES = {"ignore": u32p, "body_out": u32p}
+
+for _kind, (_ins, _outs) in CASTS.items():
+    for _device in ("", "_device"):
+        for _mask in ((), (u16p,)):
+            _args = [CAST_TYPES.get(k, f32p) for k in _ins] + list(_mask) + [CAST_TYPES.get(k, f32p) for k in _outs]
+            PROTOTYPES[f"phys_{_kind}{_device}" + ("_filtered" if _mask else "")] = (
+                C.c_int32, [C.c_void_p, C.c_uint64] + ([C.c_void_p] * len(_args) if _device else _args))
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libphysics_hip.so")
 _lib = None

@@ -221,30 +221,20 @@ static int32_t download_body_pairs(phys_world* w, const DevBuf<T>& src, std::vec
     return PHYS_OK;
 }
 
-// The device layout of a call's host arrays: a bump allocator over ONE device buffer. The call declares its arrays in order
-// (add), reserve() sizes the buffer from those declarations, copy() moves every array that is there, one hipMemcpyAsync each.
-struct Staging {
-    struct Array { void* host; size_t bytes, offset; };
-    template <typename T>
-    struct Slot { size_t offset; bool there; };  // what add() gives and at() takes: where an array of T lies, if it is there
+// A call's host arrays in ONE device buffer of the world, laid out by the call's declarations (StageLayout, staging.hpp):
+// reserve() sizes the buffer from them, copy() moves every array that is there, one hipMemcpyAsync each.
+struct Staging : StageLayout {
     phys_world* w;
     DevBuf<uint8_t>& buf;
-    Array arrays[8] = {};
-    int count = 0;
-    size_t total = 0;
-    // `n` elements at the next multiple of `align` bytes; a null array takes no room
-    template <typename T>
-    Slot<T> add(const T* host, size_t n, size_t align = alignof(T)) {
-        if (!host) return {0, false};
-        const size_t offset = (total + align - 1) / align * align;
-        arrays[count++] = {const_cast<T*>(host), n * sizeof(T), offset};
-        total = offset + n * sizeof(T);
-        return {offset, true};
+    Staging(phys_world* w, DevBuf<uint8_t>& buf) : w(w), buf(buf) {}
+    int32_t reserve() {
+        if (refused) return fail(PHYS_ERR_INVALID_ARG, "more arrays than a staging buffer holds");
+        PHYS_HIP_TRY(buf.resize(total));
+        return PHYS_OK;
     }
-    int32_t reserve() { PHYS_HIP_TRY(buf.resize(total)); return PHYS_OK; }
     // the device array of a slot, null for a null host array (valid after reserve())
     template <typename T>
-    T* at(Slot<T> s) const { return s.there ? reinterpret_cast<T*>(buf.p + s.offset) : nullptr; }
+    T* at(Slot<T> s) const { return StageLayout::at(buf.p, s); }
     int32_t copy(hipMemcpyKind kind) {
         for (int k = 0; k < count; ++k) {
             const Array& a = arrays[k];
@@ -847,162 +837,112 @@ int32_t phys_get_device_view(phys_world* w, phys_device_view* out) {
 }
 
 // ---- queries: ray casts, sphere casts, overlaps ----
-// what every cast entry point checks; `sphere`: the phys_spherecast family (radius required), phys_raycast's otherwise
-static int32_t cast_args(bool sphere, uint64_t n, const float* origin, const float* dir, const float* radius, const uint32_t* body_out,
-                         const float* t_out) {
-    if (n >= (1ull << 31))
-        return fail(PHYS_ERR_INVALID_ARG, sphere ? "phys_spherecast: n must be below 2^31" : "phys_raycast: n_rays must be below 2^31");
-    if (n && (!origin || !dir || (sphere && !radius) || !body_out || !t_out))
-        return fail(PHYS_ERR_INVALID_ARG, sphere ? "phys_spherecast: null origin, dir, radius, body_out or t_out"
-                                                 : "phys_raycast: null origin, dir, body_out or t_out");
-    return PHYS_OK;
+// casts on device arrays: checked (cast_args_error, staging.hpp), then enqueued
+static int32_t cast_device(phys_world* w, CastKind kind, const CastBatch& b) {
+    ENTER(w);
+    if (const char* bad = cast_args_error(kind, b)) return fail(PHYS_ERR_INVALID_ARG, bad);
+    if (b.n == 0) return PHYS_OK;
+    return launch_cast(w, kind, b);
 }
 
-// casts on device arrays: checked, then enqueued. radius null: rays (raycast.hip launch_trace); query_mask null: the plain call
-static int32_t cast_device(phys_world* w, bool sphere, uint64_t n, const float* origin, const float* dir, const float* radius,
-                           const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
-                           float* normal_out) {
+// casts on host arrays: staged (the inputs in w->stage, the outputs in w->rc_out), traced, read back; synchronises
+static int32_t cast_host(phys_world* w, CastKind kind, const CastBatch& b) {
     ENTER(w);
-    PHYS_TRY(cast_args(sphere, n, origin, dir, radius, body_out, t_out));
-    if (n == 0) return PHYS_OK;
-    return launch_trace(w, n, origin, dir, radius, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
-}
-
-// casts on host arrays: staged, traced, read back; synchronises
-static int32_t cast_host(phys_world* w, bool sphere, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
-                         const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out) {
-    ENTER(w);
-    PHYS_TRY(cast_args(sphere, n, origin, dir, radius, body_out, t_out));
-    if (n == 0) return PHYS_OK;
+    if (const char* bad = cast_args_error(kind, b)) return fail(PHYS_ERR_INVALID_ARG, bad);
+    if (b.n == 0) return PHYS_OK;
     Staging in{w, w->stage}, out{w, w->rc_out};
-    const auto s_origin = in.add(origin, 3 * n), s_dir = in.add(dir, 3 * n), s_radius = in.add(radius, n), s_max_t = in.add(max_t, n);
-    const auto s_ignore = in.add(ignore_body, n);
-    const auto s_mask = in.add(query_mask, n);
-    const auto s_body = out.add(body_out, n);
-    const auto s_t = out.add(t_out, n), s_normal = out.add(normal_out, 3 * n);
+    stage_cast(b, in, out);
     PHYS_TRY(in.reserve());
     PHYS_TRY(out.reserve());
     PHYS_TRY(in.copy(hipMemcpyHostToDevice));
-    PHYS_TRY(launch_trace(w, n, in.at(s_origin), in.at(s_dir), in.at(s_radius), in.at(s_max_t), in.at(s_ignore), out.at(s_body), out.at(s_t),
-                          out.at(s_normal), in.at(s_mask)));
+    PHYS_TRY(launch_cast(w, kind, staged_cast(b, in.buf.p, out.buf.p)));
     PHYS_TRY(out.copy(hipMemcpyDeviceToHost));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     return PHYS_OK;
 }
 
+// the twelve entry points: each names its kind and fills the batch from its arguments, in CastBatch's order: n, origin, dir, rot,
+// radius, half_length, max_t, ignore_body on the first line; query_mask, body_out, t_out, normal_out, point_out on the second
 int32_t phys_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                      const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    return cast_host(w, false, n_rays, origin, dir, nullptr, max_t, ignore_body, nullptr, body_out, t_out, normal_out);
+    return cast_host(w, CastKind::Ray, {n_rays, origin, dir, nullptr, nullptr, nullptr, max_t, ignore_body,
+                                        nullptr, body_out, t_out, normal_out, nullptr});
 }
 
 int32_t phys_raycast_filtered(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                               const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
                               float* normal_out) {
-    return cast_host(w, false, n_rays, origin, dir, nullptr, max_t, ignore_body, query_mask, body_out, t_out, normal_out);
+    return cast_host(w, CastKind::Ray, {n_rays, origin, dir, nullptr, nullptr, nullptr, max_t, ignore_body,
+                                        query_mask, body_out, t_out, normal_out, nullptr});
 }
 
 int32_t phys_raycast_device(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                             const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    return cast_device(w, false, n_rays, origin, dir, nullptr, max_t, ignore_body, nullptr, body_out, t_out, normal_out);
+    return cast_device(w, CastKind::Ray, {n_rays, origin, dir, nullptr, nullptr, nullptr, max_t, ignore_body,
+                                          nullptr, body_out, t_out, normal_out, nullptr});
 }
 
 int32_t phys_raycast_device_filtered(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                                      const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
                                      float* normal_out) {
-    return cast_device(w, false, n_rays, origin, dir, nullptr, max_t, ignore_body, query_mask, body_out, t_out, normal_out);
+    return cast_device(w, CastKind::Ray, {n_rays, origin, dir, nullptr, nullptr, nullptr, max_t, ignore_body,
+                                          query_mask, body_out, t_out, normal_out, nullptr});
 }
 
 int32_t phys_spherecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
                         const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    return cast_host(w, true, n, origin, dir, radius, max_t, ignore_body, nullptr, body_out, t_out, normal_out);
+    return cast_host(w, CastKind::Sphere, {n, origin, dir, nullptr, radius, nullptr, max_t, ignore_body,
+                                           nullptr, body_out, t_out, normal_out, nullptr});
 }
 
 int32_t phys_spherecast_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius,
                                  const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out,
                                  float* t_out, float* normal_out) {
-    return cast_host(w, true, n, origin, dir, radius, max_t, ignore_body, query_mask, body_out, t_out, normal_out);
+    return cast_host(w, CastKind::Sphere, {n, origin, dir, nullptr, radius, nullptr, max_t, ignore_body,
+                                           query_mask, body_out, t_out, normal_out, nullptr});
 }
 
 int32_t phys_spherecast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
                                const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    return cast_device(w, true, n, origin, dir, radius, max_t, ignore_body, nullptr, body_out, t_out, normal_out);
+    return cast_device(w, CastKind::Sphere, {n, origin, dir, nullptr, radius, nullptr, max_t, ignore_body,
+                                             nullptr, body_out, t_out, normal_out, nullptr});
 }
 
 int32_t phys_spherecast_device_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius,
                                         const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask,
                                         uint32_t* body_out, float* t_out, float* normal_out) {
-    return cast_device(w, true, n, origin, dir, radius, max_t, ignore_body, query_mask, body_out, t_out, normal_out);
+    return cast_device(w, CastKind::Sphere, {n, origin, dir, nullptr, radius, nullptr, max_t, ignore_body,
+                                             query_mask, body_out, t_out, normal_out, nullptr});
 }
 
-// ---- capsule casts: the casts' checks and staging with rot, half_length and point_out besides ----
-static int32_t capsulecast_args(uint64_t n, const float* origin, const float* dir, const float* radius, const float* half_length,
-                                const uint32_t* body_out, const float* t_out) {
-    if (n >= (1ull << 31)) return fail(PHYS_ERR_INVALID_ARG, "phys_capsulecast: n must be below 2^31");
-    if (n && (!origin || !dir || !radius || !half_length || !body_out || !t_out))
-        return fail(PHYS_ERR_INVALID_ARG, "phys_capsulecast: null origin, dir, radius, half_length, body_out or t_out");
-    return PHYS_OK;
-}
-
-static int32_t capsulecast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
-                                  const float* radius, const float* half_length, const float* max_t, const uint32_t* ignore_body,
-                                  const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out, float* point_out) {
-    ENTER(w);
-    PHYS_TRY(capsulecast_args(n, origin, dir, radius, half_length, body_out, t_out));
-    if (n == 0) return PHYS_OK;
-    return launch_capsulecast(w, n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body, body_out, t_out, normal_out, point_out,
-                              query_mask);
-}
-
-static int32_t capsulecast_host(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw, const float* radius,
-                                const float* half_length, const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask,
-                                uint32_t* body_out, float* t_out, float* normal_out, float* point_out) {
-    ENTER(w);
-    PHYS_TRY(capsulecast_args(n, origin, dir, radius, half_length, body_out, t_out));
-    if (n == 0) return PHYS_OK;
-    Staging in{w, w->stage}, out{w, w->rc_out};
-    const auto s_origin = in.add(origin, 3 * n), s_dir = in.add(dir, 3 * n), s_rot = in.add(rot_ijkw, 4 * n);
-    const auto s_radius = in.add(radius, n), s_half = in.add(half_length, n), s_max_t = in.add(max_t, n);
-    const auto s_ignore = in.add(ignore_body, n);
-    const auto s_mask = in.add(query_mask, n);
-    const auto s_body = out.add(body_out, n);
-    const auto s_t = out.add(t_out, n), s_normal = out.add(normal_out, 3 * n), s_point = out.add(point_out, 3 * n);
-    PHYS_TRY(in.reserve());
-    PHYS_TRY(out.reserve());
-    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
-    PHYS_TRY(launch_capsulecast(w, n, in.at(s_origin), in.at(s_dir), in.at(s_rot), in.at(s_radius), in.at(s_half), in.at(s_max_t),
-                                in.at(s_ignore), out.at(s_body), out.at(s_t), out.at(s_normal), out.at(s_point), in.at(s_mask)));
-    PHYS_TRY(out.copy(hipMemcpyDeviceToHost));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    return PHYS_OK;
-}
-
+// capsule casts: rot, half_length and point_out besides
 int32_t phys_capsulecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw, const float* radius,
                          const float* half_length, const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out,
                          float* normal_out, float* point_out) {
-    return capsulecast_host(w, n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body, nullptr, body_out, t_out, normal_out,
-                            point_out);
+    return cast_host(w, CastKind::Capsule, {n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body,
+                                            nullptr, body_out, t_out, normal_out, point_out});
 }
 
 int32_t phys_capsulecast_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
                                   const float* radius, const float* half_length, const float* max_t, const uint32_t* ignore_body,
                                   const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out, float* point_out) {
-    return capsulecast_host(w, n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body, query_mask, body_out, t_out, normal_out,
-                            point_out);
+    return cast_host(w, CastKind::Capsule, {n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body,
+                                            query_mask, body_out, t_out, normal_out, point_out});
 }
 
 int32_t phys_capsulecast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
                                 const float* radius, const float* half_length, const float* max_t, const uint32_t* ignore_body,
                                 uint32_t* body_out, float* t_out, float* normal_out, float* point_out) {
-    return capsulecast_device(w, n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body, nullptr, body_out, t_out, normal_out,
-                              point_out);
+    return cast_device(w, CastKind::Capsule, {n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body,
+                                              nullptr, body_out, t_out, normal_out, point_out});
 }
 
 int32_t phys_capsulecast_device_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
                                          const float* radius, const float* half_length, const float* max_t, const uint32_t* ignore_body,
                                          const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out,
                                          float* point_out) {
-    return capsulecast_device(w, n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body, query_mask, body_out, t_out, normal_out,
-                              point_out);
+    return cast_device(w, CastKind::Capsule, {n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body,
+                                              query_mask, body_out, t_out, normal_out, point_out});
 }
 
 static int32_t overlap_host(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,

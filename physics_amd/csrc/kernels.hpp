@@ -13,6 +13,7 @@
 #include "world.hpp"
 #include "readout.hpp"
 #include "records.hpp"
+#include "staging.hpp"
 #include "wave.hpp"
 
 static_assert(PHYS_MAX_COLORS == phys::kMaxColors, "colour limit mismatch");
@@ -180,6 +181,10 @@ struct QueryFilters {
     const uint2* st;             // per static collider
     uint32_t ground;             // the ground's category
 };
+// ... of world `w`, for the queries whose masks are the device array query_mask
+inline QueryFilters query_filters(const phys_world* w, const uint16_t* query_mask) {
+    return {query_mask, reinterpret_cast<const uint2*>(w->filt.p), reinterpret_cast<const uint2*>(w->st_filt.p), w->ground_filt & 0xFFFFu};
+}
 // the one filter argument of a filtered kernel instance. The filter arguments travel as a parameter pack that is empty in
 // the unfiltered instance, so that instance keeps the kernel arguments - and with them the offsets of the hidden
 // arguments it reads - and compiles to the instructions it had before filters.
@@ -378,21 +383,15 @@ int32_t static_set(phys_world* w, uint64_t n, const float* pos, const float* rot
 int32_t launch_static_pairs(phys_world* w);
 void static_narrow_args(const phys_world* w, uint64_t* cap, const uint32_t** pairs, const float** geo);
 
-// raycast.hip: builds the query's grid from the current poses and traces the rays (device pointers), all on w->stream; with
-// radius, the same walk for balls of radius[i] (the grid grown by the largest valid radius)
-int32_t launch_trace(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* radius /* null: rays */,
-                     const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out,
-                     const uint16_t* query_mask /* device, n_rays; null: no filtering */);
-// the same walk for capsules (phys_capsulecast): core origin +- half_length * (rot's y axis), radius[i];
-// the grid grown by the largest valid radius + half_length. rot (4 per query), normal_out and point_out may be null.
-int32_t launch_capsulecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot, const float* radius,
-                           const float* half_length, const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out,
-                           float* normal_out, float* point_out, const uint16_t* query_mask /* device, n; null: no filtering */);
-// the query grid alone (rc_header, rc_start, rc_records), every body AABB grown by the largest valid value of the device
-// array grow_radius (null: not grown), plus grow_half_length's of the same query where that is given (a capsule reaches
-// radius + half_length from its centre); *bits = log2 of the bucket table
-int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_radius, uint32_t* bits,
-                          const float* grow_half_length = nullptr);
+// raycast.hip: builds the query's grid from the current poses and walks it for the batch's queries (device pointers, CastBatch:
+// staging.hpp), all on w->stream. Ray: radius unused. Sphere: balls of radius[i], the grid grown by the largest valid radius.
+// Capsule: core origin +- half_length * (rot's y axis), radius[i], the grid grown by the largest valid
+// radius + half_length; rot and point_out are read for this kind alone. A query_mask makes it the filtered instance.
+int32_t launch_cast(phys_world* w, CastKind kind, const CastBatch& b);
+// the query grid alone (rc_header, rc_start, rc_records), every body AABB grown by the largest valid value of the n_grow
+// values of the device array grow_radius (null: not grown), plus grow_half_length's of the same query where that is given (a
+// capsule reaches radius + half_length from its centre); *bits = log2 of the bucket table
+int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* grow_half_length, uint64_t n_grow, uint32_t* bits);
 // query.hip: overlap queries on staged device arrays; writes the host offsets (n + 1) and, when they fit in cap, the ids
 int32_t launch_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot, const float* half_extent,
                        const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out,

@@ -178,7 +178,7 @@ int32_t launch_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, co
                        const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out, const uint16_t* query_mask) {
     hipStream_t s = w->stream;
     uint32_t bits = 12;
-    int32_t rc = launch_query_grid(w, nullptr, 0, &bits); if (rc) return rc;
+    int32_t rc = launch_query_grid(w, nullptr, nullptr, 0, &bits); if (rc) return rc;
     const RcHeader* hdr = reinterpret_cast<const RcHeader*>(w->rc_header.p);
     PHYS_HIP_TRY(w->qr_count.resize(n));
     PHYS_HIP_TRY(w->qr_off.resize(n + 1));
@@ -187,11 +187,7 @@ int32_t launch_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, co
     const uint32_t nb = (uint32_t)w->n_owned;
     const float4* st = reinterpret_cast<const float4*>(w->st_rc.p);
     const float4* rec = reinterpret_cast<const float4*>(w->rc_records.p);
-    QueryFilters qf{};
-    qf.query_mask = query_mask;
-    qf.body = reinterpret_cast<const uint2*>(w->filt.p);
-    qf.st = reinterpret_cast<const uint2*>(w->st_filt.p);
-    qf.ground = w->ground_filt & 0xFFFFu;
+    const QueryFilters qf = query_filters(w, query_mask);
     // (the filtered instances take `qf` as one more argument; the unfiltered ones are launched exactly as before filters)
 #define PHYS_OV_LAUNCH(FILL, FILT, count, offsets, ids, ...)                                                                 \
     hipLaunchKernelGGL((k_ov_query<FILL, FILT>), dim3(blocks), dim3(kOvThreads), 0, s, (uint32_t)n, shape_type, pos, rot, half_extent, \

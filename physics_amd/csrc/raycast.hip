@@ -458,7 +458,7 @@ __global__ __launch_bounds__(kRcThreads) void k_sc_grow(uint32_t n, const float*
 
 unsigned rc_blocks(uint64_t n) { return (unsigned)((n + kRcThreads - 1) / kRcThreads); }
 
-int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_radius, uint32_t* bits_out, const float* grow_half_length) {
+int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* grow_half_length, uint64_t n_grow, uint32_t* bits_out) {
     hipStream_t s = w->stream;
     const uint64_t n = w->n_owned;
     PHYS_HIP_TRY(w->rc_header.resize(sizeof(RcHeader) / 4));
@@ -476,9 +476,9 @@ int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_ra
         PHYS_HIP_TRY(w->rc_records.resize(12 * 8 * (size_t)n));  // 8 records of three float4 per body
         PHYS_HIP_TRY(hipMemsetAsync(w->rc_count.p, 0, 4 * (size_t)table, s));
         const uint32_t nn = (uint32_t)n;
-        if (grow_radius && n_radius)
-            hipLaunchKernelGGL(k_sc_grow, dim3(std::min<unsigned>(rc_blocks(n_radius), kRcMaxBoundsBlocks)), dim3(kRcThreads), 0, s,
-                               (uint32_t)n_radius, grow_radius, grow_half_length, reinterpret_cast<RcHeader*>(w->rc_header.p));
+        if (grow_radius && n_grow)
+            hipLaunchKernelGGL(k_sc_grow, dim3(std::min<unsigned>(rc_blocks(n_grow), kRcMaxBoundsBlocks)), dim3(kRcThreads), 0, s,
+                               (uint32_t)n_grow, grow_radius, grow_half_length, reinterpret_cast<RcHeader*>(w->rc_header.p));
         const unsigned bb = std::min<unsigned>(rc_blocks(n), kRcMaxBoundsBlocks);
         hipLaunchKernelGGL(k_rc_bounds, dim3(bb), dim3(kRcThreads), 0, s, nn, w->pos.p, w->rot.p, w->half_extent.p, w->shape.p,
                            reinterpret_cast<RcHeader*>(w->rc_header.p));
@@ -495,14 +495,15 @@ int32_t launch_query_grid(phys_world* w, const float* grow_radius, uint64_t n_ra
     return PHYS_OK;
 }
 
-// the walk shared by ray casts (radius == nullptr), sphere casts and capsule casts (caps != nullptr)
-static int32_t trace(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* radius, const CapsuleArgs* caps,
-                     const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out,
-                     const uint16_t* query_mask) {
+// the walk shared by ray casts, sphere casts and capsule casts: the kind names the kernel instance, the arrays are the batch's
+int32_t launch_cast(phys_world* w, CastKind kind, const CastBatch& b) {
     hipStream_t s = w->stream;
     const uint64_t n = w->n_owned;
+    const bool sweep = kind != CastKind::Ray, capsule = kind == CastKind::Capsule;
+    const float* radius = sweep ? b.radius : nullptr;
+    const CapsuleArgs caps{b.rot, b.half_length, b.point_out};
     uint32_t bits = 12;
-    int32_t rc = launch_query_grid(w, radius, radius ? n_rays : 0, &bits, caps ? caps->half_length : nullptr); if (rc) return rc;
+    PHYS_TRY(launch_query_grid(w, radius, capsule ? b.half_length : nullptr, sweep ? b.n : 0, &bits));
     const RcHeader* hdr = reinterpret_cast<const RcHeader*>(w->rc_header.p);
     const bool stats = debug_switches().raycast_stats;
     if (stats) {
@@ -510,27 +511,23 @@ static int32_t trace(phys_world* w, uint64_t n_rays, const float* origin, const 
         PHYS_HIP_TRY(hipMemsetAsync(w->rc_stats.p, 0, 16, s));
     }
     const int ground = (w->cfg.flags & PHYS_FLAG_GROUND_PLANE) ? 1 : 0;
-    QueryFilters qf{};
-    qf.query_mask = query_mask;
-    qf.body = reinterpret_cast<const uint2*>(w->filt.p);
-    qf.st = reinterpret_cast<const uint2*>(w->st_filt.p);
-    qf.ground = w->ground_filt & 0xFFFFu;
+    const QueryFilters qf = query_filters(w, b.query_mask);
 #define PHYS_RC_LAUNCH(SW, FILT, ...)                                                                                        \
-    hipLaunchKernelGGL((k_rc_trace<kSt, SW, FILT>), dim3(rc_blocks(n_rays)), dim3(kRcThreads), 0, s, (uint32_t)n_rays, origin, dir,   \
-                       radius, max_t, ignore_body, hdr, bits, (const uint32_t*)w->rc_start.p,                                      \
+    hipLaunchKernelGGL((k_rc_trace<kSt, SW, FILT>), dim3(rc_blocks(b.n)), dim3(kRcThreads), 0, s, (uint32_t)b.n, b.origin, b.dir,   \
+                       radius, b.max_t, b.ignore_body, hdr, bits, (const uint32_t*)w->rc_start.p,                                  \
                        reinterpret_cast<const float4*>(w->rc_records.p), (uint32_t)n, ground, w->cfg.ground_height,               \
-                       reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static, body_out, t_out, normal_out,           \
+                       reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static, b.body_out, b.t_out, b.normal_out,     \
                        w->rc_stats.p, ##__VA_ARGS__)
     dispatch_bool(stats, [&](auto st) {
         constexpr bool kSt = decltype(st)::value;
-        if (caps) {
-            if (query_mask) PHYS_RC_LAUNCH(true, true, *caps, qf);
-            else PHYS_RC_LAUNCH(true, false, *caps);
+        if (capsule) {
+            if (b.query_mask) PHYS_RC_LAUNCH(true, true, caps, qf);
+            else PHYS_RC_LAUNCH(true, false, caps);
             return;
         }
-        dispatch_bool(radius != nullptr, [&](auto sw) {
+        dispatch_bool(sweep, [&](auto sw) {
             constexpr bool kSw = decltype(sw)::value;
-            if (query_mask) PHYS_RC_LAUNCH(kSw, true, qf);
+            if (b.query_mask) PHYS_RC_LAUNCH(kSw, true, qf);
             else PHYS_RC_LAUNCH(kSw, false);
         });
     });
@@ -541,22 +538,10 @@ static int32_t trace(phys_world* w, uint64_t n_rays, const float* origin, const 
         PHYS_HIP_TRY(hipMemcpyAsync(h, w->rc_stats.p, 16, hipMemcpyDeviceToHost, s));
         PHYS_HIP_TRY(hipStreamSynchronize(s));
         fprintf(stderr, "%s rays=%llu cells=%llu candidates=%llu\n",
-                caps ? "PHYS_CAPSULECAST_STATS" : (radius ? "PHYS_SPHERECAST_STATS" : "PHYS_RAYCAST_STATS"),
-                (unsigned long long)n_rays, h[0], h[1]);
+                capsule ? "PHYS_CAPSULECAST_STATS" : (sweep ? "PHYS_SPHERECAST_STATS" : "PHYS_RAYCAST_STATS"),
+                (unsigned long long)b.n, h[0], h[1]);
     }
     return PHYS_OK;
-}
-
-int32_t launch_trace(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* radius, const float* max_t,
-                     const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out, const uint16_t* query_mask) {
-    return trace(w, n_rays, origin, dir, radius, nullptr, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
-}
-
-int32_t launch_capsulecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot, const float* radius,
-                           const float* half_length, const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out,
-                           float* normal_out, float* point_out, const uint16_t* query_mask) {
-    const CapsuleArgs caps{rot, half_length, point_out};
-    return trace(w, n, origin, dir, radius, &caps, max_t, ignore_body, body_out, t_out, normal_out, query_mask);
 }
 
 }  // namespace phys

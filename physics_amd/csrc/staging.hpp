@@ -1,0 +1,92 @@
+// staging.hpp — how a query call describes its arrays: the batch of one cast (rays, balls, capsules alike), what the cast entry
+// points check of it, and where a call's host arrays lie in the one device buffer they are staged in. Host-only like setup.hpp
+// (no HIP, no phys_world), held to tests/cpp/staging_probe.cpp. abi.hip keeps the buffer, the copies and the launch.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace phys {
+
+enum class CastKind { Ray, Sphere, Capsule };
+
+// the arrays of one cast call, n queries; host pointers or device pointers alike
+struct CastBatch {
+    uint64_t n;
+    const float *origin, *dir;         // 3 per query
+    const float* rot;                  // capsules: [i, j, k, w] per query; null: identity
+    const float *radius, *half_length; // balls and capsules; capsules
+    const float* max_t;                // null: +inf
+    const uint32_t* ignore_body;       // null: none
+    const uint16_t* query_mask;        // null: the plain call, otherwise the _filtered one
+    uint32_t* body_out;
+    float* t_out;
+    float *normal_out, *point_out;     // 3 per query; null: not wanted (point_out: capsules)
+};
+
+// Every array of a cast once, in the order they are staged: f(member, elements per query, is it an output). The inputs and
+// the outputs go to a buffer each, so only the order within each group is layout.
+template <class Batch, class F>
+inline void for_each_cast_array(Batch& b, F&& f) {
+    f(b.origin, 3, false); f(b.dir, 3, false); f(b.rot, 4, false); f(b.radius, 1, false); f(b.half_length, 1, false);
+    f(b.max_t, 1, false); f(b.ignore_body, 1, false); f(b.query_mask, 1, false);
+    f(b.body_out, 1, true); f(b.t_out, 1, true); f(b.normal_out, 3, true); f(b.point_out, 3, true);
+}
+
+// what every cast entry point checks before it touches anything: the text of the refusal, null when the call may go on.
+// Each family names its own required arrays; everything else is optional.
+inline const char* cast_args_error(CastKind kind, const CastBatch& b) {
+    static const char* const too_many[] = {"phys_raycast: n_rays must be below 2^31", "phys_spherecast: n must be below 2^31",
+                                           "phys_capsulecast: n must be below 2^31"};
+    static const char* const null_array[] = {"phys_raycast: null origin, dir, body_out or t_out",
+                                             "phys_spherecast: null origin, dir, radius, body_out or t_out",
+                                             "phys_capsulecast: null origin, dir, radius, half_length, body_out or t_out"};
+    if (b.n >= (1ull << 31)) return too_many[(int)kind];
+    const bool missing = !b.origin || !b.dir || (kind != CastKind::Ray && !b.radius) || (kind == CastKind::Capsule && !b.half_length) ||
+                         !b.body_out || !b.t_out;
+    return b.n && missing ? null_array[(int)kind] : nullptr;
+}
+
+// The layout of a call's host arrays in ONE device buffer: a bump allocator. The call declares its arrays in order (add);
+// `total` is then the size of the buffer, and at() gives each array's place in it.
+struct StageLayout {
+    static constexpr int kMaxArrays = 8;
+    struct Array { void* host; size_t bytes, offset; };
+    template <typename T>
+    struct Slot { int index; };  // what add() gives and at() takes: which array of T, -1 when it is not there
+    Array arrays[kMaxArrays] = {};
+    int count = 0;
+    size_t total = 0;
+    bool refused = false;  // an array beyond kMaxArrays was declared: the call fails (abi.hip Staging::reserve), nothing is written
+    // `n` elements at the next multiple of `align` bytes; a null array takes no room
+    template <typename T>
+    Slot<T> add(const T* host, size_t n, size_t align = alignof(T)) {
+        if (!host) return {-1};
+        if (count == kMaxArrays) { refused = true; return {-1}; }
+        const size_t offset = (total + align - 1) / align * align;
+        arrays[count] = {const_cast<T*>(host), n * sizeof(T), offset};
+        total = offset + n * sizeof(T);
+        return {count++};
+    }
+    // the device array of a slot in the buffer at `base`, null for a null host array
+    template <typename T>
+    T* at(uint8_t* base, Slot<T> s) const {
+        return s.index >= 0 && s.index < count ? reinterpret_cast<T*>(base + arrays[s.index].offset) : nullptr;
+    }
+};
+
+// a cast on host arrays declares them: the inputs in one buffer, the outputs in another ...
+inline void stage_cast(const CastBatch& host, StageLayout& in, StageLayout& out) {
+    for_each_cast_array(host, [&](auto* array, size_t per_query, bool output) { (output ? out : in).add(array, per_query * host.n); });
+}
+// ... and is the same batch on the device once the two buffers are there: the same declarations again, over their bases
+inline CastBatch staged_cast(const CastBatch& host, uint8_t* in_base, uint8_t* out_base) {
+    CastBatch dev = host;
+    StageLayout in, out;
+    for_each_cast_array(dev, [&](auto*& array, size_t per_query, bool output) {
+        StageLayout& l = output ? out : in;
+        array = l.at(output ? out_base : in_base, l.add(array, per_query * host.n));
+    });
+    return dev;
+}
+
+}  // namespace phys

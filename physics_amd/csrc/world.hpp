@@ -259,9 +259,9 @@ struct phys_world {
     phys::DevBuf<uint32_t> rc_start;     // table + 1: exclusive scan of rc_count
     phys::DevBuf<uint32_t> rc_tile_sum;  // the scan's own scratch (scan_block_sums is the update's)
     phys::DevBuf<float> rc_records;      // 8N records of 48 bytes {centre, shape} {rot} {half extent, id}, bucket order
-    // the queries on host arrays (phys_raycast, phys_spherecast, phys_overlap): ONE staging buffer for the inputs of whichever
-    // runs - each synchronises the stream before it returns, so no two are ever in flight - laid out by the call's own
-    // declarations (abi.hip Staging); the casts' outputs body | t | normal the same way
+    // the queries on host arrays (phys_raycast, phys_spherecast, phys_capsulecast, phys_overlap): ONE staging buffer for the
+    // inputs of whichever runs - each synchronises the stream before it returns, so no two are ever in flight - laid out by the
+    // call's own declarations (staging.hpp StageLayout); the casts' outputs body | t | normal | point the same way
     phys::DevBuf<uint8_t> stage, rc_out;
     phys::DevBuf<unsigned long long> rc_stats;  // PHYS_DEBUG_RAYCAST_STATS: cells, candidates
     // overlap queries (query.hip): they walk the grid above; their own output

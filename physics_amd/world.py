@@ -69,6 +69,14 @@ def _field_law_check(kind, coef):
         raise ValueError("coef: a RADIAL field's r0 (coef[1]) must be above 0")
 
 
+# the arrays of the casts (the names of _abi.CASTS): numpy dtype and columns per query
+_CAST_ARRAYS = {
+    "origin": (np.float32, 3), "dir": (np.float32, 3), "rot": (np.float32, 4), "radius": (np.float32, 1),
+    "half_length": (np.float32, 1), "max_t": (np.float32, 1), "ignore": (np.uint32, 1),
+    "body_out": (np.uint32, 1), "t_out": (np.float32, 1), "normal_out": (np.float32, 3), "point_out": (np.float32, 3),
+}
+
+
 def _query_mask(mask, n):
     """The per-query mask of a _filtered query: a scalar or (n,) integers in [0, 0xFFFF]."""
     return _filter_field(mask, n, "mask", 0, 0xFFFF, np.uint16)
@@ -329,84 +337,71 @@ class World:
         self._ck(self.lib.phys_get_aabbs(self.h, _p(out)))
         return out
 
+    def _cast(self, call, noun, origins, dirs, per_query, optional, mask):
+        """The casts on host arrays (raycast, spherecast, capsulecast). per_query: name -> scalar or (n,) values; optional:
+        name -> array or None; the names are those of _CAST_ARRAYS and of _abi.CASTS[call], which orders the arguments.
+        Returns the call's outputs."""
+        ins, outs = _abi.CASTS[call]
+        a = {"origin": _f(origins).reshape(-1, 3), "dir": _f(dirs).reshape(-1, 3)}
+        n = a["origin"].shape[0]
+        if a["dir"].shape[0] != n:
+            raise ValueError("origins and dirs differ in length")
+        for k, v in per_query.items():
+            a[k] = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32), (n,)))
+        for k, v in optional.items():
+            dtype, cols = _CAST_ARRAYS[k]
+            a[k] = None if v is None else np.ascontiguousarray(v, dtype=dtype).reshape(-1, cols)
+        for k in optional:
+            if a[k] is not None and a[k].size != n * _CAST_ARRAYS[k][1]:
+                raise ValueError(f"{' / '.join(optional)} do not match the {noun} count")
+        qm = _query_mask(mask, n)
+        for k in outs:
+            dtype, cols = _CAST_ARRAYS[k]
+            a[k] = np.empty(n if cols == 1 else (n, cols), dtype)
+        if n:
+            ptr = {k: _p(v, _abi.CAST_TYPES.get(k, f32p)) for k, v in a.items()}
+            fn = getattr(self.lib, f"phys_{call}" if qm is None else f"phys_{call}_filtered")
+            self._ck(fn(self.h, n, *(ptr[k] for k in ins), *(() if qm is None else (_p(qm, u16p),)), *(ptr[k] for k in outs)))
+        return tuple(a[k] for k in outs)
+
+    def _cast_device(self, call, origins, inputs, outputs, mask):
+        """The casts on device tensors: inputs and outputs as _device_args takes them, in the order of the call."""
+        n = int(origins.shape[0])
+        args = _device_args(n, inputs)
+        out = _device_args(n, outputs)
+        if mask is None:
+            self._ck(getattr(self.lib, f"phys_{call}_device")(self.h, n, *args, *out))
+        else:
+            self._ck(getattr(self.lib, f"phys_{call}_device_filtered")(self.h, n, *args, _device_mask(mask, n), *out))
+
     def raycast(self, origins, dirs, max_t=None, ignore=None, mask=None):
         """Closest hit of every ray against the current poses (phys_raycast): origins / dirs (n, 3), max_t (n,) or None
         (= +inf), ignore (n,) body ids or None. Returns (body u32[n], t f32[n], normal f32[n, 3]); a miss is
         (RAY_MISS, +inf, 0), the ground RAY_GROUND. mask (scalar or (n,) u16): only targets whose filter category meets
         it are seen (phys_raycast_filtered); None: every target."""
-        o = _f(origins).reshape(-1, 3)
-        d = _f(dirs).reshape(-1, 3)
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError("origins and dirs differ in length")
-        mt = None if max_t is None else _f(max_t).reshape(-1)
-        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.uint32).reshape(-1)
-        for a in (mt, ig):
-            if a is not None and a.size != n:
-                raise ValueError("max_t / ignore do not match the ray count")
-        qm = _query_mask(mask, n)
-        body = np.empty(n, np.uint32)
-        t = np.empty(n, np.float32)
-        normal = np.empty((n, 3), np.float32)
-        if n and qm is None:
-            self._ck(self.lib.phys_raycast(self.h, n, _p(o), _p(d), _p(mt), _p(ig, u32p), _p(body, u32p), _p(t), _p(normal)))
-        elif n:
-            self._ck(self.lib.phys_raycast_filtered(self.h, n, _p(o), _p(d), _p(mt), _p(ig, u32p), _p(qm, u16p), _p(body, u32p),
-                                                    _p(t), _p(normal)))
-        return body, t, normal
+        return self._cast("raycast", "ray", origins, dirs, {}, {"max_t": max_t, "ignore": ignore}, mask)
 
     def raycast_device(self, origins, dirs, body_out, t_out, normal_out=None, max_t=None, ignore=None, mask=None):
         """phys_raycast_device on contiguous torch tensors of the world's device: origins / dirs float32 (n, 3), body_out
         int32 or uint32 (n,), t_out float32 (n,), normal_out float32 (n, 3) or None, max_t float32 (n,) or None, ignore
         int32 / uint32 (n,) or None, mask int16 / uint16 (n,) or None (phys_raycast_device_filtered). Only enqueues on
         the world's stream (device_view().stream): order other streams' work against it yourself."""
-        n = int(origins.shape[0])
-        args = _device_args(n, (("origins", origins, 3), ("dirs", dirs, 3), ("max_t", max_t, 1), ("ignore", ignore, 1)))
-        out = _device_args(n, (("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3)))
-        if mask is None:
-            self._ck(self.lib.phys_raycast_device(self.h, n, *args, *out))
-        else:
-            self._ck(self.lib.phys_raycast_device_filtered(self.h, n, *args, _device_mask(mask, n), *out))
+        self._cast_device("raycast", origins, (("origins", origins, 3), ("dirs", dirs, 3), ("max_t", max_t, 1), ("ignore", ignore, 1)),
+                          (("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3)), mask)
 
     def spherecast(self, origins, dirs, radius, max_t=None, ignore=None, mask=None):
         """First target a moving ball touches, per ball (phys_spherecast): origins / dirs (n, 3), radius scalar or (n,),
         max_t (n,) or None (= +inf), ignore (n,) body ids or None. Returns (body u32[n], t f32[n], normal f32[n, 3]): t is
         the distance the centre travelled, normal the target's outward normal at the contact (-dir from an overlap at t = 0);
         a miss is (RAY_MISS, +inf, 0). mask: as for raycast (phys_spherecast_filtered)."""
-        o = _f(origins).reshape(-1, 3)
-        d = _f(dirs).reshape(-1, 3)
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError("origins and dirs differ in length")
-        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)))
-        mt = None if max_t is None else _f(max_t).reshape(-1)
-        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.uint32).reshape(-1)
-        for a in (mt, ig):
-            if a is not None and a.size != n:
-                raise ValueError("max_t / ignore do not match the ball count")
-        qm = _query_mask(mask, n)
-        body = np.empty(n, np.uint32)
-        t = np.empty(n, np.float32)
-        normal = np.empty((n, 3), np.float32)
-        if n and qm is None:
-            self._ck(self.lib.phys_spherecast(self.h, n, _p(o), _p(d), _p(rad), _p(mt), _p(ig, u32p), _p(body, u32p), _p(t),
-                                              _p(normal)))
-        elif n:
-            self._ck(self.lib.phys_spherecast_filtered(self.h, n, _p(o), _p(d), _p(rad), _p(mt), _p(ig, u32p), _p(qm, u16p),
-                                                       _p(body, u32p), _p(t), _p(normal)))
-        return body, t, normal
+        return self._cast("spherecast", "ball", origins, dirs, {"radius": radius}, {"max_t": max_t, "ignore": ignore}, mask)
 
     def spherecast_device(self, origins, dirs, radius, body_out, t_out, normal_out=None, max_t=None, ignore=None, mask=None):
         """phys_spherecast_device on contiguous torch tensors of the world's device, as raycast_device; radius float32 (n,).
         Only enqueues on the world's stream (device_view().stream)."""
-        n = int(origins.shape[0])
-        args = _device_args(n, (("origins", origins, 3), ("dirs", dirs, 3), ("radius", radius, 1), ("max_t", max_t, 1),
-                                ("ignore", ignore, 1)))
-        out = _device_args(n, (("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3)))
-        if mask is None:
-            self._ck(self.lib.phys_spherecast_device(self.h, n, *args, *out))
-        else:
-            self._ck(self.lib.phys_spherecast_device_filtered(self.h, n, *args, _device_mask(mask, n), *out))
+        self._cast_device("spherecast", origins, (("origins", origins, 3), ("dirs", dirs, 3), ("radius", radius, 1), ("max_t", max_t, 1),
+                                                  ("ignore", ignore, 1)),
+                          (("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3)), mask)
 
     def capsulecast(self, origins, dirs, radius, half_length, rot=None, max_t=None, ignore=None, mask=None):
         """First target a moving capsule touches, per capsule (phys_capsulecast): origins / dirs (n, 3), radius and
@@ -415,46 +410,18 @@ class World:
         the distance the centre travelled, normal runs from the target's closest point to the capsule's core (-dir from an
         overlap at t = 0), point is the touched point of the target's surface (zeros at t = 0 and on a miss); a miss is
         (RAY_MISS, +inf, 0, 0). mask: as for raycast (phys_capsulecast_filtered)."""
-        o = _f(origins).reshape(-1, 3)
-        d = _f(dirs).reshape(-1, 3)
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError("origins and dirs differ in length")
-        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)))
-        hl = np.ascontiguousarray(np.broadcast_to(np.asarray(half_length, np.float32), (n,)))
-        r = None if rot is None else _f(rot).reshape(-1, 4)
-        mt = None if max_t is None else _f(max_t).reshape(-1)
-        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.uint32).reshape(-1)
-        for a, k in ((r, 4), (mt, 1), (ig, 1)):
-            if a is not None and a.size != n * k:
-                raise ValueError("rot / max_t / ignore do not match the capsule count")
-        qm = _query_mask(mask, n)
-        body = np.empty(n, np.uint32)
-        t = np.empty(n, np.float32)
-        normal = np.empty((n, 3), np.float32)
-        point = np.empty((n, 3), np.float32)
-        if n and qm is None:
-            self._ck(self.lib.phys_capsulecast(self.h, n, _p(o), _p(d), _p(r), _p(rad), _p(hl), _p(mt), _p(ig, u32p),
-                                               _p(body, u32p), _p(t), _p(normal), _p(point)))
-        elif n:
-            self._ck(self.lib.phys_capsulecast_filtered(self.h, n, _p(o), _p(d), _p(r), _p(rad), _p(hl), _p(mt), _p(ig, u32p),
-                                                        _p(qm, u16p), _p(body, u32p), _p(t), _p(normal), _p(point)))
-        return body, t, normal, point
+        return self._cast("capsulecast", "capsule", origins, dirs, {"radius": radius, "half_length": half_length},
+                          {"rot": rot, "max_t": max_t, "ignore": ignore}, mask)
 
     def capsulecast_device(self, origins, dirs, radius, half_length, body_out, t_out, normal_out=None, point_out=None, rot=None,
                            max_t=None, ignore=None, mask=None):
         """phys_capsulecast_device on contiguous torch tensors of the world's device, as spherecast_device; radius and
         half_length float32 (n,), rot float32 (n, 4) or None, point_out float32 (n, 3) or None. Only enqueues on the
         world's stream (device_view().stream)."""
-        n = int(origins.shape[0])
-        args = _device_args(n, (("origins", origins, 3), ("dirs", dirs, 3), ("rot", rot, 4), ("radius", radius, 1),
-                                ("half_length", half_length, 1), ("max_t", max_t, 1), ("ignore", ignore, 1)))
-        out = _device_args(n, (("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3),
-                               ("point_out", point_out, 3)))
-        if mask is None:
-            self._ck(self.lib.phys_capsulecast_device(self.h, n, *args, *out))
-        else:
-            self._ck(self.lib.phys_capsulecast_device_filtered(self.h, n, *args, _device_mask(mask, n), *out))
+        self._cast_device("capsulecast", origins, (("origins", origins, 3), ("dirs", dirs, 3), ("rot", rot, 4), ("radius", radius, 1),
+                                                   ("half_length", half_length, 1), ("max_t", max_t, 1), ("ignore", ignore, 1)),
+                          (("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3), ("point_out", point_out, 3)),
+                          mask)
 
     def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None, cap=None, mask=None):
         """Every target each query shape intersects (phys_overlap): shape_type scalar or (n,) SHAPE_SPHERE / BOX / CAPSULE,

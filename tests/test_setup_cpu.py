@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "physics_amd", "csrc")
 
 
-@pytest.mark.parametrize("header", ["setup.hpp", "readout.hpp"])
+@pytest.mark.parametrize("header", ["setup.hpp", "readout.hpp", "staging.hpp"])
 def test_header_needs_no_hip(header):
     # no include path at all: the standard library, the C header of the ABI, plan.hpp and include/spec, by relative path
     subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", "-x", "c++", "-"],
