@@ -112,7 +112,7 @@ typedef struct phys_stats {
     int32_t cg_converged;   /* 1 = Some(lambda), 0 = None (sle_solver.rs:45) */
     uint64_t steps;         /* updates since creation */
     uint32_t overflow;      /* bit 0 pairs, 1 manifolds, 2 colours (> 64 manifolds at one body), 3 halo / cross pairs,
-                               4 solver hand-off timeout, 6 colour table full: the last update's bits OR every bit raised since
+                               4 solver hand-off timeout, 6 colour table full, 8 a body edit's bad ids: the last update's bits OR every bit raised since
                                the last phys_sync */
     uint32_t n_ground_manifolds; /* manifolds against the ground plane (subset of n_manifolds) */
     float max_extent;       /* largest fattened-AABB edge of the last broad phase (the grid cell is 1.001x this) */
@@ -647,6 +647,55 @@ int32_t phys_set_force_field_poses(phys_world* w, uint64_t n /* == field count *
 int32_t phys_set_force_field_params(phys_world* w, uint64_t n /* == field count */, const float* vec /*3n*/,
                                     const float* coef /*2n*/);
 int32_t phys_apply_force_fields(phys_world* w);
+
+/* --- in-place body edits: poses, velocities, impulses and forces by id list (new: the reference sets fields of one body) ---
+ * phys_set_bodies replaces the whole set and resets filters, materials, warm starting, colours, events and trigger occupancy.
+ * These calls change a few bodies and keep all of that: a jump, a hit, a respawn, a reset of one environment of many. `ids`
+ * are body indices below phys_stats.n_bodies, n is the number of entries; masses, inertia and shapes stay with phys_set_bodies.
+ * Order. An edit call behaves as if its entries were applied one after another in the order given; several entries may name
+ *   one body. For the two set calls the last entry of a body wins; impulses and forces accumulate in entry order, bit for bit
+ *   as if applied one at a time. phys_get_body_states takes ids in any order, with repeats.
+ * Arithmetic (normative: include/spec/body_edit.h, float32, no contraction).
+ *   impulse  r = point - x (zero without a point), L = ang_impulse + r x J, v = v + J * inv_mass, w = w + I^-1 L, with the
+ *            body's inverse mass and inverse inertia as the integrator applies them. It acts at once: no dt, no accumulator.
+ *   force    RigidBody::apply_force_at_position per entry (T += (point - x) x f, F += f; without a point F += f), then
+ *            T += torque if given: a batch equals the same phys_apply_force_* calls bit for bit, in one launch. The
+ *            accumulators are consumed by the next update or phys_step, as ever.
+ *   velocity only v and w are rewritten; the masses stay.
+ *   pose     pos and / or rot replaced (either may be NULL = keep). Rotations are stored as given, never renormalised.
+ * What a pose edit keeps and drops. Warm-start impulses, colours, contact events and trigger occupancy are kept: a body
+ *   teleported away raises END for its old pairs at the next update, one teleported into a trigger raises ENTER. The AABBs and
+ *   grids of the last broad phase are dropped: phys_broadphase, phys_get_aabbs, the queries and the next update see the new
+ *   poses, and phys_halo_pack / phys_halo_pairs ask for an update or phys_broadphase first.
+ * When. Between updates and between phys_update_n batches; on the world's stream, behind what is already enqueued.
+ * Host arrays (no suffix): checked before anything is written - PHYS_ERR_INVALID_ARG for a NULL ids or a NULL impulse / force
+ *   with n > 0, n >= 2^31, or a non-finite value; PHYS_ERR_OUT_OF_RANGE for an id that is not below n_bodies. The entries are
+ *   ordered by a stable sort on the id and staged; the call synchronises before it returns. n == 0 is a no-op.
+ * Device arrays (_device): every pointer in device memory; the call only enqueues on the world's stream. The caller gives ids in
+ *   NON-DECREASING order (a sort's output, or nonzero()'s). An entry whose id is out of range is skipped, nothing is written
+ *   outside the arrays, and it or an entry with ids[i - 1] > ids[i] makes the next phys_sync return PHYS_ERR_INVALID_ARG, once,
+ *   behind every other sticky error (phys_stats.overflow bit 8; the update's contact solve is NOT skipped). The other entries
+ *   of that call are applied; the state of a body named by an out-of-order entry is unspecified.
+ * A world with max_ghosts > 0 answers all ten calls with PHYS_ERR_UNSUPPORTED. Added without an ABI version change (no struct
+ * changed): a library that predates them lacks the symbols. DESIGN.md section 24. */
+int32_t phys_set_body_poses(phys_world* w, uint64_t n, const uint32_t* ids /*n*/, const float* pos /*3n or NULL*/,
+                            const float* rot_ijkw /*4n or NULL*/);
+int32_t phys_set_body_velocities(phys_world* w, uint64_t n, const uint32_t* ids /*n*/, const float* lin /*3n or NULL*/,
+                                 const float* ang /*3n or NULL*/);
+int32_t phys_apply_impulses(phys_world* w, uint64_t n, const uint32_t* ids /*n*/, const float* impulse /*3n*/,
+                            const float* point /*3n world space, or NULL = centre*/, const float* ang_impulse /*3n or NULL*/);
+int32_t phys_apply_forces(phys_world* w, uint64_t n, const uint32_t* ids /*n*/, const float* force /*3n*/,
+                          const float* point /*3n world space, or NULL = centre*/, const float* torque /*3n or NULL*/);
+int32_t phys_get_body_states(phys_world* w, uint64_t n, const uint32_t* ids /*n*/, float* pos_out /*3n*/, float* rot_out /*4n*/,
+                             float* lin_out /*3n*/, float* ang_out /*3n; each output may be NULL*/);
+int32_t phys_set_body_poses_device(phys_world* w, uint64_t n, const uint32_t* ids, const float* pos, const float* rot_ijkw);
+int32_t phys_set_body_velocities_device(phys_world* w, uint64_t n, const uint32_t* ids, const float* lin, const float* ang);
+int32_t phys_apply_impulses_device(phys_world* w, uint64_t n, const uint32_t* ids, const float* impulse, const float* point,
+                                   const float* ang_impulse);
+int32_t phys_apply_forces_device(phys_world* w, uint64_t n, const uint32_t* ids, const float* force, const float* point,
+                                 const float* torque);
+int32_t phys_get_body_states_device(phys_world* w, uint64_t n, const uint32_t* ids, float* pos_out, float* rot_out, float* lin_out,
+                                    float* ang_out);
 
 /* --- per-stage device timing (HIP events on the world's stream), for bench.py's roofline --- */
 #define PHYS_STAGE_STEP_FULL 0u     /* gravity + RigidBody::step, one kernel (no collisions) */

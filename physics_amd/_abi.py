@@ -219,6 +219,17 @@ PROTOTYPES = {
     "phys_set_force_field_poses": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p]),
     "phys_set_force_field_params": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p]),
     "phys_apply_force_fields": (C.c_int32, [C.c_void_p]),
+    "phys_set_body_poses": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p]),
+    "phys_set_body_velocities": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p]),
+    "phys_apply_impulses": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p, f32p]),
+    "phys_apply_forces": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p, f32p]),
+    "phys_get_body_states": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p, f32p, f32p]),
+    # the same five on device arrays: every pointer a c_void_p
+    "phys_set_body_poses_device": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 3),
+    "phys_set_body_velocities_device": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 3),
+    "phys_apply_impulses_device": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
+    "phys_apply_forces_device": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4),
+    "phys_get_body_states_device": (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5),
     "phys_profile_enable": (C.c_int32, [C.c_void_p, C.c_int32]),
     "phys_profile_get": (C.c_int32, [C.c_void_p, C.POINTER(PhysProfile)]),
     "phys_get_device_view": (C.c_int32, [C.c_void_p, C.POINTER(PhysDeviceView)]),

@@ -1048,6 +1048,98 @@ int32_t phys_apply_force_fields(phys_world* w) {
     return PHYS_OK;
 }
 
+// ---- in-place body edits: checked and ordered on the host (setup.hpp), applied by edit.hip ----
+// a ghost's state belongs to its owner's rank: a sharded world refuses the calls, like the materials and the force fields
+#define PHYS_NO_EDITS_WHEN_SHARDED(w) \
+    do { if ((w)->cfg.max_ghosts > 0) return fail(PHYS_ERR_UNSUPPORTED, "body edits are not supported in a world with max_ghosts > 0"); } while (0)
+
+// edits on device arrays: checked (edit_args_error), then enqueued; ids in non-decreasing order are the caller's to give
+static int32_t edit_device(phys_world* w, EditKind kind, const EditBatch& b) {
+    ENTER(w);
+    PHYS_NO_EDITS_WHEN_SHARDED(w);
+    if (const char* bad = edit_args_error(kind, b)) return fail(PHYS_ERR_INVALID_ARG, bad);
+    return launch_edit(w, kind, b);
+}
+
+// edits on host arrays: checked and ordered by id before anything is written (edit_order), staged in w->stage, applied;
+// synchronises, like the queries on host arrays
+static int32_t edit_host(phys_world* w, EditKind kind, const EditBatch& b) {
+    ENTER(w);
+    PHYS_NO_EDITS_WHEN_SHARDED(w);
+    const EditOrder o = edit_order(kind, b, w->n_owned);
+    if (o.code != PHYS_OK) return fail(o.code, o.message.c_str());
+    if (b.n == 0) return PHYS_OK;
+    std::vector<float> sorted[3];
+    Staging in{w, w->stage};
+    const auto s_ids = in.add(o.ids.data(), b.n);
+    StageLayout::Slot<float> s_a[3];
+    for (int k = 0; k < 3; ++k) {
+        sorted[k] = edit_gather(o.order, b.a[k], edit_cols(kind, k));
+        s_a[k] = in.add(b.a[k] ? sorted[k].data() : nullptr, sorted[k].size());
+    }
+    PHYS_TRY(in.reserve());
+    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
+    PHYS_TRY(launch_edit(w, kind, {b.n, in.at(s_ids), {in.at(s_a[0]), in.at(s_a[1]), in.at(s_a[2])}}));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // the ordered arrays die with this call
+    return PHYS_OK;
+}
+
+int32_t phys_set_body_poses(phys_world* w, uint64_t n, const uint32_t* ids, const float* pos, const float* rot_ijkw) {
+    return edit_host(w, EditKind::Poses, {n, ids, {pos, rot_ijkw, nullptr}});
+}
+int32_t phys_set_body_velocities(phys_world* w, uint64_t n, const uint32_t* ids, const float* lin, const float* ang) {
+    return edit_host(w, EditKind::Velocities, {n, ids, {lin, ang, nullptr}});
+}
+int32_t phys_apply_impulses(phys_world* w, uint64_t n, const uint32_t* ids, const float* impulse, const float* point, const float* ang_impulse) {
+    return edit_host(w, EditKind::Impulses, {n, ids, {impulse, point, ang_impulse}});
+}
+int32_t phys_apply_forces(phys_world* w, uint64_t n, const uint32_t* ids, const float* force, const float* point, const float* torque) {
+    return edit_host(w, EditKind::Forces, {n, ids, {force, point, torque}});
+}
+int32_t phys_set_body_poses_device(phys_world* w, uint64_t n, const uint32_t* ids, const float* pos, const float* rot_ijkw) {
+    return edit_device(w, EditKind::Poses, {n, ids, {pos, rot_ijkw, nullptr}});
+}
+int32_t phys_set_body_velocities_device(phys_world* w, uint64_t n, const uint32_t* ids, const float* lin, const float* ang) {
+    return edit_device(w, EditKind::Velocities, {n, ids, {lin, ang, nullptr}});
+}
+int32_t phys_apply_impulses_device(phys_world* w, uint64_t n, const uint32_t* ids, const float* impulse, const float* point,
+                                   const float* ang_impulse) {
+    return edit_device(w, EditKind::Impulses, {n, ids, {impulse, point, ang_impulse}});
+}
+int32_t phys_apply_forces_device(phys_world* w, uint64_t n, const uint32_t* ids, const float* force, const float* point, const float* torque) {
+    return edit_device(w, EditKind::Forces, {n, ids, {force, point, torque}});
+}
+
+// ids in any order, with repeats; an id that is not below n_owned: PHYS_ERR_OUT_OF_RANGE, nothing written
+int32_t phys_get_body_states(phys_world* w, uint64_t n, const uint32_t* ids, float* pos_out, float* rot_out, float* lin_out, float* ang_out) {
+    ENTER(w);
+    PHYS_NO_EDITS_WHEN_SHARDED(w);
+    if (n == 0) return PHYS_OK;
+    if (n >= (1ull << 31)) return fail(PHYS_ERR_INVALID_ARG, "phys_get_body_states: n must be below 2^31");
+    if (!ids) return fail(PHYS_ERR_INVALID_ARG, "phys_get_body_states: null ids");
+    for (uint64_t k = 0; k < n; ++k)
+        if (ids[k] >= w->n_owned) return fail(PHYS_ERR_OUT_OF_RANGE, "phys_get_body_states: body index out of range");
+    Staging in{w, w->stage}, out{w, w->rc_out};
+    const auto s_ids = in.add(ids, n);
+    const auto s_pos = out.add(pos_out, 3 * n), s_rot = out.add(rot_out, 4 * n), s_lin = out.add(lin_out, 3 * n), s_ang = out.add(ang_out, 3 * n);
+    PHYS_TRY(in.reserve());
+    PHYS_TRY(out.reserve());
+    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
+    PHYS_TRY(launch_get_states(w, n, in.at(s_ids), out.at(s_pos), out.at(s_rot), out.at(s_lin), out.at(s_ang)));
+    PHYS_TRY(out.copy(hipMemcpyDeviceToHost));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    return PHYS_OK;
+}
+int32_t phys_get_body_states_device(phys_world* w, uint64_t n, const uint32_t* ids, float* pos_out, float* rot_out, float* lin_out,
+                                    float* ang_out) {
+    ENTER(w);
+    PHYS_NO_EDITS_WHEN_SHARDED(w);
+    if (n == 0) return PHYS_OK;
+    if (n >= (1ull << 31)) return fail(PHYS_ERR_INVALID_ARG, "phys_get_body_states_device: n must be below 2^31");
+    if (!ids) return fail(PHYS_ERR_INVALID_ARG, "phys_get_body_states_device: null ids");
+    return launch_get_states(w, n, ids, pos_out, rot_out, lin_out, ang_out);
+}
+
 int32_t phys_set_global_ids(phys_world* w, const uint32_t* global_ids) {
     ENTER(w);
     if (!global_ids) return fail(PHYS_ERR_INVALID_ARG, "null ids");

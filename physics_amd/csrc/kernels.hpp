@@ -342,6 +342,13 @@ void launch_force_fields(phys_world* w);
 int32_t fields_set(phys_world* w, FieldStaging&& staged);
 int32_t fields_rebuild(phys_world* w);  // w->ff_host was patched (poses, params): build the records again and send them
 
+// in-place body edits (edit.hip): one batch on device arrays ordered by id (EditKind, EditBatch and the
+// argument checks: setup.hpp), enqueued on the world's stream; a pose edit drops the AABBs and grids kept from the last broad
+// phase, a force edit marks the accumulators dirty. Nothing is launched in a world that never calls them.
+int32_t launch_edit(phys_world* w, EditKind kind, const EditBatch& b);
+// the states of the bodies ids[0 .. n) into device arrays (each may be null), ids in any order
+int32_t launch_get_states(phys_world* w, uint64_t n, const uint32_t* ids, float* pos_out, float* rot_out, float* lin_out, float* ang_out);
+
 // constraints.hip
 int32_t constraints_alloc(phys_world* w);
 void launch_constraint_phase(phys_world* w, bool gravity_pending);  // Q = accumulators (+ gravity when still pending)

@@ -96,7 +96,8 @@ inline bool trigger_bits_to_csr(const uint32_t* bits, uint64_t words, uint64_t n
 
 // phys_sync: the overflow bits raised since the last call (kOvf*) and the eight debug words -> the code and the text. One error
 // per call, in this precedence: corrupt row, hand-off time-out (with k_solve_cluster's note; both notes: records.hpp), colours,
-// halo, colour table, then pairs / manifolds.
+// halo, colour table, then pairs / manifolds (any other bit too), and last a body edit's bad ids (kOvfBadEdit: an argument error
+// of a device call, not a capacity).
 struct SyncError {
     int32_t code = PHYS_OK;
     std::string message;
@@ -129,9 +130,12 @@ inline SyncError sync_error(uint32_t bits, const uint32_t g[8]) {
     if (bits & kOvfColorTable)
         return {PHYS_ERR_CAPACITY, "the persistent colour table is full (a look-up or an insert gave up after thousands of "
                                    "slots): the contact solve of that step was skipped. Raise phys_config.max_manifolds"};
-    if (bits)
+    if (bits & ~kOvfBadEdit)
         return {PHYS_ERR_CAPACITY, "pair / manifold capacity exceeded in a step since the last phys_sync (the contact "
                                    "solve of that step was skipped): raise phys_config.max_pairs / max_manifolds"};
+    if (bits & kOvfBadEdit)
+        return {PHYS_ERR_INVALID_ARG, "a body edit on device arrays since the last phys_sync met ids out of order or out of range: "
+                                      "out-of-range entries were skipped, the bodies of out-of-order entries are unspecified"};
     return {};
 }
 

@@ -1,6 +1,7 @@
 // setup.hpp — what the host computes ONCE per body set, static set or constraint list, as pure functions of host arrays and a
 // few scalars: table sizes, capacities, cluster shapes and homes, the static colliders' grid, the staged body arrays, the
-// constraint column tables, the staged force fields and trigger volumes with their records, argument validation. Nothing of HIP in here and no phys_world: a host compiler reads it alone,
+// constraint column tables, the staged force fields and trigger volumes with their records, the checks and the order of a body-edit
+// batch, argument validation. Nothing of HIP in here and no phys_world: a host compiler reads it alone,
 // and tests/cpp/setup_probe.cpp holds every function to hand-worked values or a brute-force restatement
 // (tests/test_setup_cpu.py). The .hip files keep the allocations, the copies and the launches.
 #pragma once
@@ -19,6 +20,7 @@
 #include "../../include/spec/collide.h"
 #include "../../include/spec/contact_solve.h"
 #include "../../include/spec/det_math.h"
+#include "../../include/spec/body_edit.h"
 #include "../../include/spec/force_field.h"
 #include "../../include/spec/vec.h"
 #include "plan.hpp"
@@ -78,6 +80,9 @@ constexpr uint32_t kOvfHalo = 8u;         // bit 3: halo records, ghosts or cros
 constexpr uint32_t kOvfHandoff = 16u;     // bit 4: solver hand-off timeout
 constexpr uint32_t kOvfCorruptRow = 32u;  // bit 5: corrupt solver row refused (StepCounters::debug says which)
 constexpr uint32_t kOvfColorTable = 64u;  // bit 6: colour table walk given up
+// bit 8, sticky word ONLY (edit.hip; the per-step word would make the next update skip its contact solve): a body edit on
+// device arrays met ids out of order or out of range. phys_sync reports it as PHYS_ERR_INVALID_ARG, behind everything else.
+constexpr uint32_t kOvfBadEdit = 0x100u;
 constexpr size_t kCountersStepResetBytes = offsetof(StepCounters, max_extent_bits);
 constexpr size_t kCountersExtentResetBytes = offsetof(StepCounters, sticky_overflow);
 
@@ -709,6 +714,74 @@ inline std::vector<ff_record> field_records(const std::vector<ff_staged>& staged
     std::vector<ff_record> rec(staged.size());
     for (size_t k = 0; k < staged.size(); ++k) rec[k] = ff_record_make(&staged[k]);
     return rec;
+}
+
+// ---- in-place body edits: the checks and the order of a batch on host arrays ----------------------------
+// The four edit calls and the arrays of one batch, host pointers or device pointers alike, in the header's order:
+//   Poses: pos, rot   Velocities: lin, ang   Impulses: impulse, point, ang_impulse   Forces: force, point, torque
+enum class EditKind { Poses, Velocities, Impulses, Forces };
+struct EditBatch {
+    uint64_t n;
+    const uint32_t* ids;
+    const float* a[3];
+};
+// floats per entry of array `slot` (0: the kind has no such array); only the first array of an impulse or force batch is required
+inline uint32_t edit_cols(EditKind kind, int slot) {
+    if (kind == EditKind::Poses) return slot == 0 ? 3u : (slot == 1 ? 4u : 0u);
+    if (kind == EditKind::Velocities) return slot < 2 ? 3u : 0u;
+    return 3u;
+}
+inline bool edit_required(EditKind kind, int slot) { return slot == 0 && (kind == EditKind::Impulses || kind == EditKind::Forces); }
+// what every edit entry point checks first, host or device arrays: the text of the refusal (PHYS_ERR_INVALID_ARG), null when
+// the call may go on. n == 0 is a no-op whatever the pointers.
+inline const char* edit_args_error(EditKind kind, const EditBatch& b) {
+    if (b.n == 0) return nullptr;
+    if (b.n >= (1ull << 31)) return "body edit: n must be below 2^31";
+    if (!b.ids) return "body edit: null ids";
+    for (int s = 0; s < 3; ++s)
+        if (edit_required(kind, s) && !b.a[s]) return "body edit: null impulse / force array";
+    return nullptr;
+}
+// The entries ordered by a STABLE sort on the id, so that the entries of one body keep the order the caller gave them and form
+// one run (include/spec/body_edit.h). Checked before anything is written: code is PHYS_OK, or the refusal and its text - a
+// null ids or a null required array with n > 0 (PHYS_ERR_INVALID_ARG), then an id that is not below n_owned
+// (PHYS_ERR_OUT_OF_RANGE), then a non-finite value (PHYS_ERR_INVALID_ARG). n == 0: no entries, PHYS_OK.
+struct EditOrder {
+    int32_t code = PHYS_OK;
+    std::string message;
+    std::vector<uint32_t> order;  // order[k]: the caller's entry that is applied k-th
+    std::vector<uint32_t> ids;    // ids[order[k]]: non-decreasing
+};
+inline EditOrder edit_order(EditKind kind, const EditBatch& b, uint64_t n_owned) {
+    EditOrder out;
+    const uint64_t n = b.n;
+    const uint32_t* ids = b.ids;
+    if (n == 0) return out;
+    const auto refuse = [&](int32_t code, std::string msg) { out.code = code; out.message = std::move(msg); return out; };
+    if (const char* bad = edit_args_error(kind, b)) return refuse(PHYS_ERR_INVALID_ARG, bad);
+    for (uint64_t k = 0; k < n; ++k)
+        if (ids[k] >= n_owned)
+            return refuse(PHYS_ERR_OUT_OF_RANGE, "body edit: entry " + std::to_string(k) + " names body " + std::to_string(ids[k]) + ", out of range");
+    for (int s = 0; s < 3; ++s) {
+        const uint32_t cols = edit_cols(kind, s);
+        for (uint64_t k = 0; b.a[s] && k < n * cols; ++k)
+            if (!std::isfinite(b.a[s][k])) return refuse(PHYS_ERR_INVALID_ARG, "body edit: non-finite value in entry " + std::to_string(k / cols));
+    }
+    out.order.resize(n);
+    for (uint64_t k = 0; k < n; ++k) out.order[k] = (uint32_t)k;
+    std::stable_sort(out.order.begin(), out.order.end(), [&](uint32_t x, uint32_t y) { return ids[x] < ids[y]; });
+    out.ids.resize(n);
+    for (uint64_t k = 0; k < n; ++k) out.ids[k] = ids[out.order[k]];
+    return out;
+}
+// an array of the batch in that order (`cols` values per entry); null stays null (an empty vector)
+template <typename T>
+inline std::vector<T> edit_gather(const std::vector<uint32_t>& order, const T* src, uint32_t cols) {
+    std::vector<T> out;
+    if (!src) return out;
+    out.resize(order.size() * (size_t)cols);
+    for (size_t k = 0; k < order.size(); ++k) std::memcpy(&out[k * cols], src + (size_t)order[k] * cols, sizeof(T) * cols);
+    return out;
 }
 
 }  // namespace phys

@@ -82,6 +82,19 @@ def _query_mask(mask, n):
     return _filter_field(mask, n, "mask", 0, 0xFFFF, np.uint16)
 
 
+def _edit_ids(ids):
+    """The body ids of an edit call as a contiguous (n,) uint32 array; non-integers and values outside u32 raise."""
+    v = np.asarray(ids)
+    if v.size == 0:
+        return np.zeros(0, np.uint32)
+    if v.dtype.kind not in "iu":
+        raise ValueError("ids: needs integers")
+    v = v.reshape(-1)
+    if v.min() < 0 or v.max() > 0xFFFFFFFF:
+        raise ValueError("ids: values must lie in [0, 2^32)")
+    return np.ascontiguousarray(v, dtype=np.uint32)
+
+
 def _device_args(n, items):
     """c_void_p of contiguous 4-byte device tensors of n x cols elements (None passes through)."""
     args = []
@@ -270,6 +283,88 @@ class World:
     def set_forces(self, force=None, torque=None):
         f, t = _f(force), _f(torque)
         self._ck(self.lib.phys_set_forces(self.h, _p(f), _p(t)))
+
+    # ---- in-place body edits (include/physics_hip.h): poses, velocities, impulses, forces and states by id list
+    def _edit(self, call, ids, arrays):
+        """An edit on host arrays. arrays: (name, values or None, columns) in the call's order. Entries apply in the order
+        given; the library checks ids and values before anything is written."""
+        ids = _edit_ids(ids)
+        n = ids.shape[0]
+        a = []
+        for name, v, cols in arrays:
+            v = None if v is None else _f(v).reshape(-1, cols)
+            if v is not None and v.shape[0] != n:
+                raise ValueError(f"{name}: needs {n} x {cols} values (one row per id)")
+            a.append(v)
+        self._ck(getattr(self.lib, call)(self.h, n, _p(ids, u32p), *[_p(v) for v in a]))
+
+    def _edit_device(self, call, ids, arrays):
+        """An edit on contiguous torch tensors of the world's device; ids int32 or uint32, non-decreasing. Only enqueues."""
+        n = int(ids.numel())
+        if ids.is_floating_point():
+            raise ValueError("ids: needs an int32 / uint32 device tensor")
+        self._ck(getattr(self.lib, call)(self.h, n, *_device_args(n, (("ids", ids, 1),) + tuple(arrays))))
+
+    def set_body_poses(self, ids, pos=None, rot=None):
+        """New positions (n, 3) and / or rotations (n, 4) [i, j, k, w] of the bodies `ids` (phys_set_body_poses); None keeps
+        that part. The last entry of a body wins. Rotations are stored as given. Warm starting, colours, events and trigger
+        occupancy are kept; the next update, broadphase() and the queries see the new poses."""
+        self._edit("phys_set_body_poses", ids, (("pos", pos, 3), ("rot", rot, 4)))
+
+    def set_body_velocities(self, ids, lin=None, ang=None):
+        """New linear and / or angular velocities (n, 3) of the bodies `ids` (phys_set_body_velocities); masses stay."""
+        self._edit("phys_set_body_velocities", ids, (("lin", lin, 3), ("ang", ang, 3)))
+
+    def apply_impulses(self, ids, impulse, point=None, ang_impulse=None):
+        """Impulses (n, 3) on the bodies `ids`, at world points (n, 3) or None (the centre), with angular impulses (n, 3) or
+        None (phys_apply_impulses): v += J / m, w += I^-1 (ang_impulse + (point - x) x J), entries of one body in order."""
+        if impulse is None:
+            raise ValueError("impulse is required")
+        self._edit("phys_apply_impulses", ids, (("impulse", impulse, 3), ("point", point, 3), ("ang_impulse", ang_impulse, 3)))
+
+    def apply_forces(self, ids, force, point=None, torque=None):
+        """Forces (n, 3) on the bodies `ids` into the accumulators, at world points or None (the centre), with torques or
+        None (phys_apply_forces): one launch that equals the same apply_force_at_position calls bit for bit."""
+        if force is None:
+            raise ValueError("force is required")
+        self._edit("phys_apply_forces", ids, (("force", force, 3), ("point", point, 3), ("torque", torque, 3)))
+
+    def get_body_states(self, ids):
+        """(pos (n, 3), rot (n, 4), lin (n, 3), ang (n, 3)) of the bodies `ids`, in any order and with repeats
+        (phys_get_body_states)."""
+        ids = _edit_ids(ids)
+        n = ids.shape[0]
+        out = [np.empty((n, c), np.float32) for c in (3, 4, 3, 3)]
+        self._ck(self.lib.phys_get_body_states(self.h, n, _p(ids, u32p), *[_p(o) for o in out]))
+        return tuple(out)
+
+    def set_body_poses_device(self, ids, pos=None, rot=None):
+        """phys_set_body_poses_device on contiguous torch tensors of the world's device: ids int32 / uint32 (n,) in
+        non-decreasing order, pos float32 (n, 3) or None, rot float32 (n, 4) or None. Only enqueues on the world's stream;
+        ids out of order or out of range make the next sync() raise PHYS_ERR_INVALID_ARG."""
+        self._edit_device("phys_set_body_poses_device", ids, (("pos", pos, 3), ("rot", rot, 4)))
+
+    def set_body_velocities_device(self, ids, lin=None, ang=None):
+        """phys_set_body_velocities_device, as set_body_poses_device; lin / ang float32 (n, 3) or None."""
+        self._edit_device("phys_set_body_velocities_device", ids, (("lin", lin, 3), ("ang", ang, 3)))
+
+    def apply_impulses_device(self, ids, impulse, point=None, ang_impulse=None):
+        """phys_apply_impulses_device, as set_body_poses_device; impulse float32 (n, 3), point / ang_impulse (n, 3) or None."""
+        if impulse is None:
+            raise ValueError("impulse is required")
+        self._edit_device("phys_apply_impulses_device", ids, (("impulse", impulse, 3), ("point", point, 3), ("ang_impulse", ang_impulse, 3)))
+
+    def apply_forces_device(self, ids, force, point=None, torque=None):
+        """phys_apply_forces_device, as set_body_poses_device; force float32 (n, 3), point / torque (n, 3) or None."""
+        if force is None:
+            raise ValueError("force is required")
+        self._edit_device("phys_apply_forces_device", ids, (("force", force, 3), ("point", point, 3), ("torque", torque, 3)))
+
+    def get_body_states_device(self, ids, pos_out=None, rot_out=None, lin_out=None, ang_out=None):
+        """phys_get_body_states_device: the states of the bodies `ids` (any order) into float32 device tensors (n, 3) / (n, 4)
+        / (n, 3) / (n, 3), each or None. Only enqueues on the world's stream."""
+        self._edit_device("phys_get_body_states_device", ids, (("pos_out", pos_out, 3), ("rot_out", rot_out, 4), ("lin_out", lin_out, 3),
+                                                               ("ang_out", ang_out, 3)))
 
     # ---- stepping
     def apply_gravity(self):

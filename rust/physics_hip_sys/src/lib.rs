@@ -245,6 +245,16 @@ extern "C" {
     pub fn phys_set_force_field_poses(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32) -> i32;
     pub fn phys_set_force_field_params(w: *mut phys_world, n: u64, vec: *const f32, coef: *const f32) -> i32;
     pub fn phys_apply_force_fields(w: *mut phys_world) -> i32;
+    pub fn phys_set_body_poses(w: *mut phys_world, n: u64, ids: *const u32, pos: *const f32, rot_ijkw: *const f32) -> i32;
+    pub fn phys_set_body_velocities(w: *mut phys_world, n: u64, ids: *const u32, lin: *const f32, ang: *const f32) -> i32;
+    pub fn phys_apply_impulses(w: *mut phys_world, n: u64, ids: *const u32, impulse: *const f32, point: *const f32, ang_impulse: *const f32) -> i32;
+    pub fn phys_apply_forces(w: *mut phys_world, n: u64, ids: *const u32, force: *const f32, point: *const f32, torque: *const f32) -> i32;
+    pub fn phys_get_body_states(w: *mut phys_world, n: u64, ids: *const u32, pos_out: *mut f32, rot_out: *mut f32, lin_out: *mut f32, ang_out: *mut f32) -> i32;
+    pub fn phys_set_body_poses_device(w: *mut phys_world, n: u64, ids: *const u32, pos: *const f32, rot_ijkw: *const f32) -> i32;
+    pub fn phys_set_body_velocities_device(w: *mut phys_world, n: u64, ids: *const u32, lin: *const f32, ang: *const f32) -> i32;
+    pub fn phys_apply_impulses_device(w: *mut phys_world, n: u64, ids: *const u32, impulse: *const f32, point: *const f32, ang_impulse: *const f32) -> i32;
+    pub fn phys_apply_forces_device(w: *mut phys_world, n: u64, ids: *const u32, force: *const f32, point: *const f32, torque: *const f32) -> i32;
+    pub fn phys_get_body_states_device(w: *mut phys_world, n: u64, ids: *const u32, pos_out: *mut f32, rot_out: *mut f32, lin_out: *mut f32, ang_out: *mut f32) -> i32;
     pub fn phys_profile_enable(w: *mut phys_world, on: i32) -> i32;
     pub fn phys_profile_get(w: *mut phys_world, out: *mut phys_profile) -> i32;
     pub fn phys_get_device_view(w: *mut phys_world, out: *mut phys_device_view) -> i32;
