@@ -329,6 +329,49 @@ int32_t phys_capsulecast_device_filtered(phys_world* w, uint64_t n, const float*
                                          const float* radius, const float* half_length, const float* max_t,
                                          const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
                                          float* normal_out, float* point_out);
+/* phys_move_and_slide: a capsule character (core pos[i] +- half_length[i] * a, a the y axis turned by rot_ijkw[i], radius
+ * radius[i]: phys_capsulecast's capsule) tries to move by motion[i] without turning. It casts along what is left of the motion,
+ * stops `skin` short of the first target, projects the rest of the motion onto the contact plane and casts again, up to
+ * max_slides casts, all inside ONE kernel launch over ONE query grid. The rule between two casts is stated once, in
+ * include/spec/slide.h; every cast is phys_capsulecast's (origin = the position reached, dir = the motion
+ * left, max_t = its length + skin), so targets, ids, ties, ignore_body, query_mask, ghost slots and the current-pose rule are
+ * phys_capsulecast[_filtered]'s, and half_length == 0 is a sphere cast. Read-only: nothing an update reads is written, and sticky
+ * update errors are neither reported nor cleared.
+ *   - pos_out: where the character ends. remaining_out (may be NULL): the motion it could not make (zeros when all was made).
+ *   - status_out: the number of hits (0 .. 8) in bits 0-3, and
+ *       PHYS_SLIDE_BLOCKED    a cast started touching a target (t == 0: there is no usable normal); the character stays where
+ *                             that cast began and the motion left stays in remaining_out. No depenetration is attempted.
+ *       PHYS_SLIDE_EXHAUSTED  max_slides casts were made and motion is left.
+ *       PHYS_SLIDE_INVALID    a non-finite pos, motion, rot, radius or half_length, a negative radius or half_length, or
+ *                             |motion| > 3.0e38: pos_out = pos, remaining_out = motion as given, no hits.
+ *   - hit slots (each array may be NULL): slot k of query i lies at index k * n + i (iteration-major): the body id, the normal
+ *     and the touched point phys_capsulecast reports for the k-th hit. Every slot is written; an unused one holds PHYS_RAY_MISS
+ *     and zeros.
+ *   - a crease: when the slide along the second plane would re-enter the first, the motion left is projected onto the line the
+ *     two planes share (nothing is left between parallel planes); a slide never turns back against the motion asked for.
+ *   - a zero motion is valid: status 0, pos_out = pos. skin == 0 is allowed, but the character then rests on what it hit and the
+ *     next cast starts touching, so the query normally ends BLOCKED at its second cast: use a skin around contact_margin. At a
+ *     grazing approach the clearance left is skin * |u . n|, not skin.
+ *   - the grid is grown by the call's largest valid radius + half_length, as phys_capsulecast's; the motions do not enter.
+ *   - PHYS_ERR_INVALID_ARG: n >= 2^31, a NULL pos, motion, radius, half_length, pos_out or status_out with n > 0, a non-finite or
+ *     negative skin, max_slides outside 1 .. PHYS_SLIDE_MAX_SLIDES. n == 0 is a no-op.
+ * phys_move_and_slide takes host arrays and returns with the outputs written; phys_move_and_slide_device takes device pointers
+ * and only enqueues on the world's stream. query_mask NULL = no filtering (there is no _filtered twin). */
+#define PHYS_SLIDE_MAX_SLIDES 8u
+#define PHYS_SLIDE_BLOCKED 0x100u
+#define PHYS_SLIDE_EXHAUSTED 0x200u
+#define PHYS_SLIDE_INVALID 0x400u
+int32_t phys_move_and_slide(phys_world* w, uint64_t n, const float* pos /*3n*/, const float* motion /*3n*/,
+                            const float* rot_ijkw /*4n, NULL = identity*/, const float* radius /*n*/, const float* half_length /*n*/,
+                            float skin, uint32_t max_slides, const uint32_t* ignore_body /*n, NULL = none*/,
+                            const uint16_t* query_mask /*n, NULL = no filtering*/, float* pos_out /*3n*/,
+                            float* remaining_out /*3n, may be NULL*/, uint32_t* status_out /*n*/,
+                            uint32_t* hit_body_out /*max_slides*n, may be NULL*/, float* hit_normal_out /*3*max_slides*n, may be NULL*/,
+                            float* hit_point_out /*3*max_slides*n, may be NULL*/);
+int32_t phys_move_and_slide_device(phys_world* w, uint64_t n, const float* pos, const float* motion, const float* rot_ijkw,
+                                   const float* radius, const float* half_length, float skin, uint32_t max_slides,
+                                   const uint32_t* ignore_body, const uint16_t* query_mask, float* pos_out, float* remaining_out,
+                                   uint32_t* status_out, uint32_t* hit_body_out, float* hit_normal_out, float* hit_point_out);
 /* phys_overlap: for each query shape (shape_type SPHERE, BOX or CAPSULE with the bodies' half_extent conventions, at pos
  * with the unit quaternion rot_ijkw, NULL = identity), every target whose closed shape intersects it (touching counts).
  *   - output (CSR): query i's ids are ids_out[offsets_out[i] .. offsets_out[i + 1]), ascending and each once: bodies,

@@ -272,6 +272,15 @@ for _kind, (_ins, _outs) in CASTS.items():
             PROTOTYPES[f"phys_{_kind}{_device}" + ("_filtered" if _mask else "")] = (
                 C.c_int32, [C.c_void_p, C.c_uint64] + ([C.c_void_p] * len(_args) if _device else _args))
 
+# move-and-slide: pos, motion, rot, radius, half_length, skin, max_slides, ignore, query_mask; pos_out, remaining_out, status_out,
+# hit_body_out, hit_normal_out, hit_point_out (the device variant: every array a c_void_p)
+SLIDE_MAX_SLIDES = 8
+SLIDE_BLOCKED, SLIDE_EXHAUSTED, SLIDE_INVALID = 0x100, 0x200, 0x400
+PROTOTYPES["phys_move_and_slide"] = (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, f32p, C.c_float, C.c_uint32, u32p, u16p,
+                                                 f32p, f32p, u32p, u32p, f32p, f32p])
+PROTOTYPES["phys_move_and_slide_device"] = (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_float, C.c_uint32]
+                                            + [C.c_void_p] * 8)
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libphysics_hip.so")
 _lib = None
 

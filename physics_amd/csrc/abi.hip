@@ -945,6 +945,40 @@ int32_t phys_capsulecast_device_filtered(phys_world* w, uint64_t n, const float*
                                               query_mask, body_out, t_out, normal_out, point_out});
 }
 
+// move-and-slide: the batch in SlideBatch's order; on device arrays checked and enqueued, on host arrays
+// staged as the casts are (inputs in w->stage, outputs in w->rc_out), run, read back and waited for
+int32_t phys_move_and_slide_device(phys_world* w, uint64_t n, const float* pos, const float* motion, const float* rot_ijkw,
+                                   const float* radius, const float* half_length, float skin, uint32_t max_slides,
+                                   const uint32_t* ignore_body, const uint16_t* query_mask, float* pos_out, float* remaining_out,
+                                   uint32_t* status_out, uint32_t* hit_body_out, float* hit_normal_out, float* hit_point_out) {
+    ENTER(w);
+    const SlideBatch b = {n, pos, motion, rot_ijkw, radius, half_length, skin, max_slides, ignore_body, query_mask,
+                          pos_out, remaining_out, status_out, hit_body_out, hit_normal_out, hit_point_out};
+    if (const char* bad = slide_args_error(b)) return fail(PHYS_ERR_INVALID_ARG, bad);
+    if (n == 0) return PHYS_OK;
+    return launch_slide(w, b);
+}
+
+int32_t phys_move_and_slide(phys_world* w, uint64_t n, const float* pos, const float* motion, const float* rot_ijkw, const float* radius,
+                            const float* half_length, float skin, uint32_t max_slides, const uint32_t* ignore_body,
+                            const uint16_t* query_mask, float* pos_out, float* remaining_out, uint32_t* status_out,
+                            uint32_t* hit_body_out, float* hit_normal_out, float* hit_point_out) {
+    ENTER(w);
+    const SlideBatch b = {n, pos, motion, rot_ijkw, radius, half_length, skin, max_slides, ignore_body, query_mask,
+                          pos_out, remaining_out, status_out, hit_body_out, hit_normal_out, hit_point_out};
+    if (const char* bad = slide_args_error(b)) return fail(PHYS_ERR_INVALID_ARG, bad);
+    if (n == 0) return PHYS_OK;
+    Staging in{w, w->stage}, out{w, w->rc_out};
+    stage_slide(b, in, out);
+    PHYS_TRY(in.reserve());
+    PHYS_TRY(out.reserve());
+    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
+    PHYS_TRY(launch_slide(w, staged_slide(b, in.buf.p, out.buf.p)));
+    PHYS_TRY(out.copy(hipMemcpyDeviceToHost));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    return PHYS_OK;
+}
+
 static int32_t overlap_host(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,
                             const float* half_extent, const uint32_t* ignore_body, const uint16_t* query_mask, uint64_t cap,
                             uint64_t* offsets_out, uint32_t* ids_out) {

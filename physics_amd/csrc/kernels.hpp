@@ -399,6 +399,10 @@ int32_t launch_cast(phys_world* w, CastKind kind, const CastBatch& b);
 // values of the device array grow_radius (null: not grown), plus grow_half_length's of the same query where that is given (a
 // capsule reaches radius + half_length from its centre); *bits = log2 of the bucket table
 int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* grow_half_length, uint64_t n_grow, uint32_t* bits);
+// slide.hip: move-and-slide (SlideBatch: staging.hpp, device pointers, arguments checked by the caller): the
+// query grid once, grown by the call's largest valid radius + half_length, then ONE kernel in which every lane runs its
+// character's whole cast, stop, project loop (include/spec/slide.h) against the capsule cast's own walk
+int32_t launch_slide(phys_world* w, const SlideBatch& b);
 // query.hip: overlap queries on staged device arrays; writes the host offsets (n + 1) and, when they fit in cap, the ids
 int32_t launch_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot, const float* half_extent,
                        const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out,

@@ -1,5 +1,6 @@
-// staging.hpp — how a query call describes its arrays: the batch of one cast (rays, balls, capsules alike), what the cast entry
-// points check of it, and where a call's host arrays lie in the one device buffer they are staged in. Host-only like setup.hpp
+// staging.hpp — how a query call describes its arrays: the batch of one cast (rays, balls, capsules alike) and of one
+// move-and-slide call, what their entry points check of them, and where a call's host arrays lie in the one device buffer they
+// are staged in. Host-only like setup.hpp
 // (no HIP, no phys_world), held to tests/cpp/staging_probe.cpp. abi.hip keeps the buffer, the copies and the launch.
 #pragma once
 #include <cstddef>
@@ -83,6 +84,59 @@ inline CastBatch staged_cast(const CastBatch& host, uint8_t* in_base, uint8_t* o
     CastBatch dev = host;
     StageLayout in, out;
     for_each_cast_array(dev, [&](auto*& array, size_t per_query, bool output) {
+        StageLayout& l = output ? out : in;
+        array = l.at(output ? out_base : in_base, l.add(array, per_query * host.n));
+    });
+    return dev;
+}
+
+// ---- move-and-slide (phys_move_and_slide): the arrays of one call, n characters; host pointers or device
+// pointers alike. Slot k of query i lies at index k * n + i of the hit arrays.
+struct SlideBatch {
+    uint64_t n;
+    const float *pos, *motion;         // 3 per query
+    const float* rot;                  // [i, j, k, w] per query; null: identity
+    const float *radius, *half_length; // per query
+    float skin;                        // the call's: finite, >= 0
+    uint32_t max_slides;               // the call's: 1 .. 8
+    const uint32_t* ignore_body;       // null: none
+    const uint16_t* query_mask;        // null: no filtering
+    float *pos_out, *remaining_out;    // 3 per query; remaining_out may be null
+    uint32_t* status_out;
+    uint32_t* hit_body_out;            // max_slides per query; null: not wanted
+    float *hit_normal_out, *hit_point_out;  // 3 * max_slides per query; null: not wanted
+};
+
+constexpr uint32_t kSlideMaxSlides = 8;
+
+// every array of a call once, in the order they are staged: f(member, elements per query, is it an output)
+template <class Batch, class F>
+inline void for_each_slide_array(Batch& b, F&& f) {
+    const size_t k = b.max_slides;
+    f(b.pos, 3, false); f(b.motion, 3, false); f(b.rot, 4, false); f(b.radius, 1, false); f(b.half_length, 1, false);
+    f(b.ignore_body, 1, false); f(b.query_mask, 1, false);
+    f(b.pos_out, 3, true); f(b.remaining_out, 3, true); f(b.status_out, 1, true);
+    f(b.hit_body_out, k, true); f(b.hit_normal_out, 3 * k, true); f(b.hit_point_out, 3 * k, true);
+}
+
+// what both entry points check before they touch anything: the text of the refusal, null when the call may go on
+inline const char* slide_args_error(const SlideBatch& b) {
+    if (b.n >= (1ull << 31)) return "phys_move_and_slide: n must be below 2^31";
+    if (!(b.skin >= 0.0f && b.skin <= 3.4028235e38f)) return "phys_move_and_slide: skin must be finite and not negative";
+    if (b.max_slides < 1u || b.max_slides > kSlideMaxSlides) return "phys_move_and_slide: max_slides must be 1 .. 8";
+    const bool missing = !b.pos || !b.motion || !b.radius || !b.half_length || !b.pos_out || !b.status_out;
+    return b.n && missing ? "phys_move_and_slide: null pos, motion, radius, half_length, pos_out or status_out" : nullptr;
+}
+
+// a call on host arrays declares them: the inputs in one buffer, the outputs in another ...
+inline void stage_slide(const SlideBatch& host, StageLayout& in, StageLayout& out) {
+    for_each_slide_array(host, [&](auto* array, size_t per_query, bool output) { (output ? out : in).add(array, per_query * host.n); });
+}
+// ... and is the same batch on the device once the two buffers are there
+inline SlideBatch staged_slide(const SlideBatch& host, uint8_t* in_base, uint8_t* out_base) {
+    SlideBatch dev = host;
+    StageLayout in, out;
+    for_each_slide_array(dev, [&](auto*& array, size_t per_query, bool output) {
         StageLayout& l = output ? out : in;
         array = l.at(output ? out_base : in_base, l.add(array, per_query * host.n));
     });

@@ -201,6 +201,12 @@ class PhysicsState:
         self._push()
         return self._world.capsulecast(origins, dirs, radius, half_length, rot, max_t, ignore, mask=mask)
 
+    def move_and_slide(self, pos, motion, radius, half_length, rot=None, skin=0.01, max_slides=4, ignore=None, mask=None):
+        """Capsule characters move and slide along the entities as they are now (World.move_and_slide): (pos, remaining,
+        status, hit_body, hit_normal, hit_point)."""
+        self._push()
+        return self._world.move_and_slide(pos, motion, radius, half_length, rot, skin, max_slides, ignore, mask)
+
     def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None, mask=None):
         """Every entity each query shape intersects, as they are now (World.overlap): (offsets, ascending ids)."""
         self._push()

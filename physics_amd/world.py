@@ -518,6 +518,59 @@ class World:
                           (("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3), ("point_out", point_out, 3)),
                           mask)
 
+    def move_and_slide(self, pos, motion, radius, half_length, rot=None, skin=0.01, max_slides=4, ignore=None, mask=None):
+        """Capsule characters move, stop `skin` short of what they meet and slide along it (phys_move_and_slide; the rule:
+        include/spec/slide.h): pos / motion (n, 3), radius and half_length scalar or (n,), rot (n, 4) [i, j, k, w] or None
+        (upright), ignore (n,) body ids or None, mask scalar or (n,) u16 or None (no filtering), max_slides 1 .. 8 casts per
+        character, all in one launch. Returns (pos f32[n, 3], remaining f32[n, 3], status u32[n], hit_body u32[max_slides, n],
+        hit_normal f32[max_slides, n, 3], hit_point f32[max_slides, n, 3]): status holds the hit count in bits 0-3 and the
+        SLIDE_BLOCKED / SLIDE_EXHAUSTED / SLIDE_INVALID flags; an unused hit slot holds RAY_MISS and zeros."""
+        p, m = _f(pos).reshape(-1, 3), _f(motion).reshape(-1, 3)
+        n = p.shape[0]
+        if m.shape[0] != n:
+            raise ValueError("pos and motion differ in length")
+        k = int(max_slides)
+        if not 1 <= k <= _abi.SLIDE_MAX_SLIDES:
+            raise ValueError(f"max_slides: must lie in [1, {_abi.SLIDE_MAX_SLIDES}]")
+        skin = float(skin)
+        if not (np.isfinite(skin) and skin >= 0.0):
+            raise ValueError("skin: must be finite and not negative")
+        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)))
+        hq = np.ascontiguousarray(np.broadcast_to(np.asarray(half_length, np.float32), (n,)))
+        r = None if rot is None else _f(rot).reshape(-1, 4)
+        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.uint32).reshape(-1)
+        for a, cols in ((r, 4), (ig, 1)):
+            if a is not None and a.size != n * cols:
+                raise ValueError("rot / ignore do not match the character count")
+        qm = _query_mask(mask, n)
+        pos_out, rem, status = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32), np.empty(n, np.uint32)
+        body, nrm, pnt = np.empty((k, n), np.uint32), np.empty((k, n, 3), np.float32), np.empty((k, n, 3), np.float32)
+        if n:
+            self._ck(self.lib.phys_move_and_slide(self.h, n, _p(p), _p(m), _p(r), _p(rad), _p(hq), skin, k, _p(ig, u32p), _p(qm, u16p),
+                                                  _p(pos_out), _p(rem), _p(status, u32p), _p(body, u32p), _p(nrm), _p(pnt)))
+        return pos_out, rem, status, body, nrm, pnt
+
+    def move_and_slide_device(self, pos, motion, radius, half_length, pos_out, status_out, remaining_out=None, hit_body_out=None,
+                              hit_normal_out=None, hit_point_out=None, rot=None, skin=0.01, max_slides=4, ignore=None, mask=None):
+        """phys_move_and_slide_device on contiguous torch tensors of the world's device, as capsulecast_device: pos / motion
+        float32 (n, 3), radius and half_length float32 (n,), pos_out float32 (n, 3), status_out int32 / uint32 (n,),
+        remaining_out float32 (n, 3) or None, hit_body_out int32 / uint32 (max_slides, n) or None, hit_normal_out and
+        hit_point_out float32 (max_slides, n, 3) or None, rot float32 (n, 4) or None, ignore int32 / uint32 (n,) or None, mask
+        int16 / uint16 (n,) or None. Only enqueues on the world's stream (device_view().stream)."""
+        n = int(pos.shape[0])
+        k = int(max_slides)
+        if not 1 <= k <= _abi.SLIDE_MAX_SLIDES:
+            raise ValueError(f"max_slides: must lie in [1, {_abi.SLIDE_MAX_SLIDES}]")
+        skin = float(skin)
+        if not (np.isfinite(skin) and skin >= 0.0):
+            raise ValueError("skin: must be finite and not negative")
+        ins = _device_args(n, (("pos", pos, 3), ("motion", motion, 3), ("rot", rot, 4), ("radius", radius, 1), ("half_length", half_length, 1)))
+        ig, = _device_args(n, (("ignore", ignore, 1),))
+        outs = _device_args(n, (("pos_out", pos_out, 3), ("remaining_out", remaining_out, 3), ("status_out", status_out, 1),
+                                ("hit_body_out", hit_body_out, k), ("hit_normal_out", hit_normal_out, 3 * k),
+                                ("hit_point_out", hit_point_out, 3 * k)))
+        self._ck(self.lib.phys_move_and_slide_device(self.h, n, *ins, skin, k, ig, None if mask is None else _device_mask(mask, n), *outs))
+
     def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None, cap=None, mask=None):
         """Every target each query shape intersects (phys_overlap): shape_type scalar or (n,) SHAPE_SPHERE / BOX / CAPSULE,
         pos (n, 3), rot (n, 4) [i, j, k, w] or None (identity), half_extent (3,) or (n, 3) with the bodies' conventions,

@@ -28,6 +28,10 @@ pub const PHYS_FLAG_SOLVER_CLUSTER: u32 = 0x40;
 pub const PHYS_FLAG_EXCLUSIVE_GPU: u32 = 0x80;
 pub const PHYS_FLAG_NO_WARM_START: u32 = 0x100;
 pub const PHYS_RAY_MISS: u32 = 0xFFFF_FFFE;
+pub const PHYS_SLIDE_MAX_SLIDES: u32 = 8;
+pub const PHYS_SLIDE_BLOCKED: u32 = 0x100;
+pub const PHYS_SLIDE_EXHAUSTED: u32 = 0x200;
+pub const PHYS_SLIDE_INVALID: u32 = 0x400;
 pub const PHYS_RAY_GROUND: u32 = 0xFFFF_FFFF;
 // contact events: phys_contact_event.kind
 pub const PHYS_CONTACT_BEGIN: u32 = 1;
@@ -204,6 +208,15 @@ extern "C" {
                                             radius: *const f32, half_length: *const f32, max_t: *const f32, ignore_body: *const u32,
                                             query_mask: *const u16, body_out: *mut u32, t_out: *mut f32, normal_out: *mut f32,
                                             point_out: *mut f32) -> i32;
+    pub fn phys_move_and_slide(w: *mut phys_world, n: u64, pos: *const f32, motion: *const f32, rot_ijkw: *const f32, radius: *const f32,
+                               half_length: *const f32, skin: f32, max_slides: u32, ignore_body: *const u32, query_mask: *const u16,
+                               pos_out: *mut f32, remaining_out: *mut f32, status_out: *mut u32, hit_body_out: *mut u32,
+                               hit_normal_out: *mut f32, hit_point_out: *mut f32) -> i32;
+    pub fn phys_move_and_slide_device(w: *mut phys_world, n: u64, pos: *const f32, motion: *const f32, rot_ijkw: *const f32,
+                                      radius: *const f32, half_length: *const f32, skin: f32, max_slides: u32,
+                                      ignore_body: *const u32, query_mask: *const u16, pos_out: *mut f32, remaining_out: *mut f32,
+                                      status_out: *mut u32, hit_body_out: *mut u32, hit_normal_out: *mut f32,
+                                      hit_point_out: *mut f32) -> i32;
     pub fn phys_overlap(w: *mut phys_world, n: u64, shape_type: *const u32, pos: *const f32, rot_ijkw: *const f32,
                         half_extent: *const f32, ignore_body: *const u32, cap: u64, offsets_out: *mut u64, ids_out: *mut u32) -> i32;
     pub fn phys_set_static_bodies(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32, shape_type: *const u32,
