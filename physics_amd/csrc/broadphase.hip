@@ -571,9 +571,9 @@ int32_t collision_alloc(phys_world* w) {
         PHYS_HIP_TRY(w->row_all.resize(row_plane_floats(kRowPlanes, M)));
         w->flow_vel.free();  // null unless allocated below: per-colour launches only
         if (sz.flow_buffers) {
-            PHYS_HIP_TRY(w->flow_vel.resize(8 * n));
+            PHYS_HIP_TRY(w->flow_vel.resize(kBodyGranuleBytes / sizeof(float) * n));
             // tags of an earlier scene must never look like tags of this one
-            PHYS_HIP_TRY(hipMemsetAsync(w->flow_vel.p, 0, 8 * n * sizeof(float), w->stream));
+            PHYS_HIP_TRY(hipMemsetAsync(w->flow_vel.p, 0, kBodyGranuleBytes * n, w->stream));
             PHYS_HIP_TRY(hipMemsetAsync(w->row_all.p + row_plane_floats(kRowPlaneAcc, M), 0, row_plane_floats(kRowAccPlanes, M) * sizeof(float), w->stream));
             // PHYS_DEBUG_FLOW_EPOCH=<n>: start the tag epoch near its wrap (test of the 16-bit epoch reset)
             w->flow_epoch = debug_switches().flow_epoch;

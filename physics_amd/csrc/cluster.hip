@@ -16,23 +16,20 @@
 // its rows from memory exactly once per iteration, COMPACT (contact points + bias, accumulated impulses, row masses made
 // in iteration 0; lever arms remade from the positions in LDS: solve_manifold_geo) and fetched one or two colour steps
 // ahead. A body all of whose rows lie in one cluster never leaves LDS.
-// A body touched by a row of ANOTHER cluster is `shared`: its updates travel between workgroups through the same
-// data-tagged 16-byte granules as in k_solve_flow (tag = epoch | number of updates applied, write-through stores, loads
-// past the L2; the k-th update of a body may only be made by the row holding ticket k). A shared body of the own cluster
+// A body touched by a row of ANOTHER cluster is `shared`: its updates travel between workgroups through the tagged
+// granules of k_solve_flow (the hand-off: handoff.hpp). A shared body of the own cluster
 // is also kept in LDS with its tag, so a chain of updates that stays inside the workgroup never waits for memory; only an
-// update that follows a REMOTE one polls the granule. The first update of a body reads `vel`, the last one writes it. A
-// body without a home (ghosts; bodies beyond the capacity of dynamic homes) is "another cluster's body" for every row.
-// No deadlock: every workgroup processes its rows in the global (iteration, colour) order, so the earliest unfinished
-// row of the whole solve never waits; all workgroups are resident (grid sized on the host; an all-or-nothing start where
-// other streams' work can run beside the launch: see the kernel); every spin is bounded (timeout -> overflow bit 4 ->
-// PHYS_ERR_HIP). Same arithmetic, same order per body: bit-identical to the other solver paths.
+// update that follows a REMOTE one polls the granule. A body without a home (ghosts; bodies beyond the capacity of dynamic
+// homes) is "another cluster's body" for every row.
+// No deadlock PROVIDED all workgroups are resident (grid sized on the host; an all-or-nothing start where other streams'
+// work can run beside the launch: see the kernel). Same arithmetic, same order per body: bit-identical to the other paths.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
 #include <vector>
 
-#include "kernels.hpp"
+#include "handoff.hpp"
 
 namespace phys {
 
@@ -285,10 +282,6 @@ void launch_cluster_sort(phys_world* w, const ColorPlan& plan, StepCounters* sna
 struct ClusterRowArrays { float4* all; uint64_t cap; };  // (the planes: records.hpp)
 
 constexpr int kClusterThreads = 256;
-#ifndef PHYS_POLL_SLEEP
-#define PHYS_POLL_SLEEP 8
-#endif
-constexpr int kPollSleep = PHYS_POLL_SLEEP;
 template <bool DIAG, bool GUARDED, bool MAT>
 __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kClusterPerCuFull) void k_solve_cluster(StepCounters* ctr, uint32_t iterations, uint32_t epoch,
                                                                   ClusterRowArrays rows, float friction,
@@ -309,18 +302,17 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
     if (GUARDED && attempt != 0u && ctr->cluster_state[attempt - 1u] == 1u) return;  // an earlier attempt went through (see below)
     const uint32_t cluster = blockIdx.x;
     const uint32_t n_colors = ctr->n_colors;
-    const uint32_t etag = epoch << 16;
     const size_t cap = (size_t)rows.cap;
-    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(flow_vel, 0, n_bodies * 32u, 0x00020000);
-    // own bodies into LDS; tag "no update applied yet"
+    const Handoff hv = body_handoff(flow_vel, n_bodies, epoch);
+    const float tag_none = __uint_as_float(hv.tag(0u));  // own bodies into LDS; tag "no update applied yet"
     for (uint32_t sl = threadIdx.x; sl < slots; sl += kClusterThreads) {
         const uint32_t body = cluster_body[(size_t)cluster * slots + sl];
-        float4 a = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(etag)), b = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = b, e = b;
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, tag_none), b = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = b, e = b;
         if (body != 0xFFFFFFFFu) {
             const float4 v0 = reinterpret_cast<const float4*>(vel)[2 * (size_t)body];
             const float4 v1 = reinterpret_cast<const float4*>(vel)[2 * (size_t)body + 1];
             const v3 x = ld3(pos, body);
-            a = make_float4(v0.x, v0.y, v0.z, __uint_as_float(etag));
+            a = make_float4(v0.x, v0.y, v0.z, tag_none);
             b = make_float4(v1.x, v1.y, v1.z, v0.w);
             c = make_float4(x.x, x.y, x.z, 0.0f);
             if (DIAG) e = reinterpret_cast<const float4*>(inv_inertia)[body * inertia_stride];
@@ -477,7 +469,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                     vA = v3_make(la.x, la.y, la.z); wA = v3_make(lb.x, lb.y, lb.z); ima = lb.w;
                     xA = v3_make(lc.x, lc.y, lc.z);
                     if (DIAG) { const float4 li = sa[3]; IA.m[0] = li.x; IA.m[4] = li.y; IA.m[8] = li.z; }
-                    if (modeA == kSideShared) needA = __float_as_uint(la.w) != (etag | tA);  // a remote row made the update before this one
+                    if (modeA == kSideShared) needA = __float_as_uint(la.w) != hv.tag(tA);  // a remote row made the update before this one
                 } else {
                     // a body without a home (dynamic clusters beyond their capacity): like a foreign body B, its constants
                     // came with the row - fetched here, not ahead: the case is rare by construction
@@ -496,7 +488,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                     vB = v3_make(la.x, la.y, la.z); wB = v3_make(lb.x, lb.y, lb.z); imb = lb.w;
                     xB = v3_make(lc.x, lc.y, lc.z);
                     if (DIAG) { const float4 li = sb[3]; IB.m[0] = li.x; IB.m[4] = li.y; IB.m[8] = li.z; }
-                    if (modeB == kSideShared) needB = __float_as_uint(la.w) != (etag | tB);
+                    if (modeB == kSideShared) needB = __float_as_uint(la.w) != hv.tag(tB);
                 } else if (modeB == kSideForeign) {
                     xB = v3_make(fb.x, fb.y, fb.z); imb = fb.w;  // came with the row
                     if (DIAG) { IB.m[0] = fi.x; IB.m[4] = fi.y; IB.m[8] = fi.z; }
@@ -510,25 +502,15 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                     IA = ld_inertia<false>(inv_inertia, h.x * inertia_stride);
                     if (gm.has_b) IB = ld_inertia<false>(inv_inertia, h.y * inertia_stride);
                 }
-                uint32_t sweeps = 0, late = 0;
+                uint32_t sweeps = 0, late = 0, gap;  // (gap: unused, this kernel's waiters sleep a constant)
                 while (needA || needB) {
-                    if (needA) {
-                        const u32x4 g0 = ld_granule(rv, h.x * 32u), g1 = ld_granule(rv, h.x * 32u + 16u);
-                        if (g0.w == (etag | tA) && g1.w == (etag | tA)) { vA = granule_v3(g0); wA = granule_v3(g1); needA = false; }
-                    }
-                    if (needB) {
-                        const u32x4 g0 = ld_granule(rv, h.y * 32u), g1 = ld_granule(rv, h.y * 32u + 16u);
-                        if (g0.w == (etag | tB) && g1.w == (etag | tB)) { vB = granule_v3(g0); wB = granule_v3(g1); needB = false; }
-                    }
+                    if (needA) needA = !take_body(hv, ld_body(hv, h.x), tA, vA, wA, gap);
+                    if (needB) needB = !take_body(hv, ld_body(hv, h.y), tB, vB, wB, gap);
                     if (needA || needB) {
-                        __builtin_amdgcn_s_sleep(kPollSleep);
-                        if ((++sweeps & 63u) == 0u) {
-                            const bool gone = (wall_clock64() - t_start > timeout_ticks) ||
-                                              (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kOvfHandoff);
-                            if (gone) {
-                                late = (needA ? 1u : 0u) | (needB ? 2u : 0u);
-                                flag_overflow(ctr, kOvfHandoff); dead = true; needA = false; needB = false;
-                            }
+                        __builtin_amdgcn_s_sleep(kClusterPollSleep);
+                        if ((++sweeps & 63u) == 0u && handoff_give_up(ctr, t_start, timeout_ticks)) {
+                            late = (needA ? 1u : 0u) | (needB ? 2u : 0u);
+                            flag_overflow(ctr, kOvfHandoff); dead = true; needA = false; needB = false;
                         }
                     }
                 }
@@ -543,20 +525,20 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                     solve_manifold_geo(&gm, it == 0u, (warm_sweep != 0u && it == 0u) ? 1 : 0, MAT ? hraw.z : friction, xA, ima, &IA, xB, imb, &IB, &vA, &wA, &vB, &wB);
                     // ---- write back
                     if (cluster_side_at_home(modeA)) {
-                        s_body[4 * slotA] = make_float4(vA.x, vA.y, vA.z, __uint_as_float(etag | (tA + 1u)));
+                        s_body[4 * slotA] = make_float4(vA.x, vA.y, vA.z, __uint_as_float(hv.tag(tA + 1u)));
                         s_body[4 * slotA + 1] = make_float4(wA.x, wA.y, wA.z, ima);
                     }
                     if (modeA == kSideShared || modeA == kSideForeign) {
                         if (finalA) { st3(vel + 8 * (size_t)h.x, 0, vA); st3(vel + 8 * (size_t)h.x + 4, 0, wA); }  // the masses stay where they are
-                        else if (modeA == kSideForeign || pubA) { st_granule(rv, h.x * 32u, vA, etag | (tA + 1u)); st_granule(rv, h.x * 32u + 16u, wA, etag | (tA + 1u)); }
+                        else if (modeA == kSideForeign || pubA) publish_body(hv, h.x, vA, wA, tA + 1u);
                     }
                     if (cluster_side_at_home(modeB)) {
-                        s_body[4 * slotB] = make_float4(vB.x, vB.y, vB.z, __uint_as_float(etag | (tB + 1u)));
+                        s_body[4 * slotB] = make_float4(vB.x, vB.y, vB.z, __uint_as_float(hv.tag(tB + 1u)));
                         s_body[4 * slotB + 1] = make_float4(wB.x, wB.y, wB.z, imb);
                     }
                     if (modeB == kSideShared || modeB == kSideForeign) {
                         if (finalB) { st3(vel + 8 * (size_t)h.y, 0, vB); st3(vel + 8 * (size_t)h.y + 4, 0, wB); }
-                        else if (modeB == kSideForeign || pubB) { st_granule(rv, h.y * 32u, vB, etag | (tB + 1u)); st_granule(rv, h.y * 32u + 16u, wB, etag | (tB + 1u)); }
+                        else if (modeB == kSideForeign || pubB) publish_body(hv, h.y, vB, wB, tB + 1u);
                     }
                     float4 a0, a1, a2;  // the impulses as the record and the compact rows pack them
                     impulses_pack(gm.pn, gm.pt0, gm.pt1, a0, a1, a2);

@@ -93,25 +93,6 @@ __device__ __forceinline__ m33 ld_inertia(const float* __restrict__ p, uint32_t 
     return M;
 }
 
-// Data-tagged 16-byte granules of the dataflow and cluster solvers: {x, y, z, tag}, written by ONE 16-byte store and
-// read by 16-byte loads only, so the tag is the ready flag of the data beside it (solver.hip, cluster.hip).
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4 ld_granule(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
-    // sc0 | sc1 (what the volatile form emits): read past this XCD's L2. With sc1 alone ("agent scope") a poll could keep
-    // hitting a line its own XCD had cached before the other XCD's write-through store landed: one run in two of two
-    // worlds stepping side by side ended in the hand-off time-out (tools/ghost_cluster_stress.py), none with this form -
-    // and the scope made no difference in time. (Volatile also makes the compiler re-issue the load in every sweep.)
-    return __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, (int)0x80000010);
-}
-__device__ __forceinline__ void st_granule(__amdgpu_buffer_rsrc_t r, uint32_t byte_off, v3 v, uint32_t tag) {
-    u32x4 g;
-    g.x = __float_as_uint(v.x); g.y = __float_as_uint(v.y); g.z = __float_as_uint(v.z); g.w = tag;
-    __builtin_amdgcn_raw_buffer_store_b128(g, r, byte_off, 0, 16);  // sc1: write-through
-}
-__device__ __forceinline__ v3 granule_v3(u32x4 g) {
-    return v3_make(__uint_as_float(g.x), __uint_as_float(g.y), __uint_as_float(g.z));
-}
-
 // Persistent colouring: ONE hash table (a << 32 | b) -> {colour, update stamp} that lives across updates. Open addressing,
 // linear probing, 16-byte entries {key, value word (records.hpp: stamp, manifold index, colour)} (the index of the pair's manifold in
 // the update that stamped the entry: what the next update warm-starts from); at least 1.5 slots per manifold SLOT.

@@ -16,6 +16,7 @@ namespace phys {
 
 constexpr int kMaxColors = 64;         // == PHYS_MAX_COLORS of include/spec/contact_solve.h
 constexpr int kColorCachePeriod = 64;  // == PHYS_COLOR_CACHE_PERIOD (both held by kernels.hpp)
+constexpr uint32_t kHandoffIterationsEnd = 1000;  // solver_iterations from here on: per colour only (update counts are 16-bit: records.hpp)
 
 // launch-size hints taken from an EARLIER step's counters (asynchronous read-back); never needed for
 // correctness
@@ -266,7 +267,7 @@ inline ColorPlan plan_coloring(const PlanInputs& in, const StepHint& h, const De
     // (dynamic clusters hold only the bodies that have manifolds: nothing idles, the row count alone decides)
     const bool dense = cluster_forced || dbg.cluster_min.has_value() || in.cluster_dynamic || 2ull * h.n_manifolds >= 3ull * in.n_owned;
     p.wants_cluster = (in.cluster_count > 0 || in.cluster_dynamic) && h.valid && !small && dense && h.n_manifolds >= cluster_min &&
-                      !(in.flags & PHYS_FLAG_SOLVER_PER_COLOR) && in.solver_iterations > 0 && in.solver_iterations < 1000 &&
+                      !(in.flags & PHYS_FLAG_SOLVER_PER_COLOR) && in.solver_iterations > 0 && in.solver_iterations < kHandoffIterationsEnd &&
                       h.n_colors > 0;
     // ... unless the dataflow kernel is the faster one for this many rows and colours (flow_quad_beats_cluster; only where it
     // may take the whole chip: PHYS_FLAG_EXCLUSIVE_GPU, one world on the device). PHYS_DEBUG_NO_FLOW_PREFERENCE: never
@@ -319,10 +320,9 @@ inline SolverPlan plan_solver(const PlanInputs& in, const StepHint& h, const Deb
     // the dataflow kernel wins while a colour class is too small to fill the chip (launch / latency bound);
     // beyond that the per-colour launches stream better. Both give the same bits, so the choice may change
     // from step to step.
-    // (tickets are 16-bit: iterations x 64 colours must stay below 65536)
     // PHYS_DEBUG_FLOW_MAX=<manifolds>: move the dataflow / per-colour crossover (measurements only; same bits either way)
     const uint64_t flow_max = dbg.flow_max.value_or(kFlowMaxManifolds);
-    const bool flow = cluster || (in.flow_vel && h.valid && m_hint <= flow_max && in.solver_iterations > 0 && in.solver_iterations < 1000);
+    const bool flow = cluster || (in.flow_vel && h.valid && m_hint <= flow_max && in.solver_iterations > 0 && in.solver_iterations < kHandoffIterationsEnd);
     if (cluster) {
         p.path = SolverPath::Cluster;
         return p;

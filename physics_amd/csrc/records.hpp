@@ -64,6 +64,25 @@ PHYS_REC ClusterSide cluster_side_decode(uint32_t word, bool side_b) {
 PHYS_REC bool cluster_side_rides(uint32_t word, bool side_b) { return cluster_side_decode(word, side_b).mode == kSideForeign; }
 PHYS_REC bool cluster_side_at_home(uint32_t mode) { return mode == kSideOwn || mode == kSideShared; }
 
+// ---- hand-off tag (.w of a granule of the single-launch solvers) ---------------------------------------
+// epoch of the solve in the high half | updates applied to the body (impulse granules: sweeps finished) in the low half
+constexpr uint32_t kTagHalfBits = 16, kTagHalfMask = 0xFFFFu, kHandoffEpochMax = kTagHalfMask;
+constexpr uint32_t kGranuleBytes = 16, kBodyGranuleBytes = 2 * kGranuleBytes;  // a body in flow_vel: {v, tag} {w, tag}
+static_assert(((kHandoffIterationsEnd - 1u) + 1u /* the warm sweep */) * (uint32_t)kMaxColors <= kTagHalfMask,
+              "a body is updated at most once per sweep and colour: the count fits its half of the tag");
+PHYS_REC constexpr uint32_t handoff_tag(uint32_t epoch, uint32_t updates) { return (epoch << kTagHalfBits) | updates; }
+PHYS_REC constexpr uint32_t handoff_tag_from(uint32_t tag0, uint32_t updates) { return tag0 | updates; }  // tag0 = handoff_tag(epoch, 0), kept by the kernels
+PHYS_REC constexpr uint32_t handoff_tag_epoch(uint32_t tag) { return tag >> kTagHalfBits; }
+PHYS_REC constexpr uint32_t handoff_tag_updates(uint32_t tag) { return tag & kTagHalfMask; }
+// how many updates a row holding `ticket` is away from what it saw: another epoch's tag counts as nothing seen; never below 1
+PHYS_REC constexpr uint32_t handoff_gap(uint32_t seen_tag, uint32_t epoch, uint32_t ticket) {
+    const uint32_t seen = handoff_tag_epoch(seen_tag) == epoch ? handoff_tag_updates(seen_tag) : 0u;
+    return ticket > seen ? ticket - seen : 1u;
+}
+// the host's step from one solve's epoch to the next; clear: tags would repeat, so every granule is zeroed first
+struct EpochStep { uint32_t epoch; bool clear; };
+PHYS_REC constexpr EpochStep handoff_epoch_next(uint32_t epoch) { return epoch + 1u > kHandoffEpochMax ? EpochStep{1u, true} : EpochStep{epoch + 1u, false}; }
+
 // ---- colour-table value word (the second 8 bytes of a table slot) ---------------------------------------------------------
 // stamp of the update that wrote it (32) | index of the pair's manifold in that update (26) | colour (6)
 constexpr uint32_t kUncolored = 0xFFFFFFFFu;  // man_color of a manifold that kept no colour (narrowphase.hip -> coloring.hip)

@@ -17,7 +17,7 @@
 // (inverse inertia diagonal / full).
 #include <cstdlib>
 
-#include "kernels.hpp"
+#include "handoff.hpp"
 
 namespace phys {
 
@@ -449,43 +449,15 @@ __global__ __launch_bounds__(kTailThreads) void k_solve_tail(const StepCounters*
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Single-launch dataflow solver. Same arithmetic and the same ORDER OF UPDATES PER BODY as the per-colour
-// launches (iterations outermost, colours ascending), so the results are bit-identical; what changes is how
-// the order is enforced. Instead of a kernel boundary after every colour of every iteration (8 x n_colours
-// dependent launches of 5-20 us), every body carries a ticket: the k-th update of body A in solve order may
-// only be made by the row holding ticket k for A (k = iteration * deg(A) + rank of the row's colour among A's
-// colours; k_rows_build). In-flight velocities live in `flow_vel` as two 16-byte granules {x, y, z, tag} whose
-// tag = (epoch << 16) | number of updates applied, i.e. THE DATA IS ITS OWN READY FLAG: a row polls its bodies'
-// granules (ld_granule, kernels.hpp: sc0 sc1 loads, served past the XCD's L2) until both tags equal its ticket,
-// solves, and stores them back (sc1 = write-through stores) with tag + 1. One hop costs ~0.7-1.0 us
-// (tools/hop_bench.hip) instead of a launch, and rows of different colours / iterations overlap wherever the
-// contact graph allows.
-//   * the FIRST update of a body reads the plain `vel` record (written by the previous kernel), the LAST one
-//     writes it (read by the next kernel): flow_vel never needs initialising; stale tags of earlier steps carry
-//     another epoch;
-//   * accumulated impulses cross iterations the same way (row_acc {pn, pt0, pt1, tag = iteration});
-//   * work items (iteration, chunk of blockDim rows) are handed out by an atomic ticket in solve order, so every
-//     dependency of an item was taken EARLIER by a workgroup that is running: no co-residency assumption, no
-//     deadlock by construction; and every spin is bounded (timeout -> overflow bit 4 -> PHYS_ERR_HIP at sync).
-// Granule discipline follows the guide's data-tagged hand-off: each granule is written by ONE 16-byte sc1
-// store and only ever read by 16-byte sc0 sc1 loads. Waiting waves cost issue slots and L2 bandwidth, so the launch
-// is sized to about one wave per SIMD (launch_solver) and waiters back off by their distance in hops.
-
-// back-off of a waiting dataflow wave, in proportion to how many hops away the nearest waiting lane is, and its bounded
-// spin: true when the wave gives up (time-out, or another wave gave up: overflow bit 4, flagged by lane 0)
-__device__ __forceinline__ bool flow_backoff(StepCounters* ctr, bool done, uint32_t gap, uint32_t& sweeps, long long t_start,
-                                             long long timeout_ticks) {
-    if (__any(!done && gap <= 1u)) __builtin_amdgcn_s_sleep(1);
-    else if (__any(!done && gap <= 4u)) __builtin_amdgcn_s_sleep(40);
-    else __builtin_amdgcn_s_sleep(127);
-    if ((++sweeps & 63u) != 0u) return false;
-    const bool dead = (wall_clock64() - t_start > timeout_ticks) ||
-                      (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kOvfHandoff);
-    if (dead && (threadIdx.x & 63u) == 0u) flag_overflow(ctr, kOvfHandoff);  // wave-uniform: both inputs are
-    return dead;
-}
-
-
+// Single-launch dataflow solver. Same arithmetic and the same ORDER OF UPDATES PER BODY as the per-colour launches (iterations
+// outermost, colours ascending), so the results are bit-identical; what changes is how the order is enforced. Instead of a
+// kernel boundary after every colour of every iteration (8 x n_colours dependent launches of 5-20 us), the k-th update of
+// body A in solve order may only be made by the row holding ticket k for A (k = iteration * deg(A) + rank of the row's colour
+// among A's colours; k_rows_build): a row waits for its bodies' tagged granules and publishes them with the next tag, and the
+// accumulated impulses cross sweeps the same way (the hand-off: handoff.hpp). One hop costs ~0.7-1.0 us
+// (tools/hop_bench.hip) instead of a launch, and rows of different colours / iterations overlap wherever the contact graph
+// allows. Work items (iteration, chunk of blockDim rows) are handed out by an atomic ticket in solve order, so every dependency
+// of an item was taken EARLIER by a workgroup that is running: no co-residency assumption, no deadlock by construction.
 // Work items are SOFTWARE-PIPELINED inside a workgroup: while item k waits for its bodies and is solved, the rows of
 // item k + 1 (its ticket is taken one item ahead) are already on their way, and so are - issued once those rows have
 // arrived, i.e. behind the Jacobians of item k - the records of its bodies. At one wave per SIMD nobody else hides
@@ -510,15 +482,11 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
     const uint32_t nchunks = (M + blockDim.x - 1) / blockDim.x;
     const uint32_t total = nchunks * iterations;
     const uint32_t cap = (uint32_t)rows.cap;  // collision_alloc: 64 * cap < 4 GiB (32-bit buffer offsets)
-    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(flow_vel, 0, n_bodies * 32u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(rows.acc, 0, cap * (16u * kRowAccPlanes), 0x00020000);
-    const uint32_t etag = epoch << 16;
+    const Handoff hv = body_handoff(flow_vel, n_bodies, epoch), ha = impulse_handoff(rows.acc, cap, epoch);
     const long long t_start = wall_clock64();
     auto take = [&]() -> uint32_t {  // next work item in solve order (block-uniform)
         __syncthreads();
-        if (threadIdx.x == 0)
-            s_item = (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kOvfHandoff)
-                         ? 0xFFFFFFFFu : atomicAdd(&ctr->flow_ticket, 1u);
+        if (threadIdx.x == 0) s_item = handoff_abandoned(ctr) ? 0xFFFFFFFFu : atomicAdd(&ctr->flow_ticket, 1u);
         __syncthreads();
         return s_item;
     };
@@ -610,34 +578,19 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
         for (;;) {
             uint32_t gap = 0;
             if (!done) {
-                u32x4 a0, a1, b0, b1, p[4];
-                if (needA) { a0 = ld_granule(rv, R.a * 32u); a1 = ld_granule(rv, R.a * 32u + 16u); }
-                if (needB) { b0 = ld_granule(rv, R.b * 32u); b1 = ld_granule(rv, R.b * 32u + 16u); }
+                BodyGranules a, b; u32x4 p[4];
+                if (needA) a = ld_body(hv, R.a);
+                if (needB) b = ld_body(hv, R.b);
                 if (needAcc) {
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) if (k < R.sm.count) p[k] = ld_granule(ra, (k * cap + d) * 16u);
+                    for (int k = 0; k < 4; ++k) if (k < R.sm.count) p[k] = ld_granule(ha.buf, impulse_granule(k, cap, d));
                 }
-                if (needA) {
-                    const uint32_t want = etag | tA;
-                    if (a0.w == want && a1.w == want) { vA = granule_v3(a0); wA = granule_v3(a1); needA = false; }
-                    else {
-                        const uint32_t seen = (a0.w >> 16) == epoch ? (a0.w & 0xFFFFu) : 0u;
-                        gap = tA > seen ? tA - seen : 1u;
-                    }
-                }
-                if (needB) {
-                    const uint32_t want = etag | tB;
-                    if (b0.w == want && b1.w == want) { vB = granule_v3(b0); wB = granule_v3(b1); needB = false; }
-                    else {
-                        const uint32_t seen = (b0.w >> 16) == epoch ? (b0.w & 0xFFFFu) : 0u;
-                        const uint32_t g = tB > seen ? tB - seen : 1u;
-                        gap = g > gap ? g : gap;
-                    }
-                }
+                if (needA) needA = !take_body(hv, a, tA, vA, wA, gap);
+                if (needB) { uint32_t g = 0; needB = !take_body(hv, b, tB, vB, wB, g); gap = g > gap ? g : gap; }
                 if (needAcc) {
                     bool all = true;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) if (k < R.sm.count) all = all && p[k].w == (etag | it);
+                    for (int k = 0; k < 4; ++k) if (k < R.sm.count) all = all && p[k].w == ha.tag(it);
                     if (all) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) if (k < R.sm.count) {
@@ -655,16 +608,15 @@ __global__ __launch_bounds__(256) void k_solve_flow(StepCounters* __restrict__ c
                     else solve_manifold(&R.sm, &J, friction, &vA, &wA, &vB, &wB, apply_only ? 1 : 0);
                     // publish: bodies first (they are what other rows wait for)
                     if (finalA) { BodyVel o; o.v = vA; o.inv_mass = ima; o.w = wA; o.mass = massA; st_vel(vel, R.a, o); }
-                    else { st_granule(rv, R.a * 32u, vA, etag | (tA + 1u)); st_granule(rv, R.a * 32u + 16u, wA, etag | (tA + 1u)); }
+                    else publish_body(hv, R.a, vA, wA, tA + 1u);
                     if (R.sm.has_b) {
                         if (finalB) { BodyVel o; o.v = vB; o.inv_mass = imb; o.w = wB; o.mass = massB; st_vel(vel, R.b, o); }
-                        else { st_granule(rv, R.b * 32u, vB, etag | (tB + 1u)); st_granule(rv, R.b * 32u + 16u, wB, etag | (tB + 1u)); }
+                        else publish_body(hv, R.b, vB, wB, tB + 1u);
                     }
                     if (!last_it) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) if (k < R.sm.count)
-                            st_granule(ra, (k * cap + d) * 16u, v3_make(R.sm.row[k].pn, R.sm.row[k].pt[0], R.sm.row[k].pt[1]),
-                                       etag | (it + 1u));
+                            ha.publish(impulse_granule(k, cap, d), v3_make(R.sm.row[k].pn, R.sm.row[k].pt[0], R.sm.row[k].pt[1]), it + 1u);
                     } else if (wj.man_prev) {  // the solve's last sweep: remembered for the next update
                         store_final_impulses(wj, d, R.sm);
                     }
@@ -830,10 +782,8 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
     const uint32_t nchunks = (M + rows_per_item - 1) / rows_per_item;
     const uint32_t total = nchunks * iterations;
     const uint32_t cap = (uint32_t)rows.cap;
-    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(flow_vel, 0, n_bodies * 32u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(rows.acc, 0, cap * (16u * kRowAccPlanes), 0x00020000);
-    const uint32_t etag = epoch << 16;
-    const uint32_t q = threadIdx.x & 3u;      // 0: vA, 1: wA, 2: vB, 3: wB
+    const Handoff hv = body_handoff(flow_vel, n_bodies, epoch), ha = impulse_handoff(rows.acc, cap, epoch);
+    const uint32_t q = threadIdx.x & 3u;     // 0: vA, 1: wA, 2: vB, 3: wB
     const bool side_a = q < 2u, angular = (q & 1u) != 0u;
     const long long t_start = wall_clock64();
     const v3 zero = v3_make(0.0f, 0.0f, 0.0f);
@@ -842,14 +792,10 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
     // launch whose whole time is such chains: C2 0.078 -> 0.054 ms per solve, 6400 -> 7700 steps/s. (Measured and dropped:
     // the ticket of the next item asked for when an item begins - an item reserved by a workgroup that is still busy is an
     // item nobody else may start: C2 0.095 ms.)
-    // No deadlock: an item waits only for items before it in the global order, and every workgroup walks its own items in
-    // increasing order, so the earliest unfinished item of the launch belongs to a workgroup with nothing older left to
-    // wait for - PROVIDED every workgroup of the launch gets to run. The grid is at most 224 workgroups of 256 threads
-    // at <= 160 registers: three fit a CU, so a third of the chip holds the whole launch even beside other streams'
-    // kernels; a workgroup that starts late delays its items (bounded spins: time-out after 3 s, never a silent hang).
-    // k_solve_flow (one workgroup per CU at 370 registers) needs the whole chip for that and keeps its tickets.
+    // No deadlock PROVIDED every workgroup of the launch gets to run: at most 224 workgroups, three fit a CU (the argument,
+    // and why k_solve_flow keeps its tickets: DESIGN.md section 26).
     for (uint32_t L = blockIdx.x;; L += gridDim.x) {
-        if (__hip_atomic_load(&ctr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kOvfHandoff) return;  // somebody gave up
+        if (handoff_abandoned(ctr)) return;  // somebody gave up
         if (L >= total) return;
         const uint32_t it = L / nchunks, chunk = L - it * nchunks;
         const bool last_it = it + 1 == iterations;
@@ -885,18 +831,11 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
             uint32_t gap = 0;
             if (!done) {
                 u32x4 g, p;
-                if (need) g = ld_granule(rv, s.body * 32u + (angular ? 16u : 0u));
-                if (need_acc) p = ld_granule(ra, (q * cap + d) * 16u);
-                if (need) {
-                    const uint32_t want = etag | ticket;
-                    if (g.w == want) { s.x = granule_v3(g); need = false; }
-                    else {
-                        const uint32_t seen = (g.w >> 16) == epoch ? (g.w & 0xFFFFu) : 0u;
-                        gap = ticket > seen ? ticket - seen : 1u;
-                    }
-                }
+                if (need) g = ld_granule(hv.buf, body_granule(s.body, angular));
+                if (need_acc) p = ld_granule(ha.buf, impulse_granule(q, cap, d));
+                if (need) need = !hv.take(g, ticket, s.x, gap);
                 if (need_acc) {
-                    if (p.w == (etag | it)) { my_acc = granule_v3(p); need_acc = false; }
+                    if (p.w == ha.tag(it)) { my_acc = granule_v3(p); need_acc = false; }
                     else if (gap == 0) gap = 1;
                 }
             }
@@ -916,9 +855,9 @@ __global__ __launch_bounds__(256) void k_solve_flow_quad(StepCounters* __restric
                     if (final_update)
                         reinterpret_cast<float4*>(vel)[2 * (size_t)s.body + (angular ? 1 : 0)] = make_float4(s.x.x, s.x.y, s.x.z, s.keep_w);
                     else
-                        st_granule(rv, s.body * 32u + (angular ? 16u : 0u), s.x, etag | (ticket + 1u));
+                        hv.publish(body_granule(s.body, angular), s.x, ticket + 1u);
                 }
-                if (!last_it && q < s.count) st_granule(ra, (q * cap + d) * 16u, quad_point_impulses(s, q), etag | (it + 1u));
+                if (!last_it && q < s.count) ha.publish(impulse_granule(q, cap, d), quad_point_impulses(s, q), it + 1u);
                 if (last_it && wj.man_prev) store_final_point_impulses(wj, d, q, quad_point_impulses(s, q));
                 done = true;
             }
@@ -1050,14 +989,15 @@ void launch_solver(phys_world* w, float dt, const SolverPlan& plan, const ColorP
     table.stamp = coloring.stamp;
     table.all = coloring.rebuild ? 1u : 0u;
     table.man_color = w->man_color.p; table.man_prio = w->man_prio.p;
-    if (flow && ++w->flow_epoch > 0xFFFFu) {
+    const EpochStep next = flow ? handoff_epoch_next(w->flow_epoch) : EpochStep{w->flow_epoch, false};
+    w->flow_epoch = next.epoch;
+    if (next.clear) {
         // tags would repeat: forget every old one. AHEAD of k_rows_build: on a cluster step that kernel writes the constants
         // of foreign bodies into the impulse planes (with flow != 0 it never writes the impulses there), and a memset
         // behind it wiped them - every 65535th solve ran with x = 0, 1/m = 0, I^-1 = 0 for those rows
         PHYS_PROF(w, PHYS_STAGE_MISC);
-        (void)hipMemsetAsync(w->flow_vel.p, 0, 8 * w->n * sizeof(float), s);
+        (void)hipMemsetAsync(w->flow_vel.p, 0, kBodyGranuleBytes * w->n, s);
         (void)hipMemsetAsync(rows.acc, 0, row_plane_floats(kRowAccPlanes, cap) * sizeof(float), s);
-        w->flow_epoch = 1;
     }
     // materials: once a material call was made, the material instances of every kernel below - same
     // path choice, same launch sizes; they take the friction from the row. With every material at its default they give the

@@ -235,10 +235,8 @@ struct phys_world {
     // ONE allocation of 16 planes of cap float4 each (the two plane numberings: records.hpp), so a kernel can address
     // plane p of row d as all[p * cap + d] without choosing a pointer
     phys::DevBuf<float> row_all;
-    // single-launch dataflow solver (k_solve_flow): in-flight body velocities travel between workgroups as
-    // 16-byte granules {x, y, z, tag} (the tag says WHICH update of that body the data is: the data is its own
-    // ready flag)
-    phys::DevBuf<float> flow_vel;    // 8 per body: {v.xyz, tag} {w.xyz, tag}; null = per-colour launches only
+    // single-launch solvers: in-flight body velocities travel between workgroups as tagged granules (handoff.hpp)
+    phys::DevBuf<float> flow_vel;    // kBodyGranuleBytes per body: {v.xyz, tag} {w.xyz, tag}; null = per-colour launches only
     // cluster solver (cluster.hip): spatial clusters fixed at phys_set_bodies, rows sorted by (cluster, colour) per step
     uint32_t cluster_count = 0, cluster_slots = 0;  // 0 clusters: not available for this scene (dynamic: set per update)
     bool cluster_dynamic = false;           // clusters are remade every update from the bodies that have manifolds (cluster.hip)

@@ -91,6 +91,41 @@ static void side_word() {
     CHECK("at home", cluster_side_at_home(0) && cluster_side_at_home(1) && !cluster_side_at_home(2) && !cluster_side_at_home(3), 1);
 }
 
+static void handoff_tag_word() {
+    // epoch bits 16-31 | updates applied bits 0-15; a body's granules in flow_vel: 32 bytes, two of 16
+    CHECK("tag", handoff_tag(0xABCDu, 0x1234u), 0xABCD1234u);
+    CHECK("halves", kTagHalfBits, 16); CHECK("halves", kTagHalfMask, 65535); CHECK("largest epoch", kHandoffEpochMax, 65535);
+    CHECK("granule", kGranuleBytes, 16); CHECK("a body's granules", kBodyGranuleBytes, 32);
+    for (uint32_t epoch = 0; epoch <= 0xFFFFu; ++epoch)
+        for (uint32_t updates : {0u, 1u, 63u, 64u, 64000u, 0xFFFFu}) {
+            const uint32_t t = handoff_tag(epoch, updates);
+            CHECK("tag round trip", handoff_tag_epoch(t), epoch); CHECK("tag round trip", handoff_tag_updates(t), updates);
+            CHECK("tag from the epoch in place", handoff_tag_from(handoff_tag(epoch, 0u), updates), t);
+        }
+    // the gap of a row holding `ticket` in epoch 7: {tag seen, ticket, gap}
+    const uint32_t gaps[][3] = {
+        {(7u << 16) | 12u, 10u, 1u},     // same epoch, ahead of the ticket (cannot happen; never below 1)
+        {(7u << 16) | 3u, 10u, 7u},      // same epoch, behind it
+        {(7u << 16) | 9u, 10u, 1u},      // ... by one
+        {(7u << 16) | 10u, 10u, 1u},     // equal (the other granule of the body is the one that lags)
+        {(7u << 16) | 0u, 64000u, 64000u},
+        {(6u << 16) | 9u, 10u, 10u},     // a foreign epoch: nothing seen
+        {(0x8007u << 16) | 9u, 10u, 10u},
+        {0u, 10u, 10u}, {0u, 1u, 1u},    // tag 0: a cleared buffer
+    };
+    for (const auto& g : gaps) CHECK("gap", handoff_gap(g[0], 7u, g[1]), g[2]);
+    CHECK("gap in epoch 0 from a cleared buffer", handoff_gap(0u, 0u, 5u), 5);
+    // the sweep limit: (999 iterations + the warm sweep) x 64 colours of updates fit 16 bits; 1024 sweeps would not
+    CHECK("iterations end", kHandoffIterationsEnd, 1000);
+    CHECK("largest update count", (999 + 1) * 64, 64000); CHECK("fits", (999 + 1) * 64 <= 65535, 1); CHECK("1024 sweeps do not", 1024 * 64 > 65535, 1);
+    // the host's epoch step: {epoch, next, clear}
+    const uint32_t steps[][3] = {{0u, 1u, 0u}, {1u, 2u, 0u}, {0xFFFEu, 0xFFFFu, 0u}, {0xFFFFu, 1u, 1u}};
+    for (const auto& s : steps) {
+        const EpochStep n = handoff_epoch_next(s[0]);
+        CHECK("epoch step", n.epoch, s[1]); CHECK("epoch step, clear", n.clear, s[2]);
+    }
+}
+
 static void table_value() {
     // stamp bits 32-63 | manifold index bits 6-31 | colour bits 0-5
     CHECK("table", table_value_encode(0xDEADBEEFu, 0x2ABCDEFu, 37u), (0xDEADBEEFull << 32) | (0x2ABCDEFull << 6) | 37ull);
@@ -212,6 +247,7 @@ static void debug_notes() {
 int main() {
     ticket();
     side_word();
+    handoff_tag_word();
     table_value();
     impulses();
     manifold_record();
