@@ -372,6 +372,68 @@ int32_t phys_move_and_slide_device(phys_world* w, uint64_t n, const float* pos, 
                                    const float* radius, const float* half_length, float skin, uint32_t max_slides,
                                    const uint32_t* ignore_body, const uint16_t* query_mask, float* pos_out, float* remaining_out,
                                    uint32_t* status_out, uint32_t* hit_body_out, float* hit_normal_out, float* hit_point_out);
+/* phys_penetration and phys_depenetrate: how deep a capsule (core pos[i] +- half_length[i] * a, a the y axis turned by rot_ijkw[i]
+ * and used as given, radius radius[i]: phys_capsulecast's capsule; half_length == 0 is a ball) sits in what surrounds it, and the
+ * loop that pushes it out. The rule is stated once, in include/spec/depenetrate.h; depths and normals are
+ * the narrow phase's own capsule functions (include/spec/collide.h) with the query as body A. Targets, ids, ignore_body,
+ * query_mask, ghost slots and the current-pose rule are phys_capsulecast[_filtered]'s: owned bodies with a shape and a finite
+ * pose, static colliders (PHYS_STATIC_ID_BIT | k), the ground (PHYS_RAY_GROUND) with PHYS_FLAG_GROUND_PLANE. Read-only: nothing
+ * an update or phys_broadphase reads is written, sticky update errors are neither reported nor cleared, and the calls work
+ * with or without PHYS_FLAG_COLLISIONS. Each call builds ONE query grid (not grown) and launches ONE kernel.
+ * phys_penetration: one probe, nothing moves. For each capsule the deepest target within max_gap of it:
+ *   - body_out: its id, PHYS_RAY_MISS when nothing lies within max_gap. depth_out: how far the capsule reaches into it
+ *     (>= -max_gap; negative: the clearance between them; -inf for a miss). normal_out (may be NULL): the unit direction out of
+ *     the target, from the target towards the capsule (the casts' convention; (0,1,0) on the ground; (0,-1,0) where the
+ *     cores coincide, the narrow phase's (0,1,0) fallback seen from the target; zeros for a miss): moving the capsule by
+ *     normal * depth brings the two to touch.
+ *   - the greatest depth wins, an exact tie goes to the smaller id (bodies, then statics, then the ground).
+ *   - a target whose clearance equals max_gap to within rounding may go either way: candidates are first rejected by their
+ *     boxes against the capsule's box grown by max_gap. phys_depenetrate acts at skin / 2 of a gap of skin, far from that edge.
+ *   - where the capsule's core lies inside a box, the depth is the narrow phase's: through the box face of least overlap
+ *     with the core, or across a box edge where that is clearly shallower; one push can leave a sliver of overlap, which
+ *     the next round of phys_depenetrate removes.
+ *   - a non-finite pos, rot, radius or half_length, a negative radius or half_length, or half_length > 3.4e38: a miss.
+ * phys_depenetrate: per capsule, up to max_iters rounds of: probe with max_gap = skin; when the deepest target is nearer than
+ * skin / 2 (depth > -skin / 2), move by normal * (depth + skin), out of it and a skin beyond; otherwise stop.
+ *   - pos_out: where the capsule ends (pos itself, bit for bit, when nothing was nearer than skin / 2).
+ *   - status_out: the number of pushes (0 .. 8) in bits 0-3, and
+ *       PHYS_DEPEN_STUCK    max_iters pushes were made and the capsule is still nearer than skin / 2 to something (between two
+ *                           opposed targets, or in a crease too acute for max_iters rounds); pos_out is finite, the last push's.
+ *       PHYS_DEPEN_INVALID  the query's own values are unusable (as for phys_penetration): pos_out = pos, no pushes.
+ *     A status without flags means clear: at least skin / 2 from every target, so a phys_move_and_slide from pos_out with a
+ *     skin no larger does not start BLOCKED.
+ *   - push slots (each array may be NULL): slot k of query i lies at index k * n + i (iteration-major): the id, the normal and
+ *     the depth phys_penetration reports where the k-th push began. Every slot is written; an unused one holds PHYS_RAY_MISS
+ *     and zeros.
+ *   - one target per round, the deepest first: one plane takes one push, two perpendicular planes two, an acute crease
+ *     converges geometrically. Nothing is averaged.
+ *   - skin == 0 is allowed, but a push then ends touching and round-off decides whether the next probe pushes again: such a
+ *     query tends to end touching or STUCK. Use a skin around contact_margin.
+ *   - PHYS_ERR_INVALID_ARG: n >= 2^31, a NULL pos, radius or half_length with n > 0, a NULL body_out or depth_out
+ *     (phys_penetration) or pos_out or status_out (phys_depenetrate) with n > 0, a non-finite or negative max_gap or skin,
+ *     max_iters outside 1 .. PHYS_DEPEN_MAX_ITERS. n == 0 is a no-op.
+ * The plain calls take host arrays and return with the outputs written; the _device calls take device pointers and only enqueue
+ * on the world's stream. query_mask NULL = no filtering (there are no _filtered twins). PHYS_ABI_VERSION is unchanged: a caller
+ * tells an older library by the missing symbols. */
+#define PHYS_DEPEN_MAX_ITERS 8u
+#define PHYS_DEPEN_STUCK 0x100u
+#define PHYS_DEPEN_INVALID 0x400u
+int32_t phys_penetration(phys_world* w, uint64_t n, const float* pos /*3n*/, const float* rot_ijkw /*4n, NULL = identity*/,
+                         const float* radius /*n*/, const float* half_length /*n*/, float max_gap,
+                         const uint32_t* ignore_body /*n, NULL = none*/, const uint16_t* query_mask /*n, NULL = no filtering*/,
+                         uint32_t* body_out /*n*/, float* depth_out /*n*/, float* normal_out /*3n, may be NULL*/);
+int32_t phys_penetration_device(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw, const float* radius,
+                                const float* half_length, float max_gap, const uint32_t* ignore_body, const uint16_t* query_mask,
+                                uint32_t* body_out, float* depth_out, float* normal_out);
+int32_t phys_depenetrate(phys_world* w, uint64_t n, const float* pos /*3n*/, const float* rot_ijkw /*4n, NULL = identity*/,
+                         const float* radius /*n*/, const float* half_length /*n*/, float skin, uint32_t max_iters,
+                         const uint32_t* ignore_body /*n, NULL = none*/, const uint16_t* query_mask /*n, NULL = no filtering*/,
+                         float* pos_out /*3n*/, uint32_t* status_out /*n*/, uint32_t* hit_body_out /*max_iters*n, may be NULL*/,
+                         float* hit_normal_out /*3*max_iters*n, may be NULL*/, float* hit_depth_out /*max_iters*n, may be NULL*/);
+int32_t phys_depenetrate_device(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw, const float* radius,
+                                const float* half_length, float skin, uint32_t max_iters, const uint32_t* ignore_body,
+                                const uint16_t* query_mask, float* pos_out, uint32_t* status_out, uint32_t* hit_body_out,
+                                float* hit_normal_out, float* hit_depth_out);
 /* phys_overlap: for each query shape (shape_type SPHERE, BOX or CAPSULE with the bodies' half_extent conventions, at pos
  * with the unit quaternion rot_ijkw, NULL = identity), every target whose closed shape intersects it (touching counts).
  *   - output (CSR): query i's ids are ids_out[offsets_out[i] .. offsets_out[i + 1]), ascending and each once: bodies,

@@ -281,6 +281,18 @@ PROTOTYPES["phys_move_and_slide"] = (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f
 PROTOTYPES["phys_move_and_slide_device"] = (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_float, C.c_uint32]
                                             + [C.c_void_p] * 8)
 
+# depenetration: pos, rot, radius, half_length, max_gap, ignore, query_mask; body_out, depth_out, normal_out - and pos, rot, radius,
+# half_length, skin, max_iters, ignore, query_mask; pos_out, status_out, hit_body_out, hit_normal_out, hit_depth_out (the device
+# variants: every array a c_void_p)
+DEPEN_MAX_ITERS = 8
+DEPEN_STUCK, DEPEN_INVALID = 0x100, 0x400
+PROTOTYPES["phys_penetration"] = (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, C.c_float, u32p, u16p, u32p, f32p, f32p])
+PROTOTYPES["phys_penetration_device"] = (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 5)
+PROTOTYPES["phys_depenetrate"] = (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, C.c_float, C.c_uint32, u32p, u16p,
+                                              f32p, u32p, u32p, f32p, f32p])
+PROTOTYPES["phys_depenetrate_device"] = (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.c_float, C.c_uint32]
+                                         + [C.c_void_p] * 7)
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libphysics_hip.so")
 _lib = None
 

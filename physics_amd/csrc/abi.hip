@@ -979,6 +979,59 @@ int32_t phys_move_and_slide(phys_world* w, uint64_t n, const float* pos, const f
     return PHYS_OK;
 }
 
+// depenetration: both calls are one DepenBatch (probe: phys_penetration); on device arrays checked and
+// enqueued, on host arrays staged as the casts are (inputs in w->stage, outputs in w->rc_out), run, read back and waited for
+static int32_t depen_device(phys_world* w, const DepenBatch& b) {
+    ENTER(w);
+    if (const char* bad = depen_args_error(b)) return fail(PHYS_ERR_INVALID_ARG, bad);
+    if (b.n == 0) return PHYS_OK;
+    return launch_depen(w, b);
+}
+
+static int32_t depen_host(phys_world* w, const DepenBatch& b) {
+    ENTER(w);
+    if (const char* bad = depen_args_error(b)) return fail(PHYS_ERR_INVALID_ARG, bad);
+    if (b.n == 0) return PHYS_OK;
+    Staging in{w, w->stage}, out{w, w->rc_out};
+    stage_depen(b, in, out);
+    PHYS_TRY(in.reserve());
+    PHYS_TRY(out.reserve());
+    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
+    PHYS_TRY(launch_depen(w, staged_depen(b, in.buf.p, out.buf.p)));
+    PHYS_TRY(out.copy(hipMemcpyDeviceToHost));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    return PHYS_OK;
+}
+
+int32_t phys_penetration(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw, const float* radius, const float* half_length,
+                         float max_gap, const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* depth_out,
+                         float* normal_out) {
+    return depen_host(w, {n, pos, rot_ijkw, radius, half_length, max_gap, 1u, true, ignore_body, query_mask,
+                          nullptr, nullptr, body_out, normal_out, depth_out});
+}
+
+int32_t phys_penetration_device(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw, const float* radius,
+                                const float* half_length, float max_gap, const uint32_t* ignore_body, const uint16_t* query_mask,
+                                uint32_t* body_out, float* depth_out, float* normal_out) {
+    return depen_device(w, {n, pos, rot_ijkw, radius, half_length, max_gap, 1u, true, ignore_body, query_mask,
+                            nullptr, nullptr, body_out, normal_out, depth_out});
+}
+
+int32_t phys_depenetrate(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw, const float* radius, const float* half_length,
+                         float skin, uint32_t max_iters, const uint32_t* ignore_body, const uint16_t* query_mask, float* pos_out,
+                         uint32_t* status_out, uint32_t* hit_body_out, float* hit_normal_out, float* hit_depth_out) {
+    return depen_host(w, {n, pos, rot_ijkw, radius, half_length, skin, max_iters, false, ignore_body, query_mask,
+                          pos_out, status_out, hit_body_out, hit_normal_out, hit_depth_out});
+}
+
+int32_t phys_depenetrate_device(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw, const float* radius,
+                                const float* half_length, float skin, uint32_t max_iters, const uint32_t* ignore_body,
+                                const uint16_t* query_mask, float* pos_out, uint32_t* status_out, uint32_t* hit_body_out,
+                                float* hit_normal_out, float* hit_depth_out) {
+    return depen_device(w, {n, pos, rot_ijkw, radius, half_length, skin, max_iters, false, ignore_body, query_mask,
+                            pos_out, status_out, hit_body_out, hit_normal_out, hit_depth_out});
+}
+
 static int32_t overlap_host(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,
                             const float* half_extent, const uint32_t* ignore_body, const uint16_t* query_mask, uint64_t cap,
                             uint64_t* offsets_out, uint32_t* ids_out) {

@@ -384,6 +384,10 @@ int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* 
 // query grid once, grown by the call's largest valid radius + half_length, then ONE kernel in which every lane runs its
 // character's whole cast, stop, project loop (include/spec/slide.h) against the capsule cast's own walk
 int32_t launch_slide(phys_world* w, const SlideBatch& b);
+// depen.hip: depenetration (DepenBatch: staging.hpp, device pointers, arguments checked by the caller): the
+// query grid once, not grown, then ONE kernel in which every lane probes for its capsule's deepest target (b.probe: that is
+// the answer) and runs the push-out loop of include/spec/depenetrate.h, probing again from where each push left it
+int32_t launch_depen(phys_world* w, const DepenBatch& b);
 // query.hip: overlap queries on staged device arrays; writes the host offsets (n + 1) and, when they fit in cap, the ids
 int32_t launch_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot, const float* half_extent,
                        const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out,

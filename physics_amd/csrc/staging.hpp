@@ -1,6 +1,6 @@
 // staging.hpp — how a query call describes its arrays: the batch of one cast (rays, balls, capsules alike) and of one
-// move-and-slide call, what their entry points check of them, and where a call's host arrays lie in the one device buffer they
-// are staged in. Host-only like setup.hpp
+// move-and-slide or depenetration call, what their entry points check of them, and where a call's host arrays lie in the one
+// device buffer they are staged in. Host-only like setup.hpp
 // (no HIP, no phys_world), held to tests/cpp/staging_probe.cpp. abi.hip keeps the buffer, the copies and the launch.
 #pragma once
 #include <cstddef>
@@ -137,6 +137,70 @@ inline SlideBatch staged_slide(const SlideBatch& host, uint8_t* in_base, uint8_t
     SlideBatch dev = host;
     StageLayout in, out;
     for_each_slide_array(dev, [&](auto*& array, size_t per_query, bool output) {
+        StageLayout& l = output ? out : in;
+        array = l.at(output ? out_base : in_base, l.add(array, per_query * host.n));
+    });
+    return dev;
+}
+
+// ---- depenetration (phys_penetration and phys_depenetrate): the arrays of one call, n capsules; host
+// pointers or device pointers alike. probe: phys_penetration, one probe and no move: gap is the call's max_gap, max_iters 1, and
+// the one slot per query is the answer (hit_body_out = body_out, hit_normal_out = normal_out, hit_depth_out = depth_out;
+// pos_out and status_out null). Otherwise phys_depenetrate: gap is the call's skin, slot k of query i lies at index k * n + i.
+struct DepenBatch {
+    uint64_t n;
+    const float* pos;                  // 3 per query
+    const float* rot;                  // [i, j, k, w] per query; null: identity
+    const float *radius, *half_length; // per query
+    float gap;                         // the call's max_gap or skin: finite, >= 0
+    uint32_t max_iters;                // the call's: 1 .. 8
+    bool probe;
+    const uint32_t* ignore_body;       // null: none
+    const uint16_t* query_mask;        // null: no filtering
+    float* pos_out;                    // 3 per query
+    uint32_t* status_out;
+    uint32_t* hit_body_out;            // max_iters per query
+    float* hit_normal_out;             // 3 * max_iters per query
+    float* hit_depth_out;              // max_iters per query
+};
+
+constexpr uint32_t kDepenMaxIters = 8;
+
+// every array of a call once, in the order they are staged: f(member, elements per query, is it an output)
+template <class Batch, class F>
+inline void for_each_depen_array(Batch& b, F&& f) {
+    const size_t k = b.max_iters;
+    f(b.pos, 3, false); f(b.rot, 4, false); f(b.radius, 1, false); f(b.half_length, 1, false);
+    f(b.ignore_body, 1, false); f(b.query_mask, 1, false);
+    f(b.pos_out, 3, true); f(b.status_out, 1, true);
+    f(b.hit_body_out, k, true); f(b.hit_normal_out, 3 * k, true); f(b.hit_depth_out, k, true);
+}
+
+// what the four entry points check before they touch anything: the text of the refusal, null when the call may go on
+inline const char* depen_args_error(const DepenBatch& b) {
+    const bool gap_ok = b.gap >= 0.0f && b.gap <= 3.4028235e38f;
+    if (b.probe) {
+        if (b.n >= (1ull << 31)) return "phys_penetration: n must be below 2^31";
+        if (!gap_ok) return "phys_penetration: max_gap must be finite and not negative";
+        const bool missing = !b.pos || !b.radius || !b.half_length || !b.hit_body_out || !b.hit_depth_out;
+        return b.n && missing ? "phys_penetration: null pos, radius, half_length, body_out or depth_out" : nullptr;
+    }
+    if (b.n >= (1ull << 31)) return "phys_depenetrate: n must be below 2^31";
+    if (!gap_ok) return "phys_depenetrate: skin must be finite and not negative";
+    if (b.max_iters < 1u || b.max_iters > kDepenMaxIters) return "phys_depenetrate: max_iters must be 1 .. 8";
+    const bool missing = !b.pos || !b.radius || !b.half_length || !b.pos_out || !b.status_out;
+    return b.n && missing ? "phys_depenetrate: null pos, radius, half_length, pos_out or status_out" : nullptr;
+}
+
+// a call on host arrays declares them: the inputs in one buffer, the outputs in another ...
+inline void stage_depen(const DepenBatch& host, StageLayout& in, StageLayout& out) {
+    for_each_depen_array(host, [&](auto* array, size_t per_query, bool output) { (output ? out : in).add(array, per_query * host.n); });
+}
+// ... and is the same batch on the device once the two buffers are there
+inline DepenBatch staged_depen(const DepenBatch& host, uint8_t* in_base, uint8_t* out_base) {
+    DepenBatch dev = host;
+    StageLayout in, out;
+    for_each_depen_array(dev, [&](auto*& array, size_t per_query, bool output) {
         StageLayout& l = output ? out : in;
         array = l.at(output ? out_base : in_base, l.add(array, per_query * host.n));
     });

@@ -207,6 +207,12 @@ class PhysicsState:
         self._push()
         return self._world.move_and_slide(pos, motion, radius, half_length, rot, skin, max_slides, ignore, mask)
 
+    def depenetrate(self, pos, radius, half_length, rot=None, skin=0.01, max_iters=4, ignore=None, mask=None):
+        """Capsules pushed out of the entities they overlap, as they are now (World.depenetrate): (pos, status, hit_body,
+        hit_normal, hit_depth)."""
+        self._push()
+        return self._world.depenetrate(pos, radius, half_length, rot, skin, max_iters, ignore, mask)
+
     def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None, mask=None):
         """Every entity each query shape intersects, as they are now (World.overlap): (offsets, ascending ids)."""
         self._push()

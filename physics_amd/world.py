@@ -571,6 +571,90 @@ class World:
                                 ("hit_point_out", hit_point_out, 3 * k)))
         self._ck(self.lib.phys_move_and_slide_device(self.h, n, *ins, skin, k, ig, None if mask is None else _device_mask(mask, n), *outs))
 
+    def _depen_args(self, pos, radius, half_length, rot, ignore, mask):
+        """The arrays penetration and depenetrate share, checked before the library is called."""
+        p = _f(pos).reshape(-1, 3)
+        n = p.shape[0]
+        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)))
+        hq = np.ascontiguousarray(np.broadcast_to(np.asarray(half_length, np.float32), (n,)))
+        r = None if rot is None else _f(rot).reshape(-1, 4)
+        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.uint32).reshape(-1)
+        for a, cols in ((r, 4), (ig, 1)):
+            if a is not None and a.size != n * cols:
+                raise ValueError("rot / ignore do not match the capsule count")
+        return n, p, r, rad, hq, ig, _query_mask(mask, n)
+
+    def penetration(self, pos, radius, half_length, rot=None, max_gap=0.0, ignore=None, mask=None):
+        """The deepest target within max_gap of each capsule where it stands (phys_penetration; the rule:
+        include/spec/depenetrate.h): pos (n, 3), radius and half_length scalar or (n,), rot (n, 4) [i, j, k, w] or None
+        (upright), ignore (n,) body ids or None, mask scalar or (n,) u16 or None (no filtering). Returns (body u32[n], depth
+        f32[n], normal f32[n, 3]): depth > 0 is how far the capsule reaches into the target, depth < 0 the clearance, normal
+        points out of the target towards the capsule; a miss is (RAY_MISS, -inf, 0). Nothing moves."""
+        max_gap = float(max_gap)
+        if not (np.isfinite(max_gap) and max_gap >= 0.0):
+            raise ValueError("max_gap: must be finite and not negative")
+        n, p, r, rad, hq, ig, qm = self._depen_args(pos, radius, half_length, rot, ignore, mask)
+        body, depth, nrm = np.empty(n, np.uint32), np.empty(n, np.float32), np.empty((n, 3), np.float32)
+        if n:
+            self._ck(self.lib.phys_penetration(self.h, n, _p(p), _p(r), _p(rad), _p(hq), max_gap, _p(ig, u32p), _p(qm, u16p),
+                                               _p(body, u32p), _p(depth), _p(nrm)))
+        return body, depth, nrm
+
+    def penetration_device(self, pos, radius, half_length, body_out, depth_out, normal_out=None, rot=None, max_gap=0.0, ignore=None,
+                           mask=None):
+        """phys_penetration_device on contiguous torch tensors of the world's device, as capsulecast_device: pos float32
+        (n, 3), radius and half_length float32 (n,), body_out int32 / uint32 (n,), depth_out float32 (n,), normal_out float32
+        (n, 3) or None, rot float32 (n, 4) or None, ignore int32 / uint32 (n,) or None, mask int16 / uint16 (n,) or None. Only
+        enqueues on the world's stream (device_view().stream)."""
+        n = int(pos.shape[0])
+        max_gap = float(max_gap)
+        if not (np.isfinite(max_gap) and max_gap >= 0.0):
+            raise ValueError("max_gap: must be finite and not negative")
+        ins = _device_args(n, (("pos", pos, 3), ("rot", rot, 4), ("radius", radius, 1), ("half_length", half_length, 1)))
+        ig, = _device_args(n, (("ignore", ignore, 1),))
+        outs = _device_args(n, (("body_out", body_out, 1), ("depth_out", depth_out, 1), ("normal_out", normal_out, 3)))
+        self._ck(self.lib.phys_penetration_device(self.h, n, *ins, max_gap, ig, None if mask is None else _device_mask(mask, n), *outs))
+
+    def depenetrate(self, pos, radius, half_length, rot=None, skin=0.01, max_iters=4, ignore=None, mask=None):
+        """Capsules that overlap something are pushed out of it, the deepest target first, until they are skin / 2 clear of
+        everything or max_iters (1 .. 8) pushes were made, all in one launch (phys_depenetrate; the rule:
+        include/spec/depenetrate.h). Arguments as for penetration. Returns (pos f32[n, 3], status u32[n], hit_body
+        u32[max_iters, n], hit_normal f32[max_iters, n, 3], hit_depth f32[max_iters, n]): status holds the push count in bits
+        0-3 and the DEPEN_STUCK / DEPEN_INVALID flags; slot k is what penetration reported where push k began, an unused slot
+        holds RAY_MISS and zeros."""
+        k = int(max_iters)
+        if not 1 <= k <= _abi.DEPEN_MAX_ITERS:
+            raise ValueError(f"max_iters: must lie in [1, {_abi.DEPEN_MAX_ITERS}]")
+        skin = float(skin)
+        if not (np.isfinite(skin) and skin >= 0.0):
+            raise ValueError("skin: must be finite and not negative")
+        n, p, r, rad, hq, ig, qm = self._depen_args(pos, radius, half_length, rot, ignore, mask)
+        pos_out, status = np.empty((n, 3), np.float32), np.empty(n, np.uint32)
+        body, nrm, depth = np.empty((k, n), np.uint32), np.empty((k, n, 3), np.float32), np.empty((k, n), np.float32)
+        if n:
+            self._ck(self.lib.phys_depenetrate(self.h, n, _p(p), _p(r), _p(rad), _p(hq), skin, k, _p(ig, u32p), _p(qm, u16p),
+                                               _p(pos_out), _p(status, u32p), _p(body, u32p), _p(nrm), _p(depth)))
+        return pos_out, status, body, nrm, depth
+
+    def depenetrate_device(self, pos, radius, half_length, pos_out, status_out, hit_body_out=None, hit_normal_out=None,
+                           hit_depth_out=None, rot=None, skin=0.01, max_iters=4, ignore=None, mask=None):
+        """phys_depenetrate_device on contiguous torch tensors of the world's device, as penetration_device: pos_out float32
+        (n, 3), status_out int32 / uint32 (n,), hit_body_out int32 / uint32 (max_iters, n) or None, hit_normal_out float32
+        (max_iters, n, 3) or None, hit_depth_out float32 (max_iters, n) or None. Only enqueues on the world's stream
+        (device_view().stream): pos_out may feed move_and_slide_device without a host wait."""
+        n = int(pos.shape[0])
+        k = int(max_iters)
+        if not 1 <= k <= _abi.DEPEN_MAX_ITERS:
+            raise ValueError(f"max_iters: must lie in [1, {_abi.DEPEN_MAX_ITERS}]")
+        skin = float(skin)
+        if not (np.isfinite(skin) and skin >= 0.0):
+            raise ValueError("skin: must be finite and not negative")
+        ins = _device_args(n, (("pos", pos, 3), ("rot", rot, 4), ("radius", radius, 1), ("half_length", half_length, 1)))
+        ig, = _device_args(n, (("ignore", ignore, 1),))
+        outs = _device_args(n, (("pos_out", pos_out, 3), ("status_out", status_out, 1), ("hit_body_out", hit_body_out, k),
+                                ("hit_normal_out", hit_normal_out, 3 * k), ("hit_depth_out", hit_depth_out, k)))
+        self._ck(self.lib.phys_depenetrate_device(self.h, n, *ins, skin, k, ig, None if mask is None else _device_mask(mask, n), *outs))
+
     def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None, cap=None, mask=None):
         """Every target each query shape intersects (phys_overlap): shape_type scalar or (n,) SHAPE_SPHERE / BOX / CAPSULE,
         pos (n, 3), rot (n, 4) [i, j, k, w] or None (identity), half_extent (3,) or (n, 3) with the bodies' conventions,

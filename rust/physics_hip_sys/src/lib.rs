@@ -32,6 +32,9 @@ pub const PHYS_SLIDE_MAX_SLIDES: u32 = 8;
 pub const PHYS_SLIDE_BLOCKED: u32 = 0x100;
 pub const PHYS_SLIDE_EXHAUSTED: u32 = 0x200;
 pub const PHYS_SLIDE_INVALID: u32 = 0x400;
+pub const PHYS_DEPEN_MAX_ITERS: u32 = 8;
+pub const PHYS_DEPEN_STUCK: u32 = 0x100;
+pub const PHYS_DEPEN_INVALID: u32 = 0x400;
 pub const PHYS_RAY_GROUND: u32 = 0xFFFF_FFFF;
 // contact events: phys_contact_event.kind
 pub const PHYS_CONTACT_BEGIN: u32 = 1;
@@ -217,6 +220,19 @@ extern "C" {
                                       ignore_body: *const u32, query_mask: *const u16, pos_out: *mut f32, remaining_out: *mut f32,
                                       status_out: *mut u32, hit_body_out: *mut u32, hit_normal_out: *mut f32,
                                       hit_point_out: *mut f32) -> i32;
+    pub fn phys_penetration(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32, radius: *const f32, half_length: *const f32,
+                            max_gap: f32, ignore_body: *const u32, query_mask: *const u16, body_out: *mut u32, depth_out: *mut f32,
+                            normal_out: *mut f32) -> i32;
+    pub fn phys_penetration_device(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32, radius: *const f32,
+                                   half_length: *const f32, max_gap: f32, ignore_body: *const u32, query_mask: *const u16,
+                                   body_out: *mut u32, depth_out: *mut f32, normal_out: *mut f32) -> i32;
+    pub fn phys_depenetrate(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32, radius: *const f32, half_length: *const f32,
+                            skin: f32, max_iters: u32, ignore_body: *const u32, query_mask: *const u16, pos_out: *mut f32,
+                            status_out: *mut u32, hit_body_out: *mut u32, hit_normal_out: *mut f32, hit_depth_out: *mut f32) -> i32;
+    pub fn phys_depenetrate_device(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32, radius: *const f32,
+                                   half_length: *const f32, skin: f32, max_iters: u32, ignore_body: *const u32,
+                                   query_mask: *const u16, pos_out: *mut f32, status_out: *mut u32, hit_body_out: *mut u32,
+                                   hit_normal_out: *mut f32, hit_depth_out: *mut f32) -> i32;
     pub fn phys_overlap(w: *mut phys_world, n: u64, shape_type: *const u32, pos: *const f32, rot_ijkw: *const f32,
                         half_extent: *const f32, ignore_body: *const u32, cap: u64, offsets_out: *mut u64, ids_out: *mut u32) -> i32;
     pub fn phys_set_static_bodies(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32, shape_type: *const u32,
