@@ -372,6 +372,65 @@ int32_t phys_move_and_slide_device(phys_world* w, uint64_t n, const float* pos, 
                                    const float* radius, const float* half_length, float skin, uint32_t max_slides,
                                    const uint32_t* ignore_body, const uint16_t* query_mask, float* pos_out, float* remaining_out,
                                    uint32_t* status_out, uint32_t* hit_body_out, float* hit_normal_out, float* hit_point_out);
+/* phys_character_move: a capsule character (phys_move_and_slide's capsule) walks: it makes motion[i] - the whole displacement of
+ * the frame, with whatever vertical part the caller integrated from gravity or a jump - as phys_move_and_slide does, and on top
+ * does not climb what is too steep, steps up onto low obstacles, stays on the floor it walks down and learns what it stands on.
+ * All of it inside ONE kernel launch over ONE query grid; the rule is stated once, as a state machine around one capsule cast, in
+ * include/spec/character.h, and every cast is phys_capsulecast's. Up is +y. Read-only: nothing an update
+ * reads is written, and sticky update errors are neither reported nor cleared.
+ *   - a hit normal n is FLOOR when n.y >= min_floor_ny (the cosine of the steepest walkable slope), STEEP when
+ *     0 < n.y < min_floor_ny, WALL when n.y <= 0. A character is walking in this call when grounded_in[i] != 0 (it stood on a
+ *     floor when its last call ended: pass that call's status & PHYS_CHAR_GROUNDED; NULL = nobody did) and !(motion.y > 0).
+ *   - MOVE: phys_move_and_slide on the whole motion, bit for bit for a character that is not walking; a walker's slide along a
+ *     STEEP normal that would gain height follows the slope's contour instead. Hits fill slots 0 .. max_slides - 1. BLOCKED ends
+ *     the query without a ground state.
+ *   - STEP (walking, step_height > 0, a horizontal motion, MOVE met a hit that is not FLOOR): cast up by step_height (less under
+ *     a low ceiling), slide the horizontal motion from there (hits in slots max_slides .. 2 max_slides - 1), cast down; taken
+ *     when that lands on a FLOOR further along the horizontal motion than MOVE came, otherwise MOVE's result stands.
+ *   - GROUND (not after a step taken or BLOCKED): one cast down by 2 skin, plus snap_distance when walking. A FLOOR: GROUNDED, and
+ *     a walker more than 2 skin above it is moved down to skin above it (SNAPPED). A STEEP hit: ON_STEEP, not grounded.
+ *   - pos_out, remaining_out (may be NULL): as phys_move_and_slide's, of the path taken.
+ *   - status_out: MOVE's hit count in bits 0-3, the lifted slide's in bits 4-7 (casts made, taken or not), and the flags below.
+ *     BLOCKED, EXHAUSTED, HIT_WALL (a hit that is not FLOOR) and HIT_CEILING (a hit with n.y < 0 while motion.y > 0) describe the
+ *     slide whose result was taken. INVALID: phys_move_and_slide's rule; pos_out = pos, remaining_out = motion, no hits, no floor.
+ *   - floor_body_out, floor_normal_out, floor_point_out (each may be NULL): what the character stands on (GROUNDED) or what lies
+ *     below it (ON_STEEP), as phys_capsulecast reports it; PHYS_RAY_MISS and zeros otherwise.
+ *   - hit slots (each array may be NULL): 2 * max_slides per query, slot k of query i at index k * n + i; every slot is written,
+ *     an unused one holds PHYS_RAY_MISS and zeros. They are there for phys_apply_impulses_device: the call pushes nothing.
+ *   - at most 2 * max_slides + 3 casts per character. skin == 0 is allowed and degenerate as for phys_move_and_slide (and a
+ *     character resting on a floor then finds it at t == 0: not grounded).
+ *   - not done here: gravity and velocity integration, pushing bodies, depenetration (call phys_depenetrate first), constant
+ *     speed on walkable slopes, moving platforms, an up axis other than +y.
+ *   - PHYS_ERR_INVALID_ARG: n >= 2^31, a NULL pos, motion, radius, half_length, pos_out or status_out with n > 0, a non-finite or
+ *     negative skin, step_height or snap_distance, min_floor_ny outside (0, 1], max_slides outside 1 .. PHYS_SLIDE_MAX_SLIDES.
+ *     n == 0 is a no-op.
+ * phys_character_move takes host arrays and returns with the outputs written; phys_character_move_device takes device pointers
+ * and only enqueues on the world's stream. PHYS_ABI_VERSION is unchanged: a caller tells an older library by the missing symbols. */
+#define PHYS_CHAR_BLOCKED 0x100u
+#define PHYS_CHAR_EXHAUSTED 0x200u
+#define PHYS_CHAR_INVALID 0x400u
+#define PHYS_CHAR_GROUNDED 0x1000u
+#define PHYS_CHAR_STEPPED 0x2000u
+#define PHYS_CHAR_SNAPPED 0x4000u
+#define PHYS_CHAR_ON_STEEP 0x8000u
+#define PHYS_CHAR_HIT_WALL 0x10000u
+#define PHYS_CHAR_HIT_CEILING 0x20000u
+int32_t phys_character_move(phys_world* w, uint64_t n, const float* pos /*3n*/, const float* motion /*3n*/,
+                            const float* rot_ijkw /*4n, NULL = identity*/, const float* radius /*n*/, const float* half_length /*n*/,
+                            const uint32_t* grounded_in /*n, NULL = nobody*/, float skin, uint32_t max_slides, float step_height,
+                            float snap_distance, float min_floor_ny, const uint32_t* ignore_body /*n, NULL = none*/,
+                            const uint16_t* query_mask /*n, NULL = no filtering*/, float* pos_out /*3n*/,
+                            float* remaining_out /*3n, may be NULL*/, uint32_t* status_out /*n*/,
+                            uint32_t* floor_body_out /*n, may be NULL*/, float* floor_normal_out /*3n, may be NULL*/,
+                            float* floor_point_out /*3n, may be NULL*/, uint32_t* hit_body_out /*2*max_slides*n, may be NULL*/,
+                            float* hit_normal_out /*3*2*max_slides*n, may be NULL*/,
+                            float* hit_point_out /*3*2*max_slides*n, may be NULL*/);
+int32_t phys_character_move_device(phys_world* w, uint64_t n, const float* pos, const float* motion, const float* rot_ijkw,
+                                   const float* radius, const float* half_length, const uint32_t* grounded_in, float skin,
+                                   uint32_t max_slides, float step_height, float snap_distance, float min_floor_ny,
+                                   const uint32_t* ignore_body, const uint16_t* query_mask, float* pos_out, float* remaining_out,
+                                   uint32_t* status_out, uint32_t* floor_body_out, float* floor_normal_out, float* floor_point_out,
+                                   uint32_t* hit_body_out, float* hit_normal_out, float* hit_point_out);
 /* phys_penetration and phys_depenetrate: how deep a capsule (core pos[i] +- half_length[i] * a, a the y axis turned by rot_ijkw[i]
  * and used as given, radius radius[i]: phys_capsulecast's capsule; half_length == 0 is a ball) sits in what surrounds it, and the
  * loop that pushes it out. The rule is stated once, in include/spec/depenetrate.h; depths and normals are

@@ -281,6 +281,18 @@ PROTOTYPES["phys_move_and_slide"] = (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f
 PROTOTYPES["phys_move_and_slide_device"] = (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_float, C.c_uint32]
                                             + [C.c_void_p] * 8)
 
+# character walking: pos, motion, rot, radius, half_length, grounded_in, skin, max_slides, step_height, snap_distance, min_floor_ny,
+# ignore, query_mask; pos_out, remaining_out, status_out, floor_body_out, floor_normal_out, floor_point_out, hit_body_out,
+# hit_normal_out, hit_point_out (the device variant: every array a c_void_p)
+CHAR_BLOCKED, CHAR_EXHAUSTED, CHAR_INVALID = 0x100, 0x200, 0x400
+CHAR_GROUNDED, CHAR_STEPPED, CHAR_SNAPPED, CHAR_ON_STEEP, CHAR_HIT_WALL, CHAR_HIT_CEILING = 0x1000, 0x2000, 0x4000, 0x8000, 0x10000, 0x20000
+PROTOTYPES["phys_character_move"] = (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, f32p, u32p, C.c_float, C.c_uint32,
+                                                 C.c_float, C.c_float, C.c_float, u32p, u16p, f32p, f32p, u32p, u32p, f32p, f32p,
+                                                 u32p, f32p, f32p])
+PROTOTYPES["phys_character_move_device"] = (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [C.c_float, C.c_uint32, C.c_float,
+                                                                                                    C.c_float, C.c_float]
+                                            + [C.c_void_p] * 11)
+
 # depenetration: pos, rot, radius, half_length, max_gap, ignore, query_mask; body_out, depth_out, normal_out - and pos, rot, radius,
 # half_length, skin, max_iters, ignore, query_mask; pos_out, status_out, hit_body_out, hit_normal_out, hit_depth_out (the device
 # variants: every array a c_void_p)

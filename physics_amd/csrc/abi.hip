@@ -979,6 +979,48 @@ int32_t phys_move_and_slide(phys_world* w, uint64_t n, const float* pos, const f
     return PHYS_OK;
 }
 
+// character walking: the batch in CharacterBatch's order; on device arrays checked and enqueued, on host
+// arrays staged as move-and-slide's are, the hit slots in a buffer of their own (w->rc_slots), run, read back and waited for
+int32_t phys_character_move_device(phys_world* w, uint64_t n, const float* pos, const float* motion, const float* rot_ijkw,
+                                   const float* radius, const float* half_length, const uint32_t* grounded_in, float skin,
+                                   uint32_t max_slides, float step_height, float snap_distance, float min_floor_ny,
+                                   const uint32_t* ignore_body, const uint16_t* query_mask, float* pos_out, float* remaining_out,
+                                   uint32_t* status_out, uint32_t* floor_body_out, float* floor_normal_out, float* floor_point_out,
+                                   uint32_t* hit_body_out, float* hit_normal_out, float* hit_point_out) {
+    ENTER(w);
+    const CharacterBatch b = {n, pos, motion, rot_ijkw, radius, half_length, grounded_in, skin, max_slides, step_height, snap_distance,
+                              min_floor_ny, ignore_body, query_mask, pos_out, remaining_out, status_out, floor_body_out,
+                              floor_normal_out, floor_point_out, hit_body_out, hit_normal_out, hit_point_out};
+    if (const char* bad = character_args_error(b)) return fail(PHYS_ERR_INVALID_ARG, bad);
+    if (n == 0) return PHYS_OK;
+    return launch_character(w, b);
+}
+
+int32_t phys_character_move(phys_world* w, uint64_t n, const float* pos, const float* motion, const float* rot_ijkw, const float* radius,
+                            const float* half_length, const uint32_t* grounded_in, float skin, uint32_t max_slides, float step_height,
+                            float snap_distance, float min_floor_ny, const uint32_t* ignore_body, const uint16_t* query_mask,
+                            float* pos_out, float* remaining_out, uint32_t* status_out, uint32_t* floor_body_out,
+                            float* floor_normal_out, float* floor_point_out, uint32_t* hit_body_out, float* hit_normal_out,
+                            float* hit_point_out) {
+    ENTER(w);
+    const CharacterBatch b = {n, pos, motion, rot_ijkw, radius, half_length, grounded_in, skin, max_slides, step_height, snap_distance,
+                              min_floor_ny, ignore_body, query_mask, pos_out, remaining_out, status_out, floor_body_out,
+                              floor_normal_out, floor_point_out, hit_body_out, hit_normal_out, hit_point_out};
+    if (const char* bad = character_args_error(b)) return fail(PHYS_ERR_INVALID_ARG, bad);
+    if (n == 0) return PHYS_OK;
+    Staging in{w, w->stage}, out{w, w->rc_out}, slots{w, w->rc_slots};
+    stage_character(b, in, out, slots);
+    PHYS_TRY(in.reserve());
+    PHYS_TRY(out.reserve());
+    PHYS_TRY(slots.reserve());
+    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
+    PHYS_TRY(launch_character(w, staged_character(b, in.buf.p, out.buf.p, slots.buf.p)));
+    PHYS_TRY(out.copy(hipMemcpyDeviceToHost));
+    PHYS_TRY(slots.copy(hipMemcpyDeviceToHost));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    return PHYS_OK;
+}
+
 // depenetration: both calls are one DepenBatch (probe: phys_penetration); on device arrays checked and
 // enqueued, on host arrays staged as the casts are (inputs in w->stage, outputs in w->rc_out), run, read back and waited for
 static int32_t depen_device(phys_world* w, const DepenBatch& b) {

@@ -384,6 +384,10 @@ int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* 
 // query grid once, grown by the call's largest valid radius + half_length, then ONE kernel in which every lane runs its
 // character's whole cast, stop, project loop (include/spec/slide.h) against the capsule cast's own walk
 int32_t launch_slide(phys_world* w, const SlideBatch& b);
+// character.hip: character walking (CharacterBatch: staging.hpp, device pointers, arguments checked by the
+// caller): the query grid once, grown by the call's largest valid radius + half_length, then ONE kernel in which every lane
+// drives its character's state machine (include/spec/character.h) around the capsule cast's own walk
+int32_t launch_character(phys_world* w, const CharacterBatch& b);
 // depen.hip: depenetration (DepenBatch: staging.hpp, device pointers, arguments checked by the caller): the
 // query grid once, not grown, then ONE kernel in which every lane probes for its capsule's deepest target (b.probe: that is
 // the answer) and runs the push-out loop of include/spec/depenetrate.h, probing again from where each push left it

@@ -143,6 +143,74 @@ inline SlideBatch staged_slide(const SlideBatch& host, uint8_t* in_base, uint8_t
     return dev;
 }
 
+// ---- character walking (phys_character_move): the arrays of one call, n characters; host pointers or
+// device pointers alike. Slot k of query i lies at index k * n + i of the hit arrays, 2 * max_slides slots per query.
+struct CharacterBatch {
+    uint64_t n;
+    const float *pos, *motion;         // 3 per query
+    const float* rot;                  // [i, j, k, w] per query; null: identity
+    const float *radius, *half_length; // per query
+    const uint32_t* grounded_in;       // per query, non-zero: stood on a floor when its last call ended; null: nobody did
+    float skin;                        // the call's: finite, >= 0
+    uint32_t max_slides;               // the call's: 1 .. 8
+    float step_height, snap_distance;  // the call's: finite, >= 0
+    float min_floor_ny;                // the call's: in (0, 1]
+    const uint32_t* ignore_body;       // null: none
+    const uint16_t* query_mask;        // null: no filtering
+    float *pos_out, *remaining_out;    // 3 per query; remaining_out may be null
+    uint32_t* status_out;
+    uint32_t* floor_body_out;          // per query; null: not wanted
+    float *floor_normal_out, *floor_point_out;  // 3 per query; null: not wanted
+    uint32_t* hit_body_out;            // 2 * max_slides per query; null: not wanted
+    float *hit_normal_out, *hit_point_out;  // 3 * 2 * max_slides per query; null: not wanted
+};
+
+// where an array of a character call is staged: the inputs, the per-query outputs, and the hit slots in a layout of their
+// own (the call has nine outputs, a layout holds eight arrays)
+enum class CharacterGroup { In, Out, Slots };
+
+// every array of a call once, in the order they are staged: f(member, elements per query, its group)
+template <class Batch, class F>
+inline void for_each_character_array(Batch& b, F&& f) {
+    const size_t k = 2 * (size_t)b.max_slides;
+    f(b.pos, 3, CharacterGroup::In); f(b.motion, 3, CharacterGroup::In); f(b.rot, 4, CharacterGroup::In);
+    f(b.radius, 1, CharacterGroup::In); f(b.half_length, 1, CharacterGroup::In); f(b.grounded_in, 1, CharacterGroup::In);
+    f(b.ignore_body, 1, CharacterGroup::In); f(b.query_mask, 1, CharacterGroup::In);
+    f(b.pos_out, 3, CharacterGroup::Out); f(b.remaining_out, 3, CharacterGroup::Out); f(b.status_out, 1, CharacterGroup::Out);
+    f(b.floor_body_out, 1, CharacterGroup::Out); f(b.floor_normal_out, 3, CharacterGroup::Out); f(b.floor_point_out, 3, CharacterGroup::Out);
+    f(b.hit_body_out, k, CharacterGroup::Slots); f(b.hit_normal_out, 3 * k, CharacterGroup::Slots); f(b.hit_point_out, 3 * k, CharacterGroup::Slots);
+}
+
+// what both entry points check before they touch anything: the text of the refusal, null when the call may go on
+inline const char* character_args_error(const CharacterBatch& b) {
+    const auto length_ok = [](float x) { return x >= 0.0f && x <= 3.4028235e38f; };
+    if (b.n >= (1ull << 31)) return "phys_character_move: n must be below 2^31";
+    if (!length_ok(b.skin)) return "phys_character_move: skin must be finite and not negative";
+    if (b.max_slides < 1u || b.max_slides > kSlideMaxSlides) return "phys_character_move: max_slides must be 1 .. 8";
+    if (!length_ok(b.step_height)) return "phys_character_move: step_height must be finite and not negative";
+    if (!length_ok(b.snap_distance)) return "phys_character_move: snap_distance must be finite and not negative";
+    if (!(b.min_floor_ny > 0.0f && b.min_floor_ny <= 1.0f)) return "phys_character_move: min_floor_ny must lie in (0, 1]";
+    const bool missing = !b.pos || !b.motion || !b.radius || !b.half_length || !b.pos_out || !b.status_out;
+    return b.n && missing ? "phys_character_move: null pos, motion, radius, half_length, pos_out or status_out" : nullptr;
+}
+
+// a call on host arrays declares them: the inputs in one buffer, the per-query outputs in another, the hit slots in a third ...
+inline void stage_character(const CharacterBatch& host, StageLayout& in, StageLayout& out, StageLayout& slots) {
+    for_each_character_array(host, [&](auto* array, size_t per_query, CharacterGroup g) {
+        (g == CharacterGroup::In ? in : g == CharacterGroup::Out ? out : slots).add(array, per_query * host.n);
+    });
+}
+// ... and is the same batch on the device once the three buffers are there
+inline CharacterBatch staged_character(const CharacterBatch& host, uint8_t* in_base, uint8_t* out_base, uint8_t* slots_base) {
+    CharacterBatch dev = host;
+    StageLayout in, out, slots;
+    for_each_character_array(dev, [&](auto*& array, size_t per_query, CharacterGroup g) {
+        StageLayout& l = g == CharacterGroup::In ? in : g == CharacterGroup::Out ? out : slots;
+        array = l.at(g == CharacterGroup::In ? in_base : g == CharacterGroup::Out ? out_base : slots_base, l.add(array, per_query * host.n));
+    });
+    return dev;
+}
+
 // ---- depenetration (phys_penetration and phys_depenetrate): the arrays of one call, n capsules; host
 // pointers or device pointers alike. probe: phys_penetration, one probe and no move: gap is the call's max_gap, max_iters 1, and
 // the one slot per query is the answer (hit_body_out = body_out, hit_normal_out = normal_out, hit_depth_out = depth_out;

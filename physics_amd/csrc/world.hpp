@@ -261,6 +261,7 @@ struct phys_world {
     // inputs of whichever runs - each synchronises the stream before it returns, so no two are ever in flight - laid out by the
     // call's own declarations (staging.hpp StageLayout); the casts' outputs body | t | normal | point the same way
     phys::DevBuf<uint8_t> stage, rc_out;
+    phys::DevBuf<uint8_t> rc_slots;  // phys_character_move: its hit slots, a layout of their own behind the per-query outputs
     phys::DevBuf<unsigned long long> rc_stats;  // PHYS_DEBUG_RAYCAST_STATS: cells, candidates
     // overlap queries (query.hip): they walk the grid above; their own output
     phys::DevBuf<uint32_t> qr_count;     // phys_overlap: targets per query (count pass)

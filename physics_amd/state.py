@@ -207,6 +207,14 @@ class PhysicsState:
         self._push()
         return self._world.move_and_slide(pos, motion, radius, half_length, rot, skin, max_slides, ignore, mask)
 
+    def character_move(self, pos, motion, radius, half_length, rot=None, grounded=None, skin=0.01, max_slides=4, step_height=0.3,
+                       snap_distance=0.2, min_floor_ny=0.7071068, ignore=None, mask=None):
+        """Capsule characters walk over the entities as they are now (World.character_move): (pos, remaining, status,
+        floor_body, floor_normal, floor_point, hit_body, hit_normal, hit_point)."""
+        self._push()
+        return self._world.character_move(pos, motion, radius, half_length, rot, grounded, skin, max_slides, step_height, snap_distance,
+                                          min_floor_ny, ignore, mask)
+
     def depenetrate(self, pos, radius, half_length, rot=None, skin=0.01, max_iters=4, ignore=None, mask=None):
         """Capsules pushed out of the entities they overlap, as they are now (World.depenetrate): (pos, status, hit_body,
         hit_normal, hit_depth)."""

@@ -571,6 +571,77 @@ class World:
                                 ("hit_point_out", hit_point_out, 3 * k)))
         self._ck(self.lib.phys_move_and_slide_device(self.h, n, *ins, skin, k, ig, None if mask is None else _device_mask(mask, n), *outs))
 
+    @staticmethod
+    def _character_params(skin, max_slides, step_height, snap_distance, min_floor_ny):
+        """The per-call values of character_move, checked before the library is called."""
+        k = int(max_slides)
+        if not 1 <= k <= _abi.SLIDE_MAX_SLIDES:
+            raise ValueError(f"max_slides: must lie in [1, {_abi.SLIDE_MAX_SLIDES}]")
+        lengths = []
+        for name, v in (("skin", skin), ("step_height", step_height), ("snap_distance", snap_distance)):
+            v = float(v)
+            if not (np.isfinite(v) and v >= 0.0):
+                raise ValueError(f"{name}: must be finite and not negative")
+            lengths.append(v)
+        ny = float(min_floor_ny)
+        if not 0.0 < ny <= 1.0:
+            raise ValueError("min_floor_ny: must lie in (0, 1]")
+        return k, lengths[0], lengths[1], lengths[2], ny
+
+    def character_move(self, pos, motion, radius, half_length, rot=None, grounded=None, skin=0.01, max_slides=4, step_height=0.3,
+                       snap_distance=0.2, min_floor_ny=0.7071068, ignore=None, mask=None):
+        """Capsule characters walk (phys_character_move; the rule: include/spec/character.h): move_and_slide on the whole
+        motion of the frame, and for a character that stood on a floor (grounded (n,) non-zero, None: nobody) and does not
+        move up: no climbing of slopes steeper than min_floor_ny (the cosine of the limit), a step up of at most step_height,
+        a snap down of at most snap_distance; then the ground state. pos / motion (n, 3), radius and half_length scalar or
+        (n,), rot (n, 4) or None (upright), ignore (n,) body ids or None, mask scalar or (n,) u16 or None. Returns (pos
+        f32[n, 3], remaining f32[n, 3], status u32[n], floor_body u32[n], floor_normal f32[n, 3], floor_point f32[n, 3],
+        hit_body u32[2 max_slides, n], hit_normal f32[2 max_slides, n, 3], hit_point f32[2 max_slides, n, 3]): status holds
+        MOVE's hit count in bits 0-3, the lifted slide's in bits 4-7 and the CHAR_* flags; pass status & CHAR_GROUNDED as the
+        next frame's grounded."""
+        p, m = _f(pos).reshape(-1, 3), _f(motion).reshape(-1, 3)
+        n = p.shape[0]
+        if m.shape[0] != n:
+            raise ValueError("pos and motion differ in length")
+        k, skin, step_height, snap_distance, min_floor_ny = self._character_params(skin, max_slides, step_height, snap_distance, min_floor_ny)
+        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)))
+        hq = np.ascontiguousarray(np.broadcast_to(np.asarray(half_length, np.float32), (n,)))
+        r = None if rot is None else _f(rot).reshape(-1, 4)
+        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.uint32).reshape(-1)
+        gr = None if grounded is None else np.ascontiguousarray(np.asarray(grounded) != 0, dtype=np.uint32).reshape(-1)
+        for a, cols in ((r, 4), (ig, 1), (gr, 1)):
+            if a is not None and a.size != n * cols:
+                raise ValueError("rot / ignore / grounded do not match the character count")
+        qm = _query_mask(mask, n)
+        pos_out, rem, status = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32), np.empty(n, np.uint32)
+        fbody, fnrm, fpnt = np.empty(n, np.uint32), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+        body, nrm, pnt = np.empty((2 * k, n), np.uint32), np.empty((2 * k, n, 3), np.float32), np.empty((2 * k, n, 3), np.float32)
+        if n:
+            self._ck(self.lib.phys_character_move(self.h, n, _p(p), _p(m), _p(r), _p(rad), _p(hq), _p(gr, u32p), skin, k, step_height,
+                                                  snap_distance, min_floor_ny, _p(ig, u32p), _p(qm, u16p), _p(pos_out), _p(rem),
+                                                  _p(status, u32p), _p(fbody, u32p), _p(fnrm), _p(fpnt), _p(body, u32p), _p(nrm), _p(pnt)))
+        return pos_out, rem, status, fbody, fnrm, fpnt, body, nrm, pnt
+
+    def character_move_device(self, pos, motion, radius, half_length, pos_out, status_out, remaining_out=None, floor_body_out=None,
+                              floor_normal_out=None, floor_point_out=None, hit_body_out=None, hit_normal_out=None, hit_point_out=None,
+                              rot=None, grounded=None, skin=0.01, max_slides=4, step_height=0.3, snap_distance=0.2,
+                              min_floor_ny=0.7071068, ignore=None, mask=None):
+        """phys_character_move_device on contiguous torch tensors of the world's device, as move_and_slide_device: grounded
+        int32 / uint32 (n,) or None, floor_body_out int32 / uint32 (n,) or None, floor_normal_out and floor_point_out float32
+        (n, 3) or None, hit_body_out int32 / uint32 (2 max_slides, n) or None, hit_normal_out and hit_point_out float32
+        (2 max_slides, n, 3) or None. Only enqueues on the world's stream (device_view().stream)."""
+        n = int(pos.shape[0])
+        k, skin, step_height, snap_distance, min_floor_ny = self._character_params(skin, max_slides, step_height, snap_distance, min_floor_ny)
+        ins = _device_args(n, (("pos", pos, 3), ("motion", motion, 3), ("rot", rot, 4), ("radius", radius, 1), ("half_length", half_length, 1),
+                               ("grounded", grounded, 1)))
+        ig, = _device_args(n, (("ignore", ignore, 1),))
+        outs = _device_args(n, (("pos_out", pos_out, 3), ("remaining_out", remaining_out, 3), ("status_out", status_out, 1),
+                                ("floor_body_out", floor_body_out, 1), ("floor_normal_out", floor_normal_out, 3),
+                                ("floor_point_out", floor_point_out, 3), ("hit_body_out", hit_body_out, 2 * k),
+                                ("hit_normal_out", hit_normal_out, 6 * k), ("hit_point_out", hit_point_out, 6 * k)))
+        self._ck(self.lib.phys_character_move_device(self.h, n, *ins, skin, k, step_height, snap_distance, min_floor_ny, ig,
+                                                     None if mask is None else _device_mask(mask, n), *outs))
+
     def _depen_args(self, pos, radius, half_length, rot, ignore, mask):
         """The arrays penetration and depenetrate share, checked before the library is called."""
         p = _f(pos).reshape(-1, 3)

@@ -32,6 +32,15 @@ pub const PHYS_SLIDE_MAX_SLIDES: u32 = 8;
 pub const PHYS_SLIDE_BLOCKED: u32 = 0x100;
 pub const PHYS_SLIDE_EXHAUSTED: u32 = 0x200;
 pub const PHYS_SLIDE_INVALID: u32 = 0x400;
+pub const PHYS_CHAR_BLOCKED: u32 = 0x100;
+pub const PHYS_CHAR_EXHAUSTED: u32 = 0x200;
+pub const PHYS_CHAR_INVALID: u32 = 0x400;
+pub const PHYS_CHAR_GROUNDED: u32 = 0x1000;
+pub const PHYS_CHAR_STEPPED: u32 = 0x2000;
+pub const PHYS_CHAR_SNAPPED: u32 = 0x4000;
+pub const PHYS_CHAR_ON_STEEP: u32 = 0x8000;
+pub const PHYS_CHAR_HIT_WALL: u32 = 0x10000;
+pub const PHYS_CHAR_HIT_CEILING: u32 = 0x20000;
 pub const PHYS_DEPEN_MAX_ITERS: u32 = 8;
 pub const PHYS_DEPEN_STUCK: u32 = 0x100;
 pub const PHYS_DEPEN_INVALID: u32 = 0x400;
@@ -219,6 +228,19 @@ extern "C" {
                                       radius: *const f32, half_length: *const f32, skin: f32, max_slides: u32,
                                       ignore_body: *const u32, query_mask: *const u16, pos_out: *mut f32, remaining_out: *mut f32,
                                       status_out: *mut u32, hit_body_out: *mut u32, hit_normal_out: *mut f32,
+                                      hit_point_out: *mut f32) -> i32;
+    pub fn phys_character_move(w: *mut phys_world, n: u64, pos: *const f32, motion: *const f32, rot_ijkw: *const f32, radius: *const f32,
+                               half_length: *const f32, grounded_in: *const u32, skin: f32, max_slides: u32, step_height: f32,
+                               snap_distance: f32, min_floor_ny: f32, ignore_body: *const u32, query_mask: *const u16,
+                               pos_out: *mut f32, remaining_out: *mut f32, status_out: *mut u32, floor_body_out: *mut u32,
+                               floor_normal_out: *mut f32, floor_point_out: *mut f32, hit_body_out: *mut u32,
+                               hit_normal_out: *mut f32, hit_point_out: *mut f32) -> i32;
+    pub fn phys_character_move_device(w: *mut phys_world, n: u64, pos: *const f32, motion: *const f32, rot_ijkw: *const f32,
+                                      radius: *const f32, half_length: *const f32, grounded_in: *const u32, skin: f32,
+                                      max_slides: u32, step_height: f32, snap_distance: f32, min_floor_ny: f32,
+                                      ignore_body: *const u32, query_mask: *const u16, pos_out: *mut f32, remaining_out: *mut f32,
+                                      status_out: *mut u32, floor_body_out: *mut u32, floor_normal_out: *mut f32,
+                                      floor_point_out: *mut f32, hit_body_out: *mut u32, hit_normal_out: *mut f32,
                                       hit_point_out: *mut f32) -> i32;
     pub fn phys_penetration(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32, radius: *const f32, half_length: *const f32,
                             max_gap: f32, ignore_body: *const u32, query_mask: *const u16, body_out: *mut u32, depth_out: *mut f32,
