@@ -272,38 +272,36 @@ for _kind, (_ins, _outs) in CASTS.items():
             PROTOTYPES[f"phys_{_kind}{_device}" + ("_filtered" if _mask else "")] = (
                 C.c_int32, [C.c_void_p, C.c_uint64] + ([C.c_void_p] * len(_args) if _device else _args))
 
-# move-and-slide: pos, motion, rot, radius, half_length, skin, max_slides, ignore, query_mask; pos_out, remaining_out, status_out,
-# hit_body_out, hit_normal_out, hit_point_out (the device variant: every array a c_void_p)
+# The capsule query calls (move-and-slide, character walking, depenetration): per call its input arrays, its per-call scalars
+# with their types, and its output arrays, in the order of the call: the inputs, the scalars, ignore, query_mask, the outputs
+# (the header's names but rot, ignore and grounded: its rot_ijkw, ignore_body and grounded_in). Every array is float32 but those
+# of QUERY_TYPES. Each call comes on host arrays and on device arrays (_device: every array a c_void_p).
 SLIDE_MAX_SLIDES = 8
 SLIDE_BLOCKED, SLIDE_EXHAUSTED, SLIDE_INVALID = 0x100, 0x200, 0x400
-PROTOTYPES["phys_move_and_slide"] = (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, f32p, C.c_float, C.c_uint32, u32p, u16p,
-                                                 f32p, f32p, u32p, u32p, f32p, f32p])
-PROTOTYPES["phys_move_and_slide_device"] = (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_float, C.c_uint32]
-                                            + [C.c_void_p] * 8)
-
-# character walking: pos, motion, rot, radius, half_length, grounded_in, skin, max_slides, step_height, snap_distance, min_floor_ny,
-# ignore, query_mask; pos_out, remaining_out, status_out, floor_body_out, floor_normal_out, floor_point_out, hit_body_out,
-# hit_normal_out, hit_point_out (the device variant: every array a c_void_p)
 CHAR_BLOCKED, CHAR_EXHAUSTED, CHAR_INVALID = 0x100, 0x200, 0x400
 CHAR_GROUNDED, CHAR_STEPPED, CHAR_SNAPPED, CHAR_ON_STEEP, CHAR_HIT_WALL, CHAR_HIT_CEILING = 0x1000, 0x2000, 0x4000, 0x8000, 0x10000, 0x20000
-PROTOTYPES["phys_character_move"] = (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, f32p, u32p, C.c_float, C.c_uint32,
-                                                 C.c_float, C.c_float, C.c_float, u32p, u16p, f32p, f32p, u32p, u32p, f32p, f32p,
-                                                 u32p, f32p, f32p])
-PROTOTYPES["phys_character_move_device"] = (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [C.c_float, C.c_uint32, C.c_float,
-                                                                                                    C.c_float, C.c_float]
-                                            + [C.c_void_p] * 11)
-
-# depenetration: pos, rot, radius, half_length, max_gap, ignore, query_mask; body_out, depth_out, normal_out - and pos, rot, radius,
-# half_length, skin, max_iters, ignore, query_mask; pos_out, status_out, hit_body_out, hit_normal_out, hit_depth_out (the device
-# variants: every array a c_void_p)
 DEPEN_MAX_ITERS = 8
 DEPEN_STUCK, DEPEN_INVALID = 0x100, 0x400
-PROTOTYPES["phys_penetration"] = (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, C.c_float, u32p, u16p, u32p, f32p, f32p])
-PROTOTYPES["phys_penetration_device"] = (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 5)
-PROTOTYPES["phys_depenetrate"] = (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p, C.c_float, C.c_uint32, u32p, u16p,
-                                              f32p, u32p, u32p, f32p, f32p])
-PROTOTYPES["phys_depenetrate_device"] = (C.c_int32, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 4 + [C.c_float, C.c_uint32]
-                                         + [C.c_void_p] * 7)
+QUERIES = {
+    "move_and_slide": (("pos", "motion", "rot", "radius", "half_length"), (("skin", C.c_float), ("max_slides", C.c_uint32)),
+                       ("pos_out", "remaining_out", "status_out", "hit_body_out", "hit_normal_out", "hit_point_out")),
+    "character_move": (("pos", "motion", "rot", "radius", "half_length", "grounded"),
+                       (("skin", C.c_float), ("max_slides", C.c_uint32), ("step_height", C.c_float), ("snap_distance", C.c_float),
+                        ("min_floor_ny", C.c_float)),
+                       ("pos_out", "remaining_out", "status_out", "floor_body_out", "floor_normal_out", "floor_point_out",
+                        "hit_body_out", "hit_normal_out", "hit_point_out")),
+    "penetration": (("pos", "rot", "radius", "half_length"), (("max_gap", C.c_float),), ("body_out", "depth_out", "normal_out")),
+    "depenetrate": (("pos", "rot", "radius", "half_length"), (("skin", C.c_float), ("max_iters", C.c_uint32)),
+                    ("pos_out", "status_out", "hit_body_out", "hit_normal_out", "hit_depth_out")),
+}
+QUERY_TYPES = {"grounded": u32p, "ignore": u32p, "query_mask": u16p, "status_out": u32p, "floor_body_out": u32p, "hit_body_out": u32p,
+               "body_out": u32p}
+
+for _call, (_ins, _scalars, _outs) in QUERIES.items():
+    for _device in ("", "_device"):
+        _args = [C.c_void_p if _device else QUERY_TYPES.get(k, f32p) for k in _ins + ("ignore", "query_mask") + _outs]
+        PROTOTYPES[f"phys_{_call}{_device}"] = (
+            C.c_int32, [C.c_void_p, C.c_uint64] + _args[:len(_ins)] + [t for _, t in _scalars] + _args[len(_ins):])
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libphysics_hip.so")
 _lib = None

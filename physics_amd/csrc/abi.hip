@@ -245,6 +245,36 @@ struct Staging : StageLayout {
     }
 };
 
+// The two paths of every query family that is a batch (staging.hpp): its entry points fill the batch from
+// their arguments and name one of these, with the CastKind behind the batch for the casts.
+// On device arrays: checked (args_error), then enqueued (launch_query, kernels.hpp)
+template <class Batch, class... Kind>
+static int32_t query_device(phys_world* w, const Batch& b, Kind... kind) {
+    ENTER(w);
+    if (const char* bad = args_error(kind..., b)) return fail(PHYS_ERR_INVALID_ARG, bad);
+    if (b.n == 0) return PHYS_OK;
+    return launch_query(w, kind..., b);
+}
+
+// On host arrays: checked, staged (the inputs in w->stage, the per-query outputs in w->rc_out, the character's hit slots in
+// w->rc_slots: a group without arrays takes no room and no copy), run, read back; synchronises once
+template <class Batch, class... Kind>
+static int32_t query_host(phys_world* w, const Batch& b, Kind... kind) {
+    ENTER(w);
+    if (const char* bad = args_error(kind..., b)) return fail(PHYS_ERR_INVALID_ARG, bad);
+    if (b.n == 0) return PHYS_OK;
+    Staging st[kStageGroups] = {{w, w->stage}, {w, w->rc_out}, {w, w->rc_slots}};
+    stage(b, st);
+    for (Staging& s : st) PHYS_TRY(s.reserve());
+    PHYS_TRY(st[kStageIn].copy(hipMemcpyHostToDevice));
+    uint8_t* const bases[kStageGroups] = {st[kStageIn].buf.p, st[kStageOut].buf.p, st[kStageSlots].buf.p};
+    PHYS_TRY(launch_query(w, kind..., staged(b, bases)));
+    PHYS_TRY(st[kStageOut].copy(hipMemcpyDeviceToHost));
+    PHYS_TRY(st[kStageSlots].copy(hipMemcpyDeviceToHost));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    return PHYS_OK;
+}
+
 extern "C" {
 
 void phys_config_default(phys_config* cfg) {
@@ -836,164 +866,122 @@ int32_t phys_get_device_view(phys_world* w, phys_device_view* out) {
     return PHYS_OK;
 }
 
-// ---- queries: ray casts, sphere casts, overlaps ----
-// casts on device arrays: checked (cast_args_error, staging.hpp), then enqueued
-static int32_t cast_device(phys_world* w, CastKind kind, const CastBatch& b) {
-    ENTER(w);
-    if (const char* bad = cast_args_error(kind, b)) return fail(PHYS_ERR_INVALID_ARG, bad);
-    if (b.n == 0) return PHYS_OK;
-    return launch_cast(w, kind, b);
-}
-
-// casts on host arrays: staged (the inputs in w->stage, the outputs in w->rc_out), traced, read back; synchronises
-static int32_t cast_host(phys_world* w, CastKind kind, const CastBatch& b) {
-    ENTER(w);
-    if (const char* bad = cast_args_error(kind, b)) return fail(PHYS_ERR_INVALID_ARG, bad);
-    if (b.n == 0) return PHYS_OK;
-    Staging in{w, w->stage}, out{w, w->rc_out};
-    stage_cast(b, in, out);
-    PHYS_TRY(in.reserve());
-    PHYS_TRY(out.reserve());
-    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
-    PHYS_TRY(launch_cast(w, kind, staged_cast(b, in.buf.p, out.buf.p)));
-    PHYS_TRY(out.copy(hipMemcpyDeviceToHost));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    return PHYS_OK;
-}
-
-// the twelve entry points: each names its kind and fills the batch from its arguments, in CastBatch's order: n, origin, dir, rot,
-// radius, half_length, max_t, ignore_body on the first line; query_mask, body_out, t_out, normal_out, point_out on the second
+// ---- queries: casts, move-and-slide, character walking, depenetration (all through query_host / query_device above); overlaps ----
+// the twelve cast entry points: each names its kind and fills the batch from its arguments, in CastBatch's order: n, origin, dir,
+// rot, radius, half_length, max_t, ignore_body on the first line; query_mask, body_out, t_out, normal_out, point_out on the second
 int32_t phys_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                      const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    return cast_host(w, CastKind::Ray, {n_rays, origin, dir, nullptr, nullptr, nullptr, max_t, ignore_body,
-                                        nullptr, body_out, t_out, normal_out, nullptr});
+    return query_host(w, CastBatch{n_rays, origin, dir, nullptr, nullptr, nullptr, max_t, ignore_body,
+                                   nullptr, body_out, t_out, normal_out, nullptr}, CastKind::Ray);
 }
 
 int32_t phys_raycast_filtered(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                               const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
                               float* normal_out) {
-    return cast_host(w, CastKind::Ray, {n_rays, origin, dir, nullptr, nullptr, nullptr, max_t, ignore_body,
-                                        query_mask, body_out, t_out, normal_out, nullptr});
+    return query_host(w, CastBatch{n_rays, origin, dir, nullptr, nullptr, nullptr, max_t, ignore_body,
+                                   query_mask, body_out, t_out, normal_out, nullptr}, CastKind::Ray);
 }
 
 int32_t phys_raycast_device(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                             const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    return cast_device(w, CastKind::Ray, {n_rays, origin, dir, nullptr, nullptr, nullptr, max_t, ignore_body,
-                                          nullptr, body_out, t_out, normal_out, nullptr});
+    return query_device(w, CastBatch{n_rays, origin, dir, nullptr, nullptr, nullptr, max_t, ignore_body,
+                                     nullptr, body_out, t_out, normal_out, nullptr}, CastKind::Ray);
 }
 
 int32_t phys_raycast_device_filtered(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                                      const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
                                      float* normal_out) {
-    return cast_device(w, CastKind::Ray, {n_rays, origin, dir, nullptr, nullptr, nullptr, max_t, ignore_body,
-                                          query_mask, body_out, t_out, normal_out, nullptr});
+    return query_device(w, CastBatch{n_rays, origin, dir, nullptr, nullptr, nullptr, max_t, ignore_body,
+                                     query_mask, body_out, t_out, normal_out, nullptr}, CastKind::Ray);
 }
 
 int32_t phys_spherecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
                         const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    return cast_host(w, CastKind::Sphere, {n, origin, dir, nullptr, radius, nullptr, max_t, ignore_body,
-                                           nullptr, body_out, t_out, normal_out, nullptr});
+    return query_host(w, CastBatch{n, origin, dir, nullptr, radius, nullptr, max_t, ignore_body,
+                                   nullptr, body_out, t_out, normal_out, nullptr}, CastKind::Sphere);
 }
 
 int32_t phys_spherecast_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius,
                                  const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out,
                                  float* t_out, float* normal_out) {
-    return cast_host(w, CastKind::Sphere, {n, origin, dir, nullptr, radius, nullptr, max_t, ignore_body,
-                                           query_mask, body_out, t_out, normal_out, nullptr});
+    return query_host(w, CastBatch{n, origin, dir, nullptr, radius, nullptr, max_t, ignore_body,
+                                   query_mask, body_out, t_out, normal_out, nullptr}, CastKind::Sphere);
 }
 
 int32_t phys_spherecast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius, const float* max_t,
                                const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
-    return cast_device(w, CastKind::Sphere, {n, origin, dir, nullptr, radius, nullptr, max_t, ignore_body,
-                                             nullptr, body_out, t_out, normal_out, nullptr});
+    return query_device(w, CastBatch{n, origin, dir, nullptr, radius, nullptr, max_t, ignore_body,
+                                     nullptr, body_out, t_out, normal_out, nullptr}, CastKind::Sphere);
 }
 
 int32_t phys_spherecast_device_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* radius,
                                         const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask,
                                         uint32_t* body_out, float* t_out, float* normal_out) {
-    return cast_device(w, CastKind::Sphere, {n, origin, dir, nullptr, radius, nullptr, max_t, ignore_body,
-                                             query_mask, body_out, t_out, normal_out, nullptr});
+    return query_device(w, CastBatch{n, origin, dir, nullptr, radius, nullptr, max_t, ignore_body,
+                                     query_mask, body_out, t_out, normal_out, nullptr}, CastKind::Sphere);
 }
 
 // capsule casts: rot, half_length and point_out besides
 int32_t phys_capsulecast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw, const float* radius,
                          const float* half_length, const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out,
                          float* normal_out, float* point_out) {
-    return cast_host(w, CastKind::Capsule, {n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body,
-                                            nullptr, body_out, t_out, normal_out, point_out});
+    return query_host(w, CastBatch{n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body,
+                                   nullptr, body_out, t_out, normal_out, point_out}, CastKind::Capsule);
 }
 
 int32_t phys_capsulecast_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
                                   const float* radius, const float* half_length, const float* max_t, const uint32_t* ignore_body,
                                   const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out, float* point_out) {
-    return cast_host(w, CastKind::Capsule, {n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body,
-                                            query_mask, body_out, t_out, normal_out, point_out});
+    return query_host(w, CastBatch{n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body,
+                                   query_mask, body_out, t_out, normal_out, point_out}, CastKind::Capsule);
 }
 
 int32_t phys_capsulecast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
                                 const float* radius, const float* half_length, const float* max_t, const uint32_t* ignore_body,
                                 uint32_t* body_out, float* t_out, float* normal_out, float* point_out) {
-    return cast_device(w, CastKind::Capsule, {n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body,
-                                              nullptr, body_out, t_out, normal_out, point_out});
+    return query_device(w, CastBatch{n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body,
+                                     nullptr, body_out, t_out, normal_out, point_out}, CastKind::Capsule);
 }
 
 int32_t phys_capsulecast_device_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
                                          const float* radius, const float* half_length, const float* max_t, const uint32_t* ignore_body,
                                          const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out,
                                          float* point_out) {
-    return cast_device(w, CastKind::Capsule, {n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body,
-                                              query_mask, body_out, t_out, normal_out, point_out});
+    return query_device(w, CastBatch{n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body,
+                                     query_mask, body_out, t_out, normal_out, point_out}, CastKind::Capsule);
 }
 
-// move-and-slide: the batch in SlideBatch's order; on device arrays checked and enqueued, on host arrays
-// staged as the casts are (inputs in w->stage, outputs in w->rc_out), run, read back and waited for
+// move-and-slide: both entry points have the same parameters, the batch from them in SlideBatch's order
+#define PHYS_SLIDE_BATCH                                                                                                   \
+    SlideBatch{n, pos, motion, rot_ijkw, radius, half_length, skin, max_slides, ignore_body, query_mask,                   \
+               pos_out, remaining_out, status_out, hit_body_out, hit_normal_out, hit_point_out}
 int32_t phys_move_and_slide_device(phys_world* w, uint64_t n, const float* pos, const float* motion, const float* rot_ijkw,
                                    const float* radius, const float* half_length, float skin, uint32_t max_slides,
                                    const uint32_t* ignore_body, const uint16_t* query_mask, float* pos_out, float* remaining_out,
                                    uint32_t* status_out, uint32_t* hit_body_out, float* hit_normal_out, float* hit_point_out) {
-    ENTER(w);
-    const SlideBatch b = {n, pos, motion, rot_ijkw, radius, half_length, skin, max_slides, ignore_body, query_mask,
-                          pos_out, remaining_out, status_out, hit_body_out, hit_normal_out, hit_point_out};
-    if (const char* bad = slide_args_error(b)) return fail(PHYS_ERR_INVALID_ARG, bad);
-    if (n == 0) return PHYS_OK;
-    return launch_slide(w, b);
+    return query_device(w, PHYS_SLIDE_BATCH);
 }
 
 int32_t phys_move_and_slide(phys_world* w, uint64_t n, const float* pos, const float* motion, const float* rot_ijkw, const float* radius,
                             const float* half_length, float skin, uint32_t max_slides, const uint32_t* ignore_body,
                             const uint16_t* query_mask, float* pos_out, float* remaining_out, uint32_t* status_out,
                             uint32_t* hit_body_out, float* hit_normal_out, float* hit_point_out) {
-    ENTER(w);
-    const SlideBatch b = {n, pos, motion, rot_ijkw, radius, half_length, skin, max_slides, ignore_body, query_mask,
-                          pos_out, remaining_out, status_out, hit_body_out, hit_normal_out, hit_point_out};
-    if (const char* bad = slide_args_error(b)) return fail(PHYS_ERR_INVALID_ARG, bad);
-    if (n == 0) return PHYS_OK;
-    Staging in{w, w->stage}, out{w, w->rc_out};
-    stage_slide(b, in, out);
-    PHYS_TRY(in.reserve());
-    PHYS_TRY(out.reserve());
-    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
-    PHYS_TRY(launch_slide(w, staged_slide(b, in.buf.p, out.buf.p)));
-    PHYS_TRY(out.copy(hipMemcpyDeviceToHost));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    return PHYS_OK;
+    return query_host(w, PHYS_SLIDE_BATCH);
 }
+#undef PHYS_SLIDE_BATCH
 
-// character walking: the batch in CharacterBatch's order; on device arrays checked and enqueued, on host
-// arrays staged as move-and-slide's are, the hit slots in a buffer of their own (w->rc_slots), run, read back and waited for
+// character walking: likewise, in CharacterBatch's order
+#define PHYS_CHARACTER_BATCH                                                                                               \
+    CharacterBatch{n, pos, motion, rot_ijkw, radius, half_length, grounded_in, skin, max_slides, step_height, snap_distance, \
+                   min_floor_ny, ignore_body, query_mask, pos_out, remaining_out, status_out, floor_body_out,              \
+                   floor_normal_out, floor_point_out, hit_body_out, hit_normal_out, hit_point_out}
 int32_t phys_character_move_device(phys_world* w, uint64_t n, const float* pos, const float* motion, const float* rot_ijkw,
                                    const float* radius, const float* half_length, const uint32_t* grounded_in, float skin,
                                    uint32_t max_slides, float step_height, float snap_distance, float min_floor_ny,
                                    const uint32_t* ignore_body, const uint16_t* query_mask, float* pos_out, float* remaining_out,
                                    uint32_t* status_out, uint32_t* floor_body_out, float* floor_normal_out, float* floor_point_out,
                                    uint32_t* hit_body_out, float* hit_normal_out, float* hit_point_out) {
-    ENTER(w);
-    const CharacterBatch b = {n, pos, motion, rot_ijkw, radius, half_length, grounded_in, skin, max_slides, step_height, snap_distance,
-                              min_floor_ny, ignore_body, query_mask, pos_out, remaining_out, status_out, floor_body_out,
-                              floor_normal_out, floor_point_out, hit_body_out, hit_normal_out, hit_point_out};
-    if (const char* bad = character_args_error(b)) return fail(PHYS_ERR_INVALID_ARG, bad);
-    if (n == 0) return PHYS_OK;
-    return launch_character(w, b);
+    return query_device(w, PHYS_CHARACTER_BATCH);
 }
 
 int32_t phys_character_move(phys_world* w, uint64_t n, const float* pos, const float* motion, const float* rot_ijkw, const float* radius,
@@ -1002,76 +990,39 @@ int32_t phys_character_move(phys_world* w, uint64_t n, const float* pos, const f
                             float* pos_out, float* remaining_out, uint32_t* status_out, uint32_t* floor_body_out,
                             float* floor_normal_out, float* floor_point_out, uint32_t* hit_body_out, float* hit_normal_out,
                             float* hit_point_out) {
-    ENTER(w);
-    const CharacterBatch b = {n, pos, motion, rot_ijkw, radius, half_length, grounded_in, skin, max_slides, step_height, snap_distance,
-                              min_floor_ny, ignore_body, query_mask, pos_out, remaining_out, status_out, floor_body_out,
-                              floor_normal_out, floor_point_out, hit_body_out, hit_normal_out, hit_point_out};
-    if (const char* bad = character_args_error(b)) return fail(PHYS_ERR_INVALID_ARG, bad);
-    if (n == 0) return PHYS_OK;
-    Staging in{w, w->stage}, out{w, w->rc_out}, slots{w, w->rc_slots};
-    stage_character(b, in, out, slots);
-    PHYS_TRY(in.reserve());
-    PHYS_TRY(out.reserve());
-    PHYS_TRY(slots.reserve());
-    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
-    PHYS_TRY(launch_character(w, staged_character(b, in.buf.p, out.buf.p, slots.buf.p)));
-    PHYS_TRY(out.copy(hipMemcpyDeviceToHost));
-    PHYS_TRY(slots.copy(hipMemcpyDeviceToHost));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    return PHYS_OK;
+    return query_host(w, PHYS_CHARACTER_BATCH);
 }
+#undef PHYS_CHARACTER_BATCH
 
-// depenetration: both calls are one DepenBatch (probe: phys_penetration); on device arrays checked and
-// enqueued, on host arrays staged as the casts are (inputs in w->stage, outputs in w->rc_out), run, read back and waited for
-static int32_t depen_device(phys_world* w, const DepenBatch& b) {
-    ENTER(w);
-    if (const char* bad = depen_args_error(b)) return fail(PHYS_ERR_INVALID_ARG, bad);
-    if (b.n == 0) return PHYS_OK;
-    return launch_depen(w, b);
-}
-
-static int32_t depen_host(phys_world* w, const DepenBatch& b) {
-    ENTER(w);
-    if (const char* bad = depen_args_error(b)) return fail(PHYS_ERR_INVALID_ARG, bad);
-    if (b.n == 0) return PHYS_OK;
-    Staging in{w, w->stage}, out{w, w->rc_out};
-    stage_depen(b, in, out);
-    PHYS_TRY(in.reserve());
-    PHYS_TRY(out.reserve());
-    PHYS_TRY(in.copy(hipMemcpyHostToDevice));
-    PHYS_TRY(launch_depen(w, staged_depen(b, in.buf.p, out.buf.p)));
-    PHYS_TRY(out.copy(hipMemcpyDeviceToHost));
-    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
-    return PHYS_OK;
-}
-
+// depenetration: both calls are one DepenBatch (probe: phys_penetration, max_iters 1, its body_out,
+// normal_out and depth_out the one slot per query)
 int32_t phys_penetration(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw, const float* radius, const float* half_length,
                          float max_gap, const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* depth_out,
                          float* normal_out) {
-    return depen_host(w, {n, pos, rot_ijkw, radius, half_length, max_gap, 1u, true, ignore_body, query_mask,
-                          nullptr, nullptr, body_out, normal_out, depth_out});
+    return query_host(w, DepenBatch{n, pos, rot_ijkw, radius, half_length, max_gap, 1u, true, ignore_body, query_mask,
+                                    nullptr, nullptr, body_out, normal_out, depth_out});
 }
 
 int32_t phys_penetration_device(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw, const float* radius,
                                 const float* half_length, float max_gap, const uint32_t* ignore_body, const uint16_t* query_mask,
                                 uint32_t* body_out, float* depth_out, float* normal_out) {
-    return depen_device(w, {n, pos, rot_ijkw, radius, half_length, max_gap, 1u, true, ignore_body, query_mask,
-                            nullptr, nullptr, body_out, normal_out, depth_out});
+    return query_device(w, DepenBatch{n, pos, rot_ijkw, radius, half_length, max_gap, 1u, true, ignore_body, query_mask,
+                                      nullptr, nullptr, body_out, normal_out, depth_out});
 }
 
 int32_t phys_depenetrate(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw, const float* radius, const float* half_length,
                          float skin, uint32_t max_iters, const uint32_t* ignore_body, const uint16_t* query_mask, float* pos_out,
                          uint32_t* status_out, uint32_t* hit_body_out, float* hit_normal_out, float* hit_depth_out) {
-    return depen_host(w, {n, pos, rot_ijkw, radius, half_length, skin, max_iters, false, ignore_body, query_mask,
-                          pos_out, status_out, hit_body_out, hit_normal_out, hit_depth_out});
+    return query_host(w, DepenBatch{n, pos, rot_ijkw, radius, half_length, skin, max_iters, false, ignore_body, query_mask,
+                                    pos_out, status_out, hit_body_out, hit_normal_out, hit_depth_out});
 }
 
 int32_t phys_depenetrate_device(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw, const float* radius,
                                 const float* half_length, float skin, uint32_t max_iters, const uint32_t* ignore_body,
                                 const uint16_t* query_mask, float* pos_out, uint32_t* status_out, uint32_t* hit_body_out,
                                 float* hit_normal_out, float* hit_depth_out) {
-    return depen_device(w, {n, pos, rot_ijkw, radius, half_length, skin, max_iters, false, ignore_body, query_mask,
-                            pos_out, status_out, hit_body_out, hit_normal_out, hit_depth_out});
+    return query_device(w, DepenBatch{n, pos, rot_ijkw, radius, half_length, skin, max_iters, false, ignore_body, query_mask,
+                                      pos_out, status_out, hit_body_out, hit_normal_out, hit_depth_out});
 }
 
 static int32_t overlap_host(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot_ijkw,

@@ -8,6 +8,9 @@
 // site below, ch_answer consumes the answer. Nothing but these is arithmetic here. Hit slots and the floor's normal and point
 // go straight to global memory as they become known, iteration-major (slot k of query i at k * n + i), so nothing in private
 // memory is indexed at run time. Lanes of a wave make different numbers of casts and wait for the longest.
+// The slots are written by query_slot and query_slots_empty (rc_grid.hpp), as in slide.hip and depen.hip; the host side is the
+// one query path of DESIGN.md section 16, this family's launch_query at the end. The lane's query is loaded here and not by
+// capsule_query: with it the kernel compiled to another schedule that was 1.4 and 1.7 % slower on C2 and C3.
 #include "../../include/spec/character.h"
 #include "cast_walk.hpp"
 
@@ -34,12 +37,6 @@ struct CharacterOut {
     float* hit_normal;
     float* hit_point;
 };
-
-__device__ __forceinline__ void ch_store(uint32_t* body, float* normal, float* point, size_t at, uint32_t id, v3 n, v3 p) {
-    if (body) body[at] = id;
-    if (normal) { normal[3 * at] = n.x; normal[3 * at + 1] = n.y; normal[3 * at + 2] = n.z; }
-    if (point) { point[3 * at] = p.x; point[3 * at + 1] = p.y; point[3 * at + 2] = p.z; }
-}
 
 // FILT: a query_mask was given: a target whose category misses the query's mask is skipped before its exact test (qf is
 // read by this instance alone)
@@ -81,17 +78,16 @@ __global__ __launch_bounds__(kRcThreads) void k_character(uint32_t n, const floa
                                              req.max_t, ign, rad, hq, ax, ay, az, cap_ok, best, point, cells, cands);
             const v3 nrm = v3_make(best.nx, best.ny, best.nz);
             if (req.slot >= 0 && best.id != kRayMiss)
-                ch_store(out.hit_body, out.hit_normal, out.hit_point, (size_t)(uint32_t)req.slot * n + i, best.id, nrm, point);
+                query_slot(out.hit_body, out.hit_normal, out.hit_point, (size_t)(uint32_t)req.slot * n + i, best.id, nrm, point);
             ch_answer(&s, best.id, best.t, nrm, point);
-            if (req.slot == CH_SLOT_FLOOR && ch_floor_found(&s)) ch_store(out.floor_body, out.floor_normal, out.floor_point, i, best.id, nrm, point);
+            if (req.slot == CH_SLOT_FLOOR && ch_floor_found(&s)) query_slot(out.floor_body, out.floor_normal, out.floor_point, i, best.id, nrm, point);
         }
     }
     // the kernel writes every slot: the ones neither slide used are empty
     const uint32_t k_move = s.status & SL_HITS_MASK, k_lift = (s.status >> CH_HITS_SHIFT) & SL_HITS_MASK;
-    for (uint32_t e = k_move; e < max_slides; ++e) ch_store(out.hit_body, out.hit_normal, out.hit_point, (size_t)e * n + i, kRayMiss, zero, zero);
-    for (uint32_t e = k_lift; e < max_slides; ++e)
-        ch_store(out.hit_body, out.hit_normal, out.hit_point, (size_t)(max_slides + e) * n + i, kRayMiss, zero, zero);
-    if (!ch_floor_found(&s)) ch_store(out.floor_body, out.floor_normal, out.floor_point, i, kRayMiss, zero, zero);
+    query_slots_empty(out.hit_body, out.hit_normal, out.hit_point, 0u, k_move, max_slides, n, i, zero);
+    query_slots_empty(out.hit_body, out.hit_normal, out.hit_point, max_slides, k_lift, max_slides, n, i, zero);
+    if (!ch_floor_found(&s)) query_slot(out.floor_body, out.floor_normal, out.floor_point, i, kRayMiss, zero, zero);
     st3(out.pos, i, s.sl.p);
     if (out.remaining) st3(out.remaining, i, s.sl.m);
     out.status[i] = s.status;
@@ -99,21 +95,17 @@ __global__ __launch_bounds__(kRcThreads) void k_character(uint32_t n, const floa
 
 }  // namespace
 
-int32_t launch_character(phys_world* w, const CharacterBatch& b) {
-    hipStream_t s = w->stream;
-    uint32_t bits = 12;
-    PHYS_TRY(launch_query_grid(w, b.radius, b.half_length, b.n, &bits));
-    const int ground = (w->cfg.flags & PHYS_FLAG_GROUND_PLANE) ? 1 : 0;
+int32_t launch_query(phys_world* w, const CharacterBatch& b) {
+    QueryGrid g;
+    PHYS_TRY(query_grid(w, b.radius, b.half_length, b.n, &g));
     const QueryFilters qf = query_filters(w, b.query_mask);
     const CharacterOut out{b.pos_out,          b.remaining_out,    b.status_out,  b.floor_body_out, b.floor_normal_out,
                            b.floor_point_out, b.hit_body_out,     b.hit_normal_out, b.hit_point_out};
     dispatch_bool(b.query_mask != nullptr, [&](auto filt) {
-        hipLaunchKernelGGL((k_character<decltype(filt)::value>), dim3((unsigned)((b.n + kRcThreads - 1) / kRcThreads)), dim3(kRcThreads), 0, s,
-                           (uint32_t)b.n, b.pos, b.motion, b.rot, b.radius, b.half_length, b.grounded_in, b.skin, b.max_slides,
-                           b.step_height, b.snap_distance, b.min_floor_ny, b.ignore_body, qf,
-                           reinterpret_cast<const RcHeader*>(w->rc_header.p), bits, (const uint32_t*)w->rc_start.p,
-                           reinterpret_cast<const float4*>(w->rc_records.p), (uint32_t)w->n_owned, ground, w->cfg.ground_height,
-                           reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static, out);
+        hipLaunchKernelGGL((k_character<decltype(filt)::value>), dim3(rc_blocks(b.n)), dim3(kRcThreads), 0, w->stream, (uint32_t)b.n, b.pos,
+                           b.motion, b.rot, b.radius, b.half_length, b.grounded_in, b.skin, b.max_slides, b.step_height, b.snap_distance,
+                           b.min_floor_ny, b.ignore_body, qf, g.hdr, g.bits, g.start, g.rec, g.n_bodies, g.ground, g.ground_y, g.st_rec,
+                           g.n_static, out);
     });
     PHYS_HIP_TRY(hipGetLastError());
     return PHYS_OK;

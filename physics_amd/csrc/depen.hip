@@ -10,6 +10,8 @@
 // its state in registers through all rounds; the slots go straight to global memory, iteration-major (slot k of query i at
 // k * n + i), so nothing in private memory is indexed at run time. PROBE = true is the single probe behind phys_penetration: no
 // move, slot 0 is the answer.
+// The lane's query is loaded by capsule_query and its slots are written by query_slot (rc_grid.hpp), as in slide.hip and
+// character.hip; the host side is the one query path of DESIGN.md section 16, this family's launch_query at the end.
 #include "../../include/spec/depenetrate.h"
 #include "rc_grid.hpp"
 
@@ -45,12 +47,6 @@ struct DepenWorld {
     const float4* st_rec;
     uint32_t n_static;
 };
-
-__device__ __forceinline__ void depen_slot(const DepenOut& out, size_t at, uint32_t id, v3 n, float depth) {
-    if (out.hit_body) out.hit_body[at] = id;
-    if (out.hit_normal) { out.hit_normal[3 * at] = n.x; out.hit_normal[3 * at + 1] = n.y; out.hit_normal[3 * at + 2] = n.z; }
-    if (out.hit_depth) out.hit_depth[at] = depth;
-}
 
 __device__ __forceinline__ geom_t depen_geom(v3 c, float4 q4, v3 h, uint32_t type) {
     quat q; q.i = q4.x; q.j = q4.y; q.k = q4.z; q.w = q4.w;
@@ -132,19 +128,18 @@ __global__ __launch_bounds__(kRcThreads) void k_depen(uint32_t n, const float* _
                                                      DepenWorld w, DepenOut out) {
     const uint32_t i = blockIdx.x * kRcThreads + threadIdx.x;
     if (i >= n) return;
-    const uint32_t qm = FILT ? (uint32_t)qf.query_mask[i] : 0xFFFFu;
-    const v3 p0 = ld3(pos, i);
-    const float rad = radius[i], hq = half_length[i];
-    const uint32_t ign = ignore_body && ignore_body[i] < w.n_bodies ? ignore_body[i] : 0xFFFFFFFFu;
-    quat q; q.i = 0.0f; q.j = 0.0f; q.k = 0.0f; q.w = 1.0f;
-    if (rot) { q.i = rot[4 * (size_t)i]; q.j = rot[4 * (size_t)i + 1]; q.k = rot[4 * (size_t)i + 2]; q.w = rot[4 * (size_t)i + 3]; }
+    const CapsuleQuery c = capsule_query<FILT, false>(i, qf, pos, nullptr, rot, radius, half_length, ignore_body, w.n_bodies);
+    const uint32_t qm = c.qm, ign = c.ign;
+    const v3 p0 = c.p;
+    const float rad = c.rad, hq = c.hq;
+    const quat q = c.q;
     const bool valid = dp_valid(p0, rot != nullptr, q, rad, hq);
     // the capsule's core axis: the y axis of rot, used as given (the capsule cast's rule)
     const v3 a = rot ? dp_axis(q) : v3_make(0.0f, 1.0f, 0.0f);
     if (PROBE) {
         // an invalid query is a miss
         const dp_best best = valid ? depen_probe<FILT>(w, qf, qm, ign, p0, a, rad, hq, gap) : dp_none();
-        depen_slot(out, i, best.id, best.n, best.depth);
+        query_slot(out.hit_body, out.hit_normal, out.hit_depth, i, best.id, best.n, best.depth);
         return;
     }
     dp_state s;
@@ -156,32 +151,27 @@ __global__ __launch_bounds__(kRcThreads) void k_depen(uint32_t n, const float* _
         for (;; ++k) {
             const dp_best best = depen_probe<FILT>(w, qf, qm, ign, s.p, a, rad, hq, gap);
             if (!dp_step(&s, k, max_iters, gap, &best)) break;
-            depen_slot(out, (size_t)k * n + i, best.id, best.n, best.depth);
+            query_slot(out.hit_body, out.hit_normal, out.hit_depth, (size_t)k * n + i, best.id, best.n, best.depth);
         }
     }
-    // the kernel writes every slot: the unused ones are empty
-    for (uint32_t e = k; e < max_iters; ++e) depen_slot(out, (size_t)e * n + i, kRayMiss, v3_make(0.0f, 0.0f, 0.0f), 0.0f);
+    query_slots_empty(out.hit_body, out.hit_normal, out.hit_depth, 0u, k, max_iters, n, i, 0.0f);
     st3(out.pos, i, s.p);
     out.status[i] = s.status;
 }
 
 }  // namespace
 
-int32_t launch_depen(phys_world* w, const DepenBatch& b) {
-    hipStream_t s = w->stream;
-    uint32_t bits = 12;
-    PHYS_TRY(launch_query_grid(w, nullptr, nullptr, 0, &bits));
+int32_t launch_query(phys_world* w, const DepenBatch& b) {
+    QueryGrid g;
+    PHYS_TRY(query_grid(w, nullptr, nullptr, 0, &g));
     const QueryFilters qf = query_filters(w, b.query_mask);
-    const DepenWorld dw{reinterpret_cast<const RcHeader*>(w->rc_header.p), bits, (const uint32_t*)w->rc_start.p,
-                        reinterpret_cast<const float4*>(w->rc_records.p), (uint32_t)w->n_owned, w->pos.p, w->rot.p, w->half_extent.p,
-                        w->shape.p, (w->cfg.flags & PHYS_FLAG_GROUND_PLANE) ? 1 : 0, w->cfg.ground_height,
-                        reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static};
+    const DepenWorld dw{g.hdr, g.bits, g.start, g.rec, g.n_bodies, w->pos.p, w->rot.p, w->half_extent.p, w->shape.p,
+                        g.ground, g.ground_y, g.st_rec, g.n_static};
     const DepenOut out{b.pos_out, b.status_out, b.hit_body_out, b.hit_normal_out, b.hit_depth_out};
     dispatch_bool(b.query_mask != nullptr, [&](auto filt) {
         dispatch_bool(b.probe, [&](auto probe) {
-            hipLaunchKernelGGL((k_depen<decltype(filt)::value, decltype(probe)::value>), dim3((unsigned)((b.n + kRcThreads - 1) / kRcThreads)),
-                               dim3(kRcThreads), 0, s, (uint32_t)b.n, b.pos, b.rot, b.radius, b.half_length, b.gap, b.max_iters,
-                               b.ignore_body, qf, dw, out);
+            hipLaunchKernelGGL((k_depen<decltype(filt)::value, decltype(probe)::value>), dim3(rc_blocks(b.n)), dim3(kRcThreads), 0, w->stream,
+                               (uint32_t)b.n, b.pos, b.rot, b.radius, b.half_length, b.gap, b.max_iters, b.ignore_body, qf, dw, out);
         });
     });
     PHYS_HIP_TRY(hipGetLastError());

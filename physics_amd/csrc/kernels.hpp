@@ -371,27 +371,27 @@ int32_t static_set(phys_world* w, uint64_t n, const float* pos, const float* rot
 int32_t launch_static_pairs(phys_world* w);
 void static_narrow_args(const phys_world* w, uint64_t* cap, const uint32_t** pairs, const float** geo);
 
-// raycast.hip: builds the query's grid from the current poses and walks it for the batch's queries (device pointers, CastBatch:
-// staging.hpp), all on w->stream. Ray: radius unused. Sphere: balls of radius[i], the grid grown by the largest valid radius.
-// Capsule: core origin +- half_length * (rot's y axis), radius[i], the grid grown by the largest valid
-// radius + half_length; rot and point_out are read for this kind alone. A query_mask makes it the filtered instance.
-int32_t launch_cast(phys_world* w, CastKind kind, const CastBatch& b);
+// The query families' launchers, one overload per batch (staging.hpp; device pointers, arguments checked by the caller), all on
+// w->stream: each builds the query grid once from the current poses, then runs ONE kernel with a query per lane. A query_mask
+// makes it the filtered instance.
+// raycast.hip: the casts. Ray: radius unused. Sphere: balls of radius[i], the grid grown by the largest valid radius. Capsule
+// (DESIGN.md section 23): core origin +- half_length * (rot's y axis), radius[i], the grid grown by the largest valid radius +
+// half_length; rot and point_out are read for this kind alone.
+int32_t launch_query(phys_world* w, CastKind kind, const CastBatch& b);
+// slide.hip: move-and-slide: the grid grown as for a capsule cast; every lane runs its character's whole
+// cast, stop, project loop (include/spec/slide.h) against the capsule cast's own walk
+int32_t launch_query(phys_world* w, const SlideBatch& b);
+// character.hip: character walking: the grid grown as for a capsule cast; every lane drives its character's
+// state machine (include/spec/character.h) around the capsule cast's own walk
+int32_t launch_query(phys_world* w, const CharacterBatch& b);
+// depen.hip: depenetration: the grid not grown; every lane probes for its capsule's deepest target (b.probe:
+// that is the answer) and runs the push-out loop of include/spec/depenetrate.h, probing again from where each push left it
+int32_t launch_query(phys_world* w, const DepenBatch& b);
 // the query grid alone (rc_header, rc_start, rc_records), every body AABB grown by the largest valid value of the n_grow
 // values of the device array grow_radius (null: not grown), plus grow_half_length's of the same query where that is given (a
-// capsule reaches radius + half_length from its centre); *bits = log2 of the bucket table
+// capsule reaches radius + half_length from its centre); *bits = log2 of the bucket table (rc_grid.hpp query_grid: the same
+// with everything a query kernel takes of the world in one struct)
 int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* grow_half_length, uint64_t n_grow, uint32_t* bits);
-// slide.hip: move-and-slide (SlideBatch: staging.hpp, device pointers, arguments checked by the caller): the
-// query grid once, grown by the call's largest valid radius + half_length, then ONE kernel in which every lane runs its
-// character's whole cast, stop, project loop (include/spec/slide.h) against the capsule cast's own walk
-int32_t launch_slide(phys_world* w, const SlideBatch& b);
-// character.hip: character walking (CharacterBatch: staging.hpp, device pointers, arguments checked by the
-// caller): the query grid once, grown by the call's largest valid radius + half_length, then ONE kernel in which every lane
-// drives its character's state machine (include/spec/character.h) around the capsule cast's own walk
-int32_t launch_character(phys_world* w, const CharacterBatch& b);
-// depen.hip: depenetration (DepenBatch: staging.hpp, device pointers, arguments checked by the caller): the
-// query grid once, not grown, then ONE kernel in which every lane probes for its capsule's deepest target (b.probe: that is
-// the answer) and runs the push-out loop of include/spec/depenetrate.h, probing again from where each push left it
-int32_t launch_depen(phys_world* w, const DepenBatch& b);
 // query.hip: overlap queries on staged device arrays; writes the host offsets (n + 1) and, when they fit in cap, the ids
 int32_t launch_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot, const float* half_extent,
                        const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out,

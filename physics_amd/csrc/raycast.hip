@@ -248,8 +248,6 @@ __global__ __launch_bounds__(kRcThreads) void k_sc_grow(uint32_t n, const float*
 
 }  // namespace
 
-unsigned rc_blocks(uint64_t n) { return (unsigned)((n + kRcThreads - 1) / kRcThreads); }
-
 int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* grow_half_length, uint64_t n_grow, uint32_t* bits_out) {
     hipStream_t s = w->stream;
     const uint64_t n = w->n_owned;
@@ -288,28 +286,23 @@ int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* 
 }
 
 // the walk shared by ray casts, sphere casts and capsule casts: the kind names the kernel instance, the arrays are the batch's
-int32_t launch_cast(phys_world* w, CastKind kind, const CastBatch& b) {
+int32_t launch_query(phys_world* w, CastKind kind, const CastBatch& b) {
     hipStream_t s = w->stream;
-    const uint64_t n = w->n_owned;
     const bool sweep = kind != CastKind::Ray, capsule = kind == CastKind::Capsule;
     const float* radius = sweep ? b.radius : nullptr;
     const CapsuleArgs caps{b.rot, b.half_length, b.point_out};
-    uint32_t bits = 12;
-    PHYS_TRY(launch_query_grid(w, radius, capsule ? b.half_length : nullptr, sweep ? b.n : 0, &bits));
-    const RcHeader* hdr = reinterpret_cast<const RcHeader*>(w->rc_header.p);
+    QueryGrid g;
+    PHYS_TRY(query_grid(w, radius, capsule ? b.half_length : nullptr, sweep ? b.n : 0, &g));
     const bool stats = debug_switches().raycast_stats;
     if (stats) {
         PHYS_HIP_TRY(w->rc_stats.resize(2));
         PHYS_HIP_TRY(hipMemsetAsync(w->rc_stats.p, 0, 16, s));
     }
-    const int ground = (w->cfg.flags & PHYS_FLAG_GROUND_PLANE) ? 1 : 0;
     const QueryFilters qf = query_filters(w, b.query_mask);
 #define PHYS_RC_LAUNCH(SW, FILT, ...)                                                                                        \
     hipLaunchKernelGGL((k_rc_trace<kSt, SW, FILT>), dim3(rc_blocks(b.n)), dim3(kRcThreads), 0, s, (uint32_t)b.n, b.origin, b.dir,   \
-                       radius, b.max_t, b.ignore_body, hdr, bits, (const uint32_t*)w->rc_start.p,                                  \
-                       reinterpret_cast<const float4*>(w->rc_records.p), (uint32_t)n, ground, w->cfg.ground_height,               \
-                       reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static, b.body_out, b.t_out, b.normal_out,     \
-                       w->rc_stats.p, ##__VA_ARGS__)
+                       radius, b.max_t, b.ignore_body, g.hdr, g.bits, g.start, g.rec, g.n_bodies, g.ground, g.ground_y, g.st_rec,  \
+                       g.n_static, b.body_out, b.t_out, b.normal_out, w->rc_stats.p, ##__VA_ARGS__)
     dispatch_bool(stats, [&](auto st) {
         constexpr bool kSt = decltype(st)::value;
         if (capsule) {

@@ -1,6 +1,7 @@
 // rc_grid.hpp — what the read-only queries share: the per-call query grid (raycast.hip builds it; ray casts, sphere casts
 // and overlap queries walk it) and the exact ray tests against one sphere, capsule or box. A sphere cast is a ray cast
 // against the target grown by the ball's radius, so it calls the same tests with grown sizes (DESIGN.md sections 9, 12).
+// At the end: what the capsule query kernels share (the load of a lane's query, the slot writer) and the host's QueryGrid.
 #pragma once
 #include "kernels.hpp"
 
@@ -241,6 +242,77 @@ __device__ __forceinline__ void rc_capsule_axis(float4 q4, float& wx, float& wy,
     wy = (((qw * qw) - (qi * qi)) + (qj * qj)) - (qk * qk);
     wz = (qw * qi * 2.0f) + (qj * qk * 2.0f);
 }
+
+// --- what the capsule query kernels share (k_slide, k_character, k_depen: one capsule per lane, hit slots iteration-major)
+
+// a lane's query as they load it: its mask (0xFFFF without filtering), where it stands and, with MOTION, its motion (zero
+// otherwise: depenetration has none), radius and half-length, the body it never reports (0xFFFFFFFF: none, also for an id that
+// is no owned body's), rot as given or the identity; the loads in the order the three kernels made them
+struct CapsuleQuery {
+    uint32_t qm;
+    v3 p, m;
+    float rad, hq;
+    uint32_t ign;
+    quat q;
+};
+template <bool FILT, bool MOTION>
+__device__ __forceinline__ CapsuleQuery capsule_query(uint32_t i, const QueryFilters& qf, const float* __restrict__ pos,
+                                                      const float* __restrict__ motion, const float* __restrict__ rot,
+                                                      const float* __restrict__ radius, const float* __restrict__ half_length,
+                                                      const uint32_t* __restrict__ ignore_body, uint32_t n_bodies) {
+    CapsuleQuery c;
+    c.qm = FILT ? (uint32_t)qf.query_mask[i] : 0xFFFFu;
+    c.p = ld3(pos, i);
+    c.m = v3_make(0.0f, 0.0f, 0.0f);
+    if constexpr (MOTION) c.m = ld3(motion, i);
+    c.rad = radius[i]; c.hq = half_length[i];
+    c.ign = ignore_body && ignore_body[i] < n_bodies ? ignore_body[i] : 0xFFFFFFFFu;
+    c.q.i = 0.0f; c.q.j = 0.0f; c.q.k = 0.0f; c.q.w = 1.0f;
+    if (rot) { c.q.i = rot[4 * (size_t)i]; c.q.j = rot[4 * (size_t)i + 1]; c.q.k = rot[4 * (size_t)i + 2]; c.q.w = rot[4 * (size_t)i + 3]; }
+    return c;
+}
+
+// one slot (a hit, or the character's floor): id, normal and a last value - the touched point, or the depth for
+// depenetration - each where its array is wanted
+__device__ __forceinline__ void slot_put(float* a, size_t at, v3 v) { a[3 * at] = v.x; a[3 * at + 1] = v.y; a[3 * at + 2] = v.z; }
+__device__ __forceinline__ void slot_put(float* a, size_t at, float v) { a[at] = v; }
+template <typename T>
+__device__ __forceinline__ void query_slot(uint32_t* body, float* normal, float* last, size_t at, uint32_t id, v3 n, T v) {
+    if (body) body[at] = id;
+    if (normal) slot_put(normal, at, n);
+    if (last) slot_put(last, at, v);
+}
+// the kernels write every slot: of the `count` slots of query i of n that begin at slot `first`, those from `used` on, which no
+// round used, are empty (`zero`: the last value's)
+template <typename T>
+__device__ __forceinline__ void query_slots_empty(uint32_t* body, float* normal, float* last, uint32_t first, uint32_t used,
+                                                  uint32_t count, uint32_t n, uint32_t i, T zero) {
+    for (uint32_t e = used; e < count; ++e)
+        query_slot(body, normal, last, (size_t)(first + e) * n + i, kRayMiss, v3_make(0.0f, 0.0f, 0.0f), zero);
+}
+
+// host: what a query kernel takes of the world, as launch_query_grid has just left it: the grid (header, log2 of the bucket
+// table, bucket starts, records), the ground, the statics' records. The kernels take the members as plain arguments.
+struct QueryGrid {
+    const RcHeader* hdr;
+    uint32_t bits;
+    const uint32_t* start;
+    const float4* rec;
+    uint32_t n_bodies;
+    int ground;
+    float ground_y;
+    const float4* st_rec;
+    uint32_t n_static;
+};
+inline int32_t query_grid(phys_world* w, const float* grow_radius, const float* grow_half_length, uint64_t n_grow, QueryGrid* g) {
+    uint32_t bits = 12;
+    PHYS_TRY(launch_query_grid(w, grow_radius, grow_half_length, n_grow, &bits));
+    *g = {reinterpret_cast<const RcHeader*>(w->rc_header.p), bits, (const uint32_t*)w->rc_start.p,
+          reinterpret_cast<const float4*>(w->rc_records.p), (uint32_t)w->n_owned, (w->cfg.flags & PHYS_FLAG_GROUND_PLANE) ? 1 : 0,
+          w->cfg.ground_height, reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static};
+    return PHYS_OK;
+}
+inline unsigned rc_blocks(uint64_t n) { return (unsigned)((n + kRcThreads - 1) / kRcThreads); }
 
 }  // namespace
 }  // namespace phys

@@ -9,6 +9,8 @@
 // but these two is arithmetic here. The hit slots go straight to global memory, iteration-major (slot k of query i at
 // k * n + i: the lanes of a wave write side by side), so nothing in private memory is indexed at run time.
 // Lanes of a wave leave the loop at different rounds and wait for the longest: the price of one launch.
+// The lane's query is loaded by capsule_query and its slots are written by query_slot (rc_grid.hpp), as in character.hip and
+// depen.hip; the host side is the one query path of DESIGN.md section 16, this family's launch_query at the end.
 #include "../../include/spec/slide.h"
 #include "cast_walk.hpp"
 
@@ -30,12 +32,6 @@ struct SlideOut {
     float* hit_point;
 };
 
-__device__ __forceinline__ void slide_slot(const SlideOut& out, size_t at, uint32_t id, v3 n, v3 point) {
-    if (out.hit_body) out.hit_body[at] = id;
-    if (out.hit_normal) { out.hit_normal[3 * at] = n.x; out.hit_normal[3 * at + 1] = n.y; out.hit_normal[3 * at + 2] = n.z; }
-    if (out.hit_point) { out.hit_point[3 * at] = point.x; out.hit_point[3 * at + 1] = point.y; out.hit_point[3 * at + 2] = point.z; }
-}
-
 // FILT: a query_mask was given: a target whose category misses the query's mask is skipped before its exact test (qf is
 // read by this instance alone)
 template <bool FILT>
@@ -48,12 +44,11 @@ __global__ __launch_bounds__(kRcThreads) void k_slide(uint32_t n, const float* _
                                                      const float4* __restrict__ st_rec, uint32_t n_static, SlideOut out) {
     const uint32_t i = blockIdx.x * kRcThreads + threadIdx.x;
     if (i >= n) return;
-    const uint32_t qm = FILT ? (uint32_t)qf.query_mask[i] : 0xFFFFu;
-    const v3 p0 = ld3(pos, i), m0 = ld3(motion, i);
-    const float rad = radius[i], hq = half_length[i];
-    const uint32_t ign = ignore_body && ignore_body[i] < n_bodies ? ignore_body[i] : 0xFFFFFFFFu;
-    quat q; q.i = 0.0f; q.j = 0.0f; q.k = 0.0f; q.w = 1.0f;
-    if (rot) { q.i = rot[4 * (size_t)i]; q.j = rot[4 * (size_t)i + 1]; q.k = rot[4 * (size_t)i + 2]; q.w = rot[4 * (size_t)i + 3]; }
+    const CapsuleQuery c = capsule_query<FILT, true>(i, qf, pos, motion, rot, radius, half_length, ignore_body, n_bodies);
+    const uint32_t qm = c.qm, ign = c.ign;
+    const v3 p0 = c.p, m0 = c.m;
+    const float rad = c.rad, hq = c.hq;
+    const quat q = c.q;
     sl_state s;
     sl_begin(&s, p0, m0);
     uint32_t k = 0;  // slots written
@@ -75,13 +70,12 @@ __global__ __launch_bounds__(kRcThreads) void k_slide(uint32_t n, const float* _
                                              sl_max_t(L, skin), ign, rad, hq, ax, ay, az, cap_ok, best, point, cells, cands);
             if (best.id == kRayMiss) { sl_miss(&s); ran_out = false; break; }
             const v3 nrm = v3_make(best.nx, best.ny, best.nz);
-            slide_slot(out, (size_t)k * n + i, best.id, nrm, point);
+            query_slot(out.hit_body, out.hit_normal, out.hit_point, (size_t)k * n + i, best.id, nrm, point);
             if (!sl_hit(&s, L, skin, best.t, nrm)) { ++k; ran_out = false; break; }
         }
         if (ran_out) sl_ran_out(&s);
     }
-    // the kernel writes every slot: the unused ones are empty
-    for (uint32_t e = k; e < max_slides; ++e) slide_slot(out, (size_t)e * n + i, kRayMiss, v3_make(0.0f, 0.0f, 0.0f), v3_make(0.0f, 0.0f, 0.0f));
+    query_slots_empty(out.hit_body, out.hit_normal, out.hit_point, 0u, k, max_slides, n, i, v3_make(0.0f, 0.0f, 0.0f));
     st3(out.pos, i, s.p);
     if (out.remaining) st3(out.remaining, i, s.m);
     out.status[i] = s.status;
@@ -89,19 +83,15 @@ __global__ __launch_bounds__(kRcThreads) void k_slide(uint32_t n, const float* _
 
 }  // namespace
 
-int32_t launch_slide(phys_world* w, const SlideBatch& b) {
-    hipStream_t s = w->stream;
-    uint32_t bits = 12;
-    PHYS_TRY(launch_query_grid(w, b.radius, b.half_length, b.n, &bits));
-    const int ground = (w->cfg.flags & PHYS_FLAG_GROUND_PLANE) ? 1 : 0;
+int32_t launch_query(phys_world* w, const SlideBatch& b) {
+    QueryGrid g;
+    PHYS_TRY(query_grid(w, b.radius, b.half_length, b.n, &g));
     const QueryFilters qf = query_filters(w, b.query_mask);
     const SlideOut out{b.pos_out, b.remaining_out, b.status_out, b.hit_body_out, b.hit_normal_out, b.hit_point_out};
     dispatch_bool(b.query_mask != nullptr, [&](auto filt) {
-        hipLaunchKernelGGL((k_slide<decltype(filt)::value>), dim3((unsigned)((b.n + kRcThreads - 1) / kRcThreads)), dim3(kRcThreads), 0, s,
-                           (uint32_t)b.n, b.pos, b.motion, b.rot, b.radius, b.half_length, b.skin, b.max_slides, b.ignore_body, qf,
-                           reinterpret_cast<const RcHeader*>(w->rc_header.p), bits, (const uint32_t*)w->rc_start.p,
-                           reinterpret_cast<const float4*>(w->rc_records.p), (uint32_t)w->n_owned, ground, w->cfg.ground_height,
-                           reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static, out);
+        hipLaunchKernelGGL((k_slide<decltype(filt)::value>), dim3(rc_blocks(b.n)), dim3(kRcThreads), 0, w->stream, (uint32_t)b.n, b.pos,
+                           b.motion, b.rot, b.radius, b.half_length, b.skin, b.max_slides, b.ignore_body, qf, g.hdr, g.bits, g.start, g.rec,
+                           g.n_bodies, g.ground, g.ground_y, g.st_rec, g.n_static, out);
     });
     PHYS_HIP_TRY(hipGetLastError());
     return PHYS_OK;

@@ -1,12 +1,27 @@
-// staging.hpp — how a query call describes its arrays: the batch of one cast (rays, balls, capsules alike) and of one
-// move-and-slide or depenetration call, what their entry points check of them, and where a call's host arrays lie in the one
-// device buffer they are staged in. Host-only like setup.hpp
-// (no HIP, no phys_world), held to tests/cpp/staging_probe.cpp. abi.hip keeps the buffer, the copies and the launch.
+// staging.hpp — how a query call describes its arrays, once: a batch struct per family (casts,
+// move-and-slide, character walking, depenetration) with its one array list `arrays`, what its entry points check of it
+// (args_error), and where a call's host arrays lie in the device buffers they are staged in (StageLayout, stage, staged).
+// Host-only like setup.hpp (no HIP, no phys_world), held to tests/cpp/staging_probe.cpp. abi.hip keeps the buffers, the copies
+// and the launch: one host path and one device path for every batch here.
+//
+// A batch's `arrays(b, f)` names every array once, in the order they are staged: f(member, elements per query, group). The
+// groups go to a buffer each, so only the order within a group is layout.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
 namespace phys {
+
+// the buffers a call's arrays are staged in: the inputs, the per-query outputs, and the character's hit slots (that call has
+// nine outputs, a layout holds eight arrays)
+enum StageGroup { kStageIn, kStageOut, kStageSlots, kStageGroups };
+
+// what every entry point checks of its per-call values, stated once
+inline bool count_ok(uint64_t n) { return n < (1ull << 31); }                     // the kernels index queries with 32 bits
+inline bool length_ok(float x) { return x >= 0.0f && x <= 3.4028235e38f; }         // finite and not negative (-0 passes, NaN does not)
+constexpr uint32_t kSlideMaxSlides = 8, kDepenMaxIters = 8;
+inline bool rounds_ok(uint32_t k) { return k >= 1u && k <= 8u; }                   // max_slides, max_iters: "1 .. 8" in the texts
+static_assert(kSlideMaxSlides == 8 && kDepenMaxIters == 8, "rounds_ok and the refusal texts say 1 .. 8");
 
 enum class CastKind { Ray, Sphere, Capsule };
 
@@ -22,29 +37,148 @@ struct CastBatch {
     uint32_t* body_out;
     float* t_out;
     float *normal_out, *point_out;     // 3 per query; null: not wanted (point_out: capsules)
+
+    template <class Batch, class F>
+    static void arrays(Batch& b, F&& f) {
+        f(b.origin, 3, kStageIn); f(b.dir, 3, kStageIn); f(b.rot, 4, kStageIn); f(b.radius, 1, kStageIn); f(b.half_length, 1, kStageIn);
+        f(b.max_t, 1, kStageIn); f(b.ignore_body, 1, kStageIn); f(b.query_mask, 1, kStageIn);
+        f(b.body_out, 1, kStageOut); f(b.t_out, 1, kStageOut); f(b.normal_out, 3, kStageOut); f(b.point_out, 3, kStageOut);
+    }
 };
 
-// Every array of a cast once, in the order they are staged: f(member, elements per query, is it an output). The inputs and
-// the outputs go to a buffer each, so only the order within each group is layout.
-template <class Batch, class F>
-inline void for_each_cast_array(Batch& b, F&& f) {
-    f(b.origin, 3, false); f(b.dir, 3, false); f(b.rot, 4, false); f(b.radius, 1, false); f(b.half_length, 1, false);
-    f(b.max_t, 1, false); f(b.ignore_body, 1, false); f(b.query_mask, 1, false);
-    f(b.body_out, 1, true); f(b.t_out, 1, true); f(b.normal_out, 3, true); f(b.point_out, 3, true);
-}
-
-// what every cast entry point checks before it touches anything: the text of the refusal, null when the call may go on.
-// Each family names its own required arrays; everything else is optional.
-inline const char* cast_args_error(CastKind kind, const CastBatch& b) {
+// what every entry point of a family checks before it touches anything: the text of the refusal, null when the call may go
+// on. Each family names its own required arrays; everything else is optional.
+inline const char* args_error(CastKind kind, const CastBatch& b) {
     static const char* const too_many[] = {"phys_raycast: n_rays must be below 2^31", "phys_spherecast: n must be below 2^31",
                                            "phys_capsulecast: n must be below 2^31"};
     static const char* const null_array[] = {"phys_raycast: null origin, dir, body_out or t_out",
                                              "phys_spherecast: null origin, dir, radius, body_out or t_out",
                                              "phys_capsulecast: null origin, dir, radius, half_length, body_out or t_out"};
-    if (b.n >= (1ull << 31)) return too_many[(int)kind];
+    if (!count_ok(b.n)) return too_many[(int)kind];
     const bool missing = !b.origin || !b.dir || (kind != CastKind::Ray && !b.radius) || (kind == CastKind::Capsule && !b.half_length) ||
                          !b.body_out || !b.t_out;
     return b.n && missing ? null_array[(int)kind] : nullptr;
+}
+
+// ---- move-and-slide (phys_move_and_slide, DESIGN.md section 25): the arrays of one call, n characters; host pointers or device
+// pointers alike. Slot k of query i lies at index k * n + i of the hit arrays.
+struct SlideBatch {
+    uint64_t n;
+    const float *pos, *motion;         // 3 per query
+    const float* rot;                  // [i, j, k, w] per query; null: identity
+    const float *radius, *half_length; // per query
+    float skin;                        // the call's: finite, >= 0
+    uint32_t max_slides;               // the call's: 1 .. 8
+    const uint32_t* ignore_body;       // null: none
+    const uint16_t* query_mask;        // null: no filtering
+    float *pos_out, *remaining_out;    // 3 per query; remaining_out may be null
+    uint32_t* status_out;
+    uint32_t* hit_body_out;            // max_slides per query; null: not wanted
+    float *hit_normal_out, *hit_point_out;  // 3 * max_slides per query; null: not wanted
+
+    template <class Batch, class F>
+    static void arrays(Batch& b, F&& f) {
+        const size_t k = b.max_slides;
+        f(b.pos, 3, kStageIn); f(b.motion, 3, kStageIn); f(b.rot, 4, kStageIn); f(b.radius, 1, kStageIn); f(b.half_length, 1, kStageIn);
+        f(b.ignore_body, 1, kStageIn); f(b.query_mask, 1, kStageIn);
+        f(b.pos_out, 3, kStageOut); f(b.remaining_out, 3, kStageOut); f(b.status_out, 1, kStageOut);
+        f(b.hit_body_out, k, kStageOut); f(b.hit_normal_out, 3 * k, kStageOut); f(b.hit_point_out, 3 * k, kStageOut);
+    }
+};
+
+inline const char* args_error(const SlideBatch& b) {
+    if (!count_ok(b.n)) return "phys_move_and_slide: n must be below 2^31";
+    if (!length_ok(b.skin)) return "phys_move_and_slide: skin must be finite and not negative";
+    if (!rounds_ok(b.max_slides)) return "phys_move_and_slide: max_slides must be 1 .. 8";
+    const bool missing = !b.pos || !b.motion || !b.radius || !b.half_length || !b.pos_out || !b.status_out;
+    return b.n && missing ? "phys_move_and_slide: null pos, motion, radius, half_length, pos_out or status_out" : nullptr;
+}
+
+// ---- character walking (phys_character_move, DESIGN.md section 28): the arrays of one call, n characters; host pointers or
+// device pointers alike. Slot k of query i lies at index k * n + i of the hit arrays, 2 * max_slides slots per query.
+struct CharacterBatch {
+    uint64_t n;
+    const float *pos, *motion;         // 3 per query
+    const float* rot;                  // [i, j, k, w] per query; null: identity
+    const float *radius, *half_length; // per query
+    const uint32_t* grounded_in;       // per query, non-zero: stood on a floor when its last call ended; null: nobody did
+    float skin;                        // the call's: finite, >= 0
+    uint32_t max_slides;               // the call's: 1 .. 8
+    float step_height, snap_distance;  // the call's: finite, >= 0
+    float min_floor_ny;                // the call's: in (0, 1]
+    const uint32_t* ignore_body;       // null: none
+    const uint16_t* query_mask;        // null: no filtering
+    float *pos_out, *remaining_out;    // 3 per query; remaining_out may be null
+    uint32_t* status_out;
+    uint32_t* floor_body_out;          // per query; null: not wanted
+    float *floor_normal_out, *floor_point_out;  // 3 per query; null: not wanted
+    uint32_t* hit_body_out;            // 2 * max_slides per query; null: not wanted
+    float *hit_normal_out, *hit_point_out;  // 3 * 2 * max_slides per query; null: not wanted
+
+    template <class Batch, class F>
+    static void arrays(Batch& b, F&& f) {
+        const size_t k = 2 * (size_t)b.max_slides;
+        f(b.pos, 3, kStageIn); f(b.motion, 3, kStageIn); f(b.rot, 4, kStageIn); f(b.radius, 1, kStageIn); f(b.half_length, 1, kStageIn);
+        f(b.grounded_in, 1, kStageIn); f(b.ignore_body, 1, kStageIn); f(b.query_mask, 1, kStageIn);
+        f(b.pos_out, 3, kStageOut); f(b.remaining_out, 3, kStageOut); f(b.status_out, 1, kStageOut);
+        f(b.floor_body_out, 1, kStageOut); f(b.floor_normal_out, 3, kStageOut); f(b.floor_point_out, 3, kStageOut);
+        f(b.hit_body_out, k, kStageSlots); f(b.hit_normal_out, 3 * k, kStageSlots); f(b.hit_point_out, 3 * k, kStageSlots);
+    }
+};
+
+inline const char* args_error(const CharacterBatch& b) {
+    if (!count_ok(b.n)) return "phys_character_move: n must be below 2^31";
+    if (!length_ok(b.skin)) return "phys_character_move: skin must be finite and not negative";
+    if (!rounds_ok(b.max_slides)) return "phys_character_move: max_slides must be 1 .. 8";
+    if (!length_ok(b.step_height)) return "phys_character_move: step_height must be finite and not negative";
+    if (!length_ok(b.snap_distance)) return "phys_character_move: snap_distance must be finite and not negative";
+    if (!(b.min_floor_ny > 0.0f && b.min_floor_ny <= 1.0f)) return "phys_character_move: min_floor_ny must lie in (0, 1]";
+    const bool missing = !b.pos || !b.motion || !b.radius || !b.half_length || !b.pos_out || !b.status_out;
+    return b.n && missing ? "phys_character_move: null pos, motion, radius, half_length, pos_out or status_out" : nullptr;
+}
+
+// ---- depenetration (phys_penetration and phys_depenetrate, DESIGN.md section 27): the arrays of one call, n capsules; host
+// pointers or device pointers alike. probe: phys_penetration, one probe and no move: gap is the call's max_gap, max_iters 1, and
+// the one slot per query is the answer (hit_body_out = body_out, hit_normal_out = normal_out, hit_depth_out = depth_out;
+// pos_out and status_out null). Otherwise phys_depenetrate: gap is the call's skin, slot k of query i lies at index k * n + i.
+struct DepenBatch {
+    uint64_t n;
+    const float* pos;                  // 3 per query
+    const float* rot;                  // [i, j, k, w] per query; null: identity
+    const float *radius, *half_length; // per query
+    float gap;                         // the call's max_gap or skin: finite, >= 0
+    uint32_t max_iters;                // the call's: 1 .. 8
+    bool probe;
+    const uint32_t* ignore_body;       // null: none
+    const uint16_t* query_mask;        // null: no filtering
+    float* pos_out;                    // 3 per query
+    uint32_t* status_out;
+    uint32_t* hit_body_out;            // max_iters per query
+    float* hit_normal_out;             // 3 * max_iters per query
+    float* hit_depth_out;              // max_iters per query
+
+    template <class Batch, class F>
+    static void arrays(Batch& b, F&& f) {
+        const size_t k = b.max_iters;
+        f(b.pos, 3, kStageIn); f(b.rot, 4, kStageIn); f(b.radius, 1, kStageIn); f(b.half_length, 1, kStageIn);
+        f(b.ignore_body, 1, kStageIn); f(b.query_mask, 1, kStageIn);
+        f(b.pos_out, 3, kStageOut); f(b.status_out, 1, kStageOut);
+        f(b.hit_body_out, k, kStageOut); f(b.hit_normal_out, 3 * k, kStageOut); f(b.hit_depth_out, k, kStageOut);
+    }
+};
+
+inline const char* args_error(const DepenBatch& b) {
+    if (b.probe) {
+        if (!count_ok(b.n)) return "phys_penetration: n must be below 2^31";
+        if (!length_ok(b.gap)) return "phys_penetration: max_gap must be finite and not negative";
+        const bool missing = !b.pos || !b.radius || !b.half_length || !b.hit_body_out || !b.hit_depth_out;
+        return b.n && missing ? "phys_penetration: null pos, radius, half_length, body_out or depth_out" : nullptr;
+    }
+    if (!count_ok(b.n)) return "phys_depenetrate: n must be below 2^31";
+    if (!length_ok(b.gap)) return "phys_depenetrate: skin must be finite and not negative";
+    if (!rounds_ok(b.max_iters)) return "phys_depenetrate: max_iters must be 1 .. 8";
+    const bool missing = !b.pos || !b.radius || !b.half_length || !b.pos_out || !b.status_out;
+    return b.n && missing ? "phys_depenetrate: null pos, radius, half_length, pos_out or status_out" : nullptr;
 }
 
 // The layout of a call's host arrays in ONE device buffer: a bump allocator. The call declares its arrays in order (add);
@@ -75,203 +209,17 @@ struct StageLayout {
     }
 };
 
-// a cast on host arrays declares them: the inputs in one buffer, the outputs in another ...
-inline void stage_cast(const CastBatch& host, StageLayout& in, StageLayout& out) {
-    for_each_cast_array(host, [&](auto* array, size_t per_query, bool output) { (output ? out : in).add(array, per_query * host.n); });
+// a call on host arrays declares them, each in its group's layout (Layout: a StageLayout or what abi.hip derives from it) ...
+template <class Batch, class Layout>
+inline void stage(const Batch& host, Layout (&layouts)[kStageGroups]) {
+    Batch::arrays(host, [&](auto* array, size_t per_query, StageGroup g) { layouts[g].add(array, per_query * host.n); });
 }
-// ... and is the same batch on the device once the two buffers are there: the same declarations again, over their bases
-inline CastBatch staged_cast(const CastBatch& host, uint8_t* in_base, uint8_t* out_base) {
-    CastBatch dev = host;
-    StageLayout in, out;
-    for_each_cast_array(dev, [&](auto*& array, size_t per_query, bool output) {
-        StageLayout& l = output ? out : in;
-        array = l.at(output ? out_base : in_base, l.add(array, per_query * host.n));
-    });
-    return dev;
-}
-
-// ---- move-and-slide (phys_move_and_slide, DESIGN.md section 25): the arrays of one call, n characters; host pointers or device
-// pointers alike. Slot k of query i lies at index k * n + i of the hit arrays.
-struct SlideBatch {
-    uint64_t n;
-    const float *pos, *motion;         // 3 per query
-    const float* rot;                  // [i, j, k, w] per query; null: identity
-    const float *radius, *half_length; // per query
-    float skin;                        // the call's: finite, >= 0
-    uint32_t max_slides;               // the call's: 1 .. 8
-    const uint32_t* ignore_body;       // null: none
-    const uint16_t* query_mask;        // null: no filtering
-    float *pos_out, *remaining_out;    // 3 per query; remaining_out may be null
-    uint32_t* status_out;
-    uint32_t* hit_body_out;            // max_slides per query; null: not wanted
-    float *hit_normal_out, *hit_point_out;  // 3 * max_slides per query; null: not wanted
-};
-
-constexpr uint32_t kSlideMaxSlides = 8;
-
-// every array of a call once, in the order they are staged: f(member, elements per query, is it an output)
-template <class Batch, class F>
-inline void for_each_slide_array(Batch& b, F&& f) {
-    const size_t k = b.max_slides;
-    f(b.pos, 3, false); f(b.motion, 3, false); f(b.rot, 4, false); f(b.radius, 1, false); f(b.half_length, 1, false);
-    f(b.ignore_body, 1, false); f(b.query_mask, 1, false);
-    f(b.pos_out, 3, true); f(b.remaining_out, 3, true); f(b.status_out, 1, true);
-    f(b.hit_body_out, k, true); f(b.hit_normal_out, 3 * k, true); f(b.hit_point_out, 3 * k, true);
-}
-
-// what both entry points check before they touch anything: the text of the refusal, null when the call may go on
-inline const char* slide_args_error(const SlideBatch& b) {
-    if (b.n >= (1ull << 31)) return "phys_move_and_slide: n must be below 2^31";
-    if (!(b.skin >= 0.0f && b.skin <= 3.4028235e38f)) return "phys_move_and_slide: skin must be finite and not negative";
-    if (b.max_slides < 1u || b.max_slides > kSlideMaxSlides) return "phys_move_and_slide: max_slides must be 1 .. 8";
-    const bool missing = !b.pos || !b.motion || !b.radius || !b.half_length || !b.pos_out || !b.status_out;
-    return b.n && missing ? "phys_move_and_slide: null pos, motion, radius, half_length, pos_out or status_out" : nullptr;
-}
-
-// a call on host arrays declares them: the inputs in one buffer, the outputs in another ...
-inline void stage_slide(const SlideBatch& host, StageLayout& in, StageLayout& out) {
-    for_each_slide_array(host, [&](auto* array, size_t per_query, bool output) { (output ? out : in).add(array, per_query * host.n); });
-}
-// ... and is the same batch on the device once the two buffers are there
-inline SlideBatch staged_slide(const SlideBatch& host, uint8_t* in_base, uint8_t* out_base) {
-    SlideBatch dev = host;
-    StageLayout in, out;
-    for_each_slide_array(dev, [&](auto*& array, size_t per_query, bool output) {
-        StageLayout& l = output ? out : in;
-        array = l.at(output ? out_base : in_base, l.add(array, per_query * host.n));
-    });
-    return dev;
-}
-
-// ---- character walking (phys_character_move, DESIGN.md section 28): the arrays of one call, n characters; host pointers or
-// device pointers alike. Slot k of query i lies at index k * n + i of the hit arrays, 2 * max_slides slots per query.
-struct CharacterBatch {
-    uint64_t n;
-    const float *pos, *motion;         // 3 per query
-    const float* rot;                  // [i, j, k, w] per query; null: identity
-    const float *radius, *half_length; // per query
-    const uint32_t* grounded_in;       // per query, non-zero: stood on a floor when its last call ended; null: nobody did
-    float skin;                        // the call's: finite, >= 0
-    uint32_t max_slides;               // the call's: 1 .. 8
-    float step_height, snap_distance;  // the call's: finite, >= 0
-    float min_floor_ny;                // the call's: in (0, 1]
-    const uint32_t* ignore_body;       // null: none
-    const uint16_t* query_mask;        // null: no filtering
-    float *pos_out, *remaining_out;    // 3 per query; remaining_out may be null
-    uint32_t* status_out;
-    uint32_t* floor_body_out;          // per query; null: not wanted
-    float *floor_normal_out, *floor_point_out;  // 3 per query; null: not wanted
-    uint32_t* hit_body_out;            // 2 * max_slides per query; null: not wanted
-    float *hit_normal_out, *hit_point_out;  // 3 * 2 * max_slides per query; null: not wanted
-};
-
-// where an array of a character call is staged: the inputs, the per-query outputs, and the hit slots in a layout of their
-// own (the call has nine outputs, a layout holds eight arrays)
-enum class CharacterGroup { In, Out, Slots };
-
-// every array of a call once, in the order they are staged: f(member, elements per query, its group)
-template <class Batch, class F>
-inline void for_each_character_array(Batch& b, F&& f) {
-    const size_t k = 2 * (size_t)b.max_slides;
-    f(b.pos, 3, CharacterGroup::In); f(b.motion, 3, CharacterGroup::In); f(b.rot, 4, CharacterGroup::In);
-    f(b.radius, 1, CharacterGroup::In); f(b.half_length, 1, CharacterGroup::In); f(b.grounded_in, 1, CharacterGroup::In);
-    f(b.ignore_body, 1, CharacterGroup::In); f(b.query_mask, 1, CharacterGroup::In);
-    f(b.pos_out, 3, CharacterGroup::Out); f(b.remaining_out, 3, CharacterGroup::Out); f(b.status_out, 1, CharacterGroup::Out);
-    f(b.floor_body_out, 1, CharacterGroup::Out); f(b.floor_normal_out, 3, CharacterGroup::Out); f(b.floor_point_out, 3, CharacterGroup::Out);
-    f(b.hit_body_out, k, CharacterGroup::Slots); f(b.hit_normal_out, 3 * k, CharacterGroup::Slots); f(b.hit_point_out, 3 * k, CharacterGroup::Slots);
-}
-
-// what both entry points check before they touch anything: the text of the refusal, null when the call may go on
-inline const char* character_args_error(const CharacterBatch& b) {
-    const auto length_ok = [](float x) { return x >= 0.0f && x <= 3.4028235e38f; };
-    if (b.n >= (1ull << 31)) return "phys_character_move: n must be below 2^31";
-    if (!length_ok(b.skin)) return "phys_character_move: skin must be finite and not negative";
-    if (b.max_slides < 1u || b.max_slides > kSlideMaxSlides) return "phys_character_move: max_slides must be 1 .. 8";
-    if (!length_ok(b.step_height)) return "phys_character_move: step_height must be finite and not negative";
-    if (!length_ok(b.snap_distance)) return "phys_character_move: snap_distance must be finite and not negative";
-    if (!(b.min_floor_ny > 0.0f && b.min_floor_ny <= 1.0f)) return "phys_character_move: min_floor_ny must lie in (0, 1]";
-    const bool missing = !b.pos || !b.motion || !b.radius || !b.half_length || !b.pos_out || !b.status_out;
-    return b.n && missing ? "phys_character_move: null pos, motion, radius, half_length, pos_out or status_out" : nullptr;
-}
-
-// a call on host arrays declares them: the inputs in one buffer, the per-query outputs in another, the hit slots in a third ...
-inline void stage_character(const CharacterBatch& host, StageLayout& in, StageLayout& out, StageLayout& slots) {
-    for_each_character_array(host, [&](auto* array, size_t per_query, CharacterGroup g) {
-        (g == CharacterGroup::In ? in : g == CharacterGroup::Out ? out : slots).add(array, per_query * host.n);
-    });
-}
-// ... and is the same batch on the device once the three buffers are there
-inline CharacterBatch staged_character(const CharacterBatch& host, uint8_t* in_base, uint8_t* out_base, uint8_t* slots_base) {
-    CharacterBatch dev = host;
-    StageLayout in, out, slots;
-    for_each_character_array(dev, [&](auto*& array, size_t per_query, CharacterGroup g) {
-        StageLayout& l = g == CharacterGroup::In ? in : g == CharacterGroup::Out ? out : slots;
-        array = l.at(g == CharacterGroup::In ? in_base : g == CharacterGroup::Out ? out_base : slots_base, l.add(array, per_query * host.n));
-    });
-    return dev;
-}
-
-// ---- depenetration (phys_penetration and phys_depenetrate, DESIGN.md section 27): the arrays of one call, n capsules; host
-// pointers or device pointers alike. probe: phys_penetration, one probe and no move: gap is the call's max_gap, max_iters 1, and
-// the one slot per query is the answer (hit_body_out = body_out, hit_normal_out = normal_out, hit_depth_out = depth_out;
-// pos_out and status_out null). Otherwise phys_depenetrate: gap is the call's skin, slot k of query i lies at index k * n + i.
-struct DepenBatch {
-    uint64_t n;
-    const float* pos;                  // 3 per query
-    const float* rot;                  // [i, j, k, w] per query; null: identity
-    const float *radius, *half_length; // per query
-    float gap;                         // the call's max_gap or skin: finite, >= 0
-    uint32_t max_iters;                // the call's: 1 .. 8
-    bool probe;
-    const uint32_t* ignore_body;       // null: none
-    const uint16_t* query_mask;        // null: no filtering
-    float* pos_out;                    // 3 per query
-    uint32_t* status_out;
-    uint32_t* hit_body_out;            // max_iters per query
-    float* hit_normal_out;             // 3 * max_iters per query
-    float* hit_depth_out;              // max_iters per query
-};
-
-constexpr uint32_t kDepenMaxIters = 8;
-
-// every array of a call once, in the order they are staged: f(member, elements per query, is it an output)
-template <class Batch, class F>
-inline void for_each_depen_array(Batch& b, F&& f) {
-    const size_t k = b.max_iters;
-    f(b.pos, 3, false); f(b.rot, 4, false); f(b.radius, 1, false); f(b.half_length, 1, false);
-    f(b.ignore_body, 1, false); f(b.query_mask, 1, false);
-    f(b.pos_out, 3, true); f(b.status_out, 1, true);
-    f(b.hit_body_out, k, true); f(b.hit_normal_out, 3 * k, true); f(b.hit_depth_out, k, true);
-}
-
-// what the four entry points check before they touch anything: the text of the refusal, null when the call may go on
-inline const char* depen_args_error(const DepenBatch& b) {
-    const bool gap_ok = b.gap >= 0.0f && b.gap <= 3.4028235e38f;
-    if (b.probe) {
-        if (b.n >= (1ull << 31)) return "phys_penetration: n must be below 2^31";
-        if (!gap_ok) return "phys_penetration: max_gap must be finite and not negative";
-        const bool missing = !b.pos || !b.radius || !b.half_length || !b.hit_body_out || !b.hit_depth_out;
-        return b.n && missing ? "phys_penetration: null pos, radius, half_length, body_out or depth_out" : nullptr;
-    }
-    if (b.n >= (1ull << 31)) return "phys_depenetrate: n must be below 2^31";
-    if (!gap_ok) return "phys_depenetrate: skin must be finite and not negative";
-    if (b.max_iters < 1u || b.max_iters > kDepenMaxIters) return "phys_depenetrate: max_iters must be 1 .. 8";
-    const bool missing = !b.pos || !b.radius || !b.half_length || !b.pos_out || !b.status_out;
-    return b.n && missing ? "phys_depenetrate: null pos, radius, half_length, pos_out or status_out" : nullptr;
-}
-
-// a call on host arrays declares them: the inputs in one buffer, the outputs in another ...
-inline void stage_depen(const DepenBatch& host, StageLayout& in, StageLayout& out) {
-    for_each_depen_array(host, [&](auto* array, size_t per_query, bool output) { (output ? out : in).add(array, per_query * host.n); });
-}
-// ... and is the same batch on the device once the two buffers are there
-inline DepenBatch staged_depen(const DepenBatch& host, uint8_t* in_base, uint8_t* out_base) {
-    DepenBatch dev = host;
-    StageLayout in, out;
-    for_each_depen_array(dev, [&](auto*& array, size_t per_query, bool output) {
-        StageLayout& l = output ? out : in;
-        array = l.at(output ? out_base : in_base, l.add(array, per_query * host.n));
-    });
+// ... and is the same batch on the device once the buffers are there: the same declarations again, over their bases
+template <class Batch>
+inline Batch staged(const Batch& host, uint8_t* const (&bases)[kStageGroups]) {
+    Batch dev = host;
+    StageLayout l[kStageGroups];
+    Batch::arrays(dev, [&](auto*& array, size_t per_query, StageGroup g) { array = l[g].at(bases[g], l[g].add(array, per_query * host.n)); });
     return dev;
 }
 

@@ -257,11 +257,11 @@ struct phys_world {
     phys::DevBuf<uint32_t> rc_start;     // table + 1: exclusive scan of rc_count
     phys::DevBuf<uint32_t> rc_tile_sum;  // the scan's own scratch (scan_block_sums is the update's)
     phys::DevBuf<float> rc_records;      // 8N records of 48 bytes {centre, shape} {rot} {half extent, id}, bucket order
-    // the queries on host arrays (phys_raycast, phys_spherecast, phys_capsulecast, phys_overlap): ONE staging buffer for the
-    // inputs of whichever runs - each synchronises the stream before it returns, so no two are ever in flight - laid out by the
-    // call's own declarations (staging.hpp StageLayout); the casts' outputs body | t | normal | point the same way
-    phys::DevBuf<uint8_t> stage, rc_out;
-    phys::DevBuf<uint8_t> rc_slots;  // phys_character_move: its hit slots, a layout of their own behind the per-query outputs
+    // the queries on host arrays (the casts, move-and-slide, character walking, depenetration, phys_overlap): ONE staging buffer
+    // for the inputs of whichever runs - each synchronises the stream before it returns, so no two are ever in flight - laid out
+    // by the call's own declarations (staging.hpp StageLayout); the outputs the same way, the three buffers being the groups of
+    // staging.hpp: inputs, per-query outputs, phys_character_move's hit slots
+    phys::DevBuf<uint8_t> stage, rc_out, rc_slots;
     phys::DevBuf<unsigned long long> rc_stats;  // PHYS_DEBUG_RAYCAST_STATS: cells, candidates
     // overlap queries (query.hip): they walk the grid above; their own output
     phys::DevBuf<uint32_t> qr_count;     // phys_overlap: targets per query (count pass)

@@ -115,6 +115,32 @@ def _device_mask(mask, n):
     return C.c_void_p(mask.data_ptr())
 
 
+# the input arrays of the capsule query calls (the names of _abi.QUERIES): columns per query
+_QUERY_COLS = {"pos": 3, "motion": 3, "rot": 4, "radius": 1, "half_length": 1, "grounded": 1, "ignore": 1}
+
+
+def _query_scalars(call, given):
+    """The per-call scalars of a capsule query call (_abi.QUERIES[call] names and orders them), checked before the library is
+    called: the count of rounds first, then the lengths. Returns them in the order of the call, and the count of rounds (None
+    for a call without one)."""
+    scalars = _abi.QUERIES[call][1]
+    v, rounds = {}, None
+    for k, t in scalars:
+        if t is C.c_uint32:
+            v[k] = rounds = int(given[k])
+            if not 1 <= rounds <= _abi.SLIDE_MAX_SLIDES:  # (= DEPEN_MAX_ITERS)
+                raise ValueError(f"{k}: must lie in [1, {_abi.SLIDE_MAX_SLIDES}]")
+    for k, t in scalars:
+        if t is C.c_float:
+            v[k] = float(given[k])
+            if k == "min_floor_ny":
+                if not 0.0 < v[k] <= 1.0:
+                    raise ValueError("min_floor_ny: must lie in (0, 1]")
+            elif not (np.isfinite(v[k]) and v[k] >= 0.0):
+                raise ValueError(f"{k}: must be finite and not negative")
+    return [v[k] for k, _ in scalars], rounds
+
+
 class World:
     def __init__(self, cfg=None):
         self.lib = _abi.load_library()
@@ -518,6 +544,51 @@ class World:
                           (("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3), ("point_out", point_out, 3)),
                           mask)
 
+    def _query(self, call, noun, given, mask, scalars, shapes):
+        """The capsule query calls on host arrays (move_and_slide, character_move, penetration, depenetrate). given: name ->
+        array (pos, motion), scalar or (n,) values (radius, half_length), array or None (rot, ignore, grounded); scalars: name
+        -> per-call value; the names are those of _abi.QUERIES[call], which orders the arguments. shapes(n, rounds): the shape
+        of every output. Returns the call's outputs."""
+        ins, _, outs = _abi.QUERIES[call]
+        if "motion" not in ins:  # the order of the checks is each call's own: these look at their scalars first
+            values, rounds = _query_scalars(call, scalars)
+        a = {"pos": _f(given["pos"]).reshape(-1, 3)}
+        n = a["pos"].shape[0]
+        if "motion" in ins:
+            a["motion"] = _f(given["motion"]).reshape(-1, 3)
+            if a["motion"].shape[0] != n:
+                raise ValueError("pos and motion differ in length")
+            values, rounds = _query_scalars(call, scalars)
+        for k in ("radius", "half_length"):
+            a[k] = np.ascontiguousarray(np.broadcast_to(np.asarray(given[k], np.float32), (n,)))
+        optional = [k for k in ("rot", "ignore", "grounded") if k in given]
+        for k in optional:
+            v = given[k]
+            if v is not None and k == "grounded":
+                v = np.asarray(v) != 0
+            a[k] = None if v is None else np.ascontiguousarray(v, dtype=np.float32 if k == "rot" else np.uint32).reshape(-1, _QUERY_COLS[k])
+            if a[k] is not None and a[k].size != n * _QUERY_COLS[k]:
+                raise ValueError(f"{' / '.join(optional)} do not match the {noun} count")
+        a["query_mask"] = _query_mask(mask, n)
+        for k, shape in zip(outs, shapes(n, rounds)):
+            a[k] = np.empty(shape, np.uint32 if _abi.QUERY_TYPES.get(k) is u32p else np.float32)
+        if n:
+            ptr = {k: _p(v, _abi.QUERY_TYPES.get(k, f32p)) for k, v in a.items()}
+            self._ck(getattr(self.lib, f"phys_{call}")(self.h, n, *(ptr[k] for k in ins), *values, ptr["ignore"], ptr["query_mask"],
+                                                       *(ptr[k] for k in outs)))
+        return tuple(a[k] for k in outs)
+
+    def _query_device(self, call, given, mask, scalars, outputs):
+        """The capsule query calls on device tensors. given: name -> tensor or None (the inputs of _abi.QUERIES[call] and
+        ignore); outputs(rounds): (tensor or None, columns per query) per output, in the order of the call."""
+        ins, _, outs = _abi.QUERIES[call]
+        n = int(given["pos"].shape[0])
+        values, rounds = _query_scalars(call, scalars)
+        args = _device_args(n, [(k, given[k], _QUERY_COLS[k]) for k in ins + ("ignore",)])
+        out = _device_args(n, [(k, x, cols) for k, (x, cols) in zip(outs, outputs(rounds))])
+        self._ck(getattr(self.lib, f"phys_{call}_device")(self.h, n, *args[:-1], *values, args[-1],
+                                                          None if mask is None else _device_mask(mask, n), *out))
+
     def move_and_slide(self, pos, motion, radius, half_length, rot=None, skin=0.01, max_slides=4, ignore=None, mask=None):
         """Capsule characters move, stop `skin` short of what they meet and slide along it (phys_move_and_slide; the rule:
         include/spec/slide.h): pos / motion (n, 3), radius and half_length scalar or (n,), rot (n, 4) [i, j, k, w] or None
@@ -525,30 +596,9 @@ class World:
         character, all in one launch. Returns (pos f32[n, 3], remaining f32[n, 3], status u32[n], hit_body u32[max_slides, n],
         hit_normal f32[max_slides, n, 3], hit_point f32[max_slides, n, 3]): status holds the hit count in bits 0-3 and the
         SLIDE_BLOCKED / SLIDE_EXHAUSTED / SLIDE_INVALID flags; an unused hit slot holds RAY_MISS and zeros."""
-        p, m = _f(pos).reshape(-1, 3), _f(motion).reshape(-1, 3)
-        n = p.shape[0]
-        if m.shape[0] != n:
-            raise ValueError("pos and motion differ in length")
-        k = int(max_slides)
-        if not 1 <= k <= _abi.SLIDE_MAX_SLIDES:
-            raise ValueError(f"max_slides: must lie in [1, {_abi.SLIDE_MAX_SLIDES}]")
-        skin = float(skin)
-        if not (np.isfinite(skin) and skin >= 0.0):
-            raise ValueError("skin: must be finite and not negative")
-        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)))
-        hq = np.ascontiguousarray(np.broadcast_to(np.asarray(half_length, np.float32), (n,)))
-        r = None if rot is None else _f(rot).reshape(-1, 4)
-        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.uint32).reshape(-1)
-        for a, cols in ((r, 4), (ig, 1)):
-            if a is not None and a.size != n * cols:
-                raise ValueError("rot / ignore do not match the character count")
-        qm = _query_mask(mask, n)
-        pos_out, rem, status = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32), np.empty(n, np.uint32)
-        body, nrm, pnt = np.empty((k, n), np.uint32), np.empty((k, n, 3), np.float32), np.empty((k, n, 3), np.float32)
-        if n:
-            self._ck(self.lib.phys_move_and_slide(self.h, n, _p(p), _p(m), _p(r), _p(rad), _p(hq), skin, k, _p(ig, u32p), _p(qm, u16p),
-                                                  _p(pos_out), _p(rem), _p(status, u32p), _p(body, u32p), _p(nrm), _p(pnt)))
-        return pos_out, rem, status, body, nrm, pnt
+        return self._query("move_and_slide", "character",
+                           dict(pos=pos, motion=motion, radius=radius, half_length=half_length, rot=rot, ignore=ignore), mask,
+                           dict(skin=skin, max_slides=max_slides), lambda n, k: ((n, 3), (n, 3), (n,), (k, n), (k, n, 3), (k, n, 3)))
 
     def move_and_slide_device(self, pos, motion, radius, half_length, pos_out, status_out, remaining_out=None, hit_body_out=None,
                               hit_normal_out=None, hit_point_out=None, rot=None, skin=0.01, max_slides=4, ignore=None, mask=None):
@@ -557,36 +607,10 @@ class World:
         remaining_out float32 (n, 3) or None, hit_body_out int32 / uint32 (max_slides, n) or None, hit_normal_out and
         hit_point_out float32 (max_slides, n, 3) or None, rot float32 (n, 4) or None, ignore int32 / uint32 (n,) or None, mask
         int16 / uint16 (n,) or None. Only enqueues on the world's stream (device_view().stream)."""
-        n = int(pos.shape[0])
-        k = int(max_slides)
-        if not 1 <= k <= _abi.SLIDE_MAX_SLIDES:
-            raise ValueError(f"max_slides: must lie in [1, {_abi.SLIDE_MAX_SLIDES}]")
-        skin = float(skin)
-        if not (np.isfinite(skin) and skin >= 0.0):
-            raise ValueError("skin: must be finite and not negative")
-        ins = _device_args(n, (("pos", pos, 3), ("motion", motion, 3), ("rot", rot, 4), ("radius", radius, 1), ("half_length", half_length, 1)))
-        ig, = _device_args(n, (("ignore", ignore, 1),))
-        outs = _device_args(n, (("pos_out", pos_out, 3), ("remaining_out", remaining_out, 3), ("status_out", status_out, 1),
-                                ("hit_body_out", hit_body_out, k), ("hit_normal_out", hit_normal_out, 3 * k),
-                                ("hit_point_out", hit_point_out, 3 * k)))
-        self._ck(self.lib.phys_move_and_slide_device(self.h, n, *ins, skin, k, ig, None if mask is None else _device_mask(mask, n), *outs))
-
-    @staticmethod
-    def _character_params(skin, max_slides, step_height, snap_distance, min_floor_ny):
-        """The per-call values of character_move, checked before the library is called."""
-        k = int(max_slides)
-        if not 1 <= k <= _abi.SLIDE_MAX_SLIDES:
-            raise ValueError(f"max_slides: must lie in [1, {_abi.SLIDE_MAX_SLIDES}]")
-        lengths = []
-        for name, v in (("skin", skin), ("step_height", step_height), ("snap_distance", snap_distance)):
-            v = float(v)
-            if not (np.isfinite(v) and v >= 0.0):
-                raise ValueError(f"{name}: must be finite and not negative")
-            lengths.append(v)
-        ny = float(min_floor_ny)
-        if not 0.0 < ny <= 1.0:
-            raise ValueError("min_floor_ny: must lie in (0, 1]")
-        return k, lengths[0], lengths[1], lengths[2], ny
+        self._query_device("move_and_slide", dict(pos=pos, motion=motion, rot=rot, radius=radius, half_length=half_length, ignore=ignore), mask,
+                           dict(skin=skin, max_slides=max_slides),
+                           lambda k: ((pos_out, 3), (remaining_out, 3), (status_out, 1), (hit_body_out, k), (hit_normal_out, 3 * k),
+                                      (hit_point_out, 3 * k)))
 
     def character_move(self, pos, motion, radius, half_length, rot=None, grounded=None, skin=0.01, max_slides=4, step_height=0.3,
                        snap_distance=0.2, min_floor_ny=0.7071068, ignore=None, mask=None):
@@ -599,28 +623,10 @@ class World:
         hit_body u32[2 max_slides, n], hit_normal f32[2 max_slides, n, 3], hit_point f32[2 max_slides, n, 3]): status holds
         MOVE's hit count in bits 0-3, the lifted slide's in bits 4-7 and the CHAR_* flags; pass status & CHAR_GROUNDED as the
         next frame's grounded."""
-        p, m = _f(pos).reshape(-1, 3), _f(motion).reshape(-1, 3)
-        n = p.shape[0]
-        if m.shape[0] != n:
-            raise ValueError("pos and motion differ in length")
-        k, skin, step_height, snap_distance, min_floor_ny = self._character_params(skin, max_slides, step_height, snap_distance, min_floor_ny)
-        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)))
-        hq = np.ascontiguousarray(np.broadcast_to(np.asarray(half_length, np.float32), (n,)))
-        r = None if rot is None else _f(rot).reshape(-1, 4)
-        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.uint32).reshape(-1)
-        gr = None if grounded is None else np.ascontiguousarray(np.asarray(grounded) != 0, dtype=np.uint32).reshape(-1)
-        for a, cols in ((r, 4), (ig, 1), (gr, 1)):
-            if a is not None and a.size != n * cols:
-                raise ValueError("rot / ignore / grounded do not match the character count")
-        qm = _query_mask(mask, n)
-        pos_out, rem, status = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32), np.empty(n, np.uint32)
-        fbody, fnrm, fpnt = np.empty(n, np.uint32), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
-        body, nrm, pnt = np.empty((2 * k, n), np.uint32), np.empty((2 * k, n, 3), np.float32), np.empty((2 * k, n, 3), np.float32)
-        if n:
-            self._ck(self.lib.phys_character_move(self.h, n, _p(p), _p(m), _p(r), _p(rad), _p(hq), _p(gr, u32p), skin, k, step_height,
-                                                  snap_distance, min_floor_ny, _p(ig, u32p), _p(qm, u16p), _p(pos_out), _p(rem),
-                                                  _p(status, u32p), _p(fbody, u32p), _p(fnrm), _p(fpnt), _p(body, u32p), _p(nrm), _p(pnt)))
-        return pos_out, rem, status, fbody, fnrm, fpnt, body, nrm, pnt
+        return self._query("character_move", "character",
+                           dict(pos=pos, motion=motion, radius=radius, half_length=half_length, rot=rot, ignore=ignore, grounded=grounded), mask,
+                           dict(skin=skin, max_slides=max_slides, step_height=step_height, snap_distance=snap_distance, min_floor_ny=min_floor_ny),
+                           lambda n, k: ((n, 3), (n, 3), (n,), (n,), (n, 3), (n, 3), (2 * k, n), (2 * k, n, 3), (2 * k, n, 3)))
 
     def character_move_device(self, pos, motion, radius, half_length, pos_out, status_out, remaining_out=None, floor_body_out=None,
                               floor_normal_out=None, floor_point_out=None, hit_body_out=None, hit_normal_out=None, hit_point_out=None,
@@ -630,30 +636,11 @@ class World:
         int32 / uint32 (n,) or None, floor_body_out int32 / uint32 (n,) or None, floor_normal_out and floor_point_out float32
         (n, 3) or None, hit_body_out int32 / uint32 (2 max_slides, n) or None, hit_normal_out and hit_point_out float32
         (2 max_slides, n, 3) or None. Only enqueues on the world's stream (device_view().stream)."""
-        n = int(pos.shape[0])
-        k, skin, step_height, snap_distance, min_floor_ny = self._character_params(skin, max_slides, step_height, snap_distance, min_floor_ny)
-        ins = _device_args(n, (("pos", pos, 3), ("motion", motion, 3), ("rot", rot, 4), ("radius", radius, 1), ("half_length", half_length, 1),
-                               ("grounded", grounded, 1)))
-        ig, = _device_args(n, (("ignore", ignore, 1),))
-        outs = _device_args(n, (("pos_out", pos_out, 3), ("remaining_out", remaining_out, 3), ("status_out", status_out, 1),
-                                ("floor_body_out", floor_body_out, 1), ("floor_normal_out", floor_normal_out, 3),
-                                ("floor_point_out", floor_point_out, 3), ("hit_body_out", hit_body_out, 2 * k),
-                                ("hit_normal_out", hit_normal_out, 6 * k), ("hit_point_out", hit_point_out, 6 * k)))
-        self._ck(self.lib.phys_character_move_device(self.h, n, *ins, skin, k, step_height, snap_distance, min_floor_ny, ig,
-                                                     None if mask is None else _device_mask(mask, n), *outs))
-
-    def _depen_args(self, pos, radius, half_length, rot, ignore, mask):
-        """The arrays penetration and depenetrate share, checked before the library is called."""
-        p = _f(pos).reshape(-1, 3)
-        n = p.shape[0]
-        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, np.float32), (n,)))
-        hq = np.ascontiguousarray(np.broadcast_to(np.asarray(half_length, np.float32), (n,)))
-        r = None if rot is None else _f(rot).reshape(-1, 4)
-        ig = None if ignore is None else np.ascontiguousarray(ignore, dtype=np.uint32).reshape(-1)
-        for a, cols in ((r, 4), (ig, 1)):
-            if a is not None and a.size != n * cols:
-                raise ValueError("rot / ignore do not match the capsule count")
-        return n, p, r, rad, hq, ig, _query_mask(mask, n)
+        self._query_device("character_move",
+                           dict(pos=pos, motion=motion, rot=rot, radius=radius, half_length=half_length, grounded=grounded, ignore=ignore), mask,
+                           dict(skin=skin, max_slides=max_slides, step_height=step_height, snap_distance=snap_distance, min_floor_ny=min_floor_ny),
+                           lambda k: ((pos_out, 3), (remaining_out, 3), (status_out, 1), (floor_body_out, 1), (floor_normal_out, 3),
+                                      (floor_point_out, 3), (hit_body_out, 2 * k), (hit_normal_out, 6 * k), (hit_point_out, 6 * k)))
 
     def penetration(self, pos, radius, half_length, rot=None, max_gap=0.0, ignore=None, mask=None):
         """The deepest target within max_gap of each capsule where it stands (phys_penetration; the rule:
@@ -661,15 +648,8 @@ class World:
         (upright), ignore (n,) body ids or None, mask scalar or (n,) u16 or None (no filtering). Returns (body u32[n], depth
         f32[n], normal f32[n, 3]): depth > 0 is how far the capsule reaches into the target, depth < 0 the clearance, normal
         points out of the target towards the capsule; a miss is (RAY_MISS, -inf, 0). Nothing moves."""
-        max_gap = float(max_gap)
-        if not (np.isfinite(max_gap) and max_gap >= 0.0):
-            raise ValueError("max_gap: must be finite and not negative")
-        n, p, r, rad, hq, ig, qm = self._depen_args(pos, radius, half_length, rot, ignore, mask)
-        body, depth, nrm = np.empty(n, np.uint32), np.empty(n, np.float32), np.empty((n, 3), np.float32)
-        if n:
-            self._ck(self.lib.phys_penetration(self.h, n, _p(p), _p(r), _p(rad), _p(hq), max_gap, _p(ig, u32p), _p(qm, u16p),
-                                               _p(body, u32p), _p(depth), _p(nrm)))
-        return body, depth, nrm
+        return self._query("penetration", "capsule", dict(pos=pos, radius=radius, half_length=half_length, rot=rot, ignore=ignore), mask,
+                           dict(max_gap=max_gap), lambda n, k: ((n,), (n,), (n, 3)))
 
     def penetration_device(self, pos, radius, half_length, body_out, depth_out, normal_out=None, rot=None, max_gap=0.0, ignore=None,
                            mask=None):
@@ -677,14 +657,8 @@ class World:
         (n, 3), radius and half_length float32 (n,), body_out int32 / uint32 (n,), depth_out float32 (n,), normal_out float32
         (n, 3) or None, rot float32 (n, 4) or None, ignore int32 / uint32 (n,) or None, mask int16 / uint16 (n,) or None. Only
         enqueues on the world's stream (device_view().stream)."""
-        n = int(pos.shape[0])
-        max_gap = float(max_gap)
-        if not (np.isfinite(max_gap) and max_gap >= 0.0):
-            raise ValueError("max_gap: must be finite and not negative")
-        ins = _device_args(n, (("pos", pos, 3), ("rot", rot, 4), ("radius", radius, 1), ("half_length", half_length, 1)))
-        ig, = _device_args(n, (("ignore", ignore, 1),))
-        outs = _device_args(n, (("body_out", body_out, 1), ("depth_out", depth_out, 1), ("normal_out", normal_out, 3)))
-        self._ck(self.lib.phys_penetration_device(self.h, n, *ins, max_gap, ig, None if mask is None else _device_mask(mask, n), *outs))
+        self._query_device("penetration", dict(pos=pos, rot=rot, radius=radius, half_length=half_length, ignore=ignore), mask,
+                           dict(max_gap=max_gap), lambda k: ((body_out, 1), (depth_out, 1), (normal_out, 3)))
 
     def depenetrate(self, pos, radius, half_length, rot=None, skin=0.01, max_iters=4, ignore=None, mask=None):
         """Capsules that overlap something are pushed out of it, the deepest target first, until they are skin / 2 clear of
@@ -693,19 +667,8 @@ class World:
         u32[max_iters, n], hit_normal f32[max_iters, n, 3], hit_depth f32[max_iters, n]): status holds the push count in bits
         0-3 and the DEPEN_STUCK / DEPEN_INVALID flags; slot k is what penetration reported where push k began, an unused slot
         holds RAY_MISS and zeros."""
-        k = int(max_iters)
-        if not 1 <= k <= _abi.DEPEN_MAX_ITERS:
-            raise ValueError(f"max_iters: must lie in [1, {_abi.DEPEN_MAX_ITERS}]")
-        skin = float(skin)
-        if not (np.isfinite(skin) and skin >= 0.0):
-            raise ValueError("skin: must be finite and not negative")
-        n, p, r, rad, hq, ig, qm = self._depen_args(pos, radius, half_length, rot, ignore, mask)
-        pos_out, status = np.empty((n, 3), np.float32), np.empty(n, np.uint32)
-        body, nrm, depth = np.empty((k, n), np.uint32), np.empty((k, n, 3), np.float32), np.empty((k, n), np.float32)
-        if n:
-            self._ck(self.lib.phys_depenetrate(self.h, n, _p(p), _p(r), _p(rad), _p(hq), skin, k, _p(ig, u32p), _p(qm, u16p),
-                                               _p(pos_out), _p(status, u32p), _p(body, u32p), _p(nrm), _p(depth)))
-        return pos_out, status, body, nrm, depth
+        return self._query("depenetrate", "capsule", dict(pos=pos, radius=radius, half_length=half_length, rot=rot, ignore=ignore), mask,
+                           dict(skin=skin, max_iters=max_iters), lambda n, k: ((n, 3), (n,), (k, n), (k, n, 3), (k, n)))
 
     def depenetrate_device(self, pos, radius, half_length, pos_out, status_out, hit_body_out=None, hit_normal_out=None,
                            hit_depth_out=None, rot=None, skin=0.01, max_iters=4, ignore=None, mask=None):
@@ -713,18 +676,9 @@ class World:
         (n, 3), status_out int32 / uint32 (n,), hit_body_out int32 / uint32 (max_iters, n) or None, hit_normal_out float32
         (max_iters, n, 3) or None, hit_depth_out float32 (max_iters, n) or None. Only enqueues on the world's stream
         (device_view().stream): pos_out may feed move_and_slide_device without a host wait."""
-        n = int(pos.shape[0])
-        k = int(max_iters)
-        if not 1 <= k <= _abi.DEPEN_MAX_ITERS:
-            raise ValueError(f"max_iters: must lie in [1, {_abi.DEPEN_MAX_ITERS}]")
-        skin = float(skin)
-        if not (np.isfinite(skin) and skin >= 0.0):
-            raise ValueError("skin: must be finite and not negative")
-        ins = _device_args(n, (("pos", pos, 3), ("rot", rot, 4), ("radius", radius, 1), ("half_length", half_length, 1)))
-        ig, = _device_args(n, (("ignore", ignore, 1),))
-        outs = _device_args(n, (("pos_out", pos_out, 3), ("status_out", status_out, 1), ("hit_body_out", hit_body_out, k),
-                                ("hit_normal_out", hit_normal_out, 3 * k), ("hit_depth_out", hit_depth_out, k)))
-        self._ck(self.lib.phys_depenetrate_device(self.h, n, *ins, skin, k, ig, None if mask is None else _device_mask(mask, n), *outs))
+        self._query_device("depenetrate", dict(pos=pos, rot=rot, radius=radius, half_length=half_length, ignore=ignore), mask,
+                           dict(skin=skin, max_iters=max_iters),
+                           lambda k: ((pos_out, 3), (status_out, 1), (hit_body_out, k), (hit_normal_out, 3 * k), (hit_depth_out, k)))
 
     def overlap(self, shape_type, pos, rot=None, half_extent=None, ignore=None, cap=None, mask=None):
         """Every target each query shape intersects (phys_overlap): shape_type scalar or (n,) SHAPE_SPHERE / BOX / CAPSULE,
