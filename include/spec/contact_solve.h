@@ -422,4 +422,68 @@ PHYS_HD void solve_manifold_geo(geo_manifold_t* gm, int make_masses, int apply_o
     }
 }
 
+#ifdef __cplusplus
+/* ... and the same sweep FLAT: solve_manifold_geo's arithmetic with the kind of sweep (make_masses, apply_only) fixed at
+ * compile time and the B side computed for every manifold, without a branch. One instantiation is a straight line per
+ * direction: no test of the sweep's flags, no region around body B (the cluster solver spends its time issuing exactly these
+ * instructions: DESIGN.md section 4).
+ *
+ * THE CONTRACT DIFFERS from solve_manifold_geo's. With gm->has_b == 0 the caller passes ZEROS for xB, invMB, *IB, *vB and
+ * *wB, and *vB and *wB are UNSPECIFIED on return (solve_manifold_geo ignores the five and leaves the velocities alone).
+ * Everything else - *vA, *wA, the impulses, the masses, and *vB, *wB when has_b != 0 - has solve_manifold_geo's bits for
+ * finite operands:
+ * the B side of a manifold without a body B is dead, except in two places where the A side reads it, and there the selects
+ * stay: the relative velocity (from zeros ub can be -0 where the spec says +0, which would turn the sign of a zero vrel)
+ * and the row mass (the spec adds nothing for the ground, not invMB + 0). */
+template <bool MAKE_MASSES, bool APPLY_ONLY>
+PHYS_HD void solve_manifold_flat(geo_manifold_t* gm, float friction, v3 xA, float invMA, const m33* IA, v3 xB, float invMB,
+                                 const m33* IB, v3* vA, v3* wA, v3* vB, v3* wB) {
+    const int has_b = gm->has_b;
+    v3 lA[3], lB[3];
+    PHYS_UNROLL
+    for (int t = 0; t < 3; ++t) {                                /* linear_responses */
+        const v3 dir = t == 0 ? gm->t1 : (t == 1 ? gm->t2 : gm->n);
+        lA[t] = v3_scale(dir, invMA);
+        lB[t] = v3_scale(dir, invMB);
+    }
+    PHYS_UNROLL
+    for (int k = 0; k < 4; ++k) {
+        if (k < gm->count) {
+            const v3 rA = v3_sub(gm->pt[k], xA);
+            const v3 rB = v3_sub(gm->pt[k], xB);
+            PHYS_UNROLL
+            for (int t = 0; t < 3; ++t) {
+                const v3 dir = t == 0 ? gm->t1 : (t == 1 ? gm->t2 : gm->n);
+                jac_row_t j;                                     /* jac_row_make, both sides */
+                j.aA = v3_cross_f(rA, dir);
+                j.mA = inertia_mul(IA, j.aA);
+                j.aB = v3_cross_f(rB, dir);
+                j.mB = inertia_mul(IB, j.aB);
+                if (MAKE_MASSES) {
+                    const float ka = invMA + v3_dot_f(j.mA, j.aA);
+                    const float kb = (ka + invMB) + v3_dot_f(j.mB, j.aB);
+                    const float km = has_b ? kb : ka;
+                    gm->mass[k][t] = km > 0.0f ? 1.0f / km : 0.0f;
+                }
+                float lambda;
+                if (APPLY_ONLY) {
+                    lambda = t == 0 ? gm->pt0[k] : (t == 1 ? gm->pt1[k] : gm->pn[k]);
+                } else {
+                    const float mass = gm->mass[k][t];
+                    const float ua = v3_dot_f(dir, *vA) + v3_dot_f(j.aA, *wA); /* row_velocity */
+                    const float ub = v3_dot_f(dir, *vB) + v3_dot_f(j.aB, *wB);
+                    const float vrel = (has_b ? ub : 0.0f) - ua;
+                    lambda = t < 2 ? friction_impulse(mass, vrel, friction * gm->pn[k], t == 0 ? &gm->pt0[k] : &gm->pt1[k])
+                                   : normal_impulse(mass, vrel, gm->bias[k], &gm->pn[k]);
+                }
+                *vA = v3_madd(*vA, lA[t], -lambda);              /* row_apply, both sides */
+                *wA = v3_madd(*wA, j.mA, -lambda);
+                *vB = v3_madd(*vB, lB[t], lambda);
+                *wB = v3_madd(*wB, j.mB, lambda);
+            }
+        }
+    }
+}
+#endif
+
 #endif /* PHYS_SPEC_CONTACT_SOLVE_H */

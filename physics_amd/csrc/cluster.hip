@@ -14,7 +14,7 @@
 // colour) - a row belongs to the home of its body A, else of its body B; per iteration the workgroup walks its colours in
 // ascending order with a workgroup barrier between them - the spec's order of updates per body, as before - and streams
 // its rows from memory exactly once per iteration, COMPACT (contact points + bias, accumulated impulses, row masses made
-// in iteration 0; lever arms remade from the positions in LDS: solve_manifold_geo) and fetched one or two colour steps
+// in iteration 0; lever arms remade from the positions in LDS: solve_manifold_flat) and fetched one or two colour steps
 // ahead. A body all of whose rows lie in one cluster never leaves LDS.
 // A body touched by a row of ANOTHER cluster is `shared`: its updates travel between workgroups through the tagged
 // granules of k_solve_flow (the hand-off: handoff.hpp). A shared body of the own cluster
@@ -277,7 +277,8 @@ void launch_cluster_sort(phys_world* w, const ColorPlan& plan, StepCounters* sna
 // count into the ticket word - no plane more, no load more -
 // and everything else solver_prep would have stored (the lever arms) is remade from the contact point and the two body
 // POSITIONS, which live in LDS beside the velocities (solve_manifold_geo: same operations, same bits;
-// tests/test_collide_kat.py holds the three drivers against each other). So k_rows_build reads nothing of the bodies
+// tests/test_collide_kat.py holds the three drivers against each other - and solve_manifold_flat, which this kernel calls,
+// is that driver with the kind of sweep fixed at compile time: tests/test_solve_flat_cpu.py). So k_rows_build reads nothing of the bodies
 // on a cluster step, and a 4-point row is 240 bytes per iteration instead of 320.
 struct ClusterRowArrays { float4* all; uint64_t cap; };  // (the planes: records.hpp)
 
@@ -522,7 +523,14 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                                                 ctr->debug);
                 }
                 if (!dead) {
-                    solve_manifold_geo(&gm, it == 0u, (warm_sweep != 0u && it == 0u) ? 1 : 0, MAT ? hraw.z : friction, xA, ima, &IA, xB, imb, &IB, &vA, &wA, &vB, &wB);
+                    // one straight-line row body per KIND of sweep, chosen by what is the same for the whole wave and the
+                    // whole sweep: regular (8 of 9), first of a cold solve (makes the masses), first of a warm one (makes the
+                    // masses, applies the starting impulses). solve_manifold_flat wants zeros for a body B that is not
+                    // there: xB, imb, IB, vB, wB above are, and kSideNone stores none of them
+                    const float fr = MAT ? hraw.z : friction;
+                    if (it != 0u) solve_manifold_flat<false, false>(&gm, fr, xA, ima, &IA, xB, imb, &IB, &vA, &wA, &vB, &wB);
+                    else if (warm_sweep == 0u) solve_manifold_flat<true, false>(&gm, fr, xA, ima, &IA, xB, imb, &IB, &vA, &wA, &vB, &wB);
+                    else solve_manifold_flat<true, true>(&gm, fr, xA, ima, &IA, xB, imb, &IB, &vA, &wA, &vB, &wB);
                     // ---- write back
                     if (cluster_side_at_home(modeA)) {
                         s_body[4 * slotA] = make_float4(vA.x, vA.y, vA.z, __uint_as_float(hv.tag(tA + 1u)));
