@@ -282,6 +282,19 @@ void launch_cluster_sort(phys_world* w, const ColorPlan& plan, StepCounters* sna
 // on a cluster step, and a 4-point row is 240 bytes per iteration instead of 320.
 struct ClusterRowArrays { float4* all; uint64_t cap; };  // (the planes: records.hpp)
 
+// s_waitcnt vmcnt(0) as the BUILTIN, which the compiler's own wait insertion sees (an inline-asm wait it does not). That pass
+// tracks pending loads per register and merges its state where control flow joins, and both sides of a divergent branch run
+// one after the other under complementary masks. Two consequences in k_solve_cluster's row loop:
+// - the loads of the rare paths (a homeless body A's constants, a first update's ld_vel) land in the registers that the
+//   common path fills from LDS, so the LDS reads of the two bodies waited for every load in flight - the whole row. The
+//   rare branch now waits for its own loads before it ends, and the common path waits for none.
+// - a row fetched ahead is not consumed on the path that skips the solve (`dead`), so at the loop's tail the pass saw loads
+//   possibly pending into the registers the next fetch() fills and put an unconditional vmcnt(0) between the row's stores
+//   and that fetch: loads and stores share one in-order counter, so every row iteration waited for the acknowledgement
+//   of its own stores, the write-through publishes included, before it asked for its next row. One wait ahead of the solve,
+//   where every plane of the row is needed anyway, proves them landed on all paths; the tail keeps only its hand-written d == d_row wait.
+__device__ __forceinline__ void cluster_loads_landed() { __builtin_amdgcn_s_waitcnt(0x0F70); }  // vmcnt(0); expcnt, lgkmcnt: no wait
+
 constexpr int kClusterThreads = 256;
 template <bool DIAG, bool GUARDED, bool MAT>
 __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kClusterPerCuFull) void k_solve_cluster(StepCounters* ctr, uint32_t iterations, uint32_t epoch,
@@ -482,6 +495,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                     }
                     if (tA == 0u) { const BodyVel A0 = ld_vel(vel, h.x); vA = A0.v; wA = A0.w; }
                     needA = tA != 0u;
+                    cluster_loads_landed();  // (the rare path pays for its loads itself: see there)
                 }
                 if (cluster_side_at_home(modeB)) {
                     const float4* sb = s_body + 4 * slotB;
@@ -496,6 +510,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                     if (tB == 0u) {  // first update of that body in this solve (iteration 0 only): its state is still in `vel`
                         const BodyVel B0 = ld_vel(vel, h.y);
                         vB = B0.v; wB = B0.w;
+                        cluster_loads_landed();
                     }
                     needB = tB != 0u;
                 }
@@ -522,6 +537,7 @@ __global__ __launch_bounds__(kClusterThreads, DIAG ? kClusterPerCuDiag : kCluste
                     cluster_timeout_note_encode(ClusterTimeoutNote{cluster, gridDim.x, d_row, h.x, h.y, tA, tB, late & 1u, late >> 1, modeA, modeB, col, it},
                                                 ctr->debug);
                 }
+                cluster_loads_landed();  // the row is needed from here on; shared by the `dead` path, which consumes none of it
                 if (!dead) {
                     // one straight-line row body per KIND of sweep, chosen by what is the same for the whole wave and the
                     // whole sweep: regular (8 of 9), first of a cold solve (makes the masses), first of a warm one (makes the
