@@ -812,6 +812,69 @@ int32_t phys_set_force_field_params(phys_world* w, uint64_t n /* == field count 
                                     const float* coef /*2n*/);
 int32_t phys_apply_force_fields(phys_world* w);
 
+/* --- liquids: buoyancy and drag from each body's submerged part (new: the reference has one global gravity) ---
+ * A world keeps up to PHYS_MAX_LIQUIDS liquids. A force field looks at a body's centre; a liquid looks at its SHAPE against the
+ * liquid's surface, reads its rotation and produces a torque: a crate floats at a water line and rights itself.
+ * The volume. A liquid is an oriented box: pos, the unit quaternion rot_ijkw, half_extent h. Its SURFACE is the plane through
+ *   the box's local +y face: unit normal n = column 1 of the rotation matrix, through pos + h.y * n. The liquid is the
+ *   half-space below that plane. It is NOT clipped by the box's sides or bottom: the box only decides who is in the pool.
+ * The law. Each liquid has density >= 0, gravity[3] (the acceleration the liquid is weighed by, e.g. (0, -9.81, 0);
+ *   independent of n), flow[3] (the liquid's velocity), drag[2] >= 0 (linear, angular) and an optional mask.
+ *   The world's own gravity stays the reference's FORCE, the same on every body whatever its mass or size. Whether a body
+ *   floats is therefore the caller's arithmetic: it floats iff density * V_shape * |gravity| exceeds that force.
+ * Who. Liquid k acts on OWNED body i iff the body has a shape (SPHERE, BOX or CAPSULE; PHYS_SHAPE_NONE bodies have no volume
+ *   and are not touched), its position and rotation are finite, (category[i] & mask[k]) != 0 (a NULL mask array means every
+ *   body and loads no filter), its centre is over the footprint and not under the bottom - with l = R^T (x - pos):
+ *   |l.x| <= h.x, |l.z| <= h.z, l.y >= -h.y - and its submerged volume V_sub is above 0.
+ * V_sub and M, the volume and the first moment about the body's centre of the part of the shape below the plane:
+ *   sphere   exact (the cap's closed form);
+ *   box      exact (six tetrahedra around a space diagonal, each clipped by the plane);
+ *   capsule  a stated quadrature: 8 equal slabs of the cylinder and 4 per end cap across the axis, each cap slab a short
+ *            cylinder of the radius that preserves its volume, each slab cut exactly by the plane. Within 0.5 % of the
+ *            capsule's volume of the truth (0.46 % measured); a fully submerged capsule gives its volume exactly. Each slab's buoyancy acts at
+ *            its axial midpoint ON the axis: the offset of a cut disc's centroid inside the disc is left out.
+ *   Nothing divides by V_sub: the torque stays continuous as V_sub -> 0.
+ * What it adds. With frac = min(V_sub / V_shape, 1), liquid k adds to body i
+ *   F += -density * V_sub * gravity          T += -density * (M x gravity)
+ *   F += -drag[0] * frac * (v - flow)        T += -drag[1] * frac * w
+ *   with v, w the body's velocities as the previous update left them (loaded only when the set holds a nonzero drag).
+ * Order. A body's sums start from its accumulators and take the contributions in ascending liquid index, each formed
+ *   completely before it is added; all arithmetic is float32 in the operation order of include/spec/liquid.h (which a host
+ *   compiler reads alone), no contraction: the same bits across runs, batch sizes and launch shapes. Accumulators of bodies
+ *   no liquid acts on are not touched.
+ * When. At the start of EVERY phys_update, and of each update of a phys_update_n batch, AFTER the force fields and before the
+ *   constraint phase. phys_step alone applies none; its companion is phys_apply_liquids, the twin of
+ *   phys_apply_force_fields. A world without liquids launches exactly what it launched before they existed.
+ *
+ * phys_set_liquids: replaces the whole set; n = 0 clears it and frees its buffers. rot_ijkw NULL = identity, mask NULL =
+ *   every body. PHYS_ERR_INVALID_ARG, the message naming the FIRST offending liquid and its reason, in this order: a
+ *   non-finite number, a negative half extent, a negative density, a negative drag coefficient; also n > PHYS_MAX_LIQUIDS and
+ *   a NULL array that is required. Synchronises the world's stream. The set names no body and survives phys_set_bodies.
+ * phys_set_liquid_poses: new positions (and rotations; rot_ijkw NULL keeps them) for the set that is there: a tide, a
+ *   sloshing tank. PHYS_ERR_INVALID_ARG: n differs from the liquid count, NULL pos, a non-finite value.
+ * phys_set_liquid_params: new density, gravity, flow and drag for the set that is there. PHYS_ERR_INVALID_ARG: n differs
+ *   from the liquid count, a NULL array, a non-finite or negative value as above.
+ * phys_get_submersion (host arrays; synchronises) and phys_get_submersion_device (device arrays; enqueued on the world's
+ *   stream): evaluate now, with the same arithmetic, and write NOTHING to the accumulators. Per owned body: frac in the
+ *   lowest-index liquid that acts on it and that liquid's index; 0 and 0xFFFFFFFF mean none. Either array may be NULL.
+ * Sharded worlds (phys_config.max_ghosts > 0) answer every call with PHYS_ERR_UNSUPPORTED, like the force fields.
+ * Cost: one kernel per update, one lane per owned body, only in a world with liquids; 44 bytes of pose and shape per body,
+ *   32 more with drag, 8 more with masks, and 48 of accumulators for the bodies a liquid acts on. DESIGN.md section 29.
+ *   Added without an ABI version change (no struct changed): a library that predates them lacks the symbols. */
+#define PHYS_MAX_LIQUIDS 1024u
+
+int32_t phys_set_liquids(phys_world* w, uint64_t n, const float* pos /*3n*/, const float* rot_ijkw /*4n, NULL = identity*/,
+                         const float* half_extent /*3n*/, const uint16_t* mask /*n, NULL = every body*/,
+                         const float* density /*n*/, const float* gravity /*3n*/, const float* flow /*3n*/,
+                         const float* drag /*2n*/);
+int32_t phys_set_liquid_poses(phys_world* w, uint64_t n /* == liquid count */, const float* pos /*3n*/,
+                              const float* rot_ijkw /*4n, NULL = keep*/);
+int32_t phys_set_liquid_params(phys_world* w, uint64_t n /* == liquid count */, const float* density /*n*/,
+                               const float* gravity /*3n*/, const float* flow /*3n*/, const float* drag /*2n*/);
+int32_t phys_apply_liquids(phys_world* w);
+int32_t phys_get_submersion(phys_world* w, float* frac_out /*n_bodies*/, uint32_t* liquid_out /*n_bodies*/);
+int32_t phys_get_submersion_device(phys_world* w, float* dev_frac_out /*n_bodies*/, uint32_t* dev_liquid_out /*n_bodies*/);
+
 /* --- in-place body edits: poses, velocities, impulses and forces by id list (new: the reference sets fields of one body) ---
  * phys_set_bodies replaces the whole set and resets filters, materials, warm starting, colours, events and trigger occupancy.
  * These calls change a few bodies and keep all of that: a jump, a hit, a respawn, a reset of one environment of many. `ids`

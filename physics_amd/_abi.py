@@ -40,6 +40,9 @@ TRIGGER_ENTER, TRIGGER_EXIT = 1, 2
 # force fields (include/physics_hip.h): the most a world keeps, and the kinds of law
 MAX_FORCE_FIELDS = 1024
 FIELD_ACCEL, FIELD_DRAG, FIELD_RADIAL = 0, 1, 2
+# liquids (include/physics_hip.h): the most a world keeps, and the read-out's "no liquid"
+MAX_LIQUIDS = 1024
+NO_LIQUID = 0xFFFFFFFF
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -219,6 +222,12 @@ PROTOTYPES = {
     "phys_set_force_field_poses": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p]),
     "phys_set_force_field_params": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p]),
     "phys_apply_force_fields": (C.c_int32, [C.c_void_p]),
+    "phys_set_liquids": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, u16p, f32p, f32p, f32p, f32p]),
+    "phys_set_liquid_poses": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p]),
+    "phys_set_liquid_params": (C.c_int32, [C.c_void_p, C.c_uint64, f32p, f32p, f32p, f32p]),
+    "phys_apply_liquids": (C.c_int32, [C.c_void_p]),
+    "phys_get_submersion": (C.c_int32, [C.c_void_p, f32p, u32p]),
+    "phys_get_submersion_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "phys_set_body_poses": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p]),
     "phys_set_body_velocities": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p]),
     "phys_apply_impulses": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p, f32p]),

@@ -489,6 +489,7 @@ static int32_t enqueue_update(phys_world* w, float dt) {
     const bool have_constraints = !w->constraints.empty();
     bool gravity_pending = true;
     if (w->n_fields) launch_force_fields(w);  // force fields: into the accumulators, from the poses and velocities as they stand
+    if (w->n_liquids) launch_liquids(w);      // liquids: behind the fields, from the same poses and velocities
     if (have_constraints) {
         // the constraint right-hand side reads Q = force/torque accumulators including gravity (constraints.rs:92-104):
         // the constraint kernel adds gravity to the accumulators of the bodies it reads, and the step kernel adds
@@ -1125,6 +1126,78 @@ int32_t phys_apply_force_fields(phys_world* w) {
     PHYS_NO_FIELDS_WHEN_SHARDED(w);
     launch_force_fields(w);
     PHYS_HIP_TRY(hipGetLastError());
+    return PHYS_OK;
+}
+
+// ---- liquids: checked and staged on the host (setup.hpp), where the records are built too ----
+// which rank's liquid wets a ghost is a question for a sharded scene that needs it: a sharded world refuses the calls
+#define PHYS_NO_LIQUIDS_WHEN_SHARDED(w) \
+    do { if ((w)->cfg.max_ghosts > 0) return fail(PHYS_ERR_UNSUPPORTED, "liquids are not supported in a world with max_ghosts > 0"); } while (0)
+
+int32_t phys_set_liquids(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw, const float* half_extent, const uint16_t* mask,
+                         const float* density, const float* gravity, const float* flow, const float* drag) {
+    // the arguments first, as phys_set_force_fields checks them
+    if (n > PHYS_MAX_LIQUIDS) return fail(PHYS_ERR_INVALID_ARG, "phys_set_liquids: more than PHYS_MAX_LIQUIDS liquids");
+    if (n && (!pos || !half_extent || !density || !gravity || !flow || !drag))
+        return fail(PHYS_ERR_INVALID_ARG, "liquids need pos, half_extent, density, gravity, flow and drag");
+    std::string bad;
+    if (liquid_set_error(n, pos, rot_ijkw, half_extent, density, gravity, flow, drag, bad)) return fail(PHYS_ERR_INVALID_ARG, bad.c_str());
+    ENTER(w);
+    PHYS_NO_LIQUIDS_WHEN_SHARDED(w);
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));  // updates in flight read the set that is replaced
+    return liquids_set(w, stage_liquids(n, pos, rot_ijkw, half_extent, mask, density, gravity, flow, drag));
+}
+
+int32_t phys_set_liquid_poses(phys_world* w, uint64_t n, const float* pos, const float* rot_ijkw) {
+    ENTER(w);
+    PHYS_NO_LIQUIDS_WHEN_SHARDED(w);
+    if (n != w->n_liquids) return fail(PHYS_ERR_INVALID_ARG, "phys_set_liquid_poses: n must equal the liquid count");
+    if (n && !pos) return fail(PHYS_ERR_INVALID_ARG, "phys_set_liquid_poses: null pos");
+    if (n == 0) return PHYS_OK;
+    if (!restage_liquid_poses(w->lq_host, pos, rot_ijkw)) return fail(PHYS_ERR_INVALID_ARG, "phys_set_liquid_poses: non-finite pose");
+    return liquids_rebuild(w);
+}
+
+int32_t phys_set_liquid_params(phys_world* w, uint64_t n, const float* density, const float* gravity, const float* flow, const float* drag) {
+    ENTER(w);
+    PHYS_NO_LIQUIDS_WHEN_SHARDED(w);
+    if (n != w->n_liquids) return fail(PHYS_ERR_INVALID_ARG, "phys_set_liquid_params: n must equal the liquid count");
+    if (n && (!density || !gravity || !flow || !drag)) return fail(PHYS_ERR_INVALID_ARG, "phys_set_liquid_params: null density, gravity, flow or drag");
+    if (n == 0) return PHYS_OK;
+    std::string bad;
+    if (restage_liquid_params(w->lq_host, density, gravity, flow, drag, bad)) return fail(PHYS_ERR_INVALID_ARG, bad.c_str());
+    return liquids_rebuild(w);
+}
+
+int32_t phys_apply_liquids(phys_world* w) {
+    ENTER(w);
+    PHYS_NO_LIQUIDS_WHEN_SHARDED(w);
+    launch_liquids(w);
+    PHYS_HIP_TRY(hipGetLastError());
+    return PHYS_OK;
+}
+
+int32_t phys_get_submersion_device(phys_world* w, float* dev_frac_out, uint32_t* dev_liquid_out) {
+    ENTER(w);
+    PHYS_NO_LIQUIDS_WHEN_SHARDED(w);
+    if (!dev_frac_out && !dev_liquid_out) return PHYS_OK;
+    launch_submersion(w, dev_frac_out, dev_liquid_out);
+    PHYS_HIP_TRY(hipGetLastError());
+    return PHYS_OK;
+}
+
+int32_t phys_get_submersion(phys_world* w, float* frac_out, uint32_t* liquid_out) {
+    ENTER(w);
+    PHYS_NO_LIQUIDS_WHEN_SHARDED(w);
+    if ((!frac_out && !liquid_out) || w->n_owned == 0) return PHYS_OK;
+    DevBuf<float> d;  // scratch of this call: frac, then the indices
+    PHYS_HIP_TRY(d.resize(2 * w->n_owned));
+    uint32_t* d_liquid = reinterpret_cast<uint32_t*>(d.p + w->n_owned);
+    launch_submersion(w, d.p, d_liquid);
+    PHYS_HIP_TRY(hipGetLastError());
+    if (frac_out) PHYS_HIP_TRY(hipMemcpyAsync(frac_out, d.p, 4 * w->n_owned, hipMemcpyDeviceToHost, w->stream));
+    if (liquid_out) PHYS_HIP_TRY(hipMemcpyAsync(liquid_out, d_liquid, 4 * w->n_owned, hipMemcpyDeviceToHost, w->stream));
+    PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     return PHYS_OK;
 }
 

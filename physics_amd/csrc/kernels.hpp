@@ -323,6 +323,15 @@ void launch_force_fields(phys_world* w);
 int32_t fields_set(phys_world* w, FieldStaging&& staged);
 int32_t fields_rebuild(phys_world* w);  // w->ff_host was patched (poses, params): build the records again and send them
 
+// liquids (liquid.hip): one kernel in front of every update, behind the fields', only in a world with liquids; it adds to the
+// force / torque accumulators and marks them dirty, as the fields' does
+void launch_liquids(phys_world* w);
+// frac and liquid index per owned body into device arrays (either may be null), on the world's stream; writes no accumulator
+void launch_submersion(phys_world* w, float* d_frac, uint32_t* d_liquid);
+// the set from its staged form (setup.hpp stage_liquids; arguments checked by the caller; empty: clears and frees)
+int32_t liquids_set(phys_world* w, LiquidStaging&& staged);
+int32_t liquids_rebuild(phys_world* w);  // w->lq_host was patched (poses, params): build the records again and send them
+
 // in-place body edits (edit.hip): one batch on device arrays ordered by id (EditKind, EditBatch and the
 // argument checks: setup.hpp), enqueued on the world's stream; a pose edit drops the AABBs and grids kept from the last broad
 // phase, a force edit marks the accumulators dirty. Nothing is launched in a world that never calls them.

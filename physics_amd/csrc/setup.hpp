@@ -22,6 +22,7 @@
 #include "../../include/spec/det_math.h"
 #include "../../include/spec/body_edit.h"
 #include "../../include/spec/force_field.h"
+#include "../../include/spec/liquid.h"
 #include "../../include/spec/vec.h"
 #include "plan.hpp"
 
@@ -679,6 +680,100 @@ inline const char* restage_field_params(std::vector<ff_staged>& staged, const fl
         staged[k].s[4] = vol_f4_make(vec[3 * k], vec[3 * k + 1], vec[3 * k + 2], coef[2 * k + 1]);
     }
     return nullptr;
+}
+
+// ---- liquids: the checks and the staged form of phys_set_liquids and its two updates ------------------
+// null when every number is finite, no half extent negative, no density negative and no drag negative; else the message for
+// the FIRST offending liquid (held by msg), its reasons in that order. rot null: not checked (identity).
+inline bool liquid_params_finite(const float* density, const float* gravity, const float* flow, const float* drag, uint64_t k) {
+    bool finite = std::isfinite(density[k]) && std::isfinite(drag[2 * k]) && std::isfinite(drag[2 * k + 1]);
+    for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(gravity[3 * k + a]) && std::isfinite(flow[3 * k + a]);
+    return finite;
+}
+inline const char* liquid_params_negative(const float* density, const float* drag, uint64_t k) {
+    if (density[k] < 0.0f) return ": negative density";
+    if (drag[2 * k] < 0.0f || drag[2 * k + 1] < 0.0f) return ": negative drag coefficient";
+    return nullptr;
+}
+inline const char* liquid_set_error(uint64_t n, const float* pos, const float* rot, const float* he, const float* density, const float* gravity,
+                                    const float* flow, const float* drag, std::string& msg) {
+    for (uint64_t k = 0; k < n; ++k) {
+        bool finite = true, negative = false;
+        for (int a = 0; a < 3; ++a) {
+            finite = finite && std::isfinite(pos[3 * k + a]) && std::isfinite(he[3 * k + a]);
+            negative = negative || he[3 * k + a] < 0.0f;
+        }
+        if (rot)
+            for (int a = 0; a < 4; ++a) finite = finite && std::isfinite(rot[4 * k + a]);
+        const char* what = nullptr;
+        if (!finite || !liquid_params_finite(density, gravity, flow, drag, k)) what = ": non-finite number";
+        else if (negative) what = ": negative half extent";
+        else what = liquid_params_negative(density, drag, k);
+        if (what) {
+            msg = "liquid " + std::to_string(k) + what;
+            return msg.c_str();
+        }
+    }
+    return nullptr;
+}
+// The set as the host keeps it (include/spec/liquid.h lq_staged, 96 bytes per liquid) and what selects the evaluation's
+// instance: a mask array was given; some liquid has a nonzero drag (the velocity record is read).
+struct LiquidStaging {
+    std::vector<lq_staged> staged;
+    bool masked = false, drag = false;
+};
+inline bool liquids_have_drag(const std::vector<lq_staged>& staged) {
+    for (const lq_staged& s : staged)
+        if (s.s[4].w != 0.0f || s.s[5].w != 0.0f) return true;
+    return false;
+}
+// n liquids (arguments checked by liquid_set_error); rot null: identity, mask null: every body
+inline LiquidStaging stage_liquids(uint64_t n, const float* pos, const float* rot, const float* he, const uint16_t* mask, const float* density,
+                                   const float* gravity, const float* flow, const float* drag) {
+    LiquidStaging out;
+    out.staged.resize(n);
+    out.masked = n != 0 && mask != nullptr;
+    for (uint64_t k = 0; k < n; ++k)
+        out.staged[k] = lq_staged_make(mask ? (uint32_t)mask[k] : 0xFFFFu, v3_make(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]), quat_at(rot, k),
+                                       v3_make(he[3 * k], he[3 * k + 1], he[3 * k + 2]), density[k],
+                                       v3_make(gravity[3 * k], gravity[3 * k + 1], gravity[3 * k + 2]),
+                                       v3_make(flow[3 * k], flow[3 * k + 1], flow[3 * k + 2]), drag[2 * k], drag[2 * k + 1]);
+    out.drag = liquids_have_drag(out.staged);
+    return out;
+}
+// phys_set_liquid_poses: new centres and, unless rot is null, rotations of the staged set; false: a non-finite value
+// (nothing changed then)
+inline bool restage_liquid_poses(std::vector<lq_staged>& staged, const float* pos, const float* rot) {
+    if (!poses_finite(staged.size(), pos, rot)) return false;
+    for (size_t k = 0; k < staged.size(); ++k) {
+        staged[k].s[1] = vol_f4_make(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2], 0.0f);
+        if (rot) staged[k].s[2] = vol_f4_make(rot[4 * k], rot[4 * k + 1], rot[4 * k + 2], rot[4 * k + 3]);
+    }
+    return true;
+}
+// phys_set_liquid_params: new density, gravity, flow and drag of the staged set; null, or the message for the first
+// offending liquid (nothing changed then)
+inline const char* restage_liquid_params(std::vector<lq_staged>& staged, const float* density, const float* gravity, const float* flow,
+                                         const float* drag, std::string& msg) {
+    const size_t n = staged.size();
+    for (size_t k = 0; k < n; ++k) {
+        const char* what = liquid_params_finite(density, gravity, flow, drag, k) ? liquid_params_negative(density, drag, k) : ": non-finite number";
+        if (what) {
+            msg = "liquid " + std::to_string(k) + what;
+            return msg.c_str();
+        }
+    }
+    for (size_t k = 0; k < n; ++k) {
+        staged[k].s[0].w = density[k];
+        staged[k].s[4] = vol_f4_make(flow[3 * k], flow[3 * k + 1], flow[3 * k + 2], drag[2 * k]);
+        staged[k].s[5] = vol_f4_make(gravity[3 * k], gravity[3 * k + 1], gravity[3 * k + 2], drag[2 * k + 1]);
+    }
+    return nullptr;
+}
+inline std::vector<lq_record> liquid_records(const std::vector<lq_staged>& staged) {
+    std::vector<lq_record> rec(staged.size());
+    for (size_t k = 0; k < staged.size(); ++k) rec[k] = lq_record_make(&staged[k]);
+    return rec;
 }
 
 // ---- trigger volumes: staged like the fields - the set as the host keeps it, its poses, its records ---

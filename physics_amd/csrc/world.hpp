@@ -308,6 +308,12 @@ struct phys_world {
     bool ff_drag = false, ff_accel = false;  // some field is a DRAG (the velocity record is read) / an ACCEL (the mass is)
     std::vector<ff_staged> ff_host;      // the set as staged (setup.hpp stage_fields): poses and params are patched here, the records built from it
     phys::DevBuf<float> ff_rec;          // 28 floats per field: the record the evaluation reads (include/spec/force_field.h ff_record)
+    // liquids (liquid.hip): nothing below is allocated, and nothing launched, without liquids
+    uint64_t n_liquids = 0;
+    bool lq_masked = false;              // phys_set_liquids was given a mask array: the evaluation's filtered instance
+    bool lq_drag = false;                // some liquid has a nonzero drag: the velocity record is read
+    std::vector<lq_staged> lq_host;      // the set as staged (setup.hpp stage_liquids): poses and params are patched here, the records built from it
+    phys::DevBuf<float> lq_rec;          // 32 floats per liquid: the record the evaluation reads (include/spec/liquid.h lq_record)
     // multi-GPU halo
     phys::DevBuf<uint32_t> cross_pairs;
     uint64_t max_cross_pairs = 0;

@@ -150,6 +150,7 @@ class World:
         self.n_static = 0
         self.n_triggers = 0
         self.n_fields, self._field_kinds = 0, np.zeros(0, np.uint32)
+        self.n_liquids = 0
         self._ck(self.lib.phys_create(C.byref(self.cfg), C.byref(self.h)))
 
     def _ck(self, rc):
@@ -875,6 +876,92 @@ class World:
         """Evaluate the force fields now, into the force / torque accumulators (phys_apply_force_fields): the twin of
         apply_gravity for a caller that steps with step()."""
         self._ck(self.lib.phys_apply_force_fields(self.h))
+
+    # ---- liquids (include/physics_hip.h): buoyancy and drag from the part of each body's shape below a liquid's surface
+    @staticmethod
+    def _liquid_rows(a, n, cols, name, negative_ok=True):
+        v = np.asarray(a, np.float32).reshape(-1, cols)
+        if v.shape[0] not in (1, n):
+            raise ValueError(f"{name}: needs {cols} or {n} x {cols} values, got shape {np.shape(a)}")
+        v = np.ascontiguousarray(np.broadcast_to(v, (n, cols)))
+        if not np.isfinite(v).all():
+            raise ValueError(f"{name}: non-finite value")
+        if not negative_ok and (v < 0).any():
+            raise ValueError(f"{name}: negative value")
+        return v
+
+    def _liquid_params(self, n, density, gravity, flow, drag):
+        z3 = np.zeros(3, np.float32)
+        return (self._liquid_rows(density, n, 1, "density", negative_ok=False).reshape(n),
+                self._liquid_rows(gravity, n, 3, "gravity"), self._liquid_rows(z3 if flow is None else flow, n, 3, "flow"),
+                self._liquid_rows(np.zeros(2, np.float32) if drag is None else drag, n, 2, "drag", negative_ok=False))
+
+    def set_liquids(self, pos, rot=None, half_extent=None, mask=None, density=None, gravity=None, flow=None, drag=None):
+        """Replace the liquids (phys_set_liquids): oriented boxes at pos (n, 3) with rot (n, 4) [i, j, k, w] or None (identity) and
+        half_extent (3,) or (n, 3), whose local +y face is the surface; mask a scalar or (n,) u16 or None (every body); density
+        a scalar or (n,), >= 0; gravity (3,) or (n, 3), the acceleration the liquid is weighed by; flow (3,) or (n, 3) (None:
+        zeros); drag (2,) or (n, 2), linear and angular, >= 0 (None: zeros). An empty pos clears the set. At most MAX_LIQUIDS."""
+        p = _f(pos).reshape(-1, 3)
+        n = p.shape[0]
+        if n > _abi.MAX_LIQUIDS:
+            raise ValueError(f"at most {_abi.MAX_LIQUIDS} liquids")
+        if n and (half_extent is None or density is None or gravity is None):
+            raise ValueError("half_extent, density and gravity are required")
+        if n == 0:
+            half_extent, density, gravity = np.zeros((0, 3)), np.zeros(0), np.zeros((0, 3))
+            flow, drag = np.zeros((0, 3)), np.zeros((0, 2))
+        he = self._liquid_rows(half_extent, n, 3, "half_extent", negative_ok=False)
+        dn, gv, fl, dr = self._liquid_params(n, density, gravity, flow, drag)
+        r = None if rot is None else _f(rot).reshape(-1, 4)
+        if r is not None and r.shape[0] != n:
+            raise ValueError("rot does not match the liquid count")
+        if not np.isfinite(p).all() or (r is not None and not np.isfinite(r).all()):
+            raise ValueError("pos / rot: non-finite value")
+        m = _filter_field(mask, n, "mask", 0, 0xFFFF, np.uint16)
+        self._ck(self.lib.phys_set_liquids(self.h, n, _p(p), _p(r), _p(he), _p(m, u16p), _p(dn), _p(gv), _p(fl), _p(dr)))
+        self.n_liquids = n
+
+    def set_liquid_poses(self, pos, rot=None):
+        """New positions (n_liquids, 3) and, unless None, rotations (n_liquids, 4) of the liquids (phys_set_liquid_poses), from
+        the next evaluation on: a tide, a sloshing tank."""
+        p = _f(pos).reshape(-1, 3)
+        r = None if rot is None else _f(rot).reshape(-1, 4)
+        if p.shape[0] != self.n_liquids or (r is not None and r.shape[0] != self.n_liquids):
+            raise ValueError(f"pos / rot: need {self.n_liquids} rows (the liquid count)")
+        if not np.isfinite(p).all() or (r is not None and not np.isfinite(r).all()):
+            raise ValueError("pos / rot: non-finite value")
+        self._ck(self.lib.phys_set_liquid_poses(self.h, self.n_liquids, _p(p), _p(r)))
+
+    def set_liquid_params(self, density, gravity, flow=None, drag=None):
+        """New density, gravity, flow (None: zeros) and drag (None: zeros) of the liquids (phys_set_liquid_params), each one
+        row or n_liquids rows; the volumes and masks stay."""
+        n = self.n_liquids
+        dn, gv, fl, dr = self._liquid_params(n, density, gravity, flow, drag)
+        self._ck(self.lib.phys_set_liquid_params(self.h, n, _p(dn), _p(gv), _p(fl), _p(dr)))
+
+    def apply_liquids(self):
+        """Evaluate the liquids now, into the force / torque accumulators (phys_apply_liquids): the twin of
+        apply_force_fields for a caller that steps with step()."""
+        self._ck(self.lib.phys_apply_liquids(self.h))
+
+    def get_submersion(self):
+        """(frac (n,) float32, liquid (n,) uint32): per body, the submerged fraction of its volume in the lowest-index liquid
+        that acts on it, and that liquid's index; 0 and 0xFFFFFFFF where none does (phys_get_submersion). Evaluates now and
+        leaves the accumulators alone."""
+        frac = np.zeros(self.n, np.float32)
+        liquid = np.full(self.n, _abi.NO_LIQUID, np.uint32)
+        self._ck(self.lib.phys_get_submersion(self.h, _p(frac), _p(liquid, u32p)))
+        return frac, liquid
+
+    def get_submersion_device(self, frac_out=None, liquid_out=None):
+        """phys_get_submersion_device into contiguous tensors of the world's device: frac_out float32 (n,), liquid_out int32 /
+        uint32 (n,), each or None. Only enqueues on the world's stream."""
+        for name, x, floating in (("frac_out", frac_out, True), ("liquid_out", liquid_out, False)):
+            if x is not None and (not x.is_cuda or not x.is_contiguous() or x.numel() != self.n or x.element_size() != 4
+                                  or x.is_floating_point() != floating):
+                raise ValueError(f"{name}: needs a contiguous 4-byte {'float' if floating else 'integer'} device tensor of {self.n}")
+        self._ck(self.lib.phys_get_submersion_device(self.h, None if frac_out is None else C.c_void_p(frac_out.data_ptr()),
+                                                     None if liquid_out is None else C.c_void_p(liquid_out.data_ptr())))
 
     def enable_trigger_events(self, capacity):
         """Keep up to `capacity` trigger events on the device between two drains (phys_trigger_events_enable); 0 turns

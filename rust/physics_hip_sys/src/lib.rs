@@ -57,6 +57,8 @@ pub const PHYS_MAX_FORCE_FIELDS: u32 = 1024;
 pub const PHYS_FIELD_ACCEL: u32 = 0;
 pub const PHYS_FIELD_DRAG: u32 = 1;
 pub const PHYS_FIELD_RADIAL: u32 = 2;
+// liquids: the most a world keeps
+pub const PHYS_MAX_LIQUIDS: u32 = 1024;
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -296,6 +298,12 @@ extern "C" {
     pub fn phys_set_force_field_poses(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32) -> i32;
     pub fn phys_set_force_field_params(w: *mut phys_world, n: u64, vec: *const f32, coef: *const f32) -> i32;
     pub fn phys_apply_force_fields(w: *mut phys_world) -> i32;
+    pub fn phys_set_liquids(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32, half_extent: *const f32, mask: *const u16, density: *const f32, gravity: *const f32, flow: *const f32, drag: *const f32) -> i32;
+    pub fn phys_set_liquid_poses(w: *mut phys_world, n: u64, pos: *const f32, rot_ijkw: *const f32) -> i32;
+    pub fn phys_set_liquid_params(w: *mut phys_world, n: u64, density: *const f32, gravity: *const f32, flow: *const f32, drag: *const f32) -> i32;
+    pub fn phys_apply_liquids(w: *mut phys_world) -> i32;
+    pub fn phys_get_submersion(w: *mut phys_world, frac_out: *mut f32, liquid_out: *mut u32) -> i32;
+    pub fn phys_get_submersion_device(w: *mut phys_world, dev_frac_out: *mut f32, dev_liquid_out: *mut u32) -> i32;
     pub fn phys_set_body_poses(w: *mut phys_world, n: u64, ids: *const u32, pos: *const f32, rot_ijkw: *const f32) -> i32;
     pub fn phys_set_body_velocities(w: *mut phys_world, n: u64, ids: *const u32, lin: *const f32, ang: *const f32) -> i32;
     pub fn phys_apply_impulses(w: *mut phys_world, n: u64, ids: *const u32, impulse: *const f32, point: *const f32, ang_impulse: *const f32) -> i32;
