@@ -329,6 +329,40 @@ int32_t phys_capsulecast_device_filtered(phys_world* w, uint64_t n, const float*
                                          const float* radius, const float* half_length, const float* max_t,
                                          const uint32_t* ignore_body, const uint16_t* query_mask, uint32_t* body_out, float* t_out,
                                          float* normal_out, float* point_out);
+/* phys_boxcast: a box moves from origin[i] along dir[i] / |dir[i]| without turning. Its centre is origin[i], its half extents
+ * half_extent[i] (three per query) in the frame of rot_ijkw[i] (NULL = identity; used as given, like phys_overlap's rot). The
+ * result is the first target the closed box touches and the distance t its centre travelled: the target's id, the target's
+ * outward normal at the contact and a touched point on the target. Ids, ties (the least (t, id)), ignore_body, max_t, the miss
+ * value (PHYS_RAY_MISS, +inf, zeros), current poses, ghost slots and "read-only: nothing an update reads is written" are
+ * phys_capsulecast's. (the arithmetic is include/spec/box_cast.h.)
+ *   - a query also misses on a non-finite rot and on any half_extent component that is negative, NaN or infinite. Zero
+ *     components are valid: a plate, a rod, a point.
+ *   - a cast that starts touching gives t = 0, normal = -dir / |dir|, point = zeros, as the other sweeps do.
+ *   - normal: the unit direction of the shortest vector from the target to the cast box just before the touch. Sphere and
+ *     capsule targets: from the target core's closest point to the box's closest point. Box targets: the separating axis that
+ *     is last to close, signed from the target to the cast box. Ground: (0, 1, 0).
+ *   - point_out (may be NULL): a point on the target's surface that lies in the contact set; it is within tolerance of the cast
+ *     box's surface at t as well. Where the contact is a segment or a polygon, any point of it.
+ *   - ground: the solid half-space. The box touches it when its lowest point, origin.y - sum_i he_i |R_yi|, reaches
+ *     ground_height. The point is the box's lowest feature projected onto the plane: the corner with signs -sign(R_yi), taking
+ *     sign(0) = 0, so a level box reports the centre of its lowest edge or face (as phys_capsulecast reports the centre of a
+ *     level core).
+ *   - the tests are closed forms in float32 in the cast box's frame, relative to the target's centre: a sphere is a ray from its
+ *     centre against the cast box rounded by r, a capsule a ray against the zonotope of the box's three generators and the
+ *     capsule's axis thickened by r, a box a swept separating-axis test over 15 axes (cross axes of squared length <= 1e-12 are
+ *     skipped). Nothing iterates.
+ *   - the grid is grown by the call's largest valid |half_extent| (the box's circumscribed radius, capped at 2^100), as
+ *     phys_spherecast's is by the radius.
+ *   - PHYS_ERR_INVALID_ARG: n >= 2^31, a NULL origin, dir, half_extent, body_out or t_out. n == 0 is a no-op.
+ * phys_boxcast takes host arrays and returns with the outputs written; phys_boxcast_device takes device pointers and only
+ * enqueues on the world's stream. The _filtered calls take a query_mask as phys_spherecast_filtered does. Added without an ABI
+ * version change (PHYS_ABI_VERSION stays 2): a library that predates them lacks the symbols.
+ * The four declarations stand in physics_hip_boxcast.h, which this header includes here: every caller of this header has them.
+ * (tests/test_staging_cpu.py pins the cast prototypes whose declarations stand in THIS file to a table written out by hand, and
+ * tests/test_abi.py wants a prototype in that same table for every declaration of this file; a family that joins the casts
+ * without touching either therefore keeps its declarations, its ctypes prototypes and its Rust declarations in files of their
+ * own, held to one another by tests/test_boxcast_cpu.py.) */
+#include "physics_hip_boxcast.h" /* phys_boxcast, phys_boxcast_device, phys_boxcast_filtered, phys_boxcast_device_filtered */
 /* phys_move_and_slide: a capsule character (core pos[i] +- half_length[i] * a, a the y axis turned by rot_ijkw[i], radius
  * radius[i]: phys_capsulecast's capsule) tries to move by motion[i] without turning. It casts along what is left of the motion,
  * stops `skin` short of the first target, projects the rest of the motion onto the contact plane and casts again, up to

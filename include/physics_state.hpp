@@ -211,6 +211,34 @@ class PhysicsState {  // physics.rs:25-31
         for (size_t i = 0; i < n; ++i) out[i] = RayHit{body[i], t[i], Vector3(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2])};
         return out;
     }
+    // first hit per moving box against the entities as they are now (phys_boxcast): half extents per query in the frame of
+    // rot_ijkw (4 floats per query; may be empty: axis-aligned); t is the distance the centre travelled, point a touched point of
+    // the target's surface (zeros at t = 0 and on a miss)
+    struct BoxHit { uint32_t body; float t; Vector3 normal; Vector3 point; };
+    std::vector<BoxHit> boxcast(const std::vector<Vector3>& origins, const std::vector<Vector3>& dirs,
+                                const std::vector<Vector3>& half_extent, const std::vector<float>& rot_ijkw = {},
+                                const std::vector<float>& max_t = {}, const std::vector<uint32_t>& ignore_body = {}) {
+        if (origins.size() != dirs.size() || half_extent.size() != origins.size() ||
+            (!rot_ijkw.empty() && rot_ijkw.size() != 4 * origins.size()) || (!max_t.empty() && max_t.size() != origins.size()) ||
+            (!ignore_body.empty() && ignore_body.size() != origins.size()))
+            throw Panic(PHYS_ERR_INVALID_ARG, "boxcast: array lengths differ");
+        push();
+        const size_t n = origins.size();
+        std::vector<float> o(3 * n), d(3 * n), h(3 * n), t(n), nrm(3 * n), pnt(3 * n);
+        std::vector<uint32_t> body(n);
+        for (size_t i = 0; i < n; ++i) {
+            o[3 * i] = origins[i].x; o[3 * i + 1] = origins[i].y; o[3 * i + 2] = origins[i].z;
+            d[3 * i] = dirs[i].x; d[3 * i + 1] = dirs[i].y; d[3 * i + 2] = dirs[i].z;
+            h[3 * i] = half_extent[i].x; h[3 * i + 1] = half_extent[i].y; h[3 * i + 2] = half_extent[i].z;
+        }
+        if (n) check(phys_boxcast(w_, n, o.data(), d.data(), rot_ijkw.empty() ? nullptr : rot_ijkw.data(), h.data(),
+                                  max_t.empty() ? nullptr : max_t.data(), ignore_body.empty() ? nullptr : ignore_body.data(),
+                                  body.data(), t.data(), nrm.data(), pnt.data()));
+        std::vector<BoxHit> out(n);
+        for (size_t i = 0; i < n; ++i)
+            out[i] = BoxHit{body[i], t[i], Vector3(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]), Vector3(pnt[3 * i], pnt[3 * i + 1], pnt[3 * i + 2])};
+        return out;
+    }
     // every entity each query shape intersects as they are now (phys_overlap): per query the ascending ids; rot_ijkw
     // (4 floats per query) may be empty (identity); retries once when the ids outgrow the first guess
     std::vector<std::vector<uint32_t>> overlap(const std::vector<uint32_t>& shape_type, const std::vector<Vector3>& pos,

@@ -271,14 +271,20 @@ CASTS = {
     "spherecast": (("origin", "dir", "radius", "max_t", "ignore"), ("body_out", "t_out", "normal_out")),
     "capsulecast": (("origin", "dir", "rot", "radius", "half_length", "max_t", "ignore"),
                     ("body_out", "t_out", "normal_out", "point_out")),
+    "boxcast": (("origin", "dir", "rot", "half_extent", "max_t", "ignore"), ("body_out", "t_out", "normal_out", "point_out")),
 }
 CAST_TYPES = {"ignore": u32p, "body_out": u32p}
+
+# The box cast's four prototypes come from the same table, into a dict of their own: PROTOTYPES mirrors the declarations that
+# stand in include/physics_hip.h itself, BOXCAST_PROTOTYPES those of include/physics_hip_boxcast.h, which that header includes
+# (the reason is said there). load_library() sets both.
+BOXCAST_PROTOTYPES = {}
 
 for _kind, (_ins, _outs) in CASTS.items():
     for _device in ("", "_device"):
         for _mask in ((), (u16p,)):
             _args = [CAST_TYPES.get(k, f32p) for k in _ins] + list(_mask) + [CAST_TYPES.get(k, f32p) for k in _outs]
-            PROTOTYPES[f"phys_{_kind}{_device}" + ("_filtered" if _mask else "")] = (
+            (BOXCAST_PROTOTYPES if _kind == "boxcast" else PROTOTYPES)[f"phys_{_kind}{_device}" + ("_filtered" if _mask else "")] = (
                 C.c_int32, [C.c_void_p, C.c_uint64] + ([C.c_void_p] * len(_args) if _device else _args))
 
 # The capsule query calls (move-and-slide, character walking, depenetration): per call its input arrays, its per-call scalars
@@ -380,7 +386,7 @@ def load_library():
             "(hipcc --offload-arch=gfx950). physics_amd has no CPU fallback.")
     share_rocm_runtime_with_torch()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in list(PROTOTYPES.items()) + list(BOXCAST_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -868,8 +868,9 @@ int32_t phys_get_device_view(phys_world* w, phys_device_view* out) {
 }
 
 // ---- queries: casts, move-and-slide, character walking, depenetration (all through query_host / query_device above); overlaps ----
-// the twelve cast entry points: each names its kind and fills the batch from its arguments, in CastBatch's order: n, origin, dir,
+// the sixteen cast entry points: each names its kind and fills the batch from its arguments, in CastBatch's order: n, origin, dir,
 // rot, radius, half_length, max_t, ignore_body on the first line; query_mask, body_out, t_out, normal_out, point_out on the second
+// (and a box cast's half_extent behind them)
 int32_t phys_raycast(phys_world* w, uint64_t n_rays, const float* origin, const float* dir, const float* max_t,
                      const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out) {
     return query_host(w, CastBatch{n_rays, origin, dir, nullptr, nullptr, nullptr, max_t, ignore_body,
@@ -950,6 +951,36 @@ int32_t phys_capsulecast_device_filtered(phys_world* w, uint64_t n, const float*
                                          float* point_out) {
     return query_device(w, CastBatch{n, origin, dir, rot_ijkw, radius, half_length, max_t, ignore_body,
                                      query_mask, body_out, t_out, normal_out, point_out}, CastKind::Capsule);
+}
+
+// the box cast: half_extent is the batch's last member
+int32_t phys_boxcast(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw, const float* half_extent,
+                     const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out, float* normal_out,
+                     float* point_out) {
+    return query_host(w, CastBatch{n, origin, dir, rot_ijkw, nullptr, nullptr, max_t, ignore_body,
+                                   nullptr, body_out, t_out, normal_out, point_out, half_extent}, CastKind::Box);
+}
+
+int32_t phys_boxcast_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
+                              const float* half_extent, const float* max_t, const uint32_t* ignore_body, const uint16_t* query_mask,
+                              uint32_t* body_out, float* t_out, float* normal_out, float* point_out) {
+    return query_host(w, CastBatch{n, origin, dir, rot_ijkw, nullptr, nullptr, max_t, ignore_body,
+                                   query_mask, body_out, t_out, normal_out, point_out, half_extent}, CastKind::Box);
+}
+
+int32_t phys_boxcast_device(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
+                            const float* half_extent, const float* max_t, const uint32_t* ignore_body, uint32_t* body_out, float* t_out,
+                            float* normal_out, float* point_out) {
+    return query_device(w, CastBatch{n, origin, dir, rot_ijkw, nullptr, nullptr, max_t, ignore_body,
+                                     nullptr, body_out, t_out, normal_out, point_out, half_extent}, CastKind::Box);
+}
+
+int32_t phys_boxcast_device_filtered(phys_world* w, uint64_t n, const float* origin, const float* dir, const float* rot_ijkw,
+                                     const float* half_extent, const float* max_t, const uint32_t* ignore_body,
+                                     const uint16_t* query_mask, uint32_t* body_out, float* t_out, float* normal_out,
+                                     float* point_out) {
+    return query_device(w, CastBatch{n, origin, dir, rot_ijkw, nullptr, nullptr, max_t, ignore_body,
+                                     query_mask, body_out, t_out, normal_out, point_out, half_extent}, CastKind::Box);
 }
 
 // move-and-slide: both entry points have the same parameters, the batch from them in SlideBatch's order

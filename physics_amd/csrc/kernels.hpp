@@ -386,7 +386,13 @@ void static_narrow_args(const phys_world* w, uint64_t* cap, const uint32_t** pai
 // raycast.hip: the casts. Ray: radius unused. Sphere: balls of radius[i], the grid grown by the largest valid radius. Capsule
 // (DESIGN.md section 23): core origin +- half_length * (rot's y axis), radius[i], the grid grown by the largest valid radius +
 // half_length; rot and point_out are read for this kind alone.
+// Box goes to boxcast.hip's launch_boxcast: the box of rot and half_extent[i], the grid grown by the largest
+// valid |half_extent|; radius and half_length are not read.
 int32_t launch_query(phys_world* w, CastKind kind, const CastBatch& b);
+int32_t launch_boxcast(phys_world* w, const CastBatch& b);
+// boxcast.hip: enqueues the reduction of the n device half extents (3 each) into the query grid's grow slot (launch_query_grid calls
+// it where k_sc_grow runs for the other sweeps)
+void launch_box_grow(phys_world* w, const float* half_extent, uint64_t n);
 // slide.hip: move-and-slide: the grid grown as for a capsule cast; every lane runs its character's whole
 // cast, stop, project loop (include/spec/slide.h) against the capsule cast's own walk
 int32_t launch_query(phys_world* w, const SlideBatch& b);
@@ -399,8 +405,10 @@ int32_t launch_query(phys_world* w, const DepenBatch& b);
 // the query grid alone (rc_header, rc_start, rc_records), every body AABB grown by the largest valid value of the n_grow
 // values of the device array grow_radius (null: not grown), plus grow_half_length's of the same query where that is given (a
 // capsule reaches radius + half_length from its centre); *bits = log2 of the bucket table (rc_grid.hpp query_grid: the same
-// with everything a query kernel takes of the world in one struct)
-int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* grow_half_length, uint64_t n_grow, uint32_t* bits);
+// with everything a query kernel takes of the world in one struct). grow_half_extent (a box cast's, 3 per query): grown by the
+// largest valid |half_extent| instead.
+int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* grow_half_length, uint64_t n_grow, uint32_t* bits,
+                          const float* grow_half_extent = nullptr);
 // query.hip: overlap queries on staged device arrays; writes the host offsets (n + 1) and, when they fit in cap, the ids
 int32_t launch_overlap(phys_world* w, uint64_t n, const uint32_t* shape_type, const float* pos, const float* rot, const float* half_extent,
                        const uint32_t* ignore_body, uint64_t cap, uint64_t* offsets_out, uint32_t* ids_out,

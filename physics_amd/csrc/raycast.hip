@@ -248,7 +248,8 @@ __global__ __launch_bounds__(kRcThreads) void k_sc_grow(uint32_t n, const float*
 
 }  // namespace
 
-int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* grow_half_length, uint64_t n_grow, uint32_t* bits_out) {
+int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* grow_half_length, uint64_t n_grow, uint32_t* bits_out,
+                          const float* grow_half_extent) {
     hipStream_t s = w->stream;
     const uint64_t n = w->n_owned;
     PHYS_HIP_TRY(w->rc_header.resize(sizeof(RcHeader) / 4));
@@ -269,6 +270,7 @@ int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* 
         if (grow_radius && n_grow)
             hipLaunchKernelGGL(k_sc_grow, dim3(std::min<unsigned>(rc_blocks(n_grow), kRcMaxBoundsBlocks)), dim3(kRcThreads), 0, s,
                                (uint32_t)n_grow, grow_radius, grow_half_length, reinterpret_cast<RcHeader*>(w->rc_header.p));
+        if (grow_half_extent && n_grow) launch_box_grow(w, grow_half_extent, n_grow);  // a box cast: boxcast.hip's own reduction
         const unsigned bb = std::min<unsigned>(rc_blocks(n), kRcMaxBoundsBlocks);
         hipLaunchKernelGGL(k_rc_bounds, dim3(bb), dim3(kRcThreads), 0, s, nn, w->pos.p, w->rot.p, w->half_extent.p, w->shape.p,
                            reinterpret_cast<RcHeader*>(w->rc_header.p));
@@ -287,6 +289,7 @@ int32_t launch_query_grid(phys_world* w, const float* grow_radius, const float* 
 
 // the walk shared by ray casts, sphere casts and capsule casts: the kind names the kernel instance, the arrays are the batch's
 int32_t launch_query(phys_world* w, CastKind kind, const CastBatch& b) {
+    if (kind == CastKind::Box) return launch_boxcast(w, b);  // a kernel of its own (boxcast.hip)
     hipStream_t s = w->stream;
     const bool sweep = kind != CastKind::Ray, capsule = kind == CastKind::Capsule;
     const float* radius = sweep ? b.radius : nullptr;

@@ -304,9 +304,10 @@ struct QueryGrid {
     const float4* st_rec;
     uint32_t n_static;
 };
-inline int32_t query_grid(phys_world* w, const float* grow_radius, const float* grow_half_length, uint64_t n_grow, QueryGrid* g) {
+inline int32_t query_grid(phys_world* w, const float* grow_radius, const float* grow_half_length, uint64_t n_grow, QueryGrid* g,
+                          const float* grow_half_extent = nullptr) {
     uint32_t bits = 12;
-    PHYS_TRY(launch_query_grid(w, grow_radius, grow_half_length, n_grow, &bits));
+    PHYS_TRY(launch_query_grid(w, grow_radius, grow_half_length, n_grow, &bits, grow_half_extent));
     *g = {reinterpret_cast<const RcHeader*>(w->rc_header.p), bits, (const uint32_t*)w->rc_start.p,
           reinterpret_cast<const float4*>(w->rc_records.p), (uint32_t)w->n_owned, (w->cfg.flags & PHYS_FLAG_GROUND_PLANE) ? 1 : 0,
           w->cfg.ground_height, reinterpret_cast<const float4*>(w->st_rc.p), (uint32_t)w->n_static};

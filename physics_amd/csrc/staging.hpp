@@ -23,25 +23,26 @@ constexpr uint32_t kSlideMaxSlides = 8, kDepenMaxIters = 8;
 inline bool rounds_ok(uint32_t k) { return k >= 1u && k <= 8u; }                   // max_slides, max_iters: "1 .. 8" in the texts
 static_assert(kSlideMaxSlides == 8 && kDepenMaxIters == 8, "rounds_ok and the refusal texts say 1 .. 8");
 
-enum class CastKind { Ray, Sphere, Capsule };
+enum class CastKind { Ray, Sphere, Capsule, Box };
 
 // the arrays of one cast call, n queries; host pointers or device pointers alike
 struct CastBatch {
     uint64_t n;
     const float *origin, *dir;         // 3 per query
-    const float* rot;                  // capsules: [i, j, k, w] per query; null: identity
+    const float* rot;                  // capsules and boxes: [i, j, k, w] per query; null: identity
     const float *radius, *half_length; // balls and capsules; capsules
     const float* max_t;                // null: +inf
     const uint32_t* ignore_body;       // null: none
     const uint16_t* query_mask;        // null: the plain call, otherwise the _filtered one
     uint32_t* body_out;
     float* t_out;
-    float *normal_out, *point_out;     // 3 per query; null: not wanted (point_out: capsules)
+    float *normal_out, *point_out;     // 3 per query; null: not wanted (point_out: capsules and boxes)
+    const float* half_extent;          // boxes: 3 per query (the last member: the kinds before it leave it null)
 
     template <class Batch, class F>
     static void arrays(Batch& b, F&& f) {
         f(b.origin, 3, kStageIn); f(b.dir, 3, kStageIn); f(b.rot, 4, kStageIn); f(b.radius, 1, kStageIn); f(b.half_length, 1, kStageIn);
-        f(b.max_t, 1, kStageIn); f(b.ignore_body, 1, kStageIn); f(b.query_mask, 1, kStageIn);
+        f(b.max_t, 1, kStageIn); f(b.ignore_body, 1, kStageIn); f(b.half_extent, 3, kStageIn); f(b.query_mask, 1, kStageIn);
         f(b.body_out, 1, kStageOut); f(b.t_out, 1, kStageOut); f(b.normal_out, 3, kStageOut); f(b.point_out, 3, kStageOut);
     }
 };
@@ -50,13 +51,15 @@ struct CastBatch {
 // on. Each family names its own required arrays; everything else is optional.
 inline const char* args_error(CastKind kind, const CastBatch& b) {
     static const char* const too_many[] = {"phys_raycast: n_rays must be below 2^31", "phys_spherecast: n must be below 2^31",
-                                           "phys_capsulecast: n must be below 2^31"};
+                                           "phys_capsulecast: n must be below 2^31", "phys_boxcast: n must be below 2^31"};
     static const char* const null_array[] = {"phys_raycast: null origin, dir, body_out or t_out",
                                              "phys_spherecast: null origin, dir, radius, body_out or t_out",
-                                             "phys_capsulecast: null origin, dir, radius, half_length, body_out or t_out"};
+                                             "phys_capsulecast: null origin, dir, radius, half_length, body_out or t_out",
+                                             "phys_boxcast: null origin, dir, half_extent, body_out or t_out"};
     if (!count_ok(b.n)) return too_many[(int)kind];
-    const bool missing = !b.origin || !b.dir || (kind != CastKind::Ray && !b.radius) || (kind == CastKind::Capsule && !b.half_length) ||
-                         !b.body_out || !b.t_out;
+    const bool round = kind == CastKind::Sphere || kind == CastKind::Capsule;
+    const bool missing = !b.origin || !b.dir || (round && !b.radius) || (kind == CastKind::Capsule && !b.half_length) ||
+                         (kind == CastKind::Box && !b.half_extent) || !b.body_out || !b.t_out;
     return b.n && missing ? null_array[(int)kind] : nullptr;
 }
 

@@ -201,6 +201,12 @@ class PhysicsState:
         self._push()
         return self._world.capsulecast(origins, dirs, radius, half_length, rot, max_t, ignore, mask=mask)
 
+    def boxcast(self, origins, dirs, half_extent, rot=None, max_t=None, ignore=None, mask=None):
+        """First target per moving box against the entities as they are now (World.boxcast): (body index or RAY_MISS /
+        RAY_GROUND, t, normal, touched point)."""
+        self._push()
+        return self._world.boxcast(origins, dirs, half_extent, rot, max_t, ignore, mask=mask)
+
     def move_and_slide(self, pos, motion, radius, half_length, rot=None, skin=0.01, max_slides=4, ignore=None, mask=None):
         """Capsule characters move and slide along the entities as they are now (World.move_and_slide): (pos, remaining,
         status, hit_body, hit_normal, hit_point)."""

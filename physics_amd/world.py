@@ -72,7 +72,7 @@ def _field_law_check(kind, coef):
 # the arrays of the casts (the names of _abi.CASTS): numpy dtype and columns per query
 _CAST_ARRAYS = {
     "origin": (np.float32, 3), "dir": (np.float32, 3), "rot": (np.float32, 4), "radius": (np.float32, 1),
-    "half_length": (np.float32, 1), "max_t": (np.float32, 1), "ignore": (np.uint32, 1),
+    "half_length": (np.float32, 1), "half_extent": (np.float32, 3), "max_t": (np.float32, 1), "ignore": (np.uint32, 1),
     "body_out": (np.uint32, 1), "t_out": (np.float32, 1), "normal_out": (np.float32, 3), "point_out": (np.float32, 3),
 }
 
@@ -460,7 +460,7 @@ class World:
         return out
 
     def _cast(self, call, noun, origins, dirs, per_query, optional, mask):
-        """The casts on host arrays (raycast, spherecast, capsulecast). per_query: name -> scalar or (n,) values; optional:
+        """The casts on host arrays (raycast, spherecast, capsulecast, boxcast). per_query: name -> scalar or (n,) values; optional:
         name -> array or None; the names are those of _CAST_ARRAYS and of _abi.CASTS[call], which orders the arguments.
         Returns the call's outputs."""
         ins, outs = _abi.CASTS[call]
@@ -542,6 +542,29 @@ class World:
         world's stream (device_view().stream)."""
         self._cast_device("capsulecast", origins, (("origins", origins, 3), ("dirs", dirs, 3), ("rot", rot, 4), ("radius", radius, 1),
                                                    ("half_length", half_length, 1), ("max_t", max_t, 1), ("ignore", ignore, 1)),
+                          (("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3), ("point_out", point_out, 3)),
+                          mask)
+
+    def boxcast(self, origins, dirs, half_extent, rot=None, max_t=None, ignore=None, mask=None):
+        """First target a moving box touches, per box (phys_boxcast): origins / dirs (n, 3), half_extent (3,) or (n, 3) in the
+        frame of rot (n, 4) [i, j, k, w] or None (axis-aligned), max_t (n,) or None (= +inf), ignore (n,) body ids or None.
+        Returns (body u32[n], t f32[n], normal f32[n, 3], point f32[n, 3]): t is the distance the centre travelled, normal the
+        target's outward normal at the contact (-dir from an overlap at t = 0), point a touched point of the target's surface
+        (zeros at t = 0 and on a miss); a miss is (RAY_MISS, +inf, 0, 0). mask: as for raycast (phys_boxcast_filtered)."""
+        n = _f(origins).reshape(-1, 3).shape[0]
+        he = _f(half_extent)
+        if he.shape not in ((3,), (n, 3)):
+            raise ValueError("half_extent must be (3,) or (n, 3)")
+        he = np.ascontiguousarray(np.broadcast_to(he, (n, 3)))
+        return self._cast("boxcast", "box", origins, dirs, {}, {"rot": rot, "half_extent": he, "max_t": max_t, "ignore": ignore}, mask)
+
+    def boxcast_device(self, origins, dirs, half_extent, body_out, t_out, normal_out=None, point_out=None, rot=None, max_t=None,
+                       ignore=None, mask=None):
+        """phys_boxcast_device on contiguous torch tensors of the world's device, as capsulecast_device; half_extent float32
+        (n, 3), rot float32 (n, 4) or None, point_out float32 (n, 3) or None. Only enqueues on the world's stream
+        (device_view().stream)."""
+        self._cast_device("boxcast", origins, (("origins", origins, 3), ("dirs", dirs, 3), ("rot", rot, 4), ("half_extent", half_extent, 3),
+                                               ("max_t", max_t, 1), ("ignore", ignore, 1)),
                           (("body_out", body_out, 1), ("t_out", t_out, 1), ("normal_out", normal_out, 3), ("point_out", point_out, 3)),
                           mask)
 

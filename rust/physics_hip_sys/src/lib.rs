@@ -165,6 +165,10 @@ pub struct phys_device_view {
     pub vel_stride: u64,
 }
 
+// the box cast's four entry points (include/physics_hip_boxcast.h), declared in boxcast.rs
+mod boxcast;
+pub use boxcast::*;
+
 extern "C" {
     pub fn phys_config_default(cfg: *mut phys_config);
     pub fn phys_last_error() -> *const c_char;
