@@ -909,6 +909,44 @@ int32_t phys_apply_liquids(phys_world* w);
 int32_t phys_get_submersion(phys_world* w, float* frac_out /*n_bodies*/, uint32_t* liquid_out /*n_bodies*/);
 int32_t phys_get_submersion_device(phys_world* w, float* dev_frac_out /*n_bodies*/, uint32_t* dev_liquid_out /*n_bodies*/);
 
+/* --- continuous collision: fast bodies stop at statics and the ground (new: the reference samples contacts at poses only) ---
+ * An update finds contacts at the poses its bodies start from, within contact_margin. A body that moves further than a static
+ * collider is thick in one update never overlaps it at a sampled pose and passes through; over the ground it is caught, but
+ * metres deep. The bodies LISTED here are swept along each update's motion, and one that would pass through a static
+ * collider or the ground is advanced only to its time of impact in that update.
+ * The rule (include/spec/ccd.h states it as code), per listed body, between the solver and the position
+ *   half of a collision update, from the pose at the start of the update and the velocity the solver left:
+ *   - motion m = lin_velocity * dt, L = |m|. Not swept (frac = 1, target = PHYS_RAY_MISS): L not finite or not > 0, shape NONE,
+ *     a non-finite pose. Otherwise the body translates along u = m / L without turning.
+ *   - the body is a core box plus a radius: a box itself; a sphere a point plus its radius; a capsule a rod plus its radius.
+ *   - targets: the ground (PHYS_FLAG_GROUND_PLANE) and every static collider that the body's collision filter collides with,
+ *     by the rule of the contacts. Other bodies are NOT targets.
+ *   - each target is tested with the box cast's arithmetic (include/spec/box_cast.h). A test that starts touching is no hit:
+ *     the discrete contact owns that pair. A hit counts only when its distance t < L. The least (t, id) wins.
+ *   - frac = min(t / L, 1) on a hit, else 1. The body is integrated for dt * frac, rotation too. Its velocity is left alone:
+ *     it lands touching, inside contact_margin, and the next update's contact and the materials decide what happens.
+ * Limits: the sweep does not turn (a spinning long box can clip a wall at landing; the next update's contact resolves it); the
+ *   rest of the update after the impact, (1 - frac) dt, is dropped; bodies are no targets for each other; sharded worlds
+ *   (max_ghosts > 0) have no continuous collision. It runs in collision updates only (PHYS_FLAG_COLLISIONS, dt > 0, not
+ *   PHYS_FLAG_BROADPHASE_ONLY), phys_update_n included; phys_step never sweeps.
+ * phys_set_ccd_bodies: replaces the list; n = 0 clears it and frees its buffers. Entry k is ids[k]: the order is kept and is the
+ *   order of the read-out. It resets every frac to 1 and every count to 0. PHYS_ERR_UNSUPPORTED: a world without
+ *   PHYS_FLAG_COLLISIONS or with max_ghosts > 0. PHYS_ERR_INVALID_ARG: NULL ids with n > 0, n >= 2^31, an id given twice.
+ *   PHYS_ERR_OUT_OF_RANGE: an id not below the body count. A refused call leaves the old list in force. phys_set_bodies clears
+ *   the list (its ids are stale); phys_set_static_bodies keeps it.
+ * phys_get_ccd_hits (host arrays; synchronises) and phys_get_ccd_hits_device (device arrays; enqueued on the world's stream):
+ *   per list entry, of the last update that swept: frac, the target's id (PHYS_RAY_MISS, PHYS_RAY_GROUND, PHYS_STATIC_ID_BIT | k),
+ *   the normal from the target to the body (0 without a hit), and count: the updates in which the entry was stopped since the
+ *   list was set (never zeroed in between, so a phys_update_n batch hides no hit). Any array may be NULL. Read-only.
+ * Cost: one kernel per update, one lane per listed body, every static's box tested against the body's swept box and the
+ *   survivors exactly; only in a world with a list. A world without one launches exactly what it launched before.
+ *   Added without an ABI version change (no struct changed): a library that predates it lacks the symbols. */
+int32_t phys_set_ccd_bodies(phys_world* w, uint64_t n, const uint32_t* ids /*n*/);
+int32_t phys_get_ccd_hits(phys_world* w, float* frac_out /*n_ccd*/, uint32_t* target_out /*n_ccd*/, float* normal_out /*3 n_ccd*/,
+                          uint32_t* count_out /*n_ccd*/);
+int32_t phys_get_ccd_hits_device(phys_world* w, float* dev_frac_out /*n_ccd*/, uint32_t* dev_target_out /*n_ccd*/,
+                                 float* dev_normal_out /*3 n_ccd*/, uint32_t* dev_count_out /*n_ccd*/);
+
 /* --- in-place body edits: poses, velocities, impulses and forces by id list (new: the reference sets fields of one body) ---
  * phys_set_bodies replaces the whole set and resets filters, materials, warm starting, colours, events and trigger occupancy.
  * These calls change a few bodies and keep all of that: a jump, a hit, a respawn, a reset of one environment of many. `ids`

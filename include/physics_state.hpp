@@ -239,6 +239,26 @@ class PhysicsState {  // physics.rs:25-31
             out[i] = BoxHit{body[i], t[i], Vector3(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]), Vector3(pnt[3 * i], pnt[3 * i + 1], pnt[3 * i + 2])};
         return out;
     }
+    // continuous collision (phys_set_ccd_bodies): the listed entities are swept along every update's motion and stop at the static
+    // colliders and the ground they would pass through; an empty list clears it. ccd_hits: per list entry, of the last update
+    // that swept (phys_get_ccd_hits). The library clears the list with every new entity set; push() sends it again behind one
+    // (the counts start over), unless it names an entity that is gone: then the list is dropped.
+    struct CcdHit { float frac; uint32_t target; Vector3 normal; uint32_t count; };
+    void set_ccd_bodies(const std::vector<uint32_t>& ids) {
+        push();
+        check(phys_set_ccd_bodies(w_, ids.size(), ids.empty() ? nullptr : ids.data()));
+        ccd_ids_ = ids;
+    }
+    std::vector<CcdHit> ccd_hits() {
+        push();
+        const size_t n = ccd_ids_.size();
+        std::vector<float> frac(n), nrm(3 * n);
+        std::vector<uint32_t> target(n), count(n);
+        if (n) check(phys_get_ccd_hits(w_, frac.data(), target.data(), nrm.data(), count.data()));
+        std::vector<CcdHit> out(n);
+        for (size_t i = 0; i < n; ++i) out[i] = CcdHit{frac[i], target[i], Vector3(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]), count[i]};
+        return out;
+    }
     // every entity each query shape intersects as they are now (phys_overlap): per query the ascending ids; rot_ijkw
     // (4 floats per query) may be empty (identity); retries once when the ids outgrow the first guess
     std::vector<std::vector<uint32_t>> overlap(const std::vector<uint32_t>& shape_type, const std::vector<Vector3>& pos,
@@ -300,6 +320,7 @@ class PhysicsState {  // physics.rs:25-31
     bool uploaded_ = false;
     bool materials_uploaded_ = false;  // phys_set_body_materials was called since the last phys_set_bodies
     float default_friction_ = 0.0f;
+    std::vector<uint32_t> ccd_ids_;  // the list of set_ccd_bodies
 
     static void check(int32_t rc) {
         if (rc != PHYS_OK) throw Panic(rc, phys_last_error());
@@ -348,6 +369,10 @@ class PhysicsState {  // physics.rs:25-31
             con_snapshot_.clear();
             uploaded_ = true;
             materials_uploaded_ = false;  // phys_set_bodies reset them
+            // ... and cleared the continuous-collision list: sent again while every id still names an entity
+            for (uint32_t id : ccd_ids_)
+                if (id >= n) { ccd_ids_.clear(); break; }
+            if (!ccd_ids_.empty()) check(phys_set_ccd_bodies(w_, ccd_ids_.size(), ccd_ids_.data()));
         }
         // materials: never sent while every body has the defaults (the world then runs its plain solver kernels)
         // (sent when some body is off the defaults, or to take an earlier upload back; then whenever something changed)

@@ -228,6 +228,9 @@ PROTOTYPES = {
     "phys_apply_liquids": (C.c_int32, [C.c_void_p]),
     "phys_get_submersion": (C.c_int32, [C.c_void_p, f32p, u32p]),
     "phys_get_submersion_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "phys_set_ccd_bodies": (C.c_int32, [C.c_void_p, C.c_uint64, u32p]),
+    "phys_get_ccd_hits": (C.c_int32, [C.c_void_p, f32p, u32p, f32p, u32p]),
+    "phys_get_ccd_hits_device": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "phys_set_body_poses": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p]),
     "phys_set_body_velocities": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p]),
     "phys_apply_impulses": (C.c_int32, [C.c_void_p, C.c_uint64, u32p, f32p, f32p, f32p]),

@@ -373,6 +373,7 @@ int32_t phys_set_bodies(phys_world* w, uint64_t n, const float* pos, const float
     for (int k = 0; k < phys_world::kSnapRing; ++k) w->snap_pending[k] = false;  // the stream was synchronised above
     PHYS_TRY(events_reset(w));    // contact events: history and pending events are gone
     PHYS_TRY(triggers_reset(w));  // trigger volumes: occupancy and pending events too
+    PHYS_TRY(ccd_set(w, {}));     // continuous collision: the listed ids are stale
     if (n == 0) return PHYS_OK;
 
     // host staging with RigidBody::new defaults (setup.hpp); ghost slots: no shape, immovable
@@ -520,7 +521,10 @@ static int32_t enqueue_update(phys_world* w, float dt) {
         } else {
             snapshot_counters_async(w, /*full=*/false);  // launch-size hints of later updates (the colouring stage takes it otherwise)
         }
-        launch_step_position(w, dt);
+        // continuous collision: nothing in a world without a list; behind the solver and the events, so the velocities are final
+        const bool ccd = w->n_ccd != 0 && !(w->cfg.flags & PHYS_FLAG_BROADPHASE_ONLY);
+        if (ccd) launch_ccd_sweep(w, dt);
+        launch_step_position(w, dt, ccd);
     }
     if (w->n_triggers) launch_triggers(w, (uint32_t)(w->steps + 1));  // trigger volumes, against the poses just written
     PHYS_HIP_TRY(hipGetLastError());
@@ -1230,6 +1234,30 @@ int32_t phys_get_submersion(phys_world* w, float* frac_out, uint32_t* liquid_out
     if (liquid_out) PHYS_HIP_TRY(hipMemcpyAsync(liquid_out, d_liquid, 4 * w->n_owned, hipMemcpyDeviceToHost, w->stream));
     PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
     return PHYS_OK;
+}
+
+// ---- continuous collision: the list is checked on the host (setup.hpp stage_ccd), swept by ccd.hip ----
+int32_t phys_set_ccd_bodies(phys_world* w, uint64_t n, const uint32_t* ids) {
+    ENTER(w);
+    if (!(w->cfg.flags & PHYS_FLAG_COLLISIONS)) return fail(PHYS_ERR_UNSUPPORTED, "phys_set_ccd_bodies: world created without PHYS_FLAG_COLLISIONS");
+    // a ghost's step belongs to its owner's rank: a sharded world refuses the call, like the force fields
+    if (w->cfg.max_ghosts > 0) return fail(PHYS_ERR_UNSUPPORTED, "continuous collision is not supported in a world with max_ghosts > 0");
+    CcdStaging staged = stage_ccd(n, ids, w->n_owned);
+    if (staged.code != PHYS_OK) return fail(staged.code, staged.message.c_str());  // the old list stays in force
+    return ccd_set(w, std::move(staged.ids));
+}
+
+static int32_t ccd_hits(phys_world* w, float* frac_out, uint32_t* target_out, float* normal_out, uint32_t* count_out, bool to_host) {
+    ENTER(w);
+    PHYS_TRY(ccd_read(w, frac_out, target_out, normal_out, count_out, to_host));
+    if (to_host) PHYS_HIP_TRY(hipStreamSynchronize(w->stream));
+    return PHYS_OK;
+}
+int32_t phys_get_ccd_hits(phys_world* w, float* frac_out, uint32_t* target_out, float* normal_out, uint32_t* count_out) {
+    return ccd_hits(w, frac_out, target_out, normal_out, count_out, /*to_host=*/true);
+}
+int32_t phys_get_ccd_hits_device(phys_world* w, float* dev_frac_out, uint32_t* dev_target_out, float* dev_normal_out, uint32_t* dev_count_out) {
+    return ccd_hits(w, dev_frac_out, dev_target_out, dev_normal_out, dev_count_out, /*to_host=*/false);
 }
 
 // ---- in-place body edits: checked and ordered on the host (setup.hpp), applied by edit.hip ----

@@ -189,12 +189,20 @@ __global__ __launch_bounds__(256) void k_aabb_only(uint32_t n, const float* __re
     if ((threadIdx.x & 63) == 0 && bits > ctr->max_extent_bits) atomicMax(&ctr->max_extent_bits, bits);
 }
 
+// the one share-of-dt argument of k_step_position's CCD instances (a parameter pack that is empty in the plain ones: see filter_arg)
+template <typename T>
+__device__ __forceinline__ T frac_arg(T f) { return f; }
+
 // collision mode, second half: position + rotation update
-template <bool EXACT_ROT>
+// CCD: every body is advanced by dt * frac[i], frac the array this update's sweep wrote (1 for a body that
+// was not stopped: dt * 1.0f == dt, the plain instance's bits). The plain instances keep their arguments.
+template <bool EXACT_ROT, bool CCD = false, typename... Frac>
 __global__ __launch_bounds__(256) void k_step_position(uint32_t n, float dt, float* __restrict__ pos,
-                                                       float* __restrict__ rot, const float* __restrict__ vel) {
+                                                       float* __restrict__ rot, const float* __restrict__ vel, Frac... frac) {
+    static_assert(sizeof...(Frac) == (CCD ? 1 : 0), "the CCD instance takes the frac array, the plain one nothing");
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if constexpr (CCD) dt = dt * frac_arg(frac...)[i];
     v3 x = ld3(pos, i);
     const BodyVel bv = ld_vel(vel, i);
     const v3 v = bv.v, w = bv.w;
@@ -328,11 +336,17 @@ void launch_aabb_only(phys_world* w) {
     w->aabbs_valid = true;
 }
 
-void launch_step_position(phys_world* w, float dt) {
+void launch_step_position(phys_world* w, float dt, bool ccd) {
     if (w->n == 0) return;
     const dim3 g = grid_for(w->n), b(256);
     PHYS_PROF(w, PHYS_STAGE_POSITION);
-    if (w->cfg.flags & PHYS_FLAG_EXACT_ROTATION)
+    if (ccd) {  // (a world with a list has no ghost slots: n == n_owned, the length of ccd_frac)
+        const float* frac = w->ccd_frac.p;
+        dispatch_bool((w->cfg.flags & PHYS_FLAG_EXACT_ROTATION) != 0, [&](auto exact) {
+            hipLaunchKernelGGL((k_step_position<decltype(exact)::value, true, const float*>), g, b, 0, w->stream, (uint32_t)w->n_owned, dt, w->pos.p,
+                               w->rot.p, w->vel.p, frac);
+        });
+    } else if (w->cfg.flags & PHYS_FLAG_EXACT_ROTATION)
         hipLaunchKernelGGL((k_step_position<true>), g, b, 0, w->stream, (uint32_t)w->n, dt, w->pos.p, w->rot.p, w->vel.p);
     else
         hipLaunchKernelGGL((k_step_position<false>), g, b, 0, w->stream, (uint32_t)w->n, dt, w->pos.p, w->rot.p, w->vel.p);

@@ -267,7 +267,7 @@ int32_t drain_events(phys_world* w, void* cursor_dev, uint64_t capacity, const v
 void launch_step_full(phys_world* w, float dt, bool gravity, bool constraints = false);  // constraints: entity 0 += J^T lambda of this update
 void launch_step_velocity_aabb(phys_world* w, float dt, bool gravity, bool zero_step, bool constraints = false);  // zero_step: also zero the per-step state
 void launch_aabb_only(phys_world* w);
-void launch_step_position(phys_world* w, float dt);
+void launch_step_position(phys_world* w, float dt, bool ccd = false);  // ccd: this update's sweep ran (ccd.hip): dt * ccd_frac per body
 void launch_apply_gravity(phys_world* w);
 void launch_apply_force_one(phys_world* w, uint32_t body, int mode, const float f[3], const float arg[3]);
 void launch_instance_matrices(phys_world* w, float* d_out);
@@ -331,6 +331,15 @@ void launch_submersion(phys_world* w, float* d_frac, uint32_t* d_liquid);
 // the set from its staged form (setup.hpp stage_liquids; arguments checked by the caller; empty: clears and frees)
 int32_t liquids_set(phys_world* w, LiquidStaging&& staged);
 int32_t liquids_rebuild(phys_world* w);  // w->lq_host was patched (poses, params): build the records again and send them
+
+// continuous collision (ccd.hip): one kernel between the solver and the position half of every collision
+// update, only in a world with a list; it writes the share of dt of every listed body into ccd_frac, which that update's
+// position half then reads (launch_step_position(.., ccd = true))
+void launch_ccd_sweep(phys_world* w, float dt);
+// the list from its staged form (setup.hpp stage_ccd; checked by the caller; empty: clears and frees); frac to 1, counts to 0
+int32_t ccd_set(phys_world* w, std::vector<uint32_t>&& ids);
+// the read-out of the last sweep into arrays of n_ccd entries (each may be null; host or device ones), on the world's stream
+int32_t ccd_read(phys_world* w, float* frac, uint32_t* target, float* normal, uint32_t* count, bool to_host);
 
 // in-place body edits (edit.hip): one batch on device arrays ordered by id (EditKind, EditBatch and the
 // argument checks: setup.hpp), enqueued on the world's stream; a pose edit drops the AABBs and grids kept from the last broad

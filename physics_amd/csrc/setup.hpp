@@ -1,7 +1,7 @@
 // setup.hpp — what the host computes ONCE per body set, static set or constraint list, as pure functions of host arrays and a
 // few scalars: table sizes, capacities, cluster shapes and homes, the static colliders' grid, the staged body arrays, the
 // constraint column tables, the staged force fields and trigger volumes with their records, the checks and the order of a body-edit
-// batch, argument validation. Nothing of HIP in here and no phys_world: a host compiler reads it alone,
+// batch, the list of continuous collision (checked by tests/cpp/ccd_probe.cpp), argument validation. Nothing of HIP in here and no phys_world: a host compiler reads it alone,
 // and tests/cpp/setup_probe.cpp holds every function to hand-worked values or a brute-force restatement
 // (tests/test_setup_cpu.py). The .hip files keep the allocations, the copies and the launches.
 #pragma once
@@ -876,6 +876,33 @@ inline std::vector<T> edit_gather(const std::vector<uint32_t>& order, const T* s
     if (!src) return out;
     out.resize(order.size() * (size_t)cols);
     for (size_t k = 0; k < order.size(); ++k) std::memcpy(&out[k * cols], src + (size_t)order[k] * cols, sizeof(T) * cols);
+    return out;
+}
+
+// ---- continuous collision: the list of phys_set_ccd_bodies ---------------------------------------------
+// Entry k of the list is ids[k]: the given order is kept, the read-out of phys_get_ccd_hits is in it. Checked before anything is
+// written: code is PHYS_OK, or the refusal and its text - null ids with n > 0 or n at or above 2^31 (PHYS_ERR_INVALID_ARG), then an
+// id that is not below n_owned (PHYS_ERR_OUT_OF_RANGE, as a body edit answers), then an id given twice (PHYS_ERR_INVALID_ARG: two
+// lanes would own one body's step). n == 0: an empty list, PHYS_OK.
+struct CcdStaging {
+    int32_t code = PHYS_OK;
+    std::string message;
+    std::vector<uint32_t> ids;
+};
+inline CcdStaging stage_ccd(uint64_t n, const uint32_t* ids, uint64_t n_owned) {
+    CcdStaging out;
+    if (n == 0) return out;
+    const auto refuse = [&](int32_t code, std::string msg) { out.code = code; out.message = std::move(msg); out.ids.clear(); return out; };
+    if (n >= (1ull << 31)) return refuse(PHYS_ERR_INVALID_ARG, "phys_set_ccd_bodies: n must be below 2^31");
+    if (!ids) return refuse(PHYS_ERR_INVALID_ARG, "phys_set_ccd_bodies: null ids");
+    for (uint64_t k = 0; k < n; ++k)
+        if (ids[k] >= n_owned)
+            return refuse(PHYS_ERR_OUT_OF_RANGE, "phys_set_ccd_bodies: entry " + std::to_string(k) + " names body " + std::to_string(ids[k]) + ", out of range");
+    std::vector<uint32_t> sorted(ids, ids + n);
+    std::sort(sorted.begin(), sorted.end());
+    const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
+    if (twice != sorted.end()) return refuse(PHYS_ERR_INVALID_ARG, "phys_set_ccd_bodies: body " + std::to_string(*twice) + " is listed twice");
+    out.ids.assign(ids, ids + n);
     return out;
 }
 

@@ -314,6 +314,12 @@ struct phys_world {
     bool lq_drag = false;                // some liquid has a nonzero drag: the velocity record is read
     std::vector<lq_staged> lq_host;      // the set as staged (setup.hpp stage_liquids): poses and params are patched here, the records built from it
     phys::DevBuf<float> lq_rec;          // 32 floats per liquid: the record the evaluation reads (include/spec/liquid.h lq_record)
+    // continuous collision (ccd.hip): nothing below is allocated, and nothing launched, without a list
+    uint64_t n_ccd = 0;                  // entries of phys_set_ccd_bodies
+    phys::DevBuf<uint32_t> ccd_ids;      // n_ccd: entry -> body, in the caller's order
+    phys::DevBuf<float> ccd_frac;        // n_owned: the share of dt each body is advanced by (1 for every body not stopped); the position half reads it
+    phys::DevBuf<uint32_t> ccd_hit;      // 5 n_ccd words, the read-out of the last sweep: frac | target | normal (3 per entry)
+    phys::DevBuf<uint32_t> ccd_count;    // n_ccd: updates in which the entry was stopped, since the list was set
     // multi-GPU halo
     phys::DevBuf<uint32_t> cross_pairs;
     uint64_t max_cross_pairs = 0;

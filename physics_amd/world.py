@@ -151,6 +151,7 @@ class World:
         self.n_triggers = 0
         self.n_fields, self._field_kinds = 0, np.zeros(0, np.uint32)
         self.n_liquids = 0
+        self.n_ccd = 0
         self._ck(self.lib.phys_create(C.byref(self.cfg), C.byref(self.h)))
 
     def _ck(self, rc):
@@ -187,6 +188,7 @@ class World:
         he = _f(half_extent)
         self._ck(self.lib.phys_set_bodies(self.h, n, *[_p(a) for a in arrs], _p(st, u32p), _p(he)))
         self.n = n
+        self.n_ccd = 0  # the library clears the continuous-collision list: its ids are stale
 
     def set_static_bodies(self, pos, rot=None, shape_type=None, half_extent=None):
         """Replace the static colliders (phys_set_static_bodies): pos (n, 3), rot (n, 4) [i, j, k, w] or None (identity),
@@ -975,6 +977,45 @@ class World:
         liquid = np.full(self.n, _abi.NO_LIQUID, np.uint32)
         self._ck(self.lib.phys_get_submersion(self.h, _p(frac), _p(liquid, u32p)))
         return frac, liquid
+
+    # ---- continuous collision (include/physics_hip.h): listed bodies stop at the statics and the ground they would pass through
+    def set_ccd_bodies(self, ids):
+        """Replace the list of bodies that are swept along each collision update's motion (phys_set_ccd_bodies): ids, body
+        indices in any order, none twice; empty or None clears the list. Entry k of ccd_hits() is ids[k]. Resets every frac to 1
+        and every count to 0. set_bodies clears the list, set_static_bodies keeps it."""
+        a = np.zeros(0, np.uint32) if ids is None else np.asarray(ids)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("ids: needs integers")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise ValueError("ids: needs values in [0, 2^32)")
+        a = np.ascontiguousarray(a.reshape(-1), dtype=np.uint32)
+        self._ck(self.lib.phys_set_ccd_bodies(self.h, a.size, _p(a, u32p)))
+        self.n_ccd = int(a.size)
+
+    def ccd_hits(self):
+        """(frac (n_ccd,) float32, target (n_ccd,) uint32, normal (n_ccd, 3) float32, count (n_ccd,) uint32) per list entry
+        (phys_get_ccd_hits): of the last update that swept, the share of dt the body was advanced by, what stopped it (RAY_MISS,
+        RAY_GROUND, STATIC_ID_BIT | k), the normal from that target to the body, and the updates in which the entry was stopped
+        since the list was set. Synchronises."""
+        n = self.n_ccd
+        frac, target = np.ones(n, np.float32), np.full(n, _abi.RAY_MISS, np.uint32)
+        normal, count = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+        if n:
+            self._ck(self.lib.phys_get_ccd_hits(self.h, _p(frac), _p(target, u32p), _p(normal), _p(count, u32p)))
+        return frac, target, normal, count
+
+    def ccd_hits_device(self, frac_out=None, target_out=None, normal_out=None, count_out=None):
+        """phys_get_ccd_hits_device into contiguous tensors of the world's device: frac_out float32 (n_ccd,), target_out int32 /
+        uint32 (n_ccd,), normal_out float32 (n_ccd, 3), count_out int32 / uint32 (n_ccd,); any may be None. Enqueued on the
+        world's stream: sync() before reading."""
+        ptrs = []
+        for name, x, floating, cols in (("frac_out", frac_out, True, 1), ("target_out", target_out, False, 1),
+                                        ("normal_out", normal_out, True, 3), ("count_out", count_out, False, 1)):
+            if x is not None and (not x.is_contiguous() or x.numel() != cols * self.n_ccd or x.element_size() != 4
+                                  or x.is_floating_point() != floating or not x.is_cuda):
+                raise ValueError(f"{name}: needs a contiguous 4-byte device tensor of {cols * self.n_ccd} elements")
+            ptrs.append(None if x is None or self.n_ccd == 0 else C.c_void_p(x.data_ptr()))
+        self._ck(self.lib.phys_get_ccd_hits_device(self.h, *ptrs))
 
     def get_submersion_device(self, frac_out=None, liquid_out=None):
         """phys_get_submersion_device into contiguous tensors of the world's device: frac_out float32 (n,), liquid_out int32 /

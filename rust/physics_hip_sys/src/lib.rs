@@ -308,6 +308,10 @@ extern "C" {
     pub fn phys_apply_liquids(w: *mut phys_world) -> i32;
     pub fn phys_get_submersion(w: *mut phys_world, frac_out: *mut f32, liquid_out: *mut u32) -> i32;
     pub fn phys_get_submersion_device(w: *mut phys_world, dev_frac_out: *mut f32, dev_liquid_out: *mut u32) -> i32;
+    // continuous collision (listed bodies stop at the statics and the ground they would pass through)
+    pub fn phys_set_ccd_bodies(w: *mut phys_world, n: u64, ids: *const u32) -> i32;
+    pub fn phys_get_ccd_hits(w: *mut phys_world, frac_out: *mut f32, target_out: *mut u32, normal_out: *mut f32, count_out: *mut u32) -> i32;
+    pub fn phys_get_ccd_hits_device(w: *mut phys_world, dev_frac_out: *mut f32, dev_target_out: *mut u32, dev_normal_out: *mut f32, dev_count_out: *mut u32) -> i32;
     pub fn phys_set_body_poses(w: *mut phys_world, n: u64, ids: *const u32, pos: *const f32, rot_ijkw: *const f32) -> i32;
     pub fn phys_set_body_velocities(w: *mut phys_world, n: u64, ids: *const u32, lin: *const f32, ang: *const f32) -> i32;
     pub fn phys_apply_impulses(w: *mut phys_world, n: u64, ids: *const u32, impulse: *const f32, point: *const f32, ang_impulse: *const f32) -> i32;
